@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the GNS hot path on MI355X: grids/s for forward+backward on batched case118, K=4.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 without a launcher: this process spawns the N ranks itself (``python -m torch.distributed.run``, one rank per GPU,
 rendezvous on 127.0.0.1) BEFORE anything touches a GPU, waits for them and exits with their code; under
@@ -34,6 +34,8 @@ CONFIGS = {
 SHAPES = {14: (14, 20, 5), 30: (30, 41, 6), 118: (118, 186, 54), 300: (300, 411, 69)}      # GNS/utils.py:45-56
 D, H, GAMMA, MULTI = 20, 10, 0.9, True
 CASE, BATCH_PER_GPU, K = 118, 16384, 4          # set from --config in main()
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: per-grid outputs beyond this are cut to a fixed, seeded sample of grids
+DUMP_SAMPLE_SEED = 0
 HBM_PEAK_GBS = 8000.0           # MI355X spec (MI355X_MICROARCH.md)
 FP32_PEAK_TFLOPS = 157.3
 DATA_SEED = 1234
@@ -102,6 +104,27 @@ def cpu_baseline(seconds=14.0, case=118, k=4):
                       f'{cores} single-threaded processes x ~{seconds:.0f} s, torch {__import__("torch").__version__} CPU'}
 
 
+def dump_outputs(out_dir, outs):
+    """Write what the last timed step computed as float32 .npy files: the per-grid outputs of the forward (v, theta,
+    total_loss, last_loss: rank 0's grids) and the flat gradient and the parameters after the Adam step (state_dict order).
+    Past DUMP_LIMIT_BYTES the per-grid outputs keep a fixed, seeded sample of grids, whose indices go to grid_index.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in outs.items()}
+    per_grid = ('v', 'theta', 'total_loss', 'last_loss')
+    n = arrays['v'].shape[0]
+    fixed = sum(a.nbytes for k, a in arrays.items() if k not in per_grid)
+    row = sum(arrays[k].nbytes for k in per_grid) // max(n, 1) + 8
+    keep = max(0, (DUMP_LIMIT_BYTES - 4096 - fixed) // row)         # 4096: room for the .npy headers
+    if keep < n:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+        for k in per_grid:
+            arrays[k] = np.ascontiguousarray(arrays[k][idx])
+        arrays['grid_index'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 def _free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(('127.0.0.1', 0))
@@ -130,6 +153,8 @@ def main():
     ap.add_argument('--sustained-steps', type=int, default=2000,
                     help='extra untimed-by-the-contract run reported as "sustained" (0 = skip): the K-step burst ends before the chip settles at its power limit')
     ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy, float32, at most 64 MB')
     ap.add_argument('--rehearse-cpu', action='store_true',
                     help='launcher / rendezvous / collective / JSON plumbing only, over gloo, without touching a GPU (CPU test)')
     a = ap.parse_args()
@@ -141,6 +166,8 @@ def main():
     NB, NE, NG = SHAPES[CASE]
     if a.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
     launched = 'WORLD_SIZE' in os.environ and 'RANK' in os.environ
     if not launched and a.gpus > 1:
         sys.exit(self_launch(sys.argv[1:], a.gpus))
@@ -205,9 +232,9 @@ def main():
         opt.zero_grad(set_to_none=True)
         v, th, tot, last = model(buses, lines, gens, Bc, Lc, Gc)
         tot.mean().backward()
-        amd.dist.allreduce_gradients(model, global_batch=bt * world, local_batch=bt)
+        grad = amd.dist.allreduce_gradients(model, global_batch=bt * world, local_batch=bt)
         opt.step()
-        return tot
+        return v, th, tot, last, grad
 
     def fence():
         torch.cuda.synchronize(dev)
@@ -219,18 +246,27 @@ def main():
         fence()
         t0 = time.perf_counter()
         for _ in range(nsteps):
-            tot_ = step()
+            outs_ = step()
         fence()
         dt_ = time.perf_counter() - t0
         tmax = torch.tensor([dt_], dtype=torch.float64, device=dev)
         if world > 1:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        return float(tmax.item()), tot_.detach().mean()           # (detached: no autograd graph outlives the step)
+        # the last step's (v, theta, total, last, flat gradient), detached: no autograd graph may outlive the timed steps (an
+        # AccumulateGrad node kept alive ties the eager stream into the capture of training.GraphedStep below)
+        return float(tmax.item()), tuple(x.detach() for x in outs_)
 
     for _ in range(a.warmup):
         step()
     lib.gns_profile_enable(max(a.steps, 1))
-    dt, tot = timed(a.steps)
+    dt, outs = timed(a.steps)
+    tot = outs[2].mean()
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # copied now: every later step replaces the parameters and the gradient
+        dumped = {k: x.cpu().numpy() for k, x in zip(('v', 'theta', 'total_loss', 'last_loss', 'grad'), outs)}
+        dumped['params'] = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).cpu().numpy()
+    del outs
     ms_f, n_f, ms_b, n_b = ctypes.c_float(), ctypes.c_int(), ctypes.c_float(), ctypes.c_int()
     lib.gns_profile_read(0, ctypes.byref(ms_f), ctypes.byref(n_f))
     lib.gns_profile_read(1, ctypes.byref(ms_b), ctypes.byref(n_b))
@@ -241,11 +277,11 @@ def main():
     model.unbind_dataset()
     for _ in range(2):
         step()
-    dt_pack, _ = timed(a.steps)
+    dt_pack = timed(a.steps)[0]
     model.bind_dataset(buses, lines, gens)
     sustained = None
     if a.sustained_steps > 0:
-        sdt, _ = timed(a.sustained_steps)
+        sdt = timed(a.sustained_steps)[0]
         sustained = {'steps': a.sustained_steps, 'value': round(bt * world * a.sustained_steps / sdt, 1), 'unit': 'grids/s',
                      'ms_per_step': round(sdt / a.sustained_steps * 1e3, 4)}
     # The same step as ONE captured HIP graph (training.GraphedStep on the resident, bound batch; one process only): what a loop gains
@@ -331,6 +367,8 @@ def main():
         }
         if cpu is not None:
             line['cpu_baseline'] = cpu
+        if dumped is not None:
+            dump_outputs(a.dump_outputs, dumped)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

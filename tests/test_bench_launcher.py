@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -48,3 +50,23 @@ def test_bench_byte_and_flop_models_match_the_survey():
 def test_bench_rejects_a_world_size_that_does_not_match():
     r = _run(['--gpus', '4', '--rehearse-cpu'], env={'WORLD_SIZE': '2', 'RANK': '0', 'LOCAL_RANK': '0'})
     assert r.returncode != 0 and 'does not match' in (r.stderr + r.stdout)
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: the last timed step's per-grid outputs, flat gradient and updated parameters as float32 .npy files."""
+    import numpy as np
+    out_dir = tmp_path / 'outs'
+    r = _run(['--gpus', '1', '--steps', '3', '--warmup', '1', '--batch-per-gpu', '256', '--sustained-steps', '0',
+              '--no-cpu-baseline', '--dump-outputs', str(out_dir)], timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
+    assert out['steps'] == 3 and out['ms_per_step'] > 0
+    arrays = {p.stem: np.load(p) for p in out_dir.glob('*.npy')}
+    assert sorted(arrays) == ['grad', 'last_loss', 'params', 'theta', 'total_loss', 'v']
+    assert all(a.dtype == np.float32 and np.all(np.isfinite(a)) for a in arrays.values())
+    assert arrays['v'].shape == arrays['theta'].shape == (256, 118)
+    assert arrays['total_loss'].shape == arrays['last_loss'].shape == (256,)
+    assert arrays['grad'].shape == arrays['params'].shape and arrays['grad'].ndim == 1
+    assert abs(float(arrays['total_loss'].mean()) - out['final_mean_total_loss']) <= 1e-5 * abs(out['final_mean_total_loss'])
+    assert sum(p.stat().st_size for p in out_dir.glob('*.npy')) <= 64 << 20

@@ -16,7 +16,7 @@
  *                          (GNS/utils.py:4-13), fp32, contiguous - what utils.load_all_grids returns.
  *   v, theta [Bt,N]; total_loss, last_loss [Bt].
  *   Topology (f_bus, t_bus, generator buses) is shared by the whole batch (reference data:
- *   GNS/augment_grids.py:35-53 perturbs continuous columns only).
+ *   GNS/augment_grids.py:35-53 perturbs continuous columns only); the *_grouped calls below take batches that mix topologies.
  */
 #ifndef GNS_HIP_H
 #define GNS_HIP_H
@@ -119,6 +119,35 @@ int gns_team_status(const gns_config* cfg, int64_t Bt, const void* fwd_workspace
 /* Byte offset of the status word inside the forward workspace; (size_t)-1 when this (cfg, Bt, save_state) runs without teams, i.e.
  * when there is nothing to check.  Host code only, no device access. */
 int gns_team_status_offset(const gns_config* cfg, int64_t Bt, int save_state, size_t* offset);
+
+/* ---- grouped calls: a batch that mixes topologies (N-1 contingency sets, GNS/main.py:279-283 runs every grid on its own bus ids) ----
+ * The Bt input grids (same N, E, Gn; any f_bus / t_bus / generator bus columns) are computed in G groups of 64 lanes, ONE topology per
+ * group:
+ *   topo_set_dev   : topology blobs of gns_prepare_topology, concatenated; every blob starts at a 64-byte aligned offset (a multiple of
+ *                    16 words: the blob's line records are 64-byte aligned relative to its start)
+ *   group_topo_dev : int32[G], word offset of group g's blob inside the set
+ *   slot_grid_dev  : int32[G*64], the input grid (0..Bt-1) that lane l of group g computes, or -1 for a dead slot.  Lane 0 of every
+ *                    group is live; a dead slot computes a copy of that grid and contributes nothing (its upstream gradients are zero).
+ * Every grid appears in exactly one slot; v / theta [Bt,N] and the losses [Bt] are written in INPUT order, and the upstream gradients
+ * of gns_backward_grouped are read in input order.  A group whose blob does not hold (N, E, Gn) gets NaN losses and is never indexed.
+ * A grouped call always runs the lane-per-grid forward and the split backward (bwd_variant 4), whatever "fwd_mapping", "train_mapping"
+ * and "gw_pack" say; GNS_EUNSUPPORTED when those kernels cannot run this config on the current device.  Its workspaces are exactly
+ * those of the lane-per-grid pair for 64 G grids.  Teams ("team" option) are used as for a one-topology batch of 64 G grids; their
+ * status is read with gns_team_status_grouped (gns_team_status answers for the mapping gns_forward would choose for that batch size,
+ * which can be the grid-per-workgroup pair).  The packed-input cache (gns_prepack) does not apply. */
+int gns_workspace_bytes_grouped(const gns_config* cfg, int64_t G, int save_state, size_t* fwd_bytes, size_t* bwd_bytes);
+int gns_forward_grouped(const gns_config* cfg, const void* topo_set_dev, const int32_t* group_topo_dev, const int32_t* slot_grid_dev,
+                        int64_t G, const float* params, const float* buses, const float* lines, const float* generators, int64_t Bt,
+                        float* v, float* theta, float* total_loss, float* last_loss, void* workspace, size_t workspace_bytes,
+                        int save_state, void* stream);
+int gns_backward_grouped(const gns_config* cfg, const void* topo_set_dev, const int32_t* group_topo_dev, const int32_t* slot_grid_dev,
+                         int64_t G, const float* params, const float* buses, const float* lines, const float* generators, int64_t Bt,
+                         const void* fwd_workspace, size_t fwd_workspace_bytes,
+                         const float* grad_total, const float* grad_last, const float* grad_v, const float* grad_theta,
+                         float* grad_params, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream);
+int gns_team_status_grouped(const gns_config* cfg, int64_t G, const void* fwd_workspace, size_t fwd_workspace_bytes, int save_state,
+                            int* status, void* stream);
+int gns_team_status_offset_grouped(const gns_config* cfg, int64_t G, int save_state, size_t* offset);
 
 /* The optimiser update of the reference's training loop (optimizer.step() at GNS/main.py:290 with torch.optim.Adam,
  * main.py:241-243: no weight decay, no amsgrad) on the ONE flat parameter buffer, in one launch:

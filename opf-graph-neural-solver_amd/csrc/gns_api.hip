@@ -383,6 +383,90 @@ extern "C" int gns_prepack(const gns_config* cfg, const void* topo_dev, const fl
                                 (Bt + GNS_LANES - 1) / GNS_LANES, (hipStream_t)stream);
 }
 
+// The lane-per-grid forward of Bt input grids in L.groups 64-grid groups (parameters and inputs already packed into `ws`).  group_topo /
+// slot_grid: NULL for a one-topology batch (lane l of group g computes grid 64 g + l), else the tables of a grouped call.
+static int lane_forward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLayout& L, char* ws, float* pt, float* pin,
+                        const int* topo_dev, const int* group_topo, const int* slot_grid, int64_t Bt, float* v, float* theta,
+                        float* total_loss, float* last_loss, int save_state, hipStream_t st) {
+  const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
+  const GnsTuning& T = tuning();
+  int rc;
+  GnsFwdArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.topo = topo_dev; A.group_topo = group_topo; A.slot_grid = slot_grid; A.pt = pt; A.in = pin;
+  A.state = (float*)(ws + L.off_state); A.lam = (float*)(ws + L.off_lam); A.msg = (float*)(ws + L.off_msg);
+  A.v_out = v; A.theta_out = theta; A.total_out = total_loss; A.last_out = last_loss;
+  for (int i = 0; i < fam.nfam; ++i) { A.t_off[i] = fam.t_off[i]; A.t_sz[i] = fam.t_sz[i]; }
+  for (int k = 0; k < K; ++k) A.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));   // main.py:198
+  A.Bt = Bt; A.G = L.groups; A.N = N; A.E = E; A.K = K; A.save = save_state ? 1 : 0;
+  const int team0 = lane_team(L.groups * GNS_LANES);     // (= lane_team(Bt) for a one-topology batch)
+  A.team = team0;
+  A.team_ws = (unsigned char*)(ws + L.off_team);
+  int waves = T.fwd_waves;
+  while (waves * A.team > GNS_MAXP) waves /= 2;
+  A.part_idx = gns_part_index(waves * A.team);
+  auto pick_planes = [&]() {
+    A.plane = (device().fwd_ready && gns_fwd_plane_fits(N, A.team) && T.fwd_plane) ? 1 : 0;
+    if (A.plane && gns_fwd_plane2_fits(N, A.team) && T.fwd_plane == 2) A.plane = 2;
+  };
+  pick_planes();
+  if (A.team > 1) {
+    // every workgroup of every team must be resident at once: the kernel's own occupancy at this launch configuration says
+    // how many a CU holds (not just the CU count); a configuration that does not fit runs one workgroup per group instead
+    const int per_cu = gns_fwd_blocks_per_cu(d, h, cfg->multiple_phi, A, waves * 64);
+    if ((long long)per_cu * device().ncu < A.G * A.team) {
+      A.team = 1;
+      waves = T.fwd_waves;
+      A.part_idx = gns_part_index(waves);
+      pick_planes();
+    }
+  }
+  // (the counters - and the status word gns_team_status reads - are zeroed whenever this batch size is one that may use teams)
+  if (team0 > 1 && hipMemsetAsync(A.team_ws, 0, (size_t)L.groups * GNS_TEAM_CTR_BYTES, st) != hipSuccess) return GNS_ELAUNCH;
+  prof_mark(0, true, st);
+  rc = gns_launch_forward(d, h, cfg->multiple_phi, A, waves * 64, st);
+  prof_mark(0, false, st);
+  return rc;
+}
+
+// The split backward (bwd_variant 4) of a lane-per-grid forward: one phys + sweep kernel sequence per reverse step, then the reduction.
+static int split_backward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLayout& L, const GnsBwdsLayout& S, const char* fw,
+                          char* bw, const int* topo_dev, const int* group_topo, const int* slot_grid, const float* params,
+                          const void* packed_inputs, int64_t Bt, const float* grad_total, const float* grad_last, const float* grad_v,
+                          const float* grad_theta, float* grad_params, hipStream_t st) {
+  const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
+  int rc;
+  GnsBwdsArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.topo = topo_dev; A.group_topo = group_topo; A.slot_grid = slot_grid;
+  A.pt = (const float*)(fw + L.off_pt); A.pn = (const float*)(fw + L.off_pn);
+  A.in = packed_inputs ? (const float*)packed_inputs : (const float*)(fw + L.off_in);
+  A.state = (const float*)(fw + L.off_state); A.lam = (const float*)(fw + L.off_lam); A.msg = (const float*)(fw + L.off_msg);
+  A.g_total = grad_total; A.g_last = grad_last; A.g_v = grad_v; A.g_theta = grad_theta;
+  A.adj = (float*)(bw + S.off_adj); A.slots = (float*)(bw + S.off_slots); A.slab = (float*)(bw + S.off_slab);
+  for (int i = 0; i < fam.nfam; ++i) {
+    A.t_off[i] = fam.t_off[i]; A.t_sz[i] = fam.t_sz[i]; A.n_off[i] = fam.n_off[i]; A.n_sz[i] = fam.n_sz[i];
+    A.g_off[i] = fam.g_off[i]; A.g_sz[i] = fam.g_sz[i];
+  }
+  A.Bt = Bt; A.G = S.groups; A.slab_floats = S.slab_floats; A.N = N; A.E = E; A.K = K;
+  A.C = S.C; A.part_idx = gns_part_index(S.C); A.R = S.R;
+  A.RB = (int)(1 + S.mq); A.RBA = (int)S.adj_rows;
+  A.mode = cfg->multiple_phi ? tuning().bwds_mode : 2;          // the single phi is reversed after all three L nets: bus-major
+  const size_t lds = gns_bwds_phys_lds(N, &A.use_plane);
+  prof_mark(1, true, st);
+  for (int k = K - 1; k >= 0; --k) {
+    A.k = k;
+    A.gwk = (float)std::pow((double)cfg->gamma, (double)(K - k));
+    rc = gns_launch_bwds_phys(A, lds, st);
+    if (rc != GNS_OK) return rc;
+    rc = gns_launch_bwds_sweep(d, h, cfg->multiple_phi, A, st);
+    if (rc != GNS_OK) return rc;
+  }
+  prof_mark(1, false, st);
+  return gns_launch_reduce(A.slab, (float*)(bw + S.off_part), (float*)(bw + S.off_tmp), params, grad_params, S.nslab, S.slab_floats,
+                           fam, K, d, h, st);
+}
+
 extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const float* params, const float* buses,
                            const float* lines, const float* generators, int64_t Bt, const void* packed_inputs, float* v, float* theta,
                            float* total_loss, float* last_loss, void* workspace, size_t workspace_bytes, int save_state,
@@ -398,7 +482,6 @@ extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const fl
   GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  const GnsTuning& T = tuning();
   if (const int TP = save_state ? gw_train_pack(cfg, Bt) : 0) {          // training-mode forward of the grid-per-workgroup pair
     const GwTrainLayout GL = gw_train_layout(cfg, Bt, TP);
     if (workspace_bytes < GL.fwd_total) return GNS_ESIZE;
@@ -450,42 +533,7 @@ extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const fl
     rc = gns_launch_pack_inputs((const int*)topo_dev, buses, lines, generators, pin, N, E, Gn, Bt, L.groups, st);
     if (rc != GNS_OK) return rc;
   }
-  GnsFwdArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.topo = (const int*)topo_dev; A.pt = pt; A.in = pin;
-  A.state = (float*)(ws + L.off_state); A.lam = (float*)(ws + L.off_lam); A.msg = (float*)(ws + L.off_msg);
-  A.v_out = v; A.theta_out = theta; A.total_out = total_loss; A.last_out = last_loss;
-  for (int i = 0; i < fam.nfam; ++i) { A.t_off[i] = fam.t_off[i]; A.t_sz[i] = fam.t_sz[i]; }
-  for (int k = 0; k < K; ++k) A.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));   // main.py:198
-  A.Bt = Bt; A.G = L.groups; A.N = N; A.E = E; A.K = K; A.save = save_state ? 1 : 0;
-  const int team0 = lane_team(Bt);
-  A.team = team0;
-  A.team_ws = (unsigned char*)(ws + L.off_team);
-  int waves = T.fwd_waves;
-  while (waves * A.team > GNS_MAXP) waves /= 2;
-  A.part_idx = gns_part_index(waves * A.team);
-  auto pick_planes = [&]() {
-    A.plane = (device().fwd_ready && gns_fwd_plane_fits(N, A.team) && T.fwd_plane) ? 1 : 0;
-    if (A.plane && gns_fwd_plane2_fits(N, A.team) && T.fwd_plane == 2) A.plane = 2;
-  };
-  pick_planes();
-  if (A.team > 1) {
-    // every workgroup of every team must be resident at once: the kernel's own occupancy at this launch configuration says
-    // how many a CU holds (not just the CU count); a configuration that does not fit runs one workgroup per group instead
-    const int per_cu = gns_fwd_blocks_per_cu(d, h, cfg->multiple_phi, A, waves * 64);
-    if ((long long)per_cu * device().ncu < A.G * A.team) {
-      A.team = 1;
-      waves = T.fwd_waves;
-      A.part_idx = gns_part_index(waves);
-      pick_planes();
-    }
-  }
-  // (the counters - and the status word gns_team_status reads - are zeroed whenever this batch size is one that may use teams)
-  if (team0 > 1 && hipMemsetAsync(A.team_ws, 0, (size_t)L.groups * GNS_TEAM_CTR_BYTES, st) != hipSuccess) return GNS_ELAUNCH;
-  prof_mark(0, true, st);
-  rc = gns_launch_forward(d, h, cfg->multiple_phi, A, waves * 64, st);
-  prof_mark(0, false, st);
-  return rc;
+  return lane_forward(cfg, fam, L, ws, pt, pin, (const int*)topo_dev, nullptr, nullptr, Bt, v, theta, total_loss, last_loss, save_state, st);
 }
 
 extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const float* params,
@@ -539,38 +587,8 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
     gns_bwds_layout(N, E, d, h, K, cfg->multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
     if (fwd_workspace_bytes < L.total || bwd_workspace_bytes < S.total) return GNS_ESIZE;
     GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
-    hipStream_t st = (hipStream_t)stream;
-    const char* fw = (const char*)fwd_workspace;
-    char* bw = (char*)bwd_workspace;
-    GnsBwdsArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.topo = (const int*)topo_dev;
-    A.pt = (const float*)(fw + L.off_pt); A.pn = (const float*)(fw + L.off_pn);
-    A.in = packed_inputs ? (const float*)packed_inputs : (const float*)(fw + L.off_in);
-    A.state = (const float*)(fw + L.off_state); A.lam = (const float*)(fw + L.off_lam); A.msg = (const float*)(fw + L.off_msg);
-    A.g_total = grad_total; A.g_last = grad_last; A.g_v = grad_v; A.g_theta = grad_theta;
-    A.adj = (float*)(bw + S.off_adj); A.slots = (float*)(bw + S.off_slots); A.slab = (float*)(bw + S.off_slab);
-    for (int i = 0; i < fam.nfam; ++i) {
-      A.t_off[i] = fam.t_off[i]; A.t_sz[i] = fam.t_sz[i]; A.n_off[i] = fam.n_off[i]; A.n_sz[i] = fam.n_sz[i];
-      A.g_off[i] = fam.g_off[i]; A.g_sz[i] = fam.g_sz[i];
-    }
-    A.Bt = Bt; A.G = S.groups; A.slab_floats = S.slab_floats; A.N = N; A.E = E; A.K = K;
-    A.C = S.C; A.part_idx = gns_part_index(S.C); A.R = S.R;
-    A.RB = (int)(1 + S.mq); A.RBA = (int)S.adj_rows;
-    A.mode = cfg->multiple_phi ? tuning().bwds_mode : 2;          // the single phi is reversed after all three L nets: bus-major
-    const size_t lds = gns_bwds_phys_lds(N, &A.use_plane);
-    prof_mark(1, true, st);
-    for (int k = K - 1; k >= 0; --k) {
-      A.k = k;
-      A.gwk = (float)std::pow((double)cfg->gamma, (double)(K - k));
-      rc = gns_launch_bwds_phys(A, lds, st);
-      if (rc != GNS_OK) return rc;
-      rc = gns_launch_bwds_sweep(d, h, cfg->multiple_phi, A, st);
-      if (rc != GNS_OK) return rc;
-    }
-    prof_mark(1, false, st);
-    return gns_launch_reduce(A.slab, (float*)(bw + S.off_part), (float*)(bw + S.off_tmp), params, grad_params, S.nslab, S.slab_floats,
-                             fam, K, d, h, st);
+    return split_backward(cfg, fam, L, S, (const char*)fwd_workspace, (char*)bwd_workspace, (const int*)topo_dev, nullptr, nullptr, params,
+                          packed_inputs, Bt, grad_total, grad_last, grad_v, grad_theta, grad_params, (hipStream_t)stream);
   }
   GnsBwdLayout B;
   const int team = lane_team(Bt);
@@ -612,6 +630,117 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
   // the kernel has summed each workgroup's eight slabs into its first one: one slab per workgroup is left to reduce
   return gns_launch_reduce(A.slab, (float*)(bw + B.off_part), (float*)(bw + B.off_tmp), params, grad_params, blocks, B.slab_floats,
                            fam, K, d, h, st, (long long)GNS_BWD_WAVES * B.slab_floats);
+}
+
+// ---- grouped calls: a batch that mixes topologies, one topology per 64-grid group (include/gns_hip.h) ---------------------------
+// Always the lane-per-grid forward and the split backward, whatever "fwd_mapping", "train_mapping" and "gw_pack" say; their workspace
+// layouts for Bt = 64 G.  The model's cfg in, the kernel's out.
+static int grouped_config(const gns_config* model, int64_t G, gns_config* k) {
+  int rc = check_cfg(model);
+  if (rc != GNS_OK) return rc;
+  if (G <= 0 || G > ((int64_t)1 << 24)) return GNS_EINVAL;
+  if (!kernel_config(model, k) || model->K > GNS_MAX_K) return GNS_EUNSUPPORTED;
+  if (!device().split_ready || !gns_bwds_supported(k->latent_dim, k->hidden_dim, k->multiple_phi)) return GNS_EUNSUPPORTED;
+  return GNS_OK;
+}
+
+extern "C" int gns_workspace_bytes_grouped(const gns_config* cfg, int64_t G, int save_state, size_t* fwd_bytes, size_t* bwd_bytes) {
+  gns_config k;
+  const int rc = grouped_config(cfg, G, &k);
+  if (rc != GNS_OK) return rc;
+  const int64_t Bt = G * GNS_LANES;
+  GnsFwdLayout L;
+  gns_fwd_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, Bt, save_state, &L);
+  if (fwd_bytes) *fwd_bytes = L.total;
+  if (bwd_bytes) {
+    GnsBwdsLayout S;
+    gns_bwds_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
+    *bwd_bytes = save_state ? S.total : 0;
+  }
+  return GNS_OK;
+}
+
+extern "C" int gns_forward_grouped(const gns_config* cfg, const void* topo_set_dev, const int32_t* group_topo_dev,
+                                   const int32_t* slot_grid_dev, int64_t G, const float* params, const float* buses, const float* lines,
+                                   const float* generators, int64_t Bt, float* v, float* theta, float* total_loss, float* last_loss,
+                                   void* workspace, size_t workspace_bytes, int save_state, void* stream) {
+  gns_config k;
+  int rc = grouped_config(cfg, G, &k);
+  if (rc != GNS_OK) return rc;
+  if (!topo_set_dev || !group_topo_dev || !slot_grid_dev || !params || !buses || !lines || !generators || !v || !theta || !total_loss ||
+      !last_loss || !workspace || Bt <= 0 || Bt > G * GNS_LANES)
+    return GNS_EINVAL;
+  const int N = k.n_bus, E = k.n_line, K = k.K, d = k.latent_dim, h = k.hidden_dim;
+  GnsFamilies fam; gns_families_padded(cfg->latent_dim, cfg->hidden_dim, d, h, K, k.multiple_phi, &fam);
+  GnsFwdLayout L;
+  gns_fwd_layout(N, E, d, h, K, k.multiple_phi, G * GNS_LANES, save_state, &L);
+  if (workspace_bytes < L.total) return GNS_ESIZE;
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float* pt = (float*)(ws + L.off_pt);
+  float* pn = (float*)(ws + L.off_pn);
+  float* pin = (float*)(ws + L.off_in);
+  rc = gns_launch_pack_params(params, pt, pn, fam, K, d, h, st);
+  if (rc != GNS_OK) return rc;
+  rc = gns_launch_pack_inputs((const int*)topo_set_dev, buses, lines, generators, pin, N, E, k.n_gen, Bt, L.groups, st, group_topo_dev,
+                              slot_grid_dev);
+  if (rc != GNS_OK) return rc;
+  return lane_forward(&k, fam, L, ws, pt, pin, (const int*)topo_set_dev, group_topo_dev, slot_grid_dev, Bt, v, theta, total_loss,
+                      last_loss, save_state, st);
+}
+
+extern "C" int gns_backward_grouped(const gns_config* cfg, const void* topo_set_dev, const int32_t* group_topo_dev,
+                                    const int32_t* slot_grid_dev, int64_t G, const float* params, const float* buses, const float* lines,
+                                    const float* generators, int64_t Bt, const void* fwd_workspace, size_t fwd_workspace_bytes,
+                                    const float* grad_total, const float* grad_last, const float* grad_v, const float* grad_theta,
+                                    float* grad_params, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream) {
+  (void)buses; (void)lines; (void)generators;                    // (the lane-per-grid kernels read the inputs packed by the forward)
+  gns_config k;
+  const int rc = grouped_config(cfg, G, &k);
+  if (rc != GNS_OK) return rc;
+  if (!topo_set_dev || !group_topo_dev || !slot_grid_dev || !params || !fwd_workspace || !grad_params || !bwd_workspace || Bt <= 0 ||
+      Bt > G * GNS_LANES)
+    return GNS_EINVAL;
+  const int64_t Bg = G * GNS_LANES;
+  GnsFwdLayout L;
+  gns_fwd_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, Bg, 1, &L);
+  GnsBwdsLayout S;
+  gns_bwds_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, Bg, device().ncu, tuning().bwds_chunks, &S);
+  if (fwd_workspace_bytes < L.total || bwd_workspace_bytes < S.total) return GNS_ESIZE;
+  GnsFamilies fam; gns_families_padded(cfg->latent_dim, cfg->hidden_dim, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, &fam);
+  return split_backward(&k, fam, L, S, (const char*)fwd_workspace, (char*)bwd_workspace, (const int*)topo_set_dev, group_topo_dev,
+                        slot_grid_dev, params, nullptr, Bt, grad_total, grad_last, grad_v, grad_theta, grad_params, (hipStream_t)stream);
+}
+
+// The team status of a grouped forward.  (gns_team_status answers for the call gns_forward would make for that batch size, which below
+// ~2000 grids is the grid-per-workgroup pair, without teams; a grouped call runs the lane-per-grid forward at every size.)
+extern "C" int gns_team_status_offset_grouped(const gns_config* cfg, int64_t G, int save_state, size_t* offset) {
+  gns_config k;
+  const int rc = grouped_config(cfg, G, &k);
+  if (rc != GNS_OK) return rc;
+  if (!offset) return GNS_EINVAL;
+  *offset = (size_t)-1;
+  if (lane_team(G * GNS_LANES) <= 1) return GNS_OK;
+  GnsFwdLayout L;
+  gns_fwd_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, G * GNS_LANES, save_state, &L);
+  *offset = L.off_team + GNS_TEAM_STATUS_WORD * 4;
+  return GNS_OK;
+}
+
+extern "C" int gns_team_status_grouped(const gns_config* cfg, int64_t G, const void* fwd_workspace, size_t fwd_workspace_bytes,
+                                       int save_state, int* status, void* stream) {
+  size_t off = 0;
+  const int rc = gns_team_status_offset_grouped(cfg, G, save_state, &off);
+  if (rc != GNS_OK) return rc;
+  if (!status || !fwd_workspace) return GNS_EINVAL;
+  *status = 0;
+  if (off == (size_t)-1) return GNS_OK;
+  if (fwd_workspace_bytes < off + 4) return GNS_ESIZE;
+  unsigned word = 0;
+  if (hipMemcpyAsync(&word, (const char*)fwd_workspace + off, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+      hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { (void)hipGetLastError(); return GNS_ELAUNCH; }
+  *status = word ? 1 : 0;
+  return GNS_OK;
 }
 
 // ---- Adam on the flat parameter buffer (GNS/main.py:290 with the optimiser of main.py:241-243) ---------------------------

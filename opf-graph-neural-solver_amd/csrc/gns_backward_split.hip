@@ -53,6 +53,15 @@ __global__ void __launch_bounds__(GNS_BWDS_PHYS_THREADS) gns_bwds_phys_kernel(Gn
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int N = A.N, E = A.E, K = A.K, k = A.k;
   cip topo = (cip)A.topo;
+  const long long g = blockIdx.x;
+  long long b = g * GNS_LANES + lane;
+  bool live = b < A.Bt;
+  if (A.group_topo) {                 // grouped call: the group's topology; dead slots get zero upstream gradients (the dW contraction
+    const int s = A.slot_grid[g * GNS_LANES + lane];          // sums all 64 lanes)
+    b = s;
+    live = s >= 0 && s < A.Bt;
+    if (!gns_group_topo(A.topo, A.group_topo, g, N, E, topo)) return;    // (its forward wrote NaN losses)
+  }
   constexpr int pidx = 4;                                              // gns_part_index(16): the partition tables for 16 waves
   static_assert(GNS_BWDS_PHYS_WAVES == 16, "pidx");
   const cip in_ptr = topo + topo[TH_IN_PTR], out_ptr = topo + topo[TH_OUT_PTR], q2p = topo + topo[TH_Q2P], is_gen = topo + topo[TH_IS_GEN],
@@ -67,12 +76,9 @@ __global__ void __launch_bounds__(GNS_BWDS_PHYS_THREADS) gns_bwds_phys_kernel(Gn
   float* const pl_v = lds + W * GNS_LANES;                           // [N][64] planes (when they fit)
   float* const pl_th = pl_v + (use_plane ? N * GNS_LANES : 0);
   float* const pl_dp = pl_th + (plane_dp ? N * GNS_LANES : 0);
-  const long long g = blockIdx.x;
   const long long R = gns_in_rows(N, E);
   const float* IN = A.in;
   const long long in_base = g * R, row_ein = in_base + 3LL * N, row_eout = row_ein + 3LL * E, row_grid = row_eout + E;
-  const long long b = g * GNS_LANES + lane;
-  const bool live = b < A.Bt;
   const float gt = (live && A.g_total) ? A.g_total[b] : 0.f;
   const float gl = (live && A.g_last) ? A.g_last[b] : 0.f;
   const int RB = A.RB, RBA = A.RBA;
@@ -590,7 +596,8 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
 // A kernel writes ONE X row and ONE latent-adjoint part per bus: slot 2 when it runs L_m, else slot 0 (theta, or theta + v), else 1.
 // Readers (Pb-0 for X, the L_m sweep for the latent adjoint) sum the slots of the mode in the order 2, 0, 1; slot 2 of step K-1
 // exists only in mode 2 (no gradient reaches L_m.{K-1}: in modes 0 and 1 no kernel writes it).
-template <int D, int H, bool MULTI, int FAMS, bool STEP0>      // STEP0: the instantiation that reverses step 0 (its dead work compiled out)
+// STEP0: the instantiation that reverses step 0 (its dead work compiled out); GROUPED: a grouped call (A.group_topo), instantiated apart
+template <int D, int H, bool MULTI, int FAMS, bool STEP0, bool GROUPED>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWDS_WPE))) gns_bwds_sweep_kernel(GnsBwdsArgs A) {
   using C = GnsDims<D, H, MULTI>;
   static_assert(MULTI || FAMS == 7, "the single phi is reversed after all three L nets");
@@ -610,8 +617,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
   const int N = A.N, E = A.E, K = A.K, k = A.k;
   cip topo = (cip)A.topo;
   // (a partition of its own for the {L_theta, L_v} kernel, with generator buses at half weight, measured no better: 2.02 vs 2.00 ms)
-  const cip part = topo + topo[TH_PART] + A.part_idx * (GNS_MAXP + 1), in_ptr = topo + topo[TH_IN_PTR], is_gen = topo + topo[TH_IS_GEN];
-  const int n0 = part[c], n1 = part[c + 1];
+  cip part = topo + topo[TH_PART] + A.part_idx * (GNS_MAXP + 1), in_ptr = topo + topo[TH_IN_PTR], is_gen = topo + topo[TH_IS_GEN];
+  int n0 = part[c], n1 = part[c + 1];
   const long long g0 = gb * A.R, g1 = (g0 + A.R < A.G) ? g0 + A.R : A.G;
   float* slab = A.slab + (gb * A.C + c) * A.slab_floats;
   const bool lastk = k == K - 1;           // nothing reads m_K: L_m.{K-1} / phi_m.{K-1} get no gradient (reference: .grad is None)
@@ -640,6 +647,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
   const long long R = gns_in_rows(N, E);
 
   for (long long g = g0; g < g1; ++g) {
+    if constexpr (GROUPED) {          // grouped call: groups g0..g1 may carry different topologies (the slab layout does not depend on it)
+      if (!gns_group_topo(A.topo, A.group_topo, g, N, E, topo)) continue;
+      part = topo + topo[TH_PART] + A.part_idx * (GNS_MAXP + 1); in_ptr = topo + topo[TH_IN_PTR]; is_gen = topo + topo[TH_IS_GEN];
+      n0 = part[c]; n1 = part[c + 1];
+    }
     const long long row_ein = g * R + 3LL * N;
     auto state_row = [&](int slot, int n) { return (((long long)slot * A.G + g) * N + n) * RB; };
     for (int n = n0; n < n1; ++n) {
@@ -737,8 +749,9 @@ int gns_launch_bwds_phys(const GnsBwdsArgs& A, size_t lds, hipStream_t st) {
 int gns_launch_bwds_sweep(int d, int h, int multi, const GnsBwdsArgs& A, hipStream_t st) {
   const long long GB = (A.G + A.R - 1) / A.R;
   const unsigned blocks = (unsigned)(GB * A.C);
-#define GNS_SWEEP(DD, HH, MM, FAMS) do { if (A.k == 0) hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, true>), dim3(blocks), dim3(64), 0, st, A); \
-                                         else hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, false>), dim3(blocks), dim3(64), 0, st, A); } while (0)
+#define GNS_SWEEP1(DD, HH, MM, FAMS, GR) do { if (A.k == 0) hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, true, GR>), dim3(blocks), dim3(64), 0, st, A); \
+                                             else hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, false, GR>), dim3(blocks), dim3(64), 0, st, A); } while (0)
+#define GNS_SWEEP(DD, HH, MM, FAMS) do { if (A.group_topo) GNS_SWEEP1(DD, HH, MM, FAMS, true); else GNS_SWEEP1(DD, HH, MM, FAMS, false); } while (0)
 #define GNS_CASE(DD, HH)                                                                                                    \
   if (d == DD && h == HH) {                                                                                                 \
     if (!multi) { if (A.mode != 2) return GNS_EINVAL; GNS_SWEEP(DD, HH, false, 7); }                                        \
@@ -750,6 +763,7 @@ int gns_launch_bwds_sweep(int d, int h, int multi, const GnsBwdsArgs& A, hipStre
   GNS_FOR_EACH_DIMS(GNS_CASE)
 #undef GNS_CASE
 #undef GNS_SWEEP
+#undef GNS_SWEEP1
   return GNS_EUNSUPPORTED;
 }
 

@@ -10,6 +10,15 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 // address space 4 (constant): loads with a wave-uniform address become s_load (scalar cache -> SGPRs)
 typedef const __attribute__((address_space(4))) float* cfp;
 typedef const __attribute__((address_space(4))) int* cip;
+
+// Grouped calls (gns_forward_grouped / gns_backward_grouped): 64-grid group g reads its own blob of a topology set (blobs concatenated
+// at 64-byte aligned word offsets group_topo[g]) and lane l of it computes input grid slot_grid[64 g + l] (-1: a dead slot).  The
+// offset is a scalar load (g is uniform), so every index the kernels read from the blob stays wave-uniform as before.  false: the
+// blob does not hold this launch's shape (or is not a blob) and must not be indexed.
+__device__ __forceinline__ bool gns_group_topo(const int* set, const int* group_topo, long long g, int N, int E, cip& topo) {
+  topo = (cip)set + ((cip)group_topo)[g];
+  return topo[TH_MAGIC] == GNS_TOPO_MAGIC && topo[TH_N] == N && topo[TH_E] == E;
+}
 typedef const __attribute__((address_space(4))) f16v* cf16p;
 typedef f16v f16u __attribute__((aligned(4)));                       // a 16-float chunk that starts at any dword
 typedef const __attribute__((address_space(4))) f16u* cf16up;

@@ -104,7 +104,8 @@ __global__ void gns_pack_params_kernel(const float* __restrict__ flat, float* __
 // (rows only 4-byte aligned) are read 2-4 columns at a time (gfx950 global loads need dword alignment only).
 __global__ void gns_pack_inputs_kernel(const int* __restrict__ topo, const float* __restrict__ buses,
                                        const float* __restrict__ lines, const float* __restrict__ gens,
-                                       float* __restrict__ out, int N, int E, int Gn, long long Bt, long long rows, long long groups) {
+                                       float* __restrict__ out, int N, int E, int Gn, long long Bt, long long rows, long long groups,
+                                       const int* __restrict__ group_topo, const int* __restrict__ slot_grid) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
   // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2; every workgroup of one group of 64 grids
   // re-reads the same 0.6 MB of input, so a group is kept on one XCD: linear id -> (xcd, j), group = 8 (j / chunks) + xcd.
@@ -116,6 +117,14 @@ __global__ void gns_pack_inputs_kernel(const int* __restrict__ topo, const float
   if (g >= groups) return;
   long long b = g * GNS_LANES + lane;
   if (b >= Bt) b = Bt - 1;               // dead lanes replay the last grid; their results are never stored
+  if (group_topo) {                      // grouped call: the group's own topology, the grids its slot map names
+    cip t;
+    if (!gns_group_topo(topo, group_topo, g, N, E, t) || t[TH_GN] != Gn) return;   // (the forward then writes NaN losses for the group)
+    topo = (const int*)t;
+    b = slot_grid[g * GNS_LANES + lane];
+    if (b < 0 || b >= Bt) b = slot_grid[g * GNS_LANES];        // a dead slot replays the group's first live grid: finite arithmetic
+    if (b < 0 || b >= Bt) b = 0;
+  }
   const float* bu = buses + b * (long long)N * 6;
   const float* li = lines + b * (long long)E * 7;
   const float* ge = gens + b * (long long)Gn * 7;
@@ -190,8 +199,8 @@ __global__ void gns_pack_inputs_kernel(const int* __restrict__ topo, const float
 #define GNS_FWD_ROW_STORES 0      // 1 (diagnostic): keep the dead partial stores of theta / v into the state row
 #endif
 // ------------------------------------------------------------------------------------------------
-template <int D, int H, bool MULTI>
-__global__ void __launch_bounds__(GNS_FWD_MAX_THREADS) gns_forward_kernel(GnsFwdArgs A) {
+template <int D, int H, bool MULTI, bool GROUPED>   // GROUPED: a grouped call (A.group_topo, A.slot_grid), instantiated apart so that the
+__global__ void __launch_bounds__(GNS_FWD_MAX_THREADS) gns_forward_kernel(GnsFwdArgs A) {   // one-topology code is what it was
   using C = GnsDims<D, H, MULTI>;
   constexpr int MQ = C::MQ, RB = C::RB;
   const int lane = threadIdx.x & 63;
@@ -208,6 +217,17 @@ __global__ void __launch_bounds__(GNS_FWD_MAX_THREADS) gns_forward_kernel(GnsFwd
   const int cw = member * nwaves + wave, tw = tsize * nwaves;       // this wave among the waves of the group
   const int N = A.N, E = A.E, K = A.K;
   cip topo = (cip)A.topo;
+  long long b = g * GNS_LANES + lane;
+  bool live = b < A.Bt;
+  if constexpr (GROUPED) {                               // grouped call: the group's topology; lanes compute the grids of the slot map
+    const int s = A.slot_grid[g * GNS_LANES + lane];
+    b = s;
+    live = s >= 0 && s < A.Bt;
+    if (!gns_group_topo(A.topo, A.group_topo, g, N, E, topo)) {          // a blob of another shape: never indexed, the losses say so
+      if (member == 0 && wave == 0 && live) { A.total_out[b] = __builtin_nanf(""); A.last_out[b] = __builtin_nanf(""); }
+      return;                                                            // (uniform over the team: no member reaches a barrier)
+    }
+  }
   cfp PT = (cfp)A.pt;
   const cip in_ptr = topo + topo[TH_IN_PTR], in_src = topo + topo[TH_IN_SRC], in_a = topo + topo[TH_IN_A],
             in_b = topo + topo[TH_IN_B], out_ptr = topo + topo[TH_OUT_PTR], out_dst = topo + topo[TH_OUT_DST],
@@ -221,8 +241,6 @@ __global__ void __launch_bounds__(GNS_FWD_MAX_THREADS) gns_forward_kernel(GnsFwd
   const float* IN = A.in;
   const long long in_base = g * R;
   const long long row_ein = in_base + 3LL * N, row_eout = row_ein + 3LL * E, row_grid = row_eout + E;
-  const long long b = g * GNS_LANES + lane;
-  const bool live = b < A.Bt;
 
   // (v, theta) of every bus of the 64 grids for the step being produced, written by the update phase and gathered by
   // the line physics (6 neighbour buses per line): 60 KB for case118 instead of ~19 HBM rows per bus and step.
@@ -566,7 +584,8 @@ static size_t fwd_dyn_lds(const GnsFwdArgs& A) {
 template <int D, int H, bool MULTI>
 static int launch_forward_t(const GnsFwdArgs& A, int threads, hipStream_t st) {
   // (> 64 KB of dynamic LDS needs an opt-in per kernel and device: gns_fwd_init_device, once, from the library's initialisation)
-  hipLaunchKernelGGL((gns_forward_kernel<D, H, MULTI>), dim3((unsigned)(A.G * A.team)), dim3(threads), fwd_dyn_lds(A), st, A);
+  if (A.group_topo) hipLaunchKernelGGL((gns_forward_kernel<D, H, MULTI, true>), dim3((unsigned)(A.G * A.team)), dim3(threads), fwd_dyn_lds(A), st, A);
+  else hipLaunchKernelGGL((gns_forward_kernel<D, H, MULTI, false>), dim3((unsigned)(A.G * A.team)), dim3(threads), fwd_dyn_lds(A), st, A);
   return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
 }
 
@@ -574,8 +593,10 @@ static int launch_forward_t(const GnsFwdArgs& A, int threads, hipStream_t st) {
 int gns_fwd_init_device() {
   int rc = GNS_OK;
 #define GNS_CASE(DD, HH)                                                                                                              \
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_forward_kernel<DD, HH, true>), hipFuncAttributeMaxDynamicSharedMemorySize, GNS_FWD_DYN_LDS_MAX) != hipSuccess) rc = GNS_ELAUNCH;   \
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_forward_kernel<DD, HH, false>), hipFuncAttributeMaxDynamicSharedMemorySize, GNS_FWD_DYN_LDS_MAX) != hipSuccess) rc = GNS_ELAUNCH;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_forward_kernel<DD, HH, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, GNS_FWD_DYN_LDS_MAX) != hipSuccess) rc = GNS_ELAUNCH;   \
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_forward_kernel<DD, HH, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, GNS_FWD_DYN_LDS_MAX) != hipSuccess) rc = GNS_ELAUNCH;   \
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_forward_kernel<DD, HH, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, GNS_FWD_DYN_LDS_MAX) != hipSuccess) rc = GNS_ELAUNCH;   \
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_forward_kernel<DD, HH, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, GNS_FWD_DYN_LDS_MAX) != hipSuccess) rc = GNS_ELAUNCH;
   GNS_FOR_EACH_DIMS(GNS_CASE)
 #undef GNS_CASE
   if (rc != GNS_OK) (void)hipGetLastError();
@@ -587,8 +608,12 @@ int gns_fwd_blocks_per_cu(int d, int h, int multi, const GnsFwdArgs& A, int thre
   int nb = 0;
 #define GNS_CASE(DD, HH)                                                                                                              \
   if (d == DD && h == HH) {                                                                                                           \
-    const hipError_t e = multi ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gns_forward_kernel<DD, HH, true>, threads, fwd_dyn_lds(A))     \
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gns_forward_kernel<DD, HH, false>, threads, fwd_dyn_lds(A));   \
+    const size_t lds = fwd_dyn_lds(A);                                                                                                \
+    const hipError_t e = A.group_topo                                                                                                 \
+        ? (multi ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gns_forward_kernel<DD, HH, true, true>, threads, lds)              \
+                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gns_forward_kernel<DD, HH, false, true>, threads, lds))            \
+        : (multi ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gns_forward_kernel<DD, HH, true, false>, threads, lds)             \
+                 : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gns_forward_kernel<DD, HH, false, false>, threads, lds));          \
     if (e != hipSuccess) { (void)hipGetLastError(); return 0; }                                                                       \
     return nb;                                                                                                                        \
   }
@@ -612,11 +637,12 @@ int gns_launch_pack_params(const float* flat, float* pt, float* pn, const GnsFam
 }
 
 int gns_launch_pack_inputs(const int* topo, const float* buses, const float* lines, const float* gens, float* out, int N,
-                           int E, int Gn, long long Bt, long long groups, hipStream_t st) {
+                           int E, int Gn, long long Bt, long long groups, hipStream_t st, const int* group_topo, const int* slot_grid) {
   const long long rows = gns_in_rows(N, E);
   const int W = 4;
   const long long chunks = (N + W - 1) / W + (E + W - 1) / W + ((E + 3) / 4 + W - 1) / W + 1, blocks = chunks * ((groups + 7) / 8 * 8);
   if (blocks > 0x7fffffffLL) return GNS_ESIZE;
-  hipLaunchKernelGGL(gns_pack_inputs_kernel, dim3((unsigned)blocks), dim3(64 * W), 0, st, topo, buses, lines, gens, out, N, E, Gn, Bt, rows, groups);
+  hipLaunchKernelGGL(gns_pack_inputs_kernel, dim3((unsigned)blocks), dim3(64 * W), 0, st, topo, buses, lines, gens, out, N, E, Gn, Bt, rows, groups,
+                     group_topo, slot_grid);
   return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
 }

@@ -58,6 +58,8 @@ struct GnsFwdArgs {
   int plane;              // 1: the (v, theta) of the step being produced is mirrored in LDS ([N][64] float2, dynamic shared memory); 2: and (delta_p, delta_q) between the physics and lambda phases
   int team;               // workgroups per 64-grid group (1 = none); part_idx then names the partition for team * waves
   unsigned char* team_ws; // team > 1: [G] 64-byte counter lines (zero at launch) | [G][GNS_TEAM_RED_FLOATS] partial sums
+  const int* group_topo;  // grouped call (gns_device.h, gns_group_topo): [G] word offset of group g's blob in the set `topo`; NULL: one topology
+  const int* slot_grid;   // grouped call: [G][64] input grid of each lane, -1 = dead; v / theta / losses are written in input order
 };
 
 struct GnsBwdArgs {
@@ -88,7 +90,8 @@ int gns_fwd_init_device();
 int gns_fwd_blocks_per_cu(int d, int h, int multi, const GnsFwdArgs& A, int threads);
 int gns_launch_pack_params(const float* flat, float* pt, float* pn, const GnsFamilies& fam, int K, int D, int H, hipStream_t st);
 int gns_launch_pack_inputs(const int* topo, const float* buses, const float* lines, const float* gens, float* out, int N,
-                           int E, int Gn, long long Bt, long long groups, hipStream_t st);
+                           int E, int Gn, long long Bt, long long groups, hipStream_t st,
+                           const int* group_topo = nullptr, const int* slot_grid = nullptr);   // grouped call: gns_device.h, gns_group_topo
 
 // split backward (gns_backward_split.hip; gns_common.h "split backward")
 struct GnsBwdsArgs {
@@ -105,6 +108,8 @@ struct GnsBwdsArgs {
   int RB, RBA;             // state rows per bus (1 + mq), adjoint rows per bus (4 + 6 mq)
   int use_plane;           // phys: LDS planes of the line phase: 2 (v, theta, dpbar) of all buses, 1 (v, theta) only, 0 none
   int mode;                // sweep kernels per step: 0 {m}{theta}{v}, 1 {m}{theta+v}, 2 {m+theta+v} (gns_backward_split.hip)
+  const int* group_topo;   // grouped call: as in GnsFwdArgs (NULL: one topology)
+  const int* slot_grid;
 };
 int gns_bwds_supported(int d, int h, int multi);
 size_t gns_bwds_phys_lds(int N, int* use_plane);

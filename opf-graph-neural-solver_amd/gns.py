@@ -77,6 +77,94 @@ class _Topology:
         return t
 
 
+def _validated_topology(l_np, g_np, n_bus, dev):
+    """The device blob of one topology from its id columns (``lines[:, 0:2]``, ``generators[:, 0]`` as float64 numpy), after the
+    checks every topology passes: integer ids in 1..N, and (``_Topology.build``) every connected bus id <= E."""
+    if not (np.all(l_np == np.round(l_np)) and np.all(g_np == np.round(g_np))):
+        raise ValueError('bus id columns must hold integers')
+    src, dst, gb = l_np[:, 0].astype(np.int64) - 1, l_np[:, 1].astype(np.int64) - 1, g_np.astype(np.int64) - 1
+    if src.min(initial=0) < 0 or dst.min(initial=0) < 0 or max(src.max(initial=0), dst.max(initial=0)) >= n_bus \
+            or (gb.size and (gb.min() < 0 or gb.max() >= n_bus)):
+        raise ValueError(f'bus ids must lie in 1..{n_bus}')
+    return _Topology.build(load_library(), n_bus, src, dst, gb, dev)
+
+
+def _classify_ids(lines3, gens3):
+    """Topologies of a batch: its distinct id rows ``(f_bus, t_bus | generator bus)`` (float64, host), for every grid the index of
+    its row (``inverse``, on the batch's device) and the grids per row (``counts``, host).  One ``torch.unique`` on the device."""
+    S = lines3.shape[0]
+    ids = torch.cat([lines3[:, :, 0:2].reshape(S, -1), gens3[:, :, 0]], 1).to(torch.float64)
+    ids_i = ids.round().to(torch.int64)
+    uniq, inverse, counts = torch.unique(ids_i, dim=0, return_inverse=True, return_counts=True)
+    tail = torch.cat([counts, (ids_i.to(torch.float64) != ids).any().reshape(1).to(torch.int64)]).cpu()    # one sync for both
+    if int(tail[-1]):
+        raise ValueError('bus id columns must hold integers')
+    return uniq.cpu().to(torch.float64), inverse, tail[:-1]
+
+
+def _group_tables(inverse, counts):
+    """The tables of a grouped call.  Topology t's grids fill ``ceil(counts[t] / 64)`` consecutive 64-grid groups in input order; its
+    last group is padded with dead slots (-1).  Returns (``group_idx`` [G]: the topology of each group, ``slot_grid`` [G*64]: the
+    input grid of each slot), on ``inverse``'s device; ``counts`` is a host tensor."""
+    counts = counts.to(torch.int64)
+    dev = inverse.device
+    gpt = (counts + 63) // 64                                                       # groups per topology
+    gstart = torch.cumsum(gpt, 0) - gpt
+    cstart = torch.cumsum(counts, 0) - counts
+    G = int(gpt.sum())
+    order = torch.argsort(inverse, stable=True)                                     # input grids by topology, input order kept
+    t_sorted = inverse[order]
+    rank = torch.arange(order.numel(), device=dev) - cstart.to(dev)[t_sorted]
+    slot_grid = torch.full((G * 64,), -1, dtype=torch.int32, device=dev)
+    slot_grid[64 * gstart.to(dev)[t_sorted] + rank] = order.to(torch.int32)
+    group_idx = torch.repeat_interleave(torch.arange(counts.numel()), gpt).to(dev)
+    return group_idx, slot_grid
+
+
+class _TopologySet:
+    """The topologies a model has met in mixed batches of one shape: their blobs concatenated in one device tensor at 64-byte aligned
+    word offsets (the blob's line records are 64-byte aligned relative to its start), grown as new topologies appear.  A set holding
+    more topologies than a batch uses costs nothing, so random mini-batches of a contingency data set share one set."""
+
+    ALIGN_WORDS = 16
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.index = {}                 # id row bytes -> position
+        self.blobs, self.words = [], [0]
+        self.blob = None
+        self._offsets = None
+
+    def index_of(self, ids_row, n_bus, n_line):
+        k = ids_row.tobytes()
+        i = self.index.get(k)
+        if i is None:
+            l_np = ids_row[:2 * n_line].reshape(n_line, 2)
+            t = _validated_topology(l_np, ids_row[2 * n_line:], n_bus, self.dev)
+            i = self.index[k] = len(self.blobs)
+            self.blobs.append(t)
+            w = t.blob.numel()
+            self.words.append(self.words[-1] + (w + self.ALIGN_WORDS - 1) // self.ALIGN_WORDS * self.ALIGN_WORDS)
+            self.blob = None
+        return i
+
+    def offsets(self):
+        if self.blob is None:               # (a set handed to an earlier call stays alive through that call's autograd context)
+            blob = torch.zeros(self.words[-1], dtype=torch.int32, device=self.dev)
+            for t, w in zip(self.blobs, self.words):
+                blob[w:w + t.blob.numel()] = t.blob
+            self.blob = blob
+            self._offsets = torch.as_tensor(self.words[:-1], dtype=torch.int32, device=self.dev)
+        return self._offsets
+
+
+class _TopologyGroups:
+    """What a grouped call reads: the topology set, ``group_topo`` [G] (word offset of each group's blob), ``slot_grid`` [G*64]."""
+
+    def __init__(self, topo_set, group_topo, slot_grid, groups):
+        self.topo_set, self.group_topo, self.slot_grid, self.groups = topo_set, group_topo, slot_grid, groups
+
+
 POISON_WORKSPACES = False     # test hook: workspaces are handed to the library filled with 0xFF bytes (NaN as floats) instead of
                               # uninitialised, so that a kernel reading a word nothing wrote shows up as NaN instead of by chance
 
@@ -87,11 +175,17 @@ def _workspace(nbytes, dev):
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
 
 
-def _raise_if_team_failed(lib, cfg, Bt, ws, save_state, dev):
+def _raise_if_team_failed(lib, cfg, Bt, ws, save_state, dev, groups=None):
+    """``groups``: the call was a grouped one (a batch that mixes topologies) in that many 64-grid groups."""
     st = ctypes.c_int()
     with torch.cuda.device(dev):
-        _check(lib.gns_team_status(ctypes.byref(cfg), Bt, ws.data_ptr(), ws.numel(), int(save_state), ctypes.byref(st),
-                                   torch.cuda.current_stream(dev).cuda_stream), 'gns_team_status')
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if groups is None:
+            _check(lib.gns_team_status(ctypes.byref(cfg), Bt, ws.data_ptr(), ws.numel(), int(save_state), ctypes.byref(st), stream),
+                   'gns_team_status')
+        else:
+            _check(lib.gns_team_status_grouped(ctypes.byref(cfg), groups, ws.data_ptr(), ws.numel(), int(save_state), ctypes.byref(st),
+                                               stream), 'gns_team_status_grouped')
     if st.value:
         raise GNSError('a team of workgroups gave up at a barrier: a kernel of another stream or process held a partner\'s compute unit, '
                        'so the losses of this call are NaN and no gradient was computed from them.  Teams need the device to themselves: '
@@ -177,15 +271,94 @@ class _GNSFunction(torch.autograd.Function):
             if bool(torch.isnan(grad[0])):
                 raise GNSError('a team of workgroups gave up at a barrier of the backward kernel: no gradient is delivered '
                                '(opf_graph_neural_solver_amd.set_option("team", 1) or the default bwd_variant 4 run without teams)')
-        pdev = ctx.params[0].device
-        if pdev != dev:
-            grad = grad.to(pdev)                          # CPU-resident model: 59 KB back to the host, like the reference's .grad
-        out, off = [], 0
-        for shp in ctx.shapes:
-            n = int(np.prod(shp))
-            out.append(grad[off:off + n].view(shp))
-            off += n
-        return (None, None, None, None, None, None, *out)
+        return (None, None, None, None, None, None, *_param_grads(ctx, grad))
+
+
+def _param_grads(ctx, grad):
+    """The flat gradient as one view per differentiable input (``ctx.shapes``), on the parameters' device."""
+    pdev = ctx.params[0].device
+    if pdev != grad.device:
+        grad = grad.to(pdev)                              # CPU-resident model: 59 KB back to the host, like the reference's .grad
+    out, off = [], 0
+    for shp in ctx.shapes:
+        n = int(np.prod(shp))
+        out.append(grad[off:off + n].view(shp))
+        off += n
+    return out
+
+
+class _GNSGroupedFunction(torch.autograd.Function):
+    """``_GNSFunction`` for a batch that mixes topologies: one topology per 64-grid group (``_TopologyGroups``), the grouped entry
+    points of the library (lane-per-grid forward, split backward).  Outputs and upstream gradients are in input order."""
+
+    @staticmethod
+    def forward(ctx, mod, plan, want_grad, buses, lines, gens, *params):
+        lib = load_library()
+        Bt, N = buses.shape[0], buses.shape[1]
+        cfg = mod._config(N, lines.shape[1], gens.shape[1])
+        dev = buses.device
+        need_grad = bool(want_grad)
+        ctx.set_materialize_grads(False)
+        G = plan.groups
+        fwd_b, bwd_b = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(lib.gns_workspace_bytes_grouped(ctypes.byref(cfg), G, int(need_grad), ctypes.byref(fwd_b), ctypes.byref(bwd_b)),
+               'gns_workspace_bytes_grouped')
+        ws = _workspace(fwd_b.value, dev)
+        v = torch.empty((Bt, N), dtype=torch.float32, device=dev)
+        theta = torch.empty_like(v)
+        total = torch.empty(Bt, dtype=torch.float32, device=dev)
+        last = torch.empty_like(total)
+        flat = mod._exec_flat(dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_forward_grouped(ctypes.byref(cfg), plan.topo_set.data_ptr(), plan.group_topo.data_ptr(), plan.slot_grid.data_ptr(),
+                                           G, flat.data_ptr(), buses.data_ptr(), lines.data_ptr(), gens.data_ptr(), Bt, v.data_ptr(),
+                                           theta.data_ptr(), total.data_ptr(), last.data_ptr(), ws.data_ptr(), ws.numel(), int(need_grad),
+                                           stream), 'gns_forward_grouped')
+        off = ctypes.c_size_t()
+        _check(lib.gns_team_status_offset_grouped(ctypes.byref(cfg), G, int(need_grad), ctypes.byref(off)), 'gns_team_status_offset_grouped')
+        uses_teams = off.value != ctypes.c_size_t(-1).value
+        ctx.team_status = uses_teams and need_grad
+        if uses_teams and not need_grad and not torch.cuda.is_current_stream_capturing():
+            mod.__dict__['_pending_status'] = (cfg, Bt, ws, dev, G)
+        if need_grad:
+            ctx.cfg, ctx.plan, ctx.ws, ctx.flat, ctx.Bt, ctx.bwd_bytes = cfg, plan, ws, flat, Bt, bwd_b.value
+            ctx.params = params
+            ctx.mod_flat = mod._flat
+            ctx.param_versions = tuple(p._version for p in params) + (mod._flat._version,)
+            ctx.inputs = (buses, lines, gens)
+            ctx.input_versions = (buses._version, lines._version, gens._version)
+            ctx.shapes = [p.shape for p in params]
+        return v, theta, total, last
+
+    @staticmethod
+    def backward(ctx, gv, gth, gtot, glast):
+        lib = load_library()
+        flat = ctx.flat
+        if tuple(p._version for p in ctx.params) + (ctx.mod_flat._version,) != ctx.param_versions:
+            raise GNSError('parameters were modified in place between forward and backward')
+        if tuple(t._version for t in ctx.inputs) != ctx.input_versions:
+            raise GNSError('buses / lines / generators were modified in place between forward and backward')
+        dev = flat.device
+        plan = ctx.plan
+        if ctx.team_status and not torch.cuda.is_current_stream_capturing():
+            _raise_if_team_failed(lib, ctx.cfg, ctx.Bt, ctx.ws, 1, dev, groups=plan.groups)
+        grad = torch.zeros_like(flat)
+        bws = _workspace(ctx.bwd_bytes, dev)
+
+        def ptr(t):
+            return None if t is None else t.data_ptr()
+
+        keep = [t.to(dev).contiguous() if t is not None else None for t in (gtot, glast, gv, gth)]
+        bu, li_, ge = ctx.inputs
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_backward_grouped(ctypes.byref(ctx.cfg), plan.topo_set.data_ptr(), plan.group_topo.data_ptr(),
+                                            plan.slot_grid.data_ptr(), plan.groups, flat.data_ptr(), bu.data_ptr(), li_.data_ptr(),
+                                            ge.data_ptr(), ctx.Bt, ctx.ws.data_ptr(), ctx.ws.numel(), ptr(keep[0]), ptr(keep[1]),
+                                            ptr(keep[2]), ptr(keep[3]), grad.data_ptr(), bws.data_ptr(), bws.numel(), stream),
+                   'gns_backward_grouped')
+        return (None, None, None, None, None, None, *_param_grads(ctx, grad))
 
 
 class GNS(nn.Module):
@@ -230,7 +403,10 @@ class GNS(nn.Module):
         # device compare, one flag, one sync - so a batch that mixes topologies raises like it does when a case is first seen.
         # Opt-ins for loops that have validated their data set themselves (``training.fit`` does): 'grid0' compares the first
         # grid only, 'first' trusts the cached case of that shape.
+        # 'group': every grid is compared like 'always'; a batch of one topology then takes the same path (same results, bit for
+        # bit), a batch that mixes topologies runs one topology per 64-grid group (``_topology_groups``) instead of raising.
         self.topology_check = 'always'
+        self.__dict__['_group_sets'] = {}
         self.__dict__['_mirror'] = None
         # True: a batch that is passed again unchanged (same tensors, same versions) is brought into the kernels' input
         # layout once instead of on every call (gns_prepack).  Off by default: the cache keeps the last batch alive.
@@ -407,8 +583,8 @@ class GNS(nn.Module):
         pend = self.__dict__.get('_pending_status')
         if pend is not None:
             self.__dict__['_pending_status'] = None
-            cfg, Bt, ws, dev = pend
-            _raise_if_team_failed(load_library(), cfg, Bt, ws, 0, dev)
+            cfg, Bt, ws, dev = pend[:4]
+            _raise_if_team_failed(load_library(), cfg, Bt, ws, 0, dev, groups=pend[4] if len(pend) > 4 else None)
 
     def flat_leaf(self):
         """A leaf tensor (``requires_grad``) that aliases the flat parameter buffer: with ``flat_grad = True`` the autograd graph
@@ -451,18 +627,31 @@ class GNS(nn.Module):
             if same:
                 return ent[0]
         if not (bool((lines3[:, :, 0:2] == ids_l).all()) and bool((gens3[:, :, 0] == ids_g).all())):
+            if self.topology_check == 'group':
+                return self._topology_groups(lines3, gens3, n_bus)
             raise ValueError('f_bus / t_bus / generator bus columns differ across the batch: the fused path needs one '
-                             'topology per call (group grids by topology on the host)')
+                             'topology per call (group grids by topology on the host, or set topology_check = \'group\' - '
+                             'not for bind_dataset / training.GraphedStep, which take one topology)')
         l_np, g_np = ids_l.detach().cpu().numpy().astype(np.float64), ids_g.detach().cpu().numpy().astype(np.float64)
-        if not (np.all(l_np == np.round(l_np)) and np.all(g_np == np.round(g_np))):
-            raise ValueError('bus id columns must hold integers')
-        src, dst, gb = l_np[:, 0].astype(np.int64) - 1, l_np[:, 1].astype(np.int64) - 1, g_np.astype(np.int64) - 1
-        if src.min(initial=0) < 0 or dst.min(initial=0) < 0 or max(src.max(initial=0), dst.max(initial=0)) >= n_bus \
-                or (gb.size and (gb.min() < 0 or gb.max() >= n_bus)):
-            raise ValueError(f'bus ids must lie in 1..{n_bus}')
-        topo = _Topology.build(load_library(), n_bus, src, dst, gb, dev)
+        topo = _validated_topology(l_np, g_np, n_bus, dev)
         self._topo_cache[key] = (topo, ids_l.clone(), ids_g.clone())
         return topo
+
+    def _topology_groups(self, lines3, gens3, n_bus):
+        """A batch that mixes topologies (``topology_check = 'group'``): its grids classified by id rows, one blob per topology (built
+        once per model and shape, kept in a growing device set), and the group / slot tables of the grouped kernels."""
+        dev, E, Gn = lines3.device, lines3.shape[1], gens3.shape[1]
+        ids, inverse, counts = _classify_ids(lines3, gens3)
+        key = (n_bus, E, Gn, str(dev))
+        reg = self._group_sets.get(key)
+        if reg is None:
+            reg = self._group_sets[key] = _TopologySet(dev)
+        ids_np = ids.numpy()
+        index = [reg.index_of(ids_np[t], n_bus, E) for t in range(ids_np.shape[0])]
+        group_idx, slot_grid = _group_tables(inverse, counts)
+        offsets = reg.offsets()                                  # (after every new blob of this batch is in)
+        group_topo = offsets[torch.as_tensor(index, dtype=torch.int64, device=dev)[group_idx.to(dev)]]
+        return _TopologyGroups(reg.blob, group_topo.contiguous(), slot_grid.to(dev, torch.int32).contiguous(), int(group_idx.numel()))
 
     # ---- forward --------------------------------------------------------------------------------------
     @staticmethod
@@ -511,7 +700,8 @@ class GNS(nn.Module):
         want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
         if self.flat_grad and want_grad and params[0].device.type == 'cuda':
             params = [self.flat_leaf()]                     # one differentiable input: the gradient comes back as one tensor
-        v, theta, total, last = _GNSFunction.apply(self, topo, want_grad, buses, lines, generators, *params)
+        fn = _GNSGroupedFunction if isinstance(topo, _TopologyGroups) else _GNSFunction
+        v, theta, total, last = fn.apply(self, topo, want_grad, buses, lines, generators, *params)
         if in_dev != dev:
             v, theta, total, last = v.to(in_dev), theta.to(in_dev), total.to(in_dev), last.to(in_dev)
         if single:

@@ -218,3 +218,39 @@ def raw_case_arrays(case_nr: int, batch: int, seed: int = 0, zero_tau_fraction: 
     ge[:, :, 5] = T(c['Vg']) * u(0.95, 1.05, batch, gn)
     ge[:, :, 6], ge[:, :, 7] = BASE_MVA, 1
     return bus, br, ge
+
+
+def contingency_grids(case_nr: int, batch: int, outages, seed: int = 0, device='cpu', shuffle: bool = False):
+    """N-1 contingency variants of a case: grid ``i`` is ``synth_grids(case_nr, batch, seed)[i]`` with line ``outages[j]`` (0-based)
+    removed, ``j = i % len(outages)`` (round-robin) or, with ``shuffle``, drawn per grid from a generator seeded with ``seed``.
+    Every variant keeps the other lines in their order, so all stack into one ``lines[batch, E-1, 7]`` tensor whose id columns differ
+    between variants: a batch that mixes topologies (``GNS.topology_check = 'group'``).
+
+    Returns ``(buses[batch,N,6], lines[batch,E-1,7], generators[batch,Gn,7], outage[batch])`` with ``outage[i]`` the line removed
+    from grid ``i``.  The reference reads per-line arrays at bus ids (GNS/main.py:41), so a variant is only valid when every bus id
+    of its remaining lines is at most ``E-1``: an outage list that breaks this is refused (ValueError)."""
+    if case_nr not in CASE_SHAPES:
+        raise ValueError(f'unknown case {case_nr}; known: {sorted(CASE_SHAPES)}')
+    e = CASE_SHAPES[case_nr][1]
+    outages = [int(j) for j in outages]
+    if not outages:
+        raise ValueError('contingency_grids needs at least one outage')
+    f_bus, t_bus, _ = case_topology(case_nr)
+    for j in outages:
+        if not 0 <= j < e:
+            raise ValueError(f'outage {j} is not a line index of case{case_nr} (0..{e - 1})')
+        keep = np.arange(e) != j
+        top = int(max(f_bus[keep].max(), t_bus[keep].max()))
+        if top > e - 1:
+            raise ValueError(f'outage of line {j} leaves bus id {top} on a line of case{case_nr}, above E-1 = {e - 1}: the reference '
+                             'reads per-line arrays at bus ids (GNS/main.py:41), so this variant has no valid interpretation')
+    if shuffle:
+        pick = torch.as_tensor(np.random.default_rng(seed).integers(0, len(outages), size=batch))
+    else:
+        pick = torch.arange(batch) % len(outages)
+    outage = torch.as_tensor(outages, dtype=torch.int64)[pick]
+    buses, lines, gens = synth_grids(case_nr, batch, seed=seed, device=device)
+    cols = torch.arange(e - 1).unsqueeze(0)
+    kept = cols + (cols >= outage.unsqueeze(1)).to(torch.int64)          # line indices of each variant, in order
+    lines = torch.gather(lines, 1, kept.to(lines.device).unsqueeze(2).expand(batch, e - 1, 7)).contiguous()
+    return buses, lines, gens, outage.to(buses.device)

@@ -200,6 +200,10 @@ class GraphedStep:
             if not all(t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 for t in (buses, lines, generators)):
                 raise ValueError('GraphedStep(copy_inputs=False) needs contiguous float32 device tensors')
             self.static = (buses, lines, generators)
+        ls, gs = self.static[1], self.static[2]
+        if not (bool((ls[:, :, 0:2] == ls[0, :, 0:2]).all()) and bool((gs[:, :, 0] == gs[0, :, 0]).all())):
+            raise ValueError('GraphedStep captures one topology: the batch mixes f_bus / t_bus / generator bus columns '
+                             '(run it eagerly with topology_check = \'group\')')
         B, L, G = get_BLG()
         optimizer.capturable = True
         # the id columns are validated on the warm-up call; replays trust them like ``topology_check = 'first'`` does (a host
@@ -304,7 +308,7 @@ def _graph_pays(model, optimizer, all_buses, all_lines, all_generators, batch_si
 
 
 def fit(model, all_buses, all_lines, all_generators, *, epochs=101, batch_size=128, optimizer_name='Adam', lr=None, case_nr=14,
-        print_every=1, checkpoint_dir=None, log=print, graph=None):
+        print_every=1, checkpoint_dir=None, log=print, graph=None, mixed_topologies=False):
     """Epoch loop of ``main.py:274-309``: batches in order, early stop once the epoch's mean final loss has failed to
     improve more than twice in a row (``:296-304``), checkpoint every ``print_every`` epochs (``:306-309``).
 
@@ -312,10 +316,24 @@ def fit(model, all_buses, all_lines, all_generators, *, epochs=101, batch_size=1
     parameters.  Returns the list of epoch mean final losses.
 
     ``graph``: replay one captured HIP graph per step (``GraphedStep``) instead of running the step from Python; default
-    (None) = where it pays (``_graph_pays``).  Same arithmetic, same order: the weights are those of the eager loop bit for bit."""
+    (None) = where it pays (``_graph_pays``).  Same arithmetic, same order: the weights are those of the eager loop bit for bit.
+
+    ``mixed_topologies=True``: the data set may mix topologies (an N-1 contingency set): the uniform-set check is skipped, every
+    batch is classified by the model (``topology_check = 'group'``: one topology per 64-grid group), and the data set is neither
+    bound nor captured into a graph."""
     optimizer = make_optimizer(model, optimizer_name, lr)
     nr_samples = all_buses.shape[0]
     best, bad, history = float('inf'), 0, []
+    if mixed_topologies:
+        if graph:
+            raise ValueError('fit(mixed_topologies=True) runs eagerly: a captured step holds one topology')
+        saved_check = model.topology_check
+        model.topology_check = 'group'
+        try:
+            return _fit_loop(model, optimizer, all_buses, all_lines, all_generators, nr_samples, epochs, batch_size, optimizer_name,
+                             case_nr, print_every, checkpoint_dir, log, best, bad, history, False)
+        finally:
+            model.topology_check = saved_check
     # the id columns of the whole data set are compared once here; the per-call comparison (four device->host syncs per
     # step) is switched off for the loop: the model then builds / validates the topology on the first batch only
     if not (bool((all_lines[:, :, 0:2] == all_lines[0, :, 0:2]).all()) and bool((all_generators[:, :, 0] == all_generators[0, :, 0]).all())):

@@ -108,6 +108,28 @@ int gns_backward(const gns_config* cfg, const void* topo_dev, const float* param
                  const float* grad_total, const float* grad_last, const float* grad_v, const float* grad_theta,
                  float* grad_params, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream);
 
+/* Input gradients: d loss / d buses, lines, generators (the reference's autograd gives them when the inputs require grad).
+ * save_state = 2 in gns_workspace_bytes, gns_forward, gns_team_status and gns_team_status_offset means "saved for a backward that
+ * also returns input gradients": the call always runs the lane-per-grid forward, whatever "train_mapping" / "gw_pack" say, and its
+ * workspace carries a mark behind the saved state (fwd_bytes is 256 bytes larger); bwd_bytes then includes the input-adjoint buffer
+ * (one float4 row per packed input row and grid).  save_state 0 and 1 keep their meaning.
+ * gns_backward_inputs takes the arguments of gns_backward plus grad_buses [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7]
+ * in the caller's (reference) layout.  Every output may be NULL, grad_params included; each non-NULL one is ACCUMULATED (+=).
+ * buses / lines / generators are required (the derivatives of y = 1/sqrt(r^2+x^2) and of where(v == 0, 1, v) read them).  It always
+ * runs the split backward (bwd_variant 4) in both phi modes and at every compiled or zero-padded width, and grad_params is bit for
+ * bit what gns_backward computes for the same call.  Index columns (bus_i, type, f_bus, t_bus, generator bus_i) receive 0; the
+ * line parameters receive the physics terms where the reference's bus-id-as-line-index gathers put them (main.py:38-41,68-72,
+ * 91-99).  Run-to-run bitwise reproducible, no float atomics.  Returns GNS_EINVAL for a forward workspace that was not saved with
+ * save_state = 2; checking that mark is the one synchronisation of the call (it waits for `stream` and copies one word).
+ * Grouped calls (the *_grouped entry points) offer no input gradients. */
+int gns_backward_inputs(const gns_config* cfg, const void* topo_dev, const float* params,
+                        const float* buses, const float* lines, const float* generators, int64_t Bt,
+                        const void* packed_inputs,
+                        const void* fwd_workspace, size_t fwd_workspace_bytes,
+                        const float* grad_total, const float* grad_last, const float* grad_v, const float* grad_theta,
+                        float* grad_params, float* grad_buses, float* grad_lines, float* grad_generators,
+                        void* bwd_workspace, size_t bwd_workspace_bytes, void* stream);
+
 /* Teams (lane-per-grid kernels, batches with fewer 64-grid groups than CUs: "team" option below) meet at counters in the workspace.
  * A barrier whose partner workgroup never becomes resident - another kernel or process holds its CU - gives up after ~seconds; the
  * losses of that call are NaN and the workspace's status word is set.  gns_team_status reads that word: *status = 1 if a team gave

@@ -54,6 +54,7 @@ def load_library():
     lib.gns_prepack_bytes.argtypes = [cfgp, i64, ctypes.POINTER(sz)]
     lib.gns_prepack.argtypes = [cfgp, vp, vp, vp, vp, i64, vp, sz, vp]
     lib.gns_backward.argtypes = [cfgp, vp, vp, vp, vp, vp, i64, vp, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_backward_inputs.argtypes = [cfgp, vp, vp, vp, vp, vp, i64, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.gns_adam_step.argtypes = [vp, vp, vp, vp, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, i64, vp]
     lib.gns_adam_step_dev.argtypes = [vp, vp, vp, vp, i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, vp, vp]
     lib.gns_team_status_offset.argtypes = [cfgp, i64, ctypes.c_int, ctypes.POINTER(sz)]
@@ -68,7 +69,7 @@ def load_library():
     lib.gns_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
     lib.gns_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
-              'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_profile_enable', 'gns_profile_read',
+              'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
               'gns_set_option', 'gns_get_option', 'gns_prepack_bytes', 'gns_prepack', 'gns_uses_packed_inputs', 'gns_adam_step',
               'gns_adam_step_dev', 'gns_team_status', 'gns_team_status_offset', 'gns_workspace_bytes_grouped', 'gns_forward_grouped',
               'gns_backward_grouped', 'gns_team_status_grouped', 'gns_team_status_offset_grouped'):
@@ -78,7 +79,7 @@ def load_library():
 
 
 EXPORTS = ('gns_version', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
-           'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_profile_enable', 'gns_profile_read',
+           'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
            'gns_set_option', 'gns_get_option', 'gns_prepack_bytes', 'gns_prepack', 'gns_uses_packed_inputs', 'gns_adam_step',
            'gns_adam_step_dev', 'gns_team_status', 'gns_team_status_offset', 'gns_workspace_bytes_grouped', 'gns_forward_grouped',
            'gns_backward_grouped', 'gns_team_status_grouped', 'gns_team_status_offset_grouped')

@@ -167,6 +167,19 @@ static bool use_split_backward(const gns_config* c) {
   return T.bwd_variant == 4 && T.dw_mfma;
 }
 
+// Input gradients (gns_backward_inputs): the input-adjoint buffer behind the split backward's workspace, and the caller's outputs
+#define GNS_SAVE_IGRAD 2
+#define GNS_IGRAD_MARK 0x49475244u      // written behind a forward workspace saved with save_state = 2
+#define GNS_IGRAD_MARK_BYTES 256
+static size_t igrad_bytes(const gns_config* kcfg, int64_t Bt) {
+  return gns_align256((size_t)((Bt + GNS_LANES - 1) / GNS_LANES) * gns_in_rows(kcfg->n_bus, kcfg->n_line) * GNS_LANES * 16);
+}
+struct IgradOut {
+  float* buf; size_t bytes;
+  const float *in_buses, *in_lines, *in_gens;
+  float *buses, *lines, *gens;
+};
+
 // Which mapping runs a training-mode forward and its backward.  Evaluated identically by gns_forward and gns_backward:
 // changing "train_mapping" / "gw_pack" between a forward and its backward is a caller error.
 static int gw_train_pack(const gns_config* c, int64_t Bt) {
@@ -285,7 +298,17 @@ extern "C" int gns_workspace_bytes(const gns_config* cfg, int64_t Bt, int save_s
   cfg = &kcfg_; (void)model;
   GnsFwdLayout L;
   gns_fwd_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, save_state, &L);
-  const int P = save_state ? gw_train_pack(cfg, Bt) : 0;
+  const int P = (save_state && save_state != GNS_SAVE_IGRAD) ? gw_train_pack(cfg, Bt) : 0;
+  if (save_state == GNS_SAVE_IGRAD) {                                  // lane-per-grid forward + split backward with input gradients
+    if (!device().split_ready || !gns_bwds_supported(cfg->latent_dim, cfg->hidden_dim, cfg->multiple_phi)) return GNS_EUNSUPPORTED;
+    if (fwd_bytes) *fwd_bytes = L.total + GNS_IGRAD_MARK_BYTES;
+    if (bwd_bytes) {
+      GnsBwdsLayout S;
+      gns_bwds_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
+      *bwd_bytes = S.total + igrad_bytes(cfg, Bt);
+    }
+    return GNS_OK;
+  }
   if (P > 0) {
     const GwTrainLayout G = gw_train_layout(cfg, Bt, P);
     if (fwd_bytes) *fwd_bytes = G.fwd_total;
@@ -316,6 +339,7 @@ extern "C" int gns_uses_packed_inputs(const gns_config* cfg, int64_t Bt, int sav
   const gns_config* model = cfg; gns_config kcfg_;
   if (!kernel_config(model, &kcfg_)) return 0;
   cfg = &kcfg_; (void)model;
+  if (save_state == GNS_SAVE_IGRAD) return 1;
   return (save_state ? gw_train_pack(cfg, Bt) : gw_eval_pack(cfg, Bt)) > 0 ? 0 : 1;
 }
 
@@ -335,7 +359,7 @@ extern "C" int gns_team_status_offset(const gns_config* cfg, int64_t Bt, int sav
   cfg = &kcfg_; (void)model;
   *offset = (size_t)-1;
   if (lane_team(Bt) <= 1) return GNS_OK;
-  if ((save_state ? gw_train_pack(cfg, Bt) : gw_eval_pack(cfg, Bt)) > 0) return GNS_OK;          // the grid-per-workgroup kernels have no teams
+  if (save_state != GNS_SAVE_IGRAD && (save_state ? gw_train_pack(cfg, Bt) : gw_eval_pack(cfg, Bt)) > 0) return GNS_OK;   // the grid-per-workgroup kernels have no teams
   GnsFwdLayout L;
   gns_fwd_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, save_state, &L);
   *offset = L.off_team + GNS_TEAM_STATUS_WORD * 4;
@@ -352,7 +376,7 @@ extern "C" int gns_team_status(const gns_config* cfg, int64_t Bt, const void* fw
   cfg = &kcfg_; (void)model;
   *status = 0;
   if (lane_team(Bt) <= 1) return GNS_OK;
-  if ((save_state ? gw_train_pack(cfg, Bt) : gw_eval_pack(cfg, Bt)) > 0) return GNS_OK;          // the grid-per-workgroup kernels have no teams
+  if (save_state != GNS_SAVE_IGRAD && (save_state ? gw_train_pack(cfg, Bt) : gw_eval_pack(cfg, Bt)) > 0) return GNS_OK;   // the grid-per-workgroup kernels have no teams
   GnsFwdLayout L;
   gns_fwd_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, save_state, &L);
   if (fwd_workspace_bytes < L.total) return GNS_ESIZE;
@@ -433,7 +457,7 @@ static int lane_forward(const gns_config* cfg, const GnsFamilies& fam, const Gns
 static int split_backward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLayout& L, const GnsBwdsLayout& S, const char* fw,
                           char* bw, const int* topo_dev, const int* group_topo, const int* slot_grid, const float* params,
                           const void* packed_inputs, int64_t Bt, const float* grad_total, const float* grad_last, const float* grad_v,
-                          const float* grad_theta, float* grad_params, hipStream_t st) {
+                          const float* grad_theta, float* grad_params, hipStream_t st, const IgradOut* ig = nullptr) {
   const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
   int rc;
   GnsBwdsArgs A;
@@ -453,16 +477,29 @@ static int split_backward(const gns_config* cfg, const GnsFamilies& fam, const G
   A.RB = (int)(1 + S.mq); A.RBA = (int)S.adj_rows;
   A.mode = cfg->multiple_phi ? tuning().bwds_mode : 2;          // the single phi is reversed after all three L nets: bus-major
   const size_t lds = gns_bwds_phys_lds(N, &A.use_plane);
+  if (ig) {
+    A.igrad = ig->buf;
+    if (hipMemsetAsync(A.igrad, 0, ig->bytes, st) != hipSuccess) return GNS_ELAUNCH;
+  }
   prof_mark(1, true, st);
   for (int k = K - 1; k >= 0; --k) {
     A.k = k;
     A.gwk = (float)std::pow((double)cfg->gamma, (double)(K - k));
     rc = gns_launch_bwds_phys(A, lds, st);
     if (rc != GNS_OK) return rc;
+    if (ig) {
+      rc = gns_launch_bwds_igrad_phys(A, st);
+      if (rc != GNS_OK) return rc;
+    }
     rc = gns_launch_bwds_sweep(d, h, cfg->multiple_phi, A, st);
     if (rc != GNS_OK) return rc;
   }
+  if (ig && (ig->buses || ig->lines || ig->gens)) {
+    rc = gns_launch_bwds_igrad_unpack(A, ig->in_buses, ig->in_lines, ig->in_gens, cfg->n_gen, ig->buses, ig->lines, ig->gens, st);
+    if (rc != GNS_OK) return rc;
+  }
   prof_mark(1, false, st);
+  if (!grad_params) return GNS_OK;
   return gns_launch_reduce(A.slab, (float*)(bw + S.off_part), (float*)(bw + S.off_tmp), params, grad_params, S.nslab, S.slab_floats,
                            fam, K, d, h, st);
 }
@@ -482,7 +519,7 @@ extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const fl
   GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  if (const int TP = save_state ? gw_train_pack(cfg, Bt) : 0) {          // training-mode forward of the grid-per-workgroup pair
+  if (const int TP = (save_state && save_state != GNS_SAVE_IGRAD) ? gw_train_pack(cfg, Bt) : 0) {   // training-mode forward of the grid-per-workgroup pair
     const GwTrainLayout GL = gw_train_layout(cfg, Bt, TP);
     if (workspace_bytes < GL.fwd_total) return GNS_ESIZE;
     float* gpt = (float*)(ws + GL.off_pt);
@@ -506,6 +543,11 @@ extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const fl
   GnsFwdLayout L;
   gns_fwd_layout(N, E, d, h, K, cfg->multiple_phi, Bt, save_state, &L);
   if (workspace_bytes < ((!save_state && gw_eval_pack(cfg, Bt) > 0) ? L.off_in : L.total)) return GNS_ESIZE;
+  if (save_state == GNS_SAVE_IGRAD) {                  // saved for gns_backward_inputs: the mark it checks, behind the layout
+    if (workspace_bytes < L.total + GNS_IGRAD_MARK_BYTES) return GNS_ESIZE;
+    if (!device().split_ready || !gns_bwds_supported(d, h, cfg->multiple_phi)) return GNS_EUNSUPPORTED;
+    if (hipMemsetD32Async((hipDeviceptr_t)(ws + L.total), GNS_IGRAD_MARK, 1, st) != hipSuccess) return GNS_ELAUNCH;
+  }
   float* pt = (float*)(ws + L.off_pt);
   float* pn = (float*)(ws + L.off_pn);
   float* pin = (float*)(ws + L.off_in);
@@ -630,6 +672,41 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
   // the kernel has summed each workgroup's eight slabs into its first one: one slab per workgroup is left to reduce
   return gns_launch_reduce(A.slab, (float*)(bw + B.off_part), (float*)(bw + B.off_tmp), params, grad_params, blocks, B.slab_floats,
                            fam, K, d, h, st, (long long)GNS_BWD_WAVES * B.slab_floats);
+}
+
+extern "C" int gns_backward_inputs(const gns_config* cfg, const void* topo_dev, const float* params,
+                                   const float* buses, const float* lines, const float* generators, int64_t Bt, const void* packed_inputs,
+                                   const void* fwd_workspace, size_t fwd_workspace_bytes, const float* grad_total,
+                                   const float* grad_last, const float* grad_v, const float* grad_theta, float* grad_params,
+                                   float* grad_buses, float* grad_lines, float* grad_generators,
+                                   void* bwd_workspace, size_t bwd_workspace_bytes, void* stream) {
+  int rc = check_cfg(cfg);
+  if (rc != GNS_OK) return rc;
+  if (!topo_dev || !params || !buses || !lines || !generators || !fwd_workspace || !bwd_workspace || Bt <= 0) return GNS_EINVAL;
+  const gns_config* model = cfg; gns_config kcfg_;
+  if (!kernel_config(model, &kcfg_) || cfg->K > GNS_MAX_K) return GNS_EUNSUPPORTED;
+  cfg = &kcfg_;
+  const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
+  if (!device().split_ready || !gns_bwds_supported(d, h, cfg->multiple_phi)) return GNS_EUNSUPPORTED;
+  GnsFwdLayout L;
+  gns_fwd_layout(N, E, d, h, K, cfg->multiple_phi, Bt, 1, &L);
+  GnsBwdsLayout S;
+  gns_bwds_layout(N, E, d, h, K, cfg->multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
+  if (fwd_workspace_bytes < L.total + GNS_IGRAD_MARK_BYTES) return GNS_EINVAL;       // not a save_state = 2 workspace
+  const size_t ib = igrad_bytes(cfg, Bt);
+  if (bwd_workspace_bytes < S.total + ib) return GNS_ESIZE;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned mark = 0;                   // (the one synchronisation of this call: a workspace saved without input gradients is refused)
+  if (hipMemcpyAsync(&mark, (const char*)fwd_workspace + L.total, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return GNS_ELAUNCH; }
+  if (mark != GNS_IGRAD_MARK) return GNS_EINVAL;
+  GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
+  IgradOut ig;
+  ig.buf = (float*)((char*)bwd_workspace + S.total); ig.bytes = ib;
+  ig.in_buses = buses; ig.in_lines = lines; ig.in_gens = generators;
+  ig.buses = grad_buses; ig.lines = grad_lines; ig.gens = grad_generators;
+  return split_backward(cfg, fam, L, S, (const char*)fwd_workspace, (char*)bwd_workspace, (const int*)topo_dev, nullptr, nullptr, params,
+                        packed_inputs, Bt, grad_total, grad_last, grad_v, grad_theta, grad_params, st, &ig);
 }
 
 // ---- grouped calls: a batch that mixes topologies, one topology per 64-grid group (include/gns_hip.h) ---------------------------

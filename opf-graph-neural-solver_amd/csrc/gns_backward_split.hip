@@ -344,7 +344,7 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
   // xs = [v theta | dp dq | m | (the hidden sum this net reads goes here) | deg, 1]; g3s = the upstream of the scalar output (L_theta:
   // thbar, L_v: vbar or 0 on a generator bus); L_m takes macc = d/dm_{k+1} as its upstream.  xsum (d/dv, d/dtheta, d/ddp of the L
   // inputs) and macc (d/dm) accumulate; gS = the adjoint of the hidden sum: assigned (ACC_GS false) or accumulated (the single phi).
-  template <bool ACC_GS, bool STEP0>
+  template <bool ACC_GS, bool STEP0, bool IG = false>
   __device__ __forceinline__ void bus(const GnsBwdsArgs& A, float* rec, int lane, long long g, int n, float g3s, f2 (&xs)[XL],
                                       f2 (&macc)[D / 2], f4& xsum, f2 (&gS)[H / 2]) {
     f2 (&S)[H / 2] = reinterpret_cast<f2 (&)[H / 2]>(xs[SOFF]);
@@ -416,6 +416,19 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
 #endif
 #pragma unroll
     for (int u = 0; u < H / 2; ++u) g1[u] = g1[u] * GNS_SLOPE_OF(sl, 0, a1, u);
+    if constexpr (IG && STEP0) {
+      // input gradients: the adjoints of (v, theta, dp, dq)_0, which close the initial state (main.py:144-152).  Columns 0..3 of W1,
+      // input-major in the forward layout: xsum.w (d/d dq_0) is used by this instantiation only
+      float ax[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float acc = 0.f;
+#pragma unroll
+        for (int u = 0; u < H / 2; ++u) { acc = fmaf(ptl[i * H + 2 * u], g1[u].x, acc); acc = fmaf(ptl[i * H + 2 * u + 1], g1[u].y, acc); }
+        ax[i] = acc;
+      }
+      xsum.x += ax[0]; xsum.y += ax[1]; xsum.z += ax[2]; xsum.w += ax[3];
+    }
     static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putA<SW>(rec, lane, j, g2[j]); gws_putB<SW>(rec, lane, j, a1[j]); });
     gws_putB<SW>(rec, lane, H / 2, f2{1.f, 0.f});
     gws_w2r(); gws_pass<SW>(rec, lane, T2); gws_r2w();
@@ -503,7 +516,7 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
   }
 
   // back through the hidden vectors of the lines p0..p1 ending at the bus: gS = the adjoint of their sum
-  template <bool STEP0>
+  template <bool STEP0, bool IG = false>
   __device__ __forceinline__ void bus(const GnsBwdsArgs& A, float* rec, int lane, const f2 (&xs)[XL], const f2 (&gS)[H / 2],
                                       f2 (&macc)[D / 2], int p0, int p1, long long row_ein) {
     if (p0 >= p1) return;
@@ -541,6 +554,23 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
 #endif
 #pragma unroll
       for (int u = 0; u < H / 2; ++u) { g1[u] = g1[u] * GNS_SLOPE_OF(sl, 0, a1, u); G1[u] += g1[u]; }
+      if constexpr (IG) {
+        // input gradients: the adjoint of the line's own parameters in the net's input (main.py:155), W1[:, D..D+4]^T g1 (input-major
+        // in the forward layout), added to the line's rows of the input-adjoint buffer; the families of a bus add in a fixed order
+        float fa[5];
+#pragma unroll
+        for (int f = 0; f < 5; ++f) {
+          float acc = 0.f;
+#pragma unroll
+          for (int u = 0; u < H / 2; ++u) { acc = fmaf(ptb[(D + f) * H + 2 * u], g1[u].x, acc); acc = fmaf(ptb[(D + f) * H + 2 * u + 1], g1[u].y, acc); }
+          fa[f] = acc;
+        }
+        f4* r0 = row_ptr(A.igrad, row_ein + 3LL * p, lane);
+        f4* r1 = row_ptr(A.igrad, row_ein + 3LL * p + 1, lane);
+        const f4 o0 = *r0, o1 = *r1;
+        *r0 = f4{o0.x + fa[0], o0.y + fa[1], o0.z + fa[2], o0.w + fa[3]};
+        *r1 = f4{o1.x + fa[4], o1.y, o1.z, o1.w};
+      }
       constexpr int pw = WIDE ? 8 : 0;                // wide window: the line's pass contracts columns 16..31
       static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putA<SW>(rec, lane, j, g1[j]); });
       gws_putB<SW>(rec, lane, pw + 0, xt[0]); gws_putB<SW>(rec, lane, pw + 1, xt[1]); gws_putB<SW>(rec, lane, pw + 2, f2{xt[2].x, 1.f});
@@ -597,7 +627,9 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
 // Readers (Pb-0 for X, the L_m sweep for the latent adjoint) sum the slots of the mode in the order 2, 0, 1; slot 2 of step K-1
 // exists only in mode 2 (no gradient reaches L_m.{K-1}: in modes 0 and 1 no kernel writes it).
 // STEP0: the instantiation that reverses step 0 (its dead work compiled out); GROUPED: a grouped call (A.group_topo), instantiated apart
-template <int D, int H, bool MULTI, int FAMS, bool STEP0, bool GROUPED>
+// IG: input gradients (gns_backward_inputs): the phi nets add the adjoints of their line inputs to A.igrad, and step 0 stores the
+// adjoints of (v, theta, dp, dq)_0 in its X row for gns_bwds_igrad_unpack_kernel
+template <int D, int H, bool MULTI, int FAMS, bool STEP0, bool GROUPED, bool IG>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWDS_WPE))) gns_bwds_sweep_kernel(GnsBwdsArgs A) {
   using C = GnsDims<D, H, MULTI>;
   static_assert(MULTI || FAMS == 7, "the single phi is reversed after all three L nets");
@@ -700,29 +732,265 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
 #endif
       };
       if constexpr (MULTI) {
-        if constexpr (HAS_M) { if (!lastk) { fresh(); lm.template bus<false, STEP0>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS); fresh(); pm.template bus<STEP0>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); } }
-        if constexpr (HAS_T) { fresh(); lt.template bus<false, STEP0>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS); fresh(); pt.template bus<STEP0>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); }
+        if constexpr (HAS_M) { if (!lastk) { fresh(); lm.template bus<false, STEP0, IG>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS); fresh(); pm.template bus<STEP0, IG>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); } }
+        if constexpr (HAS_T) { fresh(); lt.template bus<false, STEP0, IG>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS); fresh(); pt.template bus<STEP0, IG>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); }
         // v moves only on buses without a generator (main.py:184-186): on a generator bus the upstream of L_v is exactly zero, and with
         // it every adjoint and every weight-gradient term of L_v and of phi_v over the lines ending there - the bus is skipped (the
         // topology is the same for all 64 grids of the wave, so the branch is uniform).  46 % of case118's buses carry a generator.
-        if constexpr (HAS_V) { if (!is_gen[n]) { fresh(); lv.template bus<false, STEP0>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS); fresh(); pv.template bus<STEP0>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); } }
+        if constexpr (HAS_V) { if (!is_gen[n]) { fresh(); lv.template bus<false, STEP0, IG>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS); fresh(); pv.template bus<STEP0, IG>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); } }
       } else {
 #pragma unroll
         for (int j = 0; j < H / 2; ++j) gS[j] = f2{0.f, 0.f};
-        if (!lastk) { fresh(); lm.template bus<true, STEP0>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS); }
-        fresh(); lt.template bus<true, STEP0>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS);
-        if (!is_gen[n]) { fresh(); lv.template bus<true, STEP0>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS); }     // (a generator bus: L_v's upstream is zero, see above)
-        fresh(); pm.template bus<STEP0>(A, rec, lane, xs, gS, macc, p0, p1, row_ein);
+        if (!lastk) { fresh(); lm.template bus<true, STEP0, IG>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS); }
+        fresh(); lt.template bus<true, STEP0, IG>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS);
+        if (!is_gen[n]) { fresh(); lv.template bus<true, STEP0, IG>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS); }     // (a generator bus: L_v's upstream is zero, see above)
+        fresh(); pm.template bus<STEP0, IG>(A, rec, lane, xs, gS, macc, p0, p1, row_ein);
       }
       if constexpr (!step0) {
         *row_ptr(A.adj, ar + 1 + SLOT, lane) = xsum;
         store_pairs<D>(A.adj, ar + 4 + (par * 3 + SLOT) * MQ, lane, macc);
+      } else if constexpr (IG) {
+        *row_ptr(A.adj, ar + 1 + SLOT, lane) = xsum;     // (v, theta, dp, dq)_0 adjoints of this kernel's families
       }
     }
   }
   if constexpr (HAS_M) { if (!lastk) lm.flush(A, lane, slab); if (MULTI ? !lastk : true) pm.flush(A, lane, slab); }
   if constexpr (HAS_T) { lt.flush(A, lane, slab); if constexpr (MULTI) pt.flush(A, lane, slab); }
   if constexpr (HAS_V) { lv.flush(A, lane, slab); if constexpr (MULTI) pv.flush(A, lane, slab); }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Input gradients (gns_backward_inputs).  A.igrad holds the adjoints of the packed input rows (gns_common.h, same [G][row][64] layout as
+// the packed inputs), zeroed before the first reverse step and only ever added to, one reverse step after the other.
+//
+// gns_bwds_igrad_phys_kernel runs after gns_bwds_phys_kernel of reverse step k, whose gather left (vbar, thbar, dpbar) of every bus in
+// the adjoint row.  It reverses global_active_compensation / local_power_imbalance (main.py:34-104) of step k once more, this time with
+// respect to the inputs: Pd, Gs, the per-bus Pmin/Pset/Pmax sums, the per-grid sums and the line parameters gathered by the
+// bus-id-as-line-index quirk (y, tau, shift at line src[e] in the in-edge row, at line dst[e] in the out-edge row).  delta_q carries
+// no gradient for k >= 0 (identically zero, main.py:64-76 vs :83,98-103), so Qd, Bs and b only reach the inputs through step 0's
+// initial state and the phi nets.  It also completes the adjoint of v on generator buses: the split backward drops the line terms
+// there (v never moves, main.py:184-186), the input gradient of vg needs them, summed over every step (row 3n+2 .z).
+// Same bus / line partitions and the same summation order of the lambda adjoint as gns_bwds_phys_kernel.
+__global__ void __launch_bounds__(GNS_BWDS_PHYS_THREADS) gns_bwds_igrad_phys_kernel(GnsBwdsArgs A) {
+  __shared__ float red[GNS_BWDS_PHYS_WAVES * GNS_LANES];
+  constexpr int W = GNS_BWDS_PHYS_WAVES;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int N = A.N, E = A.E, k = A.k;
+  cip topo = (cip)A.topo;
+  const long long g = blockIdx.x;
+  constexpr int pidx = 4;
+  const cip in_ptr = topo + topo[TH_IN_PTR], out_ptr = topo + topo[TH_OUT_PTR], q2p = topo + topo[TH_Q2P], is_gen = topo + topo[TH_IS_GEN],
+            part = topo + topo[TH_PART] + pidx * (GNS_MAXP + 1), epart = topo + topo[TH_EPART] + pidx * (GNS_MAXP + 1);
+  const int n0 = part[wave], n1 = part[wave + 1];
+  const int e0 = epart[wave], e1 = epart[wave + 1];
+  const long long R = gns_in_rows(N, E);
+  const float* IN = A.in;
+  float* IG = A.igrad;
+  const long long in_base = g * R, row_ein = in_base + 3LL * N, row_eout = row_ein + 3LL * E, row_grid = row_eout + E;
+  const int RB = A.RB, RBA = A.RBA;
+  auto state_row = [&](int n) { return (((long long)(k + 1) * A.G + g) * N + n) * RB; };
+  auto adj_row = [&](int n) { return (g * N + n) * RBA; };
+  auto slot_ptr = [&](int j, int p) { return A.slots + ((g * 6 + j) * E + p) * GNS_LANES + lane; };
+  const f4 gsum = *row_ptr(IN, row_grid, lane);
+  const f2 lamv = reinterpret_cast<const f2*>(A.lam)[((long long)k * A.G + g) * GNS_LANES + lane];
+  const float lam = lamv.x;
+  const int bits = (int)lamv.y;
+  const bool low1 = bits & 1, low2 = bits & 2;
+
+  // the lambda adjoint, summed exactly as gns_bwds_phys_kernel sums it (dpbar is unchanged by its gather)
+  float lb = 0.f;
+  for (int n = n0; n < n1; ++n) {
+    const float dpb = row_ptr(A.adj, adj_row(n), lane)->z;
+    const f4 b1 = *row_ptr(IN, in_base + 3LL * n + 1, lane);
+    lb += dpb * (low2 ? 2.f * (b1.y - b1.x) : 2.f * (b1.z - b1.y));
+  }
+  red[wave * GNS_LANES + lane] = lb;
+  __syncthreads();
+  float lbar = 0.f;
+#pragma unroll
+  for (int w = 0; w < W; ++w) lbar += red[w * GNS_LANES + lane];
+  const float pgbar = lbar / (low1 ? 2.f * (gsum.y - gsum.z) : 2.f * (gsum.w - gsum.y));
+
+  // buses: dp0 = sum Pg_new - Pd - Gs v^2 (main.py:81-82), p_global = sum Pd + sum Gs v^2 + p_joule (:45), Pg_new per bus (:53-57)
+  for (int n = n0; n < n1; ++n) {
+    const float dpb = row_ptr(A.adj, adj_row(n), lane)->z;
+    const float v = row_ptr(A.state, state_row(n), lane)->x;
+    f4* r0 = row_ptr(IG, in_base + 3LL * n, lane);
+    f4* r1 = row_ptr(IG, in_base + 3LL * n + 1, lane);
+    const f4 o0 = *r0, o1 = *r1;
+    *r0 = f4{o0.x - dpb, o0.y, o0.z + (pgbar - dpb) * (v * v), o0.w};
+    const f4 dpg = low2 ? f4{dpb * (1.f - 2.f * lam), dpb * (2.f * lam), 0.f, 0.f}                 // Pmin + 2 (Pset - Pmin) lambda
+                        : f4{0.f, dpb * (2.f - 2.f * lam), dpb * (2.f * lam - 1.f), 0.f};          // 2 Pset - Pmax + 2 (Pmax - Pset) lambda
+    *r1 = f4{o1.x + dpg.x, o1.y + dpg.y, o1.z + dpg.z, o1.w};
+  }
+  if (wave == 0) {     // per-grid sums: lambda (main.py:47-51) and sum Pd of p_global
+    f4* rg = row_ptr(IG, row_grid, lane);
+    const f4 o = *rg;
+    const f4 d = low1 ? f4{pgbar, pgbar * (-2.f * lam), pgbar * (2.f * lam - 1.f), 0.f}
+                      : f4{pgbar, pgbar * (2.f * lam - 2.f), 0.f, pgbar * (1.f - 2.f * lam)};
+    *rg = f4{o.x + d.x, o.y + d.y, o.z + d.z, o.w + d.w};
+  }
+
+  // lines: the "from" expressions read (y, tau, shift) of line s = src[e] (in-edge row), the "to" expression those of line t = dst[e]
+  const cip erec = topo + topo[TH_EREC];
+  for (int p = e0; p < e1; ++p) {
+    const gns_i8v r = *reinterpret_cast<const __attribute__((address_space(4))) gns_i8v*>(erec + 8 * p);
+    const int s = r[0], t = r[1], ia = r[2], ib = r[3], q = r[4], ic = r[5], id = r[6];
+    const f4 e1v = *row_ptr(IN, row_ein + 3LL * p + 1, lane);                  // shift_e, y_s, tau_s, sh_s
+    const f4 o0 = *row_ptr(IN, row_eout + q, lane);                            // y_t, tau_t, sh_t, b_t
+    const f4 ss = *row_ptr(A.state, state_row(s), lane), st = *row_ptr(A.state, state_row(t), lane);
+    const float vs = ss.x, ths = ss.y, vt = st.x, tht = st.y;
+    const float tha = row_ptr(A.state, state_row(ia), lane)->y, thb = row_ptr(A.state, state_row(ib), lane)->y;
+    const float thc = row_ptr(A.state, state_row(ic), lane)->y, thd = row_ptr(A.state, state_row(id), lane)->y;
+    const float Fb = row_ptr(A.adj, adj_row(t), lane)->z, Tb = row_ptr(A.adj, adj_row(s), lane)->z;
+    const float ys = e1v.y, taus = e1v.z, shs = e1v.w;
+    const float dl = tha - thb, dl2 = thd - thc;
+    float sA, cA, sB, cB, sD, cD, sC, cC, sD2, cD2;
+    sincosf(ths - tht - dl - shs, &sA, &cA);
+    sincosf(tht - ths - dl + shs, &sB, &cB);
+    sincosf(dl, &sD, &cD);
+    sincosf(tht - ths - dl2 - o0.z, &sC, &cC);
+    sincosf(dl2, &sD2, &cD2);
+    const float yot = ys / taus, yot2 = ys / (taus * taus);
+    const float base = vs * vt * yot;
+    const float kJ = vs * yot2 + vt * vt * ys;
+    const float inner = base * (sA + sB) + kJ * sD;
+    const float Jb = pgbar * (inner > 0.f ? 1.f : (inner < 0.f ? -1.f : 0.f));
+    // d/d(y_s, tau_s, sh_s) of p_from (main.py:91) and of |joule| (main.py:41)
+    const float ybs = Fb * (vs * vt / taus * sA + vs * vs / (taus * taus) * sD) + Jb * (vs * vt / taus * (sA + sB) + (vs / (taus * taus) + vt * vt) * sD);
+    const float tbs = -(Fb * (base * sA + 2.f * vs * vs * yot2 * sD) + Jb * (base * (sA + sB) + 2.f * vs * yot2 * sD)) / taus;
+    const float sbs = Jb * base * cB - (Fb + Jb) * base * cA;
+    // d/d(y_t, tau_t, sh_t) of p_to (main.py:92)
+    const float yot_t = o0.x / o0.y;
+    const float base2 = vt * vs * yot_t;
+    const float ybt = Tb * (vt * vs / o0.y * sC + vt * vt * sD2);
+    const float tbt = -Tb * base2 * sC / o0.y;
+    const float sbt = -Tb * base2 * cC;
+    f4* rs = row_ptr(IG, row_ein + 3LL * p + 1, lane);
+    f4* rt = row_ptr(IG, row_eout + q, lane);
+    const f4 os = *rs, ot = *rt;
+    *rs = f4{os.x, os.y + ybs, os.z + tbs, os.w + sbs};
+    *rt = f4{ot.x + ybt, ot.y + tbt, ot.z + sbt, ot.w};
+    // d/dv of the generator-bus ends, which gns_bwds_phys_kernel does not store (its slots 0 / 1 of the other ends stay as they are)
+    const bool gs = is_gen[s] != 0, gt = is_gen[t] != 0;
+    if (gs || gt) {
+      float dvs = Fb * (vt * yot * sA + 2.f * vs * yot2 * sD) + Jb * (vt * yot * (sA + sB) + yot2 * sD);
+      float dvt = Fb * (vs * yot * sA) + Jb * (vs * yot * (sA + sB) + 2.f * vt * ys * sD);
+      dvt += Tb * (vs * yot_t * sC + 2.f * vt * o0.x * sD2);
+      dvs += Tb * (vt * yot_t * sC);
+      if (gs) *slot_ptr(0, p) = dvs;
+      if (gt) *slot_ptr(1, p) = dvt;
+    }
+  }
+  __syncthreads();
+  // generator buses: the line terms of d/dv, in-edges then out-edges in list order, into the adjoint of v_0 (row 3n+2 .z)
+  for (int n = n0; n < n1; ++n) {
+    if (!is_gen[n]) continue;
+    float dv = 0.f;
+    for (int p = in_ptr[n]; p < in_ptr[n + 1]; ++p) dv += *slot_ptr(1, p);
+    for (int qq = out_ptr[n]; qq < out_ptr[n + 1]; ++qq) dv += *slot_ptr(0, q2p[qq]);
+    f4* r2 = row_ptr(IG, in_base + 3LL * n + 2, lane);
+    const f4 o2 = *r2;
+    *r2 = f4{o2.x, o2.y, o2.z + dv, o2.w};
+  }
+}
+
+// gns_bwds_igrad_unpack_kernel: the reverse of gns_pack_inputs_kernel, after reverse step 0.  One wave per unit (lane = grid): bus n
+// (and the generators on it), or in-edge p (line e = in_eid[p]).  It closes the initial state (main.py:144-152) with the step-0 X rows
+// and the adjoint row, applies the derivatives of the per-bus generator sums, the per-grid sums, where(v == 0, 1, v) and
+// y = 1/sqrt(r^2 + x^2), and adds (+=) into the caller's [Bt,N,6] / [Bt,E,7] / [Bt,Gn,7].  Dead lanes write nothing.
+__global__ void __launch_bounds__(64) gns_bwds_igrad_unpack_kernel(GnsBwdsArgs A, const float* __restrict__ buses, const float* __restrict__ lines,
+                                                                   const float* __restrict__ gens, int Gn, float* __restrict__ gbu,
+                                                                   float* __restrict__ gli, float* __restrict__ gge) {
+  const int lane = threadIdx.x;
+  const long long g = blockIdx.x;
+  const int u = blockIdx.y;
+  const int N = A.N, E = A.E, K = A.K;
+  const long long b = g * GNS_LANES + lane;
+  if (b >= A.Bt) return;
+  cip topo = (cip)A.topo;
+  const long long R = gns_in_rows(N, E);
+  const float* IG = A.igrad;
+  const long long in_base = g * R, row_ein = in_base + 3LL * N, row_eout = row_ein + 3LL * E, row_grid = row_eout + E;
+  const f4 gs = *row_ptr(IG, row_grid, lane);            // adjoints of (sum Pd, sum Pset, sum Pmin, sum Pmax)
+  if (u < N) {
+    const int n = u;
+    const long long ar = (g * N + n) * A.RBA;
+    const f4 a0 = *row_ptr(A.adj, ar, lane);               // (vbar of v_1, ...) after reverse step 0
+    // the X rows step 0's sweeps wrote, summed as gns_bwds_phys_kernel's Pb-0 sums them (slot 2 of step 0 exists in mode 2 or when K > 1)
+    const int mode = A.mode;
+    const bool x2_live = mode == 2 || 0 < K - 1;
+    const f4 x0 = *row_ptr(A.adj, ar + 1, lane), x1 = *row_ptr(A.adj, ar + 2, lane), x2 = *row_ptr(A.adj, ar + 3, lane);
+    f4 xs;
+    if (mode == 2) xs = x2;
+    else if (mode == 1) xs = x2_live ? x2 + x0 : x0;
+    else xs = x2_live ? (x2 + x0) + x1 : x0 + x1;
+    const f4 r0 = *row_ptr(IG, in_base + 3LL * n, lane), r1 = *row_ptr(IG, in_base + 3LL * n + 1, lane),
+             r2 = *row_ptr(IG, in_base + 3LL * n + 2, lane);
+    const float* bu = buses + b * (long long)N * 6 + n * 6;
+    const float* ge = gens + b * (long long)Gn * 7;
+    const float Gs = bu[4], Bs = bu[5];
+    const int q0 = topo[topo[TH_GEN_PTR] + n], q1 = topo[topo[TH_GEN_PTR] + n + 1];
+    float vg = 0.f;
+    for (int q = q0; q < q1; ++q) vg += ge[topo[topo[TH_GEN_IDX] + q] * 7 + 4];          // the sum gns_pack_inputs_kernel formed
+    const float v0 = (vg == 0.f) ? 1.f : vg;
+    const float dp0b = xs.z, dq0b = xs.w;
+    // dp_0 = sum Pg - Pd - Gs v0^2, dq_0 = sum qg - Qd + Bs v0^2 (main.py:149-152); v stays v_0 on a generator bus (main.py:184-186)
+    const float v0b = a0.x + xs.x + r2.z - 2.f * Gs * v0 * dp0b + 2.f * Bs * v0 * dq0b;
+    const float vgb = (vg == 0.f) ? 0.f : v0b;                                             // where(v == 0, 1, v)  main.py:147
+    if (gbu) {
+      float* o = gbu + b * (long long)N * 6 + n * 6;
+      o[2] += (r0.x + gs.x) - dp0b;
+      o[3] += r0.y - dq0b;
+      o[4] += r0.z - dp0b * (v0 * v0);
+      o[5] += r0.w + dq0b * (v0 * v0);
+    }
+    if (gge) {
+      for (int q = q0; q < q1; ++q) {
+        float* o = gge + b * (long long)Gn * 7 + topo[topo[TH_GEN_IDX] + q] * 7;
+        o[1] += r1.z + gs.w;            // Pmax
+        o[2] += r1.x + gs.z;            // Pmin
+        o[3] += r1.y + gs.y;            // Pg_set
+        o[4] += vgb;
+        o[5] += dq0b;
+        o[6] += dp0b;
+      }
+    }
+    return;
+  }
+  const int p = u - N;
+  if (p >= E || !gli) return;
+  const int e = topo[topo[TH_IN_EID] + p];
+  const f4 f0 = *row_ptr(IG, row_ein + 3LL * p, lane), f1 = *row_ptr(IG, row_ein + 3LL * p + 1, lane);
+  float yb = 0.f, tb = 0.f, sb = 0.f;
+  if (e < N) {         // line NUMBER e as the reference gathers it: at the lines leaving bus e (y_s ...) and those entering it (y_t ...)
+    const cip out_ptr = topo + topo[TH_OUT_PTR], in_ptr = topo + topo[TH_IN_PTR], q2p = topo + topo[TH_Q2P], p2q = topo + topo[TH_P2Q];
+    for (int q = out_ptr[e]; q < out_ptr[e + 1]; ++q) { const f4 s = *row_ptr(IG, row_ein + 3LL * q2p[q] + 1, lane); yb += s.y; tb += s.z; sb += s.w; }
+    for (int pp = in_ptr[e]; pp < in_ptr[e + 1]; ++pp) { const f4 t = *row_ptr(IG, row_eout + p2q[pp], lane); yb += t.x; tb += t.y; sb += t.z; }
+  }
+  const float* li = lines + b * (long long)E * 7 + e * 7;
+  const float r = li[2], x = li[3];
+  const float y = __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(__fmul_rn(r, r), __fmul_rn(x, x))));
+  const float y3 = y * y * y;                                                                 // dy/dr = -r y^3, dy/dx = -x y^3
+  float* o = gli + b * (long long)E * 7 + e * 7;
+  o[2] += f0.x - r * y3 * yb;
+  o[3] += f0.y - x * y3 * yb;
+  o[4] += f0.z;
+  o[5] += f0.w + tb;
+  o[6] += f1.x + sb;
+}
+
+int gns_launch_bwds_igrad_phys(const GnsBwdsArgs& A, hipStream_t st) {
+  hipLaunchKernelGGL(gns_bwds_igrad_phys_kernel, dim3((unsigned)A.G), dim3(GNS_BWDS_PHYS_THREADS), 0, st, A);
+  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+}
+
+int gns_launch_bwds_igrad_unpack(const GnsBwdsArgs& A, const float* buses, const float* lines, const float* gens, int Gn,
+                                 float* grad_buses, float* grad_lines, float* grad_gens, hipStream_t st) {
+  hipLaunchKernelGGL(gns_bwds_igrad_unpack_kernel, dim3((unsigned)A.G, (unsigned)(A.N + A.E)), dim3(64), 0, st, A, buses, lines, gens, Gn,
+                     grad_buses, grad_lines, grad_gens);
+  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
 }
 
 int gns_bwds_supported(int d, int h, int multi) {
@@ -749,9 +1017,12 @@ int gns_launch_bwds_phys(const GnsBwdsArgs& A, size_t lds, hipStream_t st) {
 int gns_launch_bwds_sweep(int d, int h, int multi, const GnsBwdsArgs& A, hipStream_t st) {
   const long long GB = (A.G + A.R - 1) / A.R;
   const unsigned blocks = (unsigned)(GB * A.C);
-#define GNS_SWEEP1(DD, HH, MM, FAMS, GR) do { if (A.k == 0) hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, true, GR>), dim3(blocks), dim3(64), 0, st, A); \
-                                             else hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, false, GR>), dim3(blocks), dim3(64), 0, st, A); } while (0)
-#define GNS_SWEEP(DD, HH, MM, FAMS) do { if (A.group_topo) GNS_SWEEP1(DD, HH, MM, FAMS, true); else GNS_SWEEP1(DD, HH, MM, FAMS, false); } while (0)
+#define GNS_SWEEP1(DD, HH, MM, FAMS, GR, IG) do { if (A.k == 0) hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, true, GR, IG>), dim3(blocks), dim3(64), 0, st, A); \
+                                                 else hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, false, GR, IG>), dim3(blocks), dim3(64), 0, st, A); } while (0)
+  // (input gradients are not offered on grouped calls: gns_api.hip never sets both)
+#define GNS_SWEEP(DD, HH, MM, FAMS) do { if (A.group_topo) GNS_SWEEP1(DD, HH, MM, FAMS, true, false); \
+                                         else if (A.igrad) GNS_SWEEP1(DD, HH, MM, FAMS, false, true); \
+                                         else GNS_SWEEP1(DD, HH, MM, FAMS, false, false); } while (0)
 #define GNS_CASE(DD, HH)                                                                                                    \
   if (d == DD && h == HH) {                                                                                                 \
     if (!multi) { if (A.mode != 2) return GNS_EINVAL; GNS_SWEEP(DD, HH, false, 7); }                                        \

@@ -110,9 +110,13 @@ struct GnsBwdsArgs {
   int mode;                // sweep kernels per step: 0 {m}{theta}{v}, 1 {m}{theta+v}, 2 {m+theta+v} (gns_backward_split.hip)
   const int* group_topo;   // grouped call: as in GnsFwdArgs (NULL: one topology)
   const int* slot_grid;
+  float* igrad;            // input gradients (gns_backward_inputs): adjoints of the packed input rows, [G][gns_in_rows][64] float4; NULL: none
 };
 int gns_bwds_supported(int d, int h, int multi);
 size_t gns_bwds_phys_lds(int N, int* use_plane);
 int gns_launch_bwds_phys(const GnsBwdsArgs& A, size_t lds, hipStream_t st);
 int gns_launch_bwds_sweep(int d, int h, int multi, const GnsBwdsArgs& A, hipStream_t st);
+int gns_launch_bwds_igrad_phys(const GnsBwdsArgs& A, hipStream_t st);
+int gns_launch_bwds_igrad_unpack(const GnsBwdsArgs& A, const float* buses, const float* lines, const float* gens, int Gn,
+                                 float* grad_buses, float* grad_lines, float* grad_gens, hipStream_t st);
 int gns_bwds_init_device();

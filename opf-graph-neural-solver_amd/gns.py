@@ -200,9 +200,10 @@ class _GNSFunction(torch.autograd.Function):
         cfg = mod._config(N, lines.shape[1], gens.shape[1])
         dev = buses.device
         need_grad = bool(want_grad)                     # evaluation (torch.no_grad()) keeps 2 state slots and saves nothing for a backward
+        save = int(want_grad)                           # 0 evaluation, 1 saved for a backward, 2 saved for one that returns input gradients
         ctx.set_materialize_grads(False)                # unused outputs (v, theta, last_loss) arrive as None in backward, not as zero-filled tensors
         fwd_b, bwd_b = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(lib.gns_workspace_bytes(ctypes.byref(cfg), Bt, int(need_grad), ctypes.byref(fwd_b), ctypes.byref(bwd_b)),
+        _check(lib.gns_workspace_bytes(ctypes.byref(cfg), Bt, save, ctypes.byref(fwd_b), ctypes.byref(bwd_b)),
                'gns_workspace_bytes')
         ws = _workspace(fwd_b.value, dev)
         v = torch.empty((Bt, N), dtype=torch.float32, device=dev)
@@ -212,22 +213,23 @@ class _GNSFunction(torch.autograd.Function):
         flat = mod._exec_flat(dev)                       # the parameters themselves, or their device mirror for a CPU-resident model
         with torch.cuda.device(dev):                     # the launch must land on the tensors' device, whatever the current device is
             stream = torch.cuda.current_stream(dev).cuda_stream
-            packed = mod._packed_inputs(lib, cfg, topo, buses, lines, gens, stream, need_grad)
+            packed = mod._packed_inputs(lib, cfg, topo, buses, lines, gens, stream, save)
             _check(lib.gns_forward(ctypes.byref(cfg), topo.blob.data_ptr(), flat.data_ptr(), buses.data_ptr(), lines.data_ptr(),
                                    gens.data_ptr(), Bt, None if packed is None else packed.data_ptr(),
                                    v.data_ptr(), theta.data_ptr(), total.data_ptr(), last.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), int(need_grad), stream), 'gns_forward')
+                                   ws.data_ptr(), ws.numel(), save, stream), 'gns_forward')
         # Teams of workgroups (lane-per-grid kernels on a batch that leaves CUs idle) can give up at a barrier when another kernel
         # holds a partner's CU: the losses are then NaN and the workspace carries a status word.  A training call is checked before
         # its backward is launched (no gradient of invalid losses reaches an optimiser); an evaluation call at the next call of
         # the module or by ``GNS.check_status()``.
         off = ctypes.c_size_t()
-        _check(lib.gns_team_status_offset(ctypes.byref(cfg), Bt, int(need_grad), ctypes.byref(off)), 'gns_team_status_offset')
+        _check(lib.gns_team_status_offset(ctypes.byref(cfg), Bt, save, ctypes.byref(off)), 'gns_team_status_offset')
         uses_teams = off.value != ctypes.c_size_t(-1).value
         ctx.team_status = uses_teams and need_grad
         if uses_teams and not need_grad and not torch.cuda.is_current_stream_capturing():
             mod.__dict__['_pending_status'] = (cfg, Bt, ws, dev)
         if need_grad:
+            ctx.save = save
             ctx.cfg, ctx.topo, ctx.ws, ctx.flat, ctx.Bt, ctx.bwd_bytes = cfg, topo, ws, flat, Bt, bwd_b.value
             ctx.params = params
             ctx.mod_flat = mod._flat
@@ -250,8 +252,7 @@ class _GNSFunction(torch.autograd.Function):
             raise GNSError('buses / lines / generators were modified in place between forward and backward')
         dev = flat.device
         if ctx.team_status and not torch.cuda.is_current_stream_capturing():     # (the check synchronises: not inside a graph capture)
-            _raise_if_team_failed(lib, ctx.cfg, ctx.Bt, ctx.ws, 1, dev)
-        grad = torch.zeros_like(flat)
+            _raise_if_team_failed(lib, ctx.cfg, ctx.Bt, ctx.ws, ctx.save, dev)
         bws = _workspace(ctx.bwd_bytes, dev)
 
         def ptr(t):
@@ -259,6 +260,9 @@ class _GNSFunction(torch.autograd.Function):
 
         keep = [t.to(dev).contiguous() if t is not None else None for t in (gtot, glast, gv, gth)]
         bu, li_, ge = ctx.inputs
+        if ctx.save == 2:
+            return _input_backward(ctx, lib, bws, keep, dev)
+        grad = torch.zeros_like(flat)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             _check(lib.gns_backward(ctypes.byref(ctx.cfg), ctx.topo.blob.data_ptr(), flat.data_ptr(), bu.data_ptr(), li_.data_ptr(),
@@ -272,6 +276,29 @@ class _GNSFunction(torch.autograd.Function):
                 raise GNSError('a team of workgroups gave up at a barrier of the backward kernel: no gradient is delivered '
                                '(opf_graph_neural_solver_amd.set_option("team", 1) or the default bwd_variant 4 run without teams)')
         return (None, None, None, None, None, None, *_param_grads(ctx, grad))
+
+
+def _input_backward(ctx, lib, bws, keep, dev):
+    """The backward of a forward saved with save_state 2: ``gns_backward_inputs`` delivers the input gradients asked for by
+    ``ctx.needs_input_grad`` (in the layout of the tensors the kernels ran on: autograd carries them back through ``.to``, the column
+    map and ``unsqueeze``) and the parameter gradient only when a parameter requires grad (a frozen model: NULL, no dW reduction)."""
+    nig = ctx.needs_input_grad
+    bu, li_, ge = ctx.inputs
+    gin = [torch.zeros_like(t) if need else None for t, need in zip((bu, li_, ge), nig[3:6])]
+    want_p = any(nig[6:])
+    grad = torch.zeros_like(ctx.flat) if want_p else None
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib.gns_backward_inputs(ctypes.byref(ctx.cfg), ctx.topo.blob.data_ptr(), ctx.flat.data_ptr(), bu.data_ptr(), li_.data_ptr(),
+                                       ge.data_ptr(), ctx.Bt, None if ctx.packed is None else ctx.packed.data_ptr(), ctx.ws.data_ptr(),
+                                       ctx.ws.numel(), ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(keep[3]), ptr(grad),
+                                       ptr(gin[0]), ptr(gin[1]), ptr(gin[2]), bws.data_ptr(), bws.numel(), stream), 'gns_backward_inputs')
+    pgrads = _param_grads(ctx, grad) if want_p else [None] * len(ctx.shapes)
+    return (None, None, None, gin[0], gin[1], gin[2], *pgrads)
 
 
 def _param_grads(ctx, grad):
@@ -697,9 +724,16 @@ class GNS(nn.Module):
         topo = self._topology(lines, generators, buses.shape[1])
         # whether a backward pass can follow is decided HERE: inside Function.forward grad mode is always off, and
         # ctx.needs_input_grad ignores torch.no_grad()
-        want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        if self.flat_grad and want_grad and params[0].device.type == 'cuda':
+        want_params = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        # input gradients (d loss / d buses, lines, generators, as the reference's autograd gives them): the forward saves for
+        # gns_backward_inputs (save_state 2)
+        want_inputs = torch.is_grad_enabled() and (buses.requires_grad or lines.requires_grad or generators.requires_grad)
+        want_grad = 2 if want_inputs else int(want_params)
+        if self.flat_grad and want_params and params[0].device.type == 'cuda':
             params = [self.flat_leaf()]                     # one differentiable input: the gradient comes back as one tensor
+        if want_inputs and isinstance(topo, _TopologyGroups):
+            raise ValueError('gradients with respect to buses / lines / generators are not available for a batch that mixes topologies '
+                             '(topology_check = \'group\'): call the model once per topology')
         fn = _GNSGroupedFunction if isinstance(topo, _TopologyGroups) else _GNSFunction
         v, theta, total, last = fn.apply(self, topo, want_grad, buses, lines, generators, *params)
         if in_dev != dev:

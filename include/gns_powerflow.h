@@ -1,0 +1,99 @@
+/* C-ABI of the batched Newton-Raphson AC power-flow solver (libgns_hip.so).
+ *
+ * The reference evaluates a trained GNS against PYPOWER's runpf(PF_ALG=1) (GNS/evaluate.py:24-40), one grid at a time on the
+ * CPU.  This solver produces that baseline on the device for a whole batch that shares one topology: the sparse structure of the
+ * Jacobian and of its LU factor is analysed ONCE on the host (gns_pf_prepare_topology), and every grid then runs the same
+ * elimination program; only the values differ.  Conventions are those of gns_hip.h: plain pointers, caller-owned device memory,
+ * GNS_E* return codes (the enum of gns_hip.h), work enqueued on the caller's stream, no allocation and no host synchronisation
+ * inside gns_pf_solve.
+ *
+ * Semantics
+ *   Inputs: buses [Bt,N,6], lines [Bt,E,7], generators [Bt,Gn,7], fp32, the layout GNS.forward takes (GNS/utils.py:4-13): powers in
+ *   per unit, the line shift in radians, tau used as given.  The id columns are those the topology was prepared from.
+ *   Bus roles: the slack is given to the analysis; PV = every other bus with at least one generator; PQ = every remaining bus.
+ *   Y-bus (MATPOWER makeYbus): per line (f, t, r, x, b, tau, phi), y_s = 1/(r + jx), a = tau e^{j phi}:
+ *     Y_ff += (y_s + jb/2)/tau^2,  Y_tt += y_s + jb/2,  Y_ft += -y_s/conj(a),  Y_tf += -y_s/a;  parallel lines add;
+ *     Y_ii += Gs + jBs.
+ *   Specified injections: S_i = sum of Pg (generator column 6) on bus i - Pd_i - j Qd_i (generator qg is not used).
+ *   Newton-Raphson in polar form (MATPOWER newtonpf): unknowns theta at PV+PQ, |V| at PQ;
+ *     F = [Re(V conj(YV) - S) at PV+PQ ; Im(...) at PQ].
+ *   Start: |V| = vg of the first generator listed on each PV / slack bus (1 on a slack without generators), 1 at PQ buses, theta 0.
+ *   Warm start (v0, theta0 [Bt,N] fp64, both or neither): |V| at PQ buses from v0, theta = theta0 - theta0[slack].
+ *   ||F||_inf < tol is tested before every update; iterations = updates applied, at most max_iter.  theta_slack stays 0.
+ *   Arithmetic: fp64 throughout (Y-bus, mismatch, Jacobian, factorisation, update).
+ *   Failure is per grid: a zero or non-finite pivot, a non-finite mismatch or a non-finite iterate stops that grid with
+ *   converged = 0; v / theta then hold its last finite iterate and mismatch the norm there (NaN when the mismatch itself is not
+ *   finite).  No float atomics: a grid's results are bit-identical alone or in any batch, and from run to run.
+ *
+ * Outputs: v, theta [Bt,N] fp64; converged [Bt] uint8 (0/1); iterations [Bt] int32; mismatch [Bt] fp64 (the final ||F||_inf).
+ *
+ * Kernel: one wave per grid, the grid's LU factor, right-hand side and bus state in LDS (gns_powerflow.hip).  A topology whose
+ * LDS image (gns_pf_info.lds_bytes = 8 * (nnz(L+U) + dim + 8 N) bytes) exceeds GNS_PF_LDS_MAX_BYTES is refused by gns_pf_solve
+ * with GNS_EUNSUPPORTED.
+ */
+#ifndef GNS_POWERFLOW_H
+#define GNS_POWERFLOW_H
+#include <stddef.h>
+#include <stdint.h>
+
+#include "gns_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The LDS one workgroup may use on gfx950 (160 KiB): the limit of a topology's LDS image. */
+#define GNS_PF_LDS_MAX_BYTES 163840
+
+typedef struct gns_pf_config {
+  int32_t n_bus;     /* N  */
+  int32_t n_line;    /* E  */
+  int32_t n_gen;     /* Gn */
+  int32_t max_iter;  /* Newton updates at most (MATPOWER: 10)  */
+  double  tol;       /* ||F||_inf convergence bound (MATPOWER: 1e-8) */
+} gns_pf_config;
+
+/* What the analysis of a topology found (read from a HOST copy of the blob). */
+typedef struct gns_pf_info {
+  int32_t n_bus, n_line, n_gen;
+  int32_t slack;      /* 0-based */
+  int32_t n_pv, n_pq;
+  int32_t dim;        /* Jacobian dimension = (N - 1) + n_pq */
+  int32_t nnz_jac;    /* structural nonzeros of the Jacobian */
+  int32_t nnz_lu;     /* nonzeros of L + U (unit diagonal of L not stored) under the fill-reducing ordering */
+  int32_t nnz_ybus;   /* structural nonzeros of the Y-bus */
+  int32_t n_ops;      /* elimination + triangular-solve operations per Newton iteration */
+  int32_t n_steps;    /* barrier-separated steps those operations are scheduled into */
+  int64_t lds_bytes;  /* LDS image of one grid; > GNS_PF_LDS_MAX_BYTES: gns_pf_solve returns GNS_EUNSUPPORTED */
+} gns_pf_info;
+
+/* Host analysis.  From 0-based f_bus / t_bus [E], generator bus [Gn] HOST arrays and the 0-based slack bus: bus roles, the Y-bus
+ * pattern with every line's four stamps, a minimum-degree ordering on the bus graph (the theta and |V| of a PQ bus kept together),
+ * the symbolic LU (structurally symmetric, no pivoting), the map of Jacobian entries to factor slots and the elimination +
+ * triangular-solve program in barrier-separated steps, in one relocatable int32 blob of gns_pf_topology_bytes() bytes.
+ * GNS_ETOPOLOGY: a bus id out of range, a slack that is not a bus, or a bus with no path of lines to the slack (an island: its
+ * theta is undetermined and the Jacobian structurally singular).  The program's length depends on the ids, so
+ * gns_pf_topology_bytes runs the analysis and reports the blob's exact size. */
+int gns_pf_topology_bytes(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                          const int32_t* gen_bus, int32_t slack, size_t* bytes);
+int gns_pf_prepare_topology(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                            const int32_t* gen_bus, int32_t slack, void* topo_host_out, size_t topo_bytes);
+int gns_pf_topology_info(const void* topo_host, gns_pf_info* info);
+
+/* Device workspace of a solve of Bt grids (the Y-bus values, 16 bytes per structural nonzero and grid). */
+int gns_pf_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
+
+/* Solve Bt grids.  topo_host: the host blob (sizes are read from it on the host); topo_dev: the same bytes on the device.
+ * v0 / theta0: NULL (flat start) or both [Bt,N] fp64.  stream: a hipStream_t passed as void*.
+ * GNS_EINVAL: a NULL pointer or a config that does not match the blob; GNS_ESIZE: workspace too small; GNS_EUNSUPPORTED: the
+ * topology's LDS image exceeds GNS_PF_LDS_MAX_BYTES. */
+int gns_pf_solve(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                 const float* buses, const float* lines, const float* generators, int64_t Bt,
+                 const double* v0, const double* theta0,
+                 double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* GNS_POWERFLOW_H */

@@ -21,8 +21,8 @@ _os.environ.setdefault('DEBUG_CLR_GRAPH_PACKET_CAPTURE', '0')
 from .gns import GNS, LearningBlock, get_BLG, GNSError
 from . import synth
 from . import dist
-from . import prepare, metrics, training
+from . import prepare, metrics, training, powerflow
 from .prepare import prepare_grids
 from ._lib import load_library, library_path, set_option, get_option
 
-__all__ = ['GNS', 'LearningBlock', 'get_BLG', 'GNSError', 'synth', 'dist', 'prepare', 'metrics', 'training', 'prepare_grids', 'load_library', 'library_path', 'set_option', 'get_option']
+__all__ = ['GNS', 'LearningBlock', 'get_BLG', 'GNSError', 'synth', 'dist', 'prepare', 'metrics', 'training', 'powerflow', 'prepare_grids', 'load_library', 'library_path', 'set_option', 'get_option']

@@ -16,6 +16,16 @@ class GnsConfig(ctypes.Structure):
                 ('gamma', ctypes.c_float)]
 
 
+class PfConfig(ctypes.Structure):
+    _fields_ = [('n_bus', ctypes.c_int32), ('n_line', ctypes.c_int32), ('n_gen', ctypes.c_int32), ('max_iter', ctypes.c_int32),
+                ('tol', ctypes.c_double)]
+
+
+class PfInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('n_bus', 'n_line', 'n_gen', 'slack', 'n_pv', 'n_pq', 'dim', 'nnz_jac', 'nnz_lu',
+                                              'nnz_ybus', 'n_ops', 'n_steps')] + [('lds_bytes', ctypes.c_int64)]
+
+
 def library_path():
     # GNS_LIB selects an alternative build (ablation / A-B timing runs); the default is the shipped library
     return os.environ.get('GNS_LIB') or os.path.join(_HERE, 'libgns_hip.so')
@@ -68,6 +78,14 @@ def load_library():
     lib.gns_profile_read.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
     lib.gns_set_option.argtypes = [ctypes.c_char_p, ctypes.c_int]
     lib.gns_get_option.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
+    pfcp = ctypes.POINTER(PfConfig)
+    lib.gns_pf_topology_bytes.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(sz)]
+    lib.gns_pf_prepare_topology.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, sz]
+    lib.gns_pf_topology_info.argtypes = [vp, ctypes.POINTER(PfInfo)]
+    lib.gns_pf_workspace_bytes.argtypes = [pfcp, vp, i64, ctypes.POINTER(sz)]
+    lib.gns_pf_solve.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    for f in PF_EXPORTS:
+        getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
               'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
               'gns_set_option', 'gns_get_option', 'gns_prepack_bytes', 'gns_prepack', 'gns_uses_packed_inputs', 'gns_adam_step',
@@ -83,6 +101,10 @@ EXPORTS = ('gns_version', 'gns_param_count', 'gns_config_supported', 'gns_topolo
            'gns_set_option', 'gns_get_option', 'gns_prepack_bytes', 'gns_prepack', 'gns_uses_packed_inputs', 'gns_adam_step',
            'gns_adam_step_dev', 'gns_team_status', 'gns_team_status_offset', 'gns_workspace_bytes_grouped', 'gns_forward_grouped',
            'gns_backward_grouped', 'gns_team_status_grouped', 'gns_team_status_offset_grouped')
+
+
+# the power-flow solver's C-ABI (include/gns_powerflow.h)
+PF_EXPORTS = ('gns_pf_topology_bytes', 'gns_pf_prepare_topology', 'gns_pf_topology_info', 'gns_pf_workspace_bytes', 'gns_pf_solve')
 
 
 def set_option(name: str, value: int) -> None:

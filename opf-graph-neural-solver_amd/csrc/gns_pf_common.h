@@ -1,0 +1,26 @@
+// Layout of the power-flow topology blob (include/gns_powerflow.h): a header of PF_HDR_WORDS int32 words, then int32 arrays at
+// the word offsets the header names.  Written by gns_pf_topology.cpp, read by gns_powerflow.hip.
+#pragma once
+#include <stdint.h>
+
+#define GNS_PF_MAGIC 0x47504631   // "GPF1"
+
+enum {
+  PH_MAGIC = 0, PH_TOTAL, PH_N, PH_E, PH_GN, PH_SLACK, PH_NPV, PH_NPQ, PH_DIM, PH_NNZJ, PH_NNZLU, PH_NNZY, PH_NOPS, PH_NSTEPS,
+  // word offsets of the arrays
+  PH_ROLE,       // [N]      0 PQ, 1 PV, 2 slack
+  PH_TH_IDX,     // [N]      position of the bus's theta unknown in the ordered system, -1 at the slack
+  PH_VM_IDX,     // [N]      position of its |V| unknown, -1 unless PQ
+  PH_GEN_PTR,    // [N+1]    generators of each bus ...
+  PH_GEN_IDX,    // [max(Gn,1)] ... in listing order
+  PH_Y_PTR,      // [N+1]    Y-bus rows (CSR, columns ascending, diagonal included)
+  PH_Y_COL,      // [nnzY]
+  PH_Y_DIAG,     // [N]      entry of the diagonal of each row
+  PH_ST_PTR,     // [nnzY+1] stamps adding into each entry ...
+  PH_ST,         // [4E]     ... as line * 4 + kind (0 ff, 1 tt, 2 ft, 3 tf), in line order
+  PH_JSLOT,      // [4 nnzY] factor slot of (dP/dtheta_k, dP/d|V|_k, dQ/dtheta_k, dQ/d|V|_k) of entry (i, k), -1 if not in J
+  PH_PIVOT,      // [dim]    factor slot of each pivot
+  PH_STEP_PTR,   // [nsteps+1] operations of each step ...
+  PH_OPS,        // [2 nops] ... as (dst | a << 16, b): F[dst] -= F[a] * F[b], or F[dst] /= F[a] when b == -1 (8-byte aligned)
+  PF_HDR_WORDS = 32
+};

@@ -1,0 +1,200 @@
+"""Batched Newton-Raphson AC power flow on the device: the baseline the reference evaluates a trained GNS against
+(PYPOWER ``runpf(PF_ALG=1)``, ``GNS/evaluate.py:24-40``), for a whole batch of grids that share one topology.
+
+    res = powerflow.newton_raphson(buses, lines, generators, slack_bus=1)
+    res.v, res.theta, res.converged, res.iterations, res.mismatch
+
+The semantics (bus roles, Y-bus, injections, starting point, convergence test, per-grid failure) are those of
+``include/gns_powerflow.h``; the solve runs in one HIP kernel (``csrc/gns_powerflow.hip``) in float64.  The sparse structure of
+the Jacobian and of its LU factor is analysed once per topology on the host (``csrc/gns_pf_topology.cpp``) and cached.
+"""
+from __future__ import annotations
+
+import ctypes
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import gns as _gns
+from ._lib import GNS_ERRORS, PfConfig, PfInfo, load_library
+
+PowerFlowResult = namedtuple('PowerFlowResult', ['v', 'theta', 'converged', 'iterations', 'mismatch'])
+
+_TOPO_CACHE = {}
+
+
+class PowerFlowTopology:
+    """Host analysis of one topology (the blob on the host and on the device) and what it found (``info``)."""
+
+    def __init__(self, host, dev):
+        self.host = host
+        self.blob = torch.from_numpy(host).to(dev) if dev is not None else None
+        info = PfInfo()
+        _check(load_library().gns_pf_topology_info(host.ctypes.data, ctypes.byref(info)), 'gns_pf_topology_info')
+        self.info = {k: getattr(info, k) for k, _ in PfInfo._fields_}
+
+
+def _check(rc, what):
+    if rc != 0:
+        raise _gns.GNSError(f'{what} failed: {GNS_ERRORS.get(rc, rc)}')
+
+
+def _islanded(n_bus, f_bus, t_bus, slack):
+    """0-based buses without a path of lines to the (0-based) slack."""
+    adj = [[] for _ in range(n_bus)]
+    for a, b in zip(f_bus.tolist(), t_bus.tolist()):
+        adj[a].append(b)
+        adj[b].append(a)
+    seen = np.zeros(n_bus, dtype=bool)
+    seen[slack] = True
+    stack = [slack]
+    while stack:
+        i = stack.pop()
+        for k in adj[i]:
+            if not seen[k]:
+                seen[k] = True
+                stack.append(k)
+    return np.flatnonzero(~seen)
+
+
+def analyse_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
+    """Analyse one topology from 1-based ``f_bus[E]``, ``t_bus[E]``, ``gen_bus[Gn]`` and the 1-based ``slack_bus`` (host arrays).
+    Returns a ``PowerFlowTopology`` (its ``info`` dict holds the Jacobian dimension, nnz(L+U), ...); with ``device`` the blob is
+    also copied there.  Raises ValueError for ids out of range, a slack that is not a bus, or buses islanded from the slack."""
+    f = np.asarray(f_bus, dtype=np.float64).reshape(-1)
+    t = np.asarray(t_bus, dtype=np.float64).reshape(-1)
+    g = np.asarray(gen_bus, dtype=np.float64).reshape(-1)
+    if not (np.all(f == np.round(f)) and np.all(t == np.round(t)) and np.all(g == np.round(g))):
+        raise ValueError('bus id columns must hold integers')
+    if f.size != t.size:
+        raise ValueError('f_bus and t_bus differ in length')
+    if min(f.min(initial=1), t.min(initial=1), g.min(initial=1)) < 1 or max(f.max(initial=1), t.max(initial=1), g.max(initial=1)) > n_bus:
+        raise ValueError(f'bus ids must lie in 1..{n_bus}')
+    s = float(slack_bus)
+    if s != round(s) or not 1 <= s <= n_bus:
+        raise ValueError(f'slack_bus = {slack_bus!r} is not a bus (1..{n_bus})')
+    f32, t32, g32 = (np.ascontiguousarray(a - 1, dtype=np.int32) for a in (f, t, g))
+    g_arg = g32 if g32.size else np.zeros(1, dtype=np.int32)
+    slack = int(s) - 1
+    lib = load_library()
+    nbytes = ctypes.c_size_t()
+    args = (int(n_bus), int(f32.size), int(g32.size), f32.ctypes.data, t32.ctypes.data, g_arg.ctypes.data, slack)
+    rc = lib.gns_pf_topology_bytes(*args, ctypes.byref(nbytes))
+    if rc == 3:
+        isl = _islanded(int(n_bus), f32, t32, slack) + 1
+        raise ValueError(f'buses {isl.tolist()} have no path of lines to slack_bus {slack + 1}: their angles are undetermined '
+                         '(the power-flow Jacobian is structurally singular)')
+    _check(rc, 'gns_pf_topology_bytes')
+    host = np.zeros(nbytes.value // 4, dtype=np.int32)
+    _check(lib.gns_pf_prepare_topology(*args, host.ctypes.data, host.nbytes), 'gns_pf_prepare_topology')
+    return PowerFlowTopology(host, device)
+
+
+def _as_batch(buses, lines, generators, B, L, G):
+    single = buses.dim() == 2
+    if single:
+        if lines.dim() != 2 or generators.dim() != 2:
+            raise ValueError('buses, lines, generators must all be 2-D (one grid) or all 3-D (a batch)')
+        buses, lines, generators = buses.unsqueeze(0), lines.unsqueeze(0), generators.unsqueeze(0)
+    if not (buses.dim() == lines.dim() == generators.dim() == 3):
+        raise ValueError('buses, lines, generators must all be 2-D (one grid) or all 3-D (a batch)')
+    if not (buses.shape[0] == lines.shape[0] == generators.shape[0]) or buses.shape[0] == 0:
+        raise ValueError('batch sizes of buses, lines, generators differ (or are zero)')
+    buses, lines, generators = (_gns.GNS._remap(buses, B, _gns._B0), _gns.GNS._remap(lines, L, _gns._L0),
+                                _gns.GNS._remap(generators, G, _gns._G0))
+    if buses.shape[-1] != 6 or lines.shape[-1] != 7 or generators.shape[-1] != 7:
+        raise ValueError('expected buses[...,6], lines[...,7], generators[...,7] (GNS/utils.py:4-13)')
+    for name, t in (('buses', buses), ('lines', lines), ('generators', generators)):
+        if t.dtype != torch.float32:
+            raise ValueError(f'{name} must be float32')
+    return single, buses, lines, generators
+
+
+def _topology(buses, lines, gens, slack_bus):
+    """The cached analysis of the batch's one topology.  One fused device compare of every grid's id columns against grid 0's,
+    shipped to the host with grid 0's ids and type column: one synchronisation."""
+    N, E, Gn = buses.shape[1], lines.shape[1], gens.shape[1]
+    ids_l, ids_g = lines[0, :, 0:2], gens[0, :, 0]
+    same = (lines[:, :, 0:2] == ids_l).all() & (gens[:, :, 0] == ids_g).all()
+    host = torch.cat([same.to(torch.float64).reshape(1), ids_l.t().reshape(-1).double(), ids_g.double(),
+                      buses[0, :, 1].double()]).cpu().numpy()
+    if host[0] != 1.0:
+        raise ValueError('f_bus / t_bus / generator bus columns differ across the batch: newton_raphson solves one topology per '
+                         'call (group the grids by topology)')
+    f_bus, t_bus, gen_bus, btype = host[1:1 + E], host[1 + E:1 + 2 * E], host[1 + 2 * E:1 + 2 * E + Gn], host[1 + 2 * E + Gn:]
+    if slack_bus is None:
+        cand = np.flatnonzero(btype == 3)
+        if cand.size != 1:
+            raise ValueError(f'slack_bus is not given and grid 0 has {cand.size} buses of type 3: pass slack_bus (1-based) '
+                             'explicitly (synthetic grids write type 1 everywhere)')
+        slack_bus = int(cand[0]) + 1
+    key = (N, E, Gn, slack_bus, str(buses.device), f_bus.tobytes(), t_bus.tobytes(), gen_bus.tobytes())
+    topo = _TOPO_CACHE.get(key)
+    if topo is None:
+        topo = _TOPO_CACHE[key] = analyse_topology(N, f_bus, t_bus, gen_bus, slack_bus, device=buses.device)
+    return topo
+
+
+def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, v0=None, theta0=None, tol=1e-8,
+                   max_iter=10):
+    """Newton-Raphson AC power flow (polar, MATPOWER ``newtonpf``) of every grid of a batch that shares one topology.
+
+    ``buses[Bt,N,6]``, ``lines[Bt,E,7]``, ``generators[Bt,Gn,7]``: float32, the tensors ``GNS.forward`` takes (per-unit powers,
+    line shift in radians, tau as given); ``B, L, G`` column maps as in ``GNS.forward``; a 2-D single grid is accepted.
+    ``slack_bus``: 1-based; by default the one bus of grid 0 whose type column is 3.  PV = every other bus with a generator,
+    PQ = the rest.  Start: |V| = vg of the first generator listed on PV / slack buses, 1 elsewhere, theta = 0; a warm start
+    ``v0`` / ``theta0 [Bt,N]`` sets |V| at PQ buses and theta (shifted so that theta_slack = 0).  ``||F||_inf < tol`` is tested
+    before every update; at most ``max_iter`` updates.  Everything is computed in float64.
+
+    Returns ``PowerFlowResult(v, theta, converged, iterations, mismatch)``: float64 ``[Bt,N]``, bool / int32 / float64 ``[Bt]``,
+    on the inputs' device.  A grid that fails (zero or non-finite pivot, non-finite mismatch or iterate) has ``converged``
+    False and keeps its last finite iterate; the other grids are unaffected, and every grid's result is bit-identical alone,
+    in any batch and from run to run."""
+    single, buses, lines, generators = _as_batch(buses, lines, generators, B, L, G)
+    if buses.device.type != 'cuda':
+        if not torch.cuda.is_available():
+            raise _gns.GNSError('the power-flow solver runs on a ROCm device only and none is visible (there is no CPU fallback)')
+        dev = torch.device('cuda', torch.cuda.current_device())
+    else:
+        dev = buses.device
+    in_dev = buses.device
+    buses, lines, generators = (t.to(dev).contiguous() for t in (buses, lines, generators))
+    Bt, N = buses.shape[0], buses.shape[1]
+    if not (isinstance(max_iter, (int, np.integer)) and max_iter >= 0):
+        raise ValueError(f'max_iter must be a non-negative integer, got {max_iter!r}')
+    if not float(tol) >= 0.0:
+        raise ValueError(f'tol must be >= 0, got {tol!r}')
+    warm = v0 is not None or theta0 is not None
+    if warm:
+        def start(x, fill):
+            if x is None:
+                return torch.full((Bt, N), fill, dtype=torch.float64, device=dev)
+            x = torch.as_tensor(x)
+            x = x.unsqueeze(0) if (single and x.dim() == 1) else x
+            if tuple(x.shape) != (Bt, N):
+                raise ValueError(f'v0 / theta0 must be [{Bt},{N}], got {tuple(x.shape)}')
+            return x.to(device=dev, dtype=torch.float64).contiguous()
+        v0, theta0 = start(v0, 1.0), start(theta0, 0.0)
+    topo = _topology(buses, lines, generators, slack_bus)
+    lib = load_library()
+    cfg = PfConfig(N, lines.shape[1], generators.shape[1], int(max_iter), float(tol))
+    nbytes = ctypes.c_size_t()
+    _check(lib.gns_pf_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_pf_workspace_bytes')
+    ws = _gns._workspace(nbytes.value, dev)
+    v = torch.empty(Bt, N, dtype=torch.float64, device=dev)
+    theta = torch.empty_like(v)
+    conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
+    iters = torch.empty(Bt, dtype=torch.int32, device=dev)
+    mis = torch.empty(Bt, dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.gns_pf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                            generators.data_ptr(), Bt, v0.data_ptr() if warm else None, theta0.data_ptr() if warm else None,
+                            v.data_ptr(), theta.data_ptr(), conv.data_ptr(), iters.data_ptr(), mis.data_ptr(), ws.data_ptr(),
+                            ws.numel(), stream), 'gns_pf_solve')
+    out = [v, theta, conv.bool(), iters, mis]
+    if in_dev != dev:
+        out = [t.to(in_dev) for t in out]
+    if single:
+        out = [t[0] for t in out]
+    return PowerFlowResult(*out)

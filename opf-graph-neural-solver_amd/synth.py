@@ -254,3 +254,91 @@ def contingency_grids(case_nr: int, batch: int, outages, seed: int = 0, device='
     kept = cols + (cols >= outage.unsqueeze(1)).to(torch.int64)          # line indices of each variant, in order
     lines = torch.gather(lines, 1, kept.to(lines.device).unsqueeze(2).expand(batch, e - 1, 7)).contiguous()
     return buses, lines, gens, outage.to(buses.device)
+
+
+def _first_generator_mask(gen_bus):
+    """[B,Gn] bool: generator j is the first one listed on its bus (per grid)."""
+    gn = gen_bus.shape[1]
+    earlier = torch.ones(gn, gn, dtype=torch.bool, device=gen_bus.device).tril(-1)          # [j, j'] : j' < j
+    return ~((gen_bus.unsqueeze(2) == gen_bus.unsqueeze(1)) & earlier).any(dim=2)
+
+
+def manufacture_solution(buses, lines, generators, slack_bus, v, theta):
+    """Make ``(v, theta) [B,N]`` an exact power-flow solution of the grids ("manufactured solution"; the grids of ``synth_grids``
+    mostly have none).  With ``V = v e^{j theta}`` and the Y-bus of the lines and shunts (``include/gns_powerflow.h``), the
+    injections ``S = V conj(Y V)`` are computed in float64, then
+      * PQ buses (no generator, not the slack): Pd := -Re S, Qd := -Im S;
+      * PV buses (a generator, not the slack): Pg (columns 3 and 6) of the first generator listed on the bus := Re S + Pd - the
+        Pg of the bus's other generators; Qd is left as is (Q is free at a PV bus);
+      * every generator bus: vg of its first generator := v (the solver holds |V| at vg there).
+    The slack bus (1-based ``slack_bus``) is left as is.  Returns the adjusted ``(buses, generators)`` in the inputs' dtype
+    (float32 inputs: the rounded powers make the chosen point a solution to ~1e-8).  Lines, theta and the PQ magnitudes are
+    not checked against anything: ``v`` at generator buses should already be the vg the caller wants."""
+    dev = buses.device
+    f64 = torch.float64
+    Bt, N = buses.shape[0], buses.shape[1]
+    slack = int(slack_bus) - 1
+    V = torch.polar(v.to(dev, f64), theta.to(dev, f64))
+    f = lines[..., 0].long() - 1
+    t = lines[..., 1].long() - 1
+    r, x, b = lines[..., 2].to(f64), lines[..., 3].to(f64), lines[..., 4].to(f64)
+    tau, sh = lines[..., 5].to(f64), lines[..., 6].to(f64)
+    ys = 1.0 / torch.complex(r, x)
+    ytt = ys + 0.5j * b
+    yff = ytt / (tau * tau)
+    yft = -ys * torch.polar(torch.ones_like(sh), sh) / tau
+    ytf = -ys * torch.polar(torch.ones_like(sh), -sh) / tau
+    Vf, Vt = torch.gather(V, 1, f), torch.gather(V, 1, t)
+    inj = torch.cat([yff * Vf + yft * Vt, ytf * Vf + ytt * Vt], dim=1)
+    idx = torch.cat([f, t], dim=1)
+    I = torch.zeros(Bt, N, dtype=torch.complex128, device=dev)
+    I = torch.complex(I.real.scatter_add(1, idx, inj.real), I.imag.scatter_add(1, idx, inj.imag))
+    I = I + torch.complex(buses[..., 4].to(f64), buses[..., 5].to(f64)) * V
+    S = V * I.conj()
+    gb = generators[..., 0].long() - 1
+    has_gen = torch.zeros(Bt, N, dtype=torch.bool, device=dev).scatter(1, gb, True)
+    is_slack = torch.zeros(N, dtype=torch.bool, device=dev)
+    is_slack[slack] = True
+    pq = ~has_gen & ~is_slack
+    out_b = buses.clone()
+    out_b[..., 2] = torch.where(pq, -S.real, buses[..., 2].to(f64)).to(buses.dtype)
+    out_b[..., 3] = torch.where(pq, -S.imag, buses[..., 3].to(f64)).to(buses.dtype)
+    first = _first_generator_mask(gb)
+    pg = generators[..., 6].to(f64)
+    bus_pg = torch.zeros(Bt, N, dtype=f64, device=dev).scatter_add(1, gb, pg)
+    others = torch.gather(bus_pg, 1, gb) - pg
+    want = torch.gather(S.real + out_b[..., 2].to(f64), 1, gb) - others
+    pv_first = first & (gb != slack)
+    out_g = generators.clone()
+    new_pg = torch.where(pv_first, want, pg).to(generators.dtype)
+    out_g[..., 3] = torch.where(pv_first, new_pg, generators[..., 3])
+    out_g[..., 6] = new_pg
+    out_g[..., 4] = torch.where(first, torch.gather(v.to(dev, f64), 1, gb), generators[..., 4].to(f64)).to(generators.dtype)
+    return out_b, out_g
+
+
+def solvable_grids(case_nr: int, batch: int, seed: int = 0, angle_spread: float = 0.1, device='cpu'):
+    """Grids of ``synth_grids(case_nr, batch, seed)`` made solvable by construction (``manufacture_solution``): theta ~
+    U[-angle_spread, angle_spread] at every bus but the slack (theta_slack = 0), |V| ~ U[0.95, 1.05] at PQ buses and the (fp32)
+    vg of the first generator at generator buses.  The slack is the bus of the case's generator with the largest Pmax.
+
+    Returns ``(buses, lines, generators, slack_bus, v, theta)``: float32 tensors on ``device``, the 1-based slack bus, and the
+    chosen solution as float64 ``[batch,N]``.  All draws are counter-based, as in ``synth_grids``, so any device gives the same
+    grids.  At angle_spread 0.1 a flat-start Newton-Raphson recovers the chosen point; larger spreads can give grids with other
+    valid solutions (the solver may converge to one of those)."""
+    buses, lines, gens = synth_grids(case_nr, batch, seed=seed, device=device)
+    dev = buses.device
+    n = buses.shape[1]
+    c = base_case(case_nr)
+    slack_bus = int(c['gen_bus'][int(np.argmax(c['Pmax']))])
+    f64 = torch.float64
+    theta = (counter_uniform(seed, 201, 0, batch, n, dev).to(f64) * 2.0 - 1.0) * float(angle_spread)
+    theta[:, slack_bus - 1] = 0.0
+    v = counter_uniform(seed, 202, 0, batch, n, dev).to(f64) * 0.1 + 0.95
+    gb = gens[..., 0].long() - 1
+    first = _first_generator_mask(gb)
+    at = torch.where(first, gb, torch.full_like(gb, n))                         # non-first generators write a dummy column
+    vg = torch.cat([v, torch.zeros(batch, 1, dtype=f64, device=dev)], dim=1).scatter(1, at, gens[..., 4].to(f64))[:, :n]
+    v = torch.where(torch.zeros(batch, n + 1, dtype=torch.bool, device=dev).scatter(1, at, True)[:, :n], vg, v)
+    buses, gens = manufacture_solution(buses, lines, gens, slack_bus, v, theta)
+    return buses, lines, gens, slack_bus, v, theta

@@ -218,6 +218,18 @@ int gns_profile_read(int backward, float* ms_sum, int* launches);
  *                 Teams meet at counters in the workspace and need the device to themselves: a kernel of another stream or
  *                 process holding a partner's CU makes a barrier give up (bounded: NaN losses + gns_team_status, never a hang).
  *                 Only the forward uses them by default (the default backward, variant 4, has none).
+ * Read-only names (gns_get_option only; gns_set_option refuses them with GNS_EINVAL): the path the LAST launch actually took, after
+ * every fall-back above (waves halved when waves x team > 32, planes that do not fit in LDS, teams that would not all be resident,
+ * widths without a persistent backward).  Recorded on the host when gns_forward / gns_forward_grouped and gns_backward /
+ * gns_backward_inputs / gns_backward_grouped launch; no device work, no synchronisation.  -1 before the first such launch, and for a
+ * name that is not a property of the path that ran.
+ *   "last.fwd_kernel"  1 lane-per-grid forward | 2 grid-per-workgroup forward
+ *   "last.fwd_waves", "last.fwd_plane", "last.team"   waves per workgroup, LDS planes, workgroups per group of a lane-per-grid forward
+ *   "last.gw_pack"     grids per workgroup of a grid-per-workgroup forward
+ *   "last.bwd_kernel"  0 grid-per-workgroup backward | 1, 2, 3 the persistent lane-per-grid kernel of that variant | 4 split backward
+ *   "last.dw_mfma"     weight-gradient engine of a lane-per-grid backward: 1 matrix pipe | 0 packed FMAs
+ *   "last.bwds_mode", "last.bwds_chunks", "last.bwds_R"   sweep mode, bus chunks per group and groups per sweep workgroup of a split backward
+ *   "last.bwd_gw_pack" grids per workgroup of a grid-per-workgroup backward
  * Both mappings and both engines compute the same function of the reference (GNS/main.py:140-202, :288). */
 int gns_set_option(const char* name, int value);
 int gns_get_option(const char* name, int* value);

@@ -20,7 +20,7 @@ struct GnsTuning {
   int bwd_variant;   // GNS_BWD_VARIANT: lane-per-grid backward: 1 wide half-wave records, 2 layer-wise + sub-record windows, 3 = 2 + background chains (one persistent kernel each); 4 split: one kernel sequence per reverse step (gns_backward_split.hip)
   int team;          // GNS_TEAM: workgroups per 64-grid group of the lane mapping when the batch leaves CUs idle: 0 auto, 1 none, 2, 4
   int bwds_mode;     // GNS_BWDS_MODE: sweep kernels per reverse step of the split backward: 0 one per family, 1 {L_m} {L_theta + L_v}, 2 all three families per bus in one kernel
-  int bwds_chunks;   // GNS_BWDS_CHUNKS: bus chunks per 64-grid group of the split backward's sweeps (0 = auto: 12, 24 or 32)
+  int bwds_chunks;   // GNS_BWDS_CHUNKS: bus chunks per 64-grid group of the split backward's sweeps (0 = auto: 8, 16 or 32)
 };
 GnsTuning make_tuning() {
   GnsTuning t{0, 0, GNS_FWD_THREADS / 64, 2, 1, 0, 4, 0, 1, 0};
@@ -39,6 +39,22 @@ GnsTuning make_tuning() {
 GnsTuning& tuning() {
   static GnsTuning t = make_tuning();            // C++11: thread-safe one-time initialisation
   return t;
+}
+
+// ---- the path the last launches took (read-only "last.*" options): the fall-backs below (waves halved for a team, planes that do not
+// fit, teams cancelled, widths without a persistent backward) are otherwise invisible to a caller.  Plain host stores at launch time,
+// no device work.  -1: not launched yet, or not a property of the path that ran (e.g. last.fwd_plane after a grid-per-workgroup forward).
+struct GnsLast {
+  int fwd_kernel, fwd_waves, fwd_plane, team, gw_pack;                   // gns_forward / gns_forward_grouped
+  int bwd_kernel, dw_mfma, bwds_mode, bwds_chunks, bwds_R, bwd_gw_pack;   // gns_backward / gns_backward_inputs / gns_backward_grouped
+};
+GnsLast g_last{-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+void record_forward(int kernel, int waves, int plane, int team, int pack) {
+  g_last.fwd_kernel = kernel; g_last.fwd_waves = waves; g_last.fwd_plane = plane; g_last.team = team; g_last.gw_pack = pack;
+}
+void record_backward(int kernel, int dw_mfma, int mode, int chunks, int R, int pack) {
+  g_last.bwd_kernel = kernel; g_last.dw_mfma = dw_mfma; g_last.bwds_mode = mode; g_last.bwds_chunks = chunks; g_last.bwds_R = R;
+  g_last.bwd_gw_pack = pack;
 }
 
 // ---- per-device state: kernel attributes (dynamic LDS beyond 64 KB is an opt-in per kernel AND device) and the CU count, set up
@@ -97,6 +113,7 @@ extern "C" int gns_set_option(const char* name, int value) {
 extern "C" int gns_get_option(const char* name, int* value) {
   if (!name || !value) return GNS_EINVAL;
   const GnsTuning& t = tuning();
+  const GnsLast& l = g_last;
   if (!std::strcmp(name, "fwd_mapping")) *value = t.fwd_mapping;
   else if (!std::strcmp(name, "train_mapping")) *value = t.train_mapping;
   else if (!std::strcmp(name, "bwd_variant")) *value = t.bwd_variant;
@@ -107,6 +124,17 @@ extern "C" int gns_get_option(const char* name, int* value) {
   else if (!std::strcmp(name, "team")) *value = t.team;
   else if (!std::strcmp(name, "bwds_chunks")) *value = t.bwds_chunks;
   else if (!std::strcmp(name, "bwds_mode")) *value = t.bwds_mode;
+  else if (!std::strcmp(name, "last.fwd_kernel")) *value = l.fwd_kernel;
+  else if (!std::strcmp(name, "last.fwd_waves")) *value = l.fwd_waves;
+  else if (!std::strcmp(name, "last.fwd_plane")) *value = l.fwd_plane;
+  else if (!std::strcmp(name, "last.team")) *value = l.team;
+  else if (!std::strcmp(name, "last.gw_pack")) *value = l.gw_pack;
+  else if (!std::strcmp(name, "last.bwd_kernel")) *value = l.bwd_kernel;
+  else if (!std::strcmp(name, "last.dw_mfma")) *value = l.dw_mfma;
+  else if (!std::strcmp(name, "last.bwds_mode")) *value = l.bwds_mode;
+  else if (!std::strcmp(name, "last.bwds_chunks")) *value = l.bwds_chunks;
+  else if (!std::strcmp(name, "last.bwds_R")) *value = l.bwds_R;
+  else if (!std::strcmp(name, "last.bwd_gw_pack")) *value = l.bwd_gw_pack;
   else return GNS_EINVAL;
   return GNS_OK;
 }
@@ -447,6 +475,7 @@ static int lane_forward(const gns_config* cfg, const GnsFamilies& fam, const Gns
   }
   // (the counters - and the status word gns_team_status reads - are zeroed whenever this batch size is one that may use teams)
   if (team0 > 1 && hipMemsetAsync(A.team_ws, 0, (size_t)L.groups * GNS_TEAM_CTR_BYTES, st) != hipSuccess) return GNS_ELAUNCH;
+  record_forward(1, waves, A.plane, A.team, -1);
   prof_mark(0, true, st);
   rc = gns_launch_forward(d, h, cfg->multiple_phi, A, waves * 64, st);
   prof_mark(0, false, st);
@@ -481,6 +510,7 @@ static int split_backward(const gns_config* cfg, const GnsFamilies& fam, const G
     A.igrad = ig->buf;
     if (hipMemsetAsync(A.igrad, 0, ig->bytes, st) != hipSuccess) return GNS_ELAUNCH;
   }
+  record_backward(4, 1, A.mode, A.C, A.R, -1);
   prof_mark(1, true, st);
   for (int k = K - 1; k >= 0; --k) {
     A.k = k;
@@ -535,6 +565,7 @@ extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const fl
     for (int i = 0; i < fam.nfam; ++i) { G.t_off[i] = fam.t_off[i]; G.t_sz[i] = fam.t_sz[i]; }
     for (int k = 0; k < K; ++k) G.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));
     G.Bt = Bt; G.N = N; G.E = E; G.Gn = Gn; G.K = K; G.save = 1; G.P = TP; G.WPG = ((N > E ? N : E) + 63) / 64;
+    record_forward(2, -1, -1, -1, TP);
     prof_mark(0, true, st);
     rc = gns_gw_launch_forward(d, h, cfg->multiple_phi, G, st);
     prof_mark(0, false, st);
@@ -564,6 +595,7 @@ extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const fl
       for (int i = 0; i < fam.nfam; ++i) { G.t_off[i] = fam.t_off[i]; G.t_sz[i] = fam.t_sz[i]; }
       for (int k = 0; k < K; ++k) G.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));   // main.py:198
       G.Bt = Bt; G.N = N; G.E = E; G.Gn = Gn; G.K = K; G.save = 0; G.P = P; G.WPG = ((N > E ? N : E) + 63) / 64;
+      record_forward(2, -1, -1, -1, P);
       prof_mark(0, true, st);
       rc = gns_gw_launch_forward(d, h, cfg->multiple_phi, G, st);
       prof_mark(0, false, st);
@@ -615,6 +647,7 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
     for (int k = 0; k < K; ++k) G.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));
     G.Bt = Bt; G.slab_floats = GL.slab_floats; G.N = N; G.E = E; G.Gn = cfg->n_gen; G.K = K;
     G.P = TP; G.WPG = gns_gw_backward_wpg(N);
+    record_backward(0, -1, -1, -1, -1, TP);
     prof_mark(1, true, st);
     rc = gns_gw_launch_backward(d, h, cfg->multiple_phi, G, GL.blocks, st);
     prof_mark(1, false, st);
@@ -663,6 +696,9 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
   A.team = team; A.team_ws = (unsigned char*)(bw + B.off_team);
   if (team > 1 && hipMemsetAsync(A.team_ws, 0, (size_t)B.groups * GNS_TEAM_CTR_BYTES, st) != hipSuccess) return GNS_ELAUNCH;
   A.slab_dirty = v2 ? 1 : 0;
+  // (the variant gns_launch_backward dispatches to: 2 and 3 need the matrix pipe and three phi nets, everything else runs 1)
+  record_backward(tuning().dw_mfma && cfg->multiple_phi && (tuning().bwd_variant == 2 || tuning().bwd_variant == 3) ? tuning().bwd_variant : 1,
+                  tuning().dw_mfma, -1, -1, -1, -1);
   prof_mark(1, true, st);
   // The weight-gradient contraction over the grids runs on the matrix pipe (exact fp32) unless GNS_DW_MFMA=0 asks for
   // the packed-FMA register tiles; both are parity-tested (gns_backward.hip, "weight-gradient engines").

@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests."""
+import contextlib
 import glob
 import os
 
@@ -117,3 +118,98 @@ def grids_on_topology(n, f_bus, t_bus, gen_bus, batch, seed):
     gens[:, :, 5] = u(-0.2, 0.5, batch, gn)
     gens[:, :, 6] = gens[:, :, 3]
     return buses, lines, gens
+
+
+# ---- float64 reference with an error budget (tests/test_kernel_configs.py) -----------------------------------------------------------
+EPS32 = 2.0 ** -24
+
+
+def loss_weights(Bt, N, sample, seed, device='cuda'):
+    """Fixed random fp32 weights of the loss  sum_s a_s total_s + b_s last_s + <c_s, v_s> + <d_s, theta_s>; zero outside ``sample``."""
+    g = torch.Generator().manual_seed(int(seed))
+    idx = torch.as_tensor(sorted(sample), dtype=torch.int64)
+    w = dict(a=torch.zeros(Bt), b=torch.zeros(Bt), c=torch.zeros(Bt, N), d=torch.zeros(Bt, N))
+    w['a'][idx] = torch.rand(len(idx), generator=g) + 0.5
+    w['b'][idx] = torch.rand(len(idx), generator=g) + 0.5
+    w['c'][idx] = torch.randn(len(idx), N, generator=g) * 0.05
+    w['d'][idx] = torch.randn(len(idx), N, generator=g) * 0.05
+    return {k: x.to(device) for k, x in w.items()}
+
+
+def weighted_loss(out, w):
+    v, theta, total, last = out
+    return (w['a'] * total).sum() + (w['b'] * last).sum() + (w['c'] * v).sum() + (w['d'] * theta).sum()
+
+
+def oracle64(flat, buses, lines, gens, cfg, sample, weights):
+    """oracle.gns_forward on the grids ``sample`` of the batch, once in float64 and once in float32, under the weighted loss of
+    ``weighted_loss``.  Returns ``(o32, o64)``: dicts of v, theta, total, last [S,...] in sample order, grad_params (flat, the
+    model's layout) and grad_buses / grad_lines / grad_gens [S,...].  ``cfg``: latent_dim, hidden_dim, K, gamma, multiple_phi."""
+    sample = list(sample)
+    d, h, K, multi = cfg['latent_dim'], cfg['hidden_dim'], cfg['K'], bool(cfg['multiple_phi'])
+    x = [t[sample].detach().cpu() for t in (buses, lines, gens)]
+    w = {k: t[sample].detach().cpu() for k, t in weights.items()}
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)                      # per-grid graphs of tiny ops: one thread is several times faster than many
+    try:
+        return _oracle64(flat, x, w, d, h, K, multi, cfg['gamma'], len(sample))
+    finally:
+        torch.set_num_threads(threads)
+
+
+def _oracle64(flat, x, w, d, h, K, multi, gamma, S):
+    from oracle import gns_oracle as orc
+    out = []
+    for dt in (torch.float32, torch.float64):
+        fo = flat.detach().cpu().to(dt).clone().requires_grad_(True)
+        params = orc.unflatten_params(fo, d, h, K, multi)
+        xs = [t.to(dt).clone().requires_grad_(True) for t in x]
+        res = dict(v=[], theta=[], total=[], last=[])
+        loss = torch.zeros((), dtype=dt)
+        for s in range(S):
+            v, th, tot, last = orc.gns_forward(params, xs[0][s], xs[1][s], xs[2][s], latent_dim=d, K=K, gamma=gamma,
+                                               multiple_phi=multi)
+            loss = loss + w['a'][s].to(dt) * tot + w['b'][s].to(dt) * last + (w['c'][s].to(dt) * v).sum() + (w['d'][s].to(dt) * th).sum()
+            for k, val in zip(('v', 'theta', 'total', 'last'), (v, th, tot, last)):
+                res[k].append(val.detach())
+        loss.backward()
+        res = {k: torch.stack(val) for k, val in res.items()}
+        res.update(grad_params=fo.grad.detach(), grad_buses=xs[0].grad.detach(), grad_lines=xs[1].grad.detach(),
+                   grad_gens=xs[2].grad.detach())
+        out.append(res)
+    return out[0], out[1]
+
+
+def assert_budget(kernel, o32, o64, what):
+    """The kernel's error against float64 within 4x the float32 oracle's own, plus 8 fp32 ulps of the tensor's scale:
+    e_k <= 4 e_32 + 8 2^-24 S, e_k = max|kernel - o64|, e_32 = max|o32 - o64|, S = max|o64|.  Returns e_k / max(e_32, 2^-24 S)."""
+    k = np.asarray(torch.as_tensor(kernel).detach().cpu(), dtype=np.float64)
+    a = np.asarray(torch.as_tensor(o32).detach().cpu(), dtype=np.float64)
+    b = np.asarray(torch.as_tensor(o64).detach().cpu(), dtype=np.float64)
+    assert k.shape == b.shape, f'{what}: shape {k.shape} vs {b.shape}'
+    assert np.all(np.isfinite(k)), f'{what}: non-finite values'
+    e_k, e_32, S = float(np.max(np.abs(k - b))), float(np.max(np.abs(a - b))), float(np.max(np.abs(b)))
+    ratio = e_k / max(e_32, EPS32 * S, 1e-300)
+    assert e_k <= 4.0 * e_32 + 8.0 * EPS32 * S, \
+        f'{what}: max|kernel - f64| = {e_k:.3e} > 4 x {e_32:.3e} (f32 oracle) + 8 ulp of {S:.3e}  (ratio {ratio:.2f})'
+    return ratio
+
+
+@contextlib.contextmanager
+def options(**kw):
+    """Set library options (gns_set_option) for the body; the previous values are restored whatever happens."""
+    import opf_graph_neural_solver_amd as amd
+    old = {k: amd.get_option(k) for k in kw}
+    try:
+        for k, v in kw.items():
+            amd.set_option(k, v)
+        yield
+    finally:
+        for k, v in old.items():
+            amd.set_option(k, v)
+
+
+def last_path(*names):
+    """The read-only "last.*" record of the path the last launches took."""
+    import opf_graph_neural_solver_amd as amd
+    return {n: amd.get_option('last.' + n) for n in names}

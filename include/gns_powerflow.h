@@ -3,7 +3,8 @@
  * The reference evaluates a trained GNS against PYPOWER's runpf(PF_ALG=1) (GNS/evaluate.py:24-40), one grid at a time on the
  * CPU.  This solver produces that baseline on the device for a whole batch that shares one topology: the sparse structure of the
  * Jacobian and of its LU factor is analysed ONCE on the host (gns_pf_prepare_topology), and every grid then runs the same
- * elimination program; only the values differ.  Conventions are those of gns_hip.h: plain pointers, caller-owned device memory,
+ * elimination program; only the values differ.  A batch that mixes topologies runs in one launch over a set of such analyses
+ * (gns_pf_solve_set, at the end of this file), each grid on its own.  Conventions are those of gns_hip.h: plain pointers, caller-owned device memory,
  * GNS_E* return codes (the enum of gns_hip.h), work enqueued on the caller's stream, no allocation and no host synchronisation
  * inside gns_pf_solve.
  *
@@ -92,6 +93,32 @@ int gns_pf_solve(const gns_pf_config* cfg, const void* topo_host, const void* to
                  const double* v0, const double* theta0,
                  double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* Batches that mix topologies (an N-1 contingency set).  A SET is topology blobs of one (N, E, Gn) concatenated in one int32 buffer
+ * of set_words words, each starting at a word offset that is a multiple of 16 (64 bytes; blobs are relocatable, and their
+ * operation records need 8-byte alignment).  set_host and set_dev hold the same words.  member_off [n_member] (host) lists the
+ * offsets of the blobs this call may use; the host checks every member before launching: aligned, its whole blob inside
+ * set_words, a blob whose N, E and Gn are cfg's (GNS_EINVAL otherwise), and its LDS image <= GNS_PF_LDS_MAX_BYTES
+ * (GNS_EUNSUPPORTED for the whole call otherwise).  The launch uses the largest member's LDS image.
+ * Workspace: Bt x (the largest nnz(Y) of the members) Y-bus entries of 16 bytes, rounded up to 256 bytes. */
+int gns_pf_workspace_bytes_set(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
+                               int32_t n_member, int64_t Bt, size_t* bytes);
+
+/* Solve Bt grids, each on its own blob of the set.  grid_off [Bt] (device): word offset in the set of grid g's blob, or -1 for
+ * "not solved" (a topology that islands a bus).  order [Bt] (device, or NULL for 0..Bt-1): workgroup w solves grid order[w]; a
+ * permutation of 0..Bt-1 that groups the grids of one topology keeps that blob in L2 (entries outside 0..Bt-1 are skipped).
+ * Outputs go to grid g's rows whatever the order, and a grid's results do not depend on its batch, its position or the order:
+ * they are bit-identical to gns_pf_solve on its blob.  A grid whose offset is -1, misaligned, outside the set, or not at a blob of
+ * cfg's shape that fits the launch (checked on the device before the blob is indexed; the set is never read out of bounds) gets
+ * v = theta = NaN, converged = 0, iterations = -1, mismatch = NaN.
+ * Errors as gns_pf_solve: GNS_EINVAL for a NULL pointer, a config or member that does not match, GNS_ESIZE for a short
+ * workspace, GNS_EUNSUPPORTED for a member's LDS image above the limit. */
+int gns_pf_solve_set(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                     const int32_t* member_off, int32_t n_member, const int32_t* grid_off, const int32_t* order,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const double* v0, const double* theta0,
+                     double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,8 @@ def load_library():
     lib.gns_pf_topology_info.argtypes = [vp, ctypes.POINTER(PfInfo)]
     lib.gns_pf_workspace_bytes.argtypes = [pfcp, vp, i64, ctypes.POINTER(sz)]
     lib.gns_pf_solve.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_pf_workspace_bytes_set.argtypes = [pfcp, vp, sz, vp, i32, i64, ctypes.POINTER(sz)]
+    lib.gns_pf_solve_set.argtypes = [pfcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     for f in PF_EXPORTS:
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
@@ -104,7 +106,8 @@ EXPORTS = ('gns_version', 'gns_param_count', 'gns_config_supported', 'gns_topolo
 
 
 # the power-flow solver's C-ABI (include/gns_powerflow.h)
-PF_EXPORTS = ('gns_pf_topology_bytes', 'gns_pf_prepare_topology', 'gns_pf_topology_info', 'gns_pf_workspace_bytes', 'gns_pf_solve')
+PF_EXPORTS = ('gns_pf_topology_bytes', 'gns_pf_prepare_topology', 'gns_pf_topology_info', 'gns_pf_workspace_bytes', 'gns_pf_solve',
+              'gns_pf_workspace_bytes_set', 'gns_pf_solve_set')
 
 
 def set_option(name: str, value: int) -> None:

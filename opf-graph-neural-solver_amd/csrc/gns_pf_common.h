@@ -22,5 +22,17 @@ enum {
   PH_PIVOT,      // [dim]    factor slot of each pivot
   PH_STEP_PTR,   // [nsteps+1] operations of each step ...
   PH_OPS,        // [2 nops] ... as (dst | a << 16, b): F[dst] -= F[a] * F[b], or F[dst] /= F[a] when b == -1 (8-byte aligned)
-  PF_HDR_WORDS = 32
+  PF_HDR_WORDS = 32,
+  PF_SET_ALIGN_WORDS = 16   // blobs of a set (gns_pf_solve_set) start at multiples of 16 words (64 bytes)
 };
+
+#if defined(__HIPCC__)
+#define PF_HOST_DEVICE __host__ __device__
+#else
+#define PF_HOST_DEVICE
+#endif
+
+// LDS image of one grid (gns_pf_info.lds_bytes): the factor, the right-hand side and eight bus vectors, in doubles
+PF_HOST_DEVICE inline int64_t pf_lds_bytes(const int32_t* h) {
+  return 8 * ((int64_t)h[PH_NNZLU] + h[PH_DIM] + 8 * (int64_t)h[PH_N]);
+}

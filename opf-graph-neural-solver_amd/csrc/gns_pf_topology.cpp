@@ -230,6 +230,6 @@ extern "C" int gns_pf_topology_info(const void* topo_host, gns_pf_info* info) {
   info->n_bus = h[PH_N]; info->n_line = h[PH_E]; info->n_gen = h[PH_GN]; info->slack = h[PH_SLACK];
   info->n_pv = h[PH_NPV]; info->n_pq = h[PH_NPQ]; info->dim = h[PH_DIM]; info->nnz_jac = h[PH_NNZJ]; info->nnz_lu = h[PH_NNZLU];
   info->nnz_ybus = h[PH_NNZY]; info->n_ops = h[PH_NOPS]; info->n_steps = h[PH_NSTEPS];
-  info->lds_bytes = 8 * ((int64_t)h[PH_NNZLU] + h[PH_DIM] + 8 * (int64_t)h[PH_N]);
+  info->lds_bytes = pf_lds_bytes(h);
   return GNS_OK;
 }

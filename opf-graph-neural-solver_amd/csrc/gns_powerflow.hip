@@ -17,15 +17,18 @@ __device__ inline double pf_wave_max(double x) {
   return x;
 }
 
-__global__ __launch_bounds__(PF_THREADS) void gns_pf_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
-                                                            const float* __restrict__ lines, const float* __restrict__ gens,
-                                                            const double* __restrict__ v0, const double* __restrict__ th0,
-                                                            double* __restrict__ v_out, double* __restrict__ th_out,
-                                                            uint8_t* __restrict__ conv_out, int32_t* __restrict__ it_out,
-                                                            double* __restrict__ mis_out, double2* __restrict__ ybus_ws,
-                                                            int max_iter, double tol) {
+// The solve of grid g on the blob at topo: the body of both kernels below.  Its Y-bus values go to ybus_ws + g * (the blob's
+// nnz(Y)), or with SET to ybus_ws + g * ystride (the largest nnz(Y) of a set).
+template <bool SET>
+__device__ __forceinline__ void pf_solve_grid(const int32_t* topo, const int g, const float* buses,
+                                              const float* lines, const float* gens,
+                                              const double* v0, const double* th0,
+                                              double* v_out, double* th_out,
+                                              uint8_t* conv_out, int32_t* it_out,
+                                              double* mis_out, double2* ybus_ws, int ystride, int max_iter,
+                                              double tol) {
   extern __shared__ double lds[];
-  const int g = blockIdx.x, lane = threadIdx.x;
+  const int lane = threadIdx.x;
   const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN], slack = topo[PH_SLACK], dim = topo[PH_DIM];
   const int nnzLU = topo[PH_NNZLU], nnzY = topo[PH_NNZY], nsteps = topo[PH_NSTEPS];
   const int32_t* role = topo + topo[PH_ROLE];
@@ -56,7 +59,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pf_kernel(const int32_t* __res
   const float* bus = buses + (size_t)g * N * 6;
   const float* line = lines + (size_t)g * E * 7;
   const float* gen = gens + (size_t)g * Gn * 7;
-  double2* Y = ybus_ws + (size_t)g * nnzY;
+  double2* Y = ybus_ws + (size_t)g * (SET ? ystride : nnzY);
 
   // Y-bus values (makeYbus), specified injections, starting point
   for (int i = lane; i < N; i += PF_THREADS) {
@@ -196,10 +199,85 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pf_kernel(const int32_t* __res
   if (lane == 0) { conv_out[g] = conv ? 1 : 0; it_out[g] = it; mis_out[g] = mis; }
 }
 
-size_t pf_ws_bytes(const int32_t* h, int64_t Bt) { return (((size_t)Bt * h[PH_NNZY] * sizeof(double2)) + 255) & ~(size_t)255; }
+__global__ __launch_bounds__(PF_THREADS) void gns_pf_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
+                                                            const float* __restrict__ lines, const float* __restrict__ gens,
+                                                            const double* __restrict__ v0, const double* __restrict__ th0,
+                                                            double* __restrict__ v_out, double* __restrict__ th_out,
+                                                            uint8_t* __restrict__ conv_out, int32_t* __restrict__ it_out,
+                                                            double* __restrict__ mis_out, double2* __restrict__ ybus_ws,
+                                                            int max_iter, double tol) {
+  const int g = blockIdx.x;
+  pf_solve_grid<false>(topo, g, buses, lines, gens, v0, th0, v_out, th_out, conv_out, it_out, mis_out, ybus_ws, 0, max_iter, tol);
+}
+
+// A batch over a set of blobs (gns_pf_solve_set): workgroup w solves grid g = order ? order[w] : w on the blob at set + grid_off[g].
+// A grid without a usable blob (grid_off -1, or an offset that is misaligned, outside the set, or not at a blob of this shape
+// whose LDS image and Y-bus fit the launch) gets the not-solved outputs and never indexes the set.
+__global__ __launch_bounds__(PF_THREADS) void gns_pf_set_kernel(const int32_t* __restrict__ set, int64_t set_words,
+                                                                const int32_t* __restrict__ grid_off, const int32_t* __restrict__ order,
+                                                                int64_t Bt, int N, int E, int Gn, int64_t lds_bytes, int nnzy_max,
+                                                                const float* __restrict__ buses, const float* __restrict__ lines,
+                                                                const float* __restrict__ gens, const double* __restrict__ v0,
+                                                                const double* __restrict__ th0, double* __restrict__ v_out,
+                                                                double* __restrict__ th_out, uint8_t* __restrict__ conv_out,
+                                                                int32_t* __restrict__ it_out, double* __restrict__ mis_out,
+                                                                double2* __restrict__ ybus_ws, int max_iter, double tol) {
+  const int64_t w = blockIdx.x;
+  const int64_t g64 = order ? (int64_t)order[w] : w;
+  if (g64 < 0 || g64 >= Bt) return;                             // not a grid of this batch: nothing to write
+  const int g = (int)g64;
+  const int64_t off = grid_off[g];
+  bool ok = off >= 0 && off % PF_SET_ALIGN_WORDS == 0 && off + PF_HDR_WORDS <= set_words;
+  const int32_t* topo = set + (ok ? off : 0);
+  if (ok) {
+    ok = topo[PH_MAGIC] == GNS_PF_MAGIC && topo[PH_N] == N && topo[PH_E] == E && topo[PH_GN] == Gn &&
+         topo[PH_TOTAL] >= PF_HDR_WORDS && topo[PH_TOTAL] <= set_words - off && topo[PH_NNZY] >= 0 && topo[PH_NNZY] <= nnzy_max &&
+         pf_lds_bytes(topo) <= lds_bytes;
+  }
+  if (!ok) {
+    const double nan = __builtin_nan("");
+    for (int i = threadIdx.x; i < N; i += PF_THREADS) {
+      v_out[(size_t)g * N + i] = nan;
+      th_out[(size_t)g * N + i] = nan;
+    }
+    if (threadIdx.x == 0) { conv_out[g] = 0; it_out[g] = -1; mis_out[g] = nan; }
+    return;
+  }
+  pf_solve_grid<true>(topo, g, buses, lines, gens, v0, th0, v_out, th_out, conv_out, it_out, mis_out, ybus_ws, nnzy_max, max_iter,
+                      tol);
+}
+
+size_t pf_ws_bytes_nnzy(int64_t nnzy, int64_t Bt) { return (((size_t)Bt * nnzy * sizeof(double2)) + 255) & ~(size_t)255; }
+size_t pf_ws_bytes(const int32_t* h, int64_t Bt) { return pf_ws_bytes_nnzy(h[PH_NNZY], Bt); }
 
 bool pf_header_ok(const gns_pf_config* cfg, const int32_t* h) {
   return h[PH_MAGIC] == GNS_PF_MAGIC && h[PH_N] == cfg->n_bus && h[PH_E] == cfg->n_line && h[PH_GN] == cfg->n_gen;
+}
+
+// Host check of the members of a set: each at an aligned word offset with its whole blob inside set_words, a blob of cfg's shape.
+// Returns GNS_OK with the largest nnz(Y) and LDS image, GNS_EINVAL, or GNS_EUNSUPPORTED when a member's LDS image is too large.
+int pf_scan_set(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off, int32_t n_member,
+                int32_t* nnzy_max, int64_t* lds_max) {
+  if (!cfg || !set_host || !member_off || n_member <= 0 || set_words > (size_t)INT32_MAX) return GNS_EINVAL;
+  const int32_t* set = static_cast<const int32_t*>(set_host);
+  int32_t ny = 0;
+  int64_t lds = 0;
+  bool too_big = false;
+  for (int32_t m = 0; m < n_member; ++m) {
+    const int64_t off = member_off[m];
+    if (off < 0 || off % PF_SET_ALIGN_WORDS != 0 || off + PF_HDR_WORDS > (int64_t)set_words) return GNS_EINVAL;
+    const int32_t* h = set + off;
+    if (!pf_header_ok(cfg, h) || h[PH_TOTAL] < PF_HDR_WORDS || h[PH_TOTAL] > (int64_t)set_words - off || h[PH_NNZY] < 0)
+      return GNS_EINVAL;
+    ny = h[PH_NNZY] > ny ? h[PH_NNZY] : ny;
+    const int64_t b = pf_lds_bytes(h);
+    lds = b > lds ? b : lds;
+    too_big |= b > GNS_PF_LDS_MAX_BYTES;
+  }
+  if (too_big) return GNS_EUNSUPPORTED;
+  *nnzy_max = ny;
+  *lds_max = lds;
+  return GNS_OK;
 }
 
 }  // namespace
@@ -237,5 +315,44 @@ extern "C" int gns_pf_solve(const gns_pf_config* cfg, const void* topo_host, con
   hipLaunchKernelGGL(gns_pf_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)info.lds_bytes, (hipStream_t)stream,
                      static_cast<const int32_t*>(topo_dev), buses, lines, generators, v0, theta0, v, theta, converged, iterations,
                      mismatch, static_cast<double2*>(workspace), cfg->max_iter, cfg->tol);
+  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+}
+
+extern "C" int gns_pf_workspace_bytes_set(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
+                                          int32_t n_member, int64_t Bt, size_t* bytes) {
+  if (!bytes || Bt <= 0) return GNS_EINVAL;
+  int32_t nnzy = 0;
+  int64_t lds = 0;
+  const int rc = pf_scan_set(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
+  if (rc != GNS_OK) return rc;
+  *bytes = pf_ws_bytes_nnzy(nnzy, Bt);
+  return GNS_OK;
+}
+
+extern "C" int gns_pf_solve_set(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                                const int32_t* member_off, int32_t n_member, const int32_t* grid_off, const int32_t* order,
+                                const float* buses, const float* lines, const float* generators, int64_t Bt,
+                                const double* v0, const double* theta0,
+                                double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  if (!cfg || !set_dev || !grid_off || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF) return GNS_EINVAL;
+  if (!v || !theta || !converged || !iterations || !mismatch || !workspace) return GNS_EINVAL;
+  if (cfg->max_iter < 0 || !(cfg->tol >= 0.0) || (v0 == nullptr) != (theta0 == nullptr)) return GNS_EINVAL;
+  int32_t nnzy = 0;
+  int64_t lds = 0;
+  const int rc = pf_scan_set(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
+  if (rc != GNS_OK) return rc;
+  if (workspace_bytes < pf_ws_bytes_nnzy(nnzy, Bt)) return GNS_ESIZE;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_pf_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
+      return GNS_ELAUNCH;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(gns_pf_set_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)lds, (hipStream_t)stream,
+                     static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off, order, Bt, cfg->n_bus, cfg->n_line,
+                     cfg->n_gen, lds, nnzy, buses, lines, generators, v0, theta0, v, theta, converged, iterations, mismatch,
+                     static_cast<double2*>(workspace), cfg->max_iter, cfg->tol);
   return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
 }

@@ -89,17 +89,24 @@ def _validated_topology(l_np, g_np, n_bus, dev):
     return _Topology.build(load_library(), n_bus, src, dst, gb, dev)
 
 
-def _classify_ids(lines3, gens3):
+def _classify_ids(lines3, gens3, extra=None):
     """Topologies of a batch: its distinct id rows ``(f_bus, t_bus | generator bus)`` (float64, host), for every grid the index of
-    its row (``inverse``, on the batch's device) and the grids per row (``counts``, host).  One ``torch.unique`` on the device."""
+    its row (``inverse``, on the batch's device) and the grids per row (``counts``, host).  One ``torch.unique`` on the device.
+    ``extra``: an optional 1-D int64 tensor on the batch's device that rides along in the same synchronisation and is returned (on
+    the host) as a fourth value."""
     S = lines3.shape[0]
     ids = torch.cat([lines3[:, :, 0:2].reshape(S, -1), gens3[:, :, 0]], 1).to(torch.float64)
     ids_i = ids.round().to(torch.int64)
     uniq, inverse, counts = torch.unique(ids_i, dim=0, return_inverse=True, return_counts=True)
-    tail = torch.cat([counts, (ids_i.to(torch.float64) != ids).any().reshape(1).to(torch.int64)]).cpu()    # one sync for both
+    n_extra = 0 if extra is None else extra.numel()
+    parts = [counts] + ([] if extra is None else [extra.reshape(-1).to(torch.int64)])
+    tail = torch.cat(parts + [(ids_i.to(torch.float64) != ids).any().reshape(1).to(torch.int64)]).cpu()    # one sync for all
     if int(tail[-1]):
         raise ValueError('bus id columns must hold integers')
-    return uniq.cpu().to(torch.float64), inverse, tail[:-1]
+    counts = tail[:counts.numel()]
+    if extra is None:
+        return uniq.cpu().to(torch.float64), inverse, counts
+    return uniq.cpu().to(torch.float64), inverse, counts, tail[counts.numel():counts.numel() + n_extra]
 
 
 def _group_tables(inverse, counts):

@@ -1,12 +1,14 @@
 """Batched Newton-Raphson AC power flow on the device: the baseline the reference evaluates a trained GNS against
-(PYPOWER ``runpf(PF_ALG=1)``, ``GNS/evaluate.py:24-40``), for a whole batch of grids that share one topology.
+(PYPOWER ``runpf(PF_ALG=1)``, ``GNS/evaluate.py:24-40``), for a whole batch of grids that share one topology, or with
+``mixed_topologies=True`` for a batch that mixes them (an N-1 contingency set, ``synth.contingency_grids``).
 
     res = powerflow.newton_raphson(buses, lines, generators, slack_bus=1)
     res.v, res.theta, res.converged, res.iterations, res.mismatch
 
 The semantics (bus roles, Y-bus, injections, starting point, convergence test, per-grid failure) are those of
 ``include/gns_powerflow.h``; the solve runs in one HIP kernel (``csrc/gns_powerflow.hip``) in float64.  The sparse structure of
-the Jacobian and of its LU factor is analysed once per topology on the host (``csrc/gns_pf_topology.cpp``) and cached.
+the Jacobian and of its LU factor is analysed once per topology on the host (``csrc/gns_pf_topology.cpp``) and cached; a mixed
+batch reads its topologies from a device set of those blobs (``gns_pf_solve_set``) that grows as new topologies appear.
 """
 from __future__ import annotations
 
@@ -21,18 +23,63 @@ from ._lib import GNS_ERRORS, PfConfig, PfInfo, load_library
 
 PowerFlowResult = namedtuple('PowerFlowResult', ['v', 'theta', 'converged', 'iterations', 'mismatch'])
 
+MixedPlan = namedtuple('MixedPlan', ['topology', 'order', 'grid_off', 'member_off', 'topo_set', 'slack_bus', 'islanded'])
+
 _TOPO_CACHE = {}
+_ISLANDED = set()       # keys of _TOPO_CACHE's form whose topology leaves buses without a path of lines to the slack
+_SET_CACHE = {}         # (N, E, Gn, slack_bus, device) -> _PfTopologySet
+
+
+class IslandedTopology(ValueError):
+    """A topology with buses that have no path of lines to the slack (their angles are undetermined)."""
 
 
 class PowerFlowTopology:
-    """Host analysis of one topology (the blob on the host and on the device) and what it found (``info``)."""
+    """Host analysis of one topology (the blob on the host and, copied on first use, on the device) and what it found (``info``)."""
 
     def __init__(self, host, dev):
         self.host = host
-        self.blob = torch.from_numpy(host).to(dev) if dev is not None else None
+        self._dev, self._blob = dev, None
         info = PfInfo()
         _check(load_library().gns_pf_topology_info(host.ctypes.data, ctypes.byref(info)), 'gns_pf_topology_info')
         self.info = {k: getattr(info, k) for k, _ in PfInfo._fields_}
+
+    @property
+    def blob(self):
+        if self._blob is None and self._dev is not None:
+            self._blob = torch.from_numpy(self.host).to(self._dev)
+        return self._blob
+
+
+class _PfTopologySet:
+    """The topologies mixed calls of one ``(N, E, Gn, slack, device)`` have met: their blobs concatenated at 16-word (64-byte) aligned
+    word offsets, on the host (``host``, what gns_pf_solve_set validates) and in one device tensor (``blob``), grown as new topologies
+    appear (the scheme of ``gns._TopologySet``).  A call on topologies the set already holds copies nothing."""
+
+    ALIGN_WORDS = 16
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.offset = {}                # topology key -> word offset of its blob
+        self.parts, self.words = [], 0
+        self.host, self.blob = np.zeros(0, dtype=np.int32), None
+
+    def add(self, key, topo):
+        off = self.offset.get(key)
+        if off is None:
+            off = self.offset[key] = self.words
+            self.parts.append((off, topo.host))
+            self.words += (topo.host.size + self.ALIGN_WORDS - 1) // self.ALIGN_WORDS * self.ALIGN_WORDS
+        return off
+
+    def sync(self):
+        """Bring ``host`` and ``blob`` up to every member added (a kernel still reading the old device tensor keeps it alive through
+        the caching allocator's stream order)."""
+        if self.host.size != self.words:
+            host = np.zeros(self.words, dtype=np.int32)
+            for off, h in self.parts:
+                host[off:off + h.size] = h
+            self.host, self.blob = host, torch.from_numpy(host).to(self.dev)
 
 
 def _check(rc, what):
@@ -61,7 +108,8 @@ def _islanded(n_bus, f_bus, t_bus, slack):
 def analyse_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
     """Analyse one topology from 1-based ``f_bus[E]``, ``t_bus[E]``, ``gen_bus[Gn]`` and the 1-based ``slack_bus`` (host arrays).
     Returns a ``PowerFlowTopology`` (its ``info`` dict holds the Jacobian dimension, nnz(L+U), ...); with ``device`` the blob is
-    also copied there.  Raises ValueError for ids out of range, a slack that is not a bus, or buses islanded from the slack."""
+    also copied there (on first use).  Raises ValueError for ids out of range or a slack that is not a bus, and its subclass
+    ``IslandedTopology`` for buses islanded from the slack."""
     f = np.asarray(f_bus, dtype=np.float64).reshape(-1)
     t = np.asarray(t_bus, dtype=np.float64).reshape(-1)
     g = np.asarray(gen_bus, dtype=np.float64).reshape(-1)
@@ -83,7 +131,7 @@ def analyse_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
     rc = lib.gns_pf_topology_bytes(*args, ctypes.byref(nbytes))
     if rc == 3:
         isl = _islanded(int(n_bus), f32, t32, slack) + 1
-        raise ValueError(f'buses {isl.tolist()} have no path of lines to slack_bus {slack + 1}: their angles are undetermined '
+        raise IslandedTopology(f'buses {isl.tolist()} have no path of lines to slack_bus {slack + 1}: their angles are undetermined '
                          '(the power-flow Jacobian is structurally singular)')
     _check(rc, 'gns_pf_topology_bytes')
     host = np.zeros(nbytes.value // 4, dtype=np.int32)
@@ -124,11 +172,7 @@ def _topology(buses, lines, gens, slack_bus):
                          'call (group the grids by topology)')
     f_bus, t_bus, gen_bus, btype = host[1:1 + E], host[1 + E:1 + 2 * E], host[1 + 2 * E:1 + 2 * E + Gn], host[1 + 2 * E + Gn:]
     if slack_bus is None:
-        cand = np.flatnonzero(btype == 3)
-        if cand.size != 1:
-            raise ValueError(f'slack_bus is not given and grid 0 has {cand.size} buses of type 3: pass slack_bus (1-based) '
-                             'explicitly (synthetic grids write type 1 everywhere)')
-        slack_bus = int(cand[0]) + 1
+        slack_bus = _slack_from_type3(btype == 3)
     key = (N, E, Gn, slack_bus, str(buses.device), f_bus.tobytes(), t_bus.tobytes(), gen_bus.tobytes())
     topo = _TOPO_CACHE.get(key)
     if topo is None:
@@ -136,9 +180,65 @@ def _topology(buses, lines, gens, slack_bus):
     return topo
 
 
+def _slack_from_type3(is3):
+    """The 1-based slack from grid 0's buses of type 3 (a host bool array): there must be exactly one."""
+    cand = np.flatnonzero(is3)
+    if cand.size != 1:
+        raise ValueError(f'slack_bus is not given and grid 0 has {cand.size} buses of type 3: pass slack_bus (1-based) '
+                         'explicitly (synthetic grids write type 1 everywhere)')
+    return int(cand[0]) + 1
+
+
+def _plan_mixed(buses, lines, gens, slack_bus):
+    """What a ``mixed_topologies`` call launches.  The grids are classified by id rows (``gns._classify_ids``: the call's one
+    synchronisation, which also brings grid 0's type column when the slack is not given); each distinct topology is analysed once
+    per ``(N, E, Gn, slack, device, ids)`` (``_TOPO_CACHE``; islanding ones are remembered in ``_ISLANDED``) and its blob added
+    to the device set of ``(N, E, Gn, slack, device)``.  Returns a ``MixedPlan``:
+      topology   [Bt] int64, device: each grid's index among the batch's distinct topologies
+      order      [Bt] int32, device: the grids by topology (stable argsort), the order workgroups take them in
+      grid_off   [Bt] int32, device: word offset of each grid's blob in the set, -1 for a topology that islands a bus
+      member_off int32 numpy: the offsets of the blobs this call uses (distinct, ascending by topology index)
+      topo_set   the ``_PfTopologySet``; slack_bus: the 1-based slack; islanded: bool numpy per distinct topology.
+    Raises as ``analyse_topology`` does for ids out of range, non-integer ids or a bad slack; islands are not an error here."""
+    N, E, Gn = buses.shape[1], lines.shape[1], gens.shape[1]
+    dev = buses.device
+    if slack_bus is None:
+        ids, inverse, _, is3 = _gns._classify_ids(lines, gens, extra=(buses[0, :, 1] == 3).to(torch.int64))
+        slack_bus = _slack_from_type3(is3.numpy() != 0)
+    else:
+        ids, inverse, _ = _gns._classify_ids(lines, gens)
+    set_key = (N, E, Gn, slack_bus, str(dev))
+    topo_set = _SET_CACHE.get(set_key)
+    if topo_set is None:
+        topo_set = _SET_CACHE[set_key] = _PfTopologySet(dev)
+    ids_np = ids.numpy()
+    T = ids_np.shape[0]
+    off = np.full(T, -1, dtype=np.int32)
+    for k in range(T):
+        f_bus, t_bus = (np.ascontiguousarray(ids_np[k, j:2 * E:2]) for j in (0, 1))
+        gen_bus = np.ascontiguousarray(ids_np[k, 2 * E:])
+        key = (N, E, Gn, slack_bus, str(dev), f_bus.tobytes(), t_bus.tobytes(), gen_bus.tobytes())
+        if key in _ISLANDED:
+            continue
+        topo = _TOPO_CACHE.get(key)
+        if topo is None:
+            try:
+                topo = _TOPO_CACHE[key] = analyse_topology(N, f_bus, t_bus, gen_bus, slack_bus, device=dev)
+            except IslandedTopology:
+                _ISLANDED.add(key)
+                continue
+        off[k] = topo_set.add(key, topo)
+    topo_set.sync()
+    inverse = inverse.to(dev)
+    order = torch.argsort(inverse, stable=True).to(torch.int32)
+    grid_off = torch.from_numpy(off).to(dev)[inverse].contiguous()
+    return MixedPlan(inverse, order, grid_off, off[off >= 0].copy(), topo_set, slack_bus, off < 0)
+
+
 def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, v0=None, theta0=None, tol=1e-8,
-                   max_iter=10):
-    """Newton-Raphson AC power flow (polar, MATPOWER ``newtonpf``) of every grid of a batch that shares one topology.
+                   max_iter=10, mixed_topologies=False):
+    """Newton-Raphson AC power flow (polar, MATPOWER ``newtonpf``) of every grid of a batch that shares one topology, or with
+    ``mixed_topologies=True`` of a batch whose id columns differ between grids.
 
     ``buses[Bt,N,6]``, ``lines[Bt,E,7]``, ``generators[Bt,Gn,7]``: float32, the tensors ``GNS.forward`` takes (per-unit powers,
     line shift in radians, tau as given); ``B, L, G`` column maps as in ``GNS.forward``; a 2-D single grid is accepted.
@@ -150,7 +250,13 @@ def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bu
     Returns ``PowerFlowResult(v, theta, converged, iterations, mismatch)``: float64 ``[Bt,N]``, bool / int32 / float64 ``[Bt]``,
     on the inputs' device.  A grid that fails (zero or non-finite pivot, non-finite mismatch or iterate) has ``converged``
     False and keeps its last finite iterate; the other grids are unaffected, and every grid's result is bit-identical alone,
-    in any batch and from run to run."""
+    in any batch and from run to run.
+
+    ``mixed_topologies=True``: the batch is classified by id rows (one synchronisation) and solved in one launch, each grid on its
+    own topology's blob; every grid's result is bit-identical to a plain call on its topology's grids.  The slack is one per call
+    (given, or from grid 0's type column).  A grid whose topology leaves a bus without a path of lines to the slack is not solved:
+    ``converged`` False, ``iterations`` -1, ``v`` / ``theta`` / ``mismatch`` NaN; the other grids are unaffected.  Without it a batch
+    whose id columns differ, or an islanded topology, raises ValueError."""
     single, buses, lines, generators = _as_batch(buses, lines, generators, B, L, G)
     if buses.device.type != 'cuda':
         if not torch.cuda.is_available():
@@ -176,25 +282,56 @@ def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bu
                 raise ValueError(f'v0 / theta0 must be [{Bt},{N}], got {tuple(x.shape)}')
             return x.to(device=dev, dtype=torch.float64).contiguous()
         v0, theta0 = start(v0, 1.0), start(theta0, 0.0)
-    topo = _topology(buses, lines, generators, slack_bus)
+    if not isinstance(mixed_topologies, bool):
+        raise ValueError(f'mixed_topologies must be a bool, got {mixed_topologies!r}')
     lib = load_library()
     cfg = PfConfig(N, lines.shape[1], generators.shape[1], int(max_iter), float(tol))
-    nbytes = ctypes.c_size_t()
-    _check(lib.gns_pf_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_pf_workspace_bytes')
-    ws = _gns._workspace(nbytes.value, dev)
-    v = torch.empty(Bt, N, dtype=torch.float64, device=dev)
-    theta = torch.empty_like(v)
-    conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
-    iters = torch.empty(Bt, dtype=torch.int32, device=dev)
-    mis = torch.empty(Bt, dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib.gns_pf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                            generators.data_ptr(), Bt, v0.data_ptr() if warm else None, theta0.data_ptr() if warm else None,
-                            v.data_ptr(), theta.data_ptr(), conv.data_ptr(), iters.data_ptr(), mis.data_ptr(), ws.data_ptr(),
-                            ws.numel(), stream), 'gns_pf_solve')
-    out = [v, theta, conv.bool(), iters, mis]
+    if mixed_topologies:
+        plan = _plan_mixed(buses, lines, generators, slack_bus)
+        out = _solve_mixed(lib, cfg, plan, buses, lines, generators, v0 if warm else None, theta0 if warm else None)
+    else:
+        topo = _topology(buses, lines, generators, slack_bus)
+        nbytes = ctypes.c_size_t()
+        _check(lib.gns_pf_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_pf_workspace_bytes')
+        ws = _gns._workspace(nbytes.value, dev)
+        v, theta, conv, iters, mis = _outputs(Bt, N, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib.gns_pf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                                generators.data_ptr(), Bt, v0.data_ptr() if warm else None, theta0.data_ptr() if warm else None,
+                                v.data_ptr(), theta.data_ptr(), conv.data_ptr(), iters.data_ptr(), mis.data_ptr(), ws.data_ptr(),
+                                ws.numel(), stream), 'gns_pf_solve')
+        out = [v, theta, conv.bool(), iters, mis]
     if in_dev != dev:
         out = [t.to(in_dev) for t in out]
     if single:
         out = [t[0] for t in out]
     return PowerFlowResult(*out)
+
+
+def _outputs(Bt, N, dev):
+    v = torch.empty(Bt, N, dtype=torch.float64, device=dev)
+    return (v, torch.empty_like(v), torch.empty(Bt, dtype=torch.uint8, device=dev), torch.empty(Bt, dtype=torch.int32, device=dev),
+            torch.empty(Bt, dtype=torch.float64, device=dev))
+
+
+def _solve_mixed(lib, cfg, plan, buses, lines, generators, v0, theta0):
+    """One ``gns_pf_solve_set`` launch over ``plan`` (``_plan_mixed``); returns the five outputs as ``newton_raphson`` does."""
+    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
+    if plan.member_off.size == 0:                # every grid's topology islands a bus: nothing to solve
+        nan = float('nan')
+        return [torch.full((Bt, N), nan, dtype=torch.float64, device=dev), torch.full((Bt, N), nan, dtype=torch.float64, device=dev),
+                torch.zeros(Bt, dtype=torch.bool, device=dev), torch.full((Bt,), -1, dtype=torch.int32, device=dev),
+                torch.full((Bt,), nan, dtype=torch.float64, device=dev)]
+    ts, members = plan.topo_set, plan.member_off
+    nbytes = ctypes.c_size_t()
+    _check(lib.gns_pf_workspace_bytes_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.words, members.ctypes.data, members.size, Bt,
+                                          ctypes.byref(nbytes)), 'gns_pf_workspace_bytes_set')
+    ws = _gns._workspace(nbytes.value, dev)
+    v, theta, conv, iters, mis = _outputs(Bt, N, dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.gns_pf_solve_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.blob.data_ptr(), ts.words, members.ctypes.data,
+                                members.size, plan.grid_off.data_ptr(), plan.order.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                                generators.data_ptr(), Bt, v0.data_ptr() if v0 is not None else None,
+                                theta0.data_ptr() if theta0 is not None else None, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
+                                iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_pf_solve_set')
+    return [v, theta, conv.bool(), iters, mis]

@@ -327,10 +327,37 @@ def solvable_grids(case_nr: int, batch: int, seed: int = 0, angle_spread: float 
     grids.  At angle_spread 0.1 a flat-start Newton-Raphson recovers the chosen point; larger spreads can give grids with other
     valid solutions (the solver may converge to one of those)."""
     buses, lines, gens = synth_grids(case_nr, batch, seed=seed, device=device)
-    dev = buses.device
-    n = buses.shape[1]
+    slack_bus = _solvable_slack(case_nr)
+    v, theta = _draw_solution(gens, buses.shape[1], slack_bus, seed, angle_spread)
+    buses, gens = manufacture_solution(buses, lines, gens, slack_bus, v, theta)
+    return buses, lines, gens, slack_bus, v, theta
+
+
+def solvable_contingency_grids(case_nr: int, batch: int, outages, seed: int = 0, angle_spread: float = 0.1, device='cpu',
+                               shuffle: bool = False):
+    """N-1 contingency variants (``contingency_grids``) made solvable as ``solvable_grids`` makes its grids: the same slack, the
+    same draws of ``(v, theta)``, then ``manufacture_solution`` on each variant's own lines.  A batch that mixes topologies, for
+    ``powerflow.newton_raphson(..., mixed_topologies=True)``.  An outage that islands buses from the slack is allowed: its ``(v,
+    theta)`` is not a reachable solution (the solver reports such grids as not solved).
+
+    Returns ``(buses, lines, generators, slack_bus, v, theta, outage)``."""
+    buses, lines, gens, outage = contingency_grids(case_nr, batch, outages, seed=seed, device=device, shuffle=shuffle)
+    slack_bus = _solvable_slack(case_nr)
+    v, theta = _draw_solution(gens, buses.shape[1], slack_bus, seed, angle_spread)
+    buses, gens = manufacture_solution(buses, lines, gens, slack_bus, v, theta)
+    return buses, lines, gens, slack_bus, v, theta, outage
+
+
+def _solvable_slack(case_nr):
+    """The slack of ``solvable_grids``: the bus of the case's generator with the largest Pmax (1-based)."""
     c = base_case(case_nr)
-    slack_bus = int(c['gen_bus'][int(np.argmax(c['Pmax']))])
+    return int(c['gen_bus'][int(np.argmax(c['Pmax']))])
+
+
+def _draw_solution(gens, n, slack_bus, seed, angle_spread):
+    """The chosen point of ``solvable_grids``: theta ~ U[-angle_spread, angle_spread] (0 at the slack), |V| ~ U[0.95, 1.05], then
+    the vg of the first generator listed on each generator bus.  float64 ``(v, theta) [batch, n]`` on ``gens``' device."""
+    batch, dev = gens.shape[0], gens.device
     f64 = torch.float64
     theta = (counter_uniform(seed, 201, 0, batch, n, dev).to(f64) * 2.0 - 1.0) * float(angle_spread)
     theta[:, slack_bus - 1] = 0.0
@@ -340,5 +367,4 @@ def solvable_grids(case_nr: int, batch: int, seed: int = 0, angle_spread: float 
     at = torch.where(first, gb, torch.full_like(gb, n))                         # non-first generators write a dummy column
     vg = torch.cat([v, torch.zeros(batch, 1, dtype=f64, device=dev)], dim=1).scatter(1, at, gens[..., 4].to(f64))[:, :n]
     v = torch.where(torch.zeros(batch, n + 1, dtype=torch.bool, device=dev).scatter(1, at, True)[:, :n], vg, v)
-    buses, gens = manufacture_solution(buses, lines, gens, slack_bus, v, theta)
-    return buses, lines, gens, slack_bus, v, theta
+    return v, theta

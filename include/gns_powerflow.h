@@ -66,6 +66,10 @@ typedef struct gns_pf_info {
   int32_t n_ops;      /* elimination + triangular-solve operations per Newton iteration */
   int32_t n_steps;    /* barrier-separated steps those operations are scheduled into */
   int64_t lds_bytes;  /* LDS image of one grid; > GNS_PF_LDS_MAX_BYTES: gns_pf_solve returns GNS_EUNSUPPORTED */
+  int32_t n_adj_ops;      /* operations of the transposed-solve program of gns_pf_adjoint (J^T x = b on the factor) */
+  int32_t n_adj_steps;    /* barrier-separated steps of that program */
+  int32_t n_factor_steps; /* leading steps of the solve program that hold every factorisation operation: gns_pf_adjoint
+                             factors J with these (0 when J is diagonal) */
 } gns_pf_info;
 
 /* Host analysis.  From 0-based f_bus / t_bus [E], generator bus [Gn] HOST arrays and the 0-based slack bus: bus roles, the Y-bus
@@ -119,6 +123,57 @@ int gns_pf_solve_set(const gns_pf_config* cfg, const void* set_host, const void*
                      const double* v0, const double* theta0,
                      double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* Gradients (the adjoint).  gns_pf_adjoint takes the inputs of a gns_pf_solve call (cfg, blob, buses, lines, generators, Bt; not
+ * the warm start), that call's outputs v, theta [Bt,N] fp64 and converged [Bt] uint8, and the incoming gradients grad_v,
+ * grad_theta [Bt,N] fp64 of a loss l(v, theta) (either may be NULL: zero).  It writes dl/d(input) into grad_buses [Bt,N,6],
+ * grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32, each of which may be NULL (not computed).  Every element of each non-NULL
+ * output is written (overwritten, not accumulated).
+ *
+ * Method: the implicit function theorem at the solution F(x*, p) = 0, x = [theta at PV+PQ ; |V| at PQ]:
+ *   J^T lambda = dl/dx = [grad_theta at PV+PQ ; grad_v at PQ],   dl/dp = -(dF/dp)^T lambda  (+ the direct grad_v of a set |V|),
+ * with J the Newton Jacobian at (v, theta), factored by the leading n_factor_steps steps of the blob's solve program (on a zero
+ * right-hand side), and lambda from its transposed-solve program (U^T y = g, then L^T lambda = y; gns_pf_info.n_adj_ops /
+ * n_adj_steps).  One wave per grid, the solve's
+ * LDS image (lambda_P, lambda_Q in the injection vectors): every topology the solve accepts, the adjoint accepts.  Workspace: the
+ * Y-bus values only, so gns_pf_workspace_bytes / gns_pf_workspace_bytes_set give its size.  fp64 throughout, rounded once to fp32.
+ * No atomics: a grid's gradient is bit-identical alone, in any batch, in any order and from run to run.
+ *
+ * Contract (lambda_P at PV+PQ buses, lambda_Q at PQ buses, both 0 elsewhere; signs follow F = Re/Im(V conj(YV)) - S_spec,
+ * S_spec = sum Pg - Pd - j Qd):
+ *   buses      col 2 Pd: -lambda_P;  col 3 Qd: -lambda_Q;  col 4 Gs: -|V|^2 lambda_P;  col 5 Bs: +|V|^2 lambda_Q.  All 0 at the
+ *              slack; Qd and Bs 0 at PV buses.  Cols 0, 1 (id, type): 0.
+ *   lines      cols 2-6 (r, x, b, tau, shift): -lambda^T dF/dp through the line's four Y-bus stamps (ff, tt, ft, tf of makeYbus);
+ *              parallel lines each get their own.  Cols 0, 1 (ids): 0.  The line's buses are read from its id columns, which must
+ *              be those the blob was prepared from (a line whose ids are not buses of the grid gets a NaN row).
+ *   generators col 6 Pg: +lambda_P at its bus.  Col 4 vg: for the first generator listed on a PV or slack bus only (its vg is
+ *              that bus's |V|), grad_v of the bus plus -lambda^T dF/d|V_bus|; 0 for every other generator.  Cols 0-3, 5 (bus,
+ *              Pmax, Pmin, Pg_set, qg): 0.
+ *   The slack's theta is constant: its incoming gradient is ignored.  Warm starts are not differentiated.
+ *   A grid whose incoming grad_v and grad_theta rows are all exactly zero gets zero rows, whatever its convergence.  Otherwise a
+ *   grid with converged == 0, or whose factor has a zero or non-finite pivot, gets NaN in all three rows.
+ *
+ * Errors as gns_pf_solve: GNS_EINVAL for a NULL cfg / blob / input / v / theta / converged / workspace or a config that does not
+ * match the blob, GNS_ESIZE for a short workspace, GNS_EUNSUPPORTED for an LDS image above the limit.  With all three outputs
+ * NULL nothing is launched. */
+int gns_pf_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                   const float* buses, const float* lines, const float* generators, int64_t Bt,
+                   const double* v, const double* theta, const uint8_t* converged,
+                   const double* grad_v, const double* grad_theta,
+                   float* grad_buses, float* grad_lines, float* grad_generators,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/* The adjoint of a gns_pf_solve_set call: its set, members, grid_off and order (grid g's rows whatever the order), then the
+ * arguments of gns_pf_adjoint.  Each grid's blob is checked on the device as gns_pf_solve_set does; a grid without a usable blob
+ * (an islanding topology: grid_off -1) gets NaN rows, or zero rows when its incoming gradient is zero.  Results are bit-identical
+ * to gns_pf_adjoint on the grid's blob.  Errors as gns_pf_solve_set. */
+int gns_pf_adjoint_set(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                       const int32_t* member_off, int32_t n_member, const int32_t* grid_off, const int32_t* order,
+                       const float* buses, const float* lines, const float* generators, int64_t Bt,
+                       const double* v, const double* theta, const uint8_t* converged,
+                       const double* grad_v, const double* grad_theta,
+                       float* grad_buses, float* grad_lines, float* grad_generators,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -23,7 +23,8 @@ class PfConfig(ctypes.Structure):
 
 class PfInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('n_bus', 'n_line', 'n_gen', 'slack', 'n_pv', 'n_pq', 'dim', 'nnz_jac', 'nnz_lu',
-                                              'nnz_ybus', 'n_ops', 'n_steps')] + [('lds_bytes', ctypes.c_int64)]
+                                              'nnz_ybus', 'n_ops', 'n_steps')] + [('lds_bytes', ctypes.c_int64)] + \
+                [(n, ctypes.c_int32) for n in ('n_adj_ops', 'n_adj_steps', 'n_factor_steps')]
 
 
 def library_path():
@@ -86,6 +87,8 @@ def load_library():
     lib.gns_pf_solve.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.gns_pf_workspace_bytes_set.argtypes = [pfcp, vp, sz, vp, i32, i64, ctypes.POINTER(sz)]
     lib.gns_pf_solve_set.argtypes = [pfcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_pf_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_pf_adjoint_set.argtypes = [pfcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     for f in PF_EXPORTS:
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
@@ -107,7 +110,7 @@ EXPORTS = ('gns_version', 'gns_param_count', 'gns_config_supported', 'gns_topolo
 
 # the power-flow solver's C-ABI (include/gns_powerflow.h)
 PF_EXPORTS = ('gns_pf_topology_bytes', 'gns_pf_prepare_topology', 'gns_pf_topology_info', 'gns_pf_workspace_bytes', 'gns_pf_solve',
-              'gns_pf_workspace_bytes_set', 'gns_pf_solve_set')
+              'gns_pf_workspace_bytes_set', 'gns_pf_solve_set', 'gns_pf_adjoint', 'gns_pf_adjoint_set')
 
 
 def set_option(name: str, value: int) -> None:

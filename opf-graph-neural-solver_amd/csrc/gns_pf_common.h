@@ -22,9 +22,18 @@ enum {
   PH_PIVOT,      // [dim]    factor slot of each pivot
   PH_STEP_PTR,   // [nsteps+1] operations of each step ...
   PH_OPS,        // [2 nops] ... as (dst | a << 16, b): F[dst] -= F[a] * F[b], or F[dst] /= F[a] when b == -1 (8-byte aligned)
+  // the transposed-solve program of the adjoint (gns_pf_adjoint): J^T x = rhs on the factor PH_OPS leaves in the slots, as U^T y = rhs
+  // then L^T x = y, in the format and schedule of PH_OPS.  The solve kernel reads none of it.
+  PH_T_NOPS,     // operations of the transposed program
+  PH_T_NSTEPS,   // its barrier-separated steps
+  PH_T_STEP_PTR, // [t_nsteps+2] operations of each step ..., then the number of leading steps of PH_STEP_PTR that hold every
+                 //   factor operation (the adjoint factors J with those; the solve operations among them see a zero rhs)
+  PH_T_OPS,      // [2 t_nops] ... as in PH_OPS (8-byte aligned)
   PF_HDR_WORDS = 32,
   PF_SET_ALIGN_WORDS = 16   // blobs of a set (gns_pf_solve_set) start at multiples of 16 words (64 bytes)
 };
+
+static_assert(PH_T_OPS < PF_HDR_WORDS, "the header holds every word offset");
 
 #if defined(__HIPCC__)
 #define PF_HOST_DEVICE __host__ __device__

@@ -42,6 +42,38 @@ std::vector<int> min_degree_order(int N, int slack, const std::vector<std::set<i
   return order;
 }
 
+struct Op { int dst, a, b; };
+
+// List scheduling: an operation goes into the first step after every step that wrote what it reads or that read what it writes;
+// within a step no two operations touch a slot one of them writes, so its operations run in any order and on any lane.
+// Fills step_ptr [nsteps+1] and ops [2 nops] (layout of PH_STEP_PTR / PH_OPS); returns nsteps.
+int schedule(const std::vector<Op>& prog, int nslots, std::vector<int32_t>& step_ptr, std::vector<int32_t>& ops) {
+  std::vector<int> lw(nslots, -1), lr(nslots, -1), step(prog.size());
+  int nsteps = 0;
+  for (size_t o = 0; o < prog.size(); ++o) {
+    const Op& op = prog[o];
+    int s = std::max(lw[op.dst], lr[op.dst]) + 1;
+    s = std::max(s, lw[op.a] + 1);
+    if (op.b >= 0) s = std::max(s, lw[op.b] + 1);
+    step[o] = s;
+    lw[op.dst] = s;
+    lr[op.a] = std::max(lr[op.a], s);
+    if (op.b >= 0) lr[op.b] = std::max(lr[op.b], s);
+    nsteps = std::max(nsteps, s + 1);
+  }
+  step_ptr.assign(nsteps + 1, 0);
+  ops.assign(2 * prog.size(), 0);
+  for (size_t o = 0; o < prog.size(); ++o) ++step_ptr[step[o] + 1];
+  for (int s = 0; s < nsteps; ++s) step_ptr[s + 1] += step_ptr[s];
+  std::vector<int32_t> c(step_ptr.begin(), step_ptr.end() - 1);
+  for (size_t o = 0; o < prog.size(); ++o) {
+    const int q = c[step[o]]++;
+    ops[2 * q] = (int32_t)((uint32_t)prog[o].dst | ((uint32_t)prog[o].a << 16));
+    ops[2 * q + 1] = prog[o].b;
+  }
+  return nsteps;
+}
+
 int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& out) {
   if (N <= 0 || E < 0 || Gn < 0 || (E > 0 && (!f || !t)) || (Gn > 0 && !gb)) return GNS_EINVAL;
   if (slack < 0 || slack >= N) return GNS_ETOPOLOGY;
@@ -144,7 +176,6 @@ int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int3
   for (int k = 0; k < dim; ++k) pivot[k] = slot[k][k];
 
   // the sequential program: right-looking LU, forward solve with unit L, backward solve with U
-  struct Op { int dst, a, b; };
   std::vector<Op> prog;
   for (int k = 0; k < dim; ++k) {
     for (int i : lower[k]) prog.push_back({slot[i][k], slot[k][k], -1});
@@ -155,32 +186,27 @@ int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int3
     prog.push_back({nnzLU + k, slot[k][k], -1});
     for (int i = 0; i < k; ++i) if (P[i][k]) prog.push_back({nnzLU + i, slot[i][k], nnzLU + k});
   }
-  // list scheduling: an operation goes into the first step after every step that wrote what it reads or that read what it writes;
-  // within a step no two operations touch a slot one of them writes, so its operations run in any order and on any lane
-  std::vector<int> lw(nslots, -1), lr(nslots, -1), step(prog.size());
-  int nsteps = 0;
-  for (size_t o = 0; o < prog.size(); ++o) {
-    const Op& op = prog[o];
-    int s = std::max(lw[op.dst], lr[op.dst]) + 1;
-    s = std::max(s, lw[op.a] + 1);
-    if (op.b >= 0) s = std::max(s, lw[op.b] + 1);
-    step[o] = s;
-    lw[op.dst] = s;
-    lr[op.a] = std::max(lr[op.a], s);
-    if (op.b >= 0) lr[op.b] = std::max(lr[op.b], s);
-    nsteps = std::max(nsteps, s + 1);
+  std::vector<int32_t> step_ptr, ops;
+  const int nsteps = schedule(prog, nslots, step_ptr, ops);
+
+  // the transposed solve of the adjoint on the same factor: U^T y = rhs (column k of U^T is row k of U) forward, then
+  // L^T x = y (unit diagonal) backward
+  std::vector<Op> tprog;
+  for (int k = 0; k < dim; ++k) {
+    tprog.push_back({nnzLU + k, slot[k][k], -1});
+    for (int j : upper[k]) tprog.push_back({nnzLU + j, slot[k][j], nnzLU + k});
   }
-  std::vector<int32_t> step_ptr(nsteps + 1, 0), ops(2 * prog.size());
-  for (size_t o = 0; o < prog.size(); ++o) ++step_ptr[step[o] + 1];
-  for (int s = 0; s < nsteps; ++s) step_ptr[s + 1] += step_ptr[s];
-  {
-    std::vector<int32_t> c(step_ptr.begin(), step_ptr.end() - 1);
-    for (size_t o = 0; o < prog.size(); ++o) {
-      const int q = c[step[o]]++;
-      ops[2 * q] = (int32_t)((uint32_t)prog[o].dst | ((uint32_t)prog[o].a << 16));
-      ops[2 * q + 1] = prog[o].b;
-    }
-  }
+  for (int k = dim - 1; k >= 0; --k)
+    for (int j = 0; j < k; ++j) if (P[k][j]) tprog.push_back({nnzLU + j, slot[k][j], nnzLU + k});
+  std::vector<int32_t> t_step_ptr, t_ops;
+  const int t_nsteps = schedule(tprog, nslots, t_step_ptr, t_ops);
+  // the adjoint factors J with the solve program's steps up to its last factor operation (the solve ops in them see a zero
+  // right-hand side): their count follows the transposed program's step pointers
+  int nf = 0;
+  for (int s = 0; s < nsteps; ++s)
+    for (int q = step_ptr[s]; q < step_ptr[s + 1]; ++q)
+      if ((ops[2 * q] & 0xFFFF) < nnzLU) nf = s + 1;
+  t_step_ptr.push_back(nf);
 
   PfBlob b;
   b.w[PH_MAGIC] = GNS_PF_MAGIC; b.w[PH_N] = N; b.w[PH_E] = E; b.w[PH_GN] = Gn; b.w[PH_SLACK] = slack;
@@ -191,6 +217,10 @@ int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int3
   b.put(PH_JSLOT, jslot); b.put(PH_PIVOT, pivot); b.put(PH_STEP_PTR, step_ptr);
   if (b.w.size() % 2) b.w.push_back(0);
   b.put(PH_OPS, ops);
+  b.w[PH_T_NOPS] = (int32_t)tprog.size(); b.w[PH_T_NSTEPS] = t_nsteps;
+  b.put(PH_T_STEP_PTR, t_step_ptr);
+  if (b.w.size() % 2) b.w.push_back(0);
+  b.put(PH_T_OPS, t_ops);
   b.w[PH_TOTAL] = (int32_t)b.w.size();
   out.swap(b.w);
   return GNS_OK;
@@ -231,5 +261,7 @@ extern "C" int gns_pf_topology_info(const void* topo_host, gns_pf_info* info) {
   info->n_pv = h[PH_NPV]; info->n_pq = h[PH_NPQ]; info->dim = h[PH_DIM]; info->nnz_jac = h[PH_NNZJ]; info->nnz_lu = h[PH_NNZLU];
   info->nnz_ybus = h[PH_NNZY]; info->n_ops = h[PH_NOPS]; info->n_steps = h[PH_NSTEPS];
   info->lds_bytes = pf_lds_bytes(h);
+  info->n_adj_ops = h[PH_T_NOPS]; info->n_adj_steps = h[PH_T_NSTEPS];
+  info->n_factor_steps = h[h[PH_T_STEP_PTR] + h[PH_T_NSTEPS] + 1];
   return GNS_OK;
 }

@@ -17,6 +17,73 @@ __device__ inline double pf_wave_max(double x) {
   return x;
 }
 
+// Y-bus values of row i (makeYbus) into Y[y_ptr[i] .. y_ptr[i+1]): the line stamps of every entry, Gs + jBs on the diagonal
+__device__ __forceinline__ void pf_ybus_row(const int i, const int32_t* y_ptr, const int32_t* y_diag, const int32_t* st_ptr,
+                                            const int32_t* st, const float* bus, const float* line, double2* Y) {
+  for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
+    double yr = 0.0, yi = 0.0;
+    if (p == y_diag[i]) { yr = (double)bus[i * 6 + 4]; yi = (double)bus[i * 6 + 5]; }
+    for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
+      const int e = st[q] >> 2, kind = st[q] & 3;
+      const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
+      const double den = r * r + x * x;
+      const double ysr = r / den, ysi = -x / den;
+      double ar, ai;
+      if (kind == 0) { ar = ysr / (tau * tau); ai = (ysi + 0.5 * b) / (tau * tau); }
+      else if (kind == 1) { ar = ysr; ai = ysi + 0.5 * b; }
+      else {
+        const double c = cos(sh), s = kind == 2 ? sin(sh) : -sin(sh);   // -y_s e^{+-j shift} / tau
+        ar = -(ysr * c - ysi * s) / tau;
+        ai = -(ysr * s + ysi * c) / tau;
+      }
+      yr += ar; yi += ai;
+    }
+    Y[p] = make_double2(yr, yi);
+  }
+}
+
+// Row i (not the slack) of the Jacobian (MATPOWER dSbus_dV, polar) into its factor slots, at V = Vr + j Vi with I = Ir + j Ii = Y V
+__device__ __forceinline__ void pf_jacobian_row(const int i, const int slack, const int32_t* y_ptr, const int32_t* y_col,
+                                                const int32_t* jslot, const double2* Y, const double* Vm, const double* Vr,
+                                                const double* Vi, const double* Ir, const double* Ii, double* F) {
+  const double vri = Vr[i], vii = Vi[i];
+  for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
+    const int k = y_col[p];
+    if (k == slack) continue;
+    const double2 y = Y[p];
+    const double a = y.x * Vr[k] - y.y * Vi[k], b = y.x * Vi[k] + y.y * Vr[k];   // Y_ik V_k
+    const double cr = vri * a + vii * b, ci = vii * a - vri * b;                 // V_i conj(Y_ik V_k)
+    double dar = ci, dai = -cr;                                                  // dS_i / dtheta_k
+    double dmr = cr, dmi = ci;                                                   // |V_k| dS_i / d|V_k|
+    if (k == i) {
+      const double P = vri * Ir[i] + vii * Ii[i], Q = vii * Ir[i] - vri * Ii[i];
+      dar -= Q; dai += P;
+      dmr += P; dmi += Q;
+    }
+    dmr /= Vm[k]; dmi /= Vm[k];
+    const int s0 = jslot[4 * p], s1 = jslot[4 * p + 1], s2 = jslot[4 * p + 2], s3 = jslot[4 * p + 3];
+    if (s0 >= 0) F[s0] = dar;
+    if (s1 >= 0) F[s1] = dmr;
+    if (s2 >= 0) F[s2] = dai;
+    if (s3 >= 0) F[s3] = dmi;
+  }
+}
+
+// One op program of the blob (PH_STEP_PTR / PH_OPS, or the transposed PH_T_*): F[dst] -= F[a] F[b] or F[dst] /= F[a],
+// independent within a step, a barrier after each step
+__device__ __forceinline__ void pf_run_program(const int nsteps, const int32_t* step_ptr, const int2* ops, double* F, const int lane) {
+  for (int s = 0; s < nsteps; ++s) {
+    const int q1 = step_ptr[s + 1];
+    for (int q = step_ptr[s] + lane; q < q1; q += PF_THREADS) {
+      const int2 op = ops[q];
+      const int dst = op.x & 0xFFFF, a = (int)((uint32_t)op.x >> 16);
+      if (op.y < 0) F[dst] = F[dst] / F[a];
+      else F[dst] -= F[a] * F[op.y];
+    }
+    __syncthreads();
+  }
+}
+
 // The solve of grid g on the blob at topo: the body of both kernels below.  Its Y-bus values go to ybus_ws + g * (the blob's
 // nnz(Y)), or with SET to ybus_ws + g * ystride (the largest nnz(Y) of a set).
 template <bool SET>
@@ -63,26 +130,7 @@ __device__ __forceinline__ void pf_solve_grid(const int32_t* topo, const int g, 
 
   // Y-bus values (makeYbus), specified injections, starting point
   for (int i = lane; i < N; i += PF_THREADS) {
-    for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
-      double yr = 0.0, yi = 0.0;
-      if (p == y_diag[i]) { yr = (double)bus[i * 6 + 4]; yi = (double)bus[i * 6 + 5]; }
-      for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
-        const int e = st[q] >> 2, kind = st[q] & 3;
-        const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
-        const double den = r * r + x * x;
-        const double ysr = r / den, ysi = -x / den;
-        double ar, ai;
-        if (kind == 0) { ar = ysr / (tau * tau); ai = (ysi + 0.5 * b) / (tau * tau); }
-        else if (kind == 1) { ar = ysr; ai = ysi + 0.5 * b; }
-        else {
-          const double c = cos(sh), s = kind == 2 ? sin(sh) : -sin(sh);   // -y_s e^{+-j shift} / tau
-          ar = -(ysr * c - ysi * s) / tau;
-          ai = -(ysr * s + ysi * c) / tau;
-        }
-        yr += ar; yi += ai;
-      }
-      Y[p] = make_double2(yr, yi);
-    }
+    pf_ybus_row(i, y_ptr, y_diag, st_ptr, st, bus, line, Y);
     double pg = 0.0;
     for (int q = gen_ptr[i]; q < gen_ptr[i + 1]; ++q) pg += (double)gen[gen_idx[q] * 7 + 6];
     Psp[i] = pg - (double)bus[i * 6 + 2];
@@ -136,43 +184,12 @@ __device__ __forceinline__ void pf_solve_grid(const int32_t* topo, const int g, 
     // Jacobian (MATPOWER dSbus_dV, polar) into its factor slots; fill slots start at zero
     for (int s = lane; s < nnzLU; s += PF_THREADS) F[s] = 0.0;
     __syncthreads();
-    for (int i = lane; i < N; i += PF_THREADS) {
-      if (i == slack) continue;
-      const double vri = Vr[i], vii = Vi[i];
-      for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
-        const int k = y_col[p];
-        if (k == slack) continue;
-        const double2 y = Y[p];
-        const double a = y.x * Vr[k] - y.y * Vi[k], b = y.x * Vi[k] + y.y * Vr[k];   // Y_ik V_k
-        const double cr = vri * a + vii * b, ci = vii * a - vri * b;                 // V_i conj(Y_ik V_k)
-        double dar = ci, dai = -cr;                                                  // dS_i / dtheta_k
-        double dmr = cr, dmi = ci;                                                   // |V_k| dS_i / d|V_k|
-        if (k == i) {
-          const double P = vri * Ir[i] + vii * Ii[i], Q = vii * Ir[i] - vri * Ii[i];
-          dar -= Q; dai += P;
-          dmr += P; dmi += Q;
-        }
-        dmr /= Vm[k]; dmi /= Vm[k];
-        const int s0 = jslot[4 * p], s1 = jslot[4 * p + 1], s2 = jslot[4 * p + 2], s3 = jslot[4 * p + 3];
-        if (s0 >= 0) F[s0] = dar;
-        if (s1 >= 0) F[s1] = dmr;
-        if (s2 >= 0) F[s2] = dai;
-        if (s3 >= 0) F[s3] = dmi;
-      }
-    }
+    for (int i = lane; i < N; i += PF_THREADS)
+      if (i != slack) pf_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
     __syncthreads();
 
     // LU factorisation and both triangular solves: F[dst] -= F[a] F[b] or F[dst] /= F[a], independent within a step
-    for (int s = 0; s < nsteps; ++s) {
-      const int q1 = step_ptr[s + 1];
-      for (int q = step_ptr[s] + lane; q < q1; q += PF_THREADS) {
-        const int2 op = ops[q];
-        const int dst = op.x & 0xFFFF, a = (int)((uint32_t)op.x >> 16);
-        if (op.y < 0) F[dst] = F[dst] / F[a];
-        else F[dst] -= F[a] * F[op.y];
-      }
-      __syncthreads();
-    }
+    pf_run_program(nsteps, step_ptr, ops, F, lane);
 
     // the update, only if every pivot is a finite non-zero and the new iterate is finite
     for (int k = lane; k < dim; k += PF_THREADS) {
@@ -245,6 +262,257 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pf_set_kernel(const int32_t* _
   }
   pf_solve_grid<true>(topo, g, buses, lines, gens, v0, th0, v_out, th_out, conv_out, it_out, mis_out, ybus_ws, nnzy_max, max_iter,
                       tol);
+}
+
+// ---- the adjoint (gns_pf_adjoint): gradients of a loss of (v, theta) at a converged solution, by the implicit function theorem:
+// J^T lambda = dl/dx at the solution, dl/dp = -lambda^T dF/dp (include/gns_powerflow.h, "Gradients").
+
+// Every element of grid g's three gradient rows set to x
+__device__ __forceinline__ void pf_adjoint_fill(const int g, const int N, const int E, const int Gn, const float x, float* gb_out,
+                                                float* gl_out, float* gg_out) {
+  const int lane = threadIdx.x;
+  if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = x;
+  if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = x;
+  if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = x;
+}
+
+// Whether grid g's incoming gradient rows are all exactly zero (a NULL row counts as zero)
+__device__ __forceinline__ bool pf_zero_incoming(const int g, const int N, const double* gv, const double* gth) {
+  bool nz = false;
+  for (int i = threadIdx.x; i < N; i += PF_THREADS) {
+    if (gv) nz |= gv[(size_t)g * N + i] != 0.0;
+    if (gth) nz |= gth[(size_t)g * N + i] != 0.0;
+  }
+  return __ballot(nz) == 0;
+}
+
+// The Y-bus entry (i, k) of the blob's CSR pattern (columns ascending), -1 if it is not there
+__device__ __forceinline__ int pf_find_entry(const int32_t* y_ptr, const int32_t* y_col, const int i, const int k) {
+  int lo = y_ptr[i], hi = y_ptr[i + 1];
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (y_col[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < y_ptr[i + 1] && y_col[lo] == k ? lo : -1;
+}
+
+// The adjoint of grid g (converged, with a non-zero incoming gradient) on the blob at topo: the body of both adjoint kernels.
+// LDS: the solve's image, lambda in the Psp / Qsp vectors.  The Y-bus values go to the workspace as in pf_solve_grid.
+template <bool SET>
+__device__ __forceinline__ void pf_adjoint_grid(const int32_t* topo, const int g, const float* buses, const float* lines,
+                                                const double* v_in, const double* th_in, const double* gv,
+                                                const double* gth, float* gb_out, float* gl_out, float* gg_out, double2* ybus_ws,
+                                                int ystride) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x;
+  const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN], slack = topo[PH_SLACK], dim = topo[PH_DIM];
+  const int nnzLU = topo[PH_NNZLU], nnzY = topo[PH_NNZY], t_nsteps = topo[PH_T_NSTEPS];
+  const int32_t* role = topo + topo[PH_ROLE];
+  const int32_t* th_idx = topo + topo[PH_TH_IDX];
+  const int32_t* vm_idx = topo + topo[PH_VM_IDX];
+  const int32_t* gen_ptr = topo + topo[PH_GEN_PTR];
+  const int32_t* gen_idx = topo + topo[PH_GEN_IDX];
+  const int32_t* y_ptr = topo + topo[PH_Y_PTR];
+  const int32_t* y_col = topo + topo[PH_Y_COL];
+  const int32_t* y_diag = topo + topo[PH_Y_DIAG];
+  const int32_t* st_ptr = topo + topo[PH_ST_PTR];
+  const int32_t* st = topo + topo[PH_ST];
+  const int32_t* jslot = topo + topo[PH_JSLOT];
+  const int32_t* pivot = topo + topo[PH_PIVOT];
+  const int32_t* step_ptr = topo + topo[PH_STEP_PTR];
+  const int2* ops = reinterpret_cast<const int2*>(topo + topo[PH_OPS]);
+  const int32_t* t_step_ptr = topo + topo[PH_T_STEP_PTR];
+  const int2* t_ops = reinterpret_cast<const int2*>(topo + topo[PH_T_OPS]);
+
+  double* F = lds;                       // [nnzLU] factor, then [dim] right-hand side / lambda
+  double* rhs = lds + nnzLU;
+  double* Vm = rhs + dim;
+  double* Va = Vm + N;
+  double* Vr = Va + N;
+  double* Vi = Vr + N;
+  double* Ir = Vi + N;
+  double* Ii = Ir + N;
+  double* lamP = Ii + N;                 // the solve's Psp / Qsp: lambda of each bus's P and Q mismatch (0 where there is none)
+  double* lamQ = lamP + N;
+  const float* bus = buses + (size_t)g * N * 6;
+  const float* line = lines + (size_t)g * E * 7;
+  double2* Y = ybus_ws + (size_t)g * (SET ? ystride : nnzY);
+
+  // the solution, the Y-bus values and I = Y V there
+  for (int i = lane; i < N; i += PF_THREADS) {
+    pf_ybus_row(i, y_ptr, y_diag, st_ptr, st, bus, line, Y);
+    const double vm = v_in[(size_t)g * N + i], va = th_in[(size_t)g * N + i];
+    Vm[i] = vm; Va[i] = va;
+    Vr[i] = vm * cos(va); Vi[i] = vm * sin(va);
+  }
+  for (int s = lane; s < nnzLU + dim; s += PF_THREADS) F[s] = 0.0;
+  __syncthreads();
+  for (int i = lane; i < N; i += PF_THREADS) {
+    double ir = 0.0, ii = 0.0;
+    for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
+      const int k = y_col[p];
+      const double2 y = Y[p];
+      ir += y.x * Vr[k] - y.y * Vi[k];
+      ii += y.x * Vi[k] + y.y * Vr[k];
+    }
+    Ir[i] = ir; Ii[i] = ii;
+  }
+  __syncthreads();
+
+  // J at the solution, factored by the leading steps of the solve program (its solve operations there see a zero right-hand side)
+  for (int i = lane; i < N; i += PF_THREADS)
+    if (i != slack) pf_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
+  __syncthreads();
+  pf_run_program(t_step_ptr[t_nsteps + 1], step_ptr, ops, F, lane);   // the steps that hold the factorisation
+  bool bad = false;
+  for (int k = lane; k < dim; k += PF_THREADS) {
+    const double pv = F[pivot[k]];
+    bad |= pv == 0.0 || !pf_finite(pv);
+  }
+  if (__ballot(bad)) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
+
+  // J^T lambda = [dl/dtheta at PV+PQ ; dl/d|V| at PQ] (the slack's theta is constant: its incoming gradient is not used)
+  for (int i = lane; i < N; i += PF_THREADS) {
+    if (th_idx[i] >= 0) rhs[th_idx[i]] = gth ? gth[(size_t)g * N + i] : 0.0;
+    if (vm_idx[i] >= 0) rhs[vm_idx[i]] = gv ? gv[(size_t)g * N + i] : 0.0;
+  }
+  __syncthreads();
+  pf_run_program(t_nsteps, t_step_ptr, t_ops, F, lane);
+  for (int i = lane; i < N; i += PF_THREADS) {
+    lamP[i] = th_idx[i] >= 0 ? rhs[th_idx[i]] : 0.0;
+    lamQ[i] = vm_idx[i] >= 0 ? rhs[vm_idx[i]] : 0.0;
+  }
+  __syncthreads();
+
+  // dl/dp = -lambda^T dF/dp.  F_P = Re S - (Pg - Pd), F_Q = Im S + Qd with S_i = V_i conj(sum_k Y_ik V_k); a real parameter that
+  // moves Y_ik by c moves S_i by V_i conj(V_k) conj(c), so dl/dp = Re(conj(c) G_ik) with G_ik = -V_i conj(V_k) conj(Lambda_i),
+  // Lambda = lamP + j lamQ.  (0.0 - x rather than -x: an exact zero stays +0.)
+  if (gb_out)
+    for (int i = lane; i < N; i += PF_THREADS) {
+      float* row = gb_out + ((size_t)g * N + i) * 6;
+      const double m2 = Vm[i] * Vm[i], lp = lamP[i], lq = lamQ[i];
+      row[0] = 0.0f; row[1] = 0.0f;
+      row[2] = (float)(0.0 - lp);            // Pd
+      row[3] = (float)(0.0 - lq);            // Qd
+      row[4] = (float)(0.0 - m2 * lp);       // Gs: c = 1 on Y_ii
+      row[5] = (float)(m2 * lq);             // Bs: c = j
+    }
+  if (gg_out)
+    for (int q = lane; q < Gn; q += PF_THREADS) {      // a lane per generator, in the blob's by-bus order
+      int b = 0, hi = N;                               // the bus of generator slot q: gen_ptr[b] <= q < gen_ptr[b + 1]
+      while (hi - b > 1) {
+        const int mid = (b + hi) >> 1;
+        if (gen_ptr[mid] <= q) b = mid;
+        else hi = mid;
+      }
+      const int j = gen_idx[q];
+      double gvg = 0.0;
+      if (q == gen_ptr[b] && role[b] != 0) {           // the first generator of a PV / slack bus sets |V_b|
+        const double uc = cos(Va[b]), us = sin(Va[b]);   // e^{j theta_b}
+        double acc = 0.0;
+        for (int p = y_ptr[b]; p < y_ptr[b + 1]; ++p) {
+          const int k = y_col[p];
+          const int r = pf_find_entry(y_ptr, y_col, k, b);   // Y_kb (the pattern is structurally symmetric)
+          if (r < 0) continue;
+          const double2 y = Y[r];
+          const double wr = y.x * uc - y.y * us, wi = y.x * us + y.y * uc;   // Y_kb e^{j theta_b}
+          double dr = Vr[k] * wr + Vi[k] * wi, di = Vi[k] * wr - Vr[k] * wi;  // dS_k / d|V_b| = V_k conj(Y_kb e^{j theta_b}) ...
+          if (k == b) { dr += uc * Ir[b] + us * Ii[b]; di += us * Ir[b] - uc * Ii[b]; }   // ... + e^{j theta_b} conj(I_b) at k = b
+          acc += lamP[k] * dr + lamQ[k] * di;
+        }
+        gvg = (gv ? gv[(size_t)g * N + b] : 0.0) - acc;
+      }
+      float* row = gg_out + ((size_t)g * Gn + j) * 7;
+      row[0] = 0.0f; row[1] = 0.0f; row[2] = 0.0f; row[3] = 0.0f;
+      row[4] = (float)gvg;                             // vg
+      row[5] = 0.0f;
+      row[6] = (float)lamP[b];                         // Pg: S_spec += Pg
+    }
+  if (gl_out)
+    for (int e = lane; e < E; e += PF_THREADS) {      // a lane per line, over its four stamps
+      float* row = gl_out + ((size_t)g * E + e) * 7;
+      const float ff = line[e * 7 + 0], ft = line[e * 7 + 1];   // the id columns the blob was prepared from (1-based)
+      const int f = (int)ff - 1, t = (int)ft - 1;
+      if (!(ff == (float)(f + 1) && ft == (float)(t + 1) && f >= 0 && f < N && t >= 0 && t < N)) {
+        for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
+        continue;
+      }
+      const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
+      const double den = r * r + x * x;
+      const double ysr = r / den, ysi = -x / den, t2 = tau * tau;
+      const double cs = cos(sh), sn = sin(sh);
+      // G of the four entries: V_i conj(V_k) conj(Lambda_i), negated
+      const double mf = Vm[f] * Vm[f], mt = Vm[t] * Vm[t];
+      const double gffr = 0.0 - mf * lamP[f], gffi = mf * lamQ[f];
+      const double gttr = 0.0 - mt * lamP[t], gtti = mt * lamQ[t];
+      const double pr = Vr[f] * Vr[t] + Vi[f] * Vi[t], pi = Vi[f] * Vr[t] - Vr[f] * Vi[t];   // V_f conj(V_t)
+      const double gftr = 0.0 - (pr * lamP[f] + pi * lamQ[f]), gfti = 0.0 - (pi * lamP[f] - pr * lamQ[f]);
+      const double gtfr = 0.0 - (pr * lamP[t] - pi * lamQ[t]), gtfi = 0.0 - (0.0 - pi * lamP[t] - pr * lamQ[t]);
+      // through y_s: Gamma = G_ff / tau^2 + G_tt - e^{-j shift} G_ft / tau - e^{j shift} G_tf / tau; dy_s/dr = -y_s^2, dy_s/dx = -j y_s^2
+      const double gmr = gffr / t2 + gttr - ((cs * gftr + sn * gfti) + (cs * gtfr - sn * gtfi)) / tau;
+      const double gmi = gffi / t2 + gtti - ((cs * gfti - sn * gftr) + (cs * gtfi + sn * gtfr)) / tau;
+      const double y2r = ysr * ysr - ysi * ysi, y2i = 2.0 * ysr * ysi;
+      const double qr = y2r * gmr + y2i * gmi, qi = y2r * gmi - y2i * gmr;   // conj(y_s^2) Gamma
+      // the stamps A_ff = (y_s + jb/2) / tau^2, A_ft = -y_s e^{j shift} / tau, A_tf = -y_s e^{-j shift} / tau
+      const double a0r = ysr / t2, a0i = (ysi + 0.5 * b) / t2;
+      const double a2r = -(ysr * cs - ysi * sn) / tau, a2i = -(ysr * sn + ysi * cs) / tau;
+      const double a3r = -(ysr * cs + ysi * sn) / tau, a3i = -(ysi * cs - ysr * sn) / tau;
+      const double d_tau = 0.0 - (2.0 * (a0r * gffr + a0i * gffi) + (a2r * gftr + a2i * gfti) + (a3r * gtfr + a3i * gtfi)) / tau;
+      const double d_sh = (a2r * gfti - a2i * gftr) - (a3r * gtfi - a3i * gtfr);
+      row[0] = 0.0f; row[1] = 0.0f;
+      row[2] = (float)(0.0 - qr);                                  // r
+      row[3] = (float)(0.0 - qi);                                  // x
+      row[4] = (float)(0.5 * gffi / t2 + 0.5 * gtti);              // b: c = j/2 on Y_ff / tau^2 and Y_tt
+      row[5] = (float)d_tau;                                       // tau
+      row[6] = (float)d_sh;                                        // shift
+    }
+}
+
+__global__ __launch_bounds__(PF_THREADS) void gns_pf_adjoint_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
+                                                                    const float* __restrict__ lines, const float* __restrict__ gens,
+                                                                    const double* __restrict__ v_in, const double* __restrict__ th_in,
+                                                                    const uint8_t* __restrict__ conv_in,
+                                                                    const double* __restrict__ gv, const double* __restrict__ gth,
+                                                                    float* __restrict__ gb_out, float* __restrict__ gl_out,
+                                                                    float* __restrict__ gg_out, double2* __restrict__ ybus_ws) {
+  const int g = blockIdx.x;
+  const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN];
+  if (pf_zero_incoming(g, N, gv, gth)) { pf_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
+  if (!conv_in[g]) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
+  pf_adjoint_grid<false>(topo, g, buses, lines, v_in, th_in, gv, gth, gb_out, gl_out, gg_out, ybus_ws, 0);
+}
+
+// The adjoint over a set of blobs (gns_pf_adjoint_set): the grid, order and blob checks of gns_pf_set_kernel; a grid without a
+// usable blob gets NaN rows (zero rows when its incoming gradient is zero) and never indexes the set.
+__global__ __launch_bounds__(PF_THREADS) void gns_pf_adjoint_set_kernel(const int32_t* __restrict__ set, int64_t set_words,
+                                                                        const int32_t* __restrict__ grid_off,
+                                                                        const int32_t* __restrict__ order, int64_t Bt, int N, int E,
+                                                                        int Gn, int64_t lds_bytes, int nnzy_max,
+                                                                        const float* __restrict__ buses,
+                                                                        const float* __restrict__ lines,
+                                                                        const float* __restrict__ gens,
+                                                                        const double* __restrict__ v_in,
+                                                                        const double* __restrict__ th_in,
+                                                                        const uint8_t* __restrict__ conv_in,
+                                                                        const double* __restrict__ gv, const double* __restrict__ gth,
+                                                                        float* __restrict__ gb_out, float* __restrict__ gl_out,
+                                                                        float* __restrict__ gg_out, double2* __restrict__ ybus_ws) {
+  const int64_t w = blockIdx.x;
+  const int64_t g64 = order ? (int64_t)order[w] : w;
+  if (g64 < 0 || g64 >= Bt) return;
+  const int g = (int)g64;
+  if (pf_zero_incoming(g, N, gv, gth)) { pf_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
+  const int64_t off = grid_off[g];
+  bool ok = off >= 0 && off % PF_SET_ALIGN_WORDS == 0 && off + PF_HDR_WORDS <= set_words;
+  const int32_t* topo = set + (ok ? off : 0);
+  if (ok) {
+    ok = topo[PH_MAGIC] == GNS_PF_MAGIC && topo[PH_N] == N && topo[PH_E] == E && topo[PH_GN] == Gn &&
+         topo[PH_TOTAL] >= PF_HDR_WORDS && topo[PH_TOTAL] <= set_words - off && topo[PH_NNZY] >= 0 && topo[PH_NNZY] <= nnzy_max &&
+         pf_lds_bytes(topo) <= lds_bytes;
+  }
+  if (!ok || !conv_in[g]) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
+  pf_adjoint_grid<true>(topo, g, buses, lines, v_in, th_in, gv, gth, gb_out, gl_out, gg_out, ybus_ws, nnzy_max);
 }
 
 size_t pf_ws_bytes_nnzy(int64_t nnzy, int64_t Bt) { return (((size_t)Bt * nnzy * sizeof(double2)) + 255) & ~(size_t)255; }
@@ -354,5 +622,64 @@ extern "C" int gns_pf_solve_set(const gns_pf_config* cfg, const void* set_host, 
                      static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off, order, Bt, cfg->n_bus, cfg->n_line,
                      cfg->n_gen, lds, nnzy, buses, lines, generators, v0, theta0, v, theta, converged, iterations, mismatch,
                      static_cast<double2*>(workspace), cfg->max_iter, cfg->tol);
+  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+}
+
+extern "C" int gns_pf_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                              const float* buses, const float* lines, const float* generators, int64_t Bt,
+                              const double* v, const double* theta, const uint8_t* converged,
+                              const double* grad_v, const double* grad_theta,
+                              float* grad_buses, float* grad_lines, float* grad_generators,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  if (!cfg || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF) return GNS_EINVAL;
+  if (!v || !theta || !converged || !workspace) return GNS_EINVAL;
+  if (cfg->max_iter < 0 || !(cfg->tol >= 0.0)) return GNS_EINVAL;
+  const int32_t* h = static_cast<const int32_t*>(topo_host);
+  if (!pf_header_ok(cfg, h)) return GNS_EINVAL;
+  if (workspace_bytes < pf_ws_bytes(h, Bt)) return GNS_ESIZE;
+  gns_pf_info info;
+  if (gns_pf_topology_info(topo_host, &info) != GNS_OK) return GNS_EINVAL;
+  if (info.lds_bytes > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
+  if (!grad_buses && !grad_lines && !grad_generators) return GNS_OK;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_pf_adjoint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
+      return GNS_ELAUNCH;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(gns_pf_adjoint_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)info.lds_bytes, (hipStream_t)stream,
+                     static_cast<const int32_t*>(topo_dev), buses, lines, generators, v, theta, converged, grad_v, grad_theta,
+                     grad_buses, grad_lines, grad_generators, static_cast<double2*>(workspace));
+  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+}
+
+extern "C" int gns_pf_adjoint_set(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                                  const int32_t* member_off, int32_t n_member, const int32_t* grid_off, const int32_t* order,
+                                  const float* buses, const float* lines, const float* generators, int64_t Bt,
+                                  const double* v, const double* theta, const uint8_t* converged,
+                                  const double* grad_v, const double* grad_theta,
+                                  float* grad_buses, float* grad_lines, float* grad_generators,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+  if (!cfg || !set_dev || !grid_off || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF) return GNS_EINVAL;
+  if (!v || !theta || !converged || !workspace) return GNS_EINVAL;
+  if (cfg->max_iter < 0 || !(cfg->tol >= 0.0)) return GNS_EINVAL;
+  int32_t nnzy = 0;
+  int64_t lds = 0;
+  const int rc = pf_scan_set(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
+  if (rc != GNS_OK) return rc;
+  if (workspace_bytes < pf_ws_bytes_nnzy(nnzy, Bt)) return GNS_ESIZE;
+  if (!grad_buses && !grad_lines && !grad_generators) return GNS_OK;
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_pf_adjoint_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
+      return GNS_ELAUNCH;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(gns_pf_adjoint_set_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)lds, (hipStream_t)stream,
+                     static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off, order, Bt, cfg->n_bus, cfg->n_line,
+                     cfg->n_gen, lds, nnzy, buses, lines, generators, v, theta, converged, grad_v, grad_theta, grad_buses, grad_lines,
+                     grad_generators, static_cast<double2*>(workspace));
   return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
 }

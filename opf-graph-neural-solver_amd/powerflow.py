@@ -9,6 +9,8 @@ The semantics (bus roles, Y-bus, injections, starting point, convergence test, p
 ``include/gns_powerflow.h``; the solve runs in one HIP kernel (``csrc/gns_powerflow.hip``) in float64.  The sparse structure of
 the Jacobian and of its LU factor is analysed once per topology on the host (``csrc/gns_pf_topology.cpp``) and cached; a mixed
 batch reads its topologies from a device set of those blobs (``gns_pf_solve_set``) that grows as new topologies appear.
+With ``requires_grad`` on the inputs the solve is differentiable: its backward is one adjoint kernel (``gns_pf_adjoint`` /
+``gns_pf_adjoint_set``) on the same analysis.
 """
 from __future__ import annotations
 
@@ -17,6 +19,7 @@ from collections import namedtuple
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import gns as _gns
 from ._lib import GNS_ERRORS, PfConfig, PfInfo, load_library
@@ -256,7 +259,15 @@ def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bu
     own topology's blob; every grid's result is bit-identical to a plain call on its topology's grids.  The slack is one per call
     (given, or from grid 0's type column).  A grid whose topology leaves a bus without a path of lines to the slack is not solved:
     ``converged`` False, ``iterations`` -1, ``v`` / ``theta`` / ``mismatch`` NaN; the other grids are unaffected.  Without it a batch
-    whose id columns differ, or an islanded topology, raises ValueError."""
+    whose id columns differ, or an islanded topology, raises ValueError.
+
+    Gradients: with grad mode on and ``requires_grad`` on any of ``buses`` / ``lines`` / ``generators``, ``v`` and ``theta`` are
+    differentiable (``converged``, ``iterations``, ``mismatch`` are not).  The backward is exact at the returned solution (implicit
+    function theorem in float64, one ``gns_pf_adjoint`` / ``gns_pf_adjoint_set`` launch on the forward's analysis, no host
+    synchronisation): ``Pd, Qd, Gs, Bs``, the lines' ``r, x, b, tau, shift``, the generators' ``Pg`` and the ``vg`` of the first
+    generator on a PV / slack bus; every other column gets 0.  A grid that did not converge (or is not solved) gets NaN gradient
+    rows unless its incoming gradient is zero.  The forward outputs are bit-identical with and without gradients.  The warm
+    start is not differentiated.  Contract: ``include/gns_powerflow.h``, "Gradients"."""
     single, buses, lines, generators = _as_batch(buses, lines, generators, B, L, G)
     if buses.device.type != 'cuda':
         if not torch.cuda.is_available():
@@ -286,26 +297,129 @@ def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bu
         raise ValueError(f'mixed_topologies must be a bool, got {mixed_topologies!r}')
     lib = load_library()
     cfg = PfConfig(N, lines.shape[1], generators.shape[1], int(max_iter), float(tol))
+    v0, theta0 = (v0, theta0) if warm else (None, None)
+    plain = (buses.detach(), lines.detach(), generators.detach())   # what the analysis reads (host copies of id columns)
     if mixed_topologies:
-        plan = _plan_mixed(buses, lines, generators, slack_bus)
-        out = _solve_mixed(lib, cfg, plan, buses, lines, generators, v0 if warm else None, theta0 if warm else None)
+        plan = _plan_mixed(*plain, slack_bus)
+        ts = plan.topo_set
+        set_bufs = (ts.host, ts.blob)                 # the set as this call sees it (a later call may grow it: offsets stay)
+
+        def solve(bu, li, ge):
+            return _solve_mixed(lib, cfg, plan, bu, li, ge, v0, theta0)
+
+        def adjoint(*args):
+            return _adjoint_mixed(lib, cfg, plan, set_bufs, *args)
     else:
-        topo = _topology(buses, lines, generators, slack_bus)
-        nbytes = ctypes.c_size_t()
-        _check(lib.gns_pf_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_pf_workspace_bytes')
-        ws = _gns._workspace(nbytes.value, dev)
-        v, theta, conv, iters, mis = _outputs(Bt, N, dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib.gns_pf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                                generators.data_ptr(), Bt, v0.data_ptr() if warm else None, theta0.data_ptr() if warm else None,
-                                v.data_ptr(), theta.data_ptr(), conv.data_ptr(), iters.data_ptr(), mis.data_ptr(), ws.data_ptr(),
-                                ws.numel(), stream), 'gns_pf_solve')
-        out = [v, theta, conv.bool(), iters, mis]
+        topo = _topology(*plain, slack_bus)
+
+        def solve(bu, li, ge):
+            return _solve_plain(lib, cfg, topo, bu, li, ge, v0, theta0)
+
+        def adjoint(*args):
+            return _adjoint_plain(lib, cfg, topo, *args)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (buses, lines, generators)):
+        out = list(_NRFunction.apply(solve, adjoint, buses, lines, generators))
+    else:
+        out = solve(*plain)
     if in_dev != dev:
         out = [t.to(in_dev) for t in out]
     if single:
         out = [t[0] for t in out]
     return PowerFlowResult(*out)
+
+
+def _solve_plain(lib, cfg, topo, buses, lines, generators, v0, theta0):
+    """One ``gns_pf_solve`` launch on the batch's one topology; returns the five outputs as ``newton_raphson`` does."""
+    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
+    nbytes = ctypes.c_size_t()
+    _check(lib.gns_pf_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_pf_workspace_bytes')
+    ws = _gns._workspace(nbytes.value, dev)
+    v, theta, conv, iters, mis = _outputs(Bt, N, dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.gns_pf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                            generators.data_ptr(), Bt, v0.data_ptr() if v0 is not None else None,
+                            theta0.data_ptr() if theta0 is not None else None, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
+                            iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_pf_solve')
+    return [v, theta, conv.bool(), iters, mis]
+
+
+class _NRFunction(torch.autograd.Function):
+    """``newton_raphson`` when an input requires grad: the forward is the solve itself (``solve``: the plain or the mixed launch, with
+    its topology or ``MixedPlan`` already made), the backward one adjoint launch on the same analysis (``adjoint``:
+    ``gns_pf_adjoint`` / ``gns_pf_adjoint_set``, include/gns_powerflow.h "Gradients").  It sees the canonical device tensors after
+    ``_as_batch``: autograd routes the gradients back through the column maps, ``unsqueeze`` and ``.to``."""
+
+    @staticmethod
+    def forward(ctx, solve, adjoint, buses, lines, gens):
+        v, theta, conv, iters, mis = solve(buses, lines, gens)
+        ctx.mark_non_differentiable(conv, iters, mis)
+        ctx.set_materialize_grads(False)
+        ctx.adjoint = adjoint
+        ctx.save_for_backward(buses, lines, gens, v, theta, conv)
+        return v, theta, conv, iters, mis
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gv, gth, _gconv, _giters, _gmis):
+        buses, lines, gens, v, theta, conv = ctx.saved_tensors
+        grads = ctx.adjoint(buses, lines, gens, v, theta, conv, gv, gth, ctx.needs_input_grad[2:5])
+        return (None, None, *grads)
+
+
+def _adjoint_args(buses, lines, gens, gv, gth, need):
+    """The gradient outputs asked for (every element is written by the kernel) and the incoming gradients, contiguous."""
+    gin = [torch.empty_like(t) if n else None for t, n in zip((buses, lines, gens), need)]
+    gv, gth = (None if g is None else g.to(device=buses.device, dtype=torch.float64).contiguous() for g in (gv, gth))
+    return gin, gv, gth
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _adjoint_plain(lib, cfg, topo, buses, lines, gens, v, theta, conv, gv, gth, need):
+    """One ``gns_pf_adjoint`` launch on the forward's topology, on the forward's device and stream."""
+    Bt, dev = buses.shape[0], buses.device
+    gin, gv, gth = _adjoint_args(buses, lines, gens, gv, gth, need)
+    nbytes = ctypes.c_size_t()
+    _check(lib.gns_pf_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_pf_workspace_bytes')
+    ws = _gns._workspace(nbytes.value, dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib.gns_pf_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                                  gens.data_ptr(), Bt, v.data_ptr(), theta.data_ptr(), conv.data_ptr(), _ptr(gv), _ptr(gth),
+                                  _ptr(gin[0]), _ptr(gin[1]), _ptr(gin[2]), ws.data_ptr(), ws.numel(), stream), 'gns_pf_adjoint')
+    return gin
+
+
+def _adjoint_mixed(lib, cfg, plan, set_bufs, buses, lines, gens, v, theta, conv, gv, gth, need):
+    """One ``gns_pf_adjoint_set`` launch over the forward's ``MixedPlan`` (no second classification)."""
+    Bt, dev = buses.shape[0], buses.device
+    gin, gv, gth = _adjoint_args(buses, lines, gens, gv, gth, need)
+    members = plan.member_off
+    if members.size == 0:                         # every grid's topology islands a bus: NaN rows, zero rows for a zero gradient
+        zero = torch.ones(Bt, dtype=torch.bool, device=dev)
+        for g in (gv, gth):
+            if g is not None:
+                zero &= (g == 0).all(dim=1)
+        fill = torch.where(zero, 0.0, float('nan')).to(torch.float32)
+        for t in gin:
+            if t is not None:
+                t.copy_(fill.view(Bt, 1, 1).expand_as(t))
+        return gin
+    host, blob = set_bufs
+    nbytes = ctypes.c_size_t()
+    _check(lib.gns_pf_workspace_bytes_set(ctypes.byref(cfg), host.ctypes.data, host.size, members.ctypes.data, members.size, Bt,
+                                          ctypes.byref(nbytes)), 'gns_pf_workspace_bytes_set')
+    ws = _gns._workspace(nbytes.value, dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib.gns_pf_adjoint_set(ctypes.byref(cfg), host.ctypes.data, blob.data_ptr(), host.size, members.ctypes.data,
+                                      members.size, plan.grid_off.data_ptr(), plan.order.data_ptr(), buses.data_ptr(),
+                                      lines.data_ptr(), gens.data_ptr(), Bt, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
+                                      _ptr(gv), _ptr(gth), _ptr(gin[0]), _ptr(gin[1]), _ptr(gin[2]), ws.data_ptr(), ws.numel(),
+                                      stream), 'gns_pf_adjoint_set')
+    return gin
 
 
 def _outputs(Bt, N, dev):

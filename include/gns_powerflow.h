@@ -45,6 +45,9 @@ extern "C" {
 
 /* The LDS one workgroup may use on gfx950 (160 KiB): the limit of a topology's LDS image. */
 #define GNS_PF_LDS_MAX_BYTES 163840
+/* The most slots (nnz(L+U) + dim) a program may address: its operands are 16-bit.  The analysis refuses a topology whose factor
+ * needs more with GNS_EUNSUPPORTED. */
+#define GNS_PF_MAX_SLOTS 65535
 
 typedef struct gns_pf_config {
   int32_t n_bus;     /* N  */
@@ -78,12 +81,16 @@ typedef struct gns_pf_info {
  * triangular-solve program in barrier-separated steps, in one relocatable int32 blob of gns_pf_topology_bytes() bytes.
  * GNS_ETOPOLOGY: a bus id out of range, a slack that is not a bus, or a bus with no path of lines to the slack (an island: its
  * theta is undetermined and the Jacobian structurally singular).  The program's length depends on the ids, so
- * gns_pf_topology_bytes runs the analysis and reports the blob's exact size. */
+ * gns_pf_topology_bytes runs the analysis and reports the blob's exact size.  GNS_EUNSUPPORTED: the factor needs more than
+ * GNS_PF_MAX_SLOTS slots; gns_pf_topology_slots then reports how many (and the count of an accepted topology too; its errors are
+ * otherwise those of the analysis). */
 int gns_pf_topology_bytes(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                           const int32_t* gen_bus, int32_t slack, size_t* bytes);
 int gns_pf_prepare_topology(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                             const int32_t* gen_bus, int32_t slack, void* topo_host_out, size_t topo_bytes);
 int gns_pf_topology_info(const void* topo_host, gns_pf_info* info);
+int gns_pf_topology_slots(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                          const int32_t* gen_bus, int32_t slack, int64_t* slots);
 
 /* Device workspace of a solve of Bt grids (the Y-bus values, 16 bytes per structural nonzero and grid). */
 int gns_pf_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);

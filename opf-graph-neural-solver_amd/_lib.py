@@ -83,6 +83,7 @@ def load_library():
     lib.gns_pf_topology_bytes.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(sz)]
     lib.gns_pf_prepare_topology.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, sz]
     lib.gns_pf_topology_info.argtypes = [vp, ctypes.POINTER(PfInfo)]
+    lib.gns_pf_topology_slots.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i64)]
     lib.gns_pf_workspace_bytes.argtypes = [pfcp, vp, i64, ctypes.POINTER(sz)]
     lib.gns_pf_solve.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.gns_pf_workspace_bytes_set.argtypes = [pfcp, vp, sz, vp, i32, i64, ctypes.POINTER(sz)]
@@ -110,7 +111,10 @@ EXPORTS = ('gns_version', 'gns_param_count', 'gns_config_supported', 'gns_topolo
 
 # the power-flow solver's C-ABI (include/gns_powerflow.h)
 PF_EXPORTS = ('gns_pf_topology_bytes', 'gns_pf_prepare_topology', 'gns_pf_topology_info', 'gns_pf_workspace_bytes', 'gns_pf_solve',
-              'gns_pf_workspace_bytes_set', 'gns_pf_solve_set', 'gns_pf_adjoint', 'gns_pf_adjoint_set')
+              'gns_pf_workspace_bytes_set', 'gns_pf_solve_set', 'gns_pf_adjoint', 'gns_pf_adjoint_set', 'gns_pf_topology_slots')
+# the limits of include/gns_powerflow.h
+PF_LDS_MAX_BYTES = 163840
+PF_MAX_SLOTS = 65535
 
 
 def set_option(name: str, value: int) -> None:

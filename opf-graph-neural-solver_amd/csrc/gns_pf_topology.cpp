@@ -74,7 +74,9 @@ int schedule(const std::vector<Op>& prog, int nslots, std::vector<int32_t>& step
   return nsteps;
 }
 
-int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& out) {
+// With slots_out, the factor's slot count nnz(L+U) + dim is written there as soon as it is known, also when it is refused.
+int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& out,
+            int64_t* slots_out = nullptr) {
   if (N <= 0 || E < 0 || Gn < 0 || (E > 0 && (!f || !t)) || (Gn > 0 && !gb)) return GNS_EINVAL;
   if (slack < 0 || slack >= N) return GNS_ETOPOLOGY;
   for (int e = 0; e < E; ++e) if (f[e] < 0 || f[e] >= N || t[e] < 0 || t[e] >= N) return GNS_ETOPOLOGY;
@@ -159,7 +161,8 @@ int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int3
   int nnzLU = 0;
   for (int i = 0; i < dim; ++i) for (int j = 0; j < dim; ++j) if (P[i][j]) slot[i][j] = nnzLU++;
   const int nslots = nnzLU + dim;                             // factor, then the right-hand side / solution
-  if (nslots > 0xFFFF) return GNS_EUNSUPPORTED;               // (16-bit operands; such a factor is far beyond the LDS limit anyway)
+  if (slots_out) *slots_out = nslots;
+  if (nslots > GNS_PF_MAX_SLOTS) return GNS_EUNSUPPORTED;     // (16-bit operands; such a factor is far beyond the LDS limit anyway)
 
   std::vector<int32_t> jslot(4 * (size_t)nnzY, -1), pivot(dim);
   for (int i = 0; i < N; ++i) {
@@ -226,8 +229,9 @@ int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int3
   return GNS_OK;
 }
 
-int analyse_safe(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& w) {
-  try { return analyse(N, E, Gn, f, t, gb, slack, w); } catch (...) { return GNS_EINVAL; }
+int analyse_safe(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& w,
+                 int64_t* slots_out = nullptr) {
+  try { return analyse(N, E, Gn, f, t, gb, slack, w, slots_out); } catch (...) { return GNS_EINVAL; }
 }
 
 }  // namespace
@@ -240,6 +244,15 @@ extern "C" int gns_pf_topology_bytes(int32_t n_bus, int32_t n_line, int32_t n_ge
   if (rc != GNS_OK) return rc;
   *bytes = w.size() * sizeof(int32_t);
   return GNS_OK;
+}
+
+extern "C" int gns_pf_topology_slots(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                                     const int32_t* gen_bus, int32_t slack, int64_t* slots) {
+  if (!slots) return GNS_EINVAL;
+  std::vector<int32_t> w;
+  *slots = -1;
+  const int rc = analyse_safe(n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, w, slots);
+  return rc == GNS_EUNSUPPORTED && *slots > GNS_PF_MAX_SLOTS ? GNS_OK : rc;
 }
 
 extern "C" int gns_pf_prepare_topology(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,

@@ -22,7 +22,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import gns as _gns
-from ._lib import GNS_ERRORS, PfConfig, PfInfo, load_library
+from ._lib import GNS_ERRORS, PF_LDS_MAX_BYTES, PF_MAX_SLOTS, PfConfig, PfInfo, load_library
 
 PowerFlowResult = namedtuple('PowerFlowResult', ['v', 'theta', 'converged', 'iterations', 'mismatch'])
 
@@ -85,9 +85,28 @@ class _PfTopologySet:
             self.host, self.blob = host, torch.from_numpy(host).to(self.dev)
 
 
-def _check(rc, what):
+GNS_EUNSUPPORTED = 2
+
+
+def _check(rc, what, lds_bytes=None):
+    """Raise GNSError for a non-zero return code.  A solve or adjoint call refuses a topology (GNS_EUNSUPPORTED) only for its LDS
+    image: ``lds_bytes`` (the largest of a set's members, or a callable that finds it) is then named against the limit, not the
+    GNS model text."""
+    if rc == GNS_EUNSUPPORTED and lds_bytes is not None:
+        lds_bytes = lds_bytes() if callable(lds_bytes) else lds_bytes
+        raise _gns.GNSError(f'{what} failed: GNS_EUNSUPPORTED (the topology\'s LDS image of {int(lds_bytes)} B exceeds the '
+                            f'{PF_LDS_MAX_BYTES} B (160 KiB) one workgroup may use: 8 * (nnz(L+U) + dim + 8 N) bytes per grid)')
     if rc != 0:
         raise _gns.GNSError(f'{what} failed: {GNS_ERRORS.get(rc, rc)}')
+
+
+def _set_lds_bytes(set_host, member_off):
+    """The largest LDS image among the members of a set (host words)."""
+    lib, info, lds = load_library(), PfInfo(), 0
+    for off in member_off.tolist():
+        _check(lib.gns_pf_topology_info(set_host.ctypes.data + 4 * off, ctypes.byref(info)), 'gns_pf_topology_info')
+        lds = max(lds, info.lds_bytes)
+    return lds
 
 
 def _islanded(n_bus, f_bus, t_bus, slack):
@@ -136,6 +155,11 @@ def analyse_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
         isl = _islanded(int(n_bus), f32, t32, slack) + 1
         raise IslandedTopology(f'buses {isl.tolist()} have no path of lines to slack_bus {slack + 1}: their angles are undetermined '
                          '(the power-flow Jacobian is structurally singular)')
+    if rc == GNS_EUNSUPPORTED:
+        slots = ctypes.c_int64()
+        _check(lib.gns_pf_topology_slots(*args, ctypes.byref(slots)), 'gns_pf_topology_slots')
+        raise _gns.GNSError(f'gns_pf_topology_bytes failed: GNS_EUNSUPPORTED (the factor of this topology needs {slots.value} slots, '
+                            f'nnz(L+U) + dim, more than the {PF_MAX_SLOTS}-slot limit of the program\'s 16-bit operands)')
     _check(rc, 'gns_pf_topology_bytes')
     host = np.zeros(nbytes.value // 4, dtype=np.int32)
     _check(lib.gns_pf_prepare_topology(*args, host.ctypes.data, host.nbytes), 'gns_pf_prepare_topology')
@@ -339,7 +363,8 @@ def _solve_plain(lib, cfg, topo, buses, lines, generators, v0, theta0):
     _check(lib.gns_pf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
                             generators.data_ptr(), Bt, v0.data_ptr() if v0 is not None else None,
                             theta0.data_ptr() if theta0 is not None else None, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
-                            iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_pf_solve')
+                            iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_pf_solve',
+           topo.info['lds_bytes'])
     return [v, theta, conv.bool(), iters, mis]
 
 
@@ -388,7 +413,8 @@ def _adjoint_plain(lib, cfg, topo, buses, lines, gens, v, theta, conv, gv, gth, 
         stream = torch.cuda.current_stream(dev).cuda_stream
         _check(lib.gns_pf_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
                                   gens.data_ptr(), Bt, v.data_ptr(), theta.data_ptr(), conv.data_ptr(), _ptr(gv), _ptr(gth),
-                                  _ptr(gin[0]), _ptr(gin[1]), _ptr(gin[2]), ws.data_ptr(), ws.numel(), stream), 'gns_pf_adjoint')
+                                  _ptr(gin[0]), _ptr(gin[1]), _ptr(gin[2]), ws.data_ptr(), ws.numel(), stream), 'gns_pf_adjoint',
+               topo.info['lds_bytes'])
     return gin
 
 
@@ -410,7 +436,7 @@ def _adjoint_mixed(lib, cfg, plan, set_bufs, buses, lines, gens, v, theta, conv,
     host, blob = set_bufs
     nbytes = ctypes.c_size_t()
     _check(lib.gns_pf_workspace_bytes_set(ctypes.byref(cfg), host.ctypes.data, host.size, members.ctypes.data, members.size, Bt,
-                                          ctypes.byref(nbytes)), 'gns_pf_workspace_bytes_set')
+                                          ctypes.byref(nbytes)), 'gns_pf_workspace_bytes_set', lambda: _set_lds_bytes(host, members))
     ws = _gns._workspace(nbytes.value, dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -418,7 +444,7 @@ def _adjoint_mixed(lib, cfg, plan, set_bufs, buses, lines, gens, v, theta, conv,
                                       members.size, plan.grid_off.data_ptr(), plan.order.data_ptr(), buses.data_ptr(),
                                       lines.data_ptr(), gens.data_ptr(), Bt, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
                                       _ptr(gv), _ptr(gth), _ptr(gin[0]), _ptr(gin[1]), _ptr(gin[2]), ws.data_ptr(), ws.numel(),
-                                      stream), 'gns_pf_adjoint_set')
+                                      stream), 'gns_pf_adjoint_set', lambda: _set_lds_bytes(host, members))
     return gin
 
 
@@ -439,7 +465,7 @@ def _solve_mixed(lib, cfg, plan, buses, lines, generators, v0, theta0):
     ts, members = plan.topo_set, plan.member_off
     nbytes = ctypes.c_size_t()
     _check(lib.gns_pf_workspace_bytes_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.words, members.ctypes.data, members.size, Bt,
-                                          ctypes.byref(nbytes)), 'gns_pf_workspace_bytes_set')
+                                          ctypes.byref(nbytes)), 'gns_pf_workspace_bytes_set', lambda: _set_lds_bytes(ts.host, members))
     ws = _gns._workspace(nbytes.value, dev)
     v, theta, conv, iters, mis = _outputs(Bt, N, dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
@@ -447,5 +473,6 @@ def _solve_mixed(lib, cfg, plan, buses, lines, generators, v0, theta0):
                                 members.size, plan.grid_off.data_ptr(), plan.order.data_ptr(), buses.data_ptr(), lines.data_ptr(),
                                 generators.data_ptr(), Bt, v0.data_ptr() if v0 is not None else None,
                                 theta0.data_ptr() if theta0 is not None else None, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
-                                iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_pf_solve_set')
+                                iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_pf_solve_set',
+           lambda: _set_lds_bytes(ts.host, members))
     return [v, theta, conv.bool(), iters, mis]

@@ -40,23 +40,46 @@ def specified(buses, generators):
     return s - bus[:, 2] - 1j * bus[:, 3]
 
 
+def _state(vm, va):
+    return np.asarray(vm, dtype=np.float64) * np.exp(1j * np.asarray(va, dtype=np.float64))
+
+
+def mismatch_vector(buses, lines, generators, slack_bus, v, theta, Y=None):
+    """F = [Re(V conj(YV) - S) at PV+PQ ; Im(...) at PQ] of include/gns_powerflow.h at (v, theta), rows in the order of
+    ``jacobian``'s unknowns (``roles``: PV ascending, then PQ ascending)."""
+    slack, pv, pq = roles(buses, generators, slack_bus)
+    V = _state(v, theta)
+    Y = ybus(buses, lines) if Y is None else Y
+    mis = V * np.conj(Y @ V) - specified(buses, generators)
+    return np.r_[mis[np.r_[pv, pq]].real, mis[pq].imag]
+
+
+def jacobian(buses, lines, generators, slack_bus, v, theta, Y=None):
+    """dF/dx at (v, theta) (MATPOWER dSbus_dV, polar), scipy CSC, for x = [theta at PV+PQ ; |V| at PQ] in ``roles``' order."""
+    slack, pv, pq = roles(buses, generators, slack_bus)
+    pvpq = np.r_[pv, pq]
+    V = _state(v, theta)
+    Y = ybus(buses, lines) if Y is None else Y
+    Ibus = Y @ V
+    dV = sp.diags(V)
+    dS_dVa = 1j * dV @ np.conj(sp.diags(Ibus) - Y @ dV)
+    dS_dVm = dV @ np.conj(Y @ sp.diags(V / np.abs(V))) + np.conj(sp.diags(Ibus)) @ sp.diags(V / np.abs(V))
+    return sp.vstack([sp.hstack([dS_dVa[pvpq][:, pvpq].real, dS_dVm[pvpq][:, pq].real]),
+                      sp.hstack([dS_dVa[pq][:, pvpq].imag, dS_dVm[pq][:, pq].imag])]).tocsc()
+
+
 def mismatch(buses, lines, generators, slack_bus, v, theta):
     """||F||_inf of (v, theta) with the power-flow mismatch F of include/gns_powerflow.h."""
-    slack, pv, pq = roles(buses, generators, slack_bus)
-    V = np.asarray(v, dtype=np.float64) * np.exp(1j * np.asarray(theta, dtype=np.float64))
-    mis = V * np.conj(ybus(buses, lines) @ V) - specified(buses, generators)
-    pvpq = np.r_[pv, pq]
-    return float(np.max(np.abs(np.r_[mis[pvpq].real, mis[pq].imag]), initial=0.0))
+    return float(np.max(np.abs(mismatch_vector(buses, lines, generators, slack_bus, v, theta)), initial=0.0))
 
 
-def newton_raphson(buses, lines, generators, slack_bus, tol=1e-8, max_iter=10, v0=None, theta0=None):
-    """Returns (v, theta, converged, iterations, mismatch) of one grid."""
+def start(buses, generators, slack_bus, v0=None, theta0=None):
+    """The starting point (|V|, theta) [N] of include/gns_powerflow.h: vg of the first generator listed on each PV / slack bus, 1
+    elsewhere, theta 0; a warm start sets |V| at PQ buses from v0 and theta = theta0 - theta0[slack]."""
     bus = np.asarray(buses, dtype=np.float64)
     gen = np.asarray(generators, dtype=np.float64)
     n = bus.shape[0]
     slack, pv, pq = roles(bus, gen, slack_bus)
-    Y = ybus(bus, lines)
-    S = specified(bus, gen)
     vm = np.ones(n)
     for j in range(gen.shape[0] - 1, -1, -1):          # the first generator listed on a bus wins
         b = int(gen[j, 0]) - 1
@@ -69,13 +92,21 @@ def newton_raphson(buses, lines, generators, slack_bus, tol=1e-8, max_iter=10, v
         th = np.asarray(theta0, dtype=np.float64)
         va = th - th[slack]
         va[slack] = 0.0
+    return vm, va
+
+
+def newton_raphson(buses, lines, generators, slack_bus, tol=1e-8, max_iter=10, v0=None, theta0=None):
+    """Returns (v, theta, converged, iterations, mismatch) of one grid."""
+    bus = np.asarray(buses, dtype=np.float64)
+    gen = np.asarray(generators, dtype=np.float64)
+    slack, pv, pq = roles(bus, gen, slack_bus)
+    Y = ybus(bus, lines)
+    vm, va = start(bus, gen, slack_bus, v0, theta0)
     pvpq = np.r_[pv, pq]
     npvpq = pvpq.size
     it = 0
     while True:
-        V = vm * np.exp(1j * va)
-        mis = V * np.conj(Y @ V) - S
-        F = np.r_[mis[pvpq].real, mis[pq].imag]
+        F = mismatch_vector(bus, lines, gen, slack_bus, vm, va, Y)
         nrm = float(np.max(np.abs(F), initial=0.0))
         if not np.isfinite(nrm):
             return vm, va, False, it, nrm
@@ -83,12 +114,7 @@ def newton_raphson(buses, lines, generators, slack_bus, tol=1e-8, max_iter=10, v
             return vm, va, True, it, nrm
         if it >= max_iter:
             return vm, va, False, it, nrm
-        Ibus = Y @ V
-        dV = sp.diags(V)
-        dS_dVa = 1j * dV @ np.conj(sp.diags(Ibus) - Y @ dV)
-        dS_dVm = dV @ np.conj(Y @ sp.diags(V / np.abs(V))) + np.conj(sp.diags(Ibus)) @ sp.diags(V / np.abs(V))
-        J = sp.vstack([sp.hstack([dS_dVa[pvpq][:, pvpq].real, dS_dVm[pvpq][:, pq].real]),
-                       sp.hstack([dS_dVa[pq][:, pvpq].imag, dS_dVm[pq][:, pq].imag])]).tocsc()
+        J = jacobian(bus, lines, gen, slack_bus, vm, va, Y)
         dx = spla.spsolve(J, F)
         if not np.all(np.isfinite(dx)):
             return vm, va, False, it, nrm

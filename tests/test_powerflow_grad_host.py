@@ -83,6 +83,7 @@ def _run(F, step_ptr, ops):
         dst, a, b = q[:, 0] & 0xFFFF, (q[:, 0].astype(np.uint32) >> 16).astype(np.int64), q[:, 1]
         div = b < 0
         assert np.unique(dst).size == dst.size
+        assert not np.isin(np.r_[a, b[~div]], dst).any()          # no operation reads what another of its step writes
         new = np.where(div, F[dst] / F[a], F[dst] - F[a] * F[np.where(div, 0, b)])
         F[dst] = new
 

@@ -182,6 +182,87 @@ int gns_pf_adjoint_set(const gns_pf_config* cfg, const void* set_host, const voi
                        float* grad_buses, float* grad_lines, float* grad_generators,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* Fast-decoupled power flow (PYPOWER runpf with PF_ALG = 2, XB, or 3, BX: makeB + fdpf), the classical cheap iterative
+ * baseline a trained GNS is compared with next to Newton-Raphson (GNS/evaluate.py:42-58).
+ *
+ * Semantics
+ *   Inputs, bus roles, Y-bus, specified injections, start and warm start: those of the Newton-Raphson section above.
+ *   B' and B'' (makeB) are -Im(Y) of modified copies of the grid, with per-unit shunts as above:
+ *     B':  bus Bs = 0, line b = 0, tau = 1, shift kept; XB also sets r = 0.  Rows and columns of the PV+PQ buses.
+ *     B'': shift = 0, everything else as given;        BX also sets r = 0.  Rows and columns of the PQ buses.
+ *   Both share the Y-bus pattern, so one analysis serves both variants: the variant is gns_fd_config.alg, a launch argument.
+ *   Iteration (fdpf): mis = (V conj(YV) - S) / |V|, P = Re(mis) at PV+PQ, Q = Im(mis) at PQ.  max(||P||_inf, ||Q||_inf) < tol is
+ *   tested at the start; then, at most max_iter times:
+ *     P half-step: dtheta = -B'^-1 P, theta += dtheta, recompute the mismatch, test;
+ *     Q half-step: d|V| = -B''^-1 Q, |V| += d|V|, recompute the mismatch, test.
+ *   iterations = the P half-steps taken.  mismatch = the norm the last test read: the SCALED max(||P||_inf, ||Q||_inf) of mis / |V|,
+ *   not Newton-Raphson's unscaled ||F||_inf.  n_pq = 0: the Q half-step is empty and ||Q|| = 0.
+ *   Both factors are computed once per grid (fp64, no pivoting, the minimum-degree orderings of the analysis).
+ *   Failure is per grid: a grid that meets the test at its start is converged with 0 iterations, whatever its factors; otherwise a
+ *   zero or non-finite pivot in either factor stops it at its start point (converged 0, iterations 0).  A non-finite step stops
+ *   it before that update; a non-finite mismatch stops it with mismatch NaN; v / theta keep the last finite iterate.  No atomics:
+ *   a grid's results are bit-identical alone, in any batch and from run to run.
+ *   PYPOWER's defaults: tol 1e-8, max_iter 30 (PF_MAX_IT_FD).
+ *
+ * Kernel: one wave per grid; both factors, both right-hand sides and six bus vectors in LDS (gns_fd_info.lds_bytes =
+ * 8 * (nnz_lu_p + dim_p + nnz_lu_pp + dim_pp + 6 N) bytes); the Y-bus values go to the workspace once.  Workspace: that of
+ * gns_pf_workspace_bytes (16 bytes per Y-bus entry and grid).  The two factorisation programs run once, the two solve programs
+ * once per half-step.
+ *
+ * Gradients: FD solves the same equations F = 0 as Newton-Raphson, so the implicit-function gradient at its solution is the
+ * Newton-Raphson adjoint: call gns_pf_adjoint / gns_pf_adjoint_set on the Newton-Raphson analysis of the topology with FD's v,
+ * theta and converged ("Gradients" above). */
+
+typedef struct gns_fd_config {
+  gns_pf_config pf;  /* n_bus, n_line, n_gen, max_iter (P half-steps at most; PYPOWER: 30), tol (scaled mismatch bound: 1e-8) */
+  int32_t alg;       /* 2: XB, 3: BX (PYPOWER's PF_ALG) */
+} gns_fd_config;
+
+typedef struct gns_fd_info {
+  int32_t n_bus, n_line, n_gen;
+  int32_t slack;                          /* 0-based */
+  int32_t n_pv, n_pq;
+  int32_t nnz_ybus;
+  int32_t dim_p, nnz_lu_p;                /* B': N - 1, nonzeros of its L + U (unit diagonal of L not stored) */
+  int32_t dim_pp, nnz_lu_pp;              /* B'': n_pq, nonzeros of its L + U */
+  int32_t factor_p_ops, factor_p_steps;   /* operations and barrier-separated steps of the B' factorisation (once per grid) */
+  int32_t solve_p_ops, solve_p_steps;     /* ... of the B' solve (every P half-step) */
+  int32_t factor_pp_ops, factor_pp_steps; /* ... of the B'' factorisation */
+  int32_t solve_pp_ops, solve_pp_steps;   /* ... of the B'' solve (every Q half-step) */
+  int64_t lds_bytes;                      /* LDS image of one grid; > GNS_PF_LDS_MAX_BYTES: gns_fd_solve returns GNS_EUNSUPPORTED */
+} gns_fd_info;
+
+/* Host analysis, arguments and errors as gns_pf_topology_bytes / gns_pf_prepare_topology / gns_pf_topology_slots (GNS_ETOPOLOGY
+ * for an island; GNS_EUNSUPPORTED when a factor needs more than GNS_PF_MAX_SLOTS slots, nnz(L+U) + dim, and gns_fd_topology_slots
+ * then reports the larger of the two).  B' gets a minimum-degree ordering of the bus graph without the slack, B'' one of the
+ * subgraph the PQ buses induce. */
+int gns_fd_topology_bytes(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                          const int32_t* gen_bus, int32_t slack, size_t* bytes);
+int gns_fd_prepare_topology(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                            const int32_t* gen_bus, int32_t slack, void* topo_host_out, size_t topo_bytes);
+int gns_fd_topology_info(const void* topo_host, gns_fd_info* info);
+int gns_fd_topology_slots(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                          const int32_t* gen_bus, int32_t slack, int64_t* slots);
+
+/* Solve, arguments and errors as gns_pf_workspace_bytes / gns_pf_solve on an FD blob (GNS_EINVAL also for alg not 2 or 3). */
+int gns_fd_workspace_bytes(const gns_fd_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
+int gns_fd_solve(const gns_fd_config* cfg, const void* topo_host, const void* topo_dev,
+                 const float* buses, const float* lines, const float* generators, int64_t Bt,
+                 const double* v0, const double* theta0,
+                 double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* Mixed topologies: gns_pf_workspace_bytes_set / gns_pf_solve_set on a set of FD blobs (the same set layout, member checks,
+ * grid_off = -1 semantics and device-side blob checks); results are bit-identical to gns_fd_solve on each grid's blob. */
+int gns_fd_workspace_bytes_set(const gns_fd_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
+                               int32_t n_member, int64_t Bt, size_t* bytes);
+int gns_fd_solve_set(const gns_fd_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                     const int32_t* member_off, int32_t n_member, const int32_t* grid_off, const int32_t* order,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const double* v0, const double* theta0,
+                     double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

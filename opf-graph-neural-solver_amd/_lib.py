@@ -21,10 +21,21 @@ class PfConfig(ctypes.Structure):
                 ('tol', ctypes.c_double)]
 
 
+class FdConfig(ctypes.Structure):
+    _fields_ = [('pf', PfConfig), ('alg', ctypes.c_int32)]
+
+
 class PfInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ('n_bus', 'n_line', 'n_gen', 'slack', 'n_pv', 'n_pq', 'dim', 'nnz_jac', 'nnz_lu',
                                               'nnz_ybus', 'n_ops', 'n_steps')] + [('lds_bytes', ctypes.c_int64)] + \
                 [(n, ctypes.c_int32) for n in ('n_adj_ops', 'n_adj_steps', 'n_factor_steps')]
+
+
+class FdInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('n_bus', 'n_line', 'n_gen', 'slack', 'n_pv', 'n_pq', 'nnz_ybus', 'dim_p', 'nnz_lu_p',
+                                              'dim_pp', 'nnz_lu_pp', 'factor_p_ops', 'factor_p_steps', 'solve_p_ops',
+                                              'solve_p_steps', 'factor_pp_ops', 'factor_pp_steps', 'solve_pp_ops',
+                                              'solve_pp_steps')] + [('lds_bytes', ctypes.c_int64)]
 
 
 def library_path():
@@ -90,7 +101,16 @@ def load_library():
     lib.gns_pf_solve_set.argtypes = [pfcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.gns_pf_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.gns_pf_adjoint_set.argtypes = [pfcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    for f in PF_EXPORTS:
+    fdcp = ctypes.POINTER(FdConfig)
+    lib.gns_fd_topology_bytes.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(sz)]
+    lib.gns_fd_prepare_topology.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, sz]
+    lib.gns_fd_topology_info.argtypes = [vp, ctypes.POINTER(FdInfo)]
+    lib.gns_fd_topology_slots.argtypes = [i32, i32, i32, vp, vp, vp, i32, ctypes.POINTER(i64)]
+    lib.gns_fd_workspace_bytes.argtypes = [fdcp, vp, i64, ctypes.POINTER(sz)]
+    lib.gns_fd_solve.argtypes = [fdcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_fd_workspace_bytes_set.argtypes = [fdcp, vp, sz, vp, i32, i64, ctypes.POINTER(sz)]
+    lib.gns_fd_solve_set.argtypes = [fdcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    for f in PF_EXPORTS + FD_EXPORTS:
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
               'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
@@ -112,6 +132,9 @@ EXPORTS = ('gns_version', 'gns_param_count', 'gns_config_supported', 'gns_topolo
 # the power-flow solver's C-ABI (include/gns_powerflow.h)
 PF_EXPORTS = ('gns_pf_topology_bytes', 'gns_pf_prepare_topology', 'gns_pf_topology_info', 'gns_pf_workspace_bytes', 'gns_pf_solve',
               'gns_pf_workspace_bytes_set', 'gns_pf_solve_set', 'gns_pf_adjoint', 'gns_pf_adjoint_set', 'gns_pf_topology_slots')
+# the fast-decoupled solver's C-ABI (include/gns_powerflow.h, "Fast-decoupled")
+FD_EXPORTS = ('gns_fd_topology_bytes', 'gns_fd_prepare_topology', 'gns_fd_topology_info', 'gns_fd_topology_slots',
+              'gns_fd_workspace_bytes', 'gns_fd_solve', 'gns_fd_workspace_bytes_set', 'gns_fd_solve_set')
 # the limits of include/gns_powerflow.h
 PF_LDS_MAX_BYTES = 163840
 PF_MAX_SLOTS = 65535

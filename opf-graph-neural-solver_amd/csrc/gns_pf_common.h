@@ -45,3 +45,42 @@ static_assert(PH_T_OPS < PF_HDR_WORDS, "the header holds every word offset");
 PF_HOST_DEVICE inline int64_t pf_lds_bytes(const int32_t* h) {
   return 8 * ((int64_t)h[PH_NNZLU] + h[PH_DIM] + 8 * (int64_t)h[PH_N]);
 }
+
+// Layout of the fast-decoupled topology blob (gns_fd_prepare_topology): a header of FD_HDR_WORDS int32 words, then int32 arrays at
+// the word offsets the header names.  Roles, generators, the Y-bus pattern and its stamps as in the Newton-Raphson blob; B' (rows
+// and columns of the PV+PQ buses) and B'' (the PQ buses) each have their own minimum-degree ordering, symbolic LU and two programs
+// in the format of PH_OPS: the factorisation, run once per grid, and the triangular solve, run every half-iteration.  Each program
+// addresses its own factor's slots: nnz(L+U) factor slots, then dim right-hand-side / solution slots.
+#define GNS_FD_MAGIC 0x44504631   // "1FPD"
+
+enum {
+  FH_MAGIC = 0, FH_TOTAL, FH_N, FH_E, FH_GN, FH_SLACK, FH_NPV, FH_NPQ, FH_NNZY,
+  FH_DIM1, FH_NNZLU1, FH_DIM2, FH_NNZLU2,   // B' (dim N - 1) and B'' (dim n_pq)
+  FH_NOPS_F1, FH_NSTEPS_F1, FH_NOPS_S1, FH_NSTEPS_S1, FH_NOPS_F2, FH_NSTEPS_F2, FH_NOPS_S2, FH_NSTEPS_S2,
+  // word offsets of the arrays
+  FH_ROLE,       // [N]      0 PQ, 1 PV, 2 slack
+  FH_P_IDX,      // [N]      position of the bus in B' (its theta), -1 at the slack
+  FH_Q_IDX,      // [N]      position of the bus in B'' (its |V|), -1 unless PQ
+  FH_GEN_PTR,    // [N+1]
+  FH_GEN_IDX,    // [max(Gn,1)]
+  FH_Y_PTR,      // [N+1]    the Y-bus pattern and stamps of PH_Y_PTR .. PH_ST
+  FH_Y_COL,      // [nnzY]
+  FH_Y_DIAG,     // [N]
+  FH_ST_PTR,     // [nnzY+1]
+  FH_ST,         // [4E]
+  FH_BSLOT,      // [2 nnzY] slot in B' and slot in B'' of Y-bus entry p, -1 where the entry is not in that matrix
+  FH_PIVOT1,     // [dim1]   B' factor slot of each pivot
+  FH_PIVOT2,     // [dim2]
+  FH_STEP_F1, FH_OPS_F1,   // B' factorisation: [nsteps+1] step pointers, [2 nops] operations (8-byte aligned)
+  FH_STEP_S1, FH_OPS_S1,   // B' solve
+  FH_STEP_F2, FH_OPS_F2,   // B'' factorisation
+  FH_STEP_S2, FH_OPS_S2,   // B'' solve
+  FD_HDR_WORDS = 48
+};
+
+static_assert(FH_OPS_S2 < FD_HDR_WORDS, "the header holds every word offset");
+
+// LDS image of one grid (gns_fd_info.lds_bytes): both factors with their right-hand sides and six bus vectors, in doubles
+PF_HOST_DEVICE inline int64_t fd_lds_bytes(const int32_t* h) {
+  return 8 * ((int64_t)h[FH_NNZLU1] + h[FH_DIM1] + h[FH_NNZLU2] + h[FH_DIM2] + 6 * (int64_t)h[FH_N]);
+}

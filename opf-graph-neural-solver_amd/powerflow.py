@@ -11,6 +11,10 @@ the Jacobian and of its LU factor is analysed once per topology on the host (``c
 batch reads its topologies from a device set of those blobs (``gns_pf_solve_set``) that grows as new topologies appear.
 With ``requires_grad`` on the inputs the solve is differentiable: its backward is one adjoint kernel (``gns_pf_adjoint`` /
 ``gns_pf_adjoint_set``) on the same analysis.
+
+``fast_decoupled(..., variant='XB' | 'BX')`` is the second baseline of the reference's evaluation (PYPOWER ``runpf(PF_ALG=2 | 3)``,
+``GNS/evaluate.py:42-58``): B' and B'' are factored once per grid in one HIP kernel (``csrc/gns_fdpf.hip``) from their own cached
+analysis (``gns_fd_prepare_topology``); its gradients are the Newton-Raphson adjoint at its solution.
 """
 from __future__ import annotations
 
@@ -22,7 +26,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import gns as _gns
-from ._lib import GNS_ERRORS, PF_LDS_MAX_BYTES, PF_MAX_SLOTS, PfConfig, PfInfo, load_library
+from ._lib import GNS_ERRORS, PF_LDS_MAX_BYTES, PF_MAX_SLOTS, FdConfig, FdInfo, PfConfig, PfInfo, load_library
 
 PowerFlowResult = namedtuple('PowerFlowResult', ['v', 'theta', 'converged', 'iterations', 'mismatch'])
 
@@ -31,6 +35,8 @@ MixedPlan = namedtuple('MixedPlan', ['topology', 'order', 'grid_off', 'member_of
 _TOPO_CACHE = {}
 _ISLANDED = set()       # keys of _TOPO_CACHE's form whose topology leaves buses without a path of lines to the slack
 _SET_CACHE = {}         # (N, E, Gn, slack_bus, device) -> _PfTopologySet
+_FD_TOPO_CACHE = {}     # _TOPO_CACHE's keys -> FdTopology
+_FD_SET_CACHE = {}      # _SET_CACHE's keys -> _PfTopologySet of FD blobs
 
 
 class IslandedTopology(ValueError):
@@ -52,6 +58,18 @@ class PowerFlowTopology:
         if self._blob is None and self._dev is not None:
             self._blob = torch.from_numpy(self.host).to(self._dev)
         return self._blob
+
+
+class FdTopology(PowerFlowTopology):
+    """Host analysis of one topology for the fast-decoupled solver (B' and B'', ``gns_fd_prepare_topology``): ``info`` holds both
+    dimensions, both nnz(L+U), the four programs' operation and step counts and the LDS image."""
+
+    def __init__(self, host, dev):
+        self.host = host
+        self._dev, self._blob = dev, None
+        info = FdInfo()
+        _check(load_library().gns_fd_topology_info(host.ctypes.data, ctypes.byref(info)), 'gns_fd_topology_info')
+        self.info = {k: getattr(info, k) for k, _ in FdInfo._fields_}
 
 
 class _PfTopologySet:
@@ -88,23 +106,28 @@ class _PfTopologySet:
 GNS_EUNSUPPORTED = 2
 
 
-def _check(rc, what, lds_bytes=None):
+_LDS_FORMULA = '8 * (nnz(L+U) + dim + 8 N) bytes per grid'
+_FD_LDS_FORMULA = "8 * (nnz_lu_p + dim_p + nnz_lu_pp + dim_pp + 6 N) bytes per grid: both factors of B' and B''"
+
+
+def _check(rc, what, lds_bytes=None, formula=_LDS_FORMULA):
     """Raise GNSError for a non-zero return code.  A solve or adjoint call refuses a topology (GNS_EUNSUPPORTED) only for its LDS
     image: ``lds_bytes`` (the largest of a set's members, or a callable that finds it) is then named against the limit, not the
     GNS model text."""
     if rc == GNS_EUNSUPPORTED and lds_bytes is not None:
         lds_bytes = lds_bytes() if callable(lds_bytes) else lds_bytes
         raise _gns.GNSError(f'{what} failed: GNS_EUNSUPPORTED (the topology\'s LDS image of {int(lds_bytes)} B exceeds the '
-                            f'{PF_LDS_MAX_BYTES} B (160 KiB) one workgroup may use: 8 * (nnz(L+U) + dim + 8 N) bytes per grid)')
+                            f'{PF_LDS_MAX_BYTES} B (160 KiB) one workgroup may use: {formula})')
     if rc != 0:
         raise _gns.GNSError(f'{what} failed: {GNS_ERRORS.get(rc, rc)}')
 
 
-def _set_lds_bytes(set_host, member_off):
-    """The largest LDS image among the members of a set (host words)."""
-    lib, info, lds = load_library(), PfInfo(), 0
+def _set_lds_bytes(set_host, member_off, fd=False):
+    """The largest LDS image among the members of a set (host words; ``fd``: a set of FD blobs)."""
+    lib, lds = load_library(), 0
+    info, fn = (FdInfo(), 'gns_fd_topology_info') if fd else (PfInfo(), 'gns_pf_topology_info')
     for off in member_off.tolist():
-        _check(lib.gns_pf_topology_info(set_host.ctypes.data + 4 * off, ctypes.byref(info)), 'gns_pf_topology_info')
+        _check(getattr(lib, fn)(set_host.ctypes.data + 4 * off, ctypes.byref(info)), fn)
         lds = max(lds, info.lds_bytes)
     return lds
 
@@ -132,6 +155,15 @@ def analyse_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
     Returns a ``PowerFlowTopology`` (its ``info`` dict holds the Jacobian dimension, nnz(L+U), ...); with ``device`` the blob is
     also copied there (on first use).  Raises ValueError for ids out of range or a slack that is not a bus, and its subclass
     ``IslandedTopology`` for buses islanded from the slack."""
+    return _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, 'gns_pf', PowerFlowTopology)
+
+
+def analyse_fd_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
+    """The fast-decoupled analysis of one topology (arguments and errors as ``analyse_topology``): an ``FdTopology``."""
+    return _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, 'gns_fd', FdTopology)
+
+
+def _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, prefix, cls):
     f = np.asarray(f_bus, dtype=np.float64).reshape(-1)
     t = np.asarray(t_bus, dtype=np.float64).reshape(-1)
     g = np.asarray(gen_bus, dtype=np.float64).reshape(-1)
@@ -150,20 +182,20 @@ def analyse_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
     lib = load_library()
     nbytes = ctypes.c_size_t()
     args = (int(n_bus), int(f32.size), int(g32.size), f32.ctypes.data, t32.ctypes.data, g_arg.ctypes.data, slack)
-    rc = lib.gns_pf_topology_bytes(*args, ctypes.byref(nbytes))
+    rc = getattr(lib, prefix + '_topology_bytes')(*args, ctypes.byref(nbytes))
     if rc == 3:
         isl = _islanded(int(n_bus), f32, t32, slack) + 1
         raise IslandedTopology(f'buses {isl.tolist()} have no path of lines to slack_bus {slack + 1}: their angles are undetermined '
                          '(the power-flow Jacobian is structurally singular)')
     if rc == GNS_EUNSUPPORTED:
         slots = ctypes.c_int64()
-        _check(lib.gns_pf_topology_slots(*args, ctypes.byref(slots)), 'gns_pf_topology_slots')
-        raise _gns.GNSError(f'gns_pf_topology_bytes failed: GNS_EUNSUPPORTED (the factor of this topology needs {slots.value} slots, '
+        _check(getattr(lib, prefix + '_topology_slots')(*args, ctypes.byref(slots)), prefix + '_topology_slots')
+        raise _gns.GNSError(f'{prefix}_topology_bytes failed: GNS_EUNSUPPORTED (the factor of this topology needs {slots.value} slots, '
                             f'nnz(L+U) + dim, more than the {PF_MAX_SLOTS}-slot limit of the program\'s 16-bit operands)')
-    _check(rc, 'gns_pf_topology_bytes')
+    _check(rc, prefix + '_topology_bytes')
     host = np.zeros(nbytes.value // 4, dtype=np.int32)
-    _check(lib.gns_pf_prepare_topology(*args, host.ctypes.data, host.nbytes), 'gns_pf_prepare_topology')
-    return PowerFlowTopology(host, device)
+    _check(getattr(lib, prefix + '_prepare_topology')(*args, host.ctypes.data, host.nbytes), prefix + '_prepare_topology')
+    return cls(host, device)
 
 
 def _as_batch(buses, lines, generators, B, L, G):
@@ -189,22 +221,32 @@ def _as_batch(buses, lines, generators, B, L, G):
 def _topology(buses, lines, gens, slack_bus):
     """The cached analysis of the batch's one topology.  One fused device compare of every grid's id columns against grid 0's,
     shipped to the host with grid 0's ids and type column: one synchronisation."""
+    key, args = _topology_key(buses, lines, gens, slack_bus, 'newton_raphson')
+    return _cached(_TOPO_CACHE, key, analyse_topology, args, buses.device)
+
+
+def _cached(cache, key, analyse, args, device):
+    topo = cache.get(key)
+    if topo is None:
+        topo = cache[key] = analyse(*args, device=device)
+    return topo
+
+
+def _topology_key(buses, lines, gens, slack_bus, solver):
+    """The cache key of the batch's one topology (``_TOPO_CACHE``'s form) and the arguments of its analysis."""
     N, E, Gn = buses.shape[1], lines.shape[1], gens.shape[1]
     ids_l, ids_g = lines[0, :, 0:2], gens[0, :, 0]
     same = (lines[:, :, 0:2] == ids_l).all() & (gens[:, :, 0] == ids_g).all()
     host = torch.cat([same.to(torch.float64).reshape(1), ids_l.t().reshape(-1).double(), ids_g.double(),
                       buses[0, :, 1].double()]).cpu().numpy()
     if host[0] != 1.0:
-        raise ValueError('f_bus / t_bus / generator bus columns differ across the batch: newton_raphson solves one topology per '
+        raise ValueError(f'f_bus / t_bus / generator bus columns differ across the batch: {solver} solves one topology per '
                          'call (group the grids by topology)')
     f_bus, t_bus, gen_bus, btype = host[1:1 + E], host[1 + E:1 + 2 * E], host[1 + 2 * E:1 + 2 * E + Gn], host[1 + 2 * E + Gn:]
     if slack_bus is None:
         slack_bus = _slack_from_type3(btype == 3)
     key = (N, E, Gn, slack_bus, str(buses.device), f_bus.tobytes(), t_bus.tobytes(), gen_bus.tobytes())
-    topo = _TOPO_CACHE.get(key)
-    if topo is None:
-        topo = _TOPO_CACHE[key] = analyse_topology(N, f_bus, t_bus, gen_bus, slack_bus, device=buses.device)
-    return topo
+    return key, (N, f_bus, t_bus, gen_bus, slack_bus)
 
 
 def _slack_from_type3(is3):
@@ -227,18 +269,28 @@ def _plan_mixed(buses, lines, gens, slack_bus):
       member_off int32 numpy: the offsets of the blobs this call uses (distinct, ascending by topology index)
       topo_set   the ``_PfTopologySet``; slack_bus: the 1-based slack; islanded: bool numpy per distinct topology.
     Raises as ``analyse_topology`` does for ids out of range, non-integer ids or a bad slack; islands are not an error here."""
-    N, E, Gn = buses.shape[1], lines.shape[1], gens.shape[1]
-    dev = buses.device
+    return _plan_from(_classify(buses, lines, gens, slack_bus), buses, lines, gens, _TOPO_CACHE, _SET_CACHE, analyse_topology)
+
+
+def _classify(buses, lines, gens, slack_bus):
+    """The batch's distinct id rows (host), each grid's index among them (device) and the 1-based slack: one synchronisation."""
     if slack_bus is None:
         ids, inverse, _, is3 = _gns._classify_ids(lines, gens, extra=(buses[0, :, 1] == 3).to(torch.int64))
         slack_bus = _slack_from_type3(is3.numpy() != 0)
     else:
         ids, inverse, _ = _gns._classify_ids(lines, gens)
+    return ids.numpy(), inverse.to(buses.device), slack_bus
+
+
+def _plan_from(classified, buses, lines, gens, topo_cache, set_cache, analyse):
+    """The ``MixedPlan`` of a classified batch on the analyses of ``topo_cache`` (made by ``analyse``) and a set of ``set_cache``."""
+    ids_np, inverse, slack_bus = classified
+    N, E, Gn = buses.shape[1], lines.shape[1], gens.shape[1]
+    dev = buses.device
     set_key = (N, E, Gn, slack_bus, str(dev))
-    topo_set = _SET_CACHE.get(set_key)
+    topo_set = set_cache.get(set_key)
     if topo_set is None:
-        topo_set = _SET_CACHE[set_key] = _PfTopologySet(dev)
-    ids_np = ids.numpy()
+        topo_set = set_cache[set_key] = _PfTopologySet(dev)
     T = ids_np.shape[0]
     off = np.full(T, -1, dtype=np.int32)
     for k in range(T):
@@ -247,16 +299,15 @@ def _plan_mixed(buses, lines, gens, slack_bus):
         key = (N, E, Gn, slack_bus, str(dev), f_bus.tobytes(), t_bus.tobytes(), gen_bus.tobytes())
         if key in _ISLANDED:
             continue
-        topo = _TOPO_CACHE.get(key)
+        topo = topo_cache.get(key)
         if topo is None:
             try:
-                topo = _TOPO_CACHE[key] = analyse_topology(N, f_bus, t_bus, gen_bus, slack_bus, device=dev)
+                topo = topo_cache[key] = analyse(N, f_bus, t_bus, gen_bus, slack_bus, device=dev)
             except IslandedTopology:
                 _ISLANDED.add(key)
                 continue
         off[k] = topo_set.add(key, topo)
     topo_set.sync()
-    inverse = inverse.to(dev)
     order = torch.argsort(inverse, stable=True).to(torch.int32)
     grid_off = torch.from_numpy(off).to(dev)[inverse].contiguous()
     return MixedPlan(inverse, order, grid_off, off[off >= 0].copy(), topo_set, slack_bus, off < 0)
@@ -292,6 +343,35 @@ def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bu
     generator on a PV / slack bus; every other column gets 0.  A grid that did not converge (or is not solved) gets NaN gradient
     rows unless its incoming gradient is zero.  The forward outputs are bit-identical with and without gradients.  The warm
     start is not differentiated.  Contract: ``include/gns_powerflow.h``, "Gradients"."""
+    single, in_dev, buses, lines, generators, v0, theta0 = _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter,
+                                                                   mixed_topologies)
+    lib = load_library()
+    cfg = PfConfig(buses.shape[1], lines.shape[1], generators.shape[1], int(max_iter), float(tol))
+    plain = (buses.detach(), lines.detach(), generators.detach())   # what the analysis reads (host copies of id columns)
+    if mixed_topologies:
+        plan = _plan_mixed(*plain, slack_bus)
+        ts = plan.topo_set
+        set_bufs = (ts.host, ts.blob)                 # the set as this call sees it (a later call may grow it: offsets stay)
+
+        def solve(bu, li, ge):
+            return _solve_mixed(lib, cfg, plan, bu, li, ge, v0, theta0)
+
+        def adjoint(*args):
+            return _adjoint_mixed(lib, cfg, plan, set_bufs, *args)
+    else:
+        topo = _topology(*plain, slack_bus)
+
+        def solve(bu, li, ge):
+            return _solve_plain(lib, cfg, topo, bu, li, ge, v0, theta0)
+
+        def adjoint(*args):
+            return _adjoint_plain(lib, cfg, topo, *args)
+    return _run(solve, adjoint, buses, lines, generators, plain, in_dev, single)
+
+
+def _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter, mixed_topologies):
+    """The checked inputs of a solver call: ``(single, input device, buses, lines, generators, v0, theta0)``, the tensors
+    contiguous on the solve's device, the warm start float64 ``[Bt,N]`` there (both, or both None)."""
     single, buses, lines, generators = _as_batch(buses, lines, generators, B, L, G)
     if buses.device.type != 'cuda':
         if not torch.cuda.is_available():
@@ -319,37 +399,123 @@ def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bu
         v0, theta0 = start(v0, 1.0), start(theta0, 0.0)
     if not isinstance(mixed_topologies, bool):
         raise ValueError(f'mixed_topologies must be a bool, got {mixed_topologies!r}')
-    lib = load_library()
-    cfg = PfConfig(N, lines.shape[1], generators.shape[1], int(max_iter), float(tol))
     v0, theta0 = (v0, theta0) if warm else (None, None)
-    plain = (buses.detach(), lines.detach(), generators.detach())   # what the analysis reads (host copies of id columns)
-    if mixed_topologies:
-        plan = _plan_mixed(*plain, slack_bus)
-        ts = plan.topo_set
-        set_bufs = (ts.host, ts.blob)                 # the set as this call sees it (a later call may grow it: offsets stay)
+    return single, in_dev, buses, lines, generators, v0, theta0
 
-        def solve(bu, li, ge):
-            return _solve_mixed(lib, cfg, plan, bu, li, ge, v0, theta0)
 
-        def adjoint(*args):
-            return _adjoint_mixed(lib, cfg, plan, set_bufs, *args)
-    else:
-        topo = _topology(*plain, slack_bus)
-
-        def solve(bu, li, ge):
-            return _solve_plain(lib, cfg, topo, bu, li, ge, v0, theta0)
-
-        def adjoint(*args):
-            return _adjoint_plain(lib, cfg, topo, *args)
+def _run(solve, adjoint, buses, lines, generators, plain, in_dev, single):
+    """``solve`` (through ``_NRFunction`` with ``adjoint`` as its backward when an input requires grad), back on the input device."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (buses, lines, generators)):
         out = list(_NRFunction.apply(solve, adjoint, buses, lines, generators))
     else:
         out = solve(*plain)
-    if in_dev != dev:
+    if in_dev != buses.device:
         out = [t.to(in_dev) for t in out]
     if single:
         out = [t[0] for t in out]
     return PowerFlowResult(*out)
+
+
+FD_VARIANTS = {'XB': 2, 'BX': 3}    # PYPOWER's PF_ALG
+
+
+def fast_decoupled(buses, lines, generators, B=None, L=None, G=None, *, variant, slack_bus=None, v0=None, theta0=None, tol=1e-8,
+                   max_iter=30, mixed_topologies=False):
+    """Fast-decoupled AC power flow (PYPOWER ``makeB`` + ``fdpf``; ``runpf`` with ``PF_ALG`` 2 for ``variant='XB'``, 3 for
+    ``'BX'``) of every grid of a batch, on the device.
+
+    Inputs, column maps, the slack, PV / PQ roles, the start and the warm start, ``mixed_topologies`` and per-grid failure are those
+    of ``newton_raphson``.  B' (PV+PQ buses: no shunts, no charging, tau 1, shifts kept, r = 0 with XB) and B'' (PQ buses: no
+    shifts, r = 0 with BX) are factored once per grid; each iteration is a P half-step (theta -= B'^-1 P) and a Q half-step
+    (|V| -= B''^-1 Q), each followed by the test ``max(||P||_inf, ||Q||_inf) < tol`` on the scaled mismatch
+    ``(V conj(YV) - S) / |V|``, which is also tested at the start.  ``iterations`` counts P half-steps (at most ``max_iter``,
+    PYPOWER's 30); ``mismatch`` is that scaled norm where the last test read it (NR reports the unscaled ``||F||_inf``).  A zero
+    or non-finite pivot of either factor stops a grid at its start point unless the start already meets the test.
+
+    Returns ``PowerFlowResult(v, theta, converged, iterations, mismatch)`` as ``newton_raphson`` does; a grid's result is
+    bit-identical alone, in any batch and from run to run.
+
+    Gradients: FD solves F = 0, the equations of ``newton_raphson``, so with grad mode on and ``requires_grad`` on an input ``v`` and
+    ``theta`` are differentiable with NR's contract (its "Gradients" paragraph, include/gns_powerflow.h "Gradients"): the backward
+    is one ``gns_pf_adjoint`` / ``gns_pf_adjoint_set`` launch on the Newton-Raphson analysis of the same topology, at FD's
+    solution.  Contract: include/gns_powerflow.h, "Fast-decoupled"."""
+    if variant not in FD_VARIANTS:
+        raise ValueError(f"variant must be 'XB' or 'BX', got {variant!r}")
+    single, in_dev, buses, lines, generators, v0, theta0 = _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter,
+                                                                   mixed_topologies)
+    lib = load_library()
+    N, E, Gn = buses.shape[1], lines.shape[1], generators.shape[1]
+    cfg = FdConfig(PfConfig(N, E, Gn, int(max_iter), float(tol)), FD_VARIANTS[variant])
+    plain = (buses.detach(), lines.detach(), generators.detach())
+    grad = torch.is_grad_enabled() and any(t.requires_grad for t in (buses, lines, generators))
+    if mixed_topologies:
+        classified = _classify(*plain, slack_bus)
+        plan = _plan_from(classified, *plain, _FD_TOPO_CACHE, _FD_SET_CACHE, analyse_fd_topology)
+        if grad:                                      # the adjoint's NR set, from the same classification
+            nr_plan = _plan_from(classified, *plain, _TOPO_CACHE, _SET_CACHE, analyse_topology)
+            nr_bufs = (nr_plan.topo_set.host, nr_plan.topo_set.blob)
+
+        def solve(bu, li, ge):
+            return _solve_fd_mixed(lib, cfg, plan, bu, li, ge, v0, theta0)
+
+        def adjoint(*args):
+            return _adjoint_mixed(lib, cfg.pf, nr_plan, nr_bufs, *args)
+    else:
+        key, args = _topology_key(*plain, slack_bus, 'fast_decoupled')
+        topo = _cached(_FD_TOPO_CACHE, key, analyse_fd_topology, args, buses.device)
+        if grad:
+            nr_topo = _cached(_TOPO_CACHE, key, analyse_topology, args, buses.device)
+
+        def solve(bu, li, ge):
+            return _solve_fd_plain(lib, cfg, topo, bu, li, ge, v0, theta0)
+
+        def adjoint(*args):
+            return _adjoint_plain(lib, cfg.pf, nr_topo, *args)
+    return _run(solve, adjoint, buses, lines, generators, plain, in_dev, single)
+
+
+def _solve_fd_plain(lib, cfg, topo, buses, lines, generators, v0, theta0):
+    """One ``gns_fd_solve`` launch on the batch's one topology."""
+    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
+    nbytes = ctypes.c_size_t()
+    _check(lib.gns_fd_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_fd_workspace_bytes')
+    ws = _gns._workspace(nbytes.value, dev)
+    v, theta, conv, iters, mis = _outputs(Bt, N, dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.gns_fd_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                            generators.data_ptr(), Bt, _ptr(v0), _ptr(theta0), v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
+                            iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_fd_solve',
+           topo.info['lds_bytes'], _FD_LDS_FORMULA)
+    return [v, theta, conv.bool(), iters, mis]
+
+
+def _solve_fd_mixed(lib, cfg, plan, buses, lines, generators, v0, theta0):
+    """One ``gns_fd_solve_set`` launch over ``plan`` (a ``MixedPlan`` of FD blobs)."""
+    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
+    if plan.member_off.size == 0:                # every grid's topology islands a bus: nothing to solve
+        return _not_solved(Bt, N, dev)
+    ts, members = plan.topo_set, plan.member_off
+    lds = lambda: _set_lds_bytes(ts.host, members, fd=True)   # noqa: E731
+    nbytes = ctypes.c_size_t()
+    _check(lib.gns_fd_workspace_bytes_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.words, members.ctypes.data, members.size, Bt,
+                                          ctypes.byref(nbytes)), 'gns_fd_workspace_bytes_set', lds, _FD_LDS_FORMULA)
+    ws = _gns._workspace(nbytes.value, dev)
+    v, theta, conv, iters, mis = _outputs(Bt, N, dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _check(lib.gns_fd_solve_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.blob.data_ptr(), ts.words, members.ctypes.data,
+                                members.size, plan.grid_off.data_ptr(), plan.order.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                                generators.data_ptr(), Bt, _ptr(v0), _ptr(theta0), v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
+                                iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_fd_solve_set', lds,
+           _FD_LDS_FORMULA)
+    return [v, theta, conv.bool(), iters, mis]
+
+
+def _not_solved(Bt, N, dev):
+    """The outputs of a batch none of whose topologies can be solved (each islands a bus)."""
+    nan = float('nan')
+    return [torch.full((Bt, N), nan, dtype=torch.float64, device=dev), torch.full((Bt, N), nan, dtype=torch.float64, device=dev),
+            torch.zeros(Bt, dtype=torch.bool, device=dev), torch.full((Bt,), -1, dtype=torch.int32, device=dev),
+            torch.full((Bt,), nan, dtype=torch.float64, device=dev)]
 
 
 def _solve_plain(lib, cfg, topo, buses, lines, generators, v0, theta0):
@@ -458,10 +624,7 @@ def _solve_mixed(lib, cfg, plan, buses, lines, generators, v0, theta0):
     """One ``gns_pf_solve_set`` launch over ``plan`` (``_plan_mixed``); returns the five outputs as ``newton_raphson`` does."""
     Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
     if plan.member_off.size == 0:                # every grid's topology islands a bus: nothing to solve
-        nan = float('nan')
-        return [torch.full((Bt, N), nan, dtype=torch.float64, device=dev), torch.full((Bt, N), nan, dtype=torch.float64, device=dev),
-                torch.zeros(Bt, dtype=torch.bool, device=dev), torch.full((Bt,), -1, dtype=torch.int32, device=dev),
-                torch.full((Bt,), nan, dtype=torch.float64, device=dev)]
+        return _not_solved(Bt, N, dev)
     ts, members = plan.topo_set, plan.member_off
     nbytes = ctypes.c_size_t()
     _check(lib.gns_pf_workspace_bytes_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.words, members.ctypes.data, members.size, Bt,

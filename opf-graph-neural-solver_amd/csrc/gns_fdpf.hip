@@ -52,13 +52,8 @@ __device__ __forceinline__ double fd_mismatch(const int N, const int32_t* y_ptr,
   double nrm = 0.0;
   bool bad = false;
   for (int i = lane; i < N; i += PF_THREADS) {
-    double ir = 0.0, ii = 0.0;
-    for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
-      const int k = y_col[p];
-      const double2 y = Y[p];
-      ir += y.x * Vr[k] - y.y * Vi[k];
-      ii += y.x * Vi[k] + y.y * Vr[k];
-    }
+    const double2 cur = pf_row_current(i, y_ptr, y_col, Y, Vr, Vi);
+    const double ir = cur.x, ii = cur.y;
     if (p_idx[i] >= 0) {
       const double fp = ((Vr[i] * ir + Vi[i] * ii) - Psp[i]) / Vm[i];
       rhs1[p_idx[i]] = fp;
@@ -131,7 +126,8 @@ __device__ __forceinline__ void fd_solve_grid(const int32_t* topo, const int g, 
   const float* gen = gens + (size_t)g * Gn * 7;
   double2* Y = ybus_ws + (size_t)g * (SET ? ystride : nnzY);
 
-  // Y-bus values (makeYbus), specified injections, starting point (those of pf_solve_grid); fill slots of both factors start at 0
+  // Y-bus values (makeYbus), specified injections, starting point: those of pf_solve_grid, inline here and there, as the result
+  // store below (the reason is given there); fill slots of both factors start at 0
   for (int i = lane; i < N; i += PF_THREADS) {
     pf_ybus_row(i, y_ptr, y_diag, st_ptr, st, bus, line, Y);
     double pg = 0.0;
@@ -154,9 +150,8 @@ __device__ __forceinline__ void fd_solve_grid(const int32_t* topo, const int g, 
   __syncthreads();
   pf_run_program(topo[FH_NSTEPS_F1], topo + topo[FH_STEP_F1], reinterpret_cast<const int2*>(topo + topo[FH_OPS_F1]), F1, lane);
   pf_run_program(topo[FH_NSTEPS_F2], topo + topo[FH_STEP_F2], reinterpret_cast<const int2*>(topo + topo[FH_OPS_F2]), F2, lane);
-  bool bad_pivot = false;
-  for (int k = lane; k < d1; k += PF_THREADS) { const double pv = F1[piv1[k]]; bad_pivot |= pv == 0.0 || !pf_finite(pv); }
-  for (int k = lane; k < d2; k += PF_THREADS) { const double pv = F2[piv2[k]]; bad_pivot |= pv == 0.0 || !pf_finite(pv); }
+  bool bad_pivot = pf_bad_pivot(d1, piv1, F1, lane);
+  bad_pivot |= pf_bad_pivot(d2, piv2, F2, lane);
   bad_pivot = __ballot(bad_pivot) != 0;
 
   const int ns1 = topo[FH_NSTEPS_S1], ns2 = topo[FH_NSTEPS_S2];
@@ -211,19 +206,12 @@ __global__ __launch_bounds__(PF_THREADS) void gns_fd_set_kernel(const int32_t* _
                                                                 double* __restrict__ th_out, uint8_t* __restrict__ conv_out,
                                                                 int32_t* __restrict__ it_out, double* __restrict__ mis_out,
                                                                 double2* __restrict__ ybus_ws, int max_iter, double tol, int alg) {
-  const int64_t w = blockIdx.x;
-  const int64_t g64 = order ? (int64_t)order[w] : w;
+  const int64_t g64 = pf_set_grid(order);
   if (g64 < 0 || g64 >= Bt) return;                             // not a grid of this batch: nothing to write
   const int g = (int)g64;
-  const int64_t off = grid_off[g];
-  bool ok = off >= 0 && off % PF_SET_ALIGN_WORDS == 0 && off + FD_HDR_WORDS <= set_words;
-  const int32_t* topo = set + (ok ? off : 0);
-  if (ok) {
-    ok = topo[FH_MAGIC] == GNS_FD_MAGIC && topo[FH_N] == N && topo[FH_E] == E && topo[FH_GN] == Gn &&
-         topo[FH_TOTAL] >= FD_HDR_WORDS && topo[FH_TOTAL] <= set_words - off && topo[FH_NNZY] >= 0 && topo[FH_NNZY] <= nnzy_max &&
-         fd_lds_bytes(topo) <= lds_bytes;
-  }
-  if (!ok) {
+  const int32_t* topo;
+  if (!pf_set_member<FdBlobKind>(set, set_words, grid_off[g], N, E, Gn, lds_bytes, nnzy_max, topo)) {
+    // the not-solved outputs, inline as in gns_pf_set_kernel (the reason is given there)
     const double nan = __builtin_nan("");
     for (int i = threadIdx.x; i < N; i += PF_THREADS) {
       v_out[(size_t)g * N + i] = nan;
@@ -236,46 +224,14 @@ __global__ __launch_bounds__(PF_THREADS) void gns_fd_set_kernel(const int32_t* _
                       tol, alg);
 }
 
-bool fd_config_ok(const gns_fd_config* cfg) {
-  return cfg && cfg->pf.max_iter >= 0 && cfg->pf.tol >= 0.0 && (cfg->alg == 2 || cfg->alg == 3);
-}
-
-bool fd_header_ok(const gns_fd_config* cfg, const int32_t* h) {
-  return h[FH_MAGIC] == GNS_FD_MAGIC && h[FH_N] == cfg->pf.n_bus && h[FH_E] == cfg->pf.n_line && h[FH_GN] == cfg->pf.n_gen;
-}
-
-// Host check of the members of a set of FD blobs (pf_scan_set's checks): GNS_OK with the largest nnz(Y) and LDS image, GNS_EINVAL,
-// or GNS_EUNSUPPORTED when a member's LDS image is too large.
-int fd_scan_set(const gns_fd_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off, int32_t n_member,
-                int32_t* nnzy_max, int64_t* lds_max) {
-  if (!cfg || !set_host || !member_off || n_member <= 0 || set_words > (size_t)INT32_MAX) return GNS_EINVAL;
-  const int32_t* set = static_cast<const int32_t*>(set_host);
-  int32_t ny = 0;
-  int64_t lds = 0;
-  bool too_big = false;
-  for (int32_t m = 0; m < n_member; ++m) {
-    const int64_t off = member_off[m];
-    if (off < 0 || off % PF_SET_ALIGN_WORDS != 0 || off + FD_HDR_WORDS > (int64_t)set_words) return GNS_EINVAL;
-    const int32_t* h = set + off;
-    if (!fd_header_ok(cfg, h) || h[FH_TOTAL] < FD_HDR_WORDS || h[FH_TOTAL] > (int64_t)set_words - off || h[FH_NNZY] < 0)
-      return GNS_EINVAL;
-    ny = h[FH_NNZY] > ny ? h[FH_NNZY] : ny;
-    const int64_t b = fd_lds_bytes(h);
-    lds = b > lds ? b : lds;
-    too_big |= b > GNS_PF_LDS_MAX_BYTES;
-  }
-  if (too_big) return GNS_EUNSUPPORTED;
-  *nnzy_max = ny;
-  *lds_max = lds;
-  return GNS_OK;
-}
+bool fd_config_ok(const gns_fd_config* cfg) { return cfg && pf_config_ok(&cfg->pf) && (cfg->alg == 2 || cfg->alg == 3); }
 
 }  // namespace
 
 extern "C" int gns_fd_workspace_bytes(const gns_fd_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes) {
   if (!cfg || !topo_host || !bytes || Bt <= 0) return GNS_EINVAL;
   const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!fd_header_ok(cfg, h)) return GNS_EINVAL;
+  if (!pf_header_ok<FdBlobKind>(&cfg->pf, h)) return GNS_EINVAL;
   *bytes = pf_ws_bytes_nnzy(h[FH_NNZY], Bt);
   return GNS_OK;
 }
@@ -285,26 +241,15 @@ extern "C" int gns_fd_solve(const gns_fd_config* cfg, const void* topo_host, con
                             const double* v0, const double* theta0,
                             double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  if (!fd_config_ok(cfg) || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF)
+  if (!fd_config_ok(cfg) || !topo_host ||
+      !pf_solve_args_ok(topo_dev, buses, lines, generators, Bt, v0, theta0, v, theta, converged, iterations, mismatch, workspace))
     return GNS_EINVAL;
-  if (!v || !theta || !converged || !iterations || !mismatch || !workspace || (v0 == nullptr) != (theta0 == nullptr))
-    return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!fd_header_ok(cfg, h)) return GNS_EINVAL;
-  if (workspace_bytes < pf_ws_bytes_nnzy(h[FH_NNZY], Bt)) return GNS_ESIZE;
-  const int64_t lds = fd_lds_bytes(h);
-  if (lds > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_fd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
-      return GNS_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gns_fd_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)lds, (hipStream_t)stream,
-                     static_cast<const int32_t*>(topo_dev), buses, lines, generators, v0, theta0, v, theta, converged, iterations,
-                     mismatch, static_cast<double2*>(workspace), cfg->pf.max_iter, cfg->pf.tol, cfg->alg);
-  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+  int64_t lds = 0;
+  const int rc = pf_check_topology<FdBlobKind>(&cfg->pf, static_cast<const int32_t*>(topo_host), Bt, workspace_bytes, &lds);
+  if (rc != GNS_OK) return rc;
+  return pf_launch<gns_fd_kernel>(Bt, lds, stream, static_cast<const int32_t*>(topo_dev), buses, lines, generators, v0, theta0, v,
+                                  theta, converged, iterations, mismatch, static_cast<double2*>(workspace), cfg->pf.max_iter,
+                                  cfg->pf.tol, cfg->alg);
 }
 
 extern "C" int gns_fd_workspace_bytes_set(const gns_fd_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
@@ -312,7 +257,7 @@ extern "C" int gns_fd_workspace_bytes_set(const gns_fd_config* cfg, const void* 
   if (!bytes || Bt <= 0) return GNS_EINVAL;
   int32_t nnzy = 0;
   int64_t lds = 0;
-  const int rc = fd_scan_set(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
+  const int rc = pf_scan_set<FdBlobKind>(cfg ? &cfg->pf : nullptr, set_host, set_words, member_off, n_member, &nnzy, &lds);
   if (rc != GNS_OK) return rc;
   *bytes = pf_ws_bytes_nnzy(nnzy, Bt);
   return GNS_OK;
@@ -324,25 +269,16 @@ extern "C" int gns_fd_solve_set(const gns_fd_config* cfg, const void* set_host, 
                                 const double* v0, const double* theta0,
                                 double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (!fd_config_ok(cfg) || !set_dev || !grid_off || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF)
-    return GNS_EINVAL;
-  if (!v || !theta || !converged || !iterations || !mismatch || !workspace || (v0 == nullptr) != (theta0 == nullptr))
+  if (!fd_config_ok(cfg) || !grid_off ||
+      !pf_solve_args_ok(set_dev, buses, lines, generators, Bt, v0, theta0, v, theta, converged, iterations, mismatch, workspace))
     return GNS_EINVAL;
   int32_t nnzy = 0;
   int64_t lds = 0;
-  const int rc = fd_scan_set(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
+  const int rc = pf_scan_set<FdBlobKind>(&cfg->pf, set_host, set_words, member_off, n_member, &nnzy, &lds);
   if (rc != GNS_OK) return rc;
   if (workspace_bytes < pf_ws_bytes_nnzy(nnzy, Bt)) return GNS_ESIZE;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_fd_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
-      return GNS_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gns_fd_set_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)lds, (hipStream_t)stream,
-                     static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off, order, Bt, cfg->pf.n_bus, cfg->pf.n_line,
-                     cfg->pf.n_gen, lds, nnzy, buses, lines, generators, v0, theta0, v, theta, converged, iterations, mismatch,
-                     static_cast<double2*>(workspace), cfg->pf.max_iter, cfg->pf.tol, cfg->alg);
-  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+  return pf_launch<gns_fd_set_kernel>(Bt, lds, stream, static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off, order, Bt,
+                                      cfg->pf.n_bus, cfg->pf.n_line, cfg->pf.n_gen, lds, nnzy, buses, lines, generators, v0, theta0,
+                                      v, theta, converged, iterations, mismatch, static_cast<double2*>(workspace), cfg->pf.max_iter,
+                                      cfg->pf.tol, cfg->alg);
 }

@@ -1,8 +1,11 @@
-// Device helpers the power-flow kernels share (gns_powerflow.hip: Newton-Raphson and its adjoint; gns_fdpf.hip: fast-decoupled):
-// one wave per grid, the Y-bus of a grid from its line stamps, and the interpreter of the blobs' op programs.
+// What the power-flow kernels and their entry points share (gns_powerflow.hip: Newton-Raphson and its adjoint; gns_fdpf.hip:
+// fast-decoupled).  Device: one wave per grid, the Y-bus of a grid from its line stamps, I = Y V, the pivot test, the interpreter of
+// the blobs' op programs and the grid and member checks of a set kernel.  Host: the checks of a call's
+// arguments, of one blob and of a set of blobs, and the launch.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/gns_powerflow.h"
 #include "gns_pf_common.h"
 
 namespace {
@@ -41,6 +44,29 @@ __device__ __forceinline__ void pf_ybus_row(const int i, const int32_t* y_ptr, c
   }
 }
 
+// I_i = sum_k Y_ik V_k over row i of the Y-bus, as (Re, Im)
+__device__ __forceinline__ double2 pf_row_current(const int i, const int32_t* y_ptr, const int32_t* y_col, const double2* Y,
+                                                  const double* Vr, const double* Vi) {
+  double ir = 0.0, ii = 0.0;
+  for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
+    const int k = y_col[p];
+    const double2 y = Y[p];
+    ir += y.x * Vr[k] - y.y * Vi[k];
+    ii += y.x * Vi[k] + y.y * Vr[k];
+  }
+  return make_double2(ir, ii);
+}
+
+// Whether one of this lane's pivots of a factor (F at the slots pivot[0 .. dim) names) is zero or not finite
+__device__ __forceinline__ bool pf_bad_pivot(const int dim, const int32_t* pivot, const double* F, const int lane) {
+  bool bad = false;
+  for (int k = lane; k < dim; k += PF_THREADS) {
+    const double pv = F[pivot[k]];
+    bad |= pv == 0.0 || !pf_finite(pv);
+  }
+  return bad;
+}
+
 // One op program of the blob (PH_STEP_PTR / PH_OPS, or the transposed PH_T_*): F[dst] -= F[a] F[b] or F[dst] /= F[a],
 // independent within a step, a barrier after each step
 __device__ __forceinline__ void pf_run_program(const int nsteps, const int32_t* step_ptr, const int2* ops, double* F, const int lane) {
@@ -56,7 +82,112 @@ __device__ __forceinline__ void pf_run_program(const int nsteps, const int32_t* 
   }
 }
 
+// A set kernel's workgroup to its grid and blob, in two steps (the adjoint answers a zero incoming gradient between them).
+// The grid of this workgroup: order ? order[w] : w.  The caller returns, writing nothing, unless it is a grid of the batch.
+__device__ __forceinline__ int64_t pf_set_grid(const int32_t* order) {
+  const int64_t w = blockIdx.x;
+  return order ? (int64_t)order[w] : w;
+}
+
+// The blob of a grid whose grid_off is off, into topo.  False for a grid without a usable blob: off is -1, misaligned or outside
+// the set, or not at a blob of this kind and shape that lies inside the set and whose Y-bus and LDS image fit the launch.  Nothing
+// past the set's first header is read then: this is what keeps a bad offset from indexing outside the set.
+template <class Kind>
+__device__ __forceinline__ bool pf_set_member(const int32_t* set, const int64_t set_words, const int64_t off, const int N,
+                                              const int E, const int Gn, const int64_t lds_bytes, const int nnzy_max,
+                                              const int32_t*& topo) {
+  bool ok = off >= 0 && off % PF_SET_ALIGN_WORDS == 0 && off + Kind::HDR_WORDS <= set_words;
+  topo = set + (ok ? off : 0);
+  if (ok) {
+    ok = topo[PH_MAGIC] == Kind::MAGIC && topo[PH_N] == N && topo[PH_E] == E && topo[PH_GN] == Gn &&
+         topo[PH_TOTAL] >= Kind::HDR_WORDS && topo[PH_TOTAL] <= set_words - off && topo[Kind::NNZY] >= 0 &&
+         topo[Kind::NNZY] <= nnzy_max && Kind::lds_bytes(topo) <= lds_bytes;
+  }
+  return ok;
+}
+
 // Device workspace of Bt grids: their Y-bus values, 16 bytes per entry, rounded up to 256 bytes
 inline size_t pf_ws_bytes_nnzy(int64_t nnzy, int64_t Bt) { return (((size_t)Bt * nnzy * sizeof(double2)) + 255) & ~(size_t)255; }
+
+// ---- host: what the entry points (include/gns_powerflow.h) check before a launch.  shape is the gns_pf_config that holds
+// n_bus, n_line and n_gen (a gns_fd_config's pf).
+
+inline bool pf_config_ok(const gns_pf_config* cfg) { return cfg && cfg->max_iter >= 0 && cfg->tol >= 0.0; }
+
+// The arguments of a solve call, but for its configuration and host blob(s): the device blob or set, the inputs, a batch one launch
+// takes, a warm start with both parts or neither, every output, the workspace
+inline bool pf_solve_args_ok(const void* blob_dev, const float* buses, const float* lines, const float* gens, int64_t Bt,
+                             const double* v0, const double* theta0, const double* v, const double* theta, const uint8_t* converged,
+                             const int32_t* iterations, const double* mismatch, const void* workspace) {
+  return blob_dev && buses && lines && gens && Bt > 0 && Bt <= 0x7FFFFFFF && (v0 == nullptr) == (theta0 == nullptr) && v && theta &&
+         converged && iterations && mismatch && workspace;
+}
+
+// The arguments of an adjoint call, but for its configuration and host blob(s).  Unlike a solve's, any of its outputs may be NULL.
+inline bool pf_adjoint_args_ok(const void* blob_dev, const float* buses, const float* lines, const float* gens, int64_t Bt,
+                               const double* v, const double* theta, const uint8_t* converged, const void* workspace) {
+  return blob_dev && buses && lines && gens && Bt > 0 && Bt <= 0x7FFFFFFF && v && theta && converged && workspace;
+}
+
+template <class Kind>
+bool pf_header_ok(const gns_pf_config* shape, const int32_t* h) {
+  return h[PH_MAGIC] == Kind::MAGIC && h[PH_N] == shape->n_bus && h[PH_E] == shape->n_line && h[PH_GN] == shape->n_gen;
+}
+
+// Host check of a call on the one blob at h, in the order its codes win: GNS_EINVAL unless it is a blob of this kind and shape,
+// GNS_ESIZE for a workspace that does not hold the Y-bus of Bt grids, GNS_EUNSUPPORTED for an LDS image above the limit.
+template <class Kind>
+int pf_check_topology(const gns_pf_config* shape, const int32_t* h, int64_t Bt, size_t workspace_bytes, int64_t* lds) {
+  if (!pf_header_ok<Kind>(shape, h)) return GNS_EINVAL;
+  if (workspace_bytes < pf_ws_bytes_nnzy(h[Kind::NNZY], Bt)) return GNS_ESIZE;
+  *lds = Kind::lds_bytes(h);
+  return *lds > GNS_PF_LDS_MAX_BYTES ? GNS_EUNSUPPORTED : GNS_OK;
+}
+
+// Host check of the members of a set: each at an aligned word offset with its whole blob inside set_words, a blob of this kind and
+// shape.  Returns GNS_OK with the largest nnz(Y) and LDS image, GNS_EINVAL, or GNS_EUNSUPPORTED when a member's LDS image is too
+// large (GNS_EINVAL wins over it whichever member comes first).
+template <class Kind>
+int pf_scan_set(const gns_pf_config* shape, const void* set_host, size_t set_words, const int32_t* member_off, int32_t n_member,
+                int32_t* nnzy_max, int64_t* lds_max) {
+  if (!shape || !set_host || !member_off || n_member <= 0 || set_words > (size_t)INT32_MAX) return GNS_EINVAL;
+  const int32_t* set = static_cast<const int32_t*>(set_host);
+  int32_t ny = 0;
+  int64_t lds = 0;
+  bool too_big = false;
+  for (int32_t m = 0; m < n_member; ++m) {
+    const int64_t off = member_off[m];
+    if (off < 0 || off % PF_SET_ALIGN_WORDS != 0 || off + Kind::HDR_WORDS > (int64_t)set_words) return GNS_EINVAL;
+    const int32_t* h = set + off;
+    if (!pf_header_ok<Kind>(shape, h) || h[PH_TOTAL] < Kind::HDR_WORDS || h[PH_TOTAL] > (int64_t)set_words - off || h[Kind::NNZY] < 0)
+      return GNS_EINVAL;
+    ny = h[Kind::NNZY] > ny ? h[Kind::NNZY] : ny;
+    const int64_t b = Kind::lds_bytes(h);
+    lds = b > lds ? b : lds;
+    too_big |= b > GNS_PF_LDS_MAX_BYTES;
+  }
+  if (too_big) return GNS_EUNSUPPORTED;
+  *nnzy_max = ny;
+  *lds_max = lds;
+  return GNS_OK;
+}
+
+// Launches Kernel with a workgroup per grid and lds_bytes of dynamic LDS.  Before the first launch the kernel's dynamic-LDS limit
+// is raised to GNS_PF_LDS_MAX_BYTES, once per process, on the device that is current then.  The flag belongs to the instantiation
+// (kernel and argument types): that is one per kernel only because each kernel is launched from one entry point; a second call
+// site with other argument types would get a flag of its own.  State per device would change what a second device sees; it would
+// be added here alone.
+template <auto Kernel, class... Args>
+int pf_launch(int64_t Bt, int64_t lds_bytes, void* stream, Args... args) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
+      return GNS_ELAUNCH;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)lds_bytes, (hipStream_t)stream, args...);
+  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+}
 
 }  // namespace

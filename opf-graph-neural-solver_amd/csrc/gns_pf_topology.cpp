@@ -278,12 +278,6 @@ int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int3
   return GNS_OK;
 }
 
-int analyse_safe(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& w,
-                 int64_t* slots_out = nullptr) {
-  try { return analyse(N, E, Gn, f, t, gb, slack, w, slots_out); } catch (...) { return GNS_EINVAL; }
-}
-
-
 // The fast-decoupled analysis: B' on the PV+PQ buses and B'' on the PQ buses share the Y-bus pattern; each gets a minimum-degree
 // ordering of its bus subgraph, a symbolic LU, and a factorisation and a solve program (layout: gns_pf_common.h, FH_*).  With
 // slots_out, the larger of the two factors' slot counts is written there as soon as both are known.
@@ -351,41 +345,62 @@ int analyse_fd(int N, int E, int Gn, const int32_t* f, const int32_t* t, const i
   return GNS_OK;
 }
 
-int analyse_fd_safe(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& w,
-                    int64_t* slots_out = nullptr) {
-  try { return analyse_fd(N, E, Gn, f, t, gb, slack, w, slots_out); } catch (...) { return GNS_EINVAL; }
+// The three entry points of an analysis (analyse or analyse_fd), written once.  An exception of the analysis (out of memory on an
+// absurd shape) is GNS_EINVAL.
+using Analysis = int (*)(int, int, int, const int32_t*, const int32_t*, const int32_t*, int, std::vector<int32_t>&, int64_t*);
+
+struct TopologyArgs {
+  int32_t n_bus, n_line, n_gen;
+  const int32_t *f_bus, *t_bus, *gen_bus;
+  int32_t slack;
+};
+
+int analyse_safe(Analysis fn, const TopologyArgs& a, std::vector<int32_t>& w, int64_t* slots_out = nullptr) {
+  try { return fn(a.n_bus, a.n_line, a.n_gen, a.f_bus, a.t_bus, a.gen_bus, a.slack, w, slots_out); } catch (...) { return GNS_EINVAL; }
+}
+
+int topology_bytes(Analysis fn, const TopologyArgs& a, size_t* bytes) {
+  if (!bytes) return GNS_EINVAL;
+  std::vector<int32_t> w;
+  const int rc = analyse_safe(fn, a, w);
+  if (rc != GNS_OK) return rc;
+  *bytes = w.size() * sizeof(int32_t);
+  return GNS_OK;
+}
+
+int topology_slots(Analysis fn, const TopologyArgs& a, int64_t* slots) {
+  if (!slots) return GNS_EINVAL;
+  std::vector<int32_t> w;
+  *slots = -1;
+  const int rc = analyse_safe(fn, a, w, slots);
+  return rc == GNS_EUNSUPPORTED && *slots > GNS_PF_MAX_SLOTS ? GNS_OK : rc;
+}
+
+int prepare_topology(Analysis fn, const TopologyArgs& a, void* topo_host_out, size_t topo_bytes) {
+  if (!topo_host_out) return GNS_EINVAL;
+  std::vector<int32_t> w;
+  const int rc = analyse_safe(fn, a, w);
+  if (rc != GNS_OK) return rc;
+  if (w.size() * sizeof(int32_t) > topo_bytes) return GNS_ESIZE;
+  std::memcpy(topo_host_out, w.data(), w.size() * sizeof(int32_t));
+  return GNS_OK;
 }
 
 }  // namespace
 
 extern "C" int gns_pf_topology_bytes(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                                      const int32_t* gen_bus, int32_t slack, size_t* bytes) {
-  if (!bytes) return GNS_EINVAL;
-  std::vector<int32_t> w;
-  const int rc = analyse_safe(n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, w);
-  if (rc != GNS_OK) return rc;
-  *bytes = w.size() * sizeof(int32_t);
-  return GNS_OK;
+  return topology_bytes(analyse, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack}, bytes);
 }
 
 extern "C" int gns_pf_topology_slots(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                                      const int32_t* gen_bus, int32_t slack, int64_t* slots) {
-  if (!slots) return GNS_EINVAL;
-  std::vector<int32_t> w;
-  *slots = -1;
-  const int rc = analyse_safe(n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, w, slots);
-  return rc == GNS_EUNSUPPORTED && *slots > GNS_PF_MAX_SLOTS ? GNS_OK : rc;
+  return topology_slots(analyse, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack}, slots);
 }
 
 extern "C" int gns_pf_prepare_topology(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                                        const int32_t* gen_bus, int32_t slack, void* topo_host_out, size_t topo_bytes) {
-  if (!topo_host_out) return GNS_EINVAL;
-  std::vector<int32_t> w;
-  const int rc = analyse_safe(n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, w);
-  if (rc != GNS_OK) return rc;
-  if (w.size() * sizeof(int32_t) > topo_bytes) return GNS_ESIZE;
-  std::memcpy(topo_host_out, w.data(), w.size() * sizeof(int32_t));
-  return GNS_OK;
+  return prepare_topology(analyse, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack}, topo_host_out, topo_bytes);
 }
 
 extern "C" int gns_pf_topology_info(const void* topo_host, gns_pf_info* info) {
@@ -403,32 +418,17 @@ extern "C" int gns_pf_topology_info(const void* topo_host, gns_pf_info* info) {
 
 extern "C" int gns_fd_topology_bytes(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                                      const int32_t* gen_bus, int32_t slack, size_t* bytes) {
-  if (!bytes) return GNS_EINVAL;
-  std::vector<int32_t> w;
-  const int rc = analyse_fd_safe(n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, w);
-  if (rc != GNS_OK) return rc;
-  *bytes = w.size() * sizeof(int32_t);
-  return GNS_OK;
+  return topology_bytes(analyse_fd, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack}, bytes);
 }
 
 extern "C" int gns_fd_topology_slots(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                                      const int32_t* gen_bus, int32_t slack, int64_t* slots) {
-  if (!slots) return GNS_EINVAL;
-  std::vector<int32_t> w;
-  *slots = -1;
-  const int rc = analyse_fd_safe(n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, w, slots);
-  return rc == GNS_EUNSUPPORTED && *slots > GNS_PF_MAX_SLOTS ? GNS_OK : rc;
+  return topology_slots(analyse_fd, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack}, slots);
 }
 
 extern "C" int gns_fd_prepare_topology(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                                        const int32_t* gen_bus, int32_t slack, void* topo_host_out, size_t topo_bytes) {
-  if (!topo_host_out) return GNS_EINVAL;
-  std::vector<int32_t> w;
-  const int rc = analyse_fd_safe(n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, w);
-  if (rc != GNS_OK) return rc;
-  if (w.size() * sizeof(int32_t) > topo_bytes) return GNS_ESIZE;
-  std::memcpy(topo_host_out, w.data(), w.size() * sizeof(int32_t));
-  return GNS_OK;
+  return prepare_topology(analyse_fd, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack}, topo_host_out, topo_bytes);
 }
 
 extern "C" int gns_fd_topology_info(const void* topo_host, gns_fd_info* info) {

@@ -80,7 +80,11 @@ __device__ __forceinline__ void pf_solve_grid(const int32_t* topo, const int g, 
   const float* gen = gens + (size_t)g * Gn * 7;
   double2* Y = ybus_ws + (size_t)g * (SET ? ystride : nnzY);
 
-  // Y-bus values (makeYbus), specified injections, starting point
+  // Y-bus values (makeYbus), specified injections, starting point.  This loop, the row product and the pivot test in the
+  // iteration and the result store stay written out in this body although fd_solve_grid has the same loop and store and
+  // gns_pf_device.h has pf_row_current and pf_bad_pivot: with any of them behind a shared helper the compiler allocates
+  // gns_pf_kernel or gns_pf_set_kernel differently, and those variants (not kept) ran 1.1 to 3.8 % slower
+  // (profiles/pf_refactor/gpu_time_helper_variants.txt).  As written both kernels compile to the instructions they had before.
   for (int i = lane; i < N; i += PF_THREADS) {
     pf_ybus_row(i, y_ptr, y_diag, st_ptr, st, bus, line, Y);
     double pg = 0.0;
@@ -106,7 +110,7 @@ __device__ __forceinline__ void pf_solve_grid(const int32_t* topo, const int g, 
     double nrm = 0.0;
     bool bad = false;
     for (int i = lane; i < N; i += PF_THREADS) {
-      double ir = 0.0, ii = 0.0;
+      double ir = 0.0, ii = 0.0;                 // I_i = sum_k Y_ik V_k, pf_row_current's sum (written out: see the set-up loop)
       for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
         const int k = y_col[p];
         const double2 y = Y[p];
@@ -144,7 +148,7 @@ __device__ __forceinline__ void pf_solve_grid(const int32_t* topo, const int g, 
     pf_run_program(nsteps, step_ptr, ops, F, lane);
 
     // the update, only if every pivot is a finite non-zero and the new iterate is finite
-    for (int k = lane; k < dim; k += PF_THREADS) {
+    for (int k = lane; k < dim; k += PF_THREADS) {      // pf_bad_pivot's test (written out: see the set-up loop)
       const double pv = F[pivot[k]];
       bad |= pv == 0.0 || !pf_finite(pv);
     }
@@ -180,8 +184,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pf_kernel(const int32_t* __res
 }
 
 // A batch over a set of blobs (gns_pf_solve_set): workgroup w solves grid g = order ? order[w] : w on the blob at set + grid_off[g].
-// A grid without a usable blob (grid_off -1, or an offset that is misaligned, outside the set, or not at a blob of this shape
-// whose LDS image and Y-bus fit the launch) gets the not-solved outputs and never indexes the set.
+// A grid without a usable blob (pf_set_member) gets the not-solved outputs and never indexes the set.
 __global__ __launch_bounds__(PF_THREADS) void gns_pf_set_kernel(const int32_t* __restrict__ set, int64_t set_words,
                                                                 const int32_t* __restrict__ grid_off, const int32_t* __restrict__ order,
                                                                 int64_t Bt, int N, int E, int Gn, int64_t lds_bytes, int nnzy_max,
@@ -191,19 +194,13 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pf_set_kernel(const int32_t* _
                                                                 double* __restrict__ th_out, uint8_t* __restrict__ conv_out,
                                                                 int32_t* __restrict__ it_out, double* __restrict__ mis_out,
                                                                 double2* __restrict__ ybus_ws, int max_iter, double tol) {
-  const int64_t w = blockIdx.x;
-  const int64_t g64 = order ? (int64_t)order[w] : w;
+  const int64_t g64 = pf_set_grid(order);
   if (g64 < 0 || g64 >= Bt) return;                             // not a grid of this batch: nothing to write
   const int g = (int)g64;
-  const int64_t off = grid_off[g];
-  bool ok = off >= 0 && off % PF_SET_ALIGN_WORDS == 0 && off + PF_HDR_WORDS <= set_words;
-  const int32_t* topo = set + (ok ? off : 0);
-  if (ok) {
-    ok = topo[PH_MAGIC] == GNS_PF_MAGIC && topo[PH_N] == N && topo[PH_E] == E && topo[PH_GN] == Gn &&
-         topo[PH_TOTAL] >= PF_HDR_WORDS && topo[PH_TOTAL] <= set_words - off && topo[PH_NNZY] >= 0 && topo[PH_NNZY] <= nnzy_max &&
-         pf_lds_bytes(topo) <= lds_bytes;
-  }
-  if (!ok) {
+  const int32_t* topo;
+  if (!pf_set_member<PfBlobKind>(set, set_words, grid_off[g], N, E, Gn, lds_bytes, nnzy_max, topo)) {
+    // the not-solved outputs.  (Also in gns_fd_set_kernel, inline in both: as a shared helper these stores moved this kernel's
+    // scalar register allocation, 56 -> 39 SGPR spills, and it ran 2.4-3.2 % slower: profiles/pf_refactor/gpu_time_helper_variants.txt.)
     const double nan = __builtin_nan("");
     for (int i = threadIdx.x; i < N; i += PF_THREADS) {
       v_out[(size_t)g * N + i] = nan;
@@ -301,14 +298,8 @@ __device__ __forceinline__ void pf_adjoint_grid(const int32_t* topo, const int g
   for (int s = lane; s < nnzLU + dim; s += PF_THREADS) F[s] = 0.0;
   __syncthreads();
   for (int i = lane; i < N; i += PF_THREADS) {
-    double ir = 0.0, ii = 0.0;
-    for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
-      const int k = y_col[p];
-      const double2 y = Y[p];
-      ir += y.x * Vr[k] - y.y * Vi[k];
-      ii += y.x * Vi[k] + y.y * Vr[k];
-    }
-    Ir[i] = ir; Ii[i] = ii;
+    const double2 cur = pf_row_current(i, y_ptr, y_col, Y, Vr, Vi);
+    Ir[i] = cur.x; Ii[i] = cur.y;
   }
   __syncthreads();
 
@@ -317,12 +308,7 @@ __device__ __forceinline__ void pf_adjoint_grid(const int32_t* topo, const int g
     if (i != slack) pf_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
   __syncthreads();
   pf_run_program(t_step_ptr[t_nsteps + 1], step_ptr, ops, F, lane);   // the steps that hold the factorisation
-  bool bad = false;
-  for (int k = lane; k < dim; k += PF_THREADS) {
-    const double pv = F[pivot[k]];
-    bad |= pv == 0.0 || !pf_finite(pv);
-  }
-  if (__ballot(bad)) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
+  if (__ballot(pf_bad_pivot(dim, pivot, F, lane))) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
 
   // J^T lambda = [dl/dtheta at PV+PQ ; dl/d|V| at PQ] (the slack's theta is constant: its incoming gradient is not used)
   for (int i = lane; i < N; i += PF_THREADS) {
@@ -450,53 +436,14 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pf_adjoint_set_kernel(const in
                                                                         const double* __restrict__ gv, const double* __restrict__ gth,
                                                                         float* __restrict__ gb_out, float* __restrict__ gl_out,
                                                                         float* __restrict__ gg_out, double2* __restrict__ ybus_ws) {
-  const int64_t w = blockIdx.x;
-  const int64_t g64 = order ? (int64_t)order[w] : w;
+  const int64_t g64 = pf_set_grid(order);
   if (g64 < 0 || g64 >= Bt) return;
   const int g = (int)g64;
   if (pf_zero_incoming(g, N, gv, gth)) { pf_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
-  const int64_t off = grid_off[g];
-  bool ok = off >= 0 && off % PF_SET_ALIGN_WORDS == 0 && off + PF_HDR_WORDS <= set_words;
-  const int32_t* topo = set + (ok ? off : 0);
-  if (ok) {
-    ok = topo[PH_MAGIC] == GNS_PF_MAGIC && topo[PH_N] == N && topo[PH_E] == E && topo[PH_GN] == Gn &&
-         topo[PH_TOTAL] >= PF_HDR_WORDS && topo[PH_TOTAL] <= set_words - off && topo[PH_NNZY] >= 0 && topo[PH_NNZY] <= nnzy_max &&
-         pf_lds_bytes(topo) <= lds_bytes;
-  }
+  const int32_t* topo;
+  const bool ok = pf_set_member<PfBlobKind>(set, set_words, grid_off[g], N, E, Gn, lds_bytes, nnzy_max, topo);
   if (!ok || !conv_in[g]) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
   pf_adjoint_grid<true>(topo, g, buses, lines, v_in, th_in, gv, gth, gb_out, gl_out, gg_out, ybus_ws, nnzy_max);
-}
-
-size_t pf_ws_bytes(const int32_t* h, int64_t Bt) { return pf_ws_bytes_nnzy(h[PH_NNZY], Bt); }
-
-bool pf_header_ok(const gns_pf_config* cfg, const int32_t* h) {
-  return h[PH_MAGIC] == GNS_PF_MAGIC && h[PH_N] == cfg->n_bus && h[PH_E] == cfg->n_line && h[PH_GN] == cfg->n_gen;
-}
-
-// Host check of the members of a set: each at an aligned word offset with its whole blob inside set_words, a blob of cfg's shape.
-// Returns GNS_OK with the largest nnz(Y) and LDS image, GNS_EINVAL, or GNS_EUNSUPPORTED when a member's LDS image is too large.
-int pf_scan_set(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off, int32_t n_member,
-                int32_t* nnzy_max, int64_t* lds_max) {
-  if (!cfg || !set_host || !member_off || n_member <= 0 || set_words > (size_t)INT32_MAX) return GNS_EINVAL;
-  const int32_t* set = static_cast<const int32_t*>(set_host);
-  int32_t ny = 0;
-  int64_t lds = 0;
-  bool too_big = false;
-  for (int32_t m = 0; m < n_member; ++m) {
-    const int64_t off = member_off[m];
-    if (off < 0 || off % PF_SET_ALIGN_WORDS != 0 || off + PF_HDR_WORDS > (int64_t)set_words) return GNS_EINVAL;
-    const int32_t* h = set + off;
-    if (!pf_header_ok(cfg, h) || h[PH_TOTAL] < PF_HDR_WORDS || h[PH_TOTAL] > (int64_t)set_words - off || h[PH_NNZY] < 0)
-      return GNS_EINVAL;
-    ny = h[PH_NNZY] > ny ? h[PH_NNZY] : ny;
-    const int64_t b = pf_lds_bytes(h);
-    lds = b > lds ? b : lds;
-    too_big |= b > GNS_PF_LDS_MAX_BYTES;
-  }
-  if (too_big) return GNS_EUNSUPPORTED;
-  *nnzy_max = ny;
-  *lds_max = lds;
-  return GNS_OK;
 }
 
 }  // namespace
@@ -504,8 +451,8 @@ int pf_scan_set(const gns_pf_config* cfg, const void* set_host, size_t set_words
 extern "C" int gns_pf_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes) {
   if (!cfg || !topo_host || !bytes || Bt <= 0) return GNS_EINVAL;
   const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!pf_header_ok(cfg, h)) return GNS_EINVAL;
-  *bytes = pf_ws_bytes(h, Bt);
+  if (!pf_header_ok<PfBlobKind>(cfg, h)) return GNS_EINVAL;
+  *bytes = pf_ws_bytes_nnzy(h[PH_NNZY], Bt);
   return GNS_OK;
 }
 
@@ -514,27 +461,14 @@ extern "C" int gns_pf_solve(const gns_pf_config* cfg, const void* topo_host, con
                             const double* v0, const double* theta0,
                             double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  if (!cfg || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF) return GNS_EINVAL;
-  if (!v || !theta || !converged || !iterations || !mismatch || !workspace) return GNS_EINVAL;
-  if ((cfg->n_line > 0 && !lines) || cfg->max_iter < 0 || !(cfg->tol >= 0.0) || (v0 == nullptr) != (theta0 == nullptr))
+  if (!pf_config_ok(cfg) || !topo_host ||
+      !pf_solve_args_ok(topo_dev, buses, lines, generators, Bt, v0, theta0, v, theta, converged, iterations, mismatch, workspace))
     return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!pf_header_ok(cfg, h)) return GNS_EINVAL;
-  if (workspace_bytes < pf_ws_bytes(h, Bt)) return GNS_ESIZE;
-  gns_pf_info info;
-  if (gns_pf_topology_info(topo_host, &info) != GNS_OK) return GNS_EINVAL;
-  if (info.lds_bytes > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_pf_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
-      return GNS_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gns_pf_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)info.lds_bytes, (hipStream_t)stream,
-                     static_cast<const int32_t*>(topo_dev), buses, lines, generators, v0, theta0, v, theta, converged, iterations,
-                     mismatch, static_cast<double2*>(workspace), cfg->max_iter, cfg->tol);
-  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+  int64_t lds = 0;
+  const int rc = pf_check_topology<PfBlobKind>(cfg, static_cast<const int32_t*>(topo_host), Bt, workspace_bytes, &lds);
+  if (rc != GNS_OK) return rc;
+  return pf_launch<gns_pf_kernel>(Bt, lds, stream, static_cast<const int32_t*>(topo_dev), buses, lines, generators, v0, theta0, v,
+                                  theta, converged, iterations, mismatch, static_cast<double2*>(workspace), cfg->max_iter, cfg->tol);
 }
 
 extern "C" int gns_pf_workspace_bytes_set(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
@@ -542,7 +476,7 @@ extern "C" int gns_pf_workspace_bytes_set(const gns_pf_config* cfg, const void* 
   if (!bytes || Bt <= 0) return GNS_EINVAL;
   int32_t nnzy = 0;
   int64_t lds = 0;
-  const int rc = pf_scan_set(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
+  const int rc = pf_scan_set<PfBlobKind>(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
   if (rc != GNS_OK) return rc;
   *bytes = pf_ws_bytes_nnzy(nnzy, Bt);
   return GNS_OK;
@@ -554,55 +488,36 @@ extern "C" int gns_pf_solve_set(const gns_pf_config* cfg, const void* set_host, 
                                 const double* v0, const double* theta0,
                                 double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (!cfg || !set_dev || !grid_off || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF) return GNS_EINVAL;
-  if (!v || !theta || !converged || !iterations || !mismatch || !workspace) return GNS_EINVAL;
-  if (cfg->max_iter < 0 || !(cfg->tol >= 0.0) || (v0 == nullptr) != (theta0 == nullptr)) return GNS_EINVAL;
+  if (!pf_config_ok(cfg) || !grid_off ||
+      !pf_solve_args_ok(set_dev, buses, lines, generators, Bt, v0, theta0, v, theta, converged, iterations, mismatch, workspace))
+    return GNS_EINVAL;
   int32_t nnzy = 0;
   int64_t lds = 0;
-  const int rc = pf_scan_set(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
+  const int rc = pf_scan_set<PfBlobKind>(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
   if (rc != GNS_OK) return rc;
   if (workspace_bytes < pf_ws_bytes_nnzy(nnzy, Bt)) return GNS_ESIZE;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_pf_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
-      return GNS_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gns_pf_set_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)lds, (hipStream_t)stream,
-                     static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off, order, Bt, cfg->n_bus, cfg->n_line,
-                     cfg->n_gen, lds, nnzy, buses, lines, generators, v0, theta0, v, theta, converged, iterations, mismatch,
-                     static_cast<double2*>(workspace), cfg->max_iter, cfg->tol);
-  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+  return pf_launch<gns_pf_set_kernel>(Bt, lds, stream, static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off, order, Bt,
+                                      cfg->n_bus, cfg->n_line, cfg->n_gen, lds, nnzy, buses, lines, generators, v0, theta0, v, theta,
+                                      converged, iterations, mismatch, static_cast<double2*>(workspace), cfg->max_iter, cfg->tol);
 }
 
+// The adjoint calls check max_iter and tol as the solves do although they use neither: a configuration a solve refuses is
+// refused here too.  With no gradient output asked for they return GNS_OK without a launch, after every other check.
 extern "C" int gns_pf_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
                               const float* buses, const float* lines, const float* generators, int64_t Bt,
                               const double* v, const double* theta, const uint8_t* converged,
                               const double* grad_v, const double* grad_theta,
                               float* grad_buses, float* grad_lines, float* grad_generators,
                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (!cfg || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF) return GNS_EINVAL;
-  if (!v || !theta || !converged || !workspace) return GNS_EINVAL;
-  if (cfg->max_iter < 0 || !(cfg->tol >= 0.0)) return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!pf_header_ok(cfg, h)) return GNS_EINVAL;
-  if (workspace_bytes < pf_ws_bytes(h, Bt)) return GNS_ESIZE;
-  gns_pf_info info;
-  if (gns_pf_topology_info(topo_host, &info) != GNS_OK) return GNS_EINVAL;
-  if (info.lds_bytes > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
+  if (!pf_config_ok(cfg) || !topo_host || !pf_adjoint_args_ok(topo_dev, buses, lines, generators, Bt, v, theta, converged, workspace))
+    return GNS_EINVAL;
+  int64_t lds = 0;
+  const int rc = pf_check_topology<PfBlobKind>(cfg, static_cast<const int32_t*>(topo_host), Bt, workspace_bytes, &lds);
+  if (rc != GNS_OK) return rc;
   if (!grad_buses && !grad_lines && !grad_generators) return GNS_OK;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_pf_adjoint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
-      return GNS_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gns_pf_adjoint_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)info.lds_bytes, (hipStream_t)stream,
-                     static_cast<const int32_t*>(topo_dev), buses, lines, generators, v, theta, converged, grad_v, grad_theta,
-                     grad_buses, grad_lines, grad_generators, static_cast<double2*>(workspace));
-  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+  return pf_launch<gns_pf_adjoint_kernel>(Bt, lds, stream, static_cast<const int32_t*>(topo_dev), buses, lines, generators, v, theta,
+                                          converged, grad_v, grad_theta, grad_buses, grad_lines, grad_generators,
+                                          static_cast<double2*>(workspace));
 }
 
 extern "C" int gns_pf_adjoint_set(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
@@ -612,25 +527,16 @@ extern "C" int gns_pf_adjoint_set(const gns_pf_config* cfg, const void* set_host
                                   const double* grad_v, const double* grad_theta,
                                   float* grad_buses, float* grad_lines, float* grad_generators,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-  if (!cfg || !set_dev || !grid_off || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF) return GNS_EINVAL;
-  if (!v || !theta || !converged || !workspace) return GNS_EINVAL;
-  if (cfg->max_iter < 0 || !(cfg->tol >= 0.0)) return GNS_EINVAL;
+  if (!pf_config_ok(cfg) || !grid_off || !pf_adjoint_args_ok(set_dev, buses, lines, generators, Bt, v, theta, converged, workspace))
+    return GNS_EINVAL;
   int32_t nnzy = 0;
   int64_t lds = 0;
-  const int rc = pf_scan_set(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
+  const int rc = pf_scan_set<PfBlobKind>(cfg, set_host, set_words, member_off, n_member, &nnzy, &lds);
   if (rc != GNS_OK) return rc;
   if (workspace_bytes < pf_ws_bytes_nnzy(nnzy, Bt)) return GNS_ESIZE;
   if (!grad_buses && !grad_lines && !grad_generators) return GNS_OK;
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_pf_adjoint_set_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            GNS_PF_LDS_MAX_BYTES) != hipSuccess)
-      return GNS_ELAUNCH;
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(gns_pf_adjoint_set_kernel, dim3((unsigned)Bt), dim3(PF_THREADS), (size_t)lds, (hipStream_t)stream,
-                     static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off, order, Bt, cfg->n_bus, cfg->n_line,
-                     cfg->n_gen, lds, nnzy, buses, lines, generators, v, theta, converged, grad_v, grad_theta, grad_buses, grad_lines,
-                     grad_generators, static_cast<double2*>(workspace));
-  return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+  return pf_launch<gns_pf_adjoint_set_kernel>(Bt, lds, stream, static_cast<const int32_t*>(set_dev), (int64_t)set_words, grid_off,
+                                              order, Bt, cfg->n_bus, cfg->n_line, cfg->n_gen, lds, nnzy, buses, lines, generators, v,
+                                              theta, converged, grad_v, grad_theta, grad_buses, grad_lines, grad_generators,
+                                              static_cast<double2*>(workspace));
 }

@@ -19,6 +19,7 @@ analysis (``gns_fd_prepare_topology``); its gradients are the Newton-Raphson adj
 from __future__ import annotations
 
 import ctypes
+import functools
 from collections import namedtuple
 
 import numpy as np
@@ -26,7 +27,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import gns as _gns
-from ._lib import GNS_ERRORS, PF_LDS_MAX_BYTES, PF_MAX_SLOTS, FdConfig, FdInfo, PfConfig, PfInfo, load_library
+from ._lib import (GNS_ERRORS, GNS_ETOPOLOGY, GNS_EUNSUPPORTED, PF_LDS_MAX_BYTES, PF_MAX_SLOTS, FdConfig, FdInfo, PfConfig, PfInfo,
+                   load_library)
 
 PowerFlowResult = namedtuple('PowerFlowResult', ['v', 'theta', 'converged', 'iterations', 'mismatch'])
 
@@ -46,12 +48,14 @@ class IslandedTopology(ValueError):
 class PowerFlowTopology:
     """Host analysis of one topology (the blob on the host and, copied on first use, on the device) and what it found (``info``)."""
 
+    INFO, INFO_FN = PfInfo, 'gns_pf_topology_info'     # the blob's info struct and the entry point that fills it
+
     def __init__(self, host, dev):
         self.host = host
         self._dev, self._blob = dev, None
-        info = PfInfo()
-        _check(load_library().gns_pf_topology_info(host.ctypes.data, ctypes.byref(info)), 'gns_pf_topology_info')
-        self.info = {k: getattr(info, k) for k, _ in PfInfo._fields_}
+        info = self.INFO()
+        _check(getattr(load_library(), self.INFO_FN)(host.ctypes.data, ctypes.byref(info)), self.INFO_FN)
+        self.info = {k: getattr(info, k) for k, _ in self.INFO._fields_}
 
     @property
     def blob(self):
@@ -64,12 +68,7 @@ class FdTopology(PowerFlowTopology):
     """Host analysis of one topology for the fast-decoupled solver (B' and B'', ``gns_fd_prepare_topology``): ``info`` holds both
     dimensions, both nnz(L+U), the four programs' operation and step counts and the LDS image."""
 
-    def __init__(self, host, dev):
-        self.host = host
-        self._dev, self._blob = dev, None
-        info = FdInfo()
-        _check(load_library().gns_fd_topology_info(host.ctypes.data, ctypes.byref(info)), 'gns_fd_topology_info')
-        self.info = {k: getattr(info, k) for k, _ in FdInfo._fields_}
+    INFO, INFO_FN = FdInfo, 'gns_fd_topology_info'
 
 
 class _PfTopologySet:
@@ -103,11 +102,19 @@ class _PfTopologySet:
             self.host, self.blob = host, torch.from_numpy(host).to(self.dev)
 
 
-GNS_EUNSUPPORTED = 2
-
-
 _LDS_FORMULA = '8 * (nnz(L+U) + dim + 8 N) bytes per grid'
 _FD_LDS_FORMULA = "8 * (nnz_lu_p + dim_p + nnz_lu_pp + dim_pp + 6 N) bytes per grid: both factors of B' and B''"
+
+
+# A solver as the launch code sees it: the prefix of its entry points, the class of its topologies, the LDS formula a refusal names
+_Solver = namedtuple('_Solver', ['prefix', 'topology', 'formula'])
+_NR = _Solver('gns_pf', PowerFlowTopology, _LDS_FORMULA)
+_FD = _Solver('gns_fd', FdTopology, _FD_LDS_FORMULA)
+
+
+def _analysis(solver):
+    """``(topology cache, set cache, analysis function)`` of a solver, as the module holds them when the call is made."""
+    return (_FD_TOPO_CACHE, _FD_SET_CACHE, analyse_fd_topology) if solver is _FD else (_TOPO_CACHE, _SET_CACHE, analyse_topology)
 
 
 def _check(rc, what, lds_bytes=None, formula=_LDS_FORMULA):
@@ -122,10 +129,10 @@ def _check(rc, what, lds_bytes=None, formula=_LDS_FORMULA):
         raise _gns.GNSError(f'{what} failed: {GNS_ERRORS.get(rc, rc)}')
 
 
-def _set_lds_bytes(set_host, member_off, fd=False):
-    """The largest LDS image among the members of a set (host words; ``fd``: a set of FD blobs)."""
+def _set_lds_bytes(set_host, member_off, cls=PowerFlowTopology):
+    """The largest LDS image among the members of a set (host words) of ``cls`` blobs."""
     lib, lds = load_library(), 0
-    info, fn = (FdInfo(), 'gns_fd_topology_info') if fd else (PfInfo(), 'gns_pf_topology_info')
+    info, fn = cls.INFO(), cls.INFO_FN
     for off in member_off.tolist():
         _check(getattr(lib, fn)(set_host.ctypes.data + 4 * off, ctypes.byref(info)), fn)
         lds = max(lds, info.lds_bytes)
@@ -183,7 +190,7 @@ def _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, prefix, cls):
     nbytes = ctypes.c_size_t()
     args = (int(n_bus), int(f32.size), int(g32.size), f32.ctypes.data, t32.ctypes.data, g_arg.ctypes.data, slack)
     rc = getattr(lib, prefix + '_topology_bytes')(*args, ctypes.byref(nbytes))
-    if rc == 3:
+    if rc == GNS_ETOPOLOGY:
         isl = _islanded(int(n_bus), f32, t32, slack) + 1
         raise IslandedTopology(f'buses {isl.tolist()} have no path of lines to slack_bus {slack + 1}: their angles are undetermined '
                          '(the power-flow Jacobian is structurally singular)')
@@ -222,10 +229,12 @@ def _topology(buses, lines, gens, slack_bus):
     """The cached analysis of the batch's one topology.  One fused device compare of every grid's id columns against grid 0's,
     shipped to the host with grid 0's ids and type column: one synchronisation."""
     key, args = _topology_key(buses, lines, gens, slack_bus, 'newton_raphson')
-    return _cached(_TOPO_CACHE, key, analyse_topology, args, buses.device)
+    return _analysed(_NR, key, args, buses.device)
 
 
-def _cached(cache, key, analyse, args, device):
+def _analysed(solver, key, args, device):
+    """``solver``'s cached analysis of the topology ``_topology_key`` gave ``key`` and ``args`` for."""
+    cache, _, analyse = _analysis(solver)
     topo = cache.get(key)
     if topo is None:
         topo = cache[key] = analyse(*args, device=device)
@@ -269,7 +278,12 @@ def _plan_mixed(buses, lines, gens, slack_bus):
       member_off int32 numpy: the offsets of the blobs this call uses (distinct, ascending by topology index)
       topo_set   the ``_PfTopologySet``; slack_bus: the 1-based slack; islanded: bool numpy per distinct topology.
     Raises as ``analyse_topology`` does for ids out of range, non-integer ids or a bad slack; islands are not an error here."""
-    return _plan_from(_classify(buses, lines, gens, slack_bus), buses, lines, gens, _TOPO_CACHE, _SET_CACHE, analyse_topology)
+    return _planned(_NR, _classify(buses, lines, gens, slack_bus), buses, lines, gens)
+
+
+def _planned(solver, classified, buses, lines, gens):
+    """The ``MixedPlan`` of a classified batch on ``solver``'s blobs (its caches and analysis)."""
+    return _plan_from(classified, buses, lines, gens, *_analysis(solver))
 
 
 def _classify(buses, lines, gens, slack_bus):
@@ -345,28 +359,8 @@ def newton_raphson(buses, lines, generators, B=None, L=None, G=None, *, slack_bu
     start is not differentiated.  Contract: ``include/gns_powerflow.h``, "Gradients"."""
     single, in_dev, buses, lines, generators, v0, theta0 = _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter,
                                                                    mixed_topologies)
-    lib = load_library()
     cfg = PfConfig(buses.shape[1], lines.shape[1], generators.shape[1], int(max_iter), float(tol))
-    plain = (buses.detach(), lines.detach(), generators.detach())   # what the analysis reads (host copies of id columns)
-    if mixed_topologies:
-        plan = _plan_mixed(*plain, slack_bus)
-        ts = plan.topo_set
-        set_bufs = (ts.host, ts.blob)                 # the set as this call sees it (a later call may grow it: offsets stay)
-
-        def solve(bu, li, ge):
-            return _solve_mixed(lib, cfg, plan, bu, li, ge, v0, theta0)
-
-        def adjoint(*args):
-            return _adjoint_mixed(lib, cfg, plan, set_bufs, *args)
-    else:
-        topo = _topology(*plain, slack_bus)
-
-        def solve(bu, li, ge):
-            return _solve_plain(lib, cfg, topo, bu, li, ge, v0, theta0)
-
-        def adjoint(*args):
-            return _adjoint_plain(lib, cfg, topo, *args)
-    return _run(solve, adjoint, buses, lines, generators, plain, in_dev, single)
+    return _run(_NR, 'newton_raphson', cfg, buses, lines, generators, slack_bus, v0, theta0, mixed_topologies, in_dev, single)
 
 
 def _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter, mixed_topologies):
@@ -403,10 +397,35 @@ def _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter, mixed_
     return single, in_dev, buses, lines, generators, v0, theta0
 
 
-def _run(solve, adjoint, buses, lines, generators, plain, in_dev, single):
-    """``solve`` (through ``_NRFunction`` with ``adjoint`` as its backward when an input requires grad), back on the input device."""
-    if torch.is_grad_enabled() and any(t.requires_grad for t in (buses, lines, generators)):
-        out = list(_NRFunction.apply(solve, adjoint, buses, lines, generators))
+def _run(solver, name, cfg, buses, lines, generators, slack_bus, v0, theta0, mixed_topologies, in_dev, single):
+    """What ``newton_raphson`` and ``fast_decoupled`` (``name``) do with their checked inputs: the analysis of the batch's one
+    topology, or with ``mixed_topologies`` its classification (one per call) and the ``MixedPlan`` on ``solver``'s blobs; the solve
+    on it, through ``_NRFunction`` when an input requires grad; the result back on the input device.  The backward is the
+    Newton-Raphson adjoint for either solver, so fast-decoupled then also gets the Newton-Raphson analysis of the same topologies."""
+    lib = load_library()
+    pf_cfg = cfg if solver is _NR else cfg.pf
+    plain = (buses.detach(), lines.detach(), generators.detach())   # what the analysis reads (host copies of id columns)
+    grad = torch.is_grad_enabled() and any(t.requires_grad for t in (buses, lines, generators))
+    if mixed_topologies:
+        classified = _classify(*plain, slack_bus)
+
+        def target_of(s):
+            plan = _planned(s, classified, *plain)
+            ts = plan.topo_set                        # the set as this call sees it (a later call may grow it: offsets stay)
+            return _set_members(plan, (ts.host, ts.blob), s.topology)
+    else:
+        key, args = _topology_key(*plain, slack_bus, name)
+
+        def target_of(s):
+            return _one_topology(_analysed(s, key, args, buses.device))
+    target = target_of(solver)
+
+    def solve(bu, li, ge):
+        return _solve(lib, solver, cfg, target, bu, li, ge, v0, theta0)
+
+    if grad:
+        nr_target = target if solver is _NR else target_of(_NR)
+        out = list(_NRFunction.apply(solve, lambda *args: _adjoint(lib, pf_cfg, nr_target, *args), buses, lines, generators))
     else:
         out = solve(*plain)
     if in_dev != buses.device:
@@ -443,71 +462,8 @@ def fast_decoupled(buses, lines, generators, B=None, L=None, G=None, *, variant,
         raise ValueError(f"variant must be 'XB' or 'BX', got {variant!r}")
     single, in_dev, buses, lines, generators, v0, theta0 = _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter,
                                                                    mixed_topologies)
-    lib = load_library()
-    N, E, Gn = buses.shape[1], lines.shape[1], generators.shape[1]
-    cfg = FdConfig(PfConfig(N, E, Gn, int(max_iter), float(tol)), FD_VARIANTS[variant])
-    plain = (buses.detach(), lines.detach(), generators.detach())
-    grad = torch.is_grad_enabled() and any(t.requires_grad for t in (buses, lines, generators))
-    if mixed_topologies:
-        classified = _classify(*plain, slack_bus)
-        plan = _plan_from(classified, *plain, _FD_TOPO_CACHE, _FD_SET_CACHE, analyse_fd_topology)
-        if grad:                                      # the adjoint's NR set, from the same classification
-            nr_plan = _plan_from(classified, *plain, _TOPO_CACHE, _SET_CACHE, analyse_topology)
-            nr_bufs = (nr_plan.topo_set.host, nr_plan.topo_set.blob)
-
-        def solve(bu, li, ge):
-            return _solve_fd_mixed(lib, cfg, plan, bu, li, ge, v0, theta0)
-
-        def adjoint(*args):
-            return _adjoint_mixed(lib, cfg.pf, nr_plan, nr_bufs, *args)
-    else:
-        key, args = _topology_key(*plain, slack_bus, 'fast_decoupled')
-        topo = _cached(_FD_TOPO_CACHE, key, analyse_fd_topology, args, buses.device)
-        if grad:
-            nr_topo = _cached(_TOPO_CACHE, key, analyse_topology, args, buses.device)
-
-        def solve(bu, li, ge):
-            return _solve_fd_plain(lib, cfg, topo, bu, li, ge, v0, theta0)
-
-        def adjoint(*args):
-            return _adjoint_plain(lib, cfg.pf, nr_topo, *args)
-    return _run(solve, adjoint, buses, lines, generators, plain, in_dev, single)
-
-
-def _solve_fd_plain(lib, cfg, topo, buses, lines, generators, v0, theta0):
-    """One ``gns_fd_solve`` launch on the batch's one topology."""
-    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
-    nbytes = ctypes.c_size_t()
-    _check(lib.gns_fd_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_fd_workspace_bytes')
-    ws = _gns._workspace(nbytes.value, dev)
-    v, theta, conv, iters, mis = _outputs(Bt, N, dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib.gns_fd_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                            generators.data_ptr(), Bt, _ptr(v0), _ptr(theta0), v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
-                            iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_fd_solve',
-           topo.info['lds_bytes'], _FD_LDS_FORMULA)
-    return [v, theta, conv.bool(), iters, mis]
-
-
-def _solve_fd_mixed(lib, cfg, plan, buses, lines, generators, v0, theta0):
-    """One ``gns_fd_solve_set`` launch over ``plan`` (a ``MixedPlan`` of FD blobs)."""
-    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
-    if plan.member_off.size == 0:                # every grid's topology islands a bus: nothing to solve
-        return _not_solved(Bt, N, dev)
-    ts, members = plan.topo_set, plan.member_off
-    lds = lambda: _set_lds_bytes(ts.host, members, fd=True)   # noqa: E731
-    nbytes = ctypes.c_size_t()
-    _check(lib.gns_fd_workspace_bytes_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.words, members.ctypes.data, members.size, Bt,
-                                          ctypes.byref(nbytes)), 'gns_fd_workspace_bytes_set', lds, _FD_LDS_FORMULA)
-    ws = _gns._workspace(nbytes.value, dev)
-    v, theta, conv, iters, mis = _outputs(Bt, N, dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib.gns_fd_solve_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.blob.data_ptr(), ts.words, members.ctypes.data,
-                                members.size, plan.grid_off.data_ptr(), plan.order.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                                generators.data_ptr(), Bt, _ptr(v0), _ptr(theta0), v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
-                                iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_fd_solve_set', lds,
-           _FD_LDS_FORMULA)
-    return [v, theta, conv.bool(), iters, mis]
+    cfg = FdConfig(PfConfig(buses.shape[1], lines.shape[1], generators.shape[1], int(max_iter), float(tol)), FD_VARIANTS[variant])
+    return _run(_FD, 'fast_decoupled', cfg, buses, lines, generators, slack_bus, v0, theta0, mixed_topologies, in_dev, single)
 
 
 def _not_solved(Bt, N, dev):
@@ -516,22 +472,6 @@ def _not_solved(Bt, N, dev):
     return [torch.full((Bt, N), nan, dtype=torch.float64, device=dev), torch.full((Bt, N), nan, dtype=torch.float64, device=dev),
             torch.zeros(Bt, dtype=torch.bool, device=dev), torch.full((Bt,), -1, dtype=torch.int32, device=dev),
             torch.full((Bt,), nan, dtype=torch.float64, device=dev)]
-
-
-def _solve_plain(lib, cfg, topo, buses, lines, generators, v0, theta0):
-    """One ``gns_pf_solve`` launch on the batch's one topology; returns the five outputs as ``newton_raphson`` does."""
-    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
-    nbytes = ctypes.c_size_t()
-    _check(lib.gns_pf_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_pf_workspace_bytes')
-    ws = _gns._workspace(nbytes.value, dev)
-    v, theta, conv, iters, mis = _outputs(Bt, N, dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib.gns_pf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                            generators.data_ptr(), Bt, v0.data_ptr() if v0 is not None else None,
-                            theta0.data_ptr() if theta0 is not None else None, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
-                            iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_pf_solve',
-           topo.info['lds_bytes'])
-    return [v, theta, conv.bool(), iters, mis]
 
 
 class _NRFunction(torch.autograd.Function):
@@ -568,28 +508,69 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _adjoint_plain(lib, cfg, topo, buses, lines, gens, v, theta, conv, gv, gth, need):
-    """One ``gns_pf_adjoint`` launch on the forward's topology, on the forward's device and stream."""
-    Bt, dev = buses.shape[0], buses.device
-    gin, gv, gth = _adjoint_args(buses, lines, gens, gv, gth, need)
+# Where a call launches: the suffix of its entry points, the arguments that name the blob(s) to the workspace query and to the
+# launch itself (between cfg and the input tensors), the LDS image a refusal names (``_check``), and ``keep``.  The arguments are
+# raw addresses, used as late as the backward: ``keep`` is never read, it holds their owners so that they outlive the target.
+_Target = namedtuple('_Target', ['suffix', 'ws_args', 'args', 'lds', 'keep'])
+
+
+def _one_topology(topo):
+    """The target of a plain call: ``gns_*_solve`` / ``gns_pf_adjoint`` on the batch's one topology."""
+    host = topo.host.ctypes.data
+    return _Target('', (host,), (host, topo.blob.data_ptr()), topo.info['lds_bytes'], topo)
+
+
+def _set_members(plan, set_bufs, cls=PowerFlowTopology):
+    """The target of a mixed call: ``gns_*_solve_set`` / ``gns_pf_adjoint_set`` over ``plan`` (a ``MixedPlan`` of ``cls`` blobs) in
+    the set as ``set_bufs = (host, blob)`` holds it.  None when every grid's topology islands a bus: there is nothing to launch."""
+    host, blob = set_bufs
+    members = plan.member_off
+    if members.size == 0:
+        return None
+    ws_args = (host.ctypes.data, host.size, members.ctypes.data, members.size)
+    return _Target('_set', ws_args, (ws_args[0], blob.data_ptr(), *ws_args[1:], plan.grid_off.data_ptr(), plan.order.data_ptr()),
+                   lambda: _set_lds_bytes(host, members, cls), (plan, set_bufs))
+
+
+def _launch(lib, solver, op, cfg, target, inputs, rest):
+    """One launch of ``solver``'s entry point ``op`` on ``target``: the workspace its query asks for, then ``(cfg, the target's
+    blobs, inputs, Bt, rest, workspace, stream)`` with the tensors by pointer (None: NULL), on the inputs' device and its current
+    stream.  The library launches on the current device, so that is the inputs' for the length of the call."""
+    Bt, dev = inputs[0].shape[0], inputs[0].device
+    ws_name, ws_fn, name, fn = _entry_points(lib, solver.prefix, op, target.suffix)
     nbytes = ctypes.c_size_t()
-    _check(lib.gns_pf_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(nbytes)), 'gns_pf_workspace_bytes')
+    _check(ws_fn(ctypes.byref(cfg), *target.ws_args, Bt, ctypes.byref(nbytes)), ws_name, target.lds, solver.formula)
     ws = _gns._workspace(nbytes.value, dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib.gns_pf_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                                  gens.data_ptr(), Bt, v.data_ptr(), theta.data_ptr(), conv.data_ptr(), _ptr(gv), _ptr(gth),
-                                  _ptr(gin[0]), _ptr(gin[1]), _ptr(gin[2]), ws.data_ptr(), ws.numel(), stream), 'gns_pf_adjoint',
-               topo.info['lds_bytes'])
-    return gin
+        _check(fn(ctypes.byref(cfg), *target.args, *map(_ptr, inputs), Bt, *map(_ptr, rest), ws.data_ptr(), ws.numel(), stream),
+               name, target.lds, solver.formula)
 
 
-def _adjoint_mixed(lib, cfg, plan, set_bufs, buses, lines, gens, v, theta, conv, gv, gth, need):
-    """One ``gns_pf_adjoint_set`` launch over the forward's ``MixedPlan`` (no second classification)."""
+@functools.lru_cache(maxsize=None)
+def _entry_points(lib, prefix, op, suffix):
+    """Names and functions of the workspace query and of entry point ``op`` (resolved once, not per launch)."""
+    ws_name, name = f'{prefix}_workspace_bytes{suffix}', f'{prefix}_{op}{suffix}'
+    return ws_name, getattr(lib, ws_name), name, getattr(lib, name)
+
+
+def _solve(lib, solver, cfg, target, buses, lines, generators, v0, theta0):
+    """One solve launch (``gns_{pf,fd}_solve[_set]``) on ``target``; returns the five outputs as ``newton_raphson`` does."""
+    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
+    if target is None:
+        return _not_solved(Bt, N, dev)
+    out = _outputs(Bt, N, dev)
+    _launch(lib, solver, 'solve', cfg, target, (buses, lines, generators), (v0, theta0, *out))
+    v, theta, conv, iters, mis = out
+    return [v, theta, conv.bool(), iters, mis]
+
+
+def _adjoint(lib, cfg, target, buses, lines, gens, v, theta, conv, gv, gth, need):
+    """One adjoint launch (``gns_pf_adjoint[_set]``) on the forward's ``target`` (no second analysis or classification), on the
+    forward's device and stream; returns the gradients of the inputs ``need`` asks for."""
     Bt, dev = buses.shape[0], buses.device
     gin, gv, gth = _adjoint_args(buses, lines, gens, gv, gth, need)
-    members = plan.member_off
-    if members.size == 0:                         # every grid's topology islands a bus: NaN rows, zero rows for a zero gradient
+    if target is None:                            # no grid is solved: NaN rows, zero rows for a zero gradient
         zero = torch.ones(Bt, dtype=torch.bool, device=dev)
         for g in (gv, gth):
             if g is not None:
@@ -599,43 +580,16 @@ def _adjoint_mixed(lib, cfg, plan, set_bufs, buses, lines, gens, v, theta, conv,
             if t is not None:
                 t.copy_(fill.view(Bt, 1, 1).expand_as(t))
         return gin
-    host, blob = set_bufs
-    nbytes = ctypes.c_size_t()
-    _check(lib.gns_pf_workspace_bytes_set(ctypes.byref(cfg), host.ctypes.data, host.size, members.ctypes.data, members.size, Bt,
-                                          ctypes.byref(nbytes)), 'gns_pf_workspace_bytes_set', lambda: _set_lds_bytes(host, members))
-    ws = _gns._workspace(nbytes.value, dev)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib.gns_pf_adjoint_set(ctypes.byref(cfg), host.ctypes.data, blob.data_ptr(), host.size, members.ctypes.data,
-                                      members.size, plan.grid_off.data_ptr(), plan.order.data_ptr(), buses.data_ptr(),
-                                      lines.data_ptr(), gens.data_ptr(), Bt, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
-                                      _ptr(gv), _ptr(gth), _ptr(gin[0]), _ptr(gin[1]), _ptr(gin[2]), ws.data_ptr(), ws.numel(),
-                                      stream), 'gns_pf_adjoint_set', lambda: _set_lds_bytes(host, members))
+    _launch(lib, _NR, 'adjoint', cfg, target, (buses, lines, gens), (v, theta, conv, gv, gth, *gin))
     return gin
+
+
+def _adjoint_mixed(lib, cfg, plan, set_bufs, *args):
+    """``_adjoint`` over a ``MixedPlan`` of Newton-Raphson blobs."""
+    return _adjoint(lib, cfg, _set_members(plan, set_bufs), *args)
 
 
 def _outputs(Bt, N, dev):
     v = torch.empty(Bt, N, dtype=torch.float64, device=dev)
     return (v, torch.empty_like(v), torch.empty(Bt, dtype=torch.uint8, device=dev), torch.empty(Bt, dtype=torch.int32, device=dev),
             torch.empty(Bt, dtype=torch.float64, device=dev))
-
-
-def _solve_mixed(lib, cfg, plan, buses, lines, generators, v0, theta0):
-    """One ``gns_pf_solve_set`` launch over ``plan`` (``_plan_mixed``); returns the five outputs as ``newton_raphson`` does."""
-    Bt, N, dev = buses.shape[0], buses.shape[1], buses.device
-    if plan.member_off.size == 0:                # every grid's topology islands a bus: nothing to solve
-        return _not_solved(Bt, N, dev)
-    ts, members = plan.topo_set, plan.member_off
-    nbytes = ctypes.c_size_t()
-    _check(lib.gns_pf_workspace_bytes_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.words, members.ctypes.data, members.size, Bt,
-                                          ctypes.byref(nbytes)), 'gns_pf_workspace_bytes_set', lambda: _set_lds_bytes(ts.host, members))
-    ws = _gns._workspace(nbytes.value, dev)
-    v, theta, conv, iters, mis = _outputs(Bt, N, dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _check(lib.gns_pf_solve_set(ctypes.byref(cfg), ts.host.ctypes.data, ts.blob.data_ptr(), ts.words, members.ctypes.data,
-                                members.size, plan.grid_off.data_ptr(), plan.order.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                                generators.data_ptr(), Bt, v0.data_ptr() if v0 is not None else None,
-                                theta0.data_ptr() if theta0 is not None else None, v.data_ptr(), theta.data_ptr(), conv.data_ptr(),
-                                iters.data_ptr(), mis.data_ptr(), ws.data_ptr(), ws.numel(), stream), 'gns_pf_solve_set',
-           lambda: _set_lds_bytes(ts.host, members))
-    return [v, theta, conv.bool(), iters, mis]

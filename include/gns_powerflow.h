@@ -263,6 +263,89 @@ int gns_fd_solve_set(const gns_fd_config* cfg, const void* set_host, const void*
                      double* v, double* theta, uint8_t* converged, int32_t* iterations, double* mismatch,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* DC power flow (PYPOWER makeBdc + dcpf and the DC branch of runpf), the linear baseline a trained GNS is compared with
+ * (GNS/evaluate.py:13, 42-58), with the per-line active flows and the slack's balancing power, and its adjoint.
+ *
+ * Semantics
+ *   Inputs and the slack: those of the Newton-Raphson section above; PV and PQ buses are treated alike; every line is in service.
+ *   Per line (f, t, r, x, b, tau, shift): b_l = 1 / (x tau) (tau as given), Pfinj_l = -b_l shift.  r, the line charging b and the
+ *   bus Bs are not used.
+ *   Bbus (makeBdc): ff += b_l, tt += b_l, ft -= b_l, tf -= b_l; parallel lines add.
+ *   P_i = sum of Pg (generator column 6) on bus i - Pd_i - Gs_i - Pbusinj_i, with Pbusinj_f += Pfinj_l, Pbusinj_t -= Pfinj_l.
+ *   theta_slack = 0; theta at the other buses r solves Bbus[r, r] theta_r = P_r.
+ *   line_flow_l = b_l (theta_f - theta_t) + Pfinj_l: the active flow at the from end (the to end carries its negative).
+ *   slack_p = Bbus[slack, :] theta - P_slack: what the slack generates beyond its listed Pg (runpf adds it to the slack generator).
+ *   |V| = 1 at every bus: not an output.
+ *   Arithmetic: fp64 throughout.  Bbus[r, r] is factored once per grid (no pivoting, the B' ordering of the analysis).
+ *   Failure is per grid: a zero or non-finite pivot or a non-finite theta gives converged = 0 and NaN in theta, line_flow and
+ *   slack_p of that grid; the other grids are unaffected.  No atomics: a grid's results are bit-identical alone, in any batch, in
+ *   any order and from run to run.
+ *
+ * Outputs: theta [Bt,N], line_flow [Bt,E], slack_p [Bt] fp64; converged [Bt] uint8 (0/1: solved).
+ *
+ * Analysis: Bbus[r, r] has the sparsity of the fast-decoupled B', so the calls take an FD blob (gns_fd_prepare_topology) and use its B'
+ * ordering, factor slots and two B' programs; there is no DC analysis.  Configuration: a gns_pf_config for n_bus, n_line and n_gen;
+ * max_iter and tol are not read.
+ *
+ * Kernel: one wave per grid (gns_dcpf.hip): Bbus from the line rows into the B' factor slots, the B' factorisation program once, the
+ * B' solve program once, then the flows and the slack's row.  LDS image (gns_dc_lds_bytes): 8 * (nnz_lu_p + dim_p + N) bytes, the B'
+ * factor with its right-hand side and one bus vector; smaller than the fast-decoupled image, so every topology gns_fd_solve accepts
+ * is accepted.  No workspace: the queries report 0 bytes, and workspace may be NULL.
+ *
+ * Errors: GNS_EINVAL for a NULL cfg, blob, input or output, a blob that is not an FD blob or whose N, E, Gn are not cfg's;
+ * GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Nothing is allocated and the host is not synchronised. */
+int gns_dc_lds_bytes(const void* topo_host, int64_t* bytes);
+int gns_dc_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
+int gns_dc_solve(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                 const float* buses, const float* lines, const float* generators, int64_t Bt,
+                 double* theta, double* line_flow, double* slack_p, uint8_t* converged,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* Mixed topologies: the set, members, grid_off and order of gns_fd_solve_set (a set of FD blobs), with its host and device-side
+ * checks against DC's LDS image.  A grid without a usable blob (grid_off -1: a topology that islands a bus) gets converged = 0 and
+ * NaN in theta, line_flow and slack_p.  Results are bit-identical to gns_dc_solve on each grid's blob. */
+int gns_dc_workspace_bytes_set(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
+                               int32_t n_member, int64_t Bt, size_t* bytes);
+int gns_dc_solve_set(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                     const int32_t* member_off, int32_t n_member, const int32_t* grid_off, const int32_t* order,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     double* theta, double* line_flow, double* slack_p, uint8_t* converged,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Gradients.  gns_dc_adjoint takes the inputs of a gns_dc_solve call, its outputs theta and converged, and the incoming gradients
+ * grad_theta [Bt,N], grad_line_flow [Bt,E], grad_slack_p [Bt] fp64 of a loss l(theta, line_flow, slack_p) (each may be NULL: zero).
+ * It writes dl/d(input) into grad_buses [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32, each of which may be NULL (not
+ * computed; with all three NULL nothing is launched).  Every element of each non-NULL output is written (overwritten, not accumulated).
+ *
+ * Method: the map is linear in P with a symmetric matrix, so with g_r = grad_theta_r + sum_l grad_line_flow_l b_l (e_f - e_t)_r the
+ * adjoint is Bbus[r, r] lambda_r = g_r on the same factor with the same B' solve program, lambda_slack = 0.  One wave per grid, the
+ * solve's LDS image.  fp64 throughout, rounded once to fp32; no atomics: bit-identical alone, in any batch, in any order.
+ *
+ * Contract (the exact derivative of the map above; w_l = grad_line_flow_l - (lambda_f - lambda_t)):
+ *   buses      col 2 Pd and col 4 Gs: -(lambda_i - grad_slack_p), at the slack too (slack_p = -sum_i P_i: Bbus has zero column sums).
+ *              Every other column: 0.
+ *   lines      dl/db_l = w_l (theta_f - theta_t - shift_l);  col 3 x: -dl/db_l b_l / x;  col 5 tau: -dl/db_l b_l / tau;
+ *              col 6 shift: -b_l w_l.  Cols 0, 1, 2, 4 (ids, r, b): 0.  The line's buses are read from its id columns, which must be
+ *              those the blob was prepared from (a line whose ids are not buses of the grid gets a NaN row, and a NaN line_flow).
+ *   generators col 6 Pg: lambda_bus - grad_slack_p.  Every other column: 0.
+ *   A grid whose incoming gradients are all exactly zero gets zero rows, whatever its state.  Otherwise a grid with converged == 0,
+ *   or whose factor has a zero or non-finite pivot, gets NaN in all three rows.
+ * Errors as gns_dc_solve (theta and converged must not be NULL).  gns_dc_adjoint_set is the adjoint of a gns_dc_solve_set call: a
+ * grid without a usable blob gets NaN rows, or zero rows when its incoming gradients are zero. */
+int gns_dc_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                   const float* buses, const float* lines, const float* generators, int64_t Bt,
+                   const double* theta, const uint8_t* converged,
+                   const double* grad_theta, const double* grad_line_flow, const double* grad_slack_p,
+                   float* grad_buses, float* grad_lines, float* grad_generators,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int gns_dc_adjoint_set(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                       const int32_t* member_off, int32_t n_member, const int32_t* grid_off, const int32_t* order,
+                       const float* buses, const float* lines, const float* generators, int64_t Bt,
+                       const double* theta, const uint8_t* converged,
+                       const double* grad_theta, const double* grad_line_flow, const double* grad_slack_p,
+                       float* grad_buses, float* grad_lines, float* grad_generators,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

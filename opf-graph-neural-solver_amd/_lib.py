@@ -111,7 +111,14 @@ def load_library():
     lib.gns_fd_solve.argtypes = [fdcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.gns_fd_workspace_bytes_set.argtypes = [fdcp, vp, sz, vp, i32, i64, ctypes.POINTER(sz)]
     lib.gns_fd_solve_set.argtypes = [fdcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    for f in PF_EXPORTS + FD_EXPORTS:
+    lib.gns_dc_lds_bytes.argtypes = [vp, ctypes.POINTER(i64)]
+    lib.gns_dc_workspace_bytes.argtypes = [pfcp, vp, i64, ctypes.POINTER(sz)]
+    lib.gns_dc_solve.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_dc_workspace_bytes_set.argtypes = [pfcp, vp, sz, vp, i32, i64, ctypes.POINTER(sz)]
+    lib.gns_dc_solve_set.argtypes = [pfcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_dc_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_dc_adjoint_set.argtypes = [pfcp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    for f in PF_EXPORTS + FD_EXPORTS + DC_EXPORTS:
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
               'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
@@ -136,6 +143,9 @@ PF_EXPORTS = ('gns_pf_topology_bytes', 'gns_pf_prepare_topology', 'gns_pf_topolo
 # the fast-decoupled solver's C-ABI (include/gns_powerflow.h, "Fast-decoupled")
 FD_EXPORTS = ('gns_fd_topology_bytes', 'gns_fd_prepare_topology', 'gns_fd_topology_info', 'gns_fd_topology_slots',
               'gns_fd_workspace_bytes', 'gns_fd_solve', 'gns_fd_workspace_bytes_set', 'gns_fd_solve_set')
+# the DC power flow's C-ABI (include/gns_powerflow.h, "DC power flow"): it runs on the fast-decoupled blob
+DC_EXPORTS = ('gns_dc_lds_bytes', 'gns_dc_workspace_bytes', 'gns_dc_solve', 'gns_dc_workspace_bytes_set', 'gns_dc_solve_set',
+              'gns_dc_adjoint', 'gns_dc_adjoint_set')
 # the limits of include/gns_powerflow.h
 PF_LDS_MAX_BYTES = 163840
 PF_MAX_SLOTS = 65535

@@ -85,6 +85,12 @@ PF_HOST_DEVICE inline int64_t fd_lds_bytes(const int32_t* h) {
   return 8 * ((int64_t)h[FH_NNZLU1] + h[FH_DIM1] + h[FH_NNZLU2] + h[FH_DIM2] + 6 * (int64_t)h[FH_N]);
 }
 
+// LDS image of one grid of the DC power flow (gns_dc_lds_bytes), which runs on the FD blob: the B' factor with its right-hand side
+// and one bus vector, in doubles
+PF_HOST_DEVICE inline int64_t dc_lds_bytes(const int32_t* h) {
+  return 8 * ((int64_t)h[FH_NNZLU1] + h[FH_DIM1] + (int64_t)h[FH_N]);
+}
+
 // What the code that handles either kind of blob (the set checks on the host and in the set kernels) needs to know of a kind.
 // The magic, the total, N, E and Gn sit at the same header words in both.
 static_assert(FH_MAGIC == PH_MAGIC && FH_TOTAL == PH_TOTAL && FH_N == PH_N && FH_E == PH_E && FH_GN == PH_GN, "shared header words");
@@ -99,4 +105,9 @@ struct FdBlobKind {
   static constexpr int32_t MAGIC = GNS_FD_MAGIC;
   static constexpr int HDR_WORDS = FD_HDR_WORDS, NNZY = FH_NNZY;
   PF_HOST_DEVICE static int64_t lds_bytes(const int32_t* h) { return fd_lds_bytes(h); }
+};
+
+// The FD blob as the DC power flow uses it: the same blob, its own LDS image
+struct DcBlobKind : FdBlobKind {
+  PF_HOST_DEVICE static int64_t lds_bytes(const int32_t* h) { return dc_lds_bytes(h); }
 };

@@ -15,6 +15,11 @@ With ``requires_grad`` on the inputs the solve is differentiable: its backward i
 ``fast_decoupled(..., variant='XB' | 'BX')`` is the second baseline of the reference's evaluation (PYPOWER ``runpf(PF_ALG=2 | 3)``,
 ``GNS/evaluate.py:42-58``): B' and B'' are factored once per grid in one HIP kernel (``csrc/gns_fdpf.hip``) from their own cached
 analysis (``gns_fd_prepare_topology``); its gradients are the Newton-Raphson adjoint at its solution.
+
+``dc_power_flow(...)`` is the linear baseline (PYPOWER ``makeBdc`` + ``dcpf``, the DC option of the reference's commented-out
+``runpf``): angles, per-line active flows and the slack's balancing power from one factorisation and one solve per grid
+(``csrc/gns_dcpf.hip``) on the fast-decoupled analysis, whose B' has the DC matrix's sparsity; its backward is a second solve on
+the same factor (``gns_dc_adjoint``).
 """
 from __future__ import annotations
 
@@ -31,6 +36,8 @@ from ._lib import (GNS_ERRORS, GNS_ETOPOLOGY, GNS_EUNSUPPORTED, PF_LDS_MAX_BYTES
                    load_library)
 
 PowerFlowResult = namedtuple('PowerFlowResult', ['v', 'theta', 'converged', 'iterations', 'mismatch'])
+
+DcPowerFlowResult = namedtuple('DcPowerFlowResult', ['v', 'theta', 'line_flow', 'slack_p', 'converged'])
 
 MixedPlan = namedtuple('MixedPlan', ['topology', 'order', 'grid_off', 'member_off', 'topo_set', 'slack_bus', 'islanded'])
 
@@ -104,12 +111,14 @@ class _PfTopologySet:
 
 _LDS_FORMULA = '8 * (nnz(L+U) + dim + 8 N) bytes per grid'
 _FD_LDS_FORMULA = "8 * (nnz_lu_p + dim_p + nnz_lu_pp + dim_pp + 6 N) bytes per grid: both factors of B' and B''"
+_DC_LDS_FORMULA = "8 * (nnz_lu_p + dim_p + N) bytes per grid: the factor of B', its right-hand side and one bus vector"
 
 
 # A solver as the launch code sees it: the prefix of its entry points, the class of its topologies, the LDS formula a refusal names
 _Solver = namedtuple('_Solver', ['prefix', 'topology', 'formula'])
 _NR = _Solver('gns_pf', PowerFlowTopology, _LDS_FORMULA)
 _FD = _Solver('gns_fd', FdTopology, _FD_LDS_FORMULA)
+_DC = _Solver('gns_dc', FdTopology, _DC_LDS_FORMULA)     # DC runs on the fast-decoupled analysis (_FD's caches), with its own LDS image
 
 
 def _analysis(solver):
@@ -137,6 +146,16 @@ def _set_lds_bytes(set_host, member_off, cls=PowerFlowTopology):
         _check(getattr(lib, fn)(set_host.ctypes.data + 4 * off, ctypes.byref(info)), fn)
         lds = max(lds, info.lds_bytes)
     return lds
+
+
+def _dc_lds_bytes(host, member_off=(0,)):
+    """The largest DC LDS image (``gns_dc_lds_bytes``) among the FD blobs at the word offsets ``member_off`` of ``host``."""
+    lib, lds = load_library(), ctypes.c_int64()
+    out = 0
+    for off in member_off:
+        _check(lib.gns_dc_lds_bytes(host.ctypes.data + 4 * int(off), ctypes.byref(lds)), 'gns_dc_lds_bytes')
+        out = max(out, lds.value)
+    return out
 
 
 def _islanded(n_bus, f_bus, t_bus, slack):
@@ -466,6 +485,107 @@ def fast_decoupled(buses, lines, generators, B=None, L=None, G=None, *, variant,
     return _run(_FD, 'fast_decoupled', cfg, buses, lines, generators, slack_bus, v0, theta0, mixed_topologies, in_dev, single)
 
 
+def dc_power_flow(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, mixed_topologies=False):
+    """DC power flow (PYPOWER ``makeBdc`` + ``dcpf`` and the DC branch of ``runpf``) of every grid of a batch, on the device: the
+    linear approximation a GNS is compared with next to Newton-Raphson.
+
+    Inputs, column maps, the slack and ``mixed_topologies`` are those of ``newton_raphson``; PV and PQ buses are treated alike and
+    there is no start to choose.  Per line ``b = 1 / (x tau)`` and ``Pfinj = -b shift``; ``Bbus`` gets ``+b`` at ff and tt, ``-b`` at
+    ft and tf; ``P = sum Pg - Pd - Gs - Pbusinj``; ``theta`` is 0 at the slack and solves ``Bbus[r, r] theta_r = P_r`` elsewhere
+    (float64, one sparse factorisation and one solve per grid).  ``r``, line charging and ``Bs`` are not used.
+
+    Returns ``DcPowerFlowResult(v, theta, line_flow, slack_p, converged)``: float64 ``[Bt,N]``, ``[Bt,N]``, ``[Bt,E]``, ``[Bt]`` and
+    bool ``[Bt]``, on the inputs' device.  ``v`` is 1; ``line_flow = b (theta_f - theta_t) + Pfinj`` is the active flow at each line's
+    from end; ``slack_p = Bbus[slack, :] theta - P_slack`` is what the slack generates beyond its listed ``Pg``.  A grid with a zero or
+    non-finite pivot or a non-finite ``theta`` (and, with ``mixed_topologies``, one whose topology islands a bus) has ``converged``
+    False and NaN in ``theta``, ``line_flow`` and ``slack_p``; the other grids are unaffected, and every grid's result is
+    bit-identical alone, in any batch, in any order and from run to run.
+
+    The analysis is ``fast_decoupled``'s (B' has the sparsity of ``Bbus[r, r]``): a batch either of them has seen is not analysed
+    again.  DC keeps less in LDS (the factor of B', its right-hand side, one bus vector), so it solves every topology
+    ``fast_decoupled`` does, and larger ones.
+
+    Gradients: with grad mode on and ``requires_grad`` on an input, ``theta``, ``line_flow`` and ``slack_p`` are differentiable: one
+    ``gns_dc_adjoint`` / ``gns_dc_adjoint_set`` launch (a second solve on the same factor: the matrix is symmetric) gives the exact
+    derivative with respect to ``Pd``, ``Gs``, the lines' ``x``, ``tau``, ``shift`` and the generators' ``Pg``; every other column
+    gets 0.  A grid that is not solved gets NaN gradient rows unless all its incoming gradients are zero.  The forward outputs are
+    bit-identical with and without gradients.  Contract: ``include/gns_powerflow.h``, "DC power flow"."""
+    single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, 0.0, 0, mixed_topologies)
+    lib = load_library()
+    Bt, N = buses.shape[0], buses.shape[1]
+    cfg = PfConfig(N, lines.shape[1], generators.shape[1], 0, 0.0)
+    plain = (buses.detach(), lines.detach(), generators.detach())
+    if mixed_topologies:
+        plan = _planned(_FD, _classify(*plain, slack_bus), *plain)
+        host, members = plan.topo_set.host, plan.member_off
+        target = _set_members(plan, (host, plan.topo_set.blob), FdTopology)
+        if target is not None:
+            target = target._replace(lds=lambda: _dc_lds_bytes(host, members.tolist()))
+    else:
+        topo = _analysed(_FD, *_topology_key(*plain, slack_bus, 'dc_power_flow'), buses.device)
+        target = _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host))
+
+    def solve(bu, li, ge):
+        return _dc_solve(lib, cfg, target, bu, li, ge)
+
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (buses, lines, generators)):
+        out = list(_DCFunction.apply(solve, lambda *args: _dc_adjoint(lib, cfg, target, *args), buses, lines, generators))
+    else:
+        out = solve(*plain)
+    out = [torch.ones(Bt, N, dtype=torch.float64, device=buses.device), *out]
+    if in_dev != buses.device:
+        out = [t.to(in_dev) for t in out]
+    if single:
+        out = [t[0] for t in out]
+    return DcPowerFlowResult(*out)
+
+
+class _DCFunction(torch.autograd.Function):
+    """``dc_power_flow`` when an input requires grad, as ``_NRFunction``: the forward is the solve, the backward one adjoint launch on
+    the forward's target."""
+
+    @staticmethod
+    def forward(ctx, solve, adjoint, buses, lines, gens):
+        theta, flow, slack_p, conv = solve(buses, lines, gens)
+        ctx.mark_non_differentiable(conv)
+        ctx.set_materialize_grads(False)
+        ctx.adjoint = adjoint
+        ctx.save_for_backward(buses, lines, gens, theta, conv)
+        return theta, flow, slack_p, conv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gth, gfl, gsp, _gconv):
+        buses, lines, gens, theta, conv = ctx.saved_tensors
+        grads = ctx.adjoint(buses, lines, gens, theta, conv, (gth, gfl, gsp), ctx.needs_input_grad[2:5])
+        return (None, None, *grads)
+
+
+def _dc_solve(lib, cfg, target, buses, lines, generators):
+    """One DC solve launch (``gns_dc_solve[_set]``) on ``target``: ``[theta, line_flow, slack_p, converged]``."""
+    Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
+    if target is None:                            # every topology islands a bus: no grid is solved
+        nan = float('nan')
+        return [torch.full((Bt, N), nan, dtype=torch.float64, device=dev), torch.full((Bt, E), nan, dtype=torch.float64, device=dev),
+                torch.full((Bt,), nan, dtype=torch.float64, device=dev), torch.zeros(Bt, dtype=torch.bool, device=dev)]
+    theta, flow = (torch.empty(Bt, n, dtype=torch.float64, device=dev) for n in (N, E))
+    slack_p, conv = torch.empty(Bt, dtype=torch.float64, device=dev), torch.empty(Bt, dtype=torch.uint8, device=dev)
+    _launch(lib, _DC, 'solve', cfg, target, (buses, lines, generators), (theta, flow, slack_p, conv))
+    return [theta, flow, slack_p, conv.bool()]
+
+
+def _dc_adjoint(lib, cfg, target, buses, lines, gens, theta, conv, incoming, need):
+    """One DC adjoint launch (``gns_dc_adjoint[_set]``) on the forward's ``target``, ``incoming`` the gradients of ``theta``,
+    ``line_flow`` and ``slack_p`` (None: zero); returns the gradients of the inputs ``need`` asks for."""
+    Bt, dev = buses.shape[0], buses.device
+    gin = [torch.empty_like(t) if n else None for t, n in zip((buses, lines, gens), need)]
+    incoming = [None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming]
+    if target is None:
+        return _unsolved_grads(gin, incoming, Bt, dev)
+    _launch(lib, _DC, 'adjoint', cfg, target, (buses, lines, gens), (theta, conv, *incoming, *gin))
+    return gin
+
+
 def _not_solved(Bt, N, dev):
     """The outputs of a batch none of whose topologies can be solved (each islands a bus)."""
     nan = float('nan')
@@ -570,17 +690,23 @@ def _adjoint(lib, cfg, target, buses, lines, gens, v, theta, conv, gv, gth, need
     forward's device and stream; returns the gradients of the inputs ``need`` asks for."""
     Bt, dev = buses.shape[0], buses.device
     gin, gv, gth = _adjoint_args(buses, lines, gens, gv, gth, need)
-    if target is None:                            # no grid is solved: NaN rows, zero rows for a zero gradient
-        zero = torch.ones(Bt, dtype=torch.bool, device=dev)
-        for g in (gv, gth):
-            if g is not None:
-                zero &= (g == 0).all(dim=1)
-        fill = torch.where(zero, 0.0, float('nan')).to(torch.float32)
-        for t in gin:
-            if t is not None:
-                t.copy_(fill.view(Bt, 1, 1).expand_as(t))
-        return gin
+    if target is None:
+        return _unsolved_grads(gin, (gv, gth), Bt, dev)
     _launch(lib, _NR, 'adjoint', cfg, target, (buses, lines, gens), (v, theta, conv, gv, gth, *gin))
+    return gin
+
+
+def _unsolved_grads(gin, incoming, Bt, dev):
+    """The gradients ``gin`` of a batch none of whose grids is solved: NaN rows, zero rows for a grid whose ``incoming`` gradients
+    (``[Bt, ...]`` or None) are all zero."""
+    zero = torch.ones(Bt, dtype=torch.bool, device=dev)
+    for g in incoming:
+        if g is not None:
+            zero &= (g.reshape(Bt, -1) == 0).all(dim=1)
+    fill = torch.where(zero, 0.0, float('nan')).to(torch.float32)
+    for t in gin:
+        if t is not None:
+            t.copy_(fill.view(Bt, 1, 1).expand_as(t))
     return gin
 
 

@@ -1,15 +1,17 @@
 // C-ABI entry points (include/gns_hip.h).  Host code only: validates, lays out the workspace and enqueues
 // kernels on the caller's stream.  No allocation, no synchronisation, no host<->device copies.
+// In order: options, device state, profiling, call resolver and path decision, layouts and fillers, launch helpers, entry points, Adam.
 #include <atomic>
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
 #include <mutex>
+#include <vector>
 #include "gns_kernels.h"
 #include "gns_gridwg.h"
 
-// ---- process-wide tuning knobs: read from the environment ONCE (first call), never per launch ----------------------
 namespace {
+// ---- process-wide tuning knobs: read from the environment ONCE (first call), never per launch ----------------------
 struct GnsTuning {
   int fwd_mapping;   // GNS_FWD_MAPPING: 0 auto, 1 "lane" (lane = grid, state streamed through HBM), 2 "lds" (grid per workgroup, state on chip)
   int gw_pack;       // GNS_GW_PACK: grids per workgroup of the lds mapping (0 = auto)
@@ -22,18 +24,37 @@ struct GnsTuning {
   int bwds_mode;     // GNS_BWDS_MODE: sweep kernels per reverse step of the split backward: 0 one per family, 1 {L_m} {L_theta + L_v}, 2 all three families per bus in one kernel
   int bwds_chunks;   // GNS_BWDS_CHUNKS: bus chunks per 64-grid group of the split backward's sweeps (0 = auto: 8, 16 or 32)
 };
+
+// One row per option: its name (gns_set_option / gns_get_option), where it lives, the values it takes (lo..hi, or `check`, which may
+// normalise the value) and the environment variable that seeds it, read through `parse`.  A value out of range is refused by
+// gns_set_option (GNS_EINVAL) and ignored when it comes from the environment.
+bool waves_ok(int& w) { return w > 0 && (w & (w - 1)) == 0 && w * 64 <= GNS_FWD_MAX_THREADS; }
+bool chunks_ok(int& c) { return c == 0 || gns_part_index(c) >= 0; }
+bool as_flag(int& v) { v = v ? 1 : 0; return true; }                                  // any integer, stored as 0 / 1
+int env_int(const char* e) { return std::atoi(e); }
+int env_mapping(const char* e) { return !std::strcmp(e, "lane") ? 1 : (!std::strcmp(e, "lds") ? 2 : 0); }   // by word; anything else: auto
+int env_plane(const char* e) { return e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2); }     // by first character
+int env_flag(const char* e) { return e[0] == '0' ? 0 : 1; }
+struct GnsOption {
+  const char* name; int GnsTuning::*member; int lo, hi; bool (*check)(int&); const char* env; int (*parse)(const char*);
+  bool accepts(int& v) const { return check ? check(v) : (v >= lo && v <= hi); }
+};
+const GnsOption g_options[] = {
+  {"fwd_mapping",   &GnsTuning::fwd_mapping,   0, 2,            nullptr,   "GNS_FWD_MAPPING",   env_mapping},
+  {"train_mapping", &GnsTuning::train_mapping, 0, 2,            nullptr,   "GNS_TRAIN_MAPPING", env_mapping},
+  {"bwd_variant",   &GnsTuning::bwd_variant,   1, 4,            nullptr,   "GNS_BWD_VARIANT",   env_int},
+  {"gw_pack",       &GnsTuning::gw_pack,       0, 16,           nullptr,   "GNS_GW_PACK",       env_int},
+  {"fwd_waves",     &GnsTuning::fwd_waves,     0, 0,            waves_ok,  "GNS_FWD_WAVES",     env_int},
+  {"fwd_plane",     &GnsTuning::fwd_plane,     0, 2,            nullptr,   "GNS_FWD_PLANE",     env_plane},
+  {"dw_mfma",       &GnsTuning::dw_mfma,       0, 0,            as_flag,   "GNS_DW_MFMA",       env_flag},
+  {"team",          &GnsTuning::team,          0, GNS_MAX_TEAM, nullptr,   "GNS_TEAM",          env_int},
+  {"bwds_mode",     &GnsTuning::bwds_mode,     0, 2,            nullptr,   "GNS_BWDS_MODE",     env_int},
+  {"bwds_chunks",   &GnsTuning::bwds_chunks,   0, 0,            chunks_ok, "GNS_BWDS_CHUNKS",   env_int},
+};
 GnsTuning make_tuning() {
   GnsTuning t{0, 0, GNS_FWD_THREADS / 64, 2, 1, 0, 4, 0, 1, 0};
-  if (const char* e = std::getenv("GNS_TEAM")) { const int v = std::atoi(e); if (v >= 0 && v <= GNS_MAX_TEAM) t.team = v; }
-  if (const char* e = std::getenv("GNS_FWD_MAPPING")) t.fwd_mapping = !std::strcmp(e, "lane") ? 1 : (!std::strcmp(e, "lds") ? 2 : 0);
-  if (const char* e = std::getenv("GNS_GW_PACK")) { const int p = std::atoi(e); if (p >= 1 && p <= 16) t.gw_pack = p; }
-  if (const char* e = std::getenv("GNS_FWD_WAVES")) { const int w = std::atoi(e); if (w > 0 && (w & (w - 1)) == 0 && w * 64 <= GNS_FWD_MAX_THREADS) t.fwd_waves = w; }
-  if (const char* e = std::getenv("GNS_FWD_PLANE")) t.fwd_plane = e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2);
-  if (const char* e = std::getenv("GNS_DW_MFMA")) t.dw_mfma = e[0] == '0' ? 0 : 1;
-  if (const char* e = std::getenv("GNS_BWD_VARIANT")) { const int v = std::atoi(e); if (v >= 1 && v <= 4) t.bwd_variant = v; }
-  if (const char* e = std::getenv("GNS_BWDS_MODE")) { const int v = std::atoi(e); if (v >= 0 && v <= 2) t.bwds_mode = v; }
-  if (const char* e = std::getenv("GNS_BWDS_CHUNKS")) { const int v = std::atoi(e); if (v == 0 || gns_part_index(v) >= 0) t.bwds_chunks = v; }
-  if (const char* e = std::getenv("GNS_TRAIN_MAPPING")) t.train_mapping = !std::strcmp(e, "lane") ? 1 : (!std::strcmp(e, "lds") ? 2 : 0);
+  for (const GnsOption& o : g_options)
+    if (const char* e = std::getenv(o.env)) { int v = o.parse(e); if (o.accepts(v)) t.*o.member = v; }
   return t;
 }
 GnsTuning& tuning() {
@@ -49,6 +70,12 @@ struct GnsLast {
   int bwd_kernel, dw_mfma, bwds_mode, bwds_chunks, bwds_R, bwd_gw_pack;   // gns_backward / gns_backward_inputs / gns_backward_grouped
 };
 GnsLast g_last{-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+struct GnsLastName { const char* name; int GnsLast::*member; };
+const GnsLastName g_last_names[] = {                                          // read as "last.<name>"
+  {"fwd_kernel", &GnsLast::fwd_kernel}, {"fwd_waves", &GnsLast::fwd_waves}, {"fwd_plane", &GnsLast::fwd_plane}, {"team", &GnsLast::team},
+  {"gw_pack", &GnsLast::gw_pack}, {"bwd_kernel", &GnsLast::bwd_kernel}, {"dw_mfma", &GnsLast::dw_mfma}, {"bwds_mode", &GnsLast::bwds_mode},
+  {"bwds_chunks", &GnsLast::bwds_chunks}, {"bwds_R", &GnsLast::bwds_R}, {"bwd_gw_pack", &GnsLast::bwd_gw_pack},
+};
 void record_forward(int kernel, int waves, int plane, int team, int pack) {
   g_last.fwd_kernel = kernel; g_last.fwd_waves = waves; g_last.fwd_plane = plane; g_last.team = team; g_last.gw_pack = pack;
 }
@@ -92,79 +119,8 @@ const GnsDevice& device() {
   }
   return devs[dev];
 }
-}  // namespace
-
-// Explicit configuration (include/gns_hip.h).  The environment variables of the same meaning only seed the defaults.
-extern "C" int gns_set_option(const char* name, int value) {
-  if (!name) return GNS_EINVAL;
-  GnsTuning& t = tuning();
-  if (!std::strcmp(name, "fwd_mapping")) { if (value < 0 || value > 2) return GNS_EINVAL; t.fwd_mapping = value; return GNS_OK; }
-  if (!std::strcmp(name, "bwd_variant")) { if (value < 1 || value > 4) return GNS_EINVAL; t.bwd_variant = value; return GNS_OK; }
-  if (!std::strcmp(name, "train_mapping")) { if (value < 0 || value > 2) return GNS_EINVAL; t.train_mapping = value; return GNS_OK; }
-  if (!std::strcmp(name, "gw_pack")) { if (value < 0 || value > 16) return GNS_EINVAL; t.gw_pack = value; return GNS_OK; }
-  if (!std::strcmp(name, "fwd_waves")) { if (value <= 0 || (value & (value - 1)) || value * 64 > GNS_FWD_MAX_THREADS) return GNS_EINVAL; t.fwd_waves = value; return GNS_OK; }
-  if (!std::strcmp(name, "fwd_plane")) { if (value < 0 || value > 2) return GNS_EINVAL; t.fwd_plane = value; return GNS_OK; }
-  if (!std::strcmp(name, "dw_mfma")) { t.dw_mfma = value ? 1 : 0; return GNS_OK; }
-  if (!std::strcmp(name, "team")) { if (value < 0 || value > GNS_MAX_TEAM) return GNS_EINVAL; t.team = value; return GNS_OK; }
-  if (!std::strcmp(name, "bwds_mode")) { if (value < 0 || value > 2) return GNS_EINVAL; t.bwds_mode = value; return GNS_OK; }
-  if (!std::strcmp(name, "bwds_chunks")) { if (value != 0 && gns_part_index(value) < 0) return GNS_EINVAL; t.bwds_chunks = value; return GNS_OK; }
-  return GNS_EINVAL;
-}
-extern "C" int gns_get_option(const char* name, int* value) {
-  if (!name || !value) return GNS_EINVAL;
-  const GnsTuning& t = tuning();
-  const GnsLast& l = g_last;
-  if (!std::strcmp(name, "fwd_mapping")) *value = t.fwd_mapping;
-  else if (!std::strcmp(name, "train_mapping")) *value = t.train_mapping;
-  else if (!std::strcmp(name, "bwd_variant")) *value = t.bwd_variant;
-  else if (!std::strcmp(name, "gw_pack")) *value = t.gw_pack;
-  else if (!std::strcmp(name, "fwd_waves")) *value = t.fwd_waves;
-  else if (!std::strcmp(name, "fwd_plane")) *value = t.fwd_plane;
-  else if (!std::strcmp(name, "dw_mfma")) *value = t.dw_mfma;
-  else if (!std::strcmp(name, "team")) *value = t.team;
-  else if (!std::strcmp(name, "bwds_chunks")) *value = t.bwds_chunks;
-  else if (!std::strcmp(name, "bwds_mode")) *value = t.bwds_mode;
-  else if (!std::strcmp(name, "last.fwd_kernel")) *value = l.fwd_kernel;
-  else if (!std::strcmp(name, "last.fwd_waves")) *value = l.fwd_waves;
-  else if (!std::strcmp(name, "last.fwd_plane")) *value = l.fwd_plane;
-  else if (!std::strcmp(name, "last.team")) *value = l.team;
-  else if (!std::strcmp(name, "last.gw_pack")) *value = l.gw_pack;
-  else if (!std::strcmp(name, "last.bwd_kernel")) *value = l.bwd_kernel;
-  else if (!std::strcmp(name, "last.dw_mfma")) *value = l.dw_mfma;
-  else if (!std::strcmp(name, "last.bwds_mode")) *value = l.bwds_mode;
-  else if (!std::strcmp(name, "last.bwds_chunks")) *value = l.bwds_chunks;
-  else if (!std::strcmp(name, "last.bwds_R")) *value = l.bwds_R;
-  else if (!std::strcmp(name, "last.bwd_gw_pack")) *value = l.bwd_gw_pack;
-  else return GNS_EINVAL;
-  return GNS_OK;
-}
-
-// The compiled (latent_dim, hidden_dim) pair a model runs on: the smallest one that holds it.  A narrower model runs zero-padded
-// (gns_common.h, GnsFamilies): same function, same gradients; only gns_pack_params / gns_unfold know the difference.
-static bool kernel_dims(int d, int h, int* dk, int* hk) {
-  bool found = false;
-#define GNS_CASE(DD, HH) if (d <= DD && h <= HH && (!found || DD * HH < *dk * *hk)) { *dk = DD; *hk = HH; found = true; }
-  GNS_FOR_EACH_DIMS(GNS_CASE)
-#undef GNS_CASE
-  return found;
-}
-static bool dims_supported(int d, int h) { int dk, hk; return kernel_dims(d, h, &dk, &hk); }
-// cfg with the kernel's dims in place of the model's (everything but the flat parameter layout is sized by these)
-static bool kernel_config(const gns_config* model, gns_config* k) {
-  *k = *model;
-  return kernel_dims(model->latent_dim, model->hidden_dim, &k->latent_dim, &k->hidden_dim);
-}
-
-static int check_cfg(const gns_config* c) {
-  if (!c) return GNS_EINVAL;
-  if (c->n_bus <= 0 || c->n_line <= 0 || c->n_gen < 0 || c->K <= 0 || c->latent_dim <= 0 || c->hidden_dim <= 0) return GNS_EINVAL;
-  if (c->multiple_phi != 0 && c->multiple_phi != 1) return GNS_EINVAL;
-  return GNS_OK;
-}
 
 // ---- optional kernel timing (diagnostics) ---------------------------------------------------------------
-#include <vector>
-namespace {
 struct ProfRing { std::vector<hipEvent_t> a, b; int used = 0; };
 ProfRing g_prof[2];
 int g_prof_cap = 0;
@@ -175,11 +131,57 @@ void prof_mark(int which, bool start, hipStream_t st) {
   (void)hipEventRecord(start ? r.a[r.used] : r.b[r.used], st);
   if (!start) ++r.used;
 }
-}  // namespace
+
+// ---- what a call runs on: the compiled kernel pair, and which kernels take it ---------------------------------------------
+// The compiled (latent_dim, hidden_dim) pair a model runs on: the smallest one that holds it.  A narrower model runs zero-padded
+// (gns_common.h, GnsFamilies): same function, same gradients; only gns_pack_params / gns_unfold know the difference.
+bool kernel_dims(int d, int h, int* dk, int* hk) {
+  bool found = false;
+#define GNS_CASE(DD, HH) if (d <= DD && h <= HH && (!found || DD * HH < *dk * *hk)) { *dk = DD; *hk = HH; found = true; }
+  GNS_FOR_EACH_DIMS(GNS_CASE)
+#undef GNS_CASE
+  return found;
+}
+// cfg with the kernel's dims in place of the model's (everything but the flat parameter layout is sized by these)
+bool kernel_config(const gns_config* model, gns_config* k) {
+  *k = *model;
+  return kernel_dims(model->latent_dim, model->hidden_dim, &k->latent_dim, &k->hidden_dim);
+}
+
+int check_cfg(const gns_config* c) {
+  if (!c) return GNS_EINVAL;
+  if (c->n_bus <= 0 || c->n_line <= 0 || c->n_gen < 0 || c->K <= 0 || c->latent_dim <= 0 || c->hidden_dim <= 0) return GNS_EINVAL;
+  if (c->multiple_phi != 0 && c->multiple_phi != 1) return GNS_EINVAL;
+  return GNS_OK;
+}
+
+// A validated call: the model's config as the caller gave it (it only lays out the flat parameters and their gradient) and the
+// kernel's, which sizes everything else.
+struct GnsCall {
+  const gns_config* model;
+  gns_config k;
+  GnsFamilies families() const {         // the parameter families of the model, padded to the kernel's dims
+    GnsFamilies f; gns_families_padded(model->latent_dim, model->hidden_dim, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, &f);
+    return f;
+  }
+};
+// The checks every entry point opens with, in the order their codes take precedence: the config (GNS_EINVAL), the entry point's own
+// arguments (`args_ok`: GNS_EINVAL), a compiled pair that holds the model and - only where `cap_K` - K <= GNS_MAX_K (GNS_EUNSUPPORTED).
+// The launches (gns_forward, gns_backward, gns_backward_inputs, the grouped calls) cap K: their argument structs hold GNS_MAX_K loss
+// weights.  The queries (gns_workspace_bytes, gns_uses_packed_inputs, gns_team_status*) never did and still do not.
+enum KCap { ANY_K, CAP_K };
+int resolve(const gns_config* cfg, bool args_ok, KCap cap_K, GnsCall* c) {
+  const int rc = check_cfg(cfg);
+  if (rc != GNS_OK) return rc;
+  if (!args_ok) return GNS_EINVAL;
+  c->model = cfg;
+  if (!kernel_config(cfg, &c->k) || (cap_K == CAP_K && cfg->K > GNS_MAX_K)) return GNS_EUNSUPPORTED;
+  return GNS_OK;
+}
 
 // Workgroups per 64-grid group of the lane-per-grid kernels (gns_device.h, "teams").  Asked by gns_workspace_bytes,
 // gns_forward and gns_backward alike.
-static int lane_team(int64_t Bt) {
+int lane_team(int64_t Bt) {
   const GnsTuning& T = tuning();
   const int64_t groups = (Bt + GNS_LANES - 1) / GNS_LANES;
   if (groups > GNS_TEAM_MAX_GROUPS) return 1;
@@ -187,10 +189,17 @@ static int lane_team(int64_t Bt) {
   return gns_team_size(groups, ncu, T.team);
 }
 
+bool split_available(const gns_config* c) { return device().split_ready && gns_bwds_supported(c->latent_dim, c->hidden_dim, c->multiple_phi); }
+// The checks of a grouped call over G 64-grid groups (the model's cfg in, the kernel's out): it always runs the split backward's kernels
+int grouped_call(const gns_config* model, int64_t G, GnsCall* c) {
+  const int rc = resolve(model, G > 0 && G <= ((int64_t)1 << 24), CAP_K, c);
+  if (rc != GNS_OK) return rc;
+  return split_available(&c->k) ? GNS_OK : GNS_EUNSUPPORTED;
+}
 // The split backward (bwd_variant 4) runs the three-phi models on the matrix-pipe engine; everything else keeps the persistent kernel.
-static bool use_split_backward(const gns_config* c) {
+bool use_split_backward(const gns_config* c) {
   const GnsTuning& T = tuning();
-  if (!device().split_ready || !gns_bwds_supported(c->latent_dim, c->hidden_dim, c->multiple_phi)) return false;
+  if (!split_available(c)) return false;
   if (!gns_backward_persistent_supported(c->latent_dim, c->hidden_dim)) return true;      // the only lane-per-grid backward of this pair
   return T.bwd_variant == 4 && T.dw_mfma;
 }
@@ -199,7 +208,7 @@ static bool use_split_backward(const gns_config* c) {
 #define GNS_SAVE_IGRAD 2
 #define GNS_IGRAD_MARK 0x49475244u      // written behind a forward workspace saved with save_state = 2
 #define GNS_IGRAD_MARK_BYTES 256
-static size_t igrad_bytes(const gns_config* kcfg, int64_t Bt) {
+size_t igrad_bytes(const gns_config* kcfg, int64_t Bt) {
   return gns_align256((size_t)((Bt + GNS_LANES - 1) / GNS_LANES) * gns_in_rows(kcfg->n_bus, kcfg->n_line) * GNS_LANES * 16);
 }
 struct IgradOut {
@@ -210,7 +219,7 @@ struct IgradOut {
 
 // Which mapping runs a training-mode forward and its backward.  Evaluated identically by gns_forward and gns_backward:
 // changing "train_mapping" / "gw_pack" between a forward and its backward is a caller error.
-static int gw_train_pack(const gns_config* c, int64_t Bt) {
+int gw_train_pack(const gns_config* c, int64_t Bt) {
   const GnsTuning& T = tuning();
   const int P = T.gw_pack > 0 ? T.gw_pack : 1;
   if (!device().gw_ready || T.train_mapping == 1) return 0;
@@ -226,7 +235,7 @@ static int gw_train_pack(const gns_config* c, int64_t Bt) {
 }
 // Grids per workgroup of the evaluation-mode forward when it runs on the grid-per-workgroup kernel, 0 when the lane-per-grid
 // kernel runs it.  gns_workspace_bytes, gns_forward and gns_uses_packed_inputs must agree, so they all ask here.
-static int gw_eval_pack(const gns_config* c, int64_t Bt) {
+int gw_eval_pack(const gns_config* c, int64_t Bt) {
   const GnsTuning& T = tuning();
   const int N = c->n_bus, E = c->n_line;
   const int wpg = ((N > E ? N : E) + 63) / 64;
@@ -249,8 +258,43 @@ static int gw_eval_pack(const gns_config* c, int64_t Bt) {
   return (can && want) ? P : 0;
 }
 
+// Which kernels run a call.  The ONE place that decides it: gns_workspace_bytes, gns_uses_packed_inputs, both team-status calls,
+// gns_forward and gns_backward (which decides as for save_state = 1) must agree, so they all ask here and nothing else.
+enum GnsPath {
+  PATH_GW_TRAIN,      // grid-per-workgroup training pair (forward saved for gns_gw_launch_backward)
+  PATH_GW_EVAL,       // grid-per-workgroup evaluation: state on chip, inputs read in place
+  PATH_LANE,          // lane-per-grid forward (and the split or persistent backward)
+  PATH_LANE_IGRAD,    // lane-per-grid forward saved for gns_backward_inputs (save_state 2)
+};
+struct GnsRoute {
+  GnsPath path; int pack;                // pack: grids per workgroup of the grid-per-workgroup kernels, 0 on the lane paths
+  bool lane() const { return path == PATH_LANE || path == PATH_LANE_IGRAD; }
+};
+GnsRoute route(const gns_config* k, int64_t Bt, int save_state) {
+  if (save_state == GNS_SAVE_IGRAD) return {PATH_LANE_IGRAD, 0};
+  const int P = save_state ? gw_train_pack(k, Bt) : gw_eval_pack(k, Bt);
+  if (P > 0) return {save_state ? PATH_GW_TRAIN : PATH_GW_EVAL, P};
+  return {PATH_LANE, 0};
+}
+
+// ---- workspace layouts and the argument structs' tables --------------------------------------------------------------------
+GnsFwdLayout fwd_layout(const gns_config* k, int64_t Bt, int save_state) {
+  GnsFwdLayout L;
+  gns_fwd_layout(k->n_bus, k->n_line, k->latent_dim, k->hidden_dim, k->K, k->multiple_phi, Bt, save_state, &L);
+  return L;
+}
+GnsBwdsLayout bwds_layout(const gns_config* k, int64_t Bt) {
+  GnsBwdsLayout S;
+  gns_bwds_layout(k->n_bus, k->n_line, k->latent_dim, k->hidden_dim, k->K, k->multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
+  return S;
+}
+GnsBwdLayout bwd_layout(const gns_config* k, int64_t Bt, int team) {
+  GnsBwdLayout B;
+  gns_bwd_layout(k->n_bus, k->n_line, k->latent_dim, k->hidden_dim, k->K, k->multiple_phi, Bt, team, &B);
+  return B;
+}
 struct GwTrainLayout { size_t off_pt, off_pn, off_save; GwSaveLayout sv; size_t fwd_total; int blocks, waves; size_t off_slab, off_part, off_tmp, bwd_total; long long slab_floats, nslab; };
-static GwTrainLayout gw_train_layout(const gns_config* c, int64_t Bt, int P) {
+GwTrainLayout gw_train_layout(const gns_config* c, int64_t Bt, int P) {
   GwTrainLayout L;
   GnsFamilies f; gns_families(c->latent_dim, c->hidden_dim, c->K, c->multiple_phi, &f);
   size_t o = 0;
@@ -270,6 +314,182 @@ static GwTrainLayout gw_train_layout(const gns_config* c, int64_t Bt, int P) {
   L.off_tmp = o;  o = gns_align256(o + (size_t)L.slab_floats * 4);
   L.bwd_total = o;
   return L;
+}
+
+// The family tables of an argument struct: where each family's weights sit in the transposed stream (the forwards), and in the
+// natural stream and the gradient slab as well (the backwards)
+template <class Args> void fill_forward_families(Args& A, const GnsFamilies& fam) {
+  for (int i = 0; i < fam.nfam; ++i) { A.t_off[i] = fam.t_off[i]; A.t_sz[i] = fam.t_sz[i]; }
+}
+template <class Args> void fill_backward_families(Args& A, const GnsFamilies& fam) {
+  fill_forward_families(A, fam);
+  for (int i = 0; i < fam.nfam; ++i) { A.n_off[i] = fam.n_off[i]; A.n_sz[i] = fam.n_sz[i]; A.g_off[i] = fam.g_off[i]; A.g_sz[i] = fam.g_sz[i]; }
+}
+// The loss weight gamma^(K-k) of step k, rounded to fp32 from a double like the reference's python float (main.py:198)
+float loss_weight(const gns_config* cfg, int k) {
+  const int K = cfg->K;
+  return (float)std::pow((double)cfg->gamma, (double)(K - k));
+}
+template <class Args> void fill_loss_weights(Args& A, const gns_config* cfg) {
+  for (int k = 0; k < cfg->K; ++k) A.gw[k] = loss_weight(cfg, k);
+}
+
+// Byte offset of the team status word in the forward workspace of a lane-per-grid call over Bt grid slots, (size_t)-1 when it runs
+// without teams; *ws_total: the size of that workspace.
+size_t team_word_offset(const gns_config* k, int64_t Bt, int save_state, size_t* ws_total = nullptr) {
+  if (lane_team(Bt) <= 1) return (size_t)-1;
+  const GnsFwdLayout L = fwd_layout(k, Bt, save_state);
+  if (ws_total) *ws_total = L.total;
+  return L.off_team + GNS_TEAM_STATUS_WORD * 4;
+}
+// ... and the read of it: waits for `stream` and copies one word
+int read_team_word(const void* fwd_workspace, size_t off, void* stream, int* status) {
+  unsigned word = 0;
+  if (hipMemcpyAsync(&word, (const char*)fwd_workspace + off, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
+      hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { (void)hipGetLastError(); return GNS_ELAUNCH; }
+  *status = word ? 1 : 0;
+  return GNS_OK;
+}
+
+// ---- launch helpers ---------------------------------------------------------------------------------------------------------------
+// The grid-per-workgroup forward, P grids per workgroup, on parameters already packed into `pt`.  sv / GL: the save area of a training
+// forward and its layout, NULL for an evaluation.
+int gw_forward(const gns_config* cfg, const GnsFamilies& fam, const void* topo_dev, const float* pt, const float* buses, const float* lines,
+               const float* generators, int64_t Bt, float* v, float* theta, float* total_loss, float* last_loss, int P, char* sv,
+               const GwSaveLayout* GL, hipStream_t st) {
+  const int N = cfg->n_bus, E = cfg->n_line;
+  GnsGwFwdArgs G;
+  std::memset(&G, 0, sizeof(G));
+  G.topo = (const int*)topo_dev; G.pt = pt; G.buses = buses; G.lines = lines; G.gens = generators;
+  G.v_out = v; G.theta_out = theta; G.total_out = total_loss; G.last_out = last_loss;
+  if (sv) { G.sv_state = (float*)(sv + GL->off_state); G.sv_S = (float*)(sv + GL->off_S); G.sv_lam = (float*)(sv + GL->off_lam); }
+  fill_forward_families(G, fam);
+  fill_loss_weights(G, cfg);
+  G.Bt = Bt; G.N = N; G.E = E; G.Gn = cfg->n_gen; G.K = cfg->K; G.save = sv ? 1 : 0; G.P = P; G.WPG = ((N > E ? N : E) + 63) / 64;
+  record_forward(2, -1, -1, -1, P);
+  prof_mark(0, true, st);
+  const int rc = gns_gw_launch_forward(cfg->latent_dim, cfg->hidden_dim, cfg->multiple_phi, G, st);
+  prof_mark(0, false, st);
+  return rc;
+}
+
+// The lane-per-grid forward of Bt input grids in L.groups 64-grid groups (parameters and inputs already packed into `ws`).  group_topo /
+// slot_grid: NULL for a one-topology batch (lane l of group g computes grid 64 g + l), else the tables of a grouped call.
+int lane_forward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLayout& L, char* ws, float* pt, float* pin,
+                 const int* topo_dev, const int* group_topo, const int* slot_grid, int64_t Bt, float* v, float* theta,
+                 float* total_loss, float* last_loss, int save_state, hipStream_t st) {
+  const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
+  const GnsTuning& T = tuning();
+  int rc;
+  GnsFwdArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.topo = topo_dev; A.group_topo = group_topo; A.slot_grid = slot_grid; A.pt = pt; A.in = pin;
+  A.state = (float*)(ws + L.off_state); A.lam = (float*)(ws + L.off_lam); A.msg = (float*)(ws + L.off_msg);
+  A.v_out = v; A.theta_out = theta; A.total_out = total_loss; A.last_out = last_loss;
+  fill_forward_families(A, fam);
+  fill_loss_weights(A, cfg);
+  A.Bt = Bt; A.G = L.groups; A.N = N; A.E = E; A.K = K; A.save = save_state ? 1 : 0;
+  const int team0 = lane_team(L.groups * GNS_LANES);     // (= lane_team(Bt) for a one-topology batch)
+  A.team = team0;
+  A.team_ws = (unsigned char*)(ws + L.off_team);
+  int waves = T.fwd_waves;
+  while (waves * A.team > GNS_MAXP) waves /= 2;
+  A.part_idx = gns_part_index(waves * A.team);
+  auto pick_planes = [&]() {
+    A.plane = (device().fwd_ready && gns_fwd_plane_fits(N, A.team) && T.fwd_plane) ? 1 : 0;
+    if (A.plane && gns_fwd_plane2_fits(N, A.team) && T.fwd_plane == 2) A.plane = 2;
+  };
+  pick_planes();
+  if (A.team > 1) {
+    // every workgroup of every team must be resident at once: the kernel's own occupancy at this launch configuration says
+    // how many a CU holds (not just the CU count); a configuration that does not fit runs one workgroup per group instead
+    const int per_cu = gns_fwd_blocks_per_cu(d, h, cfg->multiple_phi, A, waves * 64);
+    if ((long long)per_cu * device().ncu < A.G * A.team) {
+      A.team = 1;
+      waves = T.fwd_waves;
+      A.part_idx = gns_part_index(waves);
+      pick_planes();
+    }
+  }
+  // (the counters - and the status word gns_team_status reads - are zeroed whenever this batch size is one that may use teams)
+  if (team0 > 1 && hipMemsetAsync(A.team_ws, 0, (size_t)L.groups * GNS_TEAM_CTR_BYTES, st) != hipSuccess) return GNS_ELAUNCH;
+  record_forward(1, waves, A.plane, A.team, -1);
+  prof_mark(0, true, st);
+  rc = gns_launch_forward(d, h, cfg->multiple_phi, A, waves * 64, st);
+  prof_mark(0, false, st);
+  return rc;
+}
+
+// The split backward (bwd_variant 4) of a lane-per-grid forward: one phys + sweep kernel sequence per reverse step, then the reduction.
+int split_backward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLayout& L, const GnsBwdsLayout& S, const char* fw,
+                   char* bw, const int* topo_dev, const int* group_topo, const int* slot_grid, const float* params,
+                   const void* packed_inputs, int64_t Bt, const float* grad_total, const float* grad_last, const float* grad_v,
+                   const float* grad_theta, float* grad_params, hipStream_t st, const IgradOut* ig = nullptr) {
+  const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
+  int rc;
+  GnsBwdsArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.topo = topo_dev; A.group_topo = group_topo; A.slot_grid = slot_grid;
+  A.pt = (const float*)(fw + L.off_pt); A.pn = (const float*)(fw + L.off_pn);
+  A.in = packed_inputs ? (const float*)packed_inputs : (const float*)(fw + L.off_in);
+  A.state = (const float*)(fw + L.off_state); A.lam = (const float*)(fw + L.off_lam); A.msg = (const float*)(fw + L.off_msg);
+  A.g_total = grad_total; A.g_last = grad_last; A.g_v = grad_v; A.g_theta = grad_theta;
+  A.adj = (float*)(bw + S.off_adj); A.slots = (float*)(bw + S.off_slots); A.slab = (float*)(bw + S.off_slab);
+  fill_backward_families(A, fam);
+  A.Bt = Bt; A.G = S.groups; A.slab_floats = S.slab_floats; A.N = N; A.E = E; A.K = K;
+  A.C = S.C; A.part_idx = gns_part_index(S.C); A.R = S.R;
+  A.RB = (int)(1 + S.mq); A.RBA = (int)S.adj_rows;
+  A.mode = cfg->multiple_phi ? tuning().bwds_mode : 2;          // the single phi is reversed after all three L nets: bus-major
+  const size_t lds = gns_bwds_phys_lds(N, &A.use_plane);
+  if (ig) {
+    A.igrad = ig->buf;
+    if (hipMemsetAsync(A.igrad, 0, ig->bytes, st) != hipSuccess) return GNS_ELAUNCH;
+  }
+  record_backward(4, 1, A.mode, A.C, A.R, -1);
+  prof_mark(1, true, st);
+  for (int k = K - 1; k >= 0; --k) {
+    A.k = k;
+    A.gwk = loss_weight(cfg, k);
+    rc = gns_launch_bwds_phys(A, lds, st);
+    if (rc != GNS_OK) return rc;
+    if (ig) {
+      rc = gns_launch_bwds_igrad_phys(A, st);
+      if (rc != GNS_OK) return rc;
+    }
+    rc = gns_launch_bwds_sweep(d, h, cfg->multiple_phi, A, st);
+    if (rc != GNS_OK) return rc;
+  }
+  if (ig && (ig->buses || ig->lines || ig->gens)) {
+    rc = gns_launch_bwds_igrad_unpack(A, ig->in_buses, ig->in_lines, ig->in_gens, cfg->n_gen, ig->buses, ig->lines, ig->gens, st);
+    if (rc != GNS_OK) return rc;
+  }
+  prof_mark(1, false, st);
+  if (!grad_params) return GNS_OK;
+  return gns_launch_reduce(A.slab, (float*)(bw + S.off_part), (float*)(bw + S.off_tmp), params, grad_params, S.nslab, S.slab_floats,
+                           fam, K, d, h, st);
+}
+}  // namespace
+
+// ---- entry points -----------------------------------------------------------------------------------------------------------------
+// Explicit configuration (include/gns_hip.h).  The environment variables of the same meaning only seed the defaults.
+extern "C" int gns_set_option(const char* name, int value) {
+  if (!name) return GNS_EINVAL;
+  for (const GnsOption& o : g_options)
+    if (!std::strcmp(name, o.name)) {
+      if (!o.accepts(value)) return GNS_EINVAL;
+      tuning().*o.member = value;
+      return GNS_OK;
+    }
+  return GNS_EINVAL;                     // (unknown, or one of the read-only "last.*" names)
+}
+extern "C" int gns_get_option(const char* name, int* value) {
+  if (!name || !value) return GNS_EINVAL;
+  for (const GnsOption& o : g_options)
+    if (!std::strcmp(name, o.name)) { *value = tuning().*o.member; return GNS_OK; }
+  if (!std::strncmp(name, "last.", 5))
+    for (const GnsLastName& l : g_last_names)
+      if (!std::strcmp(name + 5, l.name)) { *value = g_last.*l.member; return GNS_OK; }
+  return GNS_EINVAL;
 }
 
 extern "C" int gns_profile_enable(int capacity) {
@@ -313,62 +533,51 @@ extern "C" int gns_param_count(const gns_config* cfg, int64_t* count) {
 }
 
 extern "C" int gns_config_supported(const gns_config* cfg) {
-  if (check_cfg(cfg) != GNS_OK) return 0;
-  return dims_supported(cfg->latent_dim, cfg->hidden_dim) && cfg->K <= GNS_MAX_K ? 1 : 0;
+  GnsCall c;
+  return resolve(cfg, true, CAP_K, &c) == GNS_OK ? 1 : 0;
 }
 
 extern "C" int gns_workspace_bytes(const gns_config* cfg, int64_t Bt, int save_state, size_t* fwd_bytes, size_t* bwd_bytes) {
-  int rc = check_cfg(cfg);
+  GnsCall c;
+  const int rc = resolve(cfg, Bt > 0, ANY_K, &c);
   if (rc != GNS_OK) return rc;
-  if (Bt <= 0) return GNS_EINVAL;
-  const gns_config* model = cfg; gns_config kcfg_;
-  if (!kernel_config(model, &kcfg_)) return GNS_EUNSUPPORTED;
-  cfg = &kcfg_; (void)model;
-  GnsFwdLayout L;
-  gns_fwd_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, save_state, &L);
-  const int P = (save_state && save_state != GNS_SAVE_IGRAD) ? gw_train_pack(cfg, Bt) : 0;
-  if (save_state == GNS_SAVE_IGRAD) {                                  // lane-per-grid forward + split backward with input gradients
-    if (!device().split_ready || !gns_bwds_supported(cfg->latent_dim, cfg->hidden_dim, cfg->multiple_phi)) return GNS_EUNSUPPORTED;
+  const gns_config* k = &c.k;
+  const GnsRoute R = route(k, Bt, save_state);
+  const GnsFwdLayout L = fwd_layout(k, Bt, save_state);
+  switch (R.path) {
+  case PATH_LANE_IGRAD:                                                // lane-per-grid forward + split backward with input gradients
+    if (!split_available(k)) return GNS_EUNSUPPORTED;
     if (fwd_bytes) *fwd_bytes = L.total + GNS_IGRAD_MARK_BYTES;
-    if (bwd_bytes) {
-      GnsBwdsLayout S;
-      gns_bwds_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
-      *bwd_bytes = S.total + igrad_bytes(cfg, Bt);
-    }
+    if (bwd_bytes) *bwd_bytes = bwds_layout(k, Bt).total + igrad_bytes(k, Bt);
     return GNS_OK;
-  }
-  if (P > 0) {
-    const GwTrainLayout G = gw_train_layout(cfg, Bt, P);
+  case PATH_GW_TRAIN: {
+    const GwTrainLayout G = gw_train_layout(k, Bt, R.pack);
     if (fwd_bytes) *fwd_bytes = G.fwd_total;
     if (bwd_bytes) *bwd_bytes = G.bwd_total;
     return GNS_OK;
   }
-  if (!save_state && gw_eval_pack(cfg, Bt) > 0) {                      // state on chip, inputs read in place: only the parameter streams
+  case PATH_GW_EVAL:                                                   // state on chip, inputs read in place: only the parameter streams
     if (fwd_bytes) *fwd_bytes = L.off_in;
     if (bwd_bytes) *bwd_bytes = 0;
     return GNS_OK;
+  case PATH_LANE:
+    break;
   }
   if (fwd_bytes) *fwd_bytes = L.total;
   if (bwd_bytes) {
-    GnsBwdLayout B;
-    gns_bwd_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, lane_team(Bt), &B);
-    *bwd_bytes = B.total;
-    if (device().split_ready && gns_bwds_supported(cfg->latent_dim, cfg->hidden_dim, cfg->multiple_phi)) {   // either variant may be asked for later
-      GnsBwdsLayout S;
-      gns_bwds_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
-      if (S.total > *bwd_bytes) *bwd_bytes = S.total;
+    *bwd_bytes = bwd_layout(k, Bt, lane_team(Bt)).total;
+    if (split_available(k)) {                                          // either variant may be asked for later
+      const size_t split = bwds_layout(k, Bt).total;
+      if (split > *bwd_bytes) *bwd_bytes = split;
     }
   }
   return GNS_OK;
 }
 
 extern "C" int gns_uses_packed_inputs(const gns_config* cfg, int64_t Bt, int save_state) {
-  if (check_cfg(cfg) != GNS_OK || Bt <= 0) return 0;
-  const gns_config* model = cfg; gns_config kcfg_;
-  if (!kernel_config(model, &kcfg_)) return 0;
-  cfg = &kcfg_; (void)model;
-  if (save_state == GNS_SAVE_IGRAD) return 1;
-  return (save_state ? gw_train_pack(cfg, Bt) : gw_eval_pack(cfg, Bt)) > 0 ? 0 : 1;
+  GnsCall c;
+  if (resolve(cfg, Bt > 0, ANY_K, &c) != GNS_OK) return 0;
+  return route(&c.k, Bt, save_state).lane() ? 1 : 0;
 }
 
 // Did a team of workgroups give up at a barrier during the gns_forward that used this workspace?  (Teams: lane-per-grid kernels on a
@@ -379,40 +588,24 @@ extern "C" int gns_uses_packed_inputs(const gns_config* cfg, int64_t Bt, int sav
 // Byte offset of that status word inside the forward workspace, or (size_t)-1 in *offset when this (cfg, Bt, save_state) runs
 // without teams.  (Tests inject a failure through it; the host wrapper asks it whether a status has to be checked at all.)
 extern "C" int gns_team_status_offset(const gns_config* cfg, int64_t Bt, int save_state, size_t* offset) {
-  int rc = check_cfg(cfg);
+  GnsCall c;
+  const int rc = resolve(cfg, offset && Bt > 0, ANY_K, &c);
   if (rc != GNS_OK) return rc;
-  if (!offset || Bt <= 0) return GNS_EINVAL;
-  const gns_config* model = cfg; gns_config kcfg_;
-  if (!kernel_config(model, &kcfg_)) return GNS_EUNSUPPORTED;
-  cfg = &kcfg_; (void)model;
-  *offset = (size_t)-1;
-  if (lane_team(Bt) <= 1) return GNS_OK;
-  if (save_state != GNS_SAVE_IGRAD && (save_state ? gw_train_pack(cfg, Bt) : gw_eval_pack(cfg, Bt)) > 0) return GNS_OK;   // the grid-per-workgroup kernels have no teams
-  GnsFwdLayout L;
-  gns_fwd_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, save_state, &L);
-  *offset = L.off_team + GNS_TEAM_STATUS_WORD * 4;
+  *offset = route(&c.k, Bt, save_state).lane() ? team_word_offset(&c.k, Bt, save_state) : (size_t)-1;   // the grid-per-workgroup kernels have no teams
   return GNS_OK;
 }
 
 extern "C" int gns_team_status(const gns_config* cfg, int64_t Bt, const void* fwd_workspace, size_t fwd_workspace_bytes, int save_state,
                                int* status, void* stream) {
-  int rc = check_cfg(cfg);
+  GnsCall c;
+  const int rc = resolve(cfg, status && fwd_workspace && Bt > 0, ANY_K, &c);
   if (rc != GNS_OK) return rc;
-  if (!status || !fwd_workspace || Bt <= 0) return GNS_EINVAL;
-  const gns_config* model = cfg; gns_config kcfg_;
-  if (!kernel_config(model, &kcfg_)) return GNS_EUNSUPPORTED;
-  cfg = &kcfg_; (void)model;
   *status = 0;
-  if (lane_team(Bt) <= 1) return GNS_OK;
-  if (save_state != GNS_SAVE_IGRAD && (save_state ? gw_train_pack(cfg, Bt) : gw_eval_pack(cfg, Bt)) > 0) return GNS_OK;   // the grid-per-workgroup kernels have no teams
-  GnsFwdLayout L;
-  gns_fwd_layout(cfg->n_bus, cfg->n_line, cfg->latent_dim, cfg->hidden_dim, cfg->K, cfg->multiple_phi, Bt, save_state, &L);
-  if (fwd_workspace_bytes < L.total) return GNS_ESIZE;
-  unsigned word = 0;
-  if (hipMemcpyAsync(&word, (const char*)fwd_workspace + L.off_team + GNS_TEAM_STATUS_WORD * 4, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-      hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { (void)hipGetLastError(); return GNS_ELAUNCH; }
-  *status = word ? 1 : 0;
-  return GNS_OK;
+  size_t total = 0;
+  const size_t off = route(&c.k, Bt, save_state).lane() ? team_word_offset(&c.k, Bt, save_state, &total) : (size_t)-1;
+  if (off == (size_t)-1) return GNS_OK;
+  if (fwd_workspace_bytes < total) return GNS_ESIZE;
+  return read_team_word(fwd_workspace, off, stream, status);
 }
 
 extern "C" int gns_prepack_bytes(const gns_config* cfg, int64_t Bt, size_t* bytes) {
@@ -435,148 +628,35 @@ extern "C" int gns_prepack(const gns_config* cfg, const void* topo_dev, const fl
                                 (Bt + GNS_LANES - 1) / GNS_LANES, (hipStream_t)stream);
 }
 
-// The lane-per-grid forward of Bt input grids in L.groups 64-grid groups (parameters and inputs already packed into `ws`).  group_topo /
-// slot_grid: NULL for a one-topology batch (lane l of group g computes grid 64 g + l), else the tables of a grouped call.
-static int lane_forward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLayout& L, char* ws, float* pt, float* pin,
-                        const int* topo_dev, const int* group_topo, const int* slot_grid, int64_t Bt, float* v, float* theta,
-                        float* total_loss, float* last_loss, int save_state, hipStream_t st) {
-  const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
-  const GnsTuning& T = tuning();
-  int rc;
-  GnsFwdArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.topo = topo_dev; A.group_topo = group_topo; A.slot_grid = slot_grid; A.pt = pt; A.in = pin;
-  A.state = (float*)(ws + L.off_state); A.lam = (float*)(ws + L.off_lam); A.msg = (float*)(ws + L.off_msg);
-  A.v_out = v; A.theta_out = theta; A.total_out = total_loss; A.last_out = last_loss;
-  for (int i = 0; i < fam.nfam; ++i) { A.t_off[i] = fam.t_off[i]; A.t_sz[i] = fam.t_sz[i]; }
-  for (int k = 0; k < K; ++k) A.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));   // main.py:198
-  A.Bt = Bt; A.G = L.groups; A.N = N; A.E = E; A.K = K; A.save = save_state ? 1 : 0;
-  const int team0 = lane_team(L.groups * GNS_LANES);     // (= lane_team(Bt) for a one-topology batch)
-  A.team = team0;
-  A.team_ws = (unsigned char*)(ws + L.off_team);
-  int waves = T.fwd_waves;
-  while (waves * A.team > GNS_MAXP) waves /= 2;
-  A.part_idx = gns_part_index(waves * A.team);
-  auto pick_planes = [&]() {
-    A.plane = (device().fwd_ready && gns_fwd_plane_fits(N, A.team) && T.fwd_plane) ? 1 : 0;
-    if (A.plane && gns_fwd_plane2_fits(N, A.team) && T.fwd_plane == 2) A.plane = 2;
-  };
-  pick_planes();
-  if (A.team > 1) {
-    // every workgroup of every team must be resident at once: the kernel's own occupancy at this launch configuration says
-    // how many a CU holds (not just the CU count); a configuration that does not fit runs one workgroup per group instead
-    const int per_cu = gns_fwd_blocks_per_cu(d, h, cfg->multiple_phi, A, waves * 64);
-    if ((long long)per_cu * device().ncu < A.G * A.team) {
-      A.team = 1;
-      waves = T.fwd_waves;
-      A.part_idx = gns_part_index(waves);
-      pick_planes();
-    }
-  }
-  // (the counters - and the status word gns_team_status reads - are zeroed whenever this batch size is one that may use teams)
-  if (team0 > 1 && hipMemsetAsync(A.team_ws, 0, (size_t)L.groups * GNS_TEAM_CTR_BYTES, st) != hipSuccess) return GNS_ELAUNCH;
-  record_forward(1, waves, A.plane, A.team, -1);
-  prof_mark(0, true, st);
-  rc = gns_launch_forward(d, h, cfg->multiple_phi, A, waves * 64, st);
-  prof_mark(0, false, st);
-  return rc;
-}
-
-// The split backward (bwd_variant 4) of a lane-per-grid forward: one phys + sweep kernel sequence per reverse step, then the reduction.
-static int split_backward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLayout& L, const GnsBwdsLayout& S, const char* fw,
-                          char* bw, const int* topo_dev, const int* group_topo, const int* slot_grid, const float* params,
-                          const void* packed_inputs, int64_t Bt, const float* grad_total, const float* grad_last, const float* grad_v,
-                          const float* grad_theta, float* grad_params, hipStream_t st, const IgradOut* ig = nullptr) {
-  const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
-  int rc;
-  GnsBwdsArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.topo = topo_dev; A.group_topo = group_topo; A.slot_grid = slot_grid;
-  A.pt = (const float*)(fw + L.off_pt); A.pn = (const float*)(fw + L.off_pn);
-  A.in = packed_inputs ? (const float*)packed_inputs : (const float*)(fw + L.off_in);
-  A.state = (const float*)(fw + L.off_state); A.lam = (const float*)(fw + L.off_lam); A.msg = (const float*)(fw + L.off_msg);
-  A.g_total = grad_total; A.g_last = grad_last; A.g_v = grad_v; A.g_theta = grad_theta;
-  A.adj = (float*)(bw + S.off_adj); A.slots = (float*)(bw + S.off_slots); A.slab = (float*)(bw + S.off_slab);
-  for (int i = 0; i < fam.nfam; ++i) {
-    A.t_off[i] = fam.t_off[i]; A.t_sz[i] = fam.t_sz[i]; A.n_off[i] = fam.n_off[i]; A.n_sz[i] = fam.n_sz[i];
-    A.g_off[i] = fam.g_off[i]; A.g_sz[i] = fam.g_sz[i];
-  }
-  A.Bt = Bt; A.G = S.groups; A.slab_floats = S.slab_floats; A.N = N; A.E = E; A.K = K;
-  A.C = S.C; A.part_idx = gns_part_index(S.C); A.R = S.R;
-  A.RB = (int)(1 + S.mq); A.RBA = (int)S.adj_rows;
-  A.mode = cfg->multiple_phi ? tuning().bwds_mode : 2;          // the single phi is reversed after all three L nets: bus-major
-  const size_t lds = gns_bwds_phys_lds(N, &A.use_plane);
-  if (ig) {
-    A.igrad = ig->buf;
-    if (hipMemsetAsync(A.igrad, 0, ig->bytes, st) != hipSuccess) return GNS_ELAUNCH;
-  }
-  record_backward(4, 1, A.mode, A.C, A.R, -1);
-  prof_mark(1, true, st);
-  for (int k = K - 1; k >= 0; --k) {
-    A.k = k;
-    A.gwk = (float)std::pow((double)cfg->gamma, (double)(K - k));
-    rc = gns_launch_bwds_phys(A, lds, st);
-    if (rc != GNS_OK) return rc;
-    if (ig) {
-      rc = gns_launch_bwds_igrad_phys(A, st);
-      if (rc != GNS_OK) return rc;
-    }
-    rc = gns_launch_bwds_sweep(d, h, cfg->multiple_phi, A, st);
-    if (rc != GNS_OK) return rc;
-  }
-  if (ig && (ig->buses || ig->lines || ig->gens)) {
-    rc = gns_launch_bwds_igrad_unpack(A, ig->in_buses, ig->in_lines, ig->in_gens, cfg->n_gen, ig->buses, ig->lines, ig->gens, st);
-    if (rc != GNS_OK) return rc;
-  }
-  prof_mark(1, false, st);
-  if (!grad_params) return GNS_OK;
-  return gns_launch_reduce(A.slab, (float*)(bw + S.off_part), (float*)(bw + S.off_tmp), params, grad_params, S.nslab, S.slab_floats,
-                           fam, K, d, h, st);
-}
-
 extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const float* params, const float* buses,
                            const float* lines, const float* generators, int64_t Bt, const void* packed_inputs, float* v, float* theta,
                            float* total_loss, float* last_loss, void* workspace, size_t workspace_bytes, int save_state,
                            void* stream) {
-  int rc = check_cfg(cfg);
+  GnsCall c;
+  int rc = resolve(cfg, topo_dev && params && buses && lines && generators && v && theta && total_loss && last_loss && workspace && Bt > 0,
+                   CAP_K, &c);
   if (rc != GNS_OK) return rc;
-  if (!topo_dev || !params || !buses || !lines || !generators || !v || !theta || !total_loss || !last_loss || !workspace || Bt <= 0)
-    return GNS_EINVAL;
-  const gns_config* model = cfg; gns_config kcfg_;
-  if (!kernel_config(model, &kcfg_) || cfg->K > GNS_MAX_K) return GNS_EUNSUPPORTED;
-  cfg = &kcfg_;                          // the kernel's dims from here on; the model's only lay out the flat parameters
+  cfg = &c.k;                            // the kernel's dims from here on; the model's only lay out the flat parameters
   const int N = cfg->n_bus, E = cfg->n_line, Gn = cfg->n_gen, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
-  GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
+  const GnsFamilies fam = c.families();
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
-  if (const int TP = (save_state && save_state != GNS_SAVE_IGRAD) ? gw_train_pack(cfg, Bt) : 0) {   // training-mode forward of the grid-per-workgroup pair
-    const GwTrainLayout GL = gw_train_layout(cfg, Bt, TP);
+  const GnsRoute R = route(cfg, Bt, save_state);
+  if (R.path == PATH_GW_TRAIN) {                   // training-mode forward of the grid-per-workgroup pair
+    const GwTrainLayout GL = gw_train_layout(cfg, Bt, R.pack);
     if (workspace_bytes < GL.fwd_total) return GNS_ESIZE;
     float* gpt = (float*)(ws + GL.off_pt);
     float* gpn = (float*)(ws + GL.off_pn);
     rc = gns_launch_pack_params(params, gpt, gpn, fam, K, d, h, st);
     if (rc != GNS_OK) return rc;
-    GnsGwFwdArgs G;
-    std::memset(&G, 0, sizeof(G));
-    G.topo = (const int*)topo_dev; G.pt = gpt; G.buses = buses; G.lines = lines; G.gens = generators;
-    G.v_out = v; G.theta_out = theta; G.total_out = total_loss; G.last_out = last_loss;
-    char* sv = ws + GL.off_save;
-    G.sv_state = (float*)(sv + GL.sv.off_state); G.sv_S = (float*)(sv + GL.sv.off_S); G.sv_lam = (float*)(sv + GL.sv.off_lam);
-    for (int i = 0; i < fam.nfam; ++i) { G.t_off[i] = fam.t_off[i]; G.t_sz[i] = fam.t_sz[i]; }
-    for (int k = 0; k < K; ++k) G.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));
-    G.Bt = Bt; G.N = N; G.E = E; G.Gn = Gn; G.K = K; G.save = 1; G.P = TP; G.WPG = ((N > E ? N : E) + 63) / 64;
-    record_forward(2, -1, -1, -1, TP);
-    prof_mark(0, true, st);
-    rc = gns_gw_launch_forward(d, h, cfg->multiple_phi, G, st);
-    prof_mark(0, false, st);
-    return rc;
+    return gw_forward(cfg, fam, topo_dev, gpt, buses, lines, generators, Bt, v, theta, total_loss, last_loss, R.pack, ws + GL.off_save,
+                      &GL.sv, st);
   }
-  GnsFwdLayout L;
-  gns_fwd_layout(N, E, d, h, K, cfg->multiple_phi, Bt, save_state, &L);
-  if (workspace_bytes < ((!save_state && gw_eval_pack(cfg, Bt) > 0) ? L.off_in : L.total)) return GNS_ESIZE;
-  if (save_state == GNS_SAVE_IGRAD) {                  // saved for gns_backward_inputs: the mark it checks, behind the layout
+  const GnsFwdLayout L = fwd_layout(cfg, Bt, save_state);
+  if (workspace_bytes < (R.path == PATH_GW_EVAL ? L.off_in : L.total)) return GNS_ESIZE;
+  if (R.path == PATH_LANE_IGRAD) {                 // saved for gns_backward_inputs: the mark it checks, behind the layout
     if (workspace_bytes < L.total + GNS_IGRAD_MARK_BYTES) return GNS_ESIZE;
-    if (!device().split_ready || !gns_bwds_supported(d, h, cfg->multiple_phi)) return GNS_EUNSUPPORTED;
+    if (!split_available(cfg)) return GNS_EUNSUPPORTED;
     if (hipMemsetD32Async((hipDeviceptr_t)(ws + L.total), GNS_IGRAD_MARK, 1, st) != hipSuccess) return GNS_ELAUNCH;
   }
   float* pt = (float*)(ws + L.off_pt);
@@ -585,23 +665,8 @@ extern "C" int gns_forward(const gns_config* cfg, const void* topo_dev, const fl
   rc = gns_launch_pack_params(params, pt, pn, fam, K, d, h, st);
   if (rc != GNS_OK) return rc;
   // Evaluation (nothing saved for a backward): the grid-per-workgroup mapping keeps the whole state on chip.
-  {
-    const int P = save_state ? 0 : gw_eval_pack(cfg, Bt);
-    if (P > 0) {
-      GnsGwFwdArgs G;
-      std::memset(&G, 0, sizeof(G));
-      G.topo = (const int*)topo_dev; G.pt = pt; G.buses = buses; G.lines = lines; G.gens = generators;
-      G.v_out = v; G.theta_out = theta; G.total_out = total_loss; G.last_out = last_loss;
-      for (int i = 0; i < fam.nfam; ++i) { G.t_off[i] = fam.t_off[i]; G.t_sz[i] = fam.t_sz[i]; }
-      for (int k = 0; k < K; ++k) G.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));   // main.py:198
-      G.Bt = Bt; G.N = N; G.E = E; G.Gn = Gn; G.K = K; G.save = 0; G.P = P; G.WPG = ((N > E ? N : E) + 63) / 64;
-      record_forward(2, -1, -1, -1, P);
-      prof_mark(0, true, st);
-      rc = gns_gw_launch_forward(d, h, cfg->multiple_phi, G, st);
-      prof_mark(0, false, st);
-      return rc;
-    }
-  }
+  if (R.path == PATH_GW_EVAL)
+    return gw_forward(cfg, fam, topo_dev, pt, buses, lines, generators, Bt, v, theta, total_loss, last_loss, R.pack, nullptr, nullptr, st);
   if (packed_inputs) pin = (float*)packed_inputs;                  // a resident batch packed once by gns_prepack: nothing to redo
   else {
     rc = gns_launch_pack_inputs((const int*)topo_dev, buses, lines, generators, pin, N, E, Gn, Bt, L.groups, st);
@@ -615,21 +680,21 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
                             const void* fwd_workspace, size_t fwd_workspace_bytes, const float* grad_total,
                             const float* grad_last, const float* grad_v, const float* grad_theta, float* grad_params,
                             void* bwd_workspace, size_t bwd_workspace_bytes, void* stream) {
-  int rc = check_cfg(cfg);
+  GnsCall c;
+  int rc = resolve(cfg, topo_dev && params && fwd_workspace && grad_params && bwd_workspace && Bt > 0, CAP_K, &c);
   if (rc != GNS_OK) return rc;
-  if (!topo_dev || !params || !fwd_workspace || !grad_params || !bwd_workspace || Bt <= 0) return GNS_EINVAL;
-  const gns_config* model = cfg; gns_config kcfg_;
-  if (!kernel_config(model, &kcfg_) || cfg->K > GNS_MAX_K) return GNS_EUNSUPPORTED;
-  cfg = &kcfg_;                          // the kernel's dims from here on; the model's only lay out the flat parameters and their gradient
+  cfg = &c.k;                            // the kernel's dims from here on; the model's only lay out the flat parameters and their gradient
   const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
-  if (const int TP = gw_train_pack(cfg, Bt)) {                            // the pair of the grid-per-workgroup training forward
+  hipStream_t st = (hipStream_t)stream;
+  const char* fw = (const char*)fwd_workspace;
+  char* bw = (char*)bwd_workspace;
+  const GnsRoute R = route(cfg, Bt, 1);            // (no save_state argument: decided as for the forward that saved for this call)
+  if (R.path == PATH_GW_TRAIN) {                   // the pair of the grid-per-workgroup training forward
+    const int TP = R.pack;
     if (!buses || !lines || !generators) return GNS_EINVAL;
     const GwTrainLayout GL = gw_train_layout(cfg, Bt, TP);
     if (fwd_workspace_bytes < GL.fwd_total || bwd_workspace_bytes < GL.bwd_total) return GNS_ESIZE;
-    GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
-    hipStream_t st = (hipStream_t)stream;
-    const char* fw = (const char*)fwd_workspace;
-    char* bw = (char*)bwd_workspace;
+    const GnsFamilies fam = c.families();
     if (hipMemsetAsync(bw + GL.off_slab, 0, (size_t)GL.nslab * GL.slab_floats * 4, st) != hipSuccess) return GNS_ELAUNCH;
     GnsGwBwdArgs G;
     std::memset(&G, 0, sizeof(G));
@@ -640,11 +705,8 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
     G.sv_state = (const float*)(sv + GL.sv.off_state); G.sv_S = (const float*)(sv + GL.sv.off_S); G.sv_lam = (const float*)(sv + GL.sv.off_lam);
     G.g_total = grad_total; G.g_last = grad_last; G.g_v = grad_v; G.g_theta = grad_theta;
     G.slab = (float*)(bw + GL.off_slab);
-    for (int i = 0; i < fam.nfam; ++i) {
-      G.t_off[i] = fam.t_off[i]; G.t_sz[i] = fam.t_sz[i]; G.n_off[i] = fam.n_off[i]; G.n_sz[i] = fam.n_sz[i];
-      G.g_off[i] = fam.g_off[i]; G.g_sz[i] = fam.g_sz[i];
-    }
-    for (int k = 0; k < K; ++k) G.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));
+    fill_backward_families(G, fam);
+    fill_loss_weights(G, cfg);
     G.Bt = Bt; G.slab_floats = GL.slab_floats; G.N = N; G.E = E; G.Gn = cfg->n_gen; G.K = K;
     G.P = TP; G.WPG = gns_gw_backward_wpg(N);
     record_backward(0, -1, -1, -1, -1, TP);
@@ -655,24 +717,17 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
     return gns_launch_reduce(G.slab, (float*)(bw + GL.off_part), (float*)(bw + GL.off_tmp), params, grad_params, GL.nslab,
                              GL.slab_floats, fam, K, d, h, st);
   }
-  GnsFwdLayout L;
-  gns_fwd_layout(N, E, d, h, K, cfg->multiple_phi, Bt, 1, &L);
+  const GnsFwdLayout L = fwd_layout(cfg, Bt, 1);
   if (use_split_backward(cfg)) {
-    GnsBwdsLayout S;
-    gns_bwds_layout(N, E, d, h, K, cfg->multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
+    const GnsBwdsLayout S = bwds_layout(cfg, Bt);
     if (fwd_workspace_bytes < L.total || bwd_workspace_bytes < S.total) return GNS_ESIZE;
-    GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
-    return split_backward(cfg, fam, L, S, (const char*)fwd_workspace, (char*)bwd_workspace, (const int*)topo_dev, nullptr, nullptr, params,
-                          packed_inputs, Bt, grad_total, grad_last, grad_v, grad_theta, grad_params, (hipStream_t)stream);
+    return split_backward(cfg, c.families(), L, S, fw, bw, (const int*)topo_dev, nullptr, nullptr, params, packed_inputs, Bt, grad_total,
+                          grad_last, grad_v, grad_theta, grad_params, st);
   }
-  GnsBwdLayout B;
   const int team = lane_team(Bt);
-  gns_bwd_layout(N, E, d, h, K, cfg->multiple_phi, Bt, team, &B);
+  const GnsBwdLayout B = bwd_layout(cfg, Bt, team);
   if (fwd_workspace_bytes < L.total || bwd_workspace_bytes < B.total) return GNS_ESIZE;
-  GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
-  hipStream_t st = (hipStream_t)stream;
-  const char* fw = (const char*)fwd_workspace;
-  char* bw = (char*)bwd_workspace;
+  const GnsFamilies fam = c.families();
   const int blocks = (int)(B.groups * team < GNS_BWD_MAX_WG ? B.groups * team : GNS_BWD_MAX_WG);
   const long long nslab = (long long)blocks * GNS_BWD_WAVES;
   // the V2 sweep writes every slab entry itself on a workgroup's first group: no 90 MB memset in front of it
@@ -686,11 +741,8 @@ extern "C" int gns_backward(const gns_config* cfg, const void* topo_dev, const f
   A.state = (const float*)(fw + L.off_state); A.lam = (const float*)(fw + L.off_lam); A.msg = (const float*)(fw + L.off_msg);
   A.g_total = grad_total; A.g_last = grad_last; A.g_v = grad_v; A.g_theta = grad_theta;
   A.adj = (float*)(bw + B.off_adj); A.slots = (float*)(bw + B.off_slots); A.slab = (float*)(bw + B.off_slab);
-  for (int i = 0; i < fam.nfam; ++i) {
-    A.t_off[i] = fam.t_off[i]; A.t_sz[i] = fam.t_sz[i]; A.n_off[i] = fam.n_off[i]; A.n_sz[i] = fam.n_sz[i];
-    A.g_off[i] = fam.g_off[i]; A.g_sz[i] = fam.g_sz[i];
-  }
-  for (int k = 0; k < K; ++k) A.gw[k] = (float)std::pow((double)cfg->gamma, (double)(K - k));
+  fill_backward_families(A, fam);
+  fill_loss_weights(A, cfg);
   A.Bt = Bt; A.G = B.groups; A.slab_floats = B.slab_floats; A.N = N; A.E = E; A.K = K;
   A.part_idx = gns_part_index(GNS_BWD_WAVES * team);
   A.team = team; A.team_ws = (unsigned char*)(bw + B.off_team);
@@ -716,18 +768,13 @@ extern "C" int gns_backward_inputs(const gns_config* cfg, const void* topo_dev, 
                                    const float* grad_last, const float* grad_v, const float* grad_theta, float* grad_params,
                                    float* grad_buses, float* grad_lines, float* grad_generators,
                                    void* bwd_workspace, size_t bwd_workspace_bytes, void* stream) {
-  int rc = check_cfg(cfg);
+  GnsCall c;
+  const int rc = resolve(cfg, topo_dev && params && buses && lines && generators && fwd_workspace && bwd_workspace && Bt > 0, CAP_K, &c);
   if (rc != GNS_OK) return rc;
-  if (!topo_dev || !params || !buses || !lines || !generators || !fwd_workspace || !bwd_workspace || Bt <= 0) return GNS_EINVAL;
-  const gns_config* model = cfg; gns_config kcfg_;
-  if (!kernel_config(model, &kcfg_) || cfg->K > GNS_MAX_K) return GNS_EUNSUPPORTED;
-  cfg = &kcfg_;
-  const int N = cfg->n_bus, E = cfg->n_line, K = cfg->K, d = cfg->latent_dim, h = cfg->hidden_dim;
-  if (!device().split_ready || !gns_bwds_supported(d, h, cfg->multiple_phi)) return GNS_EUNSUPPORTED;
-  GnsFwdLayout L;
-  gns_fwd_layout(N, E, d, h, K, cfg->multiple_phi, Bt, 1, &L);
-  GnsBwdsLayout S;
-  gns_bwds_layout(N, E, d, h, K, cfg->multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
+  cfg = &c.k;
+  if (!split_available(cfg)) return GNS_EUNSUPPORTED;
+  const GnsFwdLayout L = fwd_layout(cfg, Bt, 1);
+  const GnsBwdsLayout S = bwds_layout(cfg, Bt);
   if (fwd_workspace_bytes < L.total + GNS_IGRAD_MARK_BYTES) return GNS_EINVAL;       // not a save_state = 2 workspace
   const size_t ib = igrad_bytes(cfg, Bt);
   if (bwd_workspace_bytes < S.total + ib) return GNS_ESIZE;
@@ -736,40 +783,24 @@ extern "C" int gns_backward_inputs(const gns_config* cfg, const void* topo_dev, 
   if (hipMemcpyAsync(&mark, (const char*)fwd_workspace + L.total, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return GNS_ELAUNCH; }
   if (mark != GNS_IGRAD_MARK) return GNS_EINVAL;
-  GnsFamilies fam; gns_families_padded(model->latent_dim, model->hidden_dim, d, h, K, cfg->multiple_phi, &fam);
   IgradOut ig;
   ig.buf = (float*)((char*)bwd_workspace + S.total); ig.bytes = ib;
   ig.in_buses = buses; ig.in_lines = lines; ig.in_gens = generators;
   ig.buses = grad_buses; ig.lines = grad_lines; ig.gens = grad_generators;
-  return split_backward(cfg, fam, L, S, (const char*)fwd_workspace, (char*)bwd_workspace, (const int*)topo_dev, nullptr, nullptr, params,
+  return split_backward(cfg, c.families(), L, S, (const char*)fwd_workspace, (char*)bwd_workspace, (const int*)topo_dev, nullptr, nullptr, params,
                         packed_inputs, Bt, grad_total, grad_last, grad_v, grad_theta, grad_params, st, &ig);
 }
 
 // ---- grouped calls: a batch that mixes topologies, one topology per 64-grid group (include/gns_hip.h) ---------------------------
 // Always the lane-per-grid forward and the split backward, whatever "fwd_mapping", "train_mapping" and "gw_pack" say; their workspace
-// layouts for Bt = 64 G.  The model's cfg in, the kernel's out.
-static int grouped_config(const gns_config* model, int64_t G, gns_config* k) {
-  int rc = check_cfg(model);
-  if (rc != GNS_OK) return rc;
-  if (G <= 0 || G > ((int64_t)1 << 24)) return GNS_EINVAL;
-  if (!kernel_config(model, k) || model->K > GNS_MAX_K) return GNS_EUNSUPPORTED;
-  if (!device().split_ready || !gns_bwds_supported(k->latent_dim, k->hidden_dim, k->multiple_phi)) return GNS_EUNSUPPORTED;
-  return GNS_OK;
-}
+// layouts for Bt = 64 G (grouped_call resolves them).
 
 extern "C" int gns_workspace_bytes_grouped(const gns_config* cfg, int64_t G, int save_state, size_t* fwd_bytes, size_t* bwd_bytes) {
-  gns_config k;
-  const int rc = grouped_config(cfg, G, &k);
+  GnsCall c;
+  const int rc = grouped_call(cfg, G, &c);
   if (rc != GNS_OK) return rc;
-  const int64_t Bt = G * GNS_LANES;
-  GnsFwdLayout L;
-  gns_fwd_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, Bt, save_state, &L);
-  if (fwd_bytes) *fwd_bytes = L.total;
-  if (bwd_bytes) {
-    GnsBwdsLayout S;
-    gns_bwds_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, Bt, device().ncu, tuning().bwds_chunks, &S);
-    *bwd_bytes = save_state ? S.total : 0;
-  }
+  if (fwd_bytes) *fwd_bytes = fwd_layout(&c.k, G * GNS_LANES, save_state).total;
+  if (bwd_bytes) *bwd_bytes = save_state ? bwds_layout(&c.k, G * GNS_LANES).total : 0;
   return GNS_OK;
 }
 
@@ -777,16 +808,16 @@ extern "C" int gns_forward_grouped(const gns_config* cfg, const void* topo_set_d
                                    const int32_t* slot_grid_dev, int64_t G, const float* params, const float* buses, const float* lines,
                                    const float* generators, int64_t Bt, float* v, float* theta, float* total_loss, float* last_loss,
                                    void* workspace, size_t workspace_bytes, int save_state, void* stream) {
-  gns_config k;
-  int rc = grouped_config(cfg, G, &k);
+  GnsCall c;
+  int rc = grouped_call(cfg, G, &c);
   if (rc != GNS_OK) return rc;
   if (!topo_set_dev || !group_topo_dev || !slot_grid_dev || !params || !buses || !lines || !generators || !v || !theta || !total_loss ||
       !last_loss || !workspace || Bt <= 0 || Bt > G * GNS_LANES)
     return GNS_EINVAL;
+  const gns_config& k = c.k;
   const int N = k.n_bus, E = k.n_line, K = k.K, d = k.latent_dim, h = k.hidden_dim;
-  GnsFamilies fam; gns_families_padded(cfg->latent_dim, cfg->hidden_dim, d, h, K, k.multiple_phi, &fam);
-  GnsFwdLayout L;
-  gns_fwd_layout(N, E, d, h, K, k.multiple_phi, G * GNS_LANES, save_state, &L);
+  const GnsFamilies fam = c.families();
+  const GnsFwdLayout L = fwd_layout(&k, G * GNS_LANES, save_state);
   if (workspace_bytes < L.total) return GNS_ESIZE;
   hipStream_t st = (hipStream_t)stream;
   char* ws = (char*)workspace;
@@ -808,35 +839,27 @@ extern "C" int gns_backward_grouped(const gns_config* cfg, const void* topo_set_
                                     const float* grad_total, const float* grad_last, const float* grad_v, const float* grad_theta,
                                     float* grad_params, void* bwd_workspace, size_t bwd_workspace_bytes, void* stream) {
   (void)buses; (void)lines; (void)generators;                    // (the lane-per-grid kernels read the inputs packed by the forward)
-  gns_config k;
-  const int rc = grouped_config(cfg, G, &k);
+  GnsCall c;
+  const int rc = grouped_call(cfg, G, &c);
   if (rc != GNS_OK) return rc;
   if (!topo_set_dev || !group_topo_dev || !slot_grid_dev || !params || !fwd_workspace || !grad_params || !bwd_workspace || Bt <= 0 ||
       Bt > G * GNS_LANES)
     return GNS_EINVAL;
-  const int64_t Bg = G * GNS_LANES;
-  GnsFwdLayout L;
-  gns_fwd_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, Bg, 1, &L);
-  GnsBwdsLayout S;
-  gns_bwds_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, Bg, device().ncu, tuning().bwds_chunks, &S);
+  const GnsFwdLayout L = fwd_layout(&c.k, G * GNS_LANES, 1);
+  const GnsBwdsLayout S = bwds_layout(&c.k, G * GNS_LANES);
   if (fwd_workspace_bytes < L.total || bwd_workspace_bytes < S.total) return GNS_ESIZE;
-  GnsFamilies fam; gns_families_padded(cfg->latent_dim, cfg->hidden_dim, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, &fam);
-  return split_backward(&k, fam, L, S, (const char*)fwd_workspace, (char*)bwd_workspace, (const int*)topo_set_dev, group_topo_dev,
+  return split_backward(&c.k, c.families(), L, S, (const char*)fwd_workspace, (char*)bwd_workspace, (const int*)topo_set_dev, group_topo_dev,
                         slot_grid_dev, params, nullptr, Bt, grad_total, grad_last, grad_v, grad_theta, grad_params, (hipStream_t)stream);
 }
 
 // The team status of a grouped forward.  (gns_team_status answers for the call gns_forward would make for that batch size, which below
 // ~2000 grids is the grid-per-workgroup pair, without teams; a grouped call runs the lane-per-grid forward at every size.)
 extern "C" int gns_team_status_offset_grouped(const gns_config* cfg, int64_t G, int save_state, size_t* offset) {
-  gns_config k;
-  const int rc = grouped_config(cfg, G, &k);
+  GnsCall c;
+  const int rc = grouped_call(cfg, G, &c);
   if (rc != GNS_OK) return rc;
   if (!offset) return GNS_EINVAL;
-  *offset = (size_t)-1;
-  if (lane_team(G * GNS_LANES) <= 1) return GNS_OK;
-  GnsFwdLayout L;
-  gns_fwd_layout(k.n_bus, k.n_line, k.latent_dim, k.hidden_dim, k.K, k.multiple_phi, G * GNS_LANES, save_state, &L);
-  *offset = L.off_team + GNS_TEAM_STATUS_WORD * 4;
+  *offset = team_word_offset(&c.k, G * GNS_LANES, save_state);
   return GNS_OK;
 }
 
@@ -849,11 +872,7 @@ extern "C" int gns_team_status_grouped(const gns_config* cfg, int64_t G, const v
   *status = 0;
   if (off == (size_t)-1) return GNS_OK;
   if (fwd_workspace_bytes < off + 4) return GNS_ESIZE;
-  unsigned word = 0;
-  if (hipMemcpyAsync(&word, (const char*)fwd_workspace + off, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-      hipStreamSynchronize((hipStream_t)stream) != hipSuccess) { (void)hipGetLastError(); return GNS_ELAUNCH; }
-  *status = word ? 1 : 0;
-  return GNS_OK;
+  return read_team_word(fwd_workspace, off, stream, status);
 }
 
 // ---- Adam on the flat parameter buffer (GNS/main.py:290 with the optimiser of main.py:241-243) ---------------------------

@@ -6,6 +6,7 @@ the K-step loop happens in ``libgns_hip.so``.
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -182,75 +183,129 @@ def _workspace(nbytes, dev):
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
 
 
-def _raise_if_team_failed(lib, cfg, Bt, ws, save_state, dev, groups=None):
-    """``groups``: the call was a grouped one (a batch that mixes topologies) in that many 64-grid groups."""
+@functools.lru_cache(maxsize=None)
+def _entry_points(lib, suffix):
+    """A target's five entry points, each as ``call(cfg, *args)`` that raises on a non-zero return code (resolved once, not per launch)."""
+    def checked(name):
+        fn = getattr(lib, name)
+
+        def call(cfg, *args):
+            _check(fn(ctypes.byref(cfg), *args), name)
+        return call
+    return tuple(checked(f'gns_{op}{suffix}') for op in ('workspace_bytes', 'forward', 'backward', 'team_status_offset', 'team_status'))
+
+
+class _Target:
+    """Where a call launches: its entry points, ``blobs`` (the launch arguments between cfg and the parameters, raw addresses whose
+    owners the target holds as late as the backward) and ``count`` (what the sizing queries take after cfg)."""
+
+    def __init__(self, lib, suffix, blobs, count):
+        self.workspace_bytes, self.forward, self.backward, self.team_status_offset, self.team_status = _entry_points(lib, suffix)
+        self.blobs, self.count = blobs, count
+
+
+class _PlainTarget(_Target):
+    """One ``_Topology`` for the whole batch of ``Bt`` grids: ``gns_forward`` / ``gns_backward``, whichever kernels the library picks
+    for the batch size.  The lane-per-grid kernels take their inputs packed (``packed``: None, or the cached / resident copy)."""
+    persistent_backward = True           # the opt-in backward variants 1-3 run in teams (checked after the launch)
+
+    def __init__(self, lib, topo, Bt):
+        super().__init__(lib, '', (topo.blob.data_ptr(),), Bt)
+        self.topo = topo
+
+    def save_state(self, want_grad):
+        return int(want_grad)
+
+    def packed_inputs(self, mod, lib, cfg, buses, lines, gens, stream, save):
+        """(the packed copy to keep alive, the argument tuple it contributes after Bt)"""
+        packed = mod._packed_inputs(lib, cfg, self.topo, buses, lines, gens, stream, save)
+        return packed, (_ptr(packed),)
+
+
+class _GroupedTarget(_Target):
+    """A batch that mixes topologies, one per 64-grid group (``_TopologyGroups``): the grouped entry points, always the lane-per-grid
+    forward and the split backward; they pack the inputs themselves.  Outputs and upstream gradients are in input order."""
+    persistent_backward = False
+
+    def __init__(self, lib, plan):
+        super().__init__(lib, '_grouped', (plan.topo_set.data_ptr(), plan.group_topo.data_ptr(), plan.slot_grid.data_ptr(), plan.groups),
+                         plan.groups)
+        self.plan = plan
+
+    def save_state(self, want_grad):
+        assert want_grad != 2, 'GNS.forward refuses input gradients for a mixed batch'
+        return int(bool(want_grad))
+
+    def packed_inputs(self, mod, lib, cfg, buses, lines, gens, stream, save):
+        return None, ()
+
+
+def _raise_if_team_failed(target, cfg, ws, save_state, dev):
     st = ctypes.c_int()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if groups is None:
-            _check(lib.gns_team_status(ctypes.byref(cfg), Bt, ws.data_ptr(), ws.numel(), int(save_state), ctypes.byref(st), stream),
-                   'gns_team_status')
-        else:
-            _check(lib.gns_team_status_grouped(ctypes.byref(cfg), groups, ws.data_ptr(), ws.numel(), int(save_state), ctypes.byref(st),
-                                               stream), 'gns_team_status_grouped')
+        target.team_status(cfg, target.count, ws.data_ptr(), ws.numel(), int(save_state), ctypes.byref(st),
+                           torch.cuda.current_stream(dev).cuda_stream)
     if st.value:
         raise GNSError('a team of workgroups gave up at a barrier: a kernel of another stream or process held a partner\'s compute unit, '
                        'so the losses of this call are NaN and no gradient was computed from them.  Teams need the device to themselves: '
                        'opf_graph_neural_solver_amd.set_option("team", 1) runs one workgroup per 64-grid group instead')
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 class _GNSFunction(torch.autograd.Function):
+    """The fused forward and its backward on a ``_Target``."""
+
     @staticmethod
-    def forward(ctx, mod, topo, want_grad, buses, lines, gens, *params):
+    def forward(ctx, mod, target, want_grad, buses, lines, gens, *params):
         lib = load_library()
         Bt, N = buses.shape[0], buses.shape[1]
         cfg = mod._config(N, lines.shape[1], gens.shape[1])
         dev = buses.device
         need_grad = bool(want_grad)                     # evaluation (torch.no_grad()) keeps 2 state slots and saves nothing for a backward
-        save = int(want_grad)                           # 0 evaluation, 1 saved for a backward, 2 saved for one that returns input gradients
+        save = target.save_state(want_grad)             # 0 evaluation, 1 saved for a backward, 2 saved for one that returns input gradients
         ctx.set_materialize_grads(False)                # unused outputs (v, theta, last_loss) arrive as None in backward, not as zero-filled tensors
-        fwd_b, bwd_b = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(lib.gns_workspace_bytes(ctypes.byref(cfg), Bt, save, ctypes.byref(fwd_b), ctypes.byref(bwd_b)),
-               'gns_workspace_bytes')
-        ws = _workspace(fwd_b.value, dev)
-        v = torch.empty((Bt, N), dtype=torch.float32, device=dev)
-        theta = torch.empty_like(v)
-        total = torch.empty(Bt, dtype=torch.float32, device=dev)
-        last = torch.empty_like(total)
+        fwd_b, bwd_b, off = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
         flat = mod._exec_flat(dev)                       # the parameters themselves, or their device mirror for a CPU-resident model
-        with torch.cuda.device(dev):                     # the launch must land on the tensors' device, whatever the current device is
+        # The launch must land on the tensors' device, whatever the current device is; and the sizing and offset queries are answered
+        # from the library's state of the current device (its CU count, what it could set up), so they are asked under it too.
+        with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            packed = mod._packed_inputs(lib, cfg, topo, buses, lines, gens, stream, save)
-            _check(lib.gns_forward(ctypes.byref(cfg), topo.blob.data_ptr(), flat.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                                   gens.data_ptr(), Bt, None if packed is None else packed.data_ptr(),
-                                   v.data_ptr(), theta.data_ptr(), total.data_ptr(), last.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), save, stream), 'gns_forward')
-        # Teams of workgroups (lane-per-grid kernels on a batch that leaves CUs idle) can give up at a barrier when another kernel
-        # holds a partner's CU: the losses are then NaN and the workspace carries a status word.  A training call is checked before
-        # its backward is launched (no gradient of invalid losses reaches an optimiser); an evaluation call at the next call of
-        # the module or by ``GNS.check_status()``.
-        off = ctypes.c_size_t()
-        _check(lib.gns_team_status_offset(ctypes.byref(cfg), Bt, save, ctypes.byref(off)), 'gns_team_status_offset')
+            target.workspace_bytes(cfg, target.count, save, ctypes.byref(fwd_b), ctypes.byref(bwd_b))
+            ws = _workspace(fwd_b.value, dev)
+            v = torch.empty((Bt, N), dtype=torch.float32, device=dev)
+            theta = torch.empty_like(v)
+            total = torch.empty(Bt, dtype=torch.float32, device=dev)
+            last = torch.empty_like(total)
+            packed, pack_arg = target.packed_inputs(mod, lib, cfg, buses, lines, gens, stream, save)
+            target.forward(cfg, *target.blobs, flat.data_ptr(), buses.data_ptr(), lines.data_ptr(), gens.data_ptr(), Bt, *pack_arg,
+                           v.data_ptr(), theta.data_ptr(), total.data_ptr(), last.data_ptr(), ws.data_ptr(), ws.numel(), save, stream)
+            # Teams of workgroups (lane-per-grid kernels on a batch that leaves CUs idle) can give up at a barrier when another kernel
+            # holds a partner's CU: the losses are then NaN and the workspace carries a status word.  A training call is checked before
+            # its backward is launched (no gradient of invalid losses reaches an optimiser); an evaluation call at the next call of
+            # the module or by ``GNS.check_status()``.
+            target.team_status_offset(cfg, target.count, save, ctypes.byref(off))
         uses_teams = off.value != ctypes.c_size_t(-1).value
         ctx.team_status = uses_teams and need_grad
         if uses_teams and not need_grad and not torch.cuda.is_current_stream_capturing():
-            mod.__dict__['_pending_status'] = (cfg, Bt, ws, dev)
+            mod.__dict__['_pending_status'] = (target, cfg, ws, dev)
         if need_grad:
             ctx.save = save
-            ctx.cfg, ctx.topo, ctx.ws, ctx.flat, ctx.Bt, ctx.bwd_bytes = cfg, topo, ws, flat, Bt, bwd_b.value
+            ctx.cfg, ctx.target, ctx.ws, ctx.flat, ctx.Bt, ctx.bwd_bytes = cfg, target, ws, flat, Bt, bwd_b.value
             ctx.params = params
             ctx.mod_flat = mod._flat
             ctx.param_versions = tuple(p._version for p in params) + (mod._flat._version,)   # (a flat optimiser writes through the buffer)
             ctx.inputs = (buses, lines, gens)          # the backward of the grid-per-workgroup mapping re-reads them
             ctx.input_versions = (buses._version, lines._version, gens._version)
-            ctx.packed = packed
+            ctx.pack_arg, ctx.packed = pack_arg, packed         # (the packed tensor itself: its address must outlive the backward)
             ctx.shapes = [p.shape for p in params]
         return v, theta, total, last
 
     @staticmethod
     def backward(ctx, gv, gth, gtot, glast):
-        lib = load_library()
-        flat = ctx.flat
+        flat, target = ctx.flat, ctx.target
         # the backward mixes weights packed by the forward with the live buffer: an in-place update in between (an
         # optimizer.step(), p.add_()) would give silently inconsistent gradients where torch autograd raises
         if tuple(p._version for p in ctx.params) + (ctx.mod_flat._version,) != ctx.param_versions:
@@ -259,26 +314,22 @@ class _GNSFunction(torch.autograd.Function):
             raise GNSError('buses / lines / generators were modified in place between forward and backward')
         dev = flat.device
         if ctx.team_status and not torch.cuda.is_current_stream_capturing():     # (the check synchronises: not inside a graph capture)
-            _raise_if_team_failed(lib, ctx.cfg, ctx.Bt, ctx.ws, ctx.save, dev)
+            _raise_if_team_failed(target, ctx.cfg, ctx.ws, ctx.save, dev)
         bws = _workspace(ctx.bwd_bytes, dev)
-
-        def ptr(t):
-            return None if t is None else t.contiguous().data_ptr()
-
         keep = [t.to(dev).contiguous() if t is not None else None for t in (gtot, glast, gv, gth)]
-        bu, li_, ge = ctx.inputs
         if ctx.save == 2:
-            return _input_backward(ctx, lib, bws, keep, dev)
+            return _input_backward(ctx, load_library(), bws, keep, dev)
+        bu, li_, ge = ctx.inputs
         grad = torch.zeros_like(flat)
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_backward(ctypes.byref(ctx.cfg), ctx.topo.blob.data_ptr(), flat.data_ptr(), bu.data_ptr(), li_.data_ptr(),
-                                    ge.data_ptr(), ctx.Bt, None if ctx.packed is None else ctx.packed.data_ptr(), ctx.ws.data_ptr(),
-                                    ctx.ws.numel(), ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(keep[3]), grad.data_ptr(),
-                                    bws.data_ptr(), bws.numel(), stream), 'gns_backward')
+            target.backward(ctx.cfg, *target.blobs, flat.data_ptr(), bu.data_ptr(), li_.data_ptr(), ge.data_ptr(), ctx.Bt,
+                            *ctx.pack_arg, ctx.ws.data_ptr(), ctx.ws.numel(), *map(_ptr, keep), grad.data_ptr(), bws.data_ptr(), bws.numel(),
+                            torch.cuda.current_stream(dev).cuda_stream)
         # The persistent backward kernels (bwd_variant 1-3 or the packed-FMA engine: opt-ins) run in teams too; one that gave up leaves
-        # NaN in the first gradient element (gns_backward.hip).  The default split backward has no teams and is not checked.
-        if ctx.team_status and not torch.cuda.is_current_stream_capturing() and (get_option('bwd_variant') != 4 or get_option('dw_mfma') == 0):
+        # NaN in the first gradient element (gns_backward.hip).  The default split backward - the only one of a grouped call - has no
+        # teams and is not checked.
+        if ctx.team_status and target.persistent_backward and not torch.cuda.is_current_stream_capturing() \
+                and (get_option('bwd_variant') != 4 or get_option('dw_mfma') == 0):
             if bool(torch.isnan(grad[0])):
                 raise GNSError('a team of workgroups gave up at a barrier of the backward kernel: no gradient is delivered '
                                '(opf_graph_neural_solver_amd.set_option("team", 1) or the default bwd_variant 4 run without teams)')
@@ -294,16 +345,11 @@ def _input_backward(ctx, lib, bws, keep, dev):
     gin = [torch.zeros_like(t) if need else None for t, need in zip((bu, li_, ge), nig[3:6])]
     want_p = any(nig[6:])
     grad = torch.zeros_like(ctx.flat) if want_p else None
-
-    def ptr(t):
-        return None if t is None else t.data_ptr()
-
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(lib.gns_backward_inputs(ctypes.byref(ctx.cfg), ctx.topo.blob.data_ptr(), ctx.flat.data_ptr(), bu.data_ptr(), li_.data_ptr(),
-                                       ge.data_ptr(), ctx.Bt, None if ctx.packed is None else ctx.packed.data_ptr(), ctx.ws.data_ptr(),
-                                       ctx.ws.numel(), ptr(keep[0]), ptr(keep[1]), ptr(keep[2]), ptr(keep[3]), ptr(grad),
-                                       ptr(gin[0]), ptr(gin[1]), ptr(gin[2]), bws.data_ptr(), bws.numel(), stream), 'gns_backward_inputs')
+        _check(lib.gns_backward_inputs(ctypes.byref(ctx.cfg), *ctx.target.blobs, ctx.flat.data_ptr(), bu.data_ptr(), li_.data_ptr(),
+                                       ge.data_ptr(), ctx.Bt, *ctx.pack_arg, ctx.ws.data_ptr(), ctx.ws.numel(), *map(_ptr, keep), _ptr(grad),
+                                       *map(_ptr, gin), bws.data_ptr(), bws.numel(), stream), 'gns_backward_inputs')
     pgrads = _param_grads(ctx, grad) if want_p else [None] * len(ctx.shapes)
     return (None, None, None, gin[0], gin[1], gin[2], *pgrads)
 
@@ -319,80 +365,6 @@ def _param_grads(ctx, grad):
         out.append(grad[off:off + n].view(shp))
         off += n
     return out
-
-
-class _GNSGroupedFunction(torch.autograd.Function):
-    """``_GNSFunction`` for a batch that mixes topologies: one topology per 64-grid group (``_TopologyGroups``), the grouped entry
-    points of the library (lane-per-grid forward, split backward).  Outputs and upstream gradients are in input order."""
-
-    @staticmethod
-    def forward(ctx, mod, plan, want_grad, buses, lines, gens, *params):
-        lib = load_library()
-        Bt, N = buses.shape[0], buses.shape[1]
-        cfg = mod._config(N, lines.shape[1], gens.shape[1])
-        dev = buses.device
-        need_grad = bool(want_grad)
-        ctx.set_materialize_grads(False)
-        G = plan.groups
-        fwd_b, bwd_b = ctypes.c_size_t(), ctypes.c_size_t()
-        _check(lib.gns_workspace_bytes_grouped(ctypes.byref(cfg), G, int(need_grad), ctypes.byref(fwd_b), ctypes.byref(bwd_b)),
-               'gns_workspace_bytes_grouped')
-        ws = _workspace(fwd_b.value, dev)
-        v = torch.empty((Bt, N), dtype=torch.float32, device=dev)
-        theta = torch.empty_like(v)
-        total = torch.empty(Bt, dtype=torch.float32, device=dev)
-        last = torch.empty_like(total)
-        flat = mod._exec_flat(dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_forward_grouped(ctypes.byref(cfg), plan.topo_set.data_ptr(), plan.group_topo.data_ptr(), plan.slot_grid.data_ptr(),
-                                           G, flat.data_ptr(), buses.data_ptr(), lines.data_ptr(), gens.data_ptr(), Bt, v.data_ptr(),
-                                           theta.data_ptr(), total.data_ptr(), last.data_ptr(), ws.data_ptr(), ws.numel(), int(need_grad),
-                                           stream), 'gns_forward_grouped')
-        off = ctypes.c_size_t()
-        _check(lib.gns_team_status_offset_grouped(ctypes.byref(cfg), G, int(need_grad), ctypes.byref(off)), 'gns_team_status_offset_grouped')
-        uses_teams = off.value != ctypes.c_size_t(-1).value
-        ctx.team_status = uses_teams and need_grad
-        if uses_teams and not need_grad and not torch.cuda.is_current_stream_capturing():
-            mod.__dict__['_pending_status'] = (cfg, Bt, ws, dev, G)
-        if need_grad:
-            ctx.cfg, ctx.plan, ctx.ws, ctx.flat, ctx.Bt, ctx.bwd_bytes = cfg, plan, ws, flat, Bt, bwd_b.value
-            ctx.params = params
-            ctx.mod_flat = mod._flat
-            ctx.param_versions = tuple(p._version for p in params) + (mod._flat._version,)
-            ctx.inputs = (buses, lines, gens)
-            ctx.input_versions = (buses._version, lines._version, gens._version)
-            ctx.shapes = [p.shape for p in params]
-        return v, theta, total, last
-
-    @staticmethod
-    def backward(ctx, gv, gth, gtot, glast):
-        lib = load_library()
-        flat = ctx.flat
-        if tuple(p._version for p in ctx.params) + (ctx.mod_flat._version,) != ctx.param_versions:
-            raise GNSError('parameters were modified in place between forward and backward')
-        if tuple(t._version for t in ctx.inputs) != ctx.input_versions:
-            raise GNSError('buses / lines / generators were modified in place between forward and backward')
-        dev = flat.device
-        plan = ctx.plan
-        if ctx.team_status and not torch.cuda.is_current_stream_capturing():
-            _raise_if_team_failed(lib, ctx.cfg, ctx.Bt, ctx.ws, 1, dev, groups=plan.groups)
-        grad = torch.zeros_like(flat)
-        bws = _workspace(ctx.bwd_bytes, dev)
-
-        def ptr(t):
-            return None if t is None else t.data_ptr()
-
-        keep = [t.to(dev).contiguous() if t is not None else None for t in (gtot, glast, gv, gth)]
-        bu, li_, ge = ctx.inputs
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_backward_grouped(ctypes.byref(ctx.cfg), plan.topo_set.data_ptr(), plan.group_topo.data_ptr(),
-                                            plan.slot_grid.data_ptr(), plan.groups, flat.data_ptr(), bu.data_ptr(), li_.data_ptr(),
-                                            ge.data_ptr(), ctx.Bt, ctx.ws.data_ptr(), ctx.ws.numel(), ptr(keep[0]), ptr(keep[1]),
-                                            ptr(keep[2]), ptr(keep[3]), grad.data_ptr(), bws.data_ptr(), bws.numel(), stream),
-                   'gns_backward_grouped')
-        return (None, None, None, None, None, None, *_param_grads(ctx, grad))
 
 
 class GNS(nn.Module):
@@ -617,8 +589,8 @@ class GNS(nn.Module):
         pend = self.__dict__.get('_pending_status')
         if pend is not None:
             self.__dict__['_pending_status'] = None
-            cfg, Bt, ws, dev = pend[:4]
-            _raise_if_team_failed(load_library(), cfg, Bt, ws, 0, dev, groups=pend[4] if len(pend) > 4 else None)
+            target, cfg, ws, dev = pend
+            _raise_if_team_failed(target, cfg, ws, 0, dev)
 
     def flat_leaf(self):
         """A leaf tensor (``requires_grad``) that aliases the flat parameter buffer: with ``flat_grad = True`` the autograd graph
@@ -741,8 +713,9 @@ class GNS(nn.Module):
         if want_inputs and isinstance(topo, _TopologyGroups):
             raise ValueError('gradients with respect to buses / lines / generators are not available for a batch that mixes topologies '
                              '(topology_check = \'group\'): call the model once per topology')
-        fn = _GNSGroupedFunction if isinstance(topo, _TopologyGroups) else _GNSFunction
-        v, theta, total, last = fn.apply(self, topo, want_grad, buses, lines, generators, *params)
+        lib = load_library()
+        target = _GroupedTarget(lib, topo) if isinstance(topo, _TopologyGroups) else _PlainTarget(lib, topo, buses.shape[0])
+        v, theta, total, last = _GNSFunction.apply(self, target, want_grad, buses, lines, generators, *params)
         if in_dev != dev:
             v, theta, total, last = v.to(in_dev), theta.to(in_dev), total.to(in_dev), last.to(in_dev)
         if single:

@@ -261,7 +261,7 @@ def test_weight_gradient_engines_agree_on_large_batches(case, bt, d, multi, K):
 
 @pytest.fixture(params=['lane-per-grid', 'grid-per-workgroup'])
 def train_mapping(request):
-    """Pin the training-mode kernels (the default picks per batch size: gns_api.hip, gw_train_pack)."""
+    """Pin the training-mode kernels (the default picks per batch size: gns_api.hip, route and the gw_train_pack policy it consults)."""
     import opf_graph_neural_solver_amd as amd
     old = amd.get_option('train_mapping')
     amd.set_option('train_mapping', 1 if request.param == 'lane-per-grid' else 2)
@@ -1116,3 +1116,34 @@ def test_widths_between_the_compiled_kernels_on_ragged_batches_against_oracle(d,
             for mine, ref, what in ((v[b], o[0], 'v'), (th[b], o[1], 'theta'), (tot[b], o[2], 'total'), (ev[0][b], o[0], 'v eval'), (ev[2][b], o[2], 'total eval')):
                 assert_close(mine.detach().cpu(), ref.detach(), REL, what=f'{what}[{b}]')
     assert_close(grad, g_o, 5e-5, abs_floor=1e-7, what='grad_params')
+
+
+def test_a_call_on_another_device_than_the_current_one_is_sized_for_the_tensors_device():
+    """The library sizes workspaces, picks kernels and forms teams from the state of the CURRENT device (its CU count, what it could set
+    up), so the wrapper makes every query, not only the launches, under the tensors' device: model and tensors on device 1 while device
+    0 is current give the same bits as the same call with device 1 current.  Needs two devices visible to the process."""
+    import opf_graph_neural_solver_amd as amd
+    if torch.cuda.device_count() < 2:
+        pytest.skip('one visible device')
+
+    def run(current):
+        torch.manual_seed(3)
+        m = amd.GNS(20, 10, 3, 0.9, True).to('cuda:1')
+        out = []
+        with torch.cuda.device(current):
+            for bt in (130, 4096):                       # grid-per-workgroup pair; lane-per-grid kernels in teams
+                bu, li, ge = amd.synth.synth_grids(30, bt, seed=5, device='cuda:1')
+                m.zero_grad()
+                v, th, tot, last = m(bu, li, ge)
+                (tot.mean() + 0.5 * last.mean()).backward()
+                with torch.no_grad():
+                    ev = m(bu, li, ge)
+                m.check_status()
+                out += [v, th, tot, last, torch.cat([p.grad.reshape(-1) for p in m.parameters()]), *ev]
+            torch.cuda.synchronize(1)
+        return [t.detach().cpu() for t in out]
+
+    ref, got = run(1), run(0)
+    assert all(t.device.type == 'cpu' and bool(torch.isfinite(t).all()) for t in ref)
+    for i, (a, b) in enumerate(zip(ref, got)):
+        assert torch.equal(a, b), i

@@ -346,6 +346,48 @@ int gns_dc_adjoint_set(const gns_pf_config* cfg, const void* set_host, const voi
                        float* grad_buses, float* grad_lines, float* grad_generators,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* DC contingency screening: the post-outage DC flows of a list of single-line outages (an N-1 set) of every grid of a batch, from
+ * the base factorisation alone (line-outage distribution factors).
+ *
+ * Semantics (the DC power flow above is the base case: theta, F_l = line_flow_l, b_l, Bbus; fp64 throughout)
+ *   The outage of line k with ends f, t removes its four Bbus stamps and its Pfinj, a rank-1 change of Bbus[r, r]:
+ *   a_k = (e_f - e_t) restricted to the non-slack buses; Bbus[r, r] z_k = a_k on the base factor, z_k = 0 at the slack;
+ *   d_k = z_k[f] - z_k[t];  alpha_k = F_k / (1 - b_k d_k);  theta' = theta + alpha_k z_k;
+ *   F'_l = F_l + b_l (z_k[f_l] - z_k[t_l]) alpha_k for l != k, F'_k = 0.  A line from a bus to itself has a_k = 0 and changes nothing.
+ *   worst_loading = max_l |F'_l| / rating_l (rating NULL: 1) and worst_line the 0-based line that attains it, the lowest of equals.
+ *   Islanding: an outage that disconnects the graph (a bridge) has 1 - b_k d_k = 0 in exact arithmetic.  The kernel does not decide
+ *   that numerically: the caller finds the bridges of the topology and passes islanding[n_outage] (1: bridge).  Those rows get NaN
+ *   in line_flow and worst_loading and -1 in worst_line, in every grid.
+ *   Failure: a grid whose base solve fails (converged = 0, as gns_dc_solve decides it) gets NaN / -1 in every row; a row whose z_k,
+ *   denominator or alpha_k is not finite (or whose denominator is zero) gets NaN / -1 alone.  Other rows are unaffected.
+ *   Every (grid, outage) row is bit-identical alone, in any batch, for any outage list or order that holds the outage (duplicates
+ *   are independent rows), and from run to run: no atomics, the reductions in a fixed order.
+ *
+ * Inputs: outages as 0-based line indices, on the host (checked before the launch) and on the device (read by the kernel), both
+ * [n_outage] int32; islanding [n_outage] uint8 on the device; rating NULL, [E] (rating_per_grid 0) or [Bt,E] (1) fp64 on the device.
+ * Outputs: line_flow [Bt,n_outage,E] fp64, or NULL for the summaries alone (8 Bt n_outage E bytes not written);
+ * worst_loading [Bt,n_outage] fp64; worst_line [Bt,n_outage] int32; converged [Bt] uint8, the base solve's.
+ *
+ * Kernel (gns_dcn1.hip): one wave per (grid, chunk of W outages), on the FD blob.  The wave builds and factors Bbus[r, r] once and
+ * solves the base case; then lane j runs the B' solve program on the right-hand side of outage j of its chunk, with no barrier,
+ * against the shared factor; then the chunk's outages are written one after the other with a line per lane.  LDS image
+ * (gns_dcn1_lds_bytes): 8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes, the DC image, three doubles per line and the
+ * right-hand sides [dim_p][W + 1]; W is the largest power of two up to 64 whose image fits GNS_PF_LDS_MAX_BYTES (1 when none
+ * does: the image reported is then W = 1's).  No workspace: the query reports 0 bytes, and workspace may be NULL.
+ *
+ * Errors: GNS_EINVAL for a NULL cfg, blob, input, outage list, islanding mask or output other than line_flow, a blob that is not an
+ * FD blob or whose N, E, Gn are not cfg's, n_outage <= 0, an outage outside 0 .. E-1, rating_per_grid outside {0, 1}, or
+ * Bt * ceil(n_outage / W) above 2^31 - 1; GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Every refusal comes before
+ * any launch; nothing is allocated and the host is not synchronised. */
+int gns_dcn1_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
+int gns_dcn1_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_outage, size_t* bytes);
+int gns_dcn1_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                    const float* buses, const float* lines, const float* generators, int64_t Bt,
+                    const int32_t* outages_host, const int32_t* outages_dev, int32_t n_outage, const uint8_t* islanding,
+                    const double* rating, int32_t rating_per_grid,
+                    double* line_flow, double* worst_loading, int32_t* worst_line, uint8_t* converged,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

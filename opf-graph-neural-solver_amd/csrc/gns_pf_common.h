@@ -91,6 +91,20 @@ PF_HOST_DEVICE inline int64_t dc_lds_bytes(const int32_t* h) {
   return 8 * ((int64_t)h[FH_NNZLU1] + h[FH_DIM1] + (int64_t)h[FH_N]);
 }
 
+// LDS image of one workgroup of the DC contingency screen (gns_dcn1_lds_bytes), which runs on the FD blob with `lanes` outages side
+// by side: the DC image, three doubles per line (b_l, the base flow, the two ends' B' positions) and the right-hand sides of the
+// outages as [dim_p][lanes + 1] doubles (a row per B' slot, a column per outage, one column of padding)
+PF_HOST_DEVICE inline int64_t dcn1_lds_bytes(const int32_t* h, int lanes) {
+  return dc_lds_bytes(h) + 8 * (3 * (int64_t)h[FH_E] + (int64_t)h[FH_DIM1] * (lanes + 1));
+}
+
+// Outages a workgroup of the screen takes side by side: the largest power of two up to 64 whose image fits max_bytes (1 if none does)
+PF_HOST_DEVICE inline int dcn1_lanes(const int32_t* h, int64_t max_bytes) {
+  int lanes = 64;
+  while (lanes > 1 && dcn1_lds_bytes(h, lanes) > max_bytes) lanes >>= 1;
+  return lanes;
+}
+
 // What the code that handles either kind of blob (the set checks on the host and in the set kernels) needs to know of a kind.
 // The magic, the total, N, E and Gn sit at the same header words in both.
 static_assert(FH_MAGIC == PH_MAGIC && FH_TOTAL == PH_TOTAL && FH_N == PH_N && FH_E == PH_E && FH_GN == PH_GN, "shared header words");

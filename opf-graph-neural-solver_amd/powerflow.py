@@ -20,6 +20,10 @@ analysis (``gns_fd_prepare_topology``); its gradients are the Newton-Raphson adj
 ``runpf``): angles, per-line active flows and the slack's balancing power from one factorisation and one solve per grid
 (``csrc/gns_dcpf.hip``) on the fast-decoupled analysis, whose B' has the DC matrix's sparsity; its backward is a second solve on
 the same factor (``gns_dc_adjoint``).
+
+``dc_contingency_screen(...)`` screens a batch against a list of single-line outages (an N-1 set) from the base factor alone: one
+more solve per outage gives the exact post-outage DC flows (line-outage distribution factors, ``csrc/gns_dcn1.hip``), with the worst
+loading and its line per ``(grid, outage)``; outages that disconnect the grid are found on the host as the bridges of the topology.
 """
 from __future__ import annotations
 
@@ -38,6 +42,9 @@ from ._lib import (GNS_ERRORS, GNS_ETOPOLOGY, GNS_EUNSUPPORTED, PF_LDS_MAX_BYTES
 PowerFlowResult = namedtuple('PowerFlowResult', ['v', 'theta', 'converged', 'iterations', 'mismatch'])
 
 DcPowerFlowResult = namedtuple('DcPowerFlowResult', ['v', 'theta', 'line_flow', 'slack_p', 'converged'])
+
+DcContingencyResult = namedtuple('DcContingencyResult', ['base', 'outages', 'line_flow', 'worst_loading', 'worst_line', 'islanding',
+                                                         'converged'])
 
 MixedPlan = namedtuple('MixedPlan', ['topology', 'order', 'grid_off', 'member_off', 'topo_set', 'slack_bus', 'islanded'])
 
@@ -119,6 +126,9 @@ _Solver = namedtuple('_Solver', ['prefix', 'topology', 'formula'])
 _NR = _Solver('gns_pf', PowerFlowTopology, _LDS_FORMULA)
 _FD = _Solver('gns_fd', FdTopology, _FD_LDS_FORMULA)
 _DC = _Solver('gns_dc', FdTopology, _DC_LDS_FORMULA)     # DC runs on the fast-decoupled analysis (_FD's caches), with its own LDS image
+_DCN1_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per workgroup: DC's image, three doubles per line and "
+                     "the right-hand sides of W outages side by side, here with W = 1, the narrowest")
+_DCN1 = _Solver('gns_dcn1', FdTopology, _DCN1_LDS_FORMULA)   # the DC contingency screen: the same analysis again
 
 
 def _analysis(solver):
@@ -584,6 +594,175 @@ def _dc_adjoint(lib, cfg, target, buses, lines, gens, theta, conv, incoming, nee
         return _unsolved_grads(gin, incoming, Bt, dev)
     _launch(lib, _DC, 'adjoint', cfg, target, (buses, lines, gens), (theta, conv, *incoming, *gin))
     return gin
+
+
+def _dcn1_lds_bytes(host):
+    """``(LDS image, W)`` of the DC contingency screen (``gns_dcn1_lds_bytes``) on the FD blob ``host``: W outages side by side, the
+    largest power of two up to 64 whose image fits (W = 1's image when none does)."""
+    lds, lanes = ctypes.c_int64(), ctypes.c_int32()
+    _check(load_library().gns_dcn1_lds_bytes(host.ctypes.data, ctypes.byref(lds), ctypes.byref(lanes)), 'gns_dcn1_lds_bytes')
+    return lds.value, lanes.value
+
+
+def _bridges(n_bus, f_bus, t_bus):
+    """bool ``[E]``: the lines (0-based ends) whose removal disconnects the graph they span.  One depth-first search with low
+    points (linear time); the line a bus was reached by is skipped by index, so a parallel line is never a bridge, and a line from
+    a bus to itself is not in the graph."""
+    f, t = np.asarray(f_bus).tolist(), np.asarray(t_bus).tolist()
+    adj = [[] for _ in range(n_bus)]
+    for e, (a, b) in enumerate(zip(f, t)):
+        if a != b:
+            adj[a].append((b, e))
+            adj[b].append((a, e))
+    bridge = np.zeros(len(f), dtype=bool)
+    disc, low = [-1] * n_bus, [0] * n_bus
+    clock = 0
+    for root in range(n_bus):
+        if disc[root] >= 0:
+            continue
+        disc[root] = low[root] = clock
+        clock += 1
+        stack = [(root, -1, iter(adj[root]))]
+        while stack:
+            i, via, it = stack[-1]
+            for k, e in it:
+                if e == via:
+                    continue
+                if disc[k] >= 0:
+                    low[i] = min(low[i], disc[k])
+                    continue
+                disc[k] = low[k] = clock
+                clock += 1
+                stack.append((k, e, iter(adj[k])))
+                break
+            else:
+                stack.pop()
+                if stack:
+                    parent = stack[-1][0]
+                    low[parent] = min(low[parent], low[i])
+                    if low[i] > disc[parent]:
+                        bridge[via] = True
+    return bridge
+
+
+def _topology_bridges(topo, args):
+    """The bridges of an analysed topology (``_bridges``), found once and kept with it.  The analysis has shown the topology
+    connected, so these are exactly the lines whose outage leaves a bus without a path to the slack (``_islanded``)."""
+    if getattr(topo, 'bridges', None) is None:
+        n_bus, f_bus, t_bus = args[0], args[1], args[2]
+        topo.bridges = _bridges(int(n_bus), f_bus.astype(np.int64) - 1, t_bus.astype(np.int64) - 1)
+    return topo.bridges
+
+
+def _outage_list(outages, E):
+    """The checked outage list as an int64 numpy array ``[K]``."""
+    if outages is None:
+        return np.arange(E, dtype=np.int64)
+    o = outages.detach().cpu().numpy() if isinstance(outages, torch.Tensor) else np.asarray(list(outages) if isinstance(outages, range)
+                                                                                            else outages)
+    if o.ndim != 1:
+        raise ValueError(f'outages must be a 1-D sequence of line indices, got shape {tuple(o.shape)}')
+    if o.size == 0:
+        raise ValueError('outages is empty: give at least one line index (None: every line)')
+    if o.dtype == np.bool_ or not np.issubdtype(o.dtype, np.integer):
+        raise ValueError(f'outages must hold integers (0-based line indices), got dtype {o.dtype}')
+    if o.min() < 0 or o.max() > E - 1:
+        raise ValueError(f'outages must lie in 0..{E - 1} (0-based line indices), got {int(o.min())}..{int(o.max())}')
+    return o.astype(np.int64)
+
+
+def _rating(rating, Bt, E, single):
+    """The checked rating: None, or float64 ``[E]`` / ``[Bt,E]``."""
+    if rating is None:
+        return None
+    r = torch.as_tensor(rating).to(torch.float64)
+    if single and r.dim() == 2 and r.shape[0] == 1:
+        r = r[0]
+    if tuple(r.shape) not in ((E,), (Bt, E)):
+        raise ValueError(f'rating must be [{E}] or [{Bt},{E}], got {tuple(r.shape)}')
+    if not bool((torch.isfinite(r) & (r > 0)).all()):
+        raise ValueError('rating must be positive and finite')
+    return r
+
+
+def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, outages=None, rating=None,
+                          flows=True):
+    """DC N-1 contingency screening of every grid of a batch, on the device: the exact post-outage DC flows of each single-line
+    outage of ``outages`` from the base factorisation and one more solve per outage (line-outage distribution factors), not from
+    one factorisation per ``(grid, outage)`` as ``dc_power_flow(mixed_topologies=True)`` on the expanded batch does.
+
+    Inputs, column maps, the slack and the device handling are those of ``dc_power_flow``; the whole batch shares one topology
+    (``mixed_topologies`` is out of scope here).  ``outages``: a 1-D sequence or tensor of 0-based line indices (the convention of
+    ``synth.contingency_grids``), default every line; duplicates are independent rows.  ``rating``: None (1: the loading is
+    ``|flow|``), ``[E]`` or ``[Bt,E]``, positive and finite, used in float64.
+
+    Returns ``DcContingencyResult(base, outages, line_flow, worst_loading, worst_line, islanding, converged)``:
+      base           the ``DcPowerFlowResult`` of ``dc_power_flow`` on the same inputs, bit for bit
+      outages        ``[K]`` int64
+      line_flow      ``[Bt,K,E]`` float64, the flows with the line out, 0 at the outaged line; None with ``flows=False`` (the tensor is
+                     ``8 Bt K E`` bytes: the kernel then writes the summaries alone)
+      worst_loading  ``[Bt,K]`` float64, ``max_l |line_flow| / rating``;  worst_line ``[Bt,K]`` int32, the line that attains it (the
+                     lowest of equals)
+      islanding      ``[K]`` bool: the outage disconnects the grid (the line is a bridge of the topology, found on the host once per
+                     topology, never from a numeric threshold).  Those rows are NaN / -1 in every grid.
+      converged      ``[Bt]`` bool, the base solve's.  A grid whose base solve fails has NaN / -1 in every row; a row whose update is
+                     not finite has NaN / -1 alone.
+    Every ``(grid, outage)`` row is bit-identical alone, in any batch, for any outage list or order that holds the outage and from
+    run to run.  With a 2-D single grid the batch dimension is dropped.
+
+    The analysis is ``fast_decoupled``'s and ``dc_power_flow``'s: a batch either has seen is not analysed again.  The outputs are not
+    differentiable: the call runs as under ``torch.no_grad()`` (an adjoint of the screen is future work, as are N-2 outages and an
+    AC screen).  Contract: ``include/gns_powerflow.h``, "DC contingency screening"."""
+    if not isinstance(flows, bool):
+        raise ValueError(f'flows must be a bool, got {flows!r}')
+    with torch.no_grad():
+        # the shapes first, so that a bad outage list or rating is refused where no device is visible too
+        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
+        out_np = _outage_list(outages, shaped_lines.shape[1])
+        rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None,
+                                                                 None, 0.0, 0, False)
+        lib = load_library()
+        Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
+        rating = None if rating is None else rating.to(dev).contiguous()
+        K = out_np.size
+        cfg = PfConfig(N, E, generators.shape[1], 0, 0.0)
+        key, args = _topology_key(buses, lines, generators, slack_bus, 'dc_contingency_screen')
+        topo = _analysed(_FD, key, args, dev)
+        isl_np = _topology_bridges(topo, args)[out_np]
+
+        out32 = out_np.astype(np.int32)
+        out_dev, isl_dev = torch.from_numpy(out32).to(dev), torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
+        flow = torch.empty(Bt, K, E, dtype=torch.float64, device=dev) if flows else None
+        worst = torch.empty(Bt, K, dtype=torch.float64, device=dev)
+        worst_line = torch.empty(Bt, K, dtype=torch.int32, device=dev)
+        conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
+        lds = lambda: _dcn1_lds_bytes(topo.host)[0]                       # noqa: E731
+        nbytes = ctypes.c_size_t()
+        _check(lib.gns_dcn1_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)),
+               'gns_dcn1_workspace_bytes', lds, _DCN1.formula)
+        ws = _gns._workspace(nbytes.value, dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_dcn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
+                                       lines.data_ptr(), generators.data_ptr(), Bt, out32.ctypes.data, out_dev.data_ptr(), K,
+                                       isl_dev.data_ptr(), _ptr(rating), int(rating is not None and rating.dim() == 2), _ptr(flow),
+                                       worst.data_ptr(), worst_line.data_ptr(), conv.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                   'gns_dcn1_screen', lds, _DCN1.formula)
+        # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
+        base = _dc_solve(lib, cfg, _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host)), buses, lines, generators)
+        base = [torch.ones(Bt, N, dtype=torch.float64, device=dev), *base]
+        res = [flow, worst, worst_line]
+        outages_t, islanding, conv = torch.from_numpy(out_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev), conv.bool()
+        if in_dev != dev:
+            base = [t.to(in_dev) for t in base]
+            res = [None if t is None else t.to(in_dev) for t in res]
+            outages_t, islanding, conv = outages_t.to(in_dev), islanding.to(in_dev), conv.to(in_dev)
+        if single:
+            base = [t[0] for t in base]
+            res = [None if t is None else t[0] for t in res]
+            conv = conv[0]
+        return DcContingencyResult(DcPowerFlowResult(*base), outages_t, res[0], res[1], res[2], islanding, conv)
 
 
 def _not_solved(Bt, N, dev):

@@ -388,6 +388,60 @@ int gns_dcn1_screen(const gns_pf_config* cfg, const void* topo_host, const void*
                     double* line_flow, double* worst_loading, int32_t* worst_line, uint8_t* converged,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Gradients of the screen.  gns_dcn1_adjoint takes the inputs of a gns_dcn1_screen call (the same outage list, islanding mask and
+ * rating), its outputs worst_line and converged, and the incoming gradients grad_line_flow [Bt,n_outage,E] and grad_worst_loading
+ * [Bt,n_outage] fp64 of a loss l(line_flow, worst_loading) (each may be NULL: zero).  It writes dl/d(input) into grad_buses
+ * [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32, each of which may be NULL (not computed; with all three NULL
+ * nothing is launched).  Every element of each non-NULL output is written (overwritten, not accumulated).  line_flow is not an
+ * input: each row's state is recomputed with the forward's own arithmetic.
+ *
+ * Method (A = Bbus[r, r], m_l = (e_f - e_t)_r of line l, z_k, d_k, den_k = 1 - b_k d_k, alpha_k, theta'_k as above).  For a solved
+ * row (grid, k): G_k = grad_line_flow of the row, plus grad_worst_loading sign(F'_{k,w}) / rating_w at w = worst_line (so a tie
+ * sends the gradient to the lowest of equals); its entry at l = k is ignored, F'_{k,k} being the constant 0.
+ *   q_k = sum_{l != k} G_{k,l} b_l m_l;  A u_k = q_k on the base factor with the B' solve program;
+ *   lambda_k = u_k + z_k b_k (m_k^T u_k) / den_k  (Sherman-Morrison: the DC adjoint of the grid without line k), 0 at the slack;
+ *   w_{k,l} = G_{k,l} - (lambda_k[f_l] - lambda_k[t_l]) for l != k, 0 for l = k.
+ * Summed over the outages of the list:  dl/dP_i = sum_k lambda_k[i];  dl/db_l = sum_k w_{k,l} (theta'_k[f_l] - theta'_k[t_l] -
+ * shift_l);  dl/dshift_l = -b_l sum_k w_{k,l}.  Two solves on the base factor per outage; nothing is factored per outage.
+ *
+ * Contract (gns_dc_adjoint's columns):
+ *   buses      col 2 Pd and col 4 Gs: -dl/dP_i.  Every other column: 0.
+ *   lines      col 3 x: -dl/db_l b_l / x;  col 5 tau: -dl/db_l b_l / tau;  col 6 shift: dl/dshift_l.  Cols 0, 1, 2, 4: 0.  Row k
+ *              of the screen contributes exactly 0 to line k's own columns.  A line whose ids are not buses of the grid gets a NaN row.
+ *   generators col 6 Pg: dl/dP at its bus.  Every other column: 0.
+ *   rating is a constant.  A solved row whose incoming gradients are all exactly zero is skipped.
+ *   Failure: a row the forward left NaN / -1 (an islanding outage, a non-finite update) contributes nothing when its incoming
+ *   gradients are all exactly zero or NULL; it is skipped, never multiplied by zero.  Otherwise, or when a lambda_k is not finite,
+ *   all three gradient rows of that grid are NaN.  A grid with converged == 0 (or whose base solve fails here) gets NaN rows unless
+ *   all its incoming gradients are exactly zero, and zero rows then.  Other grids are unaffected.
+ *   fp64 throughout, rounded once to fp32.  No atomics, every sum in a fixed order: a grid's gradient is bit-identical alone, in
+ *   any batch and from run to run for the same outage list.  The order and the chunking of the list set the order of the sums
+ *   over outages, so another order of the same outages may change the last bits.
+ *
+ * Kernels (gns_dcn1.hip): one wave per (grid, chunk of Wa outages) with the screen's prologue; lane j solves z_k as the screen
+ * does, fills q_k into its own column of a second right-hand-side array in line order, solves u_k and forms lambda_k; a last pass
+ * walks the chunk's outages in order with a line per lane (dl/db, sum of w) and a bus per lane (dl/dP) and stores the chunk's
+ * partial.  A second kernel, a wave per grid, sums the chunks' partials in order, applies the contract and writes the outputs.
+ * LDS image (gns_dcn1_adjoint_lds_bytes): 8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (Wa + 1) + 3 Wa) bytes, the screen's image at
+ * width Wa, the second array [dim_p][Wa + 1] and three doubles per outage; Wa is the largest power of two up to 64 whose image fits
+ * GNS_PF_LDS_MAX_BYTES (1 when none does: the image reported is then Wa = 1's).  Workspace (gns_dcn1_adjoint_workspace_bytes):
+ * Bt * ceil(n_outage / Wa) partials of N + 2 E + 1 doubles (dl/dP, dl/db, the sum of w, a status), rounded up to 256 bytes.
+ *
+ * Errors: as gns_dcn1_screen, with worst_line and converged in place of its outputs (GNS_EINVAL when NULL) and Wa in place of W;
+ * GNS_EUNSUPPORTED for an adjoint LDS image above GNS_PF_LDS_MAX_BYTES (from the workspace query too); then, when an output is
+ * asked for, GNS_EINVAL for a NULL workspace and GNS_ESIZE for a short one.  Every refusal comes before any launch; nothing is
+ * allocated and the host is not synchronised. */
+int gns_dcn1_adjoint_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* Wa; may be NULL */);
+int gns_dcn1_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_outage, size_t* bytes);
+int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const int32_t* outages_host, const int32_t* outages_dev, int32_t n_outage, const uint8_t* islanding,
+                     const double* rating, int32_t rating_per_grid,
+                     const int32_t* worst_line, const uint8_t* converged,
+                     const double* grad_line_flow, const double* grad_worst_loading,
+                     float* grad_buses, float* grad_lines, float* grad_generators,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

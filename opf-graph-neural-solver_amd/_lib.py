@@ -121,6 +121,9 @@ def load_library():
     lib.gns_dcn1_lds_bytes.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
     lib.gns_dcn1_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
     lib.gns_dcn1_screen.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_dcn1_adjoint_lds_bytes.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    lib.gns_dcn1_adjoint_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
+    lib.gns_dcn1_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     for f in PF_EXPORTS + FD_EXPORTS + DC_EXPORTS + DCN1_EXPORTS:
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
@@ -150,7 +153,8 @@ FD_EXPORTS = ('gns_fd_topology_bytes', 'gns_fd_prepare_topology', 'gns_fd_topolo
 DC_EXPORTS = ('gns_dc_lds_bytes', 'gns_dc_workspace_bytes', 'gns_dc_solve', 'gns_dc_workspace_bytes_set', 'gns_dc_solve_set',
               'gns_dc_adjoint', 'gns_dc_adjoint_set')
 # the DC contingency screen's C-ABI (include/gns_powerflow.h, "DC contingency screening"): on the fast-decoupled blob too
-DCN1_EXPORTS = ('gns_dcn1_lds_bytes', 'gns_dcn1_workspace_bytes', 'gns_dcn1_screen')
+DCN1_EXPORTS = ('gns_dcn1_lds_bytes', 'gns_dcn1_workspace_bytes', 'gns_dcn1_screen', 'gns_dcn1_adjoint_lds_bytes',
+                'gns_dcn1_adjoint_workspace_bytes', 'gns_dcn1_adjoint')
 # the limits of include/gns_powerflow.h
 PF_LDS_MAX_BYTES = 163840
 PF_MAX_SLOTS = 65535

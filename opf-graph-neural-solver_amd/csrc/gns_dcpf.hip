@@ -116,15 +116,6 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dc_set_kernel(const int32_t* _
 // ---- the adjoint (gns_dc_adjoint): theta_r = Bbus[r, r]^-1 P_r with a symmetric matrix, so lambda_r = Bbus[r, r]^-1 g_r on the same
 // factor with the same solve program (include/gns_powerflow.h, "DC power flow", gradients).
 
-// Every element of grid g's three gradient rows set to x
-__device__ __forceinline__ void dc_adjoint_fill(const int g, const int N, const int E, const int Gn, const float x, float* gb_out,
-                                                float* gl_out, float* gg_out) {
-  const int lane = threadIdx.x;
-  if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = x;
-  if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = x;
-  if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = x;
-}
-
 // Whether grid g's incoming gradients are all exactly zero (a NULL one counts as zero)
 __device__ __forceinline__ bool dc_zero_incoming(const int g, const int N, const int E, const double* gth, const double* gfl,
                                                  const double* gsp) {

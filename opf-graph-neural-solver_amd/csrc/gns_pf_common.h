@@ -105,6 +105,23 @@ PF_HOST_DEVICE inline int dcn1_lanes(const int32_t* h, int64_t max_bytes) {
   return lanes;
 }
 
+// LDS image of one workgroup of the screen's adjoint (gns_dcn1_adjoint_lds_bytes) with `lanes` outages side by side: the screen's
+// image at that width, a second [dim_p][lanes + 1] array (the adjoint right-hand sides, then lambda_k) and three doubles per outage
+// (alpha_k, the worst-loading term of its incoming gradient, its line and its worst line)
+PF_HOST_DEVICE inline int64_t dcn1_adjoint_lds_bytes(const int32_t* h, int lanes) {
+  return dcn1_lds_bytes(h, lanes) + 8 * ((int64_t)h[FH_DIM1] * (lanes + 1) + 3 * (int64_t)lanes);
+}
+
+// Outages a workgroup of the adjoint takes side by side: as dcn1_lanes, on the adjoint's image
+PF_HOST_DEVICE inline int dcn1_adjoint_lanes(const int32_t* h, int64_t max_bytes) {
+  int lanes = 64;
+  while (lanes > 1 && dcn1_adjoint_lds_bytes(h, lanes) > max_bytes) lanes >>= 1;
+  return lanes;
+}
+
+// Doubles of one (grid, chunk) partial of the adjoint's workspace: dl/dP by bus, dl/db and the sum of w by line, then the chunk's status
+PF_HOST_DEVICE inline int64_t dcn1_adjoint_partial(const int32_t* h) { return (int64_t)h[FH_N] + 2 * (int64_t)h[FH_E] + 1; }
+
 // What the code that handles either kind of blob (the set checks on the host and in the set kernels) needs to know of a kind.
 // The magic, the total, N, E and Gn sit at the same header words in both.
 static_assert(FH_MAGIC == PH_MAGIC && FH_TOTAL == PH_TOTAL && FH_N == PH_N && FH_E == PH_E && FH_GN == PH_GN, "shared header words");

@@ -24,6 +24,7 @@ the same factor (``gns_dc_adjoint``).
 ``dc_contingency_screen(...)`` screens a batch against a list of single-line outages (an N-1 set) from the base factor alone: one
 more solve per outage gives the exact post-outage DC flows (line-outage distribution factors, ``csrc/gns_dcn1.hip``), with the worst
 loading and its line per ``(grid, outage)``; outages that disconnect the grid are found on the host as the bridges of the topology.
+With ``differentiable=True`` its backward is one ``gns_dcn1_adjoint`` call: a second solve on the base factor per outage.
 """
 from __future__ import annotations
 
@@ -129,6 +130,9 @@ _DC = _Solver('gns_dc', FdTopology, _DC_LDS_FORMULA)     # DC runs on the fast-d
 _DCN1_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per workgroup: DC's image, three doubles per line and "
                      "the right-hand sides of W outages side by side, here with W = 1, the narrowest")
 _DCN1 = _Solver('gns_dcn1', FdTopology, _DCN1_LDS_FORMULA)   # the DC contingency screen: the same analysis again
+_DCN1_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W) bytes per workgroup: the screen's image, a second "
+                             "array of W right-hand sides for the adjoint solves and three doubles per outage, here with W = 1, the "
+                             "narrowest")
 
 
 def _analysis(solver):
@@ -685,8 +689,38 @@ def _rating(rating, Bt, E, single):
     return r
 
 
+def _dcn1_adjoint_lds_bytes(host):
+    """``(LDS image, W)`` of the screen's adjoint (``gns_dcn1_adjoint_lds_bytes``) on the FD blob ``host``, as ``_dcn1_lds_bytes``."""
+    lds, lanes = ctypes.c_int64(), ctypes.c_int32()
+    _check(load_library().gns_dcn1_adjoint_lds_bytes(host.ctypes.data, ctypes.byref(lds), ctypes.byref(lanes)),
+           'gns_dcn1_adjoint_lds_bytes')
+    return lds.value, lanes.value
+
+
+class _DCN1Function(torch.autograd.Function):
+    """``dc_contingency_screen(differentiable=True)`` when an input requires grad, as ``_DCFunction``: the forward is the screen's
+    launch, the backward one ``gns_dcn1_adjoint`` call on the forward's topology and outage list.  ``line_flow`` is not saved: the
+    adjoint recomputes each row's state from the inputs, the forward's ``worst_line`` and ``converged``."""
+
+    @staticmethod
+    def forward(ctx, screen, adjoint, buses, lines, gens):
+        flow, worst, worst_line, conv = screen(buses, lines, gens)
+        ctx.mark_non_differentiable(worst_line, conv)
+        ctx.set_materialize_grads(False)
+        ctx.adjoint = adjoint
+        ctx.save_for_backward(buses, lines, gens, worst_line, conv)
+        return flow, worst, worst_line, conv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gfl, gwl, _gwi, _gconv):
+        buses, lines, gens, worst_line, conv = ctx.saved_tensors
+        grads = ctx.adjoint(buses, lines, gens, worst_line, conv, (gfl, gwl), ctx.needs_input_grad[2:5])
+        return (None, None, *grads)
+
+
 def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, outages=None, rating=None,
-                          flows=True):
+                          flows=True, differentiable=False):
     """DC N-1 contingency screening of every grid of a batch, on the device: the exact post-outage DC flows of each single-line
     outage of ``outages`` from the base factorisation and one more solve per outage (line-outage distribution factors), not from
     one factorisation per ``(grid, outage)`` as ``dc_power_flow(mixed_topologies=True)`` on the expanded batch does.
@@ -710,47 +744,103 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     Every ``(grid, outage)`` row is bit-identical alone, in any batch, for any outage list or order that holds the outage and from
     run to run.  With a 2-D single grid the batch dimension is dropped.
 
-    The analysis is ``fast_decoupled``'s and ``dc_power_flow``'s: a batch either has seen is not analysed again.  The outputs are not
-    differentiable: the call runs as under ``torch.no_grad()`` (an adjoint of the screen is future work, as are N-2 outages and an
-    AC screen).  Contract: ``include/gns_powerflow.h``, "DC contingency screening"."""
+    The analysis is ``fast_decoupled``'s and ``dc_power_flow``'s: a batch either has seen is not analysed again.
+
+    Gradients: by default the outputs are not differentiable (the call runs as under ``torch.no_grad()``).  With
+    ``differentiable=True``, grad mode on and ``requires_grad`` on an input, ``line_flow`` and ``worst_loading`` are differentiable
+    through one ``gns_dcn1_adjoint`` call on the forward's topology (per outage a second solve on the base factor and a
+    Sherman-Morrison correction; nothing is factored per outage, and ``line_flow`` is not kept for the backward), and ``base.theta``,
+    ``base.line_flow`` and ``base.slack_p`` through ``dc_power_flow``'s adjoint.  The derivative is exact with respect to ``Pd``,
+    ``Gs``, the lines' ``x``, ``tau``, ``shift`` and the generators' ``Pg``; every other column gets 0, and row ``k`` gives exactly 0
+    to line ``k``'s own columns.  ``rating`` is a constant; a tie in the worst loading sends the gradient to ``worst_line``;
+    ``worst_line``, ``islanding``, ``converged`` and ``outages`` are not differentiable.  A row that is NaN / -1 (an islanding
+    outage, a non-finite update) contributes nothing when its incoming gradients are exactly zero or absent (a loss that indexes
+    ``~islanding``); otherwise, and for a grid that is not solved, the grid's three gradient rows are NaN (zero rows for an
+    unsolved grid whose incoming gradients are all zero).  The forward outputs are bit-identical with and without gradients.  A
+    grid's gradient is bit-identical alone, in any batch and from run to run for the same outage list; the order of the list may
+    change its last bits.  N-2 outages, mixed topologies and an AC screen are out of scope.
+    Contract: ``include/gns_powerflow.h``, "DC contingency screening"."""
     if not isinstance(flows, bool):
         raise ValueError(f'flows must be a bool, got {flows!r}')
+    if not isinstance(differentiable, bool):
+        raise ValueError(f'differentiable must be a bool, got {differentiable!r}')
+    grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                              for t in (buses, lines, generators))
     with torch.no_grad():
         # the shapes first, so that a bad outage list or rating is refused where no device is visible too
         single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
         out_np = _outage_list(outages, shaped_lines.shape[1])
         rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
-        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None,
-                                                                 None, 0.0, 0, False)
+    with torch.set_grad_enabled(grad):
+        if not grad:
+            buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, 0.0, 0, False)
         lib = load_library()
         Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
         rating = None if rating is None else rating.to(dev).contiguous()
         K = out_np.size
         cfg = PfConfig(N, E, generators.shape[1], 0, 0.0)
-        key, args = _topology_key(buses, lines, generators, slack_bus, 'dc_contingency_screen')
+        plain = (buses.detach(), lines.detach(), generators.detach())
+        key, args = _topology_key(*plain, slack_bus, 'dc_contingency_screen')
         topo = _analysed(_FD, key, args, dev)
         isl_np = _topology_bridges(topo, args)[out_np]
 
         out32 = out_np.astype(np.int32)
         out_dev, isl_dev = torch.from_numpy(out32).to(dev), torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
-        flow = torch.empty(Bt, K, E, dtype=torch.float64, device=dev) if flows else None
-        worst = torch.empty(Bt, K, dtype=torch.float64, device=dev)
-        worst_line = torch.empty(Bt, K, dtype=torch.int32, device=dev)
-        conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
-        lds = lambda: _dcn1_lds_bytes(topo.host)[0]                       # noqa: E731
-        nbytes = ctypes.c_size_t()
-        _check(lib.gns_dcn1_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)),
-               'gns_dcn1_workspace_bytes', lds, _DCN1.formula)
-        ws = _gns._workspace(nbytes.value, dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_dcn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
-                                       lines.data_ptr(), generators.data_ptr(), Bt, out32.ctypes.data, out_dev.data_ptr(), K,
-                                       isl_dev.data_ptr(), _ptr(rating), int(rating is not None and rating.dim() == 2), _ptr(flow),
-                                       worst.data_ptr(), worst_line.data_ptr(), conv.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                   'gns_dcn1_screen', lds, _DCN1.formula)
-        # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
-        base = _dc_solve(lib, cfg, _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host)), buses, lines, generators)
+
+        def shared():
+            """What both C calls take between Bt and their own arguments: the outage list on the host and on the device, its
+            length, the islanding mask, the rating and whether it is per grid.  (A closure, used as late as the backward: it keeps
+            their owners alive.)"""
+            return (out32.ctypes.data, out_dev.data_ptr(), K, isl_dev.data_ptr(), _ptr(rating),
+                    int(rating is not None and rating.dim() == 2))
+
+        def workspace(query, lds, formula):
+            nbytes = ctypes.c_size_t()
+            _check(getattr(lib, query)(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)), query, lds, formula)
+            return _gns._workspace(nbytes.value, dev)
+
+        def screen(bu, li, ge):
+            flow = torch.empty(Bt, K, E, dtype=torch.float64, device=dev) if flows else None
+            worst = torch.empty(Bt, K, dtype=torch.float64, device=dev)
+            worst_line = torch.empty(Bt, K, dtype=torch.int32, device=dev)
+            conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
+            lds = lambda: _dcn1_lds_bytes(topo.host)[0]                       # noqa: E731
+            ws = workspace('gns_dcn1_workspace_bytes', lds, _DCN1.formula)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(lib.gns_dcn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                           li.data_ptr(), ge.data_ptr(), Bt, *shared(), _ptr(flow), worst.data_ptr(),
+                                           worst_line.data_ptr(), conv.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                       'gns_dcn1_screen', lds, _DCN1.formula)
+            return flow, worst, worst_line, conv
+
+        def adjoint(bu, li, ge, worst_line, conv, incoming, need):
+            gb, gl, gg = (torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need))
+            gflow, gworst = (None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming)
+            ws = workspace('gns_dcn1_adjoint_workspace_bytes', adjoint_lds, _DCN1_ADJOINT_LDS_FORMULA)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(lib.gns_dcn1_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                            li.data_ptr(), ge.data_ptr(), Bt, *shared(), worst_line.data_ptr(), conv.data_ptr(),
+                                            _ptr(gflow), _ptr(gworst), _ptr(gb), _ptr(gl), _ptr(gg), ws.data_ptr(), ws.numel(),
+                                            stream), 'gns_dcn1_adjoint', adjoint_lds, _DCN1_ADJOINT_LDS_FORMULA)
+            return [gb, gl, gg]
+
+        adjoint_lds = lambda: _dcn1_adjoint_lds_bytes(topo.host)[0]          # noqa: E731
+        base_target = _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host))
+        if grad:
+            # the backward's own refusal (its LDS image is the largest of the call) comes before anything is launched
+            nbytes = ctypes.c_size_t()
+            _check(lib.gns_dcn1_adjoint_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)),
+                   'gns_dcn1_adjoint_workspace_bytes', adjoint_lds, _DCN1_ADJOINT_LDS_FORMULA)
+            flow, worst, worst_line, conv = _DCN1Function.apply(screen, adjoint, buses, lines, generators)
+            base = list(_DCFunction.apply(lambda *a: _dc_solve(lib, cfg, base_target, *a),
+                                          lambda *a: _dc_adjoint(lib, cfg, base_target, *a), buses, lines, generators))
+        else:
+            flow, worst, worst_line, conv = screen(*plain)
+            # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
+            base = _dc_solve(lib, cfg, base_target, *plain)
         base = [torch.ones(Bt, N, dtype=torch.float64, device=dev), *base]
         res = [flow, worst, worst_line]
         outages_t, islanding, conv = torch.from_numpy(out_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev), conv.bool()

@@ -442,6 +442,63 @@ int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
                      float* grad_buses, float* grad_lines, float* grad_generators,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* AC contingency screening: Newton-Raphson on every grid of a batch with each single line of a list out of service (an N-1 set),
+ * with the post-outage state, the branch flows at both ends of every line and their summaries, from the base analysis alone.
+ *
+ * Semantics (the Newton-Raphson section at the top of this file is the base case: inputs, bus roles, Y-bus, injections, fp64)
+ *   Row (grid, k) is Newton-Raphson on the grid without line outages[k]: its Y-bus is the sum of the line stamps with that line's
+ *   four skipped (each entry a sum in stamp order, never a subtraction: the values gns_pf_solve computes on the grid with the line
+ *   row deleted); injections, bus roles and the vg set points are the base case's.  The outage removes entries from the Jacobian
+ *   and adds none, so the blob of the base topology serves every row: its factor slots and its program, with numeric zeros where an
+ *   entry lost its only line.  Nothing is analysed or allocated per outage.
+ *   Start: the warm start of gns_pf_solve from base_v, base_theta (the outputs of gns_pf_solve on the same inputs): |V| at PQ buses
+ *   from base_v, theta = base_theta - base_theta[slack]; |V| at PV / slack buses from vg.  The convergence test (||F||_inf < tol
+ *   before every update), the update, max_iter and the failure rules are gns_pf_solve's, per row: a row that does not converge, or
+ *   stops at a zero or non-finite pivot, mismatch or iterate, has converged = 0 and keeps its last finite iterate (mismatch NaN
+ *   when the mismatch itself is not finite); its flows and summaries are computed from that iterate.
+ *   Branch flows (MATPOWER's branch model on the stamps of makeYbus, Y_ff = (y_s + jb/2)/tau^2, Y_tt = y_s + jb/2,
+ *   Y_ft = -y_s/conj(a), Y_tf = -y_s/a of the line alone):  S_f = V_f conj(Y_ff V_f + Y_ft V_t),  S_t = V_t conj(Y_tf V_f + Y_tt V_t);
+ *   p_from + j q_from = S_f, p_to + j q_to = S_t, all four exactly 0 at the outaged line.  The line's buses are read from its id
+ *   columns, which must be those the blob was prepared from (a line whose ids are not buses of the grid gets NaN flows).
+ *   worst_loading = max_l max(|S_f|, |S_t|) / rating_l (rating NULL: 1) and worst_line the 0-based line that attains it; v_min, v_max
+ *   the extremes of |V| over the buses and v_min_bus, v_max_bus the 0-based buses that attain them; the lowest index among equals.
+ *   Islanding: the caller finds the outages that disconnect the graph (the bridges of the topology) and passes islanding[n_outage]
+ *   (1: bridge); the kernel does not decide that numerically.  Those rows get NaN in every fp64 output, -1 in worst_line, v_min_bus,
+ *   v_max_bus and iterations, and converged = 0, in every grid.  So does every row of a grid with base_converged = 0, and a row
+ *   whose line's id columns do not name an entry of the blob's Y-bus pattern.  Other rows are unaffected.
+ *   Every (grid, outage) row is bit-identical alone, in any batch, for any outage list or order that holds the outage (duplicates
+ *   are independent rows), and from run to run: no atomics, the reductions by a total order.
+ *   Not here: gradients, batches that mix topologies (one blob per call), N-2 outages, generator reactive limits.
+ *
+ * Inputs: outages as 0-based line indices, on the host (checked before the launch) and on the device (read by the kernel), both
+ * [n_outage] int32; islanding [n_outage] uint8 on the device; rating NULL, [E] (rating_per_grid 0) or [Bt,E] (1) fp64 on the device;
+ * base_v, base_theta [Bt,N] fp64 and base_converged [Bt] uint8 on the device.  cfg: max_iter and tol as in gns_pf_solve.
+ * Outputs (row r = grid * n_outage + position in the list): v, theta [Bt,n_outage,N] and p_from, q_from, p_to, q_to
+ * [Bt,n_outage,E] fp64, each of which may be NULL (not written); worst_loading, v_min, v_max, mismatch fp64, worst_line, v_min_bus,
+ * v_max_bus, iterations int32, converged uint8 (0/1), all [Bt,n_outage].
+ *
+ * Kernels (gns_acn1.hip): a wave per grid writes the base Y-bus of every grid to the workspace once; then one wave per (grid,
+ * outage) with gns_pf_solve's LDS image (gns_pf_info.lds_bytes) reads its grid's base Y-bus and holds the at most four entries its
+ * line touches (ff, tt, ft, tf) in registers, recomputed from their stamps without the line.  After the iteration a line per lane
+ * computes the flows and the summaries are reduced over the wave.  Workspace (gns_acn1_workspace_bytes): the base Y-bus, 16 bytes
+ * per structural nonzero and GRID (gns_pf_workspace_bytes' figure, whatever n_outage is).
+ *
+ * Errors: GNS_EINVAL for a NULL cfg, blob, input, outage list, islanding mask, base_v, base_theta, base_converged, workspace or
+ * output other than v, theta and the four flows, a negative max_iter or tol, a blob that is not a Newton-Raphson blob or whose N, E,
+ * Gn are not cfg's, n_outage <= 0, an outage outside 0 .. E-1, rating_per_grid outside {0, 1}, or Bt * n_outage above 2^31 - 1;
+ * then GNS_ESIZE for a short workspace; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Every refusal comes
+ * before any launch; nothing is allocated and the host is not synchronised. */
+int gns_acn1_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_outage, size_t* bytes);
+int gns_acn1_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                    const float* buses, const float* lines, const float* generators, int64_t Bt,
+                    const int32_t* outages_host, const int32_t* outages_dev, int32_t n_outage, const uint8_t* islanding,
+                    const double* rating, int32_t rating_per_grid,
+                    const double* base_v, const double* base_theta, const uint8_t* base_converged,
+                    double* v, double* theta, double* p_from, double* q_from, double* p_to, double* q_to,
+                    double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
+                    int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

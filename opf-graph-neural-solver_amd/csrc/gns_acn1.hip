@@ -1,0 +1,427 @@
+// Batched AC N-1 contingency screening (include/gns_powerflow.h, "AC contingency screening") on the Newton-Raphson blob.  The outage
+// of a line removes its four Y-bus stamps and nothing else, so the Jacobian of the grid without the line has a subset of the base
+// pattern: the base analysis, its factor slots and its elimination program serve every outage; entries that lose their only line
+// are numeric zeros.  There is no pivoting to upset, and the caller passes the outages that island a bus (the bridges).
+//
+// Mapping: one wave per (grid, outage) pair with Newton-Raphson's LDS image (factor, right-hand side, eight bus vectors) and its
+// iteration, warm-started from the base solution.  The Y-bus: a pre-kernel with a wave per grid writes the base Y-bus of every grid
+// to the workspace once (pf_ybus_row, 16 nnz(Y) bytes per grid); a pair reads its grid's base values and replaces the at most four
+// entries its line touches (ff, tt, ft, tf) by values the wave holds in registers, each recomputed from the entry's stamps without
+// the line, in stamp order: a sum in a fixed order, never a subtraction, the bits a solve of the grid without the line computes.
+// After the iteration a line per lane computes the four branch flows from the line's own stamps (contiguous stores), and the worst
+// loading and the voltage extremes are reduced over the wave with a comparison that does not depend on the order (the extreme
+// value, the lowest index among equals).  No atomics.
+//
+// Not chosen: the pair's whole Y-bus in the workspace (16 nnz(Y) bytes per pair: 0.3 GB at 256 case118 grids and 166 outages, and
+// the wrapper would slice the outage list); it would let the iteration read Y without the four compares per entry.
+//
+// gns_pf_kernel's loop is restated here rather than shared: pf_solve_grid stays as it is (its comments record what sharing cost).
+#include <hip/hip_runtime.h>
+
+#include "../../include/gns_powerflow.h"
+#include "gns_pf_common.h"
+#include "gns_pf_device.h"
+
+namespace {
+
+// Stamp `kind` (0 ff, 1 tt, 2 ft, 3 tf) of line e as (Re, Im): pf_ybus_row's arithmetic, expression for expression
+__device__ __forceinline__ double2 acn1_stamp(const float* line, const int e, const int kind) {
+  const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
+  const double den = r * r + x * x;
+  const double ysr = r / den, ysi = -x / den;
+  double ar, ai;
+  if (kind == 0) { ar = ysr / (tau * tau); ai = (ysi + 0.5 * b) / (tau * tau); }
+  else if (kind == 1) { ar = ysr; ai = ysi + 0.5 * b; }
+  else {
+    const double c = cos(sh), s = kind == 2 ? sin(sh) : -sin(sh);   // -y_s e^{+-j shift} / tau
+    ar = -(ysr * c - ysi * s) / tau;
+    ai = -(ysr * s + ysi * c) / tau;
+  }
+  return make_double2(ar, ai);
+}
+
+// Entry p of row i of the Y-bus without line k: pf_ybus_row's sum over the entry's stamps in their order, line k's skipped
+__device__ __forceinline__ double2 acn1_entry_without(const int i, const int p, const int k, const int32_t* y_diag,
+                                                      const int32_t* st_ptr, const int32_t* st, const float* bus, const float* line) {
+  double yr = 0.0, yi = 0.0;
+  if (p == y_diag[i]) { yr = (double)bus[i * 6 + 4]; yi = (double)bus[i * 6 + 5]; }
+  for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
+    const int e = st[q] >> 2;
+    if (e == k) continue;
+    const double2 a = acn1_stamp(line, e, st[q] & 3);
+    yr += a.x; yi += a.y;
+  }
+  return make_double2(yr, yi);
+}
+
+// The Y-bus entry (i, k) of the blob's CSR pattern (columns ascending), -1 if it is not there
+__device__ __forceinline__ int acn1_find_entry(const int32_t* y_ptr, const int32_t* y_col, const int i, const int k) {
+  int lo = y_ptr[i], hi = y_ptr[i + 1];
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (y_col[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < y_ptr[i + 1] && y_col[lo] == k ? lo : -1;
+}
+
+// The 0-based ends of line e from its id columns (those the blob was prepared from); false unless both are buses of the grid
+__device__ __forceinline__ bool acn1_line_ends(const float* line, const int e, const int N, int& f, int& t) {
+  const float ff = line[e * 7 + 0], ft = line[e * 7 + 1];
+  f = (int)ff - 1; t = (int)ft - 1;
+  return ff == (float)(f + 1) && ft == (float)(t + 1) && f >= 0 && f < N && t >= 0 && t < N;
+}
+
+// The Y-bus of a pair: the grid's base values, but for the entries at p[0..3] (the outaged line's ff, tt, ft, tf; all one entry for
+// a line from a bus to itself), which read y[0..3].  The same in every lane.
+struct Acn1Ybus {
+  const double2* base;
+  int p[4];
+  double2 y[4];
+  __device__ __forceinline__ double2 at(const int q) const {
+    double2 v = base[q];
+    if (q == p[0]) v = y[0];
+    if (q == p[1]) v = y[1];
+    if (q == p[2]) v = y[2];
+    if (q == p[3]) v = y[3];
+    return v;
+  }
+};
+
+// Row i (not the slack) of the Jacobian into its factor slots: gns_powerflow.hip's pf_jacobian_row on the pair's Y-bus
+__device__ __forceinline__ void acn1_jacobian_row(const int i, const int slack, const int32_t* y_ptr, const int32_t* y_col,
+                                                  const int32_t* jslot, const Acn1Ybus& Y, const double* Vm, const double* Vr,
+                                                  const double* Vi, const double* Ir, const double* Ii, double* F) {
+  const double vri = Vr[i], vii = Vi[i];
+  for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
+    const int k = y_col[p];
+    if (k == slack) continue;
+    const double2 y = Y.at(p);
+    const double a = y.x * Vr[k] - y.y * Vi[k], b = y.x * Vi[k] + y.y * Vr[k];   // Y_ik V_k
+    const double cr = vri * a + vii * b, ci = vii * a - vri * b;                 // V_i conj(Y_ik V_k)
+    double dar = ci, dai = -cr;                                                  // dS_i / dtheta_k
+    double dmr = cr, dmi = ci;                                                   // |V_k| dS_i / d|V_k|
+    if (k == i) {
+      const double P = vri * Ir[i] + vii * Ii[i], Q = vii * Ir[i] - vri * Ii[i];
+      dar -= Q; dai += P;
+      dmr += P; dmi += Q;
+    }
+    dmr /= Vm[k]; dmi /= Vm[k];
+    const int s0 = jslot[4 * p], s1 = jslot[4 * p + 1], s2 = jslot[4 * p + 2], s3 = jslot[4 * p + 3];
+    if (s0 >= 0) F[s0] = dar;
+    if (s1 >= 0) F[s1] = dmr;
+    if (s2 >= 0) F[s2] = dai;
+    if (s3 >= 0) F[s3] = dmi;
+  }
+}
+
+// Whether v at index i comes before the best so far (at index bi): larger, or equal at a lower index; NaN comes before everything
+__device__ __forceinline__ bool acn1_before(const double v, const int i, const double best, const int bi) {
+  if (v != v) return best == best || i < bi;
+  if (best != best) return false;
+  return v > best || (v == best && i < bi);
+}
+
+// The first of the wave's (best, bi) in acn1_before's order, in every lane: a total order, so the tree's shape does not matter
+__device__ __forceinline__ void acn1_wave_first(double& best, int& bi) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(best, o);
+    const int oi = __shfl_xor(bi, o);
+    if (acn1_before(ov, oi, best, bi)) { best = ov; bi = oi; }
+  }
+}
+
+// The outputs of a call: rows [Bt * K] of the (grid, outage) pairs.  v, theta and each of the four flows may be NULL: not written.
+struct Acn1Out {
+  double* v;            // [Bt,K,N]
+  double* theta;
+  double* p_from;       // [Bt,K,E]
+  double* q_from;
+  double* p_to;
+  double* q_to;
+  double* worst;        // [Bt,K]
+  int32_t* worst_line;
+  double* v_min;
+  int32_t* v_min_bus;
+  double* v_max;
+  int32_t* v_max_bus;
+  uint8_t* conv;
+  int32_t* iters;
+  double* mis;
+};
+
+// NaN / -1 / converged 0 / iterations -1 in row `row`
+__device__ __forceinline__ void acn1_row_not_solved(const Acn1Out& o, const size_t row, const int N, const int E) {
+  const double nan = __builtin_nan("");
+  const int lane = threadIdx.x;
+  for (int i = lane; i < N; i += PF_THREADS) {
+    if (o.v) o.v[row * N + i] = nan;
+    if (o.theta) o.theta[row * N + i] = nan;
+  }
+  for (int l = lane; l < E; l += PF_THREADS) {
+    if (o.p_from) o.p_from[row * E + l] = nan;
+    if (o.q_from) o.q_from[row * E + l] = nan;
+    if (o.p_to) o.p_to[row * E + l] = nan;
+    if (o.q_to) o.q_to[row * E + l] = nan;
+  }
+  if (lane == 0) {
+    o.worst[row] = nan; o.worst_line[row] = -1;
+    o.v_min[row] = nan; o.v_min_bus[row] = -1;
+    o.v_max[row] = nan; o.v_max_bus[row] = -1;
+    o.conv[row] = 0; o.iters[row] = -1; o.mis[row] = nan;
+  }
+}
+
+// The base Y-bus of every grid into the workspace: a wave per grid, a row per lane (what gns_pf_kernel writes for itself)
+__global__ __launch_bounds__(PF_THREADS) void gns_acn1_ybus_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
+                                                                   const float* __restrict__ lines, double2* __restrict__ ybus_ws) {
+  const int g = blockIdx.x;
+  const int N = topo[PH_N], E = topo[PH_E], nnzY = topo[PH_NNZY];
+  const int32_t* y_ptr = topo + topo[PH_Y_PTR];
+  const int32_t* y_diag = topo + topo[PH_Y_DIAG];
+  const int32_t* st_ptr = topo + topo[PH_ST_PTR];
+  const int32_t* st = topo + topo[PH_ST];
+  const float* bus = buses + (size_t)g * N * 6;
+  const float* line = lines + (size_t)g * E * 7;
+  double2* Y = ybus_ws + (size_t)g * nnzY;
+  for (int i = threadIdx.x; i < N; i += PF_THREADS) pf_ybus_row(i, y_ptr, y_diag, st_ptr, st, bus, line, Y);
+}
+
+// Pair blockIdx.x = grid * K + position in the outage list
+__global__ __launch_bounds__(PF_THREADS) void gns_acn1_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
+                                                              const float* __restrict__ lines, const float* __restrict__ gens,
+                                                              const int32_t* __restrict__ outages, const int K,
+                                                              const uint8_t* __restrict__ islanding,
+                                                              const double* __restrict__ rating, const int rating_per_grid,
+                                                              const double* __restrict__ v0, const double* __restrict__ th0,
+                                                              const uint8_t* __restrict__ conv0,
+                                                              const double2* __restrict__ ybus_ws, const int max_iter,
+                                                              const double tol, const Acn1Out o) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x;
+  const size_t row = blockIdx.x;
+  const int g = (int)(blockIdx.x / (unsigned)K), j = (int)(blockIdx.x % (unsigned)K);
+  const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN], slack = topo[PH_SLACK], dim = topo[PH_DIM];
+  const int nnzLU = topo[PH_NNZLU], nnzY = topo[PH_NNZY], nsteps = topo[PH_NSTEPS];
+  const int32_t* role = topo + topo[PH_ROLE];
+  const int32_t* th_idx = topo + topo[PH_TH_IDX];
+  const int32_t* vm_idx = topo + topo[PH_VM_IDX];
+  const int32_t* gen_ptr = topo + topo[PH_GEN_PTR];
+  const int32_t* gen_idx = topo + topo[PH_GEN_IDX];
+  const int32_t* y_ptr = topo + topo[PH_Y_PTR];
+  const int32_t* y_col = topo + topo[PH_Y_COL];
+  const int32_t* y_diag = topo + topo[PH_Y_DIAG];
+  const int32_t* st_ptr = topo + topo[PH_ST_PTR];
+  const int32_t* st = topo + topo[PH_ST];
+  const int32_t* jslot = topo + topo[PH_JSLOT];
+  const int32_t* pivot = topo + topo[PH_PIVOT];
+  const int32_t* step_ptr = topo + topo[PH_STEP_PTR];
+  const int2* ops = reinterpret_cast<const int2*>(topo + topo[PH_OPS]);
+  const float* bus = buses + (size_t)g * N * 6;
+  const float* line = lines + (size_t)g * E * 7;
+  const float* gen = gens + (size_t)g * Gn * 7;
+
+  // the pair's Y-bus, or a row that is not solved: an islanding outage, a grid without a base solution, a line that is not one of
+  // the grid's (its index, or its id columns against the blob's pattern).  The same decision in every lane.
+  const int k = outages[j];
+  int f = 0, t = 0;
+  bool ok = k >= 0 && k < E && !islanding[j] && conv0[g] != 0;
+  ok = ok && acn1_line_ends(line, k, N, f, t);
+  Acn1Ybus Y;
+  Y.base = ybus_ws + (size_t)g * nnzY;
+  if (ok) {
+    Y.p[0] = y_diag[f];
+    Y.p[1] = y_diag[t];
+    Y.p[2] = acn1_find_entry(y_ptr, y_col, f, t);
+    Y.p[3] = acn1_find_entry(y_ptr, y_col, t, f);
+    ok = Y.p[2] >= 0 && Y.p[3] >= 0;
+  }
+  if (!ok) { acn1_row_not_solved(o, row, N, E); return; }
+  Y.y[0] = acn1_entry_without(f, Y.p[0], k, y_diag, st_ptr, st, bus, line);
+  Y.y[1] = acn1_entry_without(t, Y.p[1], k, y_diag, st_ptr, st, bus, line);
+  Y.y[2] = acn1_entry_without(f, Y.p[2], k, y_diag, st_ptr, st, bus, line);
+  Y.y[3] = acn1_entry_without(t, Y.p[3], k, y_diag, st_ptr, st, bus, line);
+
+  double* F = lds;                       // [nnzLU] factor, then [dim] right-hand side / Newton step: gns_pf_kernel's image
+  double* rhs = lds + nnzLU;
+  double* Vm = rhs + dim;
+  double* Va = Vm + N;
+  double* Vr = Va + N;
+  double* Vi = Vr + N;
+  double* Ir = Vi + N;
+  double* Ii = Ir + N;
+  double* Psp = Ii + N;
+  double* Qsp = Psp + N;
+
+  // specified injections, bus roles and set points as in the base case; the warm start from the base solution
+  for (int i = lane; i < N; i += PF_THREADS) {
+    double pg = 0.0;
+    for (int q = gen_ptr[i]; q < gen_ptr[i + 1]; ++q) pg += (double)gen[gen_idx[q] * 7 + 6];
+    Psp[i] = pg - (double)bus[i * 6 + 2];
+    Qsp[i] = -(double)bus[i * 6 + 3];
+    const int ro = role[i];
+    double vm = 1.0, va = 0.0;
+    if (ro != 0 && gen_ptr[i + 1] > gen_ptr[i]) vm = (double)gen[gen_idx[gen_ptr[i]] * 7 + 4];
+    if (ro == 0) vm = v0[(size_t)g * N + i];
+    if (ro != 2) va = th0[(size_t)g * N + i] - th0[(size_t)g * N + slack];
+    Vm[i] = vm; Va[i] = va;
+  }
+  __syncthreads();
+
+  int it = 0;
+  bool conv = false;
+  double mis = 0.0;
+  for (;;) {
+    for (int i = lane; i < N; i += PF_THREADS) { Vr[i] = Vm[i] * cos(Va[i]); Vi[i] = Vm[i] * sin(Va[i]); }
+    __syncthreads();
+    // mismatch F = [Re(V conj(YV)) - P ; Im(...) - Q] into the right-hand side, and its infinity norm
+    double nrm = 0.0;
+    bool bad = false;
+    for (int i = lane; i < N; i += PF_THREADS) {
+      double ir = 0.0, ii = 0.0;                 // I_i = sum_k Y_ik V_k: pf_row_current's sum on the pair's Y-bus
+      for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
+        const int c = y_col[p];
+        const double2 y = Y.at(p);
+        ir += y.x * Vr[c] - y.y * Vi[c];
+        ii += y.x * Vi[c] + y.y * Vr[c];
+      }
+      Ir[i] = ir; Ii[i] = ii;
+      if (th_idx[i] >= 0) {
+        const double fp = (Vr[i] * ir + Vi[i] * ii) - Psp[i];
+        rhs[th_idx[i]] = fp;
+        nrm = fmax(nrm, fabs(fp));
+        bad |= !pf_finite(fp);
+      }
+      if (vm_idx[i] >= 0) {
+        const double fq = (Vi[i] * ir - Vr[i] * ii) - Qsp[i];
+        rhs[vm_idx[i]] = fq;
+        nrm = fmax(nrm, fabs(fq));
+        bad |= !pf_finite(fq);
+      }
+    }
+    nrm = pf_wave_max(nrm);
+    if (__ballot(bad)) { mis = __builtin_nan(""); break; }
+    mis = nrm;
+    if (nrm < tol) { conv = true; break; }
+    if (it >= max_iter) break;
+
+    // Jacobian into its factor slots; fill slots, and the entries that lost their only line, are zeros
+    for (int s = lane; s < nnzLU; s += PF_THREADS) F[s] = 0.0;
+    __syncthreads();
+    for (int i = lane; i < N; i += PF_THREADS)
+      if (i != slack) acn1_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
+    __syncthreads();
+
+    // the base topology's program: LU factorisation and both triangular solves
+    pf_run_program(nsteps, step_ptr, ops, F, lane);
+
+    // the update, only if every pivot is a finite non-zero and the new iterate is finite
+    bad = pf_bad_pivot(dim, pivot, F, lane);
+    for (int i = lane; i < N; i += PF_THREADS) {
+      if (th_idx[i] >= 0) bad |= !pf_finite(Va[i] - rhs[th_idx[i]]);
+      if (vm_idx[i] >= 0) bad |= !pf_finite(Vm[i] - rhs[vm_idx[i]]);
+    }
+    if (__ballot(bad)) break;
+    for (int i = lane; i < N; i += PF_THREADS) {
+      if (th_idx[i] >= 0) Va[i] -= rhs[th_idx[i]];
+      if (vm_idx[i] >= 0) Vm[i] -= rhs[vm_idx[i]];
+    }
+    __syncthreads();
+    ++it;
+  }
+  // every exit leaves Vr, Vi at the iterate Vm, Va hold: the state the flows and the summaries are computed from
+
+  // the state and the voltage extremes, a bus per lane (the lowest of equal buses)
+  const double inf = __builtin_inf();
+  double lo = -inf, hi = -inf;             // lo holds -|V|: the smallest |V| is the first in acn1_before's order of the negated values
+  int lo_i = INT32_MAX, hi_i = INT32_MAX;
+  for (int i = lane; i < N; i += PF_THREADS) {
+    const double vm = Vm[i];
+    if (o.v) o.v[row * N + i] = vm;
+    if (o.theta) o.theta[row * N + i] = Va[i];
+    if (acn1_before(-vm, i, lo, lo_i)) { lo = -vm; lo_i = i; }
+    if (acn1_before(vm, i, hi, hi_i)) { hi = vm; hi_i = i; }
+  }
+  acn1_wave_first(lo, lo_i);
+  acn1_wave_first(hi, hi_i);
+
+  // the branch flows, a line per lane: S_f = V_f conj(Y_ff V_f + Y_ft V_t), S_t = V_t conj(Y_tf V_f + Y_tt V_t) on the line's own
+  // stamps; zeros at the outaged line; NaN at a line whose id columns are not buses of the grid
+  const double* rt = rating ? rating + (rating_per_grid ? (size_t)g * E : 0) : nullptr;
+  double best = -1.0;
+  int bi = INT32_MAX;
+  for (int l = lane; l < E; l += PF_THREADS) {
+    double pf = 0.0, qf = 0.0, pt = 0.0, qt = 0.0;
+    int a, b;
+    if (!acn1_line_ends(line, l, N, a, b)) pf = qf = pt = qt = __builtin_nan("");
+    else if (l != k) {
+      const double2 yff = acn1_stamp(line, l, 0), ytt = acn1_stamp(line, l, 1), yft = acn1_stamp(line, l, 2), ytf = acn1_stamp(line, l, 3);
+      const double far = Vr[a], fai = Vi[a], tor = Vr[b], toi = Vi[b];
+      const double ifr = (yff.x * far - yff.y * fai) + (yft.x * tor - yft.y * toi);
+      const double ifi = (yff.x * fai + yff.y * far) + (yft.x * toi + yft.y * tor);
+      const double itr = (ytf.x * far - ytf.y * fai) + (ytt.x * tor - ytt.y * toi);
+      const double iti = (ytf.x * fai + ytf.y * far) + (ytt.x * toi + ytt.y * tor);
+      pf = far * ifr + fai * ifi; qf = fai * ifr - far * ifi;
+      pt = tor * itr + toi * iti; qt = toi * itr - tor * iti;
+    }
+    if (o.p_from) o.p_from[row * E + l] = pf;
+    if (o.q_from) o.q_from[row * E + l] = qf;
+    if (o.p_to) o.p_to[row * E + l] = pt;
+    if (o.q_to) o.q_to[row * E + l] = qt;
+    const double sf = sqrt(pf * pf + qf * qf), s_t = sqrt(pt * pt + qt * qt);
+    const double s = sf != sf ? sf : s_t != s_t ? s_t : fmax(sf, s_t);   // NaN from either end
+    const double load = rt ? s / rt[l] : s;
+    if (acn1_before(load, l, best, bi)) { best = load; bi = l; }
+  }
+  acn1_wave_first(best, bi);
+
+  if (lane == 0) {
+    o.worst[row] = best; o.worst_line[row] = bi;
+    o.v_min[row] = -lo; o.v_min_bus[row] = lo_i;
+    o.v_max[row] = hi; o.v_max_bus[row] = hi_i;
+    o.conv[row] = conv ? 1 : 0; o.iters[row] = it; o.mis[row] = mis;
+  }
+}
+
+}  // namespace
+
+extern "C" int gns_acn1_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_outage, size_t* bytes) {
+  if (!cfg || !topo_host || !bytes || Bt <= 0 || n_outage <= 0) return GNS_EINVAL;
+  const int32_t* h = static_cast<const int32_t*>(topo_host);
+  if (!pf_header_ok<PfBlobKind>(cfg, h)) return GNS_EINVAL;
+  *bytes = pf_ws_bytes_nnzy(h[PH_NNZY], Bt);          // one base Y-bus per grid, whatever the number of outages
+  return GNS_OK;
+}
+
+extern "C" int gns_acn1_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                               const float* buses, const float* lines, const float* generators, int64_t Bt,
+                               const int32_t* outages_host, const int32_t* outages_dev, int32_t n_outage, const uint8_t* islanding,
+                               const double* rating, int32_t rating_per_grid,
+                               const double* base_v, const double* base_theta, const uint8_t* base_converged,
+                               double* v, double* theta, double* p_from, double* q_from, double* p_to, double* q_to,
+                               double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
+                               int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (!pf_config_ok(cfg) || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF ||
+      !outages_host || !outages_dev || n_outage <= 0 || !islanding || (rating_per_grid != 0 && rating_per_grid != 1) || !base_v ||
+      !base_theta || !base_converged || !worst_loading || !worst_line || !v_min || !v_min_bus || !v_max || !v_max_bus || !converged ||
+      !iterations || !mismatch || !workspace)
+    return GNS_EINVAL;
+  const int32_t* h = static_cast<const int32_t*>(topo_host);
+  if (!pf_header_ok<PfBlobKind>(cfg, h)) return GNS_EINVAL;
+  for (int32_t k = 0; k < n_outage; ++k)
+    if (outages_host[k] < 0 || outages_host[k] >= h[PH_E]) return GNS_EINVAL;
+  if (Bt > 0x7FFFFFFF / (int64_t)n_outage) return GNS_EINVAL;           // a workgroup per (grid, outage) in one launch
+  int64_t lds = 0;
+  const int rc = pf_check_topology<PfBlobKind>(cfg, h, Bt, workspace_bytes, &lds);
+  if (rc != GNS_OK) return rc;
+  const int32_t* topo = static_cast<const int32_t*>(topo_dev);
+  double2* ybus = static_cast<double2*>(workspace);
+  const int rc0 = pf_launch<gns_acn1_ybus_kernel>(Bt, 0, stream, topo, buses, lines, ybus);
+  if (rc0 != GNS_OK) return rc0;
+  const Acn1Out out = {v, theta, p_from, q_from, p_to, q_to, worst_loading, worst_line, v_min, v_min_bus, v_max, v_max_bus,
+                       converged, iterations, mismatch};
+  return pf_launch<gns_acn1_kernel>(Bt * n_outage, lds, stream, topo, buses, lines, generators, outages_dev, (int)n_outage, islanding,
+                                    rating, (int)rating_per_grid, base_v, base_theta, base_converged, (const double2*)ybus,
+                                    cfg->max_iter, cfg->tol, out);
+}

@@ -25,6 +25,10 @@ the same factor (``gns_dc_adjoint``).
 more solve per outage gives the exact post-outage DC flows (line-outage distribution factors, ``csrc/gns_dcn1.hip``), with the worst
 loading and its line per ``(grid, outage)``; outages that disconnect the grid are found on the host as the bridges of the topology.
 With ``differentiable=True`` its backward is one ``gns_dcn1_adjoint`` call: a second solve on the base factor per outage.
+
+``ac_contingency_screen(...)`` is the AC answer to the same question: Newton-Raphson on every ``(grid, outage)`` pair, warm-started
+from the base solution, on the base topology's analysis alone (an outage only removes Jacobian entries), with the post-outage
+voltages, the branch flows at both ends of every line, the worst loading and the voltage extremes (``csrc/gns_acn1.hip``).
 """
 from __future__ import annotations
 
@@ -46,6 +50,10 @@ DcPowerFlowResult = namedtuple('DcPowerFlowResult', ['v', 'theta', 'line_flow', 
 
 DcContingencyResult = namedtuple('DcContingencyResult', ['base', 'outages', 'line_flow', 'worst_loading', 'worst_line', 'islanding',
                                                          'converged'])
+
+AcContingencyResult = namedtuple('AcContingencyResult', ['base', 'outages', 'v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to',
+                                                         'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max', 'v_max_bus',
+                                                         'converged', 'iterations', 'mismatch', 'islanding'])
 
 MixedPlan = namedtuple('MixedPlan', ['topology', 'order', 'grid_off', 'member_off', 'topo_set', 'slack_bus', 'islanded'])
 
@@ -130,6 +138,7 @@ _DC = _Solver('gns_dc', FdTopology, _DC_LDS_FORMULA)     # DC runs on the fast-d
 _DCN1_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per workgroup: DC's image, three doubles per line and "
                      "the right-hand sides of W outages side by side, here with W = 1, the narrowest")
 _DCN1 = _Solver('gns_dcn1', FdTopology, _DCN1_LDS_FORMULA)   # the DC contingency screen: the same analysis again
+_ACN1 = _Solver('gns_acn1', PowerFlowTopology, _LDS_FORMULA)   # the AC contingency screen: Newton-Raphson's analysis and LDS image
 _DCN1_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W) bytes per workgroup: the screen's image, a second "
                              "array of W right-hand sides for the adjoint solves and three doubles per outage, here with W = 1, the "
                              "narrowest")
@@ -758,7 +767,8 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     ``~islanding``); otherwise, and for a grid that is not solved, the grid's three gradient rows are NaN (zero rows for an
     unsolved grid whose incoming gradients are all zero).  The forward outputs are bit-identical with and without gradients.  A
     grid's gradient is bit-identical alone, in any batch and from run to run for the same outage list; the order of the list may
-    change its last bits.  N-2 outages, mixed topologies and an AC screen are out of scope.
+    change its last bits.  N-2 outages and mixed topologies are out of scope; the AC screen is ``ac_contingency_screen``, whose
+    gradients are out of scope.
     Contract: ``include/gns_powerflow.h``, "DC contingency screening"."""
     if not isinstance(flows, bool):
         raise ValueError(f'flows must be a bool, got {flows!r}')
@@ -853,6 +863,107 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
             res = [None if t is None else t[0] for t in res]
             conv = conv[0]
         return DcContingencyResult(DcPowerFlowResult(*base), outages_t, res[0], res[1], res[2], islanding, conv)
+
+
+def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, outages=None, rating=None,
+                          tol=1e-8, max_iter=10, flows=True, states=True):
+    """AC N-1 contingency screening of every grid of a batch, on the device: Newton-Raphson on each ``(grid, outage)`` pair of the
+    single-line outages of ``outages``, with the post-outage voltages, the apparent-power flows at both ends of every line, the
+    worst loading and the voltage extremes.  An outage removes the line's four Y-bus stamps and nothing else, so the Jacobian of
+    every pair has a subset of the base sparsity: the one analysis of the base topology (``newton_raphson``'s, cached) serves every
+    outage, where ``newton_raphson(mixed_topologies=True)`` on the expanded batch analyses one topology per outage and holds a copy
+    of the inputs per pair.
+
+    Inputs, column maps, the slack and the device handling are those of ``newton_raphson``; the whole batch shares one topology.
+    ``outages``: a 1-D sequence or tensor of 0-based line indices, default every line; duplicates are independent rows.
+    ``rating``: None (1: the loading is ``max(|S_from|, |S_to|)``), ``[E]`` or ``[Bt,E]``, positive and finite, used in float64.
+    ``tol``, ``max_iter``: Newton-Raphson's, for the base solve and for every pair.
+
+    Row ``(g, k)`` is Newton-Raphson on grid ``g`` with line ``outages[k]`` out of service: the Y-bus from the line stamps without
+    that line's, the injections, bus roles and ``vg`` set points unchanged, warm-started from ``base.v[g]``, ``base.theta[g]``; the
+    convergence test, update, failure rules and float64 arithmetic of ``include/gns_powerflow.h``.
+
+    Returns ``AcContingencyResult``:
+      base           the ``PowerFlowResult`` of ``newton_raphson`` on the same inputs with the same ``tol`` and ``max_iter``, bit for bit
+      outages        ``[K]`` int64
+      v, theta       ``[Bt,K,N]`` float64, the post-outage state; None with ``states=False``
+      p_from, q_from, p_to, q_to   ``[Bt,K,E]`` float64, MATPOWER's branch model on the makeYbus quantities: ``S_f = V_f conj(Y_ff V_f +
+                     Y_ft V_t)``, ``S_t = V_t conj(Y_tf V_f + Y_tt V_t)``; all four 0 at the outaged line; None with ``flows=False``
+      worst_loading  ``[Bt,K]`` float64, ``max_l max(|S_f|, |S_t|) / rating_l``;  worst_line ``[Bt,K]`` int32, the lowest of equals
+      v_min, v_max   ``[Bt,K]`` float64 with v_min_bus, v_max_bus ``[Bt,K]`` int32 (0-based, the lowest of equals)
+      converged, iterations, mismatch   ``[Bt,K]`` bool / int32 / float64, Newton-Raphson's own meaning per row
+      islanding      ``[K]`` bool: the outage disconnects the grid (a bridge of the topology, found on the host once per topology)
+    An islanding outage has NaN / -1 / ``converged`` False / ``iterations`` -1 in every grid; so has every row of a grid whose base
+    solve did not converge.  A row that does not converge keeps its last finite iterate with ``converged`` False, as
+    ``newton_raphson`` does, and its flows and summaries are computed from that iterate.  Every row is bit-identical alone, in any
+    batch, in any list or order that holds the outage and from run to run.  With a 2-D single grid the batch dimension is dropped.
+
+    Out of scope: gradients (the outputs are not differentiable and the call runs as under ``torch.no_grad()``), batches that mix
+    topologies, N-2 outages and generator reactive limits.  Contract: ``include/gns_powerflow.h``, "AC contingency screening"."""
+    if not isinstance(flows, bool):
+        raise ValueError(f'flows must be a bool, got {flows!r}')
+    if not isinstance(states, bool):
+        raise ValueError(f'states must be a bool, got {states!r}')
+    if not (isinstance(max_iter, (int, np.integer)) and max_iter >= 0):      # (_inputs' checks, here before a device is needed)
+        raise ValueError(f'max_iter must be a non-negative integer, got {max_iter!r}')
+    if not float(tol) >= 0.0:
+        raise ValueError(f'tol must be >= 0, got {tol!r}')
+    with torch.no_grad():
+        # the shapes first, so that a bad outage list or rating is refused where no device is visible too
+        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
+        out_np = _outage_list(outages, shaped_lines.shape[1])
+        rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None,
+                                                                 None, tol, max_iter, False)
+        lib = load_library()
+        Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
+        rating = None if rating is None else rating.to(dev).contiguous()
+        K = out_np.size
+        cfg = PfConfig(N, E, generators.shape[1], int(max_iter), float(tol))
+        key, args = _topology_key(buses, lines, generators, slack_bus, 'ac_contingency_screen')
+        topo = _analysed(_NR, key, args, dev)
+        isl_np = _topology_bridges(topo, args)[out_np]
+        out32 = out_np.astype(np.int32)
+        out_dev, isl_dev = torch.from_numpy(out32).to(dev), torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
+
+        # the base case as newton_raphson solves it (its refusals come first), then every pair from it
+        base = _solve(lib, _NR, cfg, _one_topology(topo), buses, lines, generators, None, None)
+        base_conv = base[2].to(torch.uint8)
+
+        def f64(n):
+            return torch.empty(Bt, K, n, dtype=torch.float64, device=dev)
+
+        state = [f64(N), f64(N)] if states else [None, None]
+        flow = [f64(E) for _ in range(4)] if flows else [None] * 4
+        row_f64 = [torch.empty(Bt, K, dtype=torch.float64, device=dev) for _ in range(4)]       # worst, v_min, v_max, mismatch
+        row_i32 = [torch.empty(Bt, K, dtype=torch.int32, device=dev) for _ in range(4)]         # their indices, iterations
+        conv = torch.empty(Bt, K, dtype=torch.uint8, device=dev)
+        lds = topo.info['lds_bytes']
+        nbytes = ctypes.c_size_t()
+        _check(lib.gns_acn1_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)),
+               'gns_acn1_workspace_bytes', lds, _ACN1.formula)
+        ws = _gns._workspace(nbytes.value, dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_acn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
+                                       lines.data_ptr(), generators.data_ptr(), Bt, out32.ctypes.data, out_dev.data_ptr(), K,
+                                       isl_dev.data_ptr(), _ptr(rating), int(rating is not None and rating.dim() == 2),
+                                       base[0].data_ptr(), base[1].data_ptr(), base_conv.data_ptr(), *map(_ptr, state),
+                                       *map(_ptr, flow), row_f64[0].data_ptr(), row_i32[0].data_ptr(), row_f64[1].data_ptr(),
+                                       row_i32[1].data_ptr(), row_f64[2].data_ptr(), row_i32[2].data_ptr(), conv.data_ptr(),
+                                       row_i32[3].data_ptr(), row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                   'gns_acn1_screen', lds, _ACN1.formula)
+        res = [*state, *flow, row_f64[0], row_i32[0], row_f64[1], row_i32[1], row_f64[2], row_i32[2], conv.bool(), row_i32[3],
+               row_f64[3]]
+        outages_t, islanding = torch.from_numpy(out_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev)
+        if in_dev != dev:
+            base = [t.to(in_dev) for t in base]
+            res = [None if t is None else t.to(in_dev) for t in res]
+            outages_t, islanding = outages_t.to(in_dev), islanding.to(in_dev)
+        if single:
+            base = [t[0] for t in base]
+            res = [None if t is None else t[0] for t in res]
+        return AcContingencyResult(PowerFlowResult(*base), outages_t, *res, islanding)
 
 
 def _not_solved(Bt, N, dev):

@@ -462,6 +462,7 @@ int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  *   columns, which must be those the blob was prepared from (a line whose ids are not buses of the grid gets NaN flows).
  *   worst_loading = max_l max(|S_f|, |S_t|) / rating_l (rating NULL: 1) and worst_line the 0-based line that attains it; v_min, v_max
  *   the extremes of |V| over the buses and v_min_bus, v_max_bus the 0-based buses that attain them; the lowest index among equals.
+ *   A NaN loading or voltage wins its summary, at the lowest index that holds one: the value is NaN, the index that line or bus.
  *   Islanding: the caller finds the outages that disconnect the graph (the bridges of the topology) and passes islanding[n_outage]
  *   (1: bridge); the kernel does not decide that numerically.  Those rows get NaN in every fp64 output, -1 in worst_line, v_min_bus,
  *   v_max_bus and iterations, and converged = 0, in every grid.  So does every row of a grid with base_converged = 0, and a row

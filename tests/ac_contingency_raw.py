@@ -1,0 +1,77 @@
+"""``gns_acn1_screen`` (include/gns_powerflow.h, "AC contingency screening") called through ctypes on device tensors, with the base
+solution, ``base_converged`` and ``islanding`` supplied by the caller as the C contract has it.  ``powerflow.ac_contingency_screen``
+computes those three itself and applies ``max_iter`` to its base solve too, so zero or one Newton step of a row, a base angle that
+is not 0 at the slack and caller-owned flags are reachable only from here."""
+import ctypes
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+import opf_graph_neural_solver_amd as amd
+from opf_graph_neural_solver_amd import gns as gns_mod
+from opf_graph_neural_solver_amd import powerflow
+from opf_graph_neural_solver_amd._lib import PfConfig
+
+ROWS = ('v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to', 'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max', 'v_max_bus',
+        'converged', 'iterations', 'mismatch')
+Rows = namedtuple('Rows', ROWS)
+_TOPO = {}
+
+
+def analysed(tp, device):
+    """The Newton-Raphson analysis of ``tp`` (from its own id arrays, never from a grid's id columns), made once per name."""
+    key = (tp.name, str(device))
+    if key not in _TOPO:
+        _TOPO[key] = powerflow.analyse_topology(tp.n, tp.f, tp.t, tp.g, tp.slack, device=device)
+    return _TOPO[key]
+
+
+def screen(tp, buses, lines, gens, outages, base_v, base_theta, base_converged, islanding, rating, max_iter, tol):
+    """One ``gns_acn1_screen`` launch on the current stream: ``buses`` [Bt,N,6], ``lines`` [Bt,E,7], ``gens`` [Bt,Gn,7] float32 on
+    the device, ``outages`` and ``islanding`` sequences [K], ``base_v``, ``base_theta`` [Bt,N], ``base_converged`` [Bt], ``rating``
+    None, [E] or [Bt,E].  Returns ``Rows``: the fifteen outputs ([Bt,K,...], ``converged`` as bool), every one pre-filled with a
+    sentinel that no row may keep."""
+    lib = amd.load_library()
+    dev = buses.device
+    Bt, N, E = buses.shape[0], tp.n, tp.f.size
+    assert buses.shape == (Bt, N, 6) and lines.shape == (Bt, E, 7) and gens.shape == (Bt, tp.g.size, 7)
+    buses, lines, gens = (t.contiguous() for t in (buses, lines, gens))
+    assert buses.dtype == lines.dtype == gens.dtype == torch.float32
+    topo = analysed(tp, dev)
+    out32 = np.ascontiguousarray(np.asarray(outages, dtype=np.int32).reshape(-1))
+    K = out32.size
+    out_dev = torch.from_numpy(out32).to(dev)
+    isl = torch.as_tensor(np.asarray(islanding).astype(np.uint8).reshape(K)).to(dev)
+    v0 = torch.as_tensor(base_v, dtype=torch.float64).to(dev).contiguous()
+    th0 = torch.as_tensor(base_theta, dtype=torch.float64).to(dev).contiguous()
+    conv0 = torch.as_tensor(np.asarray(base_converged).astype(np.uint8).reshape(Bt)).to(dev)
+    assert v0.shape == th0.shape == (Bt, N)
+    per_grid = 0
+    if rating is not None:
+        rating = torch.as_tensor(rating, dtype=torch.float64).to(dev).contiguous()
+        assert rating.shape in ((E,), (Bt, E))
+        per_grid = int(rating.dim() == 2)
+    cfg = PfConfig(N, E, tp.g.size, int(max_iter), float(tol))
+    need = ctypes.c_size_t()
+    assert lib.gns_acn1_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(need)) == 0
+    ws = gns_mod._workspace(need.value, dev)
+    sentinel = -12345.0
+    f64 = [torch.full((Bt, K, n), sentinel, dtype=torch.float64, device=dev) for n in (N, N, E, E, E, E)]
+    row_f64 = [torch.full((Bt, K), sentinel, dtype=torch.float64, device=dev) for _ in range(4)]        # worst, v_min, v_max, mismatch
+    row_i32 = [torch.full((Bt, K), -7, dtype=torch.int32, device=dev) for _ in range(4)]               # their indices, iterations
+    conv = torch.full((Bt, K), 7, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = lib.gns_acn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                                 gens.data_ptr(), Bt, out32.ctypes.data, out_dev.data_ptr(), K, isl.data_ptr(),
+                                 None if rating is None else rating.data_ptr(), per_grid, v0.data_ptr(), th0.data_ptr(),
+                                 conv0.data_ptr(), *(t.data_ptr() for t in f64), row_f64[0].data_ptr(), row_i32[0].data_ptr(),
+                                 row_f64[1].data_ptr(), row_i32[1].data_ptr(), row_f64[2].data_ptr(), row_i32[2].data_ptr(),
+                                 conv.data_ptr(), row_i32[3].data_ptr(), row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        assert rc == 0, rc
+        torch.cuda.synchronize(dev)
+    assert bool((conv <= 1).all()) and bool((row_i32[3] >= -1).all())
+    for t in f64 + row_f64:
+        assert not bool((t == sentinel).any())
+    return Rows(*f64, row_f64[0], row_i32[0], row_f64[1], row_i32[1], row_f64[2], row_i32[2], conv.bool(), row_i32[3], row_f64[3])

@@ -105,6 +105,15 @@ def many_generators_and_lines(n=150):
     return Topo(f'hub{n}_70lines_70gens', n, *_ids(f, t, g), 1)
 
 
+def wheel(n=71):
+    """Hub bus 1 joined to each of the rim buses 2..n (n - 1 lines at one bus: 70, more than a wave's 64 lanes) and the rim ring
+    2 - 3 - ... - n - 2: no line is a bridge.  The slack is rim bus 2, so the hub is a PQ bus whose diagonal the solve reads.  Not in
+    ``families()``."""
+    rim = np.arange(2, n + 1)
+    f, t = np.r_[np.ones(n - 1, dtype=np.int64), rim], np.r_[rim, rim[1:], 2]
+    return Topo(f'wheel{n}', n, *_ids(f, t, [2, n // 3, 2 * n // 3]), 2)
+
+
 def _info(tp):
     return powerflow.analyse_topology(tp.n, tp.f, tp.t, tp.g, tp.slack).info
 

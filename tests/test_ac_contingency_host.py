@@ -315,3 +315,54 @@ def test_the_base_blob_serves_every_outage(name):
             assert np.max(np.abs(vm - want.v)) <= 1e-9 and np.max(np.abs(va - want.theta)) <= 1e-9, (name, i, k)
     print(f'{name}: {n_cmp} of {n_pairs} non-islanding pairs compared')
     assert n_cmp >= 0.6 * n_pairs, (name, n_cmp, n_pairs)
+
+
+def shifted_base(tp, v, theta, seed=4):
+    """(base_v, base_theta) float64 numpy [B,N]: ``pt.perturbed_start`` of the manufactured solution with 0.3 rad added to every
+    angle, so that base_theta[slack] = 0.3 and the start's ``theta - theta[slack]`` is a subtraction that matters."""
+    v0, th0 = pt.perturbed_start(v.cpu(), theta.cpu(), tp.slack, seed)
+    return v0.numpy(), (th0 + 0.3).numpy()
+
+
+def one_step_ratios(bus, line, gen, slack_bus, k, vm0, va0, v1, th1):
+    """(scipy's, the given step's) ``pt.one_step_ratio`` on the reference Jacobian and mismatch of the grid with row ``k`` of
+    ``line`` deleted, at the start (vm0, va0); the step is read off the state (v1, th1) one update later."""
+    import scipy.sparse.linalg as spla
+    rest = np.delete(line, k, axis=0)
+    _, pv, pq = nr.roles(bus, gen, slack_bus)
+    pvpq = np.r_[pv, pq]
+    J = nr.jacobian(bus, rest, gen, slack_bus, vm0, va0)
+    F = nr.mismatch_vector(bus, rest, gen, slack_bus, vm0, va0)
+    dx = np.r_[va0[pvpq] - th1[pvpq], vm0[pq] - v1[pq]]
+    return pt.one_step_ratio(J, F, spla.spsolve(J, F)), pt.one_step_ratio(J, F, dx)
+
+
+@pytest.mark.parametrize('regime', pt.REGIMES)
+def test_one_step_of_the_replay_on_every_pair(regime):
+    """One Newton step of the replay from a start with base_theta[slack] = 0.3, on EVERY non-bridge pair (no convergence needed):
+    the step solves the reference Jacobian of the grid with the row deleted to ``pt.STEP_TOL``, scipy's own step asserted first as
+    the guard; after zero steps the state is the reference start exactly.  Pins "the base blob serves every outage" at 100 %."""
+    fam = pt.families()
+    topos = [toy(), fam['random40_parallel_selfloop'], fam['random24_stacked_gens'], pt.ring_slack_without_generator(63)]
+    for tp in topos:
+        buses, lines, gens, v, theta = pt.grids(tp, regime, 2, seed=11)
+        base_v, base_theta = shifted_base(tp, v, theta)
+        w = powerflow.analyse_topology(tp.n, tp.f, tp.t, tp.g, tp.slack).host
+        bridges = powerflow._bridges(tp.n, tp.f - 1, tp.t - 1)
+        n_cmp, worst = 0, 0.0
+        for i in range(2):
+            b, l, g = (x[i].double().numpy() for x in (buses, lines, gens))
+            assert base_theta[i, tp.slack - 1] == 0.3
+            vm0, va0 = nr.start(b, g, tp.slack, base_v[i], base_theta[i])
+            for k in np.flatnonzero(~bridges):
+                z = emulate_row(w, b, l, g, k, base_v[i], base_theta[i], tol=0.0, max_iter=0)
+                assert np.array_equal(z[0], vm0) and np.array_equal(z[1], va0) and z[3] == 0, (tp.name, i, k)
+                v1, th1, conv, it, _ = emulate_row(w, b, l, g, k, base_v[i], base_theta[i], tol=0.0, max_iter=1)
+                assert it == 1 and not conv, (tp.name, i, k)
+                r_scipy, r_replay = one_step_ratios(b, l, g, tp.slack, k, vm0, va0, v1, th1)
+                assert r_scipy <= pt.STEP_TOL, (tp.name, regime, i, k, r_scipy)
+                assert r_replay <= pt.STEP_TOL, (tp.name, regime, i, k, r_replay)
+                worst = max(worst, r_replay)
+                n_cmp += 1
+        print(f'{tp.name} ({regime}): {n_cmp} of {2 * int((~bridges).sum())} non-bridge pairs compared, worst one-step ratio {worst:.1e}')
+        assert n_cmp == 2 * int((~bridges).sum()) > 0

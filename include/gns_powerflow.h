@@ -469,7 +469,8 @@ int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  *   whose line's id columns do not name an entry of the blob's Y-bus pattern.  Other rows are unaffected.
  *   Every (grid, outage) row is bit-identical alone, in any batch, for any outage list or order that holds the outage (duplicates
  *   are independent rows), and from run to run: no atomics, the reductions by a total order.
- *   Not here: gradients, batches that mix topologies (one blob per call), N-2 outages, generator reactive limits.
+ *   Gradients: gns_acn1_adjoint, below.  Not here: batches that mix topologies (one blob per call), N-2 outages, generator
+ *   reactive limits.
  *
  * Inputs: outages as 0-based line indices, on the host (checked before the launch) and on the device (read by the kernel), both
  * [n_outage] int32; islanding [n_outage] uint8 on the device; rating NULL, [E] (rating_per_grid 0) or [Bt,E] (1) fp64 on the device;
@@ -499,6 +500,75 @@ int gns_acn1_screen(const gns_pf_config* cfg, const void* topo_host, const void*
                     double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
                     int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Gradients of the AC screen.  gns_acn1_adjoint takes the inputs of a gns_acn1_screen call (the same outage list, islanding mask and
+ * rating), its outputs v, theta [Bt,n_outage,N], converged, worst_line, v_min_bus, v_max_bus [Bt,n_outage] and the base_converged
+ * [Bt] it was given, and the incoming gradients of a loss of its nine fp64 outputs: grad_v, grad_theta [Bt,n_outage,N], grad_p_from,
+ * grad_q_from, grad_p_to, grad_q_to [Bt,n_outage,E], grad_worst_loading, grad_v_min, grad_v_max [Bt,n_outage] (each may be NULL:
+ * zero).  It writes dl/d(input) into grad_buses [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32, each of which may be
+ * NULL (not computed; with all three NULL nothing is launched).  Every element of each non-NULL output is written (overwritten,
+ * not accumulated).  The state is the forward's: Newton-Raphson is not run again, and the warm start is not differentiated (a
+ * converged row does not depend on it).
+ *
+ * Method, per solved row (grid, k): the implicit function theorem on the grid without line k, F_k(x, p) = 0 with the unknowns x of
+ * "Gradients" above (theta at PV+PQ, |V| at PQ) and J_k = dF_k/dx on the row's Y-bus.
+ *   Effective cotangents: W_f,l = grad_p_from + j grad_q_from and W_t,l = grad_p_to + j grad_q_to of line l != k (line k's flows are
+ *   the constant 0: its entries are ignored); grad_worst_loading adds (p + jq) / |S| / rating_w at w = worst_line to the end of the
+ *   line that attains the maximum (the from end on equality; nothing at |S| = 0); grad_v_min and grad_v_max add to grad_v at
+ *   v_min_bus and v_max_bus (a tie goes to the index the forward reported).
+ *   Right-hand side: dl/dx = the theta and |V| cotangents at the unknowns plus the flows' derivatives, with A = V_f conj(Y_ft V_t),
+ *   D = |V_f|^2 conj(Y_ff), B = V_t conj(Y_tf V_f), C = |V_t|^2 conj(Y_tt) (S_f = D + A, S_t = C + B) and dl = Re(conj(W) dS):
+ *   dS_f/dtheta_f = jA = -dS_f/dtheta_t, dS_t/dtheta_t = jB = -dS_t/dtheta_f, |V_f| dS_f/d|V_f| = 2D + A, |V_t| dS_f/d|V_t| = A,
+ *   |V_t| dS_t/d|V_t| = 2C + B, |V_f| dS_t/d|V_f| = B.
+ *   Solve: J_k^T lambda = dl/dx; J_k is factored by the leading factor steps of the blob's program, then the transposed program
+ *   (PH_T_*) runs, exactly as in gns_pf_adjoint.  One factorisation and one transposed solve per row.
+ *   Gradients: dl/dp = direct - lambda^T dF_k/dp.  The line columns reuse gns_pf_adjoint's stamp algebra with Lambda_f - W_f,l and
+ *   Lambda_t - W_t,l in place of Lambda_f, Lambda_t of line l (the flow term is +Re(conj(W) S) on the line's own stamps where the
+ *   mismatch term is -Re(conj(Lambda) S)); vg gets the total direct dl/d|V_b| (the state cotangent plus the flows' dependence on
+ *   |V_b|) minus lambda^T dF_k/d|V_b|.  Summed over the rows of the list.
+ *
+ * Contract (gns_pf_adjoint's columns): buses cols 2-5 (Pd, Qd, Gs, Bs); lines cols 2-6 (r, x, b, tau, shift); generators col 6 Pg
+ *   and col 4 vg of the first generator listed on a PV / slack bus.  Every other column: 0.  Row k of the screen contributes
+ *   exactly 0 to line k's own columns.  A line whose id columns are not buses of the grid gets a NaN row.  rating is a constant.
+ *   Failure: a row whose incoming gradients are all exactly zero or NULL is skipped, never multiplied by zero (so a loss may mask
+ *   out islanding and unconverged rows by indexing).  A row with converged == 0 (an islanding outage, a stopped or unconverged
+ *   iteration, NaN / -1) and a non-zero incoming gradient, a zero or non-finite pivot, or a non-finite lambda: all three gradient
+ *   rows of that grid are NaN.  A grid with base_converged == 0 gets NaN rows when an incoming gradient of it is non-zero, zero rows
+ *   otherwise.  Other grids are unaffected.
+ *   fp64 throughout, rounded once to fp32.  No atomics, every sum in a fixed order: a grid's gradient is bit-identical alone, in
+ *   any batch and from run to run for the same outage list.  The order and the chunking of the list set the order of the sums
+ *   over rows, so another order of the same outages may change the last bits.
+ *
+ * Kernels (gns_acn1.hip): the pre-kernel of the screen writes the base Y-bus per grid; then one wave per (grid, chunk of C consecutive
+ * outages of the list) with gns_pf_solve's LDS image (gns_pf_info.lds_bytes; lambda in the Psp / Qsp vectors, the direct dl/d|V| in
+ * the theta vector), so every topology the screen accepts the adjoint accepts.  The flow cotangents reach dl/dx by a gather with a
+ * bus per lane: each bus walks the stamps of its diagonal entry, whose kinds 0 and 1 name every incident line and the end it
+ * touches (a line from a bus to itself: once per end); no scatter.  The wave walks its chunk's rows in order and every lane adds
+ * into the addresses it alone owns (a bus, a line or a generator per lane) of the chunk's fp64 partial in the workspace.  A second
+ * kernel, a wave per grid, sums the chunks' partials in order, applies the contract, rounds once and writes every element.
+ * C = min(8, max(1, ceil(n_outage / 32))): from the list's length alone, never from Bt.  Workspace
+ * (gns_acn1_adjoint_workspace_bytes): the base Y-bus (gns_acn1_workspace_bytes' figure) plus Bt * ceil(n_outage / C) partials of
+ * 4 N + 5 E + Gn + 1 doubles (per bus the sums of lambda_P, lambda_Q, |V|^2 lambda_P, |V|^2 lambda_Q; per line its five columns; per
+ * generator dl/dvg; a status), each part rounded up to 256 bytes.
+ *
+ * Errors, in order: GNS_EINVAL for a NULL cfg, blob, input, outage list, islanding mask, v, theta, converged, worst_line, v_min_bus,
+ * v_max_bus or base_converged, a negative max_iter or tol, a blob that is not a Newton-Raphson blob or whose N, E, Gn are not cfg's,
+ * n_outage <= 0, an outage outside 0 .. E-1, rating_per_grid outside {0, 1}, or Bt * ceil(n_outage / C) above 2^31 - 1; then
+ * GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES (from the workspace query too); then, when an output is asked for,
+ * GNS_EINVAL for a NULL workspace and GNS_ESIZE for a short one.  Every refusal comes before any launch; nothing is allocated and
+ * the host is not synchronised. */
+int gns_acn1_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_outage, size_t* bytes);
+int gns_acn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const int32_t* outages_host, const int32_t* outages_dev, int32_t n_outage, const uint8_t* islanding,
+                     const double* rating, int32_t rating_per_grid,
+                     const double* v, const double* theta, const uint8_t* converged, const int32_t* worst_line,
+                     const int32_t* v_min_bus, const int32_t* v_max_bus, const uint8_t* base_converged,
+                     const double* grad_v, const double* grad_theta, const double* grad_p_from, const double* grad_q_from,
+                     const double* grad_p_to, const double* grad_q_to, const double* grad_worst_loading,
+                     const double* grad_v_min, const double* grad_v_max,
+                     float* grad_buses, float* grad_lines, float* grad_generators,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

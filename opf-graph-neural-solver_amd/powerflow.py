@@ -29,6 +29,8 @@ With ``differentiable=True`` its backward is one ``gns_dcn1_adjoint`` call: a se
 ``ac_contingency_screen(...)`` is the AC answer to the same question: Newton-Raphson on every ``(grid, outage)`` pair, warm-started
 from the base solution, on the base topology's analysis alone (an outage only removes Jacobian entries), with the post-outage
 voltages, the branch flows at both ends of every line, the worst loading and the voltage extremes (``csrc/gns_acn1.hip``).
+With ``differentiable=True`` its backward is one ``gns_acn1_adjoint`` call: per pair one factorisation and one transposed solve
+at the forward's state, on the same analysis.
 """
 from __future__ import annotations
 
@@ -767,8 +769,7 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     ``~islanding``); otherwise, and for a grid that is not solved, the grid's three gradient rows are NaN (zero rows for an
     unsolved grid whose incoming gradients are all zero).  The forward outputs are bit-identical with and without gradients.  A
     grid's gradient is bit-identical alone, in any batch and from run to run for the same outage list; the order of the list may
-    change its last bits.  N-2 outages and mixed topologies are out of scope; the AC screen is ``ac_contingency_screen``, whose
-    gradients are out of scope.
+    change its last bits.  N-2 outages and mixed topologies are out of scope; the AC screen is ``ac_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "DC contingency screening"."""
     if not isinstance(flows, bool):
         raise ValueError(f'flows must be a bool, got {flows!r}')
@@ -865,8 +866,31 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
         return DcContingencyResult(DcPowerFlowResult(*base), outages_t, res[0], res[1], res[2], islanding, conv)
 
 
+class _ACN1Function(torch.autograd.Function):
+    """``ac_contingency_screen(differentiable=True)`` when an input requires grad, as ``_DCN1Function``: the forward is the screen's
+    launch (``screen`` returns the fifteen outputs in ``gns_acn1_screen``'s order, ``v`` and ``theta`` always there), the backward
+    one ``gns_acn1_adjoint`` call on the forward's topology, outage list and state.  Newton is not run again."""
+
+    @staticmethod
+    def forward(ctx, screen, adjoint, buses, lines, gens):
+        out = screen(buses, lines, gens)
+        v, theta, _, _, _, _, _, worst_line, _, v_min_bus, _, v_max_bus, conv, iters, mis = out
+        ctx.mark_non_differentiable(worst_line, v_min_bus, v_max_bus, conv, iters, mis)
+        ctx.set_materialize_grads(False)
+        ctx.adjoint = adjoint
+        ctx.save_for_backward(buses, lines, gens, v, theta, conv, worst_line, v_min_bus, v_max_bus)
+        return tuple(out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gv, gth, gpf, gqf, gpt, gqt, gwl, _gwi, gvmin, _gi0, gvmax, _gi1, _gconv, _giters, _gmis):
+        buses, lines, gens, *state = ctx.saved_tensors
+        grads = ctx.adjoint(buses, lines, gens, state, (gv, gth, gpf, gqf, gpt, gqt, gwl, gvmin, gvmax), ctx.needs_input_grad[2:5])
+        return (None, None, *grads)
+
+
 def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, outages=None, rating=None,
-                          tol=1e-8, max_iter=10, flows=True, states=True):
+                          tol=1e-8, max_iter=10, flows=True, states=True, differentiable=False):
     """AC N-1 contingency screening of every grid of a batch, on the device: Newton-Raphson on each ``(grid, outage)`` pair of the
     single-line outages of ``outages``, with the post-outage voltages, the apparent-power flows at both ends of every line, the
     worst loading and the voltage extremes.  An outage removes the line's four Y-bus stamps and nothing else, so the Jacobian of
@@ -898,8 +922,27 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     ``newton_raphson`` does, and its flows and summaries are computed from that iterate.  Every row is bit-identical alone, in any
     batch, in any list or order that holds the outage and from run to run.  With a 2-D single grid the batch dimension is dropped.
 
-    Out of scope: gradients (the outputs are not differentiable and the call runs as under ``torch.no_grad()``), batches that mix
-    topologies, N-2 outages and generator reactive limits.  Contract: ``include/gns_powerflow.h``, "AC contingency screening"."""
+    Gradients: by default the outputs are not differentiable (the call runs as under ``torch.no_grad()``).  With
+    ``differentiable=True``, grad mode on and ``requires_grad`` on an input, ``v``, ``theta``, the four flows, ``worst_loading``,
+    ``v_min`` and ``v_max`` are differentiable through one ``gns_acn1_adjoint`` call on the forward's topology, outage list and state
+    (per row the implicit function theorem on the grid without the line: one factorisation of the row's Jacobian on the base
+    analysis and one transposed solve; Newton is not run again), and ``base.v`` / ``base.theta`` through ``newton_raphson``'s adjoint.
+    The derivative is exact at the returned state with respect to ``newton_raphson``'s columns (``Pd, Qd, Gs, Bs``; the lines'
+    ``r, x, b, tau, shift``; ``Pg`` and the ``vg`` of the first generator on a PV / slack bus); every other column gets 0, and row
+    ``k`` gives exactly 0 to line ``k``'s own columns.  ``rating`` is a constant and the warm start is not differentiated (a
+    converged row does not depend on it).  ``worst_loading`` sends its gradient to ``worst_line``, at the end that attains the
+    maximum (the from end on equality), ``v_min`` / ``v_max`` to the buses reported; the index outputs, ``converged``,
+    ``iterations``, ``mismatch``, ``islanding`` and ``outages`` are not differentiable.  With ``states=False`` / ``flows=False`` the
+    summaries stay differentiable (``v`` and ``theta`` are then kept for the backward, ``16 Bt K N`` bytes, and not returned).  A row
+    whose incoming gradients are all exactly zero or absent is skipped, never multiplied by zero (a loss that indexes ``converged``
+    rows); a non-zero gradient into a row that is not converged (an islanding outage, a stopped iteration), a zero or non-finite
+    pivot or a non-finite lambda makes the grid's three gradient rows NaN; a grid without a base solution gets NaN rows, zero rows
+    when all its incoming gradients are zero.  Other grids are unaffected.  The forward outputs are bit-identical with and without
+    gradients; a grid's gradient is bit-identical alone, in any batch and from run to run for the same outage list (another order
+    of the list may change its last bits).
+
+    Out of scope: batches that mix topologies, N-2 outages and generator reactive limits.
+    Contract: ``include/gns_powerflow.h``, "AC contingency screening"."""
     if not isinstance(flows, bool):
         raise ValueError(f'flows must be a bool, got {flows!r}')
     if not isinstance(states, bool):
@@ -908,53 +951,94 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
         raise ValueError(f'max_iter must be a non-negative integer, got {max_iter!r}')
     if not float(tol) >= 0.0:
         raise ValueError(f'tol must be >= 0, got {tol!r}')
+    if not isinstance(differentiable, bool):
+        raise ValueError(f'differentiable must be a bool, got {differentiable!r}')
+    grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                              for t in (buses, lines, generators))
     with torch.no_grad():
         # the shapes first, so that a bad outage list or rating is refused where no device is visible too
         single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
         out_np = _outage_list(outages, shaped_lines.shape[1])
         rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
-        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None,
-                                                                 None, tol, max_iter, False)
+    with torch.set_grad_enabled(grad):
+        if not grad:
+            buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, tol, max_iter, False)
         lib = load_library()
         Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
         rating = None if rating is None else rating.to(dev).contiguous()
         K = out_np.size
         cfg = PfConfig(N, E, generators.shape[1], int(max_iter), float(tol))
-        key, args = _topology_key(buses, lines, generators, slack_bus, 'ac_contingency_screen')
+        plain = (buses.detach(), lines.detach(), generators.detach())
+        key, args = _topology_key(*plain, slack_bus, 'ac_contingency_screen')
         topo = _analysed(_NR, key, args, dev)
         isl_np = _topology_bridges(topo, args)[out_np]
         out32 = out_np.astype(np.int32)
         out_dev, isl_dev = torch.from_numpy(out32).to(dev), torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
+        lds = topo.info['lds_bytes']
+        target = _one_topology(topo)
 
-        # the base case as newton_raphson solves it (its refusals come first), then every pair from it
-        base = _solve(lib, _NR, cfg, _one_topology(topo), buses, lines, generators, None, None)
+        def shared():
+            """What both C calls take between Bt and their own arguments (a closure, used as late as the backward: it keeps their
+            owners alive)."""
+            return (out32.ctypes.data, out_dev.data_ptr(), K, isl_dev.data_ptr(), _ptr(rating),
+                    int(rating is not None and rating.dim() == 2))
+
+        def workspace(query):
+            nbytes = ctypes.c_size_t()
+            _check(getattr(lib, query)(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)), query, lds, _ACN1.formula)
+            return nbytes.value
+
+        # the base case as newton_raphson solves it (its refusals come first, then the backward's own, before anything is launched)
+        if grad:
+            workspace('gns_acn1_adjoint_workspace_bytes')
+            base = list(_NRFunction.apply(lambda *a: _solve(lib, _NR, cfg, target, *a, None, None),
+                                          lambda *a: _adjoint(lib, cfg, target, *a), buses, lines, generators))
+        else:
+            base = _solve(lib, _NR, cfg, target, *plain, None, None)
+        base_v, base_theta = base[0].detach(), base[1].detach()      # the warm start is not differentiated
         base_conv = base[2].to(torch.uint8)
 
-        def f64(n):
-            return torch.empty(Bt, K, n, dtype=torch.float64, device=dev)
+        def screen(bu, li, ge):
+            """One ``gns_acn1_screen`` launch: the fifteen outputs in its order (``converged`` as uint8), every pair from the base."""
+            def f64(n):
+                return torch.empty(Bt, K, n, dtype=torch.float64, device=dev)
 
-        state = [f64(N), f64(N)] if states else [None, None]
-        flow = [f64(E) for _ in range(4)] if flows else [None] * 4
-        row_f64 = [torch.empty(Bt, K, dtype=torch.float64, device=dev) for _ in range(4)]       # worst, v_min, v_max, mismatch
-        row_i32 = [torch.empty(Bt, K, dtype=torch.int32, device=dev) for _ in range(4)]         # their indices, iterations
-        conv = torch.empty(Bt, K, dtype=torch.uint8, device=dev)
-        lds = topo.info['lds_bytes']
-        nbytes = ctypes.c_size_t()
-        _check(lib.gns_acn1_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)),
-               'gns_acn1_workspace_bytes', lds, _ACN1.formula)
-        ws = _gns._workspace(nbytes.value, dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_acn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
-                                       lines.data_ptr(), generators.data_ptr(), Bt, out32.ctypes.data, out_dev.data_ptr(), K,
-                                       isl_dev.data_ptr(), _ptr(rating), int(rating is not None and rating.dim() == 2),
-                                       base[0].data_ptr(), base[1].data_ptr(), base_conv.data_ptr(), *map(_ptr, state),
-                                       *map(_ptr, flow), row_f64[0].data_ptr(), row_i32[0].data_ptr(), row_f64[1].data_ptr(),
-                                       row_i32[1].data_ptr(), row_f64[2].data_ptr(), row_i32[2].data_ptr(), conv.data_ptr(),
-                                       row_i32[3].data_ptr(), row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                   'gns_acn1_screen', lds, _ACN1.formula)
-        res = [*state, *flow, row_f64[0], row_i32[0], row_f64[1], row_i32[1], row_f64[2], row_i32[2], conv.bool(), row_i32[3],
-               row_f64[3]]
+            state = [f64(N), f64(N)] if states or grad else [None, None]
+            flow = [f64(E) for _ in range(4)] if flows else [None] * 4
+            row_f64 = [torch.empty(Bt, K, dtype=torch.float64, device=dev) for _ in range(4)]       # worst, v_min, v_max, mismatch
+            row_i32 = [torch.empty(Bt, K, dtype=torch.int32, device=dev) for _ in range(4)]         # their indices, iterations
+            conv = torch.empty(Bt, K, dtype=torch.uint8, device=dev)
+            ws = _gns._workspace(workspace('gns_acn1_workspace_bytes'), dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(lib.gns_acn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                           li.data_ptr(), ge.data_ptr(), Bt, *shared(), base_v.data_ptr(), base_theta.data_ptr(),
+                                           base_conv.data_ptr(), *map(_ptr, state), *map(_ptr, flow), row_f64[0].data_ptr(),
+                                           row_i32[0].data_ptr(), row_f64[1].data_ptr(), row_i32[1].data_ptr(),
+                                           row_f64[2].data_ptr(), row_i32[2].data_ptr(), conv.data_ptr(), row_i32[3].data_ptr(),
+                                           row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                       'gns_acn1_screen', lds, _ACN1.formula)
+            return [*state, *flow, row_f64[0], row_i32[0], row_f64[1], row_i32[1], row_f64[2], row_i32[2], conv, row_i32[3],
+                    row_f64[3]]
+
+        def adjoint(bu, li, ge, state, incoming, need):
+            """One ``gns_acn1_adjoint`` call at the forward's ``state`` (v, theta, converged, worst_line, v_min_bus, v_max_bus)."""
+            gin = [torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need)]
+            incoming = [None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming]
+            ws = _gns._workspace(workspace('gns_acn1_adjoint_workspace_bytes'), dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(lib.gns_acn1_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                            li.data_ptr(), ge.data_ptr(), Bt, *shared(), *(t.data_ptr() for t in state),
+                                            base_conv.data_ptr(), *map(_ptr, incoming), *map(_ptr, gin), ws.data_ptr(), ws.numel(),
+                                            stream), 'gns_acn1_adjoint', lds, _ACN1.formula)
+            return gin
+
+        res = list(_ACN1Function.apply(screen, adjoint, buses, lines, generators)) if grad else screen(*plain)
+        if not states:
+            res[0] = res[1] = None
+        res[12] = res[12].bool()
         outages_t, islanding = torch.from_numpy(out_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev)
         if in_dev != dev:
             base = [t.to(in_dev) for t in base]

@@ -442,6 +442,63 @@ int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
                      float* grad_buses, float* grad_lines, float* grad_generators,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* DC N-2 contingency screening: the post-outage DC flows of a list of double-line outages (an N-2 set) of every grid of a batch,
+ * from the base factorisation alone.  Two lines out are a rank-2 change of Bbus[r, r]: the single-line solves of "DC contingency
+ * screening" above, one per distinct line of the list, and a 2x2 system per pair give the exact flows.
+ *
+ * Semantics (notation of "DC contingency screening": A = Bbus[r, r]; m_l = (e_f - e_t)_r; A z_c = m_c on the base factor; F_l the
+ * base flow; fp64 throughout).  Let H_c[l] = z_c[f_l] - z_c[t_l], with z taken as 0 at the slack.  For a pair of lines j < k (the
+ * kernel orders the two lines itself, so (k, j) gives the same bits as (j, k)):
+ *   m11 = 1 - b_j H_j[j]      m12 = -b_j H_k[j]
+ *   m21 = -b_k H_j[k]         m22 = 1 - b_k H_k[k]
+ *   det = m11 m22 - m12 m21
+ *   a_j = (F_j m22 - m12 F_k) / det
+ *   a_k = (m11 F_k - m21 F_j) / det
+ *   F'_l = F_l + b_l (H_j[l] a_j + H_k[l] a_k)   for l not in {j, k};   F'_j = F'_k = 0
+ *   (with theta' = theta + Z a, Z = [z_j z_k], the flows of the two lines must vanish: (I - diag(b) M^T Z) a = F_S).  A line from
+ *   a bus to itself has m = 0 and changes nothing.
+ *   worst_loading = max_l |F'_l| / rating_l (rating NULL: 1) and worst_line the 0-based line that attains it, the lowest of equals,
+ *   by the total order of the N-1 screen's reduction (NaN is worst of all).
+ *   Islanding: a pair that disconnects the graph has det = 0 in exact arithmetic.  The kernel does not decide that numerically: the
+ *   caller passes islanding[n_pair] (1: j is a bridge, or k is a bridge of the graph without j).  Those rows get NaN in line_flow
+ *   and worst_loading and -1 in worst_line, in every grid.
+ *   Failure: a grid whose base solve fails (converged = 0, as gns_dc_solve decides it) gets NaN / -1 in every row; a pair one of
+ *   whose z_c is not finite, or whose det, a_j or a_k is not finite (or whose det is zero) gets NaN / -1 alone.
+ *   Every (grid, pair) row is bit-identical alone, in any batch, in any pair list or order that holds it (duplicates are independent
+ *   rows), in either order of its two lines, and from run to run: no atomics, the reductions in a fixed order.
+ *
+ * Inputs: cand [n_cand] int32, the distinct lines that occur in the pairs, ascending, on the host (checked before the launch) and
+ * on the device; pair_cols [n_pair,2] int32, each pair as two positions into cand, on the host and on the device; islanding [n_pair]
+ * uint8 on the device; rating NULL, [E] (rating_per_grid 0) or [Bt,E] (1) fp64 on the device.
+ * Outputs: line_flow [Bt,n_pair,E] fp64, or NULL for the summaries alone (8 Bt n_pair E bytes not written); worst_loading
+ * [Bt,n_pair] fp64; worst_line [Bt,n_pair] int32; converged [Bt] uint8, the base solve's.
+ *
+ * Kernels (gns_dcn2.hip).  Factor: one wave per (grid, chunk of W candidate lines) with the N-1 screen's prologue, LDS image and
+ * lane solve (gns_dcn1_device.h), so z_c is that screen's bit for bit; a pass with a line per lane then stores H_c[0 .. E)
+ * contiguously into the workspace with a finite flag per candidate, and chunk 0 also stores F_l, b_l and the grid's status.  Its LDS
+ * image and W are gns_dcn1_lds_bytes' (gns_dcn2_lds_bytes reports them).  Pair: one wave per (grid, chunk of Q consecutive pairs), F,
+ * b and the rating in LDS (24 E bytes); per pair the six scalars above are computed identically on every lane, a line per lane
+ * forms F'_l from the two H rows, and the wave reduction of the N-1 screen finishes the row.  Q comes from n_pair alone (32 from
+ * 8192 pairs on, else 8).  Workspace (gns_dcn2_workspace_bytes): Bt * (n_cand * E + 2 E + n_cand + 1) doubles (H, F, b, the flags,
+ * the status), rounded up to 256 bytes.
+ *
+ * Errors: GNS_EINVAL for a NULL cfg, blob, input, cand, pair_cols, islanding mask, output other than line_flow or workspace, a blob
+ * that is not an FD blob or whose N, E, Gn are not cfg's, n_cand <= 0 or n_pair <= 0, a candidate outside 0 .. E-1, cand not
+ * ascending or not distinct, a column outside 0 .. n_cand-1, a pair with equal columns, rating_per_grid outside {0, 1}, or Bt, or
+ * Bt times the chunks of either kernel, above 2^31 - 1; GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES; GNS_ESIZE
+ * for a short workspace.  GNS_EINVAL wins over GNS_EUNSUPPORTED, which wins over GNS_ESIZE (a NULL workspace is looked at with its
+ * size).  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
+ * Not here: gradients, batches that mix topologies, AC N-2, line plus generator outages. */
+int gns_dcn2_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
+int gns_dcn2_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_cand, size_t* bytes);
+int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                    const float* buses, const float* lines, const float* generators, int64_t Bt,
+                    const int32_t* cand_host, const int32_t* cand_dev, int32_t n_cand,
+                    const int32_t* pair_cols_host, const int32_t* pair_cols_dev, int32_t n_pair, const uint8_t* islanding,
+                    const double* rating, int32_t rating_per_grid,
+                    double* line_flow, double* worst_loading, int32_t* worst_line, uint8_t* converged,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 /* AC contingency screening: Newton-Raphson on every grid of a batch with each single line of a list out of service (an N-1 set),
  * with the post-outage state, the branch flows at both ends of every line and their summaries, from the base analysis alone.
  *

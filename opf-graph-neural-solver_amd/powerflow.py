@@ -26,6 +26,10 @@ more solve per outage gives the exact post-outage DC flows (line-outage distribu
 loading and its line per ``(grid, outage)``; outages that disconnect the grid are found on the host as the bridges of the topology.
 With ``differentiable=True`` its backward is one ``gns_dcn1_adjoint`` call: a second solve on the base factor per outage.
 
+``dc_n2_contingency_screen(...)`` screens a batch against a list of double-line outages (an N-2 set): a pair is a rank-2 change of
+the DC matrix, so the single-outage solves (one per distinct line of the list) and a 2x2 system per pair give the exact flows
+(``csrc/gns_dcn2.hip``); the pairs that disconnect the grid are found on the host.
+
 ``ac_contingency_screen(...)`` is the AC answer to the same question: Newton-Raphson on every ``(grid, outage)`` pair, warm-started
 from the base solution, on the base topology's analysis alone (an outage only removes Jacobian entries), with the post-outage
 voltages, the branch flows at both ends of every line, the worst loading and the voltage extremes (``csrc/gns_acn1.hip``).
@@ -52,6 +56,9 @@ DcPowerFlowResult = namedtuple('DcPowerFlowResult', ['v', 'theta', 'line_flow', 
 
 DcContingencyResult = namedtuple('DcContingencyResult', ['base', 'outages', 'line_flow', 'worst_loading', 'worst_line', 'islanding',
                                                          'converged'])
+
+DcN2ContingencyResult = namedtuple('DcN2ContingencyResult', ['base', 'pairs', 'line_flow', 'worst_loading', 'worst_line', 'islanding',
+                                                             'converged'])
 
 AcContingencyResult = namedtuple('AcContingencyResult', ['base', 'outages', 'v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to',
                                                          'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max', 'v_max_bus',
@@ -140,6 +147,9 @@ _DC = _Solver('gns_dc', FdTopology, _DC_LDS_FORMULA)     # DC runs on the fast-d
 _DCN1_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per workgroup: DC's image, three doubles per line and "
                      "the right-hand sides of W outages side by side, here with W = 1, the narrowest")
 _DCN1 = _Solver('gns_dcn1', FdTopology, _DCN1_LDS_FORMULA)   # the DC contingency screen: the same analysis again
+_DCN2_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per workgroup of the factor kernel: the DC N-1 screen's image, "
+                     "the right-hand sides of W candidate lines side by side, here with W = 1, the narrowest")
+_DCN2 = _Solver('gns_dcn2', FdTopology, _DCN2_LDS_FORMULA)   # the DC N-2 screen: the N-1 screen's analysis and image
 _ACN1 = _Solver('gns_acn1', PowerFlowTopology, _LDS_FORMULA)   # the AC contingency screen: Newton-Raphson's analysis and LDS image
 _DCN1_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W) bytes per workgroup: the screen's image, a second "
                              "array of W right-hand sides for the adjoint solves and three doubles per outage, here with W = 1, the "
@@ -769,7 +779,8 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     ``~islanding``); otherwise, and for a grid that is not solved, the grid's three gradient rows are NaN (zero rows for an
     unsolved grid whose incoming gradients are all zero).  The forward outputs are bit-identical with and without gradients.  A
     grid's gradient is bit-identical alone, in any batch and from run to run for the same outage list; the order of the list may
-    change its last bits.  N-2 outages and mixed topologies are out of scope; the AC screen is ``ac_contingency_screen``.
+    change its last bits.  Mixed topologies are out of scope; double outages are ``dc_n2_contingency_screen``, the AC screen is
+    ``ac_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "DC contingency screening"."""
     if not isinstance(flows, bool):
         raise ValueError(f'flows must be a bool, got {flows!r}')
@@ -864,6 +875,152 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
             res = [None if t is None else t[0] for t in res]
             conv = conv[0]
         return DcContingencyResult(DcPowerFlowResult(*base), outages_t, res[0], res[1], res[2], islanding, conv)
+
+
+def _pair_list(pairs, E):
+    """The checked list of line pairs as an int64 numpy array ``[P,2]``; None: every ``j < k`` in lexicographic order."""
+    if pairs is None:
+        if E < 2:
+            raise ValueError(f'pairs: a grid with {E} line(s) has no pair of lines to take out')
+        j, k = np.triu_indices(E, 1)
+        return np.stack([j, k], axis=1).astype(np.int64)
+    o = pairs.detach().cpu().numpy() if isinstance(pairs, torch.Tensor) else np.asarray(pairs)
+    if o.size == 0:
+        raise ValueError('pairs is empty: give at least one pair of line indices (None: every pair)')
+    if o.ndim != 2 or o.shape[1] != 2:
+        raise ValueError(f'pairs must be a [P,2] sequence of line indices, got shape {tuple(o.shape)}')
+    if o.dtype == np.bool_ or not np.issubdtype(o.dtype, np.integer):
+        raise ValueError(f'pairs must hold integers (0-based line indices), got dtype {o.dtype}')
+    if o.min() < 0 or o.max() > E - 1:
+        raise ValueError(f'pairs must lie in 0..{E - 1} (0-based line indices), got {int(o.min())}..{int(o.max())}')
+    o = o.astype(np.int64)
+    same = np.flatnonzero(o[:, 0] == o[:, 1])
+    if same.size:
+        raise ValueError(f'pairs must name two different lines, got ({int(o[same[0], 0])}, {int(o[same[0], 1])}) at row {int(same[0])}: '
+                         'a single outage is dc_contingency_screen\'s')
+    return o
+
+
+def _pair_islanding(n_bus, f_bus, t_bus, pairs, bridges=None, cache=None):
+    """bool ``[P]``: the pairs of lines (0-based ends, ``pairs`` ``[P,2]``) whose removal disconnects the graph the lines span:
+    ``j`` is a bridge, or ``k`` is a bridge of the graph without line ``j``.  The relation is symmetric, so the lower line of a pair
+    is taken as ``j``: one more search (``_bridges``) per distinct lower line that is not itself a bridge, kept in ``cache`` (a dict
+    line -> bool ``[E]``, the bridges of the graph without that line)."""
+    f, t = np.asarray(f_bus), np.asarray(t_bus)
+    bridges = _bridges(n_bus, f, t) if bridges is None else bridges
+    cache = {} if cache is None else cache
+    lo, hi = pairs.min(axis=1), pairs.max(axis=1)
+    out = bridges[lo] | bridges[hi]
+    todo = np.flatnonzero(~out)
+    order = todo[np.argsort(lo[todo], kind='stable')]
+    starts = np.flatnonzero(np.r_[True, lo[order][1:] != lo[order][:-1]]) if order.size else np.zeros(0, dtype=np.int64)
+    for a, b in zip(starts.tolist(), starts.tolist()[1:] + [order.size]):
+        j = int(lo[order[a]])
+        row = cache.get(j)
+        if row is None:
+            row = cache[j] = np.insert(_bridges(n_bus, np.delete(f, j), np.delete(t, j)), j, False)
+        idx = order[a:b]
+        out[idx] = row[hi[idx]]
+    return out
+
+
+def _topology_pair_islanding(topo, args, pairs):
+    """The islanding pairs of an analysed topology (``_pair_islanding``); the bridges of the graph without a line are found once
+    per line and kept with the topology, as ``_topology_bridges`` keeps the bridges."""
+    if getattr(topo, 'bridges_without', None) is None:
+        topo.bridges_without = {}
+    n_bus, f_bus, t_bus = args[0], args[1], args[2]
+    return _pair_islanding(int(n_bus), f_bus.astype(np.int64) - 1, t_bus.astype(np.int64) - 1, pairs, _topology_bridges(topo, args),
+                           topo.bridges_without)
+
+
+def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, pairs=None, rating=None,
+                             flows=False):
+    """DC N-2 contingency screening of every grid of a batch, on the device: the exact post-outage DC flows of each double-line
+    outage of ``pairs``.  Two lines out are a rank-2 change of the DC matrix: the single-outage solves on the base factor (one per
+    distinct line of the list, the ones ``dc_contingency_screen`` makes) and a 2x2 system per pair give the flows, not one
+    factorisation per ``(grid, pair)`` as ``dc_power_flow(mixed_topologies=True)`` on the expanded batch does.
+
+    Inputs, column maps, the slack, the device handling and ``rating`` are those of ``dc_contingency_screen``; the whole batch
+    shares one topology.  ``pairs``: a ``[P,2]`` integer tensor, array or sequence of 0-based line indices, default every ``j < k`` in
+    lexicographic order (``E (E - 1) / 2`` rows).  The two lines of a pair differ; duplicate pairs and both orders of a pair are
+    allowed and are independent rows.
+
+    Returns ``DcN2ContingencyResult(base, pairs, line_flow, worst_loading, worst_line, islanding, converged)``:
+      base           the ``DcPowerFlowResult`` of ``dc_power_flow`` on the same inputs, bit for bit
+      pairs          ``[P,2]`` int64, as given
+      line_flow      None by default; with ``flows=True`` ``[Bt,P,E]`` float64, the flows with both lines out, 0 at the two outaged
+                     lines.  The default is the opposite of ``dc_contingency_screen``'s: the tensor is ``8 Bt P E`` bytes (1.6 GB for
+                     one case300 grid and every pair), and the kernel writes the summaries alone without it.
+      worst_loading  ``[Bt,P]`` float64, ``max_l |line_flow| / rating``;  worst_line ``[Bt,P]`` int32, the line that attains it (the
+                     lowest of equals)
+      islanding      ``[P]`` bool: the pair disconnects the grid (one line is a bridge of the topology, or the second is a bridge of
+                     the graph without the first; found on the host and kept with the topology, never from a numeric threshold).
+                     Those rows are NaN / -1 in every grid.
+      converged      ``[Bt]`` bool, the base solve's.  A grid whose base solve fails has NaN / -1 in every row; a pair whose update
+                     is not finite (a singular 2x2 system included) has NaN / -1 alone.
+    Every ``(grid, pair)`` row is bit-identical alone, in any batch, in any pair list or order that holds it, in either order of
+    its two lines, and from run to run.  With a 2-D single grid the batch dimension is dropped.
+
+    The outputs are not differentiable (the call runs as under ``torch.no_grad()``).  Mixed topologies, AC N-2 and line plus
+    generator outages are out of scope.  Contract: ``include/gns_powerflow.h``, "DC N-2 contingency screening"."""
+    if not isinstance(flows, bool):
+        raise ValueError(f'flows must be a bool, got {flows!r}')
+    with torch.no_grad():
+        # the shapes first, so that a bad pair list or rating is refused where no device is visible too
+        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
+        pairs_np = _pair_list(pairs, shaped_lines.shape[1])
+        rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
+        buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, 0.0, 0, False)
+        lib = load_library()
+        Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
+        rating = None if rating is None else rating.to(dev).contiguous()
+        P = pairs_np.shape[0]
+        cfg = PfConfig(N, E, generators.shape[1], 0, 0.0)
+        key, args = _topology_key(buses, lines, generators, slack_bus, 'dc_n2_contingency_screen')
+        topo = _analysed(_FD, key, args, dev)
+        isl_np = _topology_pair_islanding(topo, args, pairs_np)
+
+        # the distinct lines of the list, ascending, and each pair as two positions into them
+        cand_np, cols_np = np.unique(pairs_np, return_inverse=True)
+        cand32 = cand_np.astype(np.int32)
+        cols32 = np.ascontiguousarray(cols_np.reshape(P, 2).astype(np.int32))
+        n_cand = cand32.size
+        cand_dev, cols_dev = torch.from_numpy(cand32).to(dev), torch.from_numpy(cols32).to(dev)
+        isl_dev = torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
+
+        flow = torch.empty(Bt, P, E, dtype=torch.float64, device=dev) if flows else None
+        worst = torch.empty(Bt, P, dtype=torch.float64, device=dev)
+        worst_line = torch.empty(Bt, P, dtype=torch.int32, device=dev)
+        conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
+        lds = lambda: _dcn1_lds_bytes(topo.host)[0]                           # noqa: E731
+        nbytes = ctypes.c_size_t()
+        _check(lib.gns_dcn2_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, n_cand, ctypes.byref(nbytes)),
+               'gns_dcn2_workspace_bytes', lds, _DCN2.formula)
+        ws = _gns._workspace(nbytes.value, dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_dcn2_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
+                                       lines.data_ptr(), generators.data_ptr(), Bt, cand32.ctypes.data, cand_dev.data_ptr(), n_cand,
+                                       cols32.ctypes.data, cols_dev.data_ptr(), P, isl_dev.data_ptr(), _ptr(rating),
+                                       int(rating is not None and rating.dim() == 2), _ptr(flow), worst.data_ptr(),
+                                       worst_line.data_ptr(), conv.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                   'gns_dcn2_screen', lds, _DCN2.formula)
+        # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
+        base = _dc_solve(lib, cfg, _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host)), buses, lines, generators)
+        base = [torch.ones(Bt, N, dtype=torch.float64, device=dev), *base]
+        res = [flow, worst, worst_line]
+        pairs_t, islanding, conv = torch.from_numpy(pairs_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev), conv.bool()
+        if in_dev != dev:
+            base = [t.to(in_dev) for t in base]
+            res = [None if t is None else t.to(in_dev) for t in res]
+            pairs_t, islanding, conv = pairs_t.to(in_dev), islanding.to(in_dev), conv.to(in_dev)
+        if single:
+            base = [t[0] for t in base]
+            res = [None if t is None else t[0] for t in res]
+            conv = conv[0]
+        return DcN2ContingencyResult(DcPowerFlowResult(*base), pairs_t, res[0], res[1], res[2], islanding, conv)
 
 
 class _ACN1Function(torch.autograd.Function):

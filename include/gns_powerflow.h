@@ -488,7 +488,7 @@ int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  * Bt times the chunks of either kernel, above 2^31 - 1; GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES; GNS_ESIZE
  * for a short workspace.  GNS_EINVAL wins over GNS_EUNSUPPORTED, which wins over GNS_ESIZE (a NULL workspace is looked at with its
  * size).  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
- * Not here: gradients, batches that mix topologies, AC N-2, line plus generator outages. */
+ * Gradients: gns_dcn2_adjoint, below.  Not here: batches that mix topologies, AC N-2, line plus generator outages. */
 int gns_dcn2_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
 int gns_dcn2_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_cand, size_t* bytes);
 int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
@@ -498,6 +498,66 @@ int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, const void*
                     const double* rating, int32_t rating_per_grid,
                     double* line_flow, double* worst_loading, int32_t* worst_line, uint8_t* converged,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Gradients of the N-2 screen.  gns_dcn2_adjoint takes the inputs of a gns_dcn2_screen call (the same candidate and pair lists,
+ * islanding mask and rating), its outputs worst_line [Bt,n_pair] and converged [Bt], and the incoming gradients of a loss of its two
+ * fp64 outputs: grad_line_flow [Bt,n_pair,E] and grad_worst_loading [Bt,n_pair] (each may be NULL: zero).  It writes dl/d(input)
+ * into grad_buses [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32, each of which may be NULL (not computed; with all
+ * three NULL nothing is launched).  Every element of each non-NULL output is written (overwritten, not accumulated).  The row state is
+ * recomputed from the inputs, not kept by the forward.
+ *
+ * Method, per grid, with A = Bbus[r, r], z_c = A^-1 m_c and H_c[l] = m_l^T z_c of candidate c (the forward's rows), and per pair
+ * S = (j, k) the forward's M = I - diag(b_S) H[S,S], a = M^-1 F_S and F'_l = F_l + b_l (H_j[l] a_j + H_k[l] a_k):
+ *   G_l = grad_line_flow[l] plus, at l = worst_line, grad_worst_loading sign(F'_w) / rating_w; G_j = G_k = 0.
+ *   Per pair: gF_l += G_l;  ga = sum_l G_l b_l (H_j[l], H_k[l]);  v = M^-T ga;  gF_j += v_j, gF_k += v_k;
+ *   T'_c[l] += G_l a_c for c in S, and T'_c[e_r] += v_r a_c at the two outaged lines e_r (the derivative of M).
+ *   Per grid: y_0 = A^-1 sum_l gF_l b_l m_l and y_c = A^-1 sum_l b_l T'_c[l] m_l, one solve on the base factor per candidate and
+ *   one more;  w_l = gF_l - m_l^T y_0;  dl/db_l = w_l (theta_f - theta_t - shift_l) + sum_c H_c[l] (T'_c[l] - m_l^T y_c);
+ *   dl/dP = y_0;  dl/dshift_l = -b_l w_l.  At most n_cand + 1 solves for the gradient and the n_cand solves and the base case that
+ *   recompute the forward's state; nothing is factored or solved per pair, and with grad_line_flow NULL a pair is O(1) work.
+ *
+ * Contract (gns_dcn1_adjoint's): buses cols 2, 4 (Pd, Gs); lines cols 3, 5, 6 (x, tau, shift); generators col 6 (Pg); every other
+ *   column exactly 0.  rating is a constant; a tie in the worst loading goes to the worst_line the forward reported.  A row the
+ *   forward left NaN / -1 (an islanding pair, a non-finite 2x2 update) is skipped when its incoming gradients are exactly zero or
+ *   NULL, never multiplied by zero; with a non-zero incoming gradient, or a non-finite solve, the grid's three gradient rows are NaN.
+ *   A grid with converged == 0 gets NaN rows when an incoming gradient of it is non-zero, zero rows otherwise.  Other grids are
+ *   unaffected.  Row (j, k) contributes 0 to the own columns of lines j and k.  The sums over pairs run through shared solves, in
+ *   which a row's contribution to its own two lines cancels to rounding (of the order of 1e-16 of the row's other entries); the
+ *   columns of a line are therefore the sum over the contributing rows that do not hold it plus that rounding, and a line that every
+ *   contributing row of the grid holds (the sum over the others is empty: a single row, rows that share a line) gets exactly 0.
+ *   fp64 throughout, rounded once to fp32.  No atomics, every sum in a fixed order: a grid's gradient is bit-identical alone, in any
+ *   batch and from run to run for the same pair list, and (k, j) gives the bits of (j, k); another order of the list may change the
+ *   last bits.
+ *
+ * Kernels (gns_dcn2.hip), five launches: the forward's factor kernel again, into the adjoint's own workspace (the pool is reused
+ * between forward and backward, so nothing of the forward's is read); a pair kernel, one wave per (grid, chunk of Q pairs, the
+ * forward's Q), 32 E bytes of LDS, which writes a record of 6 doubles per (grid, pair) (a, v, the worst-line term, whether the row
+ * contributes and its worst line) and the chunk's partial of gF; a gather kernel, one wave per (grid, candidate), 8 E bytes of LDS,
+ * which scans the pair list 64 pairs at a time and sums T'_c over the pairs that hold its candidate in list order, lane l mod 64
+ * owning line l, and counts the contributing pairs that do not hold it; a solve kernel, one wave per (grid, chunk of W columns: column 0 is y_0, column c + 1 candidate c) on the N-1
+ * adjoint's LDS image and width (gns_dcn1_adjoint_lds_bytes; gns_dcn2_adjoint_lds_bytes reports the larger of that image and
+ * 32 E), lane j running the solve program on its column; and gns_dcn1_adjoint's reduce kernel over the chunks' partials.
+ * Workspace (gns_dcn2_adjoint_workspace_bytes): gns_dcn2_workspace_bytes' figure, plus
+ * Bt * (n_cand * E + 6 n_pair + ceil(n_pair / Q) * (E + 1) + E + n_cand + ceil((n_cand + 1) / W) * (N + 2 E + 1)) doubles and Bt bytes,
+ * rounded up to 256 bytes.
+ *
+ * Errors, in order (gns_dcn1_adjoint's): GNS_EINVAL for what gns_dcn2_screen refuses with it, a NULL worst_line or converged, or
+ * Bt times the chunks of any kernel, or Bt * n_cand, above 2^31 - 1; then GNS_EUNSUPPORTED for an LDS image above
+ * GNS_PF_LDS_MAX_BYTES (from the workspace query too); then, when an output is asked for, GNS_EINVAL for a NULL workspace and
+ * GNS_ESIZE for a short one.  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
+ * Not here: batches that mix topologies, AC N-2, line plus generator outages, second derivatives. */
+int gns_dcn2_adjoint_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
+int gns_dcn2_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_cand, int32_t n_pair,
+                                     size_t* bytes);
+int gns_dcn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const int32_t* cand_host, const int32_t* cand_dev, int32_t n_cand,
+                     const int32_t* pair_cols_host, const int32_t* pair_cols_dev, int32_t n_pair, const uint8_t* islanding,
+                     const double* rating, int32_t rating_per_grid,
+                     const int32_t* worst_line, const uint8_t* converged,
+                     const double* grad_line_flow, const double* grad_worst_loading,
+                     float* grad_buses, float* grad_lines, float* grad_generators,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* AC contingency screening: Newton-Raphson on every grid of a batch with each single line of a list out of service (an N-1 set),
  * with the post-outage state, the branch flows at both ends of every line and their summaries, from the base analysis alone.

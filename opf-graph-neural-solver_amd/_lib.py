@@ -127,11 +127,15 @@ def load_library():
     lib.gns_dcn2_lds_bytes.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
     lib.gns_dcn2_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
     lib.gns_dcn2_screen.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.gns_dcn2_adjoint_lds_bytes.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    lib.gns_dcn2_adjoint_workspace_bytes.argtypes = [pfcp, vp, i64, i32, i32, ctypes.POINTER(sz)]
+    lib.gns_dcn2_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz,
+                                     vp]
     lib.gns_acn1_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
     lib.gns_acn1_screen.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32] + [vp] * 18 + [vp, sz, vp]
     lib.gns_acn1_adjoint_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
     lib.gns_acn1_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32] + [vp] * 19 + [vp, sz, vp]
-    for f in PF_EXPORTS + FD_EXPORTS + DC_EXPORTS + DCN1_EXPORTS + DCN2_EXPORTS + ACN1_EXPORTS + ACN1_ADJOINT_EXPORTS:
+    for f in PF_EXPORTS + FD_EXPORTS + DC_EXPORTS + DCN1_EXPORTS + DCN2_EXPORTS + DCN2_ADJOINT_EXPORTS + ACN1_EXPORTS + ACN1_ADJOINT_EXPORTS:
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
               'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
@@ -164,6 +168,8 @@ DCN1_EXPORTS = ('gns_dcn1_lds_bytes', 'gns_dcn1_workspace_bytes', 'gns_dcn1_scre
                 'gns_dcn1_adjoint_workspace_bytes', 'gns_dcn1_adjoint')
 # the DC N-2 contingency screen's C-ABI (include/gns_powerflow.h, "DC N-2 contingency screening"): on the fast-decoupled blob too
 DCN2_EXPORTS = ('gns_dcn2_lds_bytes', 'gns_dcn2_workspace_bytes', 'gns_dcn2_screen')
+# the gradients of the DC N-2 screen (the same section, "Gradients of the N-2 screen")
+DCN2_ADJOINT_EXPORTS = ('gns_dcn2_adjoint_lds_bytes', 'gns_dcn2_adjoint_workspace_bytes', 'gns_dcn2_adjoint')
 # the AC contingency screen's C-ABI (include/gns_powerflow.h, "AC contingency screening"): on the Newton-Raphson blob
 ACN1_EXPORTS = ('gns_acn1_workspace_bytes', 'gns_acn1_screen')
 # the gradients of the AC screen (the same section, "Gradients of the AC screen")

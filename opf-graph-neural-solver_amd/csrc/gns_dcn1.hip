@@ -90,29 +90,6 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcn1_kernel(const int32_t* __r
 
 constexpr int DCN1_GRAD_PREFETCH = 8;   // incoming gradients of its row a lane fetches ahead of adding them to its right-hand side
 
-// Whether one of the rows row0 + j of the incoming gradients, j a set bit of rows, holds a value that is not exactly zero (NaN
-// counts).  The whole wave scans each row with a line per lane; the answer is the same in every lane.
-__device__ __forceinline__ bool dcn1_rows_nonzero(unsigned long long rows, const size_t row0, const int E, const double* gfl,
-                                                  const double* gwl) {
-  bool nz = false;
-  for (; rows; rows &= rows - 1) {
-    const size_t row = row0 + (__ffsll((long long)rows) - 1);
-    if (gwl && threadIdx.x == 0) nz |= gwl[row] != 0.0;
-    if (gfl) for (int l = threadIdx.x; l < E; l += PF_THREADS) nz |= gfl[row * E + l] != 0.0;
-  }
-  return __ballot(nz) != 0;
-}
-
-// The status of a chunk's partial: its sums are valid; the grid's gradient is NaN; the grid is not solved and the chunk's incoming
-// gradients are zero (the sums are zeros; when every chunk says so the grid gets zero rows, whatever its inputs hold)
-constexpr double DCN1_PART_OK = 0.0, DCN1_PART_NAN = 1.0, DCN1_PART_UNSOLVED_ZERO = 2.0;
-
-// The partial of a chunk that adds nothing: zeros and the status
-__device__ __forceinline__ void dcn1_partial_none(double* part, const int n, const double status) {
-  for (int q = threadIdx.x; q < n - 1; q += PF_THREADS) part[q] = 0.0;
-  if (threadIdx.x == 0) part[n - 1] = status;
-}
-
 __global__ __launch_bounds__(PF_THREADS) void gns_dcn1_adjoint_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
                                                                       const float* __restrict__ lines, const float* __restrict__ gens,
                                                                       const int32_t* __restrict__ outages, const int K,
@@ -247,79 +224,6 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcn1_adjoint_kernel(const int3
     part[i] = dp;
   }
   if (lane == 0) part[np - 1] = DCN1_PART_OK;
-}
-
-// A wave per grid: the chunks' partials summed in order, the contract applied, every element of the three gradient rows written
-__global__ __launch_bounds__(PF_THREADS) void gns_dcn1_adjoint_reduce_kernel(const int32_t* __restrict__ topo,
-                                                                             const float* __restrict__ lines, const int nchunks,
-                                                                             const double* __restrict__ partials,
-                                                                             float* __restrict__ gb_out, float* __restrict__ gl_out,
-                                                                             float* __restrict__ gg_out) {
-  const int lane = threadIdx.x, g = blockIdx.x;
-  const int N = topo[FH_N], E = topo[FH_E], Gn = topo[FH_GN];
-  const int32_t* gen_ptr = topo + topo[FH_GEN_PTR];
-  const int32_t* gen_idx = topo + topo[FH_GEN_IDX];
-  const int np = (int)dcn1_adjoint_partial(topo);
-  const double* part = partials + (size_t)g * nchunks * np;
-  const float* line = lines + (size_t)g * E * 7;
-
-  bool bad = false, solved = false;
-  for (int c = lane; c < nchunks; c += PF_THREADS) {
-    const double status = part[(size_t)c * np + np - 1];
-    bad |= status != DCN1_PART_OK && status != DCN1_PART_UNSOLVED_ZERO;
-    solved |= status != DCN1_PART_UNSOLVED_ZERO;
-  }
-  if (__ballot(bad)) { dc_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
-  if (!__ballot(solved)) { dc_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
-
-  // (0.0 - x rather than -x: an exact zero stays +0)
-  if (gb_out)
-    for (int i = lane; i < N; i += PF_THREADS) {
-      double dp = 0.0;
-      for (int c = 0; c < nchunks; ++c) dp += part[(size_t)c * np + i];
-      float* row = gb_out + ((size_t)g * N + i) * 6;
-      const float d = (float)(0.0 - dp);
-      row[0] = 0.0f; row[1] = 0.0f;
-      row[2] = d;                              // Pd
-      row[3] = 0.0f;
-      row[4] = d;                              // Gs
-      row[5] = 0.0f;
-    }
-  if (gg_out)
-    for (int q = lane; q < Gn; q += PF_THREADS) {      // a lane per generator, in the blob's by-bus order
-      int b = 0, hi = N;                               // the bus of generator slot q: gen_ptr[b] <= q < gen_ptr[b + 1]
-      while (hi - b > 1) {
-        const int mid = (b + hi) >> 1;
-        if (gen_ptr[mid] <= q) b = mid;
-        else hi = mid;
-      }
-      double dp = 0.0;
-      for (int c = 0; c < nchunks; ++c) dp += part[(size_t)c * np + b];
-      float* row = gg_out + ((size_t)g * Gn + gen_idx[q]) * 7;
-      for (int c = 0; c < 6; ++c) row[c] = 0.0f;
-      row[6] = (float)dp;                              // Pg
-    }
-  if (gl_out)
-    for (int e = lane; e < E; e += PF_THREADS) {
-      float* row = gl_out + ((size_t)g * E + e) * 7;
-      int f, t;
-      if (!dc_line_ends(line, e, N, f, t)) {
-        for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
-        continue;
-      }
-      double d_b = 0.0, sw = 0.0;
-      for (int c = 0; c < nchunks; ++c) {
-        d_b += part[(size_t)c * np + N + e];
-        sw += part[(size_t)c * np + N + E + e];
-      }
-      const double x = line[e * 7 + 3], tau = line[e * 7 + 5];
-      const double b = dc_line_b(line, e);
-      row[0] = 0.0f; row[1] = 0.0f; row[2] = 0.0f;
-      row[3] = (float)(0.0 - d_b * b / x);             // x: db/dx = -b / x
-      row[4] = 0.0f;
-      row[5] = (float)(0.0 - d_b * b / tau);           // tau: db/dtau = -b / tau
-      row[6] = (float)(0.0 - b * sw);                  // shift
-    }
 }
 
 // ---- host

@@ -156,6 +156,11 @@ _DCN1_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) 
                              "narrowest")
 
 
+_DCN2_ADJOINT_LDS_FORMULA = ("max(8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W), 32 E) bytes per workgroup: the DC N-1 adjoint's image "
+                             "(the screen's image and a second array of W right-hand sides) for the solves on the base factor, or "
+                             "four doubles per line for the pair kernel, here with W = 1, the narrowest")
+
+
 def _analysis(solver):
     """``(topology cache, set cache, analysis function)`` of a solver, as the module holds them when the call is made."""
     return (_FD_TOPO_CACHE, _FD_SET_CACHE, analyse_fd_topology) if solver is _FD else (_TOPO_CACHE, _SET_CACHE, analyse_topology)
@@ -934,8 +939,17 @@ def _topology_pair_islanding(topo, args, pairs):
                            topo.bridges_without)
 
 
+def _dcn2_adjoint_lds_bytes(host):
+    """``(LDS image, W)`` of the N-2 screen's adjoint (``gns_dcn2_adjoint_lds_bytes``) on the FD blob ``host``, as
+    ``_dcn1_adjoint_lds_bytes``: W columns side by side in its solve kernel."""
+    lds, lanes = ctypes.c_int64(), ctypes.c_int32()
+    _check(load_library().gns_dcn2_adjoint_lds_bytes(host.ctypes.data, ctypes.byref(lds), ctypes.byref(lanes)),
+           'gns_dcn2_adjoint_lds_bytes')
+    return lds.value, lanes.value
+
+
 def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, pairs=None, rating=None,
-                             flows=False):
+                             flows=False, differentiable=False):
     """DC N-2 contingency screening of every grid of a batch, on the device: the exact post-outage DC flows of each double-line
     outage of ``pairs``.  Two lines out are a rank-2 change of the DC matrix: the single-outage solves on the base factor (one per
     distinct line of the list, the ones ``dc_contingency_screen`` makes) and a 2x2 system per pair give the flows, not one
@@ -962,23 +976,45 @@ def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
     Every ``(grid, pair)`` row is bit-identical alone, in any batch, in any pair list or order that holds it, in either order of
     its two lines, and from run to run.  With a 2-D single grid the batch dimension is dropped.
 
-    The outputs are not differentiable (the call runs as under ``torch.no_grad()``).  Mixed topologies, AC N-2 and line plus
-    generator outages are out of scope.  Contract: ``include/gns_powerflow.h``, "DC N-2 contingency screening"."""
+    Gradients: by default the outputs are not differentiable (the call runs as under ``torch.no_grad()``).  With
+    ``differentiable=True``, grad mode on and ``requires_grad`` on an input, ``worst_loading`` (and ``line_flow`` with
+    ``flows=True``) is differentiable through one ``gns_dcn2_adjoint`` call on the forward's topology and pair list (per pair a
+    2x2 system again, per distinct line of the list one more solve on the base factor and one for the whole list; nothing is
+    factored or solved per pair, ``line_flow`` is not kept for the backward, and with ``flows=False`` no ``[Bt,P,E]`` tensor is
+    formed), and ``base.theta``, ``base.line_flow`` and ``base.slack_p`` through ``dc_power_flow``'s adjoint.  The derivative is
+    exact with respect to ``Pd``, ``Gs``, the lines' ``x``, ``tau``, ``shift`` and the generators' ``Pg``; every other column gets
+    0, and row ``(j,k)`` gives exactly 0 to the own columns of lines ``j`` and ``k`` (a line that every contributing row holds has
+    exact zeros; next to other rows' contributions the row's own cancels to rounding in the shared solves).  ``rating`` is a constant; a tie in the worst loading
+    sends the gradient to ``worst_line``; ``worst_line``, ``islanding``, ``converged`` and ``pairs`` are not differentiable.  A row
+    that is NaN / -1 (an islanding pair, a non-finite 2x2 update) contributes nothing when its incoming gradients are exactly zero
+    or absent (a loss that indexes ``~islanding``); otherwise, and for a grid that is not solved, the grid's three gradient rows
+    are NaN (zero rows for an unsolved grid whose incoming gradients are all zero).  The forward outputs are bit-identical with and
+    without gradients.  A grid's gradient is bit-identical alone, in any batch and from run to run for the same pair list, and a
+    list that holds ``(k,j)`` where another holds ``(j,k)`` gives the same bits; the order of the list may change its last bits.
+    Mixed topologies, AC N-2, line plus generator outages and second derivatives are out of scope.
+    Contract: ``include/gns_powerflow.h``, "DC N-2 contingency screening"."""
     if not isinstance(flows, bool):
         raise ValueError(f'flows must be a bool, got {flows!r}')
+    if not isinstance(differentiable, bool):
+        raise ValueError(f'differentiable must be a bool, got {differentiable!r}')
+    grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                              for t in (buses, lines, generators))
     with torch.no_grad():
         # the shapes first, so that a bad pair list or rating is refused where no device is visible too
         single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
         pairs_np = _pair_list(pairs, shaped_lines.shape[1])
         rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
-        buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
+    with torch.set_grad_enabled(grad):
+        if not grad:
+            buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
         single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, 0.0, 0, False)
         lib = load_library()
         Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
         rating = None if rating is None else rating.to(dev).contiguous()
         P = pairs_np.shape[0]
         cfg = PfConfig(N, E, generators.shape[1], 0, 0.0)
-        key, args = _topology_key(buses, lines, generators, slack_bus, 'dc_n2_contingency_screen')
+        plain = (buses.detach(), lines.detach(), generators.detach())
+        key, args = _topology_key(*plain, slack_bus, 'dc_n2_contingency_screen')
         topo = _analysed(_FD, key, args, dev)
         isl_np = _topology_pair_islanding(topo, args, pairs_np)
 
@@ -990,25 +1026,62 @@ def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
         cand_dev, cols_dev = torch.from_numpy(cand32).to(dev), torch.from_numpy(cols32).to(dev)
         isl_dev = torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
 
-        flow = torch.empty(Bt, P, E, dtype=torch.float64, device=dev) if flows else None
-        worst = torch.empty(Bt, P, dtype=torch.float64, device=dev)
-        worst_line = torch.empty(Bt, P, dtype=torch.int32, device=dev)
-        conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
+        def shared():
+            """What both C calls take between Bt and their own arguments: the candidate and pair lists on the host and on the
+            device, the islanding mask, the rating and whether it is per grid.  (A closure, used as late as the backward: it keeps
+            their owners alive.)"""
+            return (cand32.ctypes.data, cand_dev.data_ptr(), n_cand, cols32.ctypes.data, cols_dev.data_ptr(), P, isl_dev.data_ptr(),
+                    _ptr(rating), int(rating is not None and rating.dim() == 2))
+
         lds = lambda: _dcn1_lds_bytes(topo.host)[0]                           # noqa: E731
-        nbytes = ctypes.c_size_t()
-        _check(lib.gns_dcn2_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, n_cand, ctypes.byref(nbytes)),
-               'gns_dcn2_workspace_bytes', lds, _DCN2.formula)
-        ws = _gns._workspace(nbytes.value, dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_dcn2_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
-                                       lines.data_ptr(), generators.data_ptr(), Bt, cand32.ctypes.data, cand_dev.data_ptr(), n_cand,
-                                       cols32.ctypes.data, cols_dev.data_ptr(), P, isl_dev.data_ptr(), _ptr(rating),
-                                       int(rating is not None and rating.dim() == 2), _ptr(flow), worst.data_ptr(),
-                                       worst_line.data_ptr(), conv.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                   'gns_dcn2_screen', lds, _DCN2.formula)
-        # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
-        base = _dc_solve(lib, cfg, _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host)), buses, lines, generators)
+        adjoint_lds = lambda: _dcn2_adjoint_lds_bytes(topo.host)[0]           # noqa: E731
+
+        def adjoint_workspace_bytes():
+            nbytes = ctypes.c_size_t()
+            _check(lib.gns_dcn2_adjoint_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, n_cand, P, ctypes.byref(nbytes)),
+                   'gns_dcn2_adjoint_workspace_bytes', adjoint_lds, _DCN2_ADJOINT_LDS_FORMULA)
+            return nbytes.value
+
+        def screen(bu, li, ge):
+            flow = torch.empty(Bt, P, E, dtype=torch.float64, device=dev) if flows else None
+            worst = torch.empty(Bt, P, dtype=torch.float64, device=dev)
+            worst_line = torch.empty(Bt, P, dtype=torch.int32, device=dev)
+            conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
+            nbytes = ctypes.c_size_t()
+            _check(lib.gns_dcn2_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, n_cand, ctypes.byref(nbytes)),
+                   'gns_dcn2_workspace_bytes', lds, _DCN2.formula)
+            ws = _gns._workspace(nbytes.value, dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(lib.gns_dcn2_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                           li.data_ptr(), ge.data_ptr(), Bt, *shared(), _ptr(flow), worst.data_ptr(),
+                                           worst_line.data_ptr(), conv.data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                       'gns_dcn2_screen', lds, _DCN2.formula)
+            return flow, worst, worst_line, conv
+
+        def adjoint(bu, li, ge, worst_line, conv, incoming, need):
+            gb, gl, gg = (torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need))
+            gflow, gworst = (None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming)
+            ws = _gns._workspace(adjoint_workspace_bytes(), dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(lib.gns_dcn2_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                            li.data_ptr(), ge.data_ptr(), Bt, *shared(), worst_line.data_ptr(), conv.data_ptr(),
+                                            _ptr(gflow), _ptr(gworst), _ptr(gb), _ptr(gl), _ptr(gg), ws.data_ptr(), ws.numel(),
+                                            stream), 'gns_dcn2_adjoint', adjoint_lds, _DCN2_ADJOINT_LDS_FORMULA)
+            return [gb, gl, gg]
+
+        base_target = _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host))
+        if grad:
+            # the backward's own refusal (its LDS image is the largest of the call) comes before anything is launched
+            adjoint_workspace_bytes()
+            flow, worst, worst_line, conv = _DCN1Function.apply(screen, adjoint, buses, lines, generators)
+            base = list(_DCFunction.apply(lambda *a: _dc_solve(lib, cfg, base_target, *a),
+                                          lambda *a: _dc_adjoint(lib, cfg, base_target, *a), buses, lines, generators))
+        else:
+            flow, worst, worst_line, conv = screen(*plain)
+            # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
+            base = _dc_solve(lib, cfg, base_target, *plain)
         base = [torch.ones(Bt, N, dtype=torch.float64, device=dev), *base]
         res = [flow, worst, worst_line]
         pairs_t, islanding, conv = torch.from_numpy(pairs_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev), conv.bool()

@@ -488,7 +488,8 @@ int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  * Bt times the chunks of either kernel, above 2^31 - 1; GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES; GNS_ESIZE
  * for a short workspace.  GNS_EINVAL wins over GNS_EUNSUPPORTED, which wins over GNS_ESIZE (a NULL workspace is looked at with its
  * size).  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
- * Gradients: gns_dcn2_adjoint, below.  Not here: batches that mix topologies, AC N-2, line plus generator outages. */
+ * Gradients: gns_dcn2_adjoint, below.  The AC solve of chosen pairs: gns_acn2_screen.  Not here: batches that mix topologies, line
+ * plus generator outages. */
 int gns_dcn2_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
 int gns_dcn2_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_cand, size_t* bytes);
 int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
@@ -545,7 +546,7 @@ int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, const void*
  * Bt times the chunks of any kernel, or Bt * n_cand, above 2^31 - 1; then GNS_EUNSUPPORTED for an LDS image above
  * GNS_PF_LDS_MAX_BYTES (from the workspace query too); then, when an output is asked for, GNS_EINVAL for a NULL workspace and
  * GNS_ESIZE for a short one.  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
- * Not here: batches that mix topologies, AC N-2, line plus generator outages, second derivatives. */
+ * Not here: batches that mix topologies, line plus generator outages, second derivatives. */
 int gns_dcn2_adjoint_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
 int gns_dcn2_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_cand, int32_t n_pair,
                                      size_t* bytes);
@@ -586,8 +587,8 @@ int gns_dcn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  *   whose line's id columns do not name an entry of the blob's Y-bus pattern.  Other rows are unaffected.
  *   Every (grid, outage) row is bit-identical alone, in any batch, for any outage list or order that holds the outage (duplicates
  *   are independent rows), and from run to run: no atomics, the reductions by a total order.
- *   Gradients: gns_acn1_adjoint, below.  Not here: batches that mix topologies (one blob per call), N-2 outages, generator
- *   reactive limits.
+ *   Gradients: gns_acn1_adjoint, below.  Double outages: gns_acn2_screen, "AC N-2 contingency screening" below.  Not here: batches
+ *   that mix topologies (one blob per call), generator reactive limits.
  *
  * Inputs: outages as 0-based line indices, on the host (checked before the launch) and on the device (read by the kernel), both
  * [n_outage] int32; islanding [n_outage] uint8 on the device; rating NULL, [E] (rating_per_grid 0) or [Bt,E] (1) fp64 on the device;
@@ -686,6 +687,56 @@ int gns_acn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
                      const double* grad_v_min, const double* grad_v_max,
                      float* grad_buses, float* grad_lines, float* grad_generators,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* AC N-2 contingency screening: Newton-Raphson on every grid of a batch with each PAIR of lines of a list out of service at once (an
+ * N-2 set), with the outputs of "AC contingency screening" above per (grid, pair), from the base analysis alone.
+ *
+ * Semantics: those of gns_acn1_screen with two lines out.  Row (grid, p) is Newton-Raphson on the grid without the lines
+ *   pairs[p][0] and pairs[p][1]: its Y-bus is the sum of the line stamps with those two lines' eight skipped (each entry a sum in
+ *   stamp order, never a subtraction: the values gns_pf_solve computes on the grid with both line rows deleted); injections, bus
+ *   roles and the vg set points are the base case's.  Two outages remove entries from the Jacobian and add none, so the blob of the
+ *   base topology serves every row, with numeric zeros where an entry lost its only lines (two parallel lines with no third).
+ *   Nothing is analysed or allocated per pair.  The warm start from base_v, base_theta, the convergence test, the update, max_iter,
+ *   the failure rules, the branch flows (all four exactly 0 at BOTH outaged lines), worst_loading / worst_line, v_min / v_max and
+ *   their buses, and the order of the summaries (the lowest index among equals, NaN first) are gns_acn1_screen's, word for word.
+ *   The two lines of a pair differ; either order of them is the same row bit for bit (the kernel orders them itself), and duplicate
+ *   pairs are independent rows.  Lines may share a bus, be parallel, or run from a bus to itself.
+ *   Islanding: the caller finds the pairs that disconnect the graph (one line a bridge of the topology, or the second a bridge of
+ *   the graph without the first) and passes islanding[n_pair] (1: islanding); the kernel does not decide that numerically.  Those
+ *   rows get NaN in every fp64 output, -1 in worst_line, v_min_bus, v_max_bus and iterations, and converged = 0, in every grid.  So
+ *   does every row of a grid with base_converged = 0, and a row one of whose lines has id columns that do not name an entry of the
+ *   blob's Y-bus pattern (nothing is read out of bounds for it).  Other rows are unaffected.
+ *   Every (grid, pair) row is bit-identical alone, in any batch, for any pair list or order that holds the pair, in either order of
+ *   its two lines, and from run to run: no atomics, the reductions by a total order.
+ *   Not here: gradients, batches that mix topologies (one blob per call), line plus generator outages, generator reactive limits.
+ *
+ * Inputs: gns_acn1_screen's, but for the list: pairs as 0-based line indices [n_pair,2] int32, on the host (checked before the
+ * launch) and on the device (read by the kernel); islanding [n_pair] uint8 on the device.
+ * Outputs (row r = grid * n_pair + position in the list): v, theta [Bt,n_pair,N] and p_from, q_from, p_to, q_to [Bt,n_pair,E] fp64,
+ * each of which may be NULL (not written); worst_loading, v_min, v_max, mismatch fp64, worst_line, v_min_bus, v_max_bus, iterations
+ * int32, converged uint8 (0/1), all [Bt,n_pair].
+ *
+ * Kernels (gns_acn2.hip): gns_acn1_screen's pre-kernel writes the base Y-bus of every grid to the workspace once; then one wave per
+ * (grid, pair) with gns_pf_solve's LDS image (gns_pf_info.lds_bytes: every topology gns_acn1_screen accepts this call accepts) reads
+ * its grid's base Y-bus and holds the at most eight entries its lines touch (ff, tt, ft, tf of each) in registers, the same in every
+ * lane, each recomputed from its stamps without both lines; an entry both lines touch is held more than once with the same value.
+ * Workspace (gns_acn2_workspace_bytes): the base Y-bus, gns_acn1_workspace_bytes' figure for the same Bt, whatever n_pair is.
+ *
+ * Errors: GNS_EINVAL for a NULL cfg, blob, input, pair list, islanding mask, base_v, base_theta, base_converged, workspace or
+ * output other than v, theta and the four flows, a negative max_iter or tol, a blob that is not a Newton-Raphson blob or whose N, E,
+ * Gn are not cfg's, n_pair <= 0, a line outside 0 .. E-1, a pair of twice the same line, rating_per_grid outside {0, 1}, or
+ * Bt * n_pair above 2^31 - 1; then GNS_ESIZE for a short workspace; then GNS_EUNSUPPORTED for an LDS image above
+ * GNS_PF_LDS_MAX_BYTES.  Every refusal comes before any launch; nothing is allocated and the host is not synchronised. */
+int gns_acn2_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_pair, size_t* bytes);
+int gns_acn2_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                    const float* buses, const float* lines, const float* generators, int64_t Bt,
+                    const int32_t* pairs_host, const int32_t* pairs_dev, int32_t n_pair, const uint8_t* islanding,
+                    const double* rating, int32_t rating_per_grid,
+                    const double* base_v, const double* base_theta, const uint8_t* base_converged,
+                    double* v, double* theta, double* p_from, double* q_from, double* p_to, double* q_to,
+                    double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
+                    int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

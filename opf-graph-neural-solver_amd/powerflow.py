@@ -35,6 +35,10 @@ from the base solution, on the base topology's analysis alone (an outage only re
 voltages, the branch flows at both ends of every line, the worst loading and the voltage extremes (``csrc/gns_acn1.hip``).
 With ``differentiable=True`` its backward is one ``gns_acn1_adjoint`` call: per pair one factorisation and one transposed solve
 at the forward's state, on the same analysis.
+
+``ac_n2_contingency_screen(...)`` is that screen for a list of double-line outages, such as the worst pairs
+``dc_n2_contingency_screen`` ranked: Newton-Raphson on every ``(grid, pair)``, again on the base topology's analysis alone
+(``csrc/gns_acn2.hip``).
 """
 from __future__ import annotations
 
@@ -63,6 +67,10 @@ DcN2ContingencyResult = namedtuple('DcN2ContingencyResult', ['base', 'pairs', 'l
 AcContingencyResult = namedtuple('AcContingencyResult', ['base', 'outages', 'v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to',
                                                          'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max', 'v_max_bus',
                                                          'converged', 'iterations', 'mismatch', 'islanding'])
+
+AcN2ContingencyResult = namedtuple('AcN2ContingencyResult', ['base', 'pairs', 'v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to',
+                                                             'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max', 'v_max_bus',
+                                                             'converged', 'iterations', 'mismatch', 'islanding'])
 
 MixedPlan = namedtuple('MixedPlan', ['topology', 'order', 'grid_off', 'member_off', 'topo_set', 'slack_bus', 'islanded'])
 
@@ -151,6 +159,7 @@ _DCN2_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per
                      "the right-hand sides of W candidate lines side by side, here with W = 1, the narrowest")
 _DCN2 = _Solver('gns_dcn2', FdTopology, _DCN2_LDS_FORMULA)   # the DC N-2 screen: the N-1 screen's analysis and image
 _ACN1 = _Solver('gns_acn1', PowerFlowTopology, _LDS_FORMULA)   # the AC contingency screen: Newton-Raphson's analysis and LDS image
+_ACN2 = _Solver('gns_acn2', PowerFlowTopology, _LDS_FORMULA)   # the AC N-2 screen: the same analysis and image again
 _DCN1_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W) bytes per workgroup: the screen's image, a second "
                              "array of W right-hand sides for the adjoint solves and three doubles per outage, here with W = 1, the "
                              "narrowest")
@@ -882,8 +891,9 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
         return DcContingencyResult(DcPowerFlowResult(*base), outages_t, res[0], res[1], res[2], islanding, conv)
 
 
-def _pair_list(pairs, E):
-    """The checked list of line pairs as an int64 numpy array ``[P,2]``; None: every ``j < k`` in lexicographic order."""
+def _pair_list(pairs, E, single='dc_contingency_screen'):
+    """The checked list of line pairs as an int64 numpy array ``[P,2]``; None: every ``j < k`` in lexicographic order.  ``single``:
+    the single-outage call a pair of twice the same line is sent to."""
     if pairs is None:
         if E < 2:
             raise ValueError(f'pairs: a grid with {E} line(s) has no pair of lines to take out')
@@ -902,7 +912,7 @@ def _pair_list(pairs, E):
     same = np.flatnonzero(o[:, 0] == o[:, 1])
     if same.size:
         raise ValueError(f'pairs must name two different lines, got ({int(o[same[0], 0])}, {int(o[same[0], 1])}) at row {int(same[0])}: '
-                         'a single outage is dc_contingency_screen\'s')
+                         f'a single outage is {single}\'s')
     return o
 
 
@@ -991,7 +1001,8 @@ def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
     are NaN (zero rows for an unsolved grid whose incoming gradients are all zero).  The forward outputs are bit-identical with and
     without gradients.  A grid's gradient is bit-identical alone, in any batch and from run to run for the same pair list, and a
     list that holds ``(k,j)`` where another holds ``(j,k)`` gives the same bits; the order of the list may change its last bits.
-    Mixed topologies, AC N-2, line plus generator outages and second derivatives are out of scope.
+    Mixed topologies, line plus generator outages and second derivatives are out of scope; the AC solve of chosen pairs is
+    ``ac_n2_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "DC N-2 contingency screening"."""
     if not isinstance(flows, bool):
         raise ValueError(f'flows must be a bool, got {flows!r}')
@@ -1171,7 +1182,7 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     gradients; a grid's gradient is bit-identical alone, in any batch and from run to run for the same outage list (another order
     of the list may change its last bits).
 
-    Out of scope: batches that mix topologies, N-2 outages and generator reactive limits.
+    Out of scope: batches that mix topologies and generator reactive limits.  Double outages: ``ac_n2_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "AC contingency screening"."""
     if not isinstance(flows, bool):
         raise ValueError(f'flows must be a bool, got {flows!r}')
@@ -1278,6 +1289,113 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
             base = [t[0] for t in base]
             res = [None if t is None else t[0] for t in res]
         return AcContingencyResult(PowerFlowResult(*base), outages_t, *res, islanding)
+
+
+def ac_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, pairs=None, rating=None,
+                             tol=1e-8, max_iter=10, flows=False, states=False):
+    """AC N-2 contingency screening of every grid of a batch, on the device: Newton-Raphson on each ``(grid, pair)`` of the
+    double-line outages of ``pairs``, with the outputs of ``ac_contingency_screen`` per pair.  Two outages remove eight Y-bus stamps
+    and nothing else, so the one analysis of the base topology (``newton_raphson``'s, cached) serves every pair, where
+    ``newton_raphson(mixed_topologies=True)`` on the expanded batch analyses one topology per distinct pair and holds a copy of the
+    inputs per row.  It is the AC check of the pairs a linear screen ranked worst: ``dc_n2_contingency_screen`` over every pair,
+    the few hundred highest ``worst_loading``, then this call with ``pairs=`` those.
+
+    Inputs, column maps, the slack, the device handling, ``rating``, ``tol`` and ``max_iter`` are those of
+    ``ac_contingency_screen``; the whole batch shares one topology.  ``pairs``: a ``[P,2]`` integer tensor, array or sequence of
+    0-based line indices, default every ``j < k`` in lexicographic order (``E (E - 1) / 2`` rows).  The two lines of a pair differ
+    (a single outage is ``ac_contingency_screen``'s); duplicate pairs and both orders of a pair are allowed and are independent rows.
+
+    Row ``(g, p)`` is Newton-Raphson on grid ``g`` with both lines of ``pairs[p]`` out of service: the Y-bus from the line stamps
+    without those two lines', the injections, bus roles and ``vg`` set points unchanged, warm-started from ``base.v[g]``,
+    ``base.theta[g]``; the convergence test, update, failure rules and float64 arithmetic of ``include/gns_powerflow.h``.  The lines
+    may share a bus, be parallel, or run from a bus to itself.
+
+    Returns ``AcN2ContingencyResult``, ``AcContingencyResult``'s fields with ``pairs`` in place of ``outages``:
+      base           the ``PowerFlowResult`` of ``newton_raphson`` on the same inputs with the same ``tol`` and ``max_iter``, bit for bit
+      pairs          ``[P,2]`` int64, as given
+      v, theta       None by default; with ``states=True`` ``[Bt,P,N]`` float64, the post-outage state
+      p_from, q_from, p_to, q_to   None by default; with ``flows=True`` ``[Bt,P,E]`` float64, ``ac_contingency_screen``'s branch flows,
+                     all four 0 at both outaged lines.  The defaults are the opposite of ``ac_contingency_screen``'s: at every pair
+                     of case118 the four flow tensors are 102 MB per grid, and the kernel writes the summaries alone without them.
+      worst_loading  ``[Bt,P]`` float64, ``max_l max(|S_f|, |S_t|) / rating_l``;  worst_line ``[Bt,P]`` int32, the lowest of equals
+      v_min, v_max   ``[Bt,P]`` float64 with v_min_bus, v_max_bus ``[Bt,P]`` int32 (0-based, the lowest of equals)
+      converged, iterations, mismatch   ``[Bt,P]`` bool / int32 / float64, Newton-Raphson's own meaning per row
+      islanding      ``[P]`` bool: the pair disconnects the grid (one line is a bridge of the topology, or the second is a bridge of
+                     the graph without the first; found on the host and kept with the topology, never from a numeric threshold)
+    An islanding pair has NaN / -1 / ``converged`` False / ``iterations`` -1 in every grid; so has every row of a grid whose base
+    solve did not converge.  A row that does not converge keeps its last finite iterate with ``converged`` False, as
+    ``ac_contingency_screen`` does, and its flows and summaries are computed from that iterate.  Every row is bit-identical alone,
+    in any batch, in any pair list or order that holds it, in either order of its two lines, and from run to run.  With a 2-D single
+    grid the batch dimension is dropped.
+
+    Not differentiable: the call runs as under ``torch.no_grad()``, and ``requires_grad`` on an input is ignored without an error.
+    Out of scope: gradients, batches that mix topologies, line plus generator outages and generator reactive limits.
+    Contract: ``include/gns_powerflow.h``, "AC N-2 contingency screening"."""
+    if not isinstance(flows, bool):
+        raise ValueError(f'flows must be a bool, got {flows!r}')
+    if not isinstance(states, bool):
+        raise ValueError(f'states must be a bool, got {states!r}')
+    if not (isinstance(max_iter, (int, np.integer)) and max_iter >= 0):      # (_inputs' checks, here before a device is needed)
+        raise ValueError(f'max_iter must be a non-negative integer, got {max_iter!r}')
+    if not float(tol) >= 0.0:
+        raise ValueError(f'tol must be >= 0, got {tol!r}')
+    with torch.no_grad():
+        # the shapes first, so that a bad pair list or rating is refused where no device is visible too
+        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
+        pairs_np = _pair_list(pairs, shaped_lines.shape[1], 'ac_contingency_screen')
+        rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None,
+                                                                 None, tol, max_iter, False)
+        lib = load_library()
+        Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
+        rating = None if rating is None else rating.to(dev).contiguous()
+        P = pairs_np.shape[0]
+        cfg = PfConfig(N, E, generators.shape[1], int(max_iter), float(tol))
+        key, args = _topology_key(buses, lines, generators, slack_bus, 'ac_n2_contingency_screen')
+        topo = _analysed(_NR, key, args, dev)
+        isl_np = _topology_pair_islanding(topo, args, pairs_np)
+        pairs32 = np.ascontiguousarray(pairs_np.astype(np.int32))
+        pairs_dev, isl_dev = torch.from_numpy(pairs32).to(dev), torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
+        lds = topo.info['lds_bytes']
+
+        # the base case as newton_raphson solves it (its refusals come first)
+        base = _solve(lib, _NR, cfg, _one_topology(topo), buses, lines, generators, None, None)
+        base_conv = base[2].to(torch.uint8)
+
+        def f64(n):
+            return torch.empty(Bt, P, n, dtype=torch.float64, device=dev)
+
+        # one gns_acn2_screen launch: the fifteen outputs in its order (converged as uint8), every pair from the base
+        state = [f64(N), f64(N)] if states else [None, None]
+        flow = [f64(E) for _ in range(4)] if flows else [None] * 4
+        row_f64 = [torch.empty(Bt, P, dtype=torch.float64, device=dev) for _ in range(4)]       # worst, v_min, v_max, mismatch
+        row_i32 = [torch.empty(Bt, P, dtype=torch.int32, device=dev) for _ in range(4)]         # their indices, iterations
+        conv = torch.empty(Bt, P, dtype=torch.uint8, device=dev)
+        nbytes = ctypes.c_size_t()
+        _check(lib.gns_acn2_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, P, ctypes.byref(nbytes)),
+               'gns_acn2_workspace_bytes', lds, _ACN2.formula)
+        ws = _gns._workspace(nbytes.value, dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_acn2_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
+                                       lines.data_ptr(), generators.data_ptr(), Bt, pairs32.ctypes.data, pairs_dev.data_ptr(), P,
+                                       isl_dev.data_ptr(), _ptr(rating), int(rating is not None and rating.dim() == 2),
+                                       base[0].data_ptr(), base[1].data_ptr(), base_conv.data_ptr(), *map(_ptr, state),
+                                       *map(_ptr, flow), row_f64[0].data_ptr(), row_i32[0].data_ptr(), row_f64[1].data_ptr(),
+                                       row_i32[1].data_ptr(), row_f64[2].data_ptr(), row_i32[2].data_ptr(), conv.data_ptr(),
+                                       row_i32[3].data_ptr(), row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream),
+                   'gns_acn2_screen', lds, _ACN2.formula)
+        res = [*state, *flow, row_f64[0], row_i32[0], row_f64[1], row_i32[1], row_f64[2], row_i32[2], conv.bool(), row_i32[3],
+               row_f64[3]]
+        pairs_t, islanding = torch.from_numpy(pairs_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev)
+        if in_dev != dev:
+            base = [t.to(in_dev) for t in base]
+            res = [None if t is None else t.to(in_dev) for t in res]
+            pairs_t, islanding = pairs_t.to(in_dev), islanding.to(in_dev)
+        if single:
+            base = [t[0] for t in base]
+            res = [None if t is None else t[0] for t in res]
+        return AcN2ContingencyResult(PowerFlowResult(*base), pairs_t, *res, islanding)
 
 
 def _not_solved(Bt, N, dev):

@@ -1,8 +1,10 @@
-// The device helpers of the AC contingency screens that gns_acn1.hip (single outages and their adjoint) and gns_acn2.hip (double
-// outages) share: a line's Y-bus stamps, an entry of the Y-bus without one or two lines, the Y-bus view of a pair (the base values
-// but for the entries its lines touch), the Jacobian row on such a view, the total order of the reductions, the outputs of a call
-// with the writer of a row that is not solved, and the kernel that writes the base Y-bus of every grid.  Both screens run this
-// code, so a row of the double-outage screen is computed with the single-outage screen's arithmetic, expression for expression.
+// What the AC contingency screens share, gns_acn1.hip (single outages and their adjoint) and gns_acn2.hip (double outages).  Device:
+// a line's Y-bus stamps, the Y-bus view of a row (the base values but for the entries its line or lines touch, with the predicate
+// "line l is out"), an entry of the Y-bus without the view's lines, the Jacobian row on such a view, the total order of the
+// reductions, the outputs of a call with the writer of a row that is not solved, the row routine both screen kernels run after
+// their prologue (acn_solve_row: Newton-Raphson, the extremes, the flows, the worst loading) and the kernel that writes the base
+// Y-bus of every grid.  Host: the workspace query and the checks and pre-kernel launch of a screen call.  Both screens run this code,
+// so a row of the double-outage screen is computed by the single-outage screen's routine, not by a copy of it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,34 +29,6 @@ __device__ __forceinline__ double2 acn1_stamp(const float* line, const int e, co
   return make_double2(ar, ai);
 }
 
-// Entry p of row i of the Y-bus without line k: pf_ybus_row's sum over the entry's stamps in their order, line k's skipped
-__device__ __forceinline__ double2 acn1_entry_without(const int i, const int p, const int k, const int32_t* y_diag,
-                                                      const int32_t* st_ptr, const int32_t* st, const float* bus, const float* line) {
-  double yr = 0.0, yi = 0.0;
-  if (p == y_diag[i]) { yr = (double)bus[i * 6 + 4]; yi = (double)bus[i * 6 + 5]; }
-  for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
-    const int e = st[q] >> 2;
-    if (e == k) continue;
-    const double2 a = acn1_stamp(line, e, st[q] & 3);
-    yr += a.x; yi += a.y;
-  }
-  return make_double2(yr, yi);
-}
-
-// Entry p of row i of the Y-bus without lines j and k: the same sum with both lines' stamps skipped
-__device__ __forceinline__ double2 acn2_entry_without(const int i, const int p, const int j, const int k, const int32_t* y_diag,
-                                                      const int32_t* st_ptr, const int32_t* st, const float* bus, const float* line) {
-  double yr = 0.0, yi = 0.0;
-  if (p == y_diag[i]) { yr = (double)bus[i * 6 + 4]; yi = (double)bus[i * 6 + 5]; }
-  for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
-    const int e = st[q] >> 2;
-    if (e == j || e == k) continue;
-    const double2 a = acn1_stamp(line, e, st[q] & 3);
-    yr += a.x; yi += a.y;
-  }
-  return make_double2(yr, yi);
-}
-
 // The Y-bus entry (i, k) of the blob's CSR pattern (columns ascending), -1 if it is not there
 __device__ __forceinline__ int acn1_find_entry(const int32_t* y_ptr, const int32_t* y_col, const int i, const int k) {
   int lo = y_ptr[i], hi = y_ptr[i + 1];
@@ -77,8 +51,10 @@ __device__ __forceinline__ bool acn1_line_ends(const float* line, const int e, c
 // a line from a bus to itself), which read y[0..3].  The same in every lane.
 struct Acn1Ybus {
   const double2* base;
+  int k;                  // the outaged line
   int p[4];
   double2 y[4];
+  __device__ __forceinline__ bool out(const int l) const { return l == k; }
   __device__ __forceinline__ double2 at(const int q) const {
     double2 v = base[q];
     if (q == p[0]) v = y[0];
@@ -94,8 +70,10 @@ struct Acn1Ybus {
 // than once and hold the same value each time: the entry without both lines.  The same in every lane.
 struct Acn2Ybus {
   const double2* base;
+  int j, k;               // the outaged lines, j < k
   int p[8];
   double2 y[8];
+  __device__ __forceinline__ bool out(const int l) const { return l == j || l == k; }
   __device__ __forceinline__ double2 at(const int q) const {
     double2 v = base[q];
 #pragma unroll
@@ -104,6 +82,22 @@ struct Acn2Ybus {
     return v;
   }
 };
+
+// Entry p of row i of the Y-bus without the line(s) of the view Y (Y.out): pf_ybus_row's sum over the entry's stamps in their order,
+// the outaged lines' skipped
+template <class YB>   // Acn1Ybus or Acn2Ybus
+__device__ __forceinline__ double2 acn_entry_without(const int i, const int p, const YB& Y, const int32_t* y_diag,
+                                                     const int32_t* st_ptr, const int32_t* st, const float* bus, const float* line) {
+  double yr = 0.0, yi = 0.0;
+  if (p == y_diag[i]) { yr = (double)bus[i * 6 + 4]; yi = (double)bus[i * 6 + 5]; }
+  for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
+    const int e = st[q] >> 2;
+    if (Y.out(e)) continue;
+    const double2 a = acn1_stamp(line, e, st[q] & 3);
+    yr += a.x; yi += a.y;
+  }
+  return make_double2(yr, yi);
+}
 
 // Row i (not the slack) of the Jacobian into its factor slots: gns_powerflow.hip's pf_jacobian_row on the pair's Y-bus
 template <class YB>   // Acn1Ybus or Acn2Ybus
@@ -190,6 +184,173 @@ __device__ __forceinline__ void acn1_row_not_solved(const Acn1Out& o, const size
   }
 }
 
+// A row of either AC screen after its kernel's prologue (the row decode, the decision that the row is solved, the Y-bus view Y of
+// the grid without the row's line or lines): Newton-Raphson on gns_pf_kernel's LDS image from the base solution v0, th0 of grid g,
+// then the state, the voltage extremes, the branch flows and the worst loading of the iterate into row `row` of o.  gns_pf_kernel's
+// loop is restated here, once for both screens, rather than shared with it: pf_solve_grid stays as it is (its comments record what
+// sharing cost).
+template <class YB>   // Acn1Ybus or Acn2Ybus
+__device__ __forceinline__ void acn_solve_row(const int32_t* __restrict__ topo, const float* bus, const float* line, const float* gen,
+                                              const int g, const size_t row, const YB& Y, const double* __restrict__ rating,
+                                              const int rating_per_grid, const double* __restrict__ v0,
+                                              const double* __restrict__ th0, const int max_iter, const double tol, const Acn1Out& o) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x;
+  const int N = topo[PH_N], E = topo[PH_E], slack = topo[PH_SLACK], dim = topo[PH_DIM];
+  const int nnzLU = topo[PH_NNZLU], nsteps = topo[PH_NSTEPS];
+  const int32_t* role = topo + topo[PH_ROLE];
+  const int32_t* th_idx = topo + topo[PH_TH_IDX];
+  const int32_t* vm_idx = topo + topo[PH_VM_IDX];
+  const int32_t* gen_ptr = topo + topo[PH_GEN_PTR];
+  const int32_t* gen_idx = topo + topo[PH_GEN_IDX];
+  const int32_t* y_ptr = topo + topo[PH_Y_PTR];
+  const int32_t* y_col = topo + topo[PH_Y_COL];
+  const int32_t* jslot = topo + topo[PH_JSLOT];
+  const int32_t* pivot = topo + topo[PH_PIVOT];
+  const int32_t* step_ptr = topo + topo[PH_STEP_PTR];
+  const int2* ops = reinterpret_cast<const int2*>(topo + topo[PH_OPS]);
+
+  double* F = lds;                       // [nnzLU] factor, then [dim] right-hand side / Newton step: gns_pf_kernel's image
+  double* rhs = lds + nnzLU;
+  double* Vm = rhs + dim;
+  double* Va = Vm + N;
+  double* Vr = Va + N;
+  double* Vi = Vr + N;
+  double* Ir = Vi + N;
+  double* Ii = Ir + N;
+  double* Psp = Ii + N;
+  double* Qsp = Psp + N;
+
+  // specified injections, bus roles and set points as in the base case; the warm start from the base solution
+  for (int i = lane; i < N; i += PF_THREADS) {
+    double pg = 0.0;
+    for (int q = gen_ptr[i]; q < gen_ptr[i + 1]; ++q) pg += (double)gen[gen_idx[q] * 7 + 6];
+    Psp[i] = pg - (double)bus[i * 6 + 2];
+    Qsp[i] = -(double)bus[i * 6 + 3];
+    const int ro = role[i];
+    double vm = 1.0, va = 0.0;
+    if (ro != 0 && gen_ptr[i + 1] > gen_ptr[i]) vm = (double)gen[gen_idx[gen_ptr[i]] * 7 + 4];
+    if (ro == 0) vm = v0[(size_t)g * N + i];
+    if (ro != 2) va = th0[(size_t)g * N + i] - th0[(size_t)g * N + slack];
+    Vm[i] = vm; Va[i] = va;
+  }
+  __syncthreads();
+
+  int it = 0;
+  bool conv = false;
+  double mis = 0.0;
+  for (;;) {
+    for (int i = lane; i < N; i += PF_THREADS) { Vr[i] = Vm[i] * cos(Va[i]); Vi[i] = Vm[i] * sin(Va[i]); }
+    __syncthreads();
+    // mismatch F = [Re(V conj(YV)) - P ; Im(...) - Q] into the right-hand side, and its infinity norm
+    double nrm = 0.0;
+    bool bad = false;
+    for (int i = lane; i < N; i += PF_THREADS) {
+      double ir = 0.0, ii = 0.0;                 // I_i = sum_k Y_ik V_k: pf_row_current's sum on the pair's Y-bus
+      for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
+        const int c = y_col[p];
+        const double2 y = Y.at(p);
+        ir += y.x * Vr[c] - y.y * Vi[c];
+        ii += y.x * Vi[c] + y.y * Vr[c];
+      }
+      Ir[i] = ir; Ii[i] = ii;
+      if (th_idx[i] >= 0) {
+        const double fp = (Vr[i] * ir + Vi[i] * ii) - Psp[i];
+        rhs[th_idx[i]] = fp;
+        nrm = fmax(nrm, fabs(fp));
+        bad |= !pf_finite(fp);
+      }
+      if (vm_idx[i] >= 0) {
+        const double fq = (Vi[i] * ir - Vr[i] * ii) - Qsp[i];
+        rhs[vm_idx[i]] = fq;
+        nrm = fmax(nrm, fabs(fq));
+        bad |= !pf_finite(fq);
+      }
+    }
+    nrm = pf_wave_max(nrm);
+    if (__ballot(bad)) { mis = __builtin_nan(""); break; }
+    mis = nrm;
+    if (nrm < tol) { conv = true; break; }
+    if (it >= max_iter) break;
+
+    // Jacobian into its factor slots; fill slots, and the entries that lost their only line(s), are zeros
+    for (int s = lane; s < nnzLU; s += PF_THREADS) F[s] = 0.0;
+    __syncthreads();
+    for (int i = lane; i < N; i += PF_THREADS)
+      if (i != slack) acn1_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
+    __syncthreads();
+
+    // the base topology's program: LU factorisation and both triangular solves
+    pf_run_program(nsteps, step_ptr, ops, F, lane);
+
+    // the update, only if every pivot is a finite non-zero and the new iterate is finite
+    bad = pf_bad_pivot(dim, pivot, F, lane);
+    for (int i = lane; i < N; i += PF_THREADS) {
+      if (th_idx[i] >= 0) bad |= !pf_finite(Va[i] - rhs[th_idx[i]]);
+      if (vm_idx[i] >= 0) bad |= !pf_finite(Vm[i] - rhs[vm_idx[i]]);
+    }
+    if (__ballot(bad)) break;
+    for (int i = lane; i < N; i += PF_THREADS) {
+      if (th_idx[i] >= 0) Va[i] -= rhs[th_idx[i]];
+      if (vm_idx[i] >= 0) Vm[i] -= rhs[vm_idx[i]];
+    }
+    __syncthreads();
+    ++it;
+  }
+  // every exit leaves Vr, Vi at the iterate Vm, Va hold: the state the flows and the summaries are computed from
+
+  // the state and the voltage extremes, a bus per lane (the lowest of equal buses)
+  const double inf = __builtin_inf();
+  double lo = -inf, hi = -inf;             // lo holds -|V|: the smallest |V| is the first in acn1_before's order of the negated values
+  int lo_i = INT32_MAX, hi_i = INT32_MAX;
+  for (int i = lane; i < N; i += PF_THREADS) {
+    const double vm = Vm[i];
+    if (o.v) o.v[row * N + i] = vm;
+    if (o.theta) o.theta[row * N + i] = Va[i];
+    if (acn1_before(-vm, i, lo, lo_i)) { lo = -vm; lo_i = i; }
+    if (acn1_before(vm, i, hi, hi_i)) { hi = vm; hi_i = i; }
+  }
+  acn1_wave_first(lo, lo_i);
+  acn1_wave_first(hi, hi_i);
+
+  // the branch flows, a line per lane: S_f = V_f conj(Y_ff V_f + Y_ft V_t), S_t = V_t conj(Y_tf V_f + Y_tt V_t) on the line's own
+  // stamps; zeros at the outaged line(s); NaN at a line whose id columns are not buses of the grid
+  const double* rt = rating ? rating + (rating_per_grid ? (size_t)g * E : 0) : nullptr;
+  double best = -1.0;
+  int bi = INT32_MAX;
+  for (int l = lane; l < E; l += PF_THREADS) {
+    double pf = 0.0, qf = 0.0, pt = 0.0, qt = 0.0;
+    int a, b;
+    if (!acn1_line_ends(line, l, N, a, b)) pf = qf = pt = qt = __builtin_nan("");
+    else if (!Y.out(l)) {
+      const double2 yff = acn1_stamp(line, l, 0), ytt = acn1_stamp(line, l, 1), yft = acn1_stamp(line, l, 2), ytf = acn1_stamp(line, l, 3);
+      const double far = Vr[a], fai = Vi[a], tor = Vr[b], toi = Vi[b];
+      const double ifr = (yff.x * far - yff.y * fai) + (yft.x * tor - yft.y * toi);
+      const double ifi = (yff.x * fai + yff.y * far) + (yft.x * toi + yft.y * tor);
+      const double itr = (ytf.x * far - ytf.y * fai) + (ytt.x * tor - ytt.y * toi);
+      const double iti = (ytf.x * fai + ytf.y * far) + (ytt.x * toi + ytt.y * tor);
+      pf = far * ifr + fai * ifi; qf = fai * ifr - far * ifi;
+      pt = tor * itr + toi * iti; qt = toi * itr - tor * iti;
+    }
+    if (o.p_from) o.p_from[row * E + l] = pf;
+    if (o.q_from) o.q_from[row * E + l] = qf;
+    if (o.p_to) o.p_to[row * E + l] = pt;
+    if (o.q_to) o.q_to[row * E + l] = qt;
+    const double sf = sqrt(pf * pf + qf * qf), s_t = sqrt(pt * pt + qt * qt);
+    const double s = sf != sf ? sf : s_t != s_t ? s_t : fmax(sf, s_t);   // NaN from either end
+    const double load = rt ? s / rt[l] : s;
+    if (acn1_before(load, l, best, bi)) { best = load; bi = l; }
+  }
+  acn1_wave_first(best, bi);
+
+  if (lane == 0) {
+    o.worst[row] = best; o.worst_line[row] = bi;
+    o.v_min[row] = -lo; o.v_min_bus[row] = lo_i;
+    o.v_max[row] = hi; o.v_max_bus[row] = hi_i;
+    o.conv[row] = conv ? 1 : 0; o.iters[row] = it; o.mis[row] = mis;
+  }
+}
+
 // The base Y-bus of every grid into the workspace: a wave per grid, a row per lane (what gns_pf_kernel writes for itself)
 __global__ __launch_bounds__(PF_THREADS) void gns_acn1_ybus_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
                                                                    const float* __restrict__ lines, double2* __restrict__ ybus_ws) {
@@ -203,6 +364,46 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acn1_ybus_kernel(const int32_t
   const float* line = lines + (size_t)g * E * 7;
   double2* Y = ybus_ws + (size_t)g * nnzY;
   for (int i = threadIdx.x; i < N; i += PF_THREADS) pf_ybus_row(i, y_ptr, y_diag, st_ptr, st, bus, line, Y);
+}
+
+// ---- host: what gns_acn1_screen and gns_acn2_screen (and their workspace queries) do alike
+
+// The workspace of either screen: one base Y-bus per grid, whatever the number of rows
+inline int acn_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_row, size_t* bytes) {
+  if (!cfg || !topo_host || !bytes || Bt <= 0 || n_row <= 0) return GNS_EINVAL;
+  const int32_t* h = static_cast<const int32_t*>(topo_host);
+  if (!pf_header_ok<PfBlobKind>(cfg, h)) return GNS_EINVAL;
+  *bytes = pf_ws_bytes_nnzy(h[PH_NNZY], Bt);
+  return GNS_OK;
+}
+
+// A screen call up to its own launch, in the order the codes win: the arguments, the blob's header, the list (list_ok(h): the entry
+// point's own check of its n_row outages or pairs against the blob at h), a workgroup per (grid, row) in one launch, the workspace
+// and the LDS image (pf_check_topology); then the launch of the base Y-bus of every grid into the workspace.  Returns GNS_OK with
+// the LDS image of the row kernel and the outputs as that kernel takes them.
+template <class ListOk>
+int acn_screen_begin(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev, const float* buses, const float* lines,
+                     const float* generators, int64_t Bt, const int32_t* list_host, const int32_t* list_dev, int32_t n_row,
+                     const uint8_t* islanding, int32_t rating_per_grid, const double* base_v, const double* base_theta,
+                     const uint8_t* base_converged, double* v, double* theta, double* p_from, double* q_from, double* p_to,
+                     double* q_to, double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
+                     int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch, void* workspace,
+                     size_t workspace_bytes, void* stream, ListOk list_ok, int64_t* lds, Acn1Out* out) {
+  if (!pf_config_ok(cfg) || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF ||
+      !list_host || !list_dev || n_row <= 0 || !islanding || (rating_per_grid != 0 && rating_per_grid != 1) || !base_v ||
+      !base_theta || !base_converged || !worst_loading || !worst_line || !v_min || !v_min_bus || !v_max || !v_max_bus || !converged ||
+      !iterations || !mismatch || !workspace)
+    return GNS_EINVAL;
+  const int32_t* h = static_cast<const int32_t*>(topo_host);
+  if (!pf_header_ok<PfBlobKind>(cfg, h) || !list_ok(h)) return GNS_EINVAL;
+  int64_t rows = 0;
+  if (!pf_chunks(n_row, 1, Bt, &rows)) return GNS_EINVAL;
+  const int rc = pf_check_topology<PfBlobKind>(cfg, h, Bt, workspace_bytes, lds);
+  if (rc != GNS_OK) return rc;
+  *out = {v, theta, p_from, q_from, p_to, q_to, worst_loading, worst_line, v_min, v_min_bus, v_max, v_max_bus,
+          converged, iterations, mismatch};
+  return pf_launch<gns_acn1_ybus_kernel>(Bt, 0, stream, static_cast<const int32_t*>(topo_dev), buses, lines,
+                                         static_cast<double2*>(workspace));
 }
 
 }  // namespace

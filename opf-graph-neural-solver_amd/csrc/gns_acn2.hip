@@ -17,7 +17,8 @@
 // subtracting the two lines' stamps from the base entries (other bits than a solve without the lines); the N-1 rows of the two
 // lines as a start (a second screen before this one, for an iteration or so saved).
 //
-// gns_acn1_kernel's loop is restated here rather than shared, as that kernel restates gns_pf_kernel's (gns_acn1.hip says why).
+// A row after the prologue is acn_solve_row (gns_acn1_device.h), the routine gns_acn1_kernel runs, on this screen's Y-bus view: a
+// row here is computed with the single-outage screen's code, not a copy of it.
 #include <hip/hip_runtime.h>
 
 #include "../../include/gns_powerflow.h"
@@ -35,26 +36,14 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acn2_kernel(const int32_t* __r
                                                               const uint8_t* __restrict__ conv0,
                                                               const double2* __restrict__ ybus_ws, const int max_iter,
                                                               const double tol, const Acn1Out o) {
-  extern __shared__ double lds[];
-  const int lane = threadIdx.x;
   const size_t row = blockIdx.x;
   const int g = (int)(blockIdx.x / (unsigned)P), pi = (int)(blockIdx.x % (unsigned)P);
-  const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN], slack = topo[PH_SLACK], dim = topo[PH_DIM];
-  const int nnzLU = topo[PH_NNZLU], nnzY = topo[PH_NNZY], nsteps = topo[PH_NSTEPS];
-  const int32_t* role = topo + topo[PH_ROLE];
-  const int32_t* th_idx = topo + topo[PH_TH_IDX];
-  const int32_t* vm_idx = topo + topo[PH_VM_IDX];
-  const int32_t* gen_ptr = topo + topo[PH_GEN_PTR];
-  const int32_t* gen_idx = topo + topo[PH_GEN_IDX];
+  const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN], nnzY = topo[PH_NNZY];
   const int32_t* y_ptr = topo + topo[PH_Y_PTR];
   const int32_t* y_col = topo + topo[PH_Y_COL];
   const int32_t* y_diag = topo + topo[PH_Y_DIAG];
   const int32_t* st_ptr = topo + topo[PH_ST_PTR];
   const int32_t* st = topo + topo[PH_ST];
-  const int32_t* jslot = topo + topo[PH_JSLOT];
-  const int32_t* pivot = topo + topo[PH_PIVOT];
-  const int32_t* step_ptr = topo + topo[PH_STEP_PTR];
-  const int2* ops = reinterpret_cast<const int2*>(topo + topo[PH_OPS]);
   const float* bus = buses + (size_t)g * N * 6;
   const float* line = lines + (size_t)g * E * 7;
   const float* gen = gens + (size_t)g * Gn * 7;
@@ -67,6 +56,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acn2_kernel(const int32_t* __r
   ok = ok && acn1_line_ends(line, j, N, fj, tj) && acn1_line_ends(line, k, N, fk, tk);
   Acn2Ybus Y;
   Y.base = ybus_ws + (size_t)g * nnzY;
+  Y.j = j; Y.k = k;
   if (ok) {
     Y.p[0] = y_diag[fj];
     Y.p[1] = y_diag[tj];
@@ -79,164 +69,22 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acn2_kernel(const int32_t* __r
     ok = Y.p[2] >= 0 && Y.p[3] >= 0 && Y.p[6] >= 0 && Y.p[7] >= 0;
   }
   if (!ok) { acn1_row_not_solved(o, row, N, E); return; }
-  Y.y[0] = acn2_entry_without(fj, Y.p[0], j, k, y_diag, st_ptr, st, bus, line);
-  Y.y[1] = acn2_entry_without(tj, Y.p[1], j, k, y_diag, st_ptr, st, bus, line);
-  Y.y[2] = acn2_entry_without(fj, Y.p[2], j, k, y_diag, st_ptr, st, bus, line);
-  Y.y[3] = acn2_entry_without(tj, Y.p[3], j, k, y_diag, st_ptr, st, bus, line);
-  Y.y[4] = acn2_entry_without(fk, Y.p[4], j, k, y_diag, st_ptr, st, bus, line);
-  Y.y[5] = acn2_entry_without(tk, Y.p[5], j, k, y_diag, st_ptr, st, bus, line);
-  Y.y[6] = acn2_entry_without(fk, Y.p[6], j, k, y_diag, st_ptr, st, bus, line);
-  Y.y[7] = acn2_entry_without(tk, Y.p[7], j, k, y_diag, st_ptr, st, bus, line);
+  Y.y[0] = acn_entry_without(fj, Y.p[0], Y, y_diag, st_ptr, st, bus, line);
+  Y.y[1] = acn_entry_without(tj, Y.p[1], Y, y_diag, st_ptr, st, bus, line);
+  Y.y[2] = acn_entry_without(fj, Y.p[2], Y, y_diag, st_ptr, st, bus, line);
+  Y.y[3] = acn_entry_without(tj, Y.p[3], Y, y_diag, st_ptr, st, bus, line);
+  Y.y[4] = acn_entry_without(fk, Y.p[4], Y, y_diag, st_ptr, st, bus, line);
+  Y.y[5] = acn_entry_without(tk, Y.p[5], Y, y_diag, st_ptr, st, bus, line);
+  Y.y[6] = acn_entry_without(fk, Y.p[6], Y, y_diag, st_ptr, st, bus, line);
+  Y.y[7] = acn_entry_without(tk, Y.p[7], Y, y_diag, st_ptr, st, bus, line);
 
-  double* F = lds;                       // [nnzLU] factor, then [dim] right-hand side / Newton step: gns_acn1_kernel's image
-  double* rhs = lds + nnzLU;
-  double* Vm = rhs + dim;
-  double* Va = Vm + N;
-  double* Vr = Va + N;
-  double* Vi = Vr + N;
-  double* Ir = Vi + N;
-  double* Ii = Ir + N;
-  double* Psp = Ii + N;
-  double* Qsp = Psp + N;
-
-  // specified injections, bus roles and set points as in the base case; the warm start from the base solution
-  for (int i = lane; i < N; i += PF_THREADS) {
-    double pg = 0.0;
-    for (int q = gen_ptr[i]; q < gen_ptr[i + 1]; ++q) pg += (double)gen[gen_idx[q] * 7 + 6];
-    Psp[i] = pg - (double)bus[i * 6 + 2];
-    Qsp[i] = -(double)bus[i * 6 + 3];
-    const int ro = role[i];
-    double vm = 1.0, va = 0.0;
-    if (ro != 0 && gen_ptr[i + 1] > gen_ptr[i]) vm = (double)gen[gen_idx[gen_ptr[i]] * 7 + 4];
-    if (ro == 0) vm = v0[(size_t)g * N + i];
-    if (ro != 2) va = th0[(size_t)g * N + i] - th0[(size_t)g * N + slack];
-    Vm[i] = vm; Va[i] = va;
-  }
-  __syncthreads();
-
-  int it = 0;
-  bool conv = false;
-  double mis = 0.0;
-  for (;;) {
-    for (int i = lane; i < N; i += PF_THREADS) { Vr[i] = Vm[i] * cos(Va[i]); Vi[i] = Vm[i] * sin(Va[i]); }
-    __syncthreads();
-    // mismatch F = [Re(V conj(YV)) - P ; Im(...) - Q] into the right-hand side, and its infinity norm
-    double nrm = 0.0;
-    bool bad = false;
-    for (int i = lane; i < N; i += PF_THREADS) {
-      double ir = 0.0, ii = 0.0;                 // I_i = sum_k Y_ik V_k: pf_row_current's sum on the pair's Y-bus
-      for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
-        const int c = y_col[p];
-        const double2 y = Y.at(p);
-        ir += y.x * Vr[c] - y.y * Vi[c];
-        ii += y.x * Vi[c] + y.y * Vr[c];
-      }
-      Ir[i] = ir; Ii[i] = ii;
-      if (th_idx[i] >= 0) {
-        const double fp = (Vr[i] * ir + Vi[i] * ii) - Psp[i];
-        rhs[th_idx[i]] = fp;
-        nrm = fmax(nrm, fabs(fp));
-        bad |= !pf_finite(fp);
-      }
-      if (vm_idx[i] >= 0) {
-        const double fq = (Vi[i] * ir - Vr[i] * ii) - Qsp[i];
-        rhs[vm_idx[i]] = fq;
-        nrm = fmax(nrm, fabs(fq));
-        bad |= !pf_finite(fq);
-      }
-    }
-    nrm = pf_wave_max(nrm);
-    if (__ballot(bad)) { mis = __builtin_nan(""); break; }
-    mis = nrm;
-    if (nrm < tol) { conv = true; break; }
-    if (it >= max_iter) break;
-
-    // Jacobian into its factor slots; fill slots, and the entries that lost their only lines, are zeros
-    for (int s = lane; s < nnzLU; s += PF_THREADS) F[s] = 0.0;
-    __syncthreads();
-    for (int i = lane; i < N; i += PF_THREADS)
-      if (i != slack) acn1_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
-    __syncthreads();
-
-    // the base topology's program: LU factorisation and both triangular solves
-    pf_run_program(nsteps, step_ptr, ops, F, lane);
-
-    // the update, only if every pivot is a finite non-zero and the new iterate is finite
-    bad = pf_bad_pivot(dim, pivot, F, lane);
-    for (int i = lane; i < N; i += PF_THREADS) {
-      if (th_idx[i] >= 0) bad |= !pf_finite(Va[i] - rhs[th_idx[i]]);
-      if (vm_idx[i] >= 0) bad |= !pf_finite(Vm[i] - rhs[vm_idx[i]]);
-    }
-    if (__ballot(bad)) break;
-    for (int i = lane; i < N; i += PF_THREADS) {
-      if (th_idx[i] >= 0) Va[i] -= rhs[th_idx[i]];
-      if (vm_idx[i] >= 0) Vm[i] -= rhs[vm_idx[i]];
-    }
-    __syncthreads();
-    ++it;
-  }
-  // every exit leaves Vr, Vi at the iterate Vm, Va hold: the state the flows and the summaries are computed from
-
-  // the state and the voltage extremes, a bus per lane (the lowest of equal buses)
-  const double inf = __builtin_inf();
-  double lo = -inf, hi = -inf;             // lo holds -|V|: the smallest |V| is the first in acn1_before's order of the negated values
-  int lo_i = INT32_MAX, hi_i = INT32_MAX;
-  for (int i = lane; i < N; i += PF_THREADS) {
-    const double vm = Vm[i];
-    if (o.v) o.v[row * N + i] = vm;
-    if (o.theta) o.theta[row * N + i] = Va[i];
-    if (acn1_before(-vm, i, lo, lo_i)) { lo = -vm; lo_i = i; }
-    if (acn1_before(vm, i, hi, hi_i)) { hi = vm; hi_i = i; }
-  }
-  acn1_wave_first(lo, lo_i);
-  acn1_wave_first(hi, hi_i);
-
-  // the branch flows, a line per lane: S_f = V_f conj(Y_ff V_f + Y_ft V_t), S_t = V_t conj(Y_tf V_f + Y_tt V_t) on the line's own
-  // stamps; zeros at the two outaged lines; NaN at a line whose id columns are not buses of the grid
-  const double* rt = rating ? rating + (rating_per_grid ? (size_t)g * E : 0) : nullptr;
-  double best = -1.0;
-  int bi = INT32_MAX;
-  for (int l = lane; l < E; l += PF_THREADS) {
-    double pf = 0.0, qf = 0.0, pt = 0.0, qt = 0.0;
-    int a, b;
-    if (!acn1_line_ends(line, l, N, a, b)) pf = qf = pt = qt = __builtin_nan("");
-    else if (l != j && l != k) {
-      const double2 yff = acn1_stamp(line, l, 0), ytt = acn1_stamp(line, l, 1), yft = acn1_stamp(line, l, 2), ytf = acn1_stamp(line, l, 3);
-      const double far = Vr[a], fai = Vi[a], tor = Vr[b], toi = Vi[b];
-      const double ifr = (yff.x * far - yff.y * fai) + (yft.x * tor - yft.y * toi);
-      const double ifi = (yff.x * fai + yff.y * far) + (yft.x * toi + yft.y * tor);
-      const double itr = (ytf.x * far - ytf.y * fai) + (ytt.x * tor - ytt.y * toi);
-      const double iti = (ytf.x * fai + ytf.y * far) + (ytt.x * toi + ytt.y * tor);
-      pf = far * ifr + fai * ifi; qf = fai * ifr - far * ifi;
-      pt = tor * itr + toi * iti; qt = toi * itr - tor * iti;
-    }
-    if (o.p_from) o.p_from[row * E + l] = pf;
-    if (o.q_from) o.q_from[row * E + l] = qf;
-    if (o.p_to) o.p_to[row * E + l] = pt;
-    if (o.q_to) o.q_to[row * E + l] = qt;
-    const double sf = sqrt(pf * pf + qf * qf), s_t = sqrt(pt * pt + qt * qt);
-    const double s = sf != sf ? sf : s_t != s_t ? s_t : fmax(sf, s_t);   // NaN from either end
-    const double load = rt ? s / rt[l] : s;
-    if (acn1_before(load, l, best, bi)) { best = load; bi = l; }
-  }
-  acn1_wave_first(best, bi);
-
-  if (lane == 0) {
-    o.worst[row] = best; o.worst_line[row] = bi;
-    o.v_min[row] = -lo; o.v_min_bus[row] = lo_i;
-    o.v_max[row] = hi; o.v_max_bus[row] = hi_i;
-    o.conv[row] = conv ? 1 : 0; o.iters[row] = it; o.mis[row] = mis;
-  }
+  acn_solve_row(topo, bus, line, gen, g, row, Y, rating, rating_per_grid, v0, th0, max_iter, tol, o);
 }
 
 }  // namespace
 
 extern "C" int gns_acn2_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_pair, size_t* bytes) {
-  if (!cfg || !topo_host || !bytes || Bt <= 0 || n_pair <= 0) return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!pf_header_ok<PfBlobKind>(cfg, h)) return GNS_EINVAL;
-  *bytes = pf_ws_bytes_nnzy(h[PH_NNZY], Bt);          // one base Y-bus per grid, whatever the number of pairs
-  return GNS_OK;
+  return acn_workspace_bytes(cfg, topo_host, Bt, n_pair, bytes);
 }
 
 extern "C" int gns_acn2_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
@@ -248,28 +96,21 @@ extern "C" int gns_acn2_screen(const gns_pf_config* cfg, const void* topo_host, 
                                double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
                                int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch,
                                void* workspace, size_t workspace_bytes, void* stream) {
-  if (!pf_config_ok(cfg) || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF ||
-      !pairs_host || !pairs_dev || n_pair <= 0 || !islanding || (rating_per_grid != 0 && rating_per_grid != 1) || !base_v ||
-      !base_theta || !base_converged || !worst_loading || !worst_line || !v_min || !v_min_bus || !v_max || !v_max_bus || !converged ||
-      !iterations || !mismatch || !workspace)
-    return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!pf_header_ok<PfBlobKind>(cfg, h)) return GNS_EINVAL;
-  for (int32_t p = 0; p < n_pair; ++p) {
-    const int32_t j = pairs_host[2 * p], k = pairs_host[2 * p + 1];
-    if (j < 0 || j >= h[PH_E] || k < 0 || k >= h[PH_E] || j == k) return GNS_EINVAL;
-  }
-  if (Bt > 0x7FFFFFFF / (int64_t)n_pair) return GNS_EINVAL;             // a workgroup per (grid, pair) in one launch
+  // every pair: two different lines of the blob
+  const auto pairs_ok = [&](const int32_t* h) {
+    if (!pf_lines_ok(h, pairs_host, 2 * (int64_t)n_pair)) return false;
+    for (int32_t p = 0; p < n_pair; ++p)
+      if (pairs_host[2 * p] == pairs_host[2 * p + 1]) return false;
+    return true;
+  };
   int64_t lds = 0;
-  const int rc = pf_check_topology<PfBlobKind>(cfg, h, Bt, workspace_bytes, &lds);
+  Acn1Out out;
+  const int rc = acn_screen_begin(cfg, topo_host, topo_dev, buses, lines, generators, Bt, pairs_host, pairs_dev, n_pair, islanding,
+                                  rating_per_grid, base_v, base_theta, base_converged, v, theta, p_from, q_from, p_to, q_to,
+                                  worst_loading, worst_line, v_min, v_min_bus, v_max, v_max_bus, converged, iterations, mismatch,
+                                  workspace, workspace_bytes, stream, pairs_ok, &lds, &out);
   if (rc != GNS_OK) return rc;
-  const int32_t* topo = static_cast<const int32_t*>(topo_dev);
-  double2* ybus = static_cast<double2*>(workspace);
-  const int rc0 = pf_launch<gns_acn1_ybus_kernel>(Bt, 0, stream, topo, buses, lines, ybus);
-  if (rc0 != GNS_OK) return rc0;
-  const Acn1Out out = {v, theta, p_from, q_from, p_to, q_to, worst_loading, worst_line, v_min, v_min_bus, v_max, v_max_bus,
-                       converged, iterations, mismatch};
-  return pf_launch<gns_acn2_kernel>(Bt * n_pair, lds, stream, topo, buses, lines, generators, pairs_dev, (int)n_pair, islanding,
-                                    rating, (int)rating_per_grid, base_v, base_theta, base_converged, (const double2*)ybus,
-                                    cfg->max_iter, cfg->tol, out);
+  return pf_launch<gns_acn2_kernel>(Bt * n_pair, lds, stream, static_cast<const int32_t*>(topo_dev), buses, lines, generators,
+                                    pairs_dev, (int)n_pair, islanding, rating, (int)rating_per_grid, base_v, base_theta,
+                                    base_converged, static_cast<const double2*>(workspace), cfg->max_iter, cfg->tol, out);
 }

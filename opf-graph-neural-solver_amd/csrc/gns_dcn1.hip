@@ -235,8 +235,7 @@ int dcn1_check(const gns_pf_config* cfg, const void* topo_host, const int32_t* o
   if (!cfg || !topo_host || !outages_host || n_outage <= 0) return GNS_EINVAL;
   const int32_t* h = static_cast<const int32_t*>(topo_host);
   if (!pf_header_ok<DcBlobKind>(cfg, h)) return GNS_EINVAL;
-  for (int32_t k = 0; k < n_outage; ++k)
-    if (outages_host[k] < 0 || outages_host[k] >= h[FH_E]) return GNS_EINVAL;
+  if (!pf_lines_ok(h, outages_host, n_outage)) return GNS_EINVAL;
   *lanes = dcn1_lanes(h, GNS_PF_LDS_MAX_BYTES);
   *lds = dcn1_lds_bytes(h, *lanes);
   return GNS_OK;
@@ -250,13 +249,7 @@ size_t dcn1_adjoint_ws_bytes(const int32_t* h, int64_t Bt, int64_t nchunks) {
 }  // namespace
 
 extern "C" int gns_dcn1_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes) {
-  if (!topo_host || !bytes) return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (h[FH_MAGIC] != GNS_FD_MAGIC) return GNS_EINVAL;
-  const int w = dcn1_lanes(h, GNS_PF_LDS_MAX_BYTES);
-  *bytes = dcn1_lds_bytes(h, w);
-  if (lanes) *lanes = w;
-  return GNS_OK;
+  return pf_fd_lds_query(topo_host, bytes, lanes, dcn1_lanes, dcn1_lds_bytes);
 }
 
 extern "C" int gns_dcn1_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_outage, size_t* bytes) {
@@ -279,8 +272,8 @@ extern "C" int gns_dcn1_screen(const gns_pf_config* cfg, const void* topo_host, 
   int64_t lds = 0;
   const int rc = dcn1_check(cfg, topo_host, outages_host, n_outage, &lanes, &lds);
   if (rc != GNS_OK) return rc;
-  const int64_t nchunks = ((int64_t)n_outage + lanes - 1) / lanes;
-  if (Bt > 0x7FFFFFFF / nchunks) return GNS_EINVAL;           // a workgroup per (grid, chunk) in one launch
+  int64_t nchunks = 0;
+  if (!pf_chunks(n_outage, lanes, Bt, &nchunks)) return GNS_EINVAL;
   if (lds > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
   return pf_launch<gns_dcn1_kernel>(Bt * nchunks, lds, stream, static_cast<const int32_t*>(topo_dev), buses, lines, generators,
                                     outages_dev, (int)n_outage, islanding, rating, (int)rating_per_grid, lanes, (int)nchunks,
@@ -288,13 +281,7 @@ extern "C" int gns_dcn1_screen(const gns_pf_config* cfg, const void* topo_host, 
 }
 
 extern "C" int gns_dcn1_adjoint_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes) {
-  if (!topo_host || !bytes) return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (h[FH_MAGIC] != GNS_FD_MAGIC) return GNS_EINVAL;
-  const int w = dcn1_adjoint_lanes(h, GNS_PF_LDS_MAX_BYTES);
-  *bytes = dcn1_adjoint_lds_bytes(h, w);
-  if (lanes) *lanes = w;
-  return GNS_OK;
+  return pf_fd_lds_query(topo_host, bytes, lanes, dcn1_adjoint_lanes, dcn1_adjoint_lds_bytes);
 }
 
 extern "C" int gns_dcn1_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_outage,
@@ -303,8 +290,8 @@ extern "C" int gns_dcn1_adjoint_workspace_bytes(const gns_pf_config* cfg, const 
   const int32_t* h = static_cast<const int32_t*>(topo_host);
   if (!pf_header_ok<DcBlobKind>(cfg, h)) return GNS_EINVAL;
   const int w = dcn1_adjoint_lanes(h, GNS_PF_LDS_MAX_BYTES);
-  const int64_t nchunks = ((int64_t)n_outage + w - 1) / w;
-  if (Bt > 0x7FFFFFFF / nchunks) return GNS_EINVAL;
+  int64_t nchunks = 0;
+  if (!pf_chunks(n_outage, w, Bt, &nchunks)) return GNS_EINVAL;
   if (dcn1_adjoint_lds_bytes(h, w) > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
   *bytes = dcn1_adjoint_ws_bytes(h, Bt, nchunks);
   return GNS_OK;
@@ -329,8 +316,8 @@ extern "C" int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host,
   const int32_t* h = static_cast<const int32_t*>(topo_host);
   lanes = dcn1_adjoint_lanes(h, GNS_PF_LDS_MAX_BYTES);
   lds = dcn1_adjoint_lds_bytes(h, lanes);
-  const int64_t nchunks = ((int64_t)n_outage + lanes - 1) / lanes;
-  if (Bt > 0x7FFFFFFF / nchunks) return GNS_EINVAL;           // a workgroup per (grid, chunk) in one launch
+  int64_t nchunks = 0;
+  if (!pf_chunks(n_outage, lanes, Bt, &nchunks)) return GNS_EINVAL;
   if (lds > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
   if (!grad_buses && !grad_lines && !grad_generators) return GNS_OK;
   if (!workspace) return GNS_EINVAL;

@@ -613,8 +613,8 @@ extern "C" int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, 
   if (rc != GNS_OK) return rc;
   const int32_t* h = static_cast<const int32_t*>(topo_host);
   const int Q = dcn2_pairs_per_wave(n_pair);
-  const int64_t nchunks_c = ((int64_t)n_cand + lanes - 1) / lanes, nchunks_p = ((int64_t)n_pair + Q - 1) / Q;
-  if (Bt > 0x7FFFFFFF / nchunks_c || Bt > 0x7FFFFFFF / nchunks_p) return GNS_EINVAL;   // a workgroup per (grid, chunk) in one launch
+  int64_t nchunks_c = 0, nchunks_p = 0;
+  if (!pf_chunks(n_cand, lanes, Bt, &nchunks_c) || !pf_chunks(n_pair, Q, Bt, &nchunks_p)) return GNS_EINVAL;
   if (lds > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
   if (!workspace) return GNS_EINVAL;
   if (workspace_bytes < dcn2_ws_bytes(h, Bt, n_cand)) return GNS_ESIZE;
@@ -628,13 +628,8 @@ extern "C" int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, 
 }
 
 extern "C" int gns_dcn2_adjoint_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes) {
-  if (!topo_host || !bytes) return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (h[FH_MAGIC] != GNS_FD_MAGIC) return GNS_EINVAL;
-  const Dcn2AdjointShape s = dcn2_adjoint_shape(h, 1, 1);
-  *bytes = s.lds;
-  if (lanes) *lanes = s.lanes;
-  return GNS_OK;
+  // the shape of the shortest lists: the width and the image depend on the blob alone
+  return pf_fd_lds_query(topo_host, bytes, lanes, dcn1_adjoint_lanes, [](const int32_t* h, int) { return dcn2_adjoint_shape(h, 1, 1).lds; });
 }
 
 extern "C" int gns_dcn2_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_cand,

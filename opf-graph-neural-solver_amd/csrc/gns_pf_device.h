@@ -1,7 +1,8 @@
 // What the power-flow kernels and their entry points share (gns_powerflow.hip: Newton-Raphson and its adjoint; gns_fdpf.hip:
 // fast-decoupled).  Device: one wave per grid, the Y-bus of a grid from its line stamps, I = Y V, the pivot test, the interpreter of
 // the blobs' op programs and the grid and member checks of a set kernel.  Host: the checks of a call's
-// arguments, of one blob and of a set of blobs, and the launch.
+// arguments, of one blob and of a set of blobs, and the launch; for the contingency screens (gns_dcn1.hip, gns_dcn2.hip, gns_acn1.hip,
+// gns_acn2.hip) the check of a list of lines, the chunk count of a launch and the body of their LDS queries.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -132,6 +133,33 @@ inline bool pf_adjoint_args_ok(const void* blob_dev, const float* buses, const f
 template <class Kind>
 bool pf_header_ok(const gns_pf_config* shape, const int32_t* h) {
   return h[PH_MAGIC] == Kind::MAGIC && h[PH_N] == shape->n_bus && h[PH_E] == shape->n_line && h[PH_GN] == shape->n_gen;
+}
+
+// Whether every one of the n indices at list is a line of the blob at h (an outage list, or a pair list as 2 P indices)
+inline bool pf_lines_ok(const int32_t* h, const int32_t* list, int64_t n) {
+  for (int64_t k = 0; k < n; ++k)
+    if (list[k] < 0 || list[k] >= h[PH_E]) return false;
+  return true;
+}
+
+// The chunks of `width` a list of n items is cut into; false when Bt grids of that many chunks are more workgroups than one launch
+// takes (a workgroup per (grid, chunk))
+inline bool pf_chunks(int64_t n, int64_t width, int64_t Bt, int64_t* nchunks) {
+  *nchunks = (n + width - 1) / width;
+  return Bt <= 0x7FFFFFFF / *nchunks;
+}
+
+// The body of a contingency screen's *_lds_bytes query on an FD blob: the chunk width lanes_of gives under the limit, and the LDS
+// image bytes_of gives at that width
+template <class Lanes, class Bytes>
+int pf_fd_lds_query(const void* topo_host, int64_t* bytes, int32_t* lanes, Lanes lanes_of, Bytes bytes_of) {
+  if (!topo_host || !bytes) return GNS_EINVAL;
+  const int32_t* h = static_cast<const int32_t*>(topo_host);
+  if (h[FH_MAGIC] != GNS_FD_MAGIC) return GNS_EINVAL;
+  const int w = lanes_of(h, GNS_PF_LDS_MAX_BYTES);
+  *bytes = bytes_of(h, w);
+  if (lanes) *lanes = w;
+  return GNS_OK;
 }
 
 // Host check of a call on the one blob at h, in the order its codes win: GNS_EINVAL unless it is a blob of this kind and shape,

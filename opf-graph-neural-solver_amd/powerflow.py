@@ -45,6 +45,7 @@ from __future__ import annotations
 import ctypes
 import functools
 from collections import namedtuple
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -444,10 +445,7 @@ def _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter, mixed_
     in_dev = buses.device
     buses, lines, generators = (t.to(dev).contiguous() for t in (buses, lines, generators))
     Bt, N = buses.shape[0], buses.shape[1]
-    if not (isinstance(max_iter, (int, np.integer)) and max_iter >= 0):
-        raise ValueError(f'max_iter must be a non-negative integer, got {max_iter!r}')
-    if not float(tol) >= 0.0:
-        raise ValueError(f'tol must be >= 0, got {tol!r}')
+    _check_iteration(tol, max_iter)
     warm = v0 is not None or theta0 is not None
     if warm:
         def start(x, fill):
@@ -463,6 +461,14 @@ def _inputs(buses, lines, generators, B, L, G, v0, theta0, tol, max_iter, mixed_
         raise ValueError(f'mixed_topologies must be a bool, got {mixed_topologies!r}')
     v0, theta0 = (v0, theta0) if warm else (None, None)
     return single, in_dev, buses, lines, generators, v0, theta0
+
+
+def _check_iteration(tol, max_iter):
+    """``tol`` and ``max_iter`` as every iterative solver and screen takes them."""
+    if not (isinstance(max_iter, (int, np.integer)) and max_iter >= 0):
+        raise ValueError(f'max_iter must be a non-negative integer, got {max_iter!r}')
+    if not float(tol) >= 0.0:
+        raise ValueError(f'tol must be >= 0, got {tol!r}')
 
 
 def _run(solver, name, cfg, buses, lines, generators, slack_bus, v0, theta0, mixed_topologies, in_dev, single):
@@ -638,8 +644,13 @@ def _dc_adjoint(lib, cfg, target, buses, lines, gens, theta, conv, incoming, nee
 def _dcn1_lds_bytes(host):
     """``(LDS image, W)`` of the DC contingency screen (``gns_dcn1_lds_bytes``) on the FD blob ``host``: W outages side by side, the
     largest power of two up to 64 whose image fits (W = 1's image when none does)."""
+    return _screen_lds_bytes('gns_dcn1_lds_bytes', host)
+
+
+def _screen_lds_bytes(query, host):
+    """``(LDS image, W)`` as the entry point ``query`` gives them for the FD blob ``host``."""
     lds, lanes = ctypes.c_int64(), ctypes.c_int32()
-    _check(load_library().gns_dcn1_lds_bytes(host.ctypes.data, ctypes.byref(lds), ctypes.byref(lanes)), 'gns_dcn1_lds_bytes')
+    _check(getattr(load_library(), query)(host.ctypes.data, ctypes.byref(lds), ctypes.byref(lanes)), query)
     return lds.value, lanes.value
 
 
@@ -726,10 +737,162 @@ def _rating(rating, Bt, E, single):
 
 def _dcn1_adjoint_lds_bytes(host):
     """``(LDS image, W)`` of the screen's adjoint (``gns_dcn1_adjoint_lds_bytes``) on the FD blob ``host``, as ``_dcn1_lds_bytes``."""
-    lds, lanes = ctypes.c_int64(), ctypes.c_int32()
-    _check(load_library().gns_dcn1_adjoint_lds_bytes(host.ctypes.data, ctypes.byref(lds), ctypes.byref(lanes)),
-           'gns_dcn1_adjoint_lds_bytes')
-    return lds.value, lanes.value
+    return _screen_lds_bytes('gns_dcn1_adjoint_lds_bytes', host)
+
+
+def _screen_setup(name, solver, buses, lines, generators, B, L, G, slack_bus, rows, rating, flags, differentiable, tol=0.0,
+                  max_iter=0):
+    """What the four contingency screens do before their own launches, in the order their refusals are raised: the bool ``flags``
+    (a dict by name), ``tol`` / ``max_iter`` (the DC screens' never fail) and ``differentiable`` (False from a screen without
+    gradients); whether the call is differentiated (``grad``); the shapes, the list ``rows`` (outages, or pairs for a screen named
+    ``*_n2_*``) and the rating, checked where no device is visible too; ``_inputs``; ``solver``'s cached analysis of the one topology;
+    the islanding mask of the list, on the host (``isl_np``) and uploaded (``isl_dev``).  Returns a namespace of these and of the
+    shapes, the configuration ``cfg`` and the detached inputs ``plain``.  The caller goes on under
+    ``torch.set_grad_enabled(s.grad)``."""
+    for flag, value in flags.items():
+        if not isinstance(value, bool):
+            raise ValueError(f'{flag} must be a bool, got {value!r}')
+    _check_iteration(tol, max_iter)                  # (_inputs' checks, here before a device is needed)
+    if not isinstance(differentiable, bool):
+        raise ValueError(f'differentiable must be a bool, got {differentiable!r}')
+    s = SimpleNamespace()
+    s.grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                                for t in (buses, lines, generators))
+    pairs = '_n2_' in name
+    with torch.no_grad():
+        # the shapes first, so that a bad list or rating is refused where no device is visible too
+        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
+        E = shaped_lines.shape[1]
+        s.rows = _pair_list(rows, E, name.replace('_n2', '')) if pairs else _outage_list(rows, E)
+        rating = _rating(rating, shaped.shape[0], E, single)
+    with torch.set_grad_enabled(s.grad):
+        if not s.grad:
+            buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
+        s.single, s.in_dev, s.buses, s.lines, s.generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, tol, max_iter,
+                                                                           False)
+        s.lib = load_library()
+        s.Bt, s.N, s.E, s.dev = s.buses.shape[0], s.buses.shape[1], s.lines.shape[1], s.buses.device
+        s.rating = None if rating is None else rating.to(s.dev).contiguous()
+        s.cfg = PfConfig(s.N, s.E, s.generators.shape[1], int(max_iter), float(tol))
+        s.plain = (s.buses.detach(), s.lines.detach(), s.generators.detach())
+        key, args = _topology_key(*s.plain, slack_bus, name)
+        s.topo = _analysed(solver, key, args, s.dev)
+        s.isl_np = _topology_pair_islanding(s.topo, args, s.rows) if pairs else _topology_bridges(s.topo, args)[s.rows]
+        s.isl_dev = torch.from_numpy(s.isl_np.astype(np.uint8)).to(s.dev)
+    return s
+
+
+def _upload32(a, dev):
+    """An index list as the C calls take it: contiguous int32 on the host, and its copy on the device."""
+    host = np.ascontiguousarray(a.astype(np.int32))
+    return host, torch.from_numpy(host).to(dev)
+
+
+def _shared_args(s, *lists):
+    """``shared()`` gives what every C call of a screen takes between Bt and its own arguments: each of ``lists`` (``_upload32``'s
+    pairs) on the host and on the device with its length, the islanding mask, the rating and whether it is per grid.  (A closure,
+    used as late as the backward: it keeps their owners alive.)"""
+    def shared():
+        return (*(x for host, dev in lists for x in (host.ctypes.data, dev.data_ptr(), host.shape[0])), s.isl_dev.data_ptr(),
+                _ptr(s.rating), int(s.rating is not None and s.rating.dim() == 2))
+    return shared
+
+
+def _screen_workspace_bytes(s, query, counts, lds, formula):
+    """The bytes the workspace query ``query`` of a screen asks for: it takes the configuration, the host blob, Bt and ``counts``."""
+    return _size_query(getattr(s.lib, query), query, (ctypes.byref(s.cfg), s.topo.host.ctypes.data, s.Bt, *counts), lds, formula)
+
+
+def _screen_results(s, base, res, conv_at):
+    """The tail of a screen: ``(base, list, res, islanding)`` on the input device, ``res[conv_at]`` (``converged``, uint8) as bool, and
+    without the batch dimension for a single grid.  ``res`` holds ``[Bt, ...]`` tensors or None."""
+    res[conv_at] = res[conv_at].bool()
+    rows_t, islanding = torch.from_numpy(s.rows).to(s.dev), torch.from_numpy(s.isl_np.copy()).to(s.dev)
+    if s.in_dev != s.dev:
+        base = [t.to(s.in_dev) for t in base]
+        res = [None if t is None else t.to(s.in_dev) for t in res]
+        rows_t, islanding = rows_t.to(s.in_dev), islanding.to(s.in_dev)
+    if s.single:
+        base = [t[0] for t in base]
+        res = [None if t is None else t[0] for t in res]
+    return base, rows_t, res, islanding
+
+
+def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_bytes, adjoint_formula, flows):
+    """Both DC screens after ``_screen_setup``: ``solver``'s screen launch (with its adjoint through ``_DCN1Function`` when the call is
+    differentiated) and the base case.  ``shared``: ``_shared_args``'s closure; ``n_rows``: the rows per grid; ``counts`` /
+    ``adjoint_counts``: what the two workspace queries take after Bt; ``adjoint_lds_bytes`` / ``adjoint_formula``: the adjoint's LDS
+    query and the formula its refusal names.  Returns ``(base, [line_flow, worst_loading, worst_line, converged])``."""
+    lib, cfg, topo, Bt, dev = s.lib, s.cfg, s.topo, s.Bt, s.dev
+    lds = lambda: _dcn1_lds_bytes(topo.host)[0]                              # noqa: E731
+    adjoint_lds = lambda: adjoint_lds_bytes(topo.host)[0]                    # noqa: E731
+    name, adjoint_name = solver.prefix + '_screen', solver.prefix + '_adjoint'
+
+    def adjoint_workspace_bytes():
+        return _screen_workspace_bytes(s, adjoint_name + '_workspace_bytes', adjoint_counts, adjoint_lds, adjoint_formula)
+
+    def screen(bu, li, ge):
+        flow = torch.empty(Bt, n_rows, s.E, dtype=torch.float64, device=dev) if flows else None
+        worst = torch.empty(Bt, n_rows, dtype=torch.float64, device=dev)
+        worst_line = torch.empty(Bt, n_rows, dtype=torch.int32, device=dev)
+        conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
+        ws = _gns._workspace(_screen_workspace_bytes(s, solver.prefix + '_workspace_bytes', counts, lds, solver.formula), dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(getattr(lib, name)(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(), li.data_ptr(),
+                                      ge.data_ptr(), Bt, *shared(), _ptr(flow), worst.data_ptr(), worst_line.data_ptr(),
+                                      conv.data_ptr(), ws.data_ptr(), ws.numel(), stream), name, lds, solver.formula)
+        return flow, worst, worst_line, conv
+
+    def adjoint(bu, li, ge, worst_line, conv, incoming, need):
+        gb, gl, gg = (torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need))
+        gflow, gworst = (None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming)
+        ws = _gns._workspace(adjoint_workspace_bytes(), dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(getattr(lib, adjoint_name)(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                              li.data_ptr(), ge.data_ptr(), Bt, *shared(), worst_line.data_ptr(), conv.data_ptr(),
+                                              _ptr(gflow), _ptr(gworst), _ptr(gb), _ptr(gl), _ptr(gg), ws.data_ptr(), ws.numel(),
+                                              stream), adjoint_name, adjoint_lds, adjoint_formula)
+        return [gb, gl, gg]
+
+    base_target = _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host))
+    if s.grad:
+        # the backward's own refusal (its LDS image is the largest of the call) comes before anything is launched
+        adjoint_workspace_bytes()
+        res = _DCN1Function.apply(screen, adjoint, s.buses, s.lines, s.generators)
+        base = list(_DCFunction.apply(lambda *a: _dc_solve(lib, cfg, base_target, *a),
+                                      lambda *a: _dc_adjoint(lib, cfg, base_target, *a), s.buses, s.lines, s.generators))
+    else:
+        res = screen(*s.plain)
+        # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
+        base = _dc_solve(lib, cfg, base_target, *s.plain)
+    return [torch.ones(Bt, s.N, dtype=torch.float64, device=dev), *base], list(res)
+
+
+def _ac_screen_launch(s, solver, shared, n_rows, base_state, keep_state, flows, bu, li, ge):
+    """One ``gns_acn1_screen`` / ``gns_acn2_screen`` launch (``solver``): the fifteen outputs in its order (``converged`` as uint8),
+    every row warm-started from ``base_state`` (the base ``v``, ``theta`` and ``converged`` as uint8).  ``v`` and ``theta`` are None
+    unless ``keep_state``, the four flows unless ``flows``."""
+    lib, cfg, topo, Bt, dev = s.lib, s.cfg, s.topo, s.Bt, s.dev
+    lds, name = topo.info['lds_bytes'], solver.prefix + '_screen'
+
+    def rows(n, dtype):
+        return [torch.empty(Bt, n_rows, dtype=dtype, device=dev) for _ in range(n)]
+
+    state = [torch.empty(Bt, n_rows, s.N, dtype=torch.float64, device=dev) for _ in range(2)] if keep_state else [None, None]
+    flow = [torch.empty(Bt, n_rows, s.E, dtype=torch.float64, device=dev) for _ in range(4)] if flows else [None] * 4
+    worst, v_min, v_max, mismatch = rows(4, torch.float64)
+    worst_line, v_min_bus, v_max_bus, iterations = rows(4, torch.int32)
+    conv, = rows(1, torch.uint8)
+    out = [*state, *flow, worst, worst_line, v_min, v_min_bus, v_max, v_max_bus, conv, iterations, mismatch]
+    ws = _gns._workspace(_screen_workspace_bytes(s, solver.prefix + '_workspace_bytes', (n_rows,), lds, solver.formula), dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(getattr(lib, name)(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(), li.data_ptr(),
+                                  ge.data_ptr(), Bt, *shared(), *(t.data_ptr() for t in base_state), *map(_ptr, out), ws.data_ptr(),
+                                  ws.numel(), stream), name, lds, solver.formula)
+    return out
 
 
 class _DCN1Function(torch.autograd.Function):
@@ -796,99 +959,14 @@ def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     change its last bits.  Mixed topologies are out of scope; double outages are ``dc_n2_contingency_screen``, the AC screen is
     ``ac_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "DC contingency screening"."""
-    if not isinstance(flows, bool):
-        raise ValueError(f'flows must be a bool, got {flows!r}')
-    if not isinstance(differentiable, bool):
-        raise ValueError(f'differentiable must be a bool, got {differentiable!r}')
-    grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                              for t in (buses, lines, generators))
-    with torch.no_grad():
-        # the shapes first, so that a bad outage list or rating is refused where no device is visible too
-        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
-        out_np = _outage_list(outages, shaped_lines.shape[1])
-        rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
-    with torch.set_grad_enabled(grad):
-        if not grad:
-            buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
-        single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, 0.0, 0, False)
-        lib = load_library()
-        Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
-        rating = None if rating is None else rating.to(dev).contiguous()
-        K = out_np.size
-        cfg = PfConfig(N, E, generators.shape[1], 0, 0.0)
-        plain = (buses.detach(), lines.detach(), generators.detach())
-        key, args = _topology_key(*plain, slack_bus, 'dc_contingency_screen')
-        topo = _analysed(_FD, key, args, dev)
-        isl_np = _topology_bridges(topo, args)[out_np]
-
-        out32 = out_np.astype(np.int32)
-        out_dev, isl_dev = torch.from_numpy(out32).to(dev), torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
-
-        def shared():
-            """What both C calls take between Bt and their own arguments: the outage list on the host and on the device, its
-            length, the islanding mask, the rating and whether it is per grid.  (A closure, used as late as the backward: it keeps
-            their owners alive.)"""
-            return (out32.ctypes.data, out_dev.data_ptr(), K, isl_dev.data_ptr(), _ptr(rating),
-                    int(rating is not None and rating.dim() == 2))
-
-        def workspace(query, lds, formula):
-            nbytes = ctypes.c_size_t()
-            _check(getattr(lib, query)(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)), query, lds, formula)
-            return _gns._workspace(nbytes.value, dev)
-
-        def screen(bu, li, ge):
-            flow = torch.empty(Bt, K, E, dtype=torch.float64, device=dev) if flows else None
-            worst = torch.empty(Bt, K, dtype=torch.float64, device=dev)
-            worst_line = torch.empty(Bt, K, dtype=torch.int32, device=dev)
-            conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
-            lds = lambda: _dcn1_lds_bytes(topo.host)[0]                       # noqa: E731
-            ws = workspace('gns_dcn1_workspace_bytes', lds, _DCN1.formula)
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _check(lib.gns_dcn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
-                                           li.data_ptr(), ge.data_ptr(), Bt, *shared(), _ptr(flow), worst.data_ptr(),
-                                           worst_line.data_ptr(), conv.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                       'gns_dcn1_screen', lds, _DCN1.formula)
-            return flow, worst, worst_line, conv
-
-        def adjoint(bu, li, ge, worst_line, conv, incoming, need):
-            gb, gl, gg = (torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need))
-            gflow, gworst = (None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming)
-            ws = workspace('gns_dcn1_adjoint_workspace_bytes', adjoint_lds, _DCN1_ADJOINT_LDS_FORMULA)
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _check(lib.gns_dcn1_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
-                                            li.data_ptr(), ge.data_ptr(), Bt, *shared(), worst_line.data_ptr(), conv.data_ptr(),
-                                            _ptr(gflow), _ptr(gworst), _ptr(gb), _ptr(gl), _ptr(gg), ws.data_ptr(), ws.numel(),
-                                            stream), 'gns_dcn1_adjoint', adjoint_lds, _DCN1_ADJOINT_LDS_FORMULA)
-            return [gb, gl, gg]
-
-        adjoint_lds = lambda: _dcn1_adjoint_lds_bytes(topo.host)[0]          # noqa: E731
-        base_target = _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host))
-        if grad:
-            # the backward's own refusal (its LDS image is the largest of the call) comes before anything is launched
-            nbytes = ctypes.c_size_t()
-            _check(lib.gns_dcn1_adjoint_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)),
-                   'gns_dcn1_adjoint_workspace_bytes', adjoint_lds, _DCN1_ADJOINT_LDS_FORMULA)
-            flow, worst, worst_line, conv = _DCN1Function.apply(screen, adjoint, buses, lines, generators)
-            base = list(_DCFunction.apply(lambda *a: _dc_solve(lib, cfg, base_target, *a),
-                                          lambda *a: _dc_adjoint(lib, cfg, base_target, *a), buses, lines, generators))
-        else:
-            flow, worst, worst_line, conv = screen(*plain)
-            # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
-            base = _dc_solve(lib, cfg, base_target, *plain)
-        base = [torch.ones(Bt, N, dtype=torch.float64, device=dev), *base]
-        res = [flow, worst, worst_line]
-        outages_t, islanding, conv = torch.from_numpy(out_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev), conv.bool()
-        if in_dev != dev:
-            base = [t.to(in_dev) for t in base]
-            res = [None if t is None else t.to(in_dev) for t in res]
-            outages_t, islanding, conv = outages_t.to(in_dev), islanding.to(in_dev), conv.to(in_dev)
-        if single:
-            base = [t[0] for t in base]
-            res = [None if t is None else t[0] for t in res]
-            conv = conv[0]
-        return DcContingencyResult(DcPowerFlowResult(*base), outages_t, res[0], res[1], res[2], islanding, conv)
+    s = _screen_setup('dc_contingency_screen', _FD, buses, lines, generators, B, L, G, slack_bus, outages, rating, dict(flows=flows),
+                      differentiable)
+    with torch.set_grad_enabled(s.grad):
+        K = s.rows.size
+        base, res = _dc_screen(s, _DCN1, _shared_args(s, _upload32(s.rows, s.dev)), K, (K,), (K,), _dcn1_adjoint_lds_bytes,
+                               _DCN1_ADJOINT_LDS_FORMULA, flows)
+        base, outages_t, res, islanding = _screen_results(s, base, res, 3)
+        return DcContingencyResult(DcPowerFlowResult(*base), outages_t, res[0], res[1], res[2], islanding, res[3])
 
 
 def _pair_list(pairs, E, single='dc_contingency_screen'):
@@ -952,10 +1030,7 @@ def _topology_pair_islanding(topo, args, pairs):
 def _dcn2_adjoint_lds_bytes(host):
     """``(LDS image, W)`` of the N-2 screen's adjoint (``gns_dcn2_adjoint_lds_bytes``) on the FD blob ``host``, as
     ``_dcn1_adjoint_lds_bytes``: W columns side by side in its solve kernel."""
-    lds, lanes = ctypes.c_int64(), ctypes.c_int32()
-    _check(load_library().gns_dcn2_adjoint_lds_bytes(host.ctypes.data, ctypes.byref(lds), ctypes.byref(lanes)),
-           'gns_dcn2_adjoint_lds_bytes')
-    return lds.value, lanes.value
+    return _screen_lds_bytes('gns_dcn2_adjoint_lds_bytes', host)
 
 
 def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, pairs=None, rating=None,
@@ -1004,107 +1079,17 @@ def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
     Mixed topologies, line plus generator outages and second derivatives are out of scope; the AC solve of chosen pairs is
     ``ac_n2_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "DC N-2 contingency screening"."""
-    if not isinstance(flows, bool):
-        raise ValueError(f'flows must be a bool, got {flows!r}')
-    if not isinstance(differentiable, bool):
-        raise ValueError(f'differentiable must be a bool, got {differentiable!r}')
-    grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                              for t in (buses, lines, generators))
-    with torch.no_grad():
-        # the shapes first, so that a bad pair list or rating is refused where no device is visible too
-        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
-        pairs_np = _pair_list(pairs, shaped_lines.shape[1])
-        rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
-    with torch.set_grad_enabled(grad):
-        if not grad:
-            buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
-        single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, 0.0, 0, False)
-        lib = load_library()
-        Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
-        rating = None if rating is None else rating.to(dev).contiguous()
-        P = pairs_np.shape[0]
-        cfg = PfConfig(N, E, generators.shape[1], 0, 0.0)
-        plain = (buses.detach(), lines.detach(), generators.detach())
-        key, args = _topology_key(*plain, slack_bus, 'dc_n2_contingency_screen')
-        topo = _analysed(_FD, key, args, dev)
-        isl_np = _topology_pair_islanding(topo, args, pairs_np)
-
+    s = _screen_setup('dc_n2_contingency_screen', _FD, buses, lines, generators, B, L, G, slack_bus, pairs, rating, dict(flows=flows),
+                      differentiable)
+    with torch.set_grad_enabled(s.grad):
         # the distinct lines of the list, ascending, and each pair as two positions into them
-        cand_np, cols_np = np.unique(pairs_np, return_inverse=True)
-        cand32 = cand_np.astype(np.int32)
-        cols32 = np.ascontiguousarray(cols_np.reshape(P, 2).astype(np.int32))
-        n_cand = cand32.size
-        cand_dev, cols_dev = torch.from_numpy(cand32).to(dev), torch.from_numpy(cols32).to(dev)
-        isl_dev = torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
-
-        def shared():
-            """What both C calls take between Bt and their own arguments: the candidate and pair lists on the host and on the
-            device, the islanding mask, the rating and whether it is per grid.  (A closure, used as late as the backward: it keeps
-            their owners alive.)"""
-            return (cand32.ctypes.data, cand_dev.data_ptr(), n_cand, cols32.ctypes.data, cols_dev.data_ptr(), P, isl_dev.data_ptr(),
-                    _ptr(rating), int(rating is not None and rating.dim() == 2))
-
-        lds = lambda: _dcn1_lds_bytes(topo.host)[0]                           # noqa: E731
-        adjoint_lds = lambda: _dcn2_adjoint_lds_bytes(topo.host)[0]           # noqa: E731
-
-        def adjoint_workspace_bytes():
-            nbytes = ctypes.c_size_t()
-            _check(lib.gns_dcn2_adjoint_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, n_cand, P, ctypes.byref(nbytes)),
-                   'gns_dcn2_adjoint_workspace_bytes', adjoint_lds, _DCN2_ADJOINT_LDS_FORMULA)
-            return nbytes.value
-
-        def screen(bu, li, ge):
-            flow = torch.empty(Bt, P, E, dtype=torch.float64, device=dev) if flows else None
-            worst = torch.empty(Bt, P, dtype=torch.float64, device=dev)
-            worst_line = torch.empty(Bt, P, dtype=torch.int32, device=dev)
-            conv = torch.empty(Bt, dtype=torch.uint8, device=dev)
-            nbytes = ctypes.c_size_t()
-            _check(lib.gns_dcn2_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, n_cand, ctypes.byref(nbytes)),
-                   'gns_dcn2_workspace_bytes', lds, _DCN2.formula)
-            ws = _gns._workspace(nbytes.value, dev)
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _check(lib.gns_dcn2_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
-                                           li.data_ptr(), ge.data_ptr(), Bt, *shared(), _ptr(flow), worst.data_ptr(),
-                                           worst_line.data_ptr(), conv.data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                       'gns_dcn2_screen', lds, _DCN2.formula)
-            return flow, worst, worst_line, conv
-
-        def adjoint(bu, li, ge, worst_line, conv, incoming, need):
-            gb, gl, gg = (torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need))
-            gflow, gworst = (None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming)
-            ws = _gns._workspace(adjoint_workspace_bytes(), dev)
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _check(lib.gns_dcn2_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
-                                            li.data_ptr(), ge.data_ptr(), Bt, *shared(), worst_line.data_ptr(), conv.data_ptr(),
-                                            _ptr(gflow), _ptr(gworst), _ptr(gb), _ptr(gl), _ptr(gg), ws.data_ptr(), ws.numel(),
-                                            stream), 'gns_dcn2_adjoint', adjoint_lds, _DCN2_ADJOINT_LDS_FORMULA)
-            return [gb, gl, gg]
-
-        base_target = _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host))
-        if grad:
-            # the backward's own refusal (its LDS image is the largest of the call) comes before anything is launched
-            adjoint_workspace_bytes()
-            flow, worst, worst_line, conv = _DCN1Function.apply(screen, adjoint, buses, lines, generators)
-            base = list(_DCFunction.apply(lambda *a: _dc_solve(lib, cfg, base_target, *a),
-                                          lambda *a: _dc_adjoint(lib, cfg, base_target, *a), buses, lines, generators))
-        else:
-            flow, worst, worst_line, conv = screen(*plain)
-            # the base case as dc_power_flow solves it (after the screen, whose larger LDS image is the one a refusal names)
-            base = _dc_solve(lib, cfg, base_target, *plain)
-        base = [torch.ones(Bt, N, dtype=torch.float64, device=dev), *base]
-        res = [flow, worst, worst_line]
-        pairs_t, islanding, conv = torch.from_numpy(pairs_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev), conv.bool()
-        if in_dev != dev:
-            base = [t.to(in_dev) for t in base]
-            res = [None if t is None else t.to(in_dev) for t in res]
-            pairs_t, islanding, conv = pairs_t.to(in_dev), islanding.to(in_dev), conv.to(in_dev)
-        if single:
-            base = [t[0] for t in base]
-            res = [None if t is None else t[0] for t in res]
-            conv = conv[0]
-        return DcN2ContingencyResult(DcPowerFlowResult(*base), pairs_t, res[0], res[1], res[2], islanding, conv)
+        P = s.rows.shape[0]
+        cand_np, cols_np = np.unique(s.rows, return_inverse=True)
+        shared = _shared_args(s, _upload32(cand_np, s.dev), _upload32(cols_np.reshape(P, 2), s.dev))
+        n_cand = cand_np.size
+        base, res = _dc_screen(s, _DCN2, shared, P, (n_cand,), (n_cand, P), _dcn2_adjoint_lds_bytes, _DCN2_ADJOINT_LDS_FORMULA, flows)
+        base, pairs_t, res, islanding = _screen_results(s, base, res, 3)
+        return DcN2ContingencyResult(DcPowerFlowResult(*base), pairs_t, res[0], res[1], res[2], islanding, res[3])
 
 
 class _ACN1Function(torch.autograd.Function):
@@ -1184,90 +1169,36 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
 
     Out of scope: batches that mix topologies and generator reactive limits.  Double outages: ``ac_n2_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "AC contingency screening"."""
-    if not isinstance(flows, bool):
-        raise ValueError(f'flows must be a bool, got {flows!r}')
-    if not isinstance(states, bool):
-        raise ValueError(f'states must be a bool, got {states!r}')
-    if not (isinstance(max_iter, (int, np.integer)) and max_iter >= 0):      # (_inputs' checks, here before a device is needed)
-        raise ValueError(f'max_iter must be a non-negative integer, got {max_iter!r}')
-    if not float(tol) >= 0.0:
-        raise ValueError(f'tol must be >= 0, got {tol!r}')
-    if not isinstance(differentiable, bool):
-        raise ValueError(f'differentiable must be a bool, got {differentiable!r}')
-    grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                              for t in (buses, lines, generators))
-    with torch.no_grad():
-        # the shapes first, so that a bad outage list or rating is refused where no device is visible too
-        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
-        out_np = _outage_list(outages, shaped_lines.shape[1])
-        rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
-    with torch.set_grad_enabled(grad):
-        if not grad:
-            buses, lines, generators = buses.detach(), lines.detach(), generators.detach()
-        single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, tol, max_iter, False)
-        lib = load_library()
-        Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
-        rating = None if rating is None else rating.to(dev).contiguous()
-        K = out_np.size
-        cfg = PfConfig(N, E, generators.shape[1], int(max_iter), float(tol))
-        plain = (buses.detach(), lines.detach(), generators.detach())
-        key, args = _topology_key(*plain, slack_bus, 'ac_contingency_screen')
-        topo = _analysed(_NR, key, args, dev)
-        isl_np = _topology_bridges(topo, args)[out_np]
-        out32 = out_np.astype(np.int32)
-        out_dev, isl_dev = torch.from_numpy(out32).to(dev), torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
+    s = _screen_setup('ac_contingency_screen', _NR, buses, lines, generators, B, L, G, slack_bus, outages, rating,
+                      dict(flows=flows, states=states), differentiable, tol, max_iter)
+    with torch.set_grad_enabled(s.grad):
+        lib, cfg, topo, Bt, dev, grad = s.lib, s.cfg, s.topo, s.Bt, s.dev, s.grad
+        K = s.rows.size
+        shared = _shared_args(s, _upload32(s.rows, dev))
         lds = topo.info['lds_bytes']
         target = _one_topology(topo)
 
-        def shared():
-            """What both C calls take between Bt and their own arguments (a closure, used as late as the backward: it keeps their
-            owners alive)."""
-            return (out32.ctypes.data, out_dev.data_ptr(), K, isl_dev.data_ptr(), _ptr(rating),
-                    int(rating is not None and rating.dim() == 2))
-
-        def workspace(query):
-            nbytes = ctypes.c_size_t()
-            _check(getattr(lib, query)(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(nbytes)), query, lds, _ACN1.formula)
-            return nbytes.value
+        def adjoint_workspace_bytes():
+            return _screen_workspace_bytes(s, 'gns_acn1_adjoint_workspace_bytes', (K,), lds, _ACN1.formula)
 
         # the base case as newton_raphson solves it (its refusals come first, then the backward's own, before anything is launched)
         if grad:
-            workspace('gns_acn1_adjoint_workspace_bytes')
+            adjoint_workspace_bytes()
             base = list(_NRFunction.apply(lambda *a: _solve(lib, _NR, cfg, target, *a, None, None),
-                                          lambda *a: _adjoint(lib, cfg, target, *a), buses, lines, generators))
+                                          lambda *a: _adjoint(lib, cfg, target, *a), s.buses, s.lines, s.generators))
         else:
-            base = _solve(lib, _NR, cfg, target, *plain, None, None)
-        base_v, base_theta = base[0].detach(), base[1].detach()      # the warm start is not differentiated
+            base = _solve(lib, _NR, cfg, target, *s.plain, None, None)
         base_conv = base[2].to(torch.uint8)
+        base_state = (base[0].detach(), base[1].detach(), base_conv)      # the warm start is not differentiated
 
         def screen(bu, li, ge):
-            """One ``gns_acn1_screen`` launch: the fifteen outputs in its order (``converged`` as uint8), every pair from the base."""
-            def f64(n):
-                return torch.empty(Bt, K, n, dtype=torch.float64, device=dev)
-
-            state = [f64(N), f64(N)] if states or grad else [None, None]
-            flow = [f64(E) for _ in range(4)] if flows else [None] * 4
-            row_f64 = [torch.empty(Bt, K, dtype=torch.float64, device=dev) for _ in range(4)]       # worst, v_min, v_max, mismatch
-            row_i32 = [torch.empty(Bt, K, dtype=torch.int32, device=dev) for _ in range(4)]         # their indices, iterations
-            conv = torch.empty(Bt, K, dtype=torch.uint8, device=dev)
-            ws = _gns._workspace(workspace('gns_acn1_workspace_bytes'), dev)
-            with torch.cuda.device(dev):
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                _check(lib.gns_acn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
-                                           li.data_ptr(), ge.data_ptr(), Bt, *shared(), base_v.data_ptr(), base_theta.data_ptr(),
-                                           base_conv.data_ptr(), *map(_ptr, state), *map(_ptr, flow), row_f64[0].data_ptr(),
-                                           row_i32[0].data_ptr(), row_f64[1].data_ptr(), row_i32[1].data_ptr(),
-                                           row_f64[2].data_ptr(), row_i32[2].data_ptr(), conv.data_ptr(), row_i32[3].data_ptr(),
-                                           row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                       'gns_acn1_screen', lds, _ACN1.formula)
-            return [*state, *flow, row_f64[0], row_i32[0], row_f64[1], row_i32[1], row_f64[2], row_i32[2], conv, row_i32[3],
-                    row_f64[3]]
+            return _ac_screen_launch(s, _ACN1, shared, K, base_state, states or grad, flows, bu, li, ge)
 
         def adjoint(bu, li, ge, state, incoming, need):
             """One ``gns_acn1_adjoint`` call at the forward's ``state`` (v, theta, converged, worst_line, v_min_bus, v_max_bus)."""
             gin = [torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need)]
             incoming = [None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming]
-            ws = _gns._workspace(workspace('gns_acn1_adjoint_workspace_bytes'), dev)
+            ws = _gns._workspace(adjoint_workspace_bytes(), dev)
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream
                 _check(lib.gns_acn1_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
@@ -1276,18 +1207,10 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
                                             stream), 'gns_acn1_adjoint', lds, _ACN1.formula)
             return gin
 
-        res = list(_ACN1Function.apply(screen, adjoint, buses, lines, generators)) if grad else screen(*plain)
+        res = list(_ACN1Function.apply(screen, adjoint, s.buses, s.lines, s.generators)) if grad else screen(*s.plain)
         if not states:
             res[0] = res[1] = None
-        res[12] = res[12].bool()
-        outages_t, islanding = torch.from_numpy(out_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev)
-        if in_dev != dev:
-            base = [t.to(in_dev) for t in base]
-            res = [None if t is None else t.to(in_dev) for t in res]
-            outages_t, islanding = outages_t.to(in_dev), islanding.to(in_dev)
-        if single:
-            base = [t[0] for t in base]
-            res = [None if t is None else t[0] for t in res]
+        base, outages_t, res, islanding = _screen_results(s, base, res, 12)
         return AcContingencyResult(PowerFlowResult(*base), outages_t, *res, islanding)
 
 
@@ -1331,70 +1254,14 @@ def ac_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
     Not differentiable: the call runs as under ``torch.no_grad()``, and ``requires_grad`` on an input is ignored without an error.
     Out of scope: gradients, batches that mix topologies, line plus generator outages and generator reactive limits.
     Contract: ``include/gns_powerflow.h``, "AC N-2 contingency screening"."""
-    if not isinstance(flows, bool):
-        raise ValueError(f'flows must be a bool, got {flows!r}')
-    if not isinstance(states, bool):
-        raise ValueError(f'states must be a bool, got {states!r}')
-    if not (isinstance(max_iter, (int, np.integer)) and max_iter >= 0):      # (_inputs' checks, here before a device is needed)
-        raise ValueError(f'max_iter must be a non-negative integer, got {max_iter!r}')
-    if not float(tol) >= 0.0:
-        raise ValueError(f'tol must be >= 0, got {tol!r}')
+    s = _screen_setup('ac_n2_contingency_screen', _NR, buses, lines, generators, B, L, G, slack_bus, pairs, rating,
+                      dict(flows=flows, states=states), False, tol, max_iter)
     with torch.no_grad():
-        # the shapes first, so that a bad pair list or rating is refused where no device is visible too
-        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
-        pairs_np = _pair_list(pairs, shaped_lines.shape[1], 'ac_contingency_screen')
-        rating = _rating(rating, shaped.shape[0], shaped_lines.shape[1], single)
-        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None,
-                                                                 None, tol, max_iter, False)
-        lib = load_library()
-        Bt, N, E, dev = buses.shape[0], buses.shape[1], lines.shape[1], buses.device
-        rating = None if rating is None else rating.to(dev).contiguous()
-        P = pairs_np.shape[0]
-        cfg = PfConfig(N, E, generators.shape[1], int(max_iter), float(tol))
-        key, args = _topology_key(buses, lines, generators, slack_bus, 'ac_n2_contingency_screen')
-        topo = _analysed(_NR, key, args, dev)
-        isl_np = _topology_pair_islanding(topo, args, pairs_np)
-        pairs32 = np.ascontiguousarray(pairs_np.astype(np.int32))
-        pairs_dev, isl_dev = torch.from_numpy(pairs32).to(dev), torch.from_numpy(isl_np.astype(np.uint8)).to(dev)
-        lds = topo.info['lds_bytes']
-
         # the base case as newton_raphson solves it (its refusals come first)
-        base = _solve(lib, _NR, cfg, _one_topology(topo), buses, lines, generators, None, None)
-        base_conv = base[2].to(torch.uint8)
-
-        def f64(n):
-            return torch.empty(Bt, P, n, dtype=torch.float64, device=dev)
-
-        # one gns_acn2_screen launch: the fifteen outputs in its order (converged as uint8), every pair from the base
-        state = [f64(N), f64(N)] if states else [None, None]
-        flow = [f64(E) for _ in range(4)] if flows else [None] * 4
-        row_f64 = [torch.empty(Bt, P, dtype=torch.float64, device=dev) for _ in range(4)]       # worst, v_min, v_max, mismatch
-        row_i32 = [torch.empty(Bt, P, dtype=torch.int32, device=dev) for _ in range(4)]         # their indices, iterations
-        conv = torch.empty(Bt, P, dtype=torch.uint8, device=dev)
-        nbytes = ctypes.c_size_t()
-        _check(lib.gns_acn2_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, P, ctypes.byref(nbytes)),
-               'gns_acn2_workspace_bytes', lds, _ACN2.formula)
-        ws = _gns._workspace(nbytes.value, dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_acn2_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
-                                       lines.data_ptr(), generators.data_ptr(), Bt, pairs32.ctypes.data, pairs_dev.data_ptr(), P,
-                                       isl_dev.data_ptr(), _ptr(rating), int(rating is not None and rating.dim() == 2),
-                                       base[0].data_ptr(), base[1].data_ptr(), base_conv.data_ptr(), *map(_ptr, state),
-                                       *map(_ptr, flow), row_f64[0].data_ptr(), row_i32[0].data_ptr(), row_f64[1].data_ptr(),
-                                       row_i32[1].data_ptr(), row_f64[2].data_ptr(), row_i32[2].data_ptr(), conv.data_ptr(),
-                                       row_i32[3].data_ptr(), row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream),
-                   'gns_acn2_screen', lds, _ACN2.formula)
-        res = [*state, *flow, row_f64[0], row_i32[0], row_f64[1], row_i32[1], row_f64[2], row_i32[2], conv.bool(), row_i32[3],
-               row_f64[3]]
-        pairs_t, islanding = torch.from_numpy(pairs_np).to(dev), torch.from_numpy(isl_np.copy()).to(dev)
-        if in_dev != dev:
-            base = [t.to(in_dev) for t in base]
-            res = [None if t is None else t.to(in_dev) for t in res]
-            pairs_t, islanding = pairs_t.to(in_dev), islanding.to(in_dev)
-        if single:
-            base = [t[0] for t in base]
-            res = [None if t is None else t[0] for t in res]
+        base = _solve(s.lib, _NR, s.cfg, _one_topology(s.topo), *s.plain, None, None)
+        res = _ac_screen_launch(s, _ACN2, _shared_args(s, _upload32(s.rows, s.dev)), s.rows.shape[0],
+                                (base[0], base[1], base[2].to(torch.uint8)), states, flows, *s.plain)
+        base, pairs_t, res, islanding = _screen_results(s, base, res, 12)
         return AcN2ContingencyResult(PowerFlowResult(*base), pairs_t, *res, islanding)
 
 
@@ -1470,13 +1337,19 @@ def _launch(lib, solver, op, cfg, target, inputs, rest):
     stream.  The library launches on the current device, so that is the inputs' for the length of the call."""
     Bt, dev = inputs[0].shape[0], inputs[0].device
     ws_name, ws_fn, name, fn = _entry_points(lib, solver.prefix, op, target.suffix)
-    nbytes = ctypes.c_size_t()
-    _check(ws_fn(ctypes.byref(cfg), *target.ws_args, Bt, ctypes.byref(nbytes)), ws_name, target.lds, solver.formula)
-    ws = _gns._workspace(nbytes.value, dev)
+    ws = _gns._workspace(_size_query(ws_fn, ws_name, (ctypes.byref(cfg), *target.ws_args, Bt), target.lds, solver.formula), dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
         _check(fn(ctypes.byref(cfg), *target.args, *map(_ptr, inputs), Bt, *map(_ptr, rest), ws.data_ptr(), ws.numel(), stream),
                name, target.lds, solver.formula)
+
+
+def _size_query(fn, name, args, lds, formula):
+    """The bytes a workspace query ``fn`` (``name``) answers for ``args``, its ``size_t`` out-parameter; ``lds`` and ``formula`` are
+    what a refusal names (``_check``)."""
+    nbytes = ctypes.c_size_t()
+    _check(fn(*args, ctypes.byref(nbytes)), name, lds, formula)
+    return nbytes.value
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,8 @@
-"""``gns_acn1_screen`` (include/gns_powerflow.h, "AC contingency screening") called through ctypes on device tensors, with the base
-solution, ``base_converged`` and ``islanding`` supplied by the caller as the C contract has it.  ``powerflow.ac_contingency_screen``
-computes those three itself and applies ``max_iter`` to its base solve too, so zero or one Newton step of a row, a base angle that
-is not 0 at the slack and caller-owned flags are reachable only from here."""
+"""``gns_acn1_screen`` and ``gns_acn2_screen`` (include/gns_powerflow.h, "AC contingency screening" and "AC N-2 contingency
+screening") called through ctypes on device tensors, with the base solution, ``base_converged`` and ``islanding`` supplied by the
+caller as the C contract has it.  ``powerflow.ac_contingency_screen`` and ``powerflow.ac_n2_contingency_screen`` compute those three
+themselves and apply ``max_iter`` to their base solve too, so zero or one Newton step of a row, a base angle that is not 0 at the
+slack and caller-owned flags are reachable only from here."""
 import ctypes
 from collections import namedtuple
 
@@ -32,6 +33,21 @@ def screen(tp, buses, lines, gens, outages, base_v, base_theta, base_converged, 
     the device, ``outages`` and ``islanding`` sequences [K], ``base_v``, ``base_theta`` [Bt,N], ``base_converged`` [Bt], ``rating``
     None, [E] or [Bt,E].  Returns ``Rows``: the fifteen outputs ([Bt,K,...], ``converged`` as bool), every one pre-filled with a
     sentinel that no row may keep."""
+    out32 = np.ascontiguousarray(np.asarray(outages, dtype=np.int32).reshape(-1))
+    return _call('gns_acn1', tp, buses, lines, gens, out32, out32.size, base_v, base_theta, base_converged, islanding, rating,
+                 max_iter, tol)
+
+
+def screen_pairs(tp, buses, lines, gens, pairs, base_v, base_theta, base_converged, islanding, rating, max_iter, tol):
+    """One ``gns_acn2_screen`` launch: ``screen`` with ``pairs`` [P,2] (either order within a pair; passed as int32 [2P] on host and
+    device) in the place of ``outages`` and ``islanding`` [P].  Returns ``Rows`` [Bt,P,...]."""
+    p32 = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+    return _call('gns_acn2', tp, buses, lines, gens, p32.reshape(-1), p32.shape[0], base_v, base_theta, base_converged, islanding,
+                 rating, max_iter, tol)
+
+
+def _call(prefix, tp, buses, lines, gens, list32, K, base_v, base_theta, base_converged, islanding, rating, max_iter, tol):
+    """``<prefix>_workspace_bytes`` and ``<prefix>_screen`` on the ``K`` rows that the int32 array ``list32`` names."""
     lib = amd.load_library()
     dev = buses.device
     Bt, N, E = buses.shape[0], tp.n, tp.f.size
@@ -39,9 +55,7 @@ def screen(tp, buses, lines, gens, outages, base_v, base_theta, base_converged, 
     buses, lines, gens = (t.contiguous() for t in (buses, lines, gens))
     assert buses.dtype == lines.dtype == gens.dtype == torch.float32
     topo = analysed(tp, dev)
-    out32 = np.ascontiguousarray(np.asarray(outages, dtype=np.int32).reshape(-1))
-    K = out32.size
-    out_dev = torch.from_numpy(out32).to(dev)
+    list_dev = torch.from_numpy(list32).to(dev)
     isl = torch.as_tensor(np.asarray(islanding).astype(np.uint8).reshape(K)).to(dev)
     v0 = torch.as_tensor(base_v, dtype=torch.float64).to(dev).contiguous()
     th0 = torch.as_tensor(base_theta, dtype=torch.float64).to(dev).contiguous()
@@ -54,7 +68,7 @@ def screen(tp, buses, lines, gens, outages, base_v, base_theta, base_converged, 
         per_grid = int(rating.dim() == 2)
     cfg = PfConfig(N, E, tp.g.size, int(max_iter), float(tol))
     need = ctypes.c_size_t()
-    assert lib.gns_acn1_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(need)) == 0
+    assert getattr(lib, prefix + '_workspace_bytes')(ctypes.byref(cfg), topo.host.ctypes.data, Bt, K, ctypes.byref(need)) == 0
     ws = gns_mod._workspace(need.value, dev)
     sentinel = -12345.0
     f64 = [torch.full((Bt, K, n), sentinel, dtype=torch.float64, device=dev) for n in (N, N, E, E, E, E)]
@@ -63,12 +77,12 @@ def screen(tp, buses, lines, gens, outages, base_v, base_theta, base_converged, 
     conv = torch.full((Bt, K), 7, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = lib.gns_acn1_screen(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                                 gens.data_ptr(), Bt, out32.ctypes.data, out_dev.data_ptr(), K, isl.data_ptr(),
-                                 None if rating is None else rating.data_ptr(), per_grid, v0.data_ptr(), th0.data_ptr(),
-                                 conv0.data_ptr(), *(t.data_ptr() for t in f64), row_f64[0].data_ptr(), row_i32[0].data_ptr(),
-                                 row_f64[1].data_ptr(), row_i32[1].data_ptr(), row_f64[2].data_ptr(), row_i32[2].data_ptr(),
-                                 conv.data_ptr(), row_i32[3].data_ptr(), row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream)
+        rc = getattr(lib, prefix + '_screen')(
+            ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(), gens.data_ptr(), Bt,
+            list32.ctypes.data, list_dev.data_ptr(), K, isl.data_ptr(), None if rating is None else rating.data_ptr(), per_grid,
+            v0.data_ptr(), th0.data_ptr(), conv0.data_ptr(), *(t.data_ptr() for t in f64), row_f64[0].data_ptr(),
+            row_i32[0].data_ptr(), row_f64[1].data_ptr(), row_i32[1].data_ptr(), row_f64[2].data_ptr(), row_i32[2].data_ptr(),
+            conv.data_ptr(), row_i32[3].data_ptr(), row_f64[3].data_ptr(), ws.data_ptr(), ws.numel(), stream)
         assert rc == 0, rc
         torch.cuda.synchronize(dev)
     assert bool((conv <= 1).all()) and bool((row_i32[3] >= -1).all())

@@ -172,21 +172,21 @@ def test_lds_refusal_is_newton_raphsons():
 
 
 def _blob_ybus_without(w, bus, line, k):
-    """Dense Y-bus from the blob's own pattern and stamp lists with line k's stamps skipped: what gns_acn1.hip's rows read."""
+    """Dense Y-bus from the blob's own pattern and stamp lists with the stamps of line ``k`` (or of every line of the sequence ``k``)
+    skipped: what the rows of gns_acn1.hip and gns_acn2.hip read."""
+    out = {int(e) for e in np.atleast_1d(k)}
     N, E, nnzy = int(w[H['N']]), int(w[H['E']]), int(w[H['NNZY']])
     y_ptr, y_col, y_diag = _arr(w, 'Y_PTR', N + 1), _arr(w, 'Y_COL', nnzy), _arr(w, 'Y_DIAG', N)
     st_ptr, st = _arr(w, 'ST_PTR', nnzy + 1), _arr(w, 'ST', 4 * E)
     _, _, yff, ytt, yft, ytf = aref.line_admittances(line)
-    kinds = (yff, ytt, yft, ytf)
+    kinds = np.stack([yff, ytt, yft, ytf])
+    val = np.zeros(nnzy, dtype=np.complex128)
+    val[y_diag] = bus[:, 4] + 1j * bus[:, 5]
+    e, kind = st >> 2, st & 3
+    keep = ~np.isin(e, list(out))
+    np.add.at(val, np.repeat(np.arange(nnzy), np.diff(st_ptr))[keep], kinds[kind, e][keep])      # each entry's stamps, in their order
     Y = np.zeros((N, N), dtype=np.complex128)
-    for i in range(N):
-        for p in range(y_ptr[i], y_ptr[i + 1]):
-            val = complex(bus[i, 4], bus[i, 5]) if p == y_diag[i] else 0j
-            for q in range(st_ptr[p], st_ptr[p + 1]):
-                e, kind = int(st[q]) >> 2, int(st[q]) & 3
-                if e != k:
-                    val += kinds[kind][e]
-            Y[i, y_col[p]] = val
+    Y[np.repeat(np.arange(N), np.diff(y_ptr)), y_col] = val
     return Y
 
 
@@ -239,9 +239,9 @@ def test_reference_flows_balance_at_every_bus():
 # ---- the kernel's algorithm in numpy on the Newton-Raphson blob: what gns_acn1.hip does but for the order of sums
 
 def emulate_row(w, bus, line, gen, k, v0, th0, tol=1e-8, max_iter=10):
-    """Row k of one grid as the kernel computes it: the base pattern's Y-bus without line k's stamps, the Jacobian into the base
-    topology's factor slots (zeros where an entry lost its only line), the base topology's program, warm-started from (v0, th0).
-    Returns (v, theta, converged, iterations, mismatch)."""
+    """Row k of one grid as the kernel computes it (``k`` one line, or the pair of lines of a double outage): the base pattern's Y-bus
+    without the stamps of ``k``, the Jacobian into the base topology's factor slots (zeros where an entry lost its only lines), the
+    base topology's program, warm-started from (v0, th0).  Returns (v, theta, converged, iterations, mismatch)."""
     from test_powerflow_programs_host import _programs, run_gather
     N, dim, nnzlu, nnzy, slack = (int(w[H[x]]) for x in ('N', 'DIM', 'NNZLU', 'NNZY', 'SLACK'))
     y_ptr, y_col = _arr(w, 'Y_PTR', N + 1), _arr(w, 'Y_COL', nnzy)
@@ -325,8 +325,9 @@ def shifted_base(tp, v, theta, seed=4):
 
 
 def one_step_ratios(bus, line, gen, slack_bus, k, vm0, va0, v1, th1):
-    """(scipy's, the given step's) ``pt.one_step_ratio`` on the reference Jacobian and mismatch of the grid with row ``k`` of
-    ``line`` deleted, at the start (vm0, va0); the step is read off the state (v1, th1) one update later."""
+    """(scipy's, the given step's) ``pt.one_step_ratio`` on the reference Jacobian and mismatch of the grid with row ``k`` (or every
+    row of the sequence ``k``) of ``line`` deleted, at the start (vm0, va0); the step is read off the state (v1, th1) one update
+    later."""
     import scipy.sparse.linalg as spla
     rest = np.delete(line, k, axis=0)
     _, pv, pq = nr.roles(bus, gen, slack_bus)

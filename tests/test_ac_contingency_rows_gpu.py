@@ -130,8 +130,8 @@ def _flow_bar(line, vm):
 
 
 def _mismatch_and_bar(bus, line, gen, slack, k, vm, va):
-    """(||F||_inf of the reference on the grid with row k deleted, 4 deg EPS scale): the bar and the scale of
-    ``test_zero_steps_return_the_start_and_its_mismatch`` on the post-outage Y-bus."""
+    """(||F||_inf of the reference on the grid with row k, or every row of the sequence k, deleted, 4 deg EPS scale): the bar and the
+    scale of ``test_zero_steps_return_the_start_and_its_mismatch`` on the post-outage Y-bus."""
     rest = np.delete(line, k, axis=0)
     Y = nr.ybus(bus, rest)
     F = nr.mismatch_vector(bus, rest, gen, slack, vm, va, Y)
@@ -142,11 +142,13 @@ def _mismatch_and_bar(bus, line, gen, slack, k, vm, va):
 
 
 def _check_flows(got, line, vm, va, k, what):
-    """The four flows of one returned row against the reference at (vm, va); exactly 0 at line k.  Returns the worst error / bar."""
+    """The four flows of one returned row against the reference at (vm, va); exactly 0 at line k (at every line of the sequence k).
+    Returns the worst error / bar."""
+    k = np.atleast_1d(k)
     bar = _flow_bar(line, vm)
     worst = 0.0
     for key, want in zip(FLOWS, aref.branch_flows(line, vm, va, k)):
-        assert got[key][k] == 0.0, (what, key)
+        assert np.all(got[key][k] == 0.0), (what, key)
         err = float(np.max(np.abs(got[key] - want)))
         worst = max(worst, err / bar)
         assert err <= bar, (what, key, err, bar)
@@ -154,7 +156,8 @@ def _check_flows(got, line, vm, va, k, what):
 
 
 def _check_zero_step_row(s, got, i, k, tol, what):
-    """Row (grid i, line k) after zero steps: the start bit for bit, the reference mismatch, flows from the start."""
+    """Row (grid i, line k or the pair of lines k) after zero steps: the start bit for bit, the reference mismatch, flows from the
+    start."""
     vm0, va0 = s.starts[i]
     assert int(got['iterations']) == 0, what
     assert np.array_equal(got['v'], vm0) and np.array_equal(got['theta'], va0), what

@@ -21,6 +21,7 @@ from opf_graph_neural_solver_amd import gns as gns_mod
 from opf_graph_neural_solver_amd import powerflow, synth
 import ac_contingency_reference as aref
 import ac_n2_reference as n2ref
+from ac_n2_pairs import every_pair, pair_kinds
 import nr_reference as nr
 import pf_topologies as pt
 from test_ac_contingency_gpu import MAX_IT, ROWS, TOL, _check_base, _check_summaries_from_flows, _not_solved
@@ -38,10 +39,6 @@ def _screen(s, **kw):
 
 def _full(s, **kw):
     return _screen(s, flows=True, states=True, **kw)
-
-
-def every_pair(E):
-    return [tuple(p) for p in powerflow._pair_list(None, E, 'ac_contingency_screen').tolist()]
 
 
 def reference_rows(s, pairs, grids):
@@ -228,23 +225,6 @@ def test_agrees_with_the_expanded_route():
     dth = (mixed.theta.reshape(3, S, -1) - res.theta[:, cols]).abs().amax(dim=-1)[conv]
     print(f'expanded route: {int(conv.sum())} converged rows of {3 * S}, max |dv| {float(dv.max()):.2e}, max |dtheta| {float(dth.max()):.2e}')
     assert float(dv.max()) <= 1e-9 and float(dth.max()) <= 1e-9
-
-
-def pair_kinds(tp):
-    """{(j, k): kind} of every pair of a topology whose eight entries overlap: 'parallel' (the same two different buses),
-    'shared_bus', 'loop_at_bus' (a line from a bus to itself with a line at that bus), 'loop_elsewhere'."""
-    ends = [tuple(sorted(p)) for p in zip(tp.f.tolist(), tp.t.tolist())]
-    kinds = {}
-    for j, k in every_pair(tp.f.size):
-        a, b = ends[j], ends[k]
-        loops = (a[0] == a[1]) + (b[0] == b[1])
-        if loops == 1:
-            kinds[j, k] = 'loop_at_bus' if set(a) & set(b) else 'loop_elsewhere'
-        elif loops == 0 and a == b:
-            kinds[j, k] = 'parallel'
-        elif loops == 0 and set(a) & set(b):
-            kinds[j, k] = 'shared_bus'
-    return kinds
 
 
 # (rows the reference alone converges with two iterations to spare, non-islanding rows) of two grids and every pair, counted on the

@@ -2,7 +2,8 @@
 the refusals of the Python wrapper and of the C entry points (each before a launch, so no device is needed), the pair islanding
 against a graph search, and the claim the kernel rests on: each of the at most eight Y-bus entries of a pair, summed from the blob's
 own stamp lists in order with both lines skipped, is the entry of the Y-bus of the grid without the two lines, and no other entry
-changes."""
+changes; then one Newton step of the kernel's algorithm replayed in numpy on those entries, on every pair of the lists
+(``rows_pairs``) that ``test_ac_n2_rows_gpu`` runs on the device."""
 import ctypes
 import os
 
@@ -16,9 +17,10 @@ from opf_graph_neural_solver_amd._lib import PfConfig
 from helpers import ROOT
 import ac_contingency_reference as aref
 import ac_n2_reference as n2ref
+from ac_n2_pairs import pair_kinds, rows_islanding, rows_pairs
 import nr_reference as nr
 import pf_topologies as pt
-from test_ac_contingency_host import EINVAL, ESIZE, EUNSUPPORTED, _case14, toy
+from test_ac_contingency_host import EINVAL, ESIZE, EUNSUPPORTED, _case14, emulate_row, one_step_ratios, shifted_base, toy
 from test_powerflow_grad_host import H, _arr
 
 FIELDS = ('base', 'pairs', 'v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to', 'worst_loading', 'worst_line', 'v_min', 'v_min_bus',
@@ -195,7 +197,7 @@ def test_lds_refusal_is_newton_raphsons():
 
 def pair_entries(w, bus, line, j, k):
     """[(row, column, CSR position, value)] x 8: ff, tt, ft, tf of the lower line, then of the higher, each value the sum of the
-    entry's stamps in their order with the stamps of both lines skipped (gns_acn1_device.h, acn2_entry_without)."""
+    entry's stamps in their order with the stamps of both lines skipped (gns_acn1_device.h, acn_entry_without)."""
     N, E, nnzy = int(w[H['N']]), int(w[H['E']]), int(w[H['NNZY']])
     y_ptr, y_col, y_diag = _arr(w, 'Y_PTR', N + 1), _arr(w, 'Y_COL', nnzy), _arr(w, 'Y_DIAG', N)
     st_ptr, st = _arr(w, 'ST_PTR', nnzy + 1), _arr(w, 'ST', 4 * E)
@@ -293,3 +295,61 @@ def test_reference_rows_are_solutions_of_the_grid_without_both_lines():
         assert np.max(np.abs(bal.real[np.r_[pv, pq]])) <= 1e-10 and np.max(np.abs(bal.imag[pq])) <= 1e-10, (j, k)
         n_checked += 1
     assert n_checked >= 8, n_checked
+
+
+# ---- the pair lists of the row-level tests (ac_n2_pairs.rows_pairs) and one Newton step of the replay on each of them
+
+def test_the_lists_of_the_row_tests():
+    fam = pt.families()
+    for tp in (toy(), fam['random40_parallel_selfloop'], fam['lattice16x16'], pt.ring_slack_without_generator(64), pt.wheel(71)):
+        E = tp.f.size
+        pairs = rows_pairs(tp)
+        assert pairs == rows_pairs(tp) and len(set(pairs)) == len(pairs) == min(128, E * (E - 1) // 2), tp.name
+        assert all(0 <= j < k < E for j, k in pairs), tp.name
+        if E * (E - 1) // 2 > 128:
+            kinds = pair_kinds(tp)
+            n_kinds = len(set(kinds.values()))
+            assert sorted(kinds[p] for p in pairs[:n_kinds]) == sorted(set(kinds.values())), tp.name
+            edge = [e for e in (0, 62, 63, 64, 65, E - 1) if e < E]
+            assert {(j, k) for j in edge for k in edge if j < k} <= set(pairs), tp.name
+        isl = rows_islanding(tp, pairs)
+        assert 0 < int((~isl).sum()), tp.name
+    assert len(rows_pairs(toy())) == 21
+
+
+@pytest.mark.parametrize('regime', pt.REGIMES)
+def test_one_step_of_the_replay_on_every_listed_pair(regime):
+    """``test_ac_contingency_host.test_one_step_of_the_replay_on_every_pair`` for double outages, from a start with
+    base_theta[slack] = 0.3, on EVERY non-islanding pair of ``rows_pairs`` (no convergence needed): after zero steps the replay's
+    state is the reference start bit for bit; after one its update solves the reference Jacobian of the grid with both rows deleted
+    to ``pt.STEP_TOL``, scipy's own step asserted first as the guard.  Pins "the base blob serves every pair" at 100 %.
+    Non-islanding rows of two grids, in either regime: toy 30 (of 42), random40 188, random24_stacked_gens 196, ring63 128 (of 256
+    each)."""
+    fam = pt.families()
+    topos = [toy(), fam['random40_parallel_selfloop'], fam['random24_stacked_gens'], pt.ring_slack_without_generator(63)]
+    for tp in topos:
+        buses, lines, gens, v, theta = pt.grids(tp, regime, 2, seed=11)
+        base_v, base_theta = shifted_base(tp, v, theta)
+        w = powerflow.analyse_topology(tp.n, tp.f, tp.t, tp.g, tp.slack).host
+        pairs = rows_pairs(tp)
+        isl = rows_islanding(tp, pairs)
+        n_cmp, worst = 0, 0.0
+        for i in range(2):
+            b, l, g = (x[i].double().numpy() for x in (buses, lines, gens))
+            assert base_theta[i, tp.slack - 1] == 0.3
+            vm0, va0 = nr.start(b, g, tp.slack, base_v[i], base_theta[i])
+            for (j, k), island in zip(pairs, isl):
+                if island:
+                    continue
+                z = emulate_row(w, b, l, g, [j, k], base_v[i], base_theta[i], tol=0.0, max_iter=0)
+                assert np.array_equal(z[0], vm0) and np.array_equal(z[1], va0) and z[3] == 0, (tp.name, i, j, k)
+                v1, th1, conv, it, _ = emulate_row(w, b, l, g, [j, k], base_v[i], base_theta[i], tol=0.0, max_iter=1)
+                assert it == 1 and not conv, (tp.name, i, j, k)
+                r_scipy, r_replay = one_step_ratios(b, l, g, tp.slack, [j, k], vm0, va0, v1, th1)
+                assert r_scipy <= pt.STEP_TOL, (tp.name, regime, i, j, k, r_scipy)
+                assert r_replay <= pt.STEP_TOL, (tp.name, regime, i, j, k, r_replay)
+                worst = max(worst, r_replay)
+                n_cmp += 1
+        n_rows = 2 * int((~isl).sum())
+        print(f'{tp.name} ({regime}): {n_cmp} of {n_rows} non-islanding rows compared, worst one-step ratio {worst:.1e}')
+        assert n_cmp == n_rows > 0

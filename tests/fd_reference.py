@@ -31,6 +31,26 @@ def _scaled_mismatch(Y, V, S, pvpq, pq):
     return mis[pvpq].real, mis[pq].imag
 
 
+def setting(buses, lines, generators, slack_bus):
+    """(pvpq, pq, Y, S) of one grid: the unknowns' buses in ``roles``' order, the Y-bus and the specified injections."""
+    slack, pv, pq = ref.roles(buses, generators, slack_bus)
+    return np.r_[pv, pq], pq, ref.ybus(buses, lines), ref.specified(buses, generators)
+
+
+def scaled_norm(Y, S, pvpq, pq, vm, va):
+    """(P, Q, max(||P||_inf, ||Q||_inf)) of the scaled mismatch at (vm, va): the norm every test of the iteration reads."""
+    P, Q = _scaled_mismatch(Y, vm * np.exp(1j * va), S, pvpq, pq)
+    return P, Q, float(max(np.max(np.abs(P), initial=0.0), np.max(np.abs(Q), initial=0.0)))
+
+
+def norm_rounding_bound(Y, S, vm):
+    """What float64 rounding may move the scaled norm by: the bound of the Newton-Raphson zero-steps test on ||F||_inf, 4 deg eps
+    max_i(|V_i| (|Y| |V|)_i + |S_i|) with deg the longest Y-bus row + 2, divided by the smallest |V| the mismatch is scaled by."""
+    scale = np.max(np.abs(vm) * (abs(Y) @ np.abs(vm)) + np.abs(S))
+    deg = int(np.max(np.diff(Y.indptr))) + 2
+    return 4 * deg * np.finfo(np.float64).eps * scale / np.min(np.abs(vm))
+
+
 def fast_decoupled(buses, lines, generators, slack_bus, variant, tol=1e-8, max_iter=30, v0=None, theta0=None):
     """Returns (v, theta, converged, iterations, mismatch) of one grid, with the per-grid failure rules of
     include/gns_powerflow.h ("Fast-decoupled"): mismatch is max(||P||_inf, ||Q||_inf) of the scaled mismatch at the last test."""

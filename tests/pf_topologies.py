@@ -1,6 +1,7 @@
 """Test-side topologies and grid values for the power-flow programs (``powerflow.analyse_topology``, ``gns_pf_solve`` and
-``gns_pf_adjoint``): generated families at the shapes where the analysis and the kernels could go wrong, finders of the largest
-topologies whose LDS image fits the 160 KiB limit, grids on a topology in two value regimes, and the one-step residual bound.
+``gns_pf_adjoint``; through the ``fd_`` functions ``powerflow.analyse_fd_topology`` and ``gns_fd_solve``): generated families at the
+shapes where the analysis and the kernels could go wrong, finders of the largest topologies whose LDS image fits the 160 KiB limit,
+grids on a topology in two value regimes, and the one-step residual bound.
 
 A topology is ``Topo(name, n, f, t, g, slack)``: 1-based int64 numpy ids of the lines' ends and the generators' buses."""
 import functools
@@ -114,15 +115,17 @@ def wheel(n=71):
     return Topo(f'wheel{n}', n, *_ids(f, t, [2, n // 3, 2 * n // 3]), 2)
 
 
-def _info(tp):
-    return powerflow.analyse_topology(tp.n, tp.f, tp.t, tp.g, tp.slack).info
+def _info(tp, analyse=powerflow.analyse_topology):
+    """The info dict of ``analyse`` (``powerflow.analyse_topology`` or ``powerflow.analyse_fd_topology``) on tp."""
+    return analyse(tp.n, tp.f, tp.t, tp.g, tp.slack).info
 
 
-def _largest(make, lo, hi):
-    """The largest size s in [lo, hi) with make(s)'s LDS image within the limit (monotone in s); an analysis refusal counts as over."""
+def _largest(make, lo, hi, analyse=powerflow.analyse_topology):
+    """The largest size s in [lo, hi) with make(s)'s LDS image (of ``analyse``) within the limit (monotone in s); an analysis refusal
+    counts as over."""
     def fits(s):
         try:
-            return _info(make(s))['lds_bytes'] <= LDS_LIMIT
+            return _info(make(s), analyse)['lds_bytes'] <= LDS_LIMIT
         except gns_mod.GNSError:
             return False
     assert fits(lo) and not fits(hi)
@@ -132,20 +135,32 @@ def _largest(make, lo, hi):
     return lo
 
 
-@functools.lru_cache(maxsize=None)
-def boundary():
-    """The largest path and complete graph whose LDS image fits, and the smallest path over the limit (searched, not assumed)."""
-    n_path = _largest(path, 2, 4096)
-    n_k = _largest(complete, 2, 256)
+def _boundary(analyse):
+    n_path = _largest(path, 2, 4096, analyse)
+    n_k = _largest(complete, 2, 256, analyse)
     return {'path_fit': path(n_path), 'path_over': path(n_path + 1), 'complete_fit': complete(n_k)}
 
 
-def _near_multiples(makes, lo, hi, key):
-    """The first topologies make(s), s in [lo, hi), of any of ``makes`` whose info[key] is one below and one above a multiple of 64."""
+@functools.lru_cache(maxsize=None)
+def boundary():
+    """The largest path and complete graph whose LDS image fits, and the smallest path over the limit (searched, not assumed)."""
+    return _boundary(powerflow.analyse_topology)
+
+
+@functools.lru_cache(maxsize=None)
+def fd_boundary():
+    """``boundary()`` for the fast-decoupled LDS image, 8 * (nnz_lu_p + dim_p + nnz_lu_pp + dim_pp + 6 N) bytes
+    (``powerflow.analyse_fd_topology``)."""
+    return _boundary(powerflow.analyse_fd_topology)
+
+
+def _near_multiples(makes, lo, hi, key, analyse=powerflow.analyse_topology):
+    """The first topologies make(s), s in [lo, hi), of any of ``makes`` whose info[key] (of ``analyse``) is one below and one above a
+    multiple of 64."""
     out = {}
     for make in makes:
         for s in range(lo, hi):
-            r = _info(make(s))[key] % 64
+            r = _info(make(s), analyse)[key] % 64
             if r in (63, 1) and r not in out:
                 out[r] = make(s)
     assert sorted(out) == [1, 63], (key, out)
@@ -167,12 +182,32 @@ def families():
     return fam
 
 
-def coverage(topos):
-    """For N, dim and nnz_lu: which residues mod 64 among {63, 0, 1} the topologies reach."""
+def coverage(topos, keys=('n_bus', 'dim', 'nnz_lu'), analyse=powerflow.analyse_topology):
+    """For N, dim and nnz_lu (or ``keys`` of ``analyse``'s info): which residues mod 64 among {63, 0, 1} the topologies reach."""
     out = {}
-    for key in ('n_bus', 'dim', 'nnz_lu'):
-        out[key] = sorted({_info(tp)[key] % 64 for tp in topos} & {63, 0, 1})
+    for key in keys:
+        out[key] = sorted({_info(tp, analyse)[key] % 64 for tp in topos} & {63, 0, 1})
     return out
+
+
+FD_KEYS = ('n_bus', 'dim_p', 'dim_pp', 'nnz_lu_p', 'nnz_lu_pp')
+
+
+@functools.lru_cache(maxsize=None)
+def fd_families():
+    """name -> Topo: ``families()`` and paths with PV buses that bring nnz(L+U) of B' and of B'' (``analyse_fd_topology``) to one
+    below and one above a multiple of 64, which no family reaches on a factor of more than one slot."""
+    # a path's B' has 3 N - 5 nonzeros in L + U whatever its PV buses; B'' loses the PV buses' rows and the chain breaks there
+    makes = [lambda s: path(s, pv=(2,)), lambda s: path(s, pv=(2, 3, 4))]
+    fam = dict(families())
+    for key in ('nnz_lu_p', 'nnz_lu_pp'):
+        fam.update({tp.name: tp for tp in _near_multiples(makes, 20, 80, key, powerflow.analyse_fd_topology)})
+    return fam
+
+
+def fd_coverage(topos):
+    """``coverage`` of the fast-decoupled analysis: N, both dimensions and both nnz(L+U)."""
+    return coverage(topos, FD_KEYS, powerflow.analyse_fd_topology)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ values

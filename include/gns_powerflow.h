@@ -708,7 +708,8 @@ int gns_acn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  *   blob's Y-bus pattern (nothing is read out of bounds for it).  Other rows are unaffected.
  *   Every (grid, pair) row is bit-identical alone, in any batch, for any pair list or order that holds the pair, in either order of
  *   its two lines, and from run to run: no atomics, the reductions by a total order.
- *   Not here: gradients, batches that mix topologies (one blob per call), line plus generator outages, generator reactive limits.
+ *   Gradients: gns_acn2_adjoint, below.  Not here: batches that mix topologies (one blob per call), line plus generator outages,
+ *   generator reactive limits.
  *
  * Inputs: gns_acn1_screen's, but for the list: pairs as 0-based line indices [n_pair,2] int32, on the host (checked before the
  * launch) and on the device (read by the kernel); islanding [n_pair] uint8 on the device.
@@ -737,6 +738,63 @@ int gns_acn2_screen(const gns_pf_config* cfg, const void* topo_host, const void*
                     double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
                     int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Gradients of the AC N-2 screen.  gns_acn2_adjoint is gns_acn1_adjoint ("Gradients of the AC screen" above) with two lines out per
+ * row.  It takes the inputs of a gns_acn2_screen call (the same pair list, islanding mask and rating), its outputs v, theta
+ * [Bt,n_pair,N], converged, worst_line, v_min_bus, v_max_bus [Bt,n_pair] and the base_converged [Bt] it was given, and the incoming
+ * gradients of a loss of its nine fp64 outputs: grad_v, grad_theta [Bt,n_pair,N], grad_p_from, grad_q_from, grad_p_to, grad_q_to
+ * [Bt,n_pair,E], grad_worst_loading, grad_v_min, grad_v_max [Bt,n_pair] (each may be NULL: zero).  It writes dl/d(input) into
+ * grad_buses [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32, each of which may be NULL (not computed; with all three
+ * NULL nothing is launched).  Every element of each non-NULL output is written (overwritten, not accumulated).  The state is the
+ * forward's: Newton-Raphson is not run again, and the warm start is not differentiated.
+ *
+ * Method, per solved row (grid, p) with j = min(pairs[p]), k = max(pairs[p]): gns_acn1_adjoint's, word for word, on the grid without
+ * lines j and k: F_jk(x, p) = 0, J_jk = dF_jk/dx on the row's Y-bus (gns_acn2_screen's: each of the at most eight entries the lines
+ * touch recomputed from its stamps without both lines), factored on the base analysis, one transposed solve.  What differs for two
+ * lines: the flows of BOTH lines are the constant 0, so the entries of the four flow gradients at lines j and k are ignored, a
+ * worst_line that is j or k (a forward's never is) gets nothing, and the row adds exactly 0 to the own columns of lines j and k.
+ * Two parallel lines that are both out leave numeric zeros in the pattern; a line from a bus to itself and two lines that share a
+ * bus are handled as in the forward.  The kernel orders the two lines itself: (k, j) and (j, k) give the same row contribution bit
+ * for bit.
+ *
+ * Contract, failure rules and arithmetic: gns_acn1_adjoint's, with "pair" for "outage": gns_pf_adjoint's columns, every other column
+ *   0; a line whose id columns are not buses of the grid gets a NaN row; rating is a constant.  A row whose incoming gradients are
+ *   all exactly zero or NULL is skipped, never multiplied by zero.  A row with converged == 0 (an islanding pair, a stopped or
+ *   unconverged iteration, NaN / -1) and a non-zero incoming gradient, a zero or non-finite pivot, or a non-finite lambda: all three
+ *   gradient rows of that grid are NaN.  A grid with base_converged == 0 gets NaN rows when an incoming gradient of it is non-zero,
+ *   zero rows otherwise.  Other grids are unaffected.  fp64 throughout, rounded once to fp32.  No atomics, every sum in a fixed
+ *   order: a grid's gradient is bit-identical alone, in any batch, from run to run and with the two lines of any pair swapped, for
+ *   the same pair list.  The order and the chunking of the list set the order of the sums over rows, so another order of the same
+ *   pairs may change the last bits.
+ *
+ * Kernels (gns_acn2.hip): the screen's pre-kernel writes the base Y-bus per grid; then one wave per (grid, chunk of C consecutive
+ * pairs of the list) with gns_pf_solve's LDS image, so every topology the screen accepts the adjoint accepts.  After the row's
+ * prologue (its Y-bus view) the wave runs the routine gns_acn1_adjoint's kernel runs (acn_adjoint_row, gns_acn_adjoint_device.h), and
+ * gns_acn1_adjoint's second kernel sums the chunks' partials (the same layout) in order.  C = max(1, ceil(n_pair / 64)): from the
+ * list's length alone, never from Bt, and without gns_acn1_adjoint's cap of 8 rows per wave, so that a grid has at most 64 partials
+ * however long the list (pair lists are long: every pair of case118 is 17 205 rows).  Workspace
+ * (gns_acn2_adjoint_workspace_bytes): the base Y-bus (gns_acn2_workspace_bytes' figure) plus Bt * ceil(n_pair / C) partials of
+ * 4 N + 5 E + Gn + 1 doubles, each part rounded up to 256 bytes.
+ *
+ * Errors, in order: GNS_EINVAL for a NULL cfg, blob, input, pair list, islanding mask, v, theta, converged, worst_line, v_min_bus,
+ * v_max_bus or base_converged, a negative max_iter or tol, a blob that is not a Newton-Raphson blob or whose N, E, Gn are not cfg's,
+ * n_pair <= 0, a line outside 0 .. E-1, a pair of twice the same line, rating_per_grid outside {0, 1}, or Bt * ceil(n_pair / C)
+ * above 2^31 - 1; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES (from the workspace query too); then, when an
+ * output is asked for, GNS_EINVAL for a NULL workspace and GNS_ESIZE for a short one.  Every refusal comes before any launch;
+ * nothing is allocated and the host is not synchronised.
+ * Not here: batches that mix topologies, line plus generator outages, generator reactive limits, second derivatives. */
+int gns_acn2_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_pair, size_t* bytes);
+int gns_acn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const int32_t* pairs_host, const int32_t* pairs_dev, int32_t n_pair, const uint8_t* islanding,
+                     const double* rating, int32_t rating_per_grid,
+                     const double* v, const double* theta, const uint8_t* converged, const int32_t* worst_line,
+                     const int32_t* v_min_bus, const int32_t* v_max_bus, const uint8_t* base_converged,
+                     const double* grad_v, const double* grad_theta, const double* grad_p_from, const double* grad_q_from,
+                     const double* grad_p_to, const double* grad_q_to, const double* grad_worst_loading,
+                     const double* grad_v_min, const double* grad_v_max,
+                     float* grad_buses, float* grad_lines, float* grad_generators,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,440 @@
+// What the adjoints of the two AC contingency screens share, gns_acn1_adjoint (gns_acn1.hip) and gns_acn2_adjoint (gns_acn2.hip).
+// Device: the incoming gradients of a call, a row's effective flow cotangents and their gather to the buses, the layout and the
+// status of a (grid, chunk) partial, the routine both adjoint kernels run per solved row after their prologue (acn_adjoint_row: the
+// implicit function theorem on the grid without the row's line or lines, templated on the Y-bus view as acn_solve_row is) and the
+// kernel that sums a grid's partials.  Host: the workspace query and the checks and launches of an adjoint call around its own
+// row kernel.  Both adjoints run this code: a row of the double-outage adjoint is computed by the single-outage adjoint's routine,
+// not by a copy of it.
+#pragma once
+#include "gns_acn1_device.h"
+
+namespace {
+
+// The status of a chunk's partial: gns_dcn1.hip's (valid sums; the grid's gradient is NaN; the grid has no base solution and the
+// chunk's incoming gradients are zero)
+constexpr double ACN1_PART_OK = 0.0, ACN1_PART_NAN = 1.0, ACN1_PART_UNSOLVED_ZERO = 2.0;
+
+// The incoming gradients of a call (each may be NULL: zero), in the layout of Acn1Out's rows
+struct Acn1Grad {
+  const double* v;        // [Bt,K,N]
+  const double* theta;
+  const double* p_from;   // [Bt,K,E]
+  const double* q_from;
+  const double* p_to;
+  const double* q_to;
+  const double* worst;    // [Bt,K]
+  const double* v_min;
+  const double* v_max;
+};
+
+// Whether any incoming gradient of row `row` is not exactly zero (a NaN counts); the same answer in every lane
+__device__ __forceinline__ bool acn1_row_nonzero(const Acn1Grad& gr, const size_t row, const int N, const int E) {
+  bool nz = false;
+  if (threadIdx.x == 0)
+    nz = (gr.worst && gr.worst[row] != 0.0) || (gr.v_min && gr.v_min[row] != 0.0) || (gr.v_max && gr.v_max[row] != 0.0);
+  for (int i = threadIdx.x; i < N; i += PF_THREADS) {
+    if (gr.v) nz |= gr.v[row * N + i] != 0.0;
+    if (gr.theta) nz |= gr.theta[row * N + i] != 0.0;
+  }
+  for (int l = threadIdx.x; l < E; l += PF_THREADS) {
+    if (gr.p_from) nz |= gr.p_from[row * E + l] != 0.0;
+    if (gr.q_from) nz |= gr.q_from[row * E + l] != 0.0;
+    if (gr.p_to) nz |= gr.p_to[row * E + l] != 0.0;
+    if (gr.q_to) nz |= gr.q_to[row * E + l] != 0.0;
+  }
+  return __ballot(nz) != 0;
+}
+
+// The effective flow cotangents of one row: W_f = grad_p_from + j grad_q_from and W_t likewise, with what grad_worst_loading adds
+// at line w's from end (wf) or to end (wt); zero at the outaged line(s) of the row's Y-bus view.  The same in every lane.
+template <class YB>   // Acn1Ybus or Acn2Ybus
+struct Acn1Cot {
+  const double* gpf;   // the row's [E] incoming gradients, NULL: zero
+  const double* gqf;
+  const double* gpt;
+  const double* gqt;
+  const YB& Y;
+  int w;
+  double2 wf, wt;
+  __device__ __forceinline__ void at(const int l, double2& Wf, double2& Wt) const {
+    Wf = make_double2(0.0, 0.0); Wt = Wf;
+    if (Y.out(l)) return;
+    if (gpf) Wf.x = gpf[l];
+    if (gqf) Wf.y = gqf[l];
+    if (gpt) Wt.x = gpt[l];
+    if (gqt) Wt.y = gqt[l];
+    if (l == w) { Wf.x += wf.x; Wf.y += wf.y; Wt.x += wt.x; Wt.y += wt.y; }
+  }
+};
+
+// The four terms of the flows of line l between buses a and b at V: A = V_a conj(Y_ft V_b), D = |V_a|^2 conj(Y_ff) (S_f = D + A),
+// B = V_b conj(Y_tf V_a), C = |V_b|^2 conj(Y_tt) (S_t = C + B), on the line's own stamps
+__device__ __forceinline__ void acn1_flow_terms(const float* line, const int l, const int a, const int b, const double* Vm,
+                                                const double* Vr, const double* Vi, double2& A, double2& D, double2& B, double2& C) {
+  const double2 yff = acn1_stamp(line, l, 0), ytt = acn1_stamp(line, l, 1), yft = acn1_stamp(line, l, 2), ytf = acn1_stamp(line, l, 3);
+  const double far = Vr[a], fai = Vi[a], tor = Vr[b], toi = Vi[b];
+  const double xr = yft.x * tor - yft.y * toi, xi = yft.x * toi + yft.y * tor;   // Y_ft V_t
+  A = make_double2(far * xr + fai * xi, fai * xr - far * xi);
+  const double zr = ytf.x * far - ytf.y * fai, zi = ytf.x * fai + ytf.y * far;   // Y_tf V_f
+  B = make_double2(tor * zr + toi * zi, toi * zr - tor * zi);
+  const double mf = Vm[a] * Vm[a], mt = Vm[b] * Vm[b];
+  D = make_double2(mf * yff.x, 0.0 - mf * yff.y);
+  C = make_double2(mt * ytt.x, 0.0 - mt * ytt.y);
+}
+
+// What the flow cotangents add to dl/dtheta_i and dl/d|V_i|: a gather.  Bus i walks the stamps of its diagonal entry, where kind 0
+// names every line it is the from end of and kind 1 every line it is the to end of (a line from a bus to itself: once per end).
+//   dS_f/dtheta_f = jA = -dS_f/dtheta_t,  dS_t/dtheta_t = jB = -dS_t/dtheta_f,
+//   |V_f| dS_f/d|V_f| = 2D + A,  |V_t| dS_f/d|V_t| = A,  |V_t| dS_t/d|V_t| = 2C + B,  |V_f| dS_t/d|V_f| = B;  dl = Re(conj(W) dS)
+template <class YB>
+__device__ __forceinline__ void acn1_flow_cot_bus(const int i, const int N, const int32_t* y_diag, const int32_t* st_ptr,
+                                                  const int32_t* st, const float* line, const Acn1Cot<YB>& cot, const double* Vm,
+                                                  const double* Vr, const double* Vi, double& dth, double& dvm) {
+  const int p = y_diag[i];
+  for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
+    const int e = st[q] >> 2, kind = st[q] & 3;
+    if (kind > 1) continue;
+    double2 Wf, Wt;
+    cot.at(e, Wf, Wt);
+    if (Wf.x == 0.0 && Wf.y == 0.0 && Wt.x == 0.0 && Wt.y == 0.0) continue;
+    int a, b;
+    if (!acn1_line_ends(line, e, N, a, b)) continue;       // NaN flows: the line's own gradient row is NaN
+    double2 A, D, B, C;
+    acn1_flow_terms(line, e, a, b, Vm, Vr, Vi, A, D, B, C);
+    const double tf = Wf.y * A.x - Wf.x * A.y, tt = Wt.y * B.x - Wt.x * B.y;   // Re(conj(W_f) jA), Re(conj(W_t) jB)
+    if (kind == 0) {
+      dth += tf - tt;
+      dvm += ((Wf.x * (2.0 * D.x + A.x) + Wf.y * (2.0 * D.y + A.y)) + (Wt.x * B.x + Wt.y * B.y)) / Vm[a];
+    } else {
+      dth += tt - tf;
+      dvm += ((Wt.x * (2.0 * C.x + B.x) + Wt.y * (2.0 * C.y + B.y)) + (Wf.x * A.x + Wf.y * A.y)) / Vm[b];
+    }
+  }
+}
+
+// Doubles of one (grid, chunk) partial: per bus the sums of lambda_P, lambda_Q, |V|^2 lambda_P, |V|^2 lambda_Q; per line its five
+// columns; per generator slot (the blob's by-bus order) dl/dvg; the chunk's status
+__device__ __host__ inline int64_t acn1_adjoint_partial(const int32_t* h) {
+  return 4 * (int64_t)h[PH_N] + 5 * (int64_t)h[PH_E] + (int64_t)h[PH_GN] + 1;
+}
+
+// The wave's exit with the chunk's status alone (its sums are not read then)
+__device__ __forceinline__ void acn1_partial_status(double* part, const int np, const double status) {
+  if (threadIdx.x == 0) part[np - 1] = status;
+}
+
+// A solved row of either adjoint after its kernel's prologue (the row decode, the skip of a row nobody asks for, the decision that
+// the row has a solution, the Y-bus view Y of the grid without the row's line or lines): the forward's state of row `row` (read,
+// not solved again), I = Y V, the Jacobian on Y factored on Newton-Raphson's LDS image, the row's cotangents, one transposed
+// solve, and the bus, generator and line sums added into the chunk's partial `part`, every lane into the addresses it alone owns.
+// False when the row gives the grid a NaN gradient (a zero or non-finite pivot, a non-finite lambda); the same in every lane.
+// Flows and flow cotangents are skipped at every line Y.out names, and the row adds exactly 0 to those lines' own columns.
+template <class YB>   // Acn1Ybus or Acn2Ybus
+__device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo, const float* line, const size_t row, const YB& Y,
+                                                const double* rt, const Acn1Grad& gr, const double* __restrict__ v_in,
+                                                const double* __restrict__ th_in, const int32_t* __restrict__ wl_in,
+                                                const int32_t* __restrict__ lo_in, const int32_t* __restrict__ hi_in, double* part) {
+  extern __shared__ double lds[];
+  const int lane = threadIdx.x;
+  const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN], slack = topo[PH_SLACK], dim = topo[PH_DIM];
+  const int nnzLU = topo[PH_NNZLU], t_nsteps = topo[PH_T_NSTEPS];
+  const int32_t* role = topo + topo[PH_ROLE];
+  const int32_t* th_idx = topo + topo[PH_TH_IDX];
+  const int32_t* vm_idx = topo + topo[PH_VM_IDX];
+  const int32_t* gen_ptr = topo + topo[PH_GEN_PTR];
+  const int32_t* y_ptr = topo + topo[PH_Y_PTR];
+  const int32_t* y_col = topo + topo[PH_Y_COL];
+  const int32_t* y_diag = topo + topo[PH_Y_DIAG];
+  const int32_t* st_ptr = topo + topo[PH_ST_PTR];
+  const int32_t* st = topo + topo[PH_ST];
+  const int32_t* jslot = topo + topo[PH_JSLOT];
+  const int32_t* pivot = topo + topo[PH_PIVOT];
+  const int32_t* step_ptr = topo + topo[PH_STEP_PTR];
+  const int2* ops = reinterpret_cast<const int2*>(topo + topo[PH_OPS]);
+  const int32_t* t_step_ptr = topo + topo[PH_T_STEP_PTR];
+  const int2* t_ops = reinterpret_cast<const int2*>(topo + topo[PH_T_OPS]);
+  double* part_bus = part;                 // [N][4]
+  double* part_line = part + 4 * N;        // [E][5]
+  double* part_gen = part_line + 5 * E;    // [Gn]
+
+  double* F = lds;                         // Newton-Raphson's image: [nnzLU] factor, then [dim] right-hand side / lambda
+  double* rhs = lds + nnzLU;
+  double* Vm = rhs + dim;
+  double* dV = Vm + N;                     // the solve's Va: the total direct dl/d|V_i| of the row (vg reads it at PV / slack buses)
+  double* Vr = dV + N;
+  double* Vi = Vr + N;
+  double* Ir = Vi + N;
+  double* Ii = Ir + N;
+  double* lamP = Ii + N;                   // the solve's Psp / Qsp: lambda of each bus's P and Q mismatch (0 where there is none)
+  double* lamQ = lamP + N;
+
+  // the forward's state of the row (read, not solved again) and I = Y V there
+  __syncthreads();                         // the row before has read its last LDS value
+  for (int i = lane; i < N; i += PF_THREADS) {
+    const double vm = v_in[row * N + i], va = th_in[row * N + i];
+    Vm[i] = vm;
+    Vr[i] = vm * cos(va); Vi[i] = vm * sin(va);
+  }
+  for (int s = lane; s < nnzLU + dim; s += PF_THREADS) F[s] = 0.0;
+  __syncthreads();
+  for (int i = lane; i < N; i += PF_THREADS) {
+    double ir = 0.0, ii = 0.0;
+    for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
+      const int c = y_col[p];
+      const double2 y = Y.at(p);
+      ir += y.x * Vr[c] - y.y * Vi[c];
+      ii += y.x * Vi[c] + y.y * Vr[c];
+    }
+    Ir[i] = ir; Ii[i] = ii;
+  }
+  __syncthreads();
+
+  // the Jacobian at that state, factored by the leading steps of the solve program (its solve operations there see a zero
+  // right-hand side)
+  for (int i = lane; i < N; i += PF_THREADS)
+    if (i != slack) acn1_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
+  __syncthreads();
+  pf_run_program(t_step_ptr[t_nsteps + 1], step_ptr, ops, F, lane);
+  if (__ballot(pf_bad_pivot(dim, pivot, F, lane))) return false;
+
+  // the row's effective cotangents.  grad_worst_loading goes to the end of worst_line that attains the maximum (the from end on
+  // equality) as S / |S| / rating, nothing at |S| = 0; grad_v_min and grad_v_max go to the buses the forward reported.
+  Acn1Cot<YB> cot = {gr.p_from ? gr.p_from + row * E : nullptr, gr.q_from ? gr.q_from + row * E : nullptr,
+                     gr.p_to ? gr.p_to + row * E : nullptr, gr.q_to ? gr.q_to + row * E : nullptr, Y, -1,
+                     make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
+  const double gw = gr.worst ? gr.worst[row] : 0.0;
+  const int w = wl_in[row];
+  int wa = 0, wb = 0;
+  if (gw != 0.0 && w >= 0 && w < E && !Y.out(w) && acn1_line_ends(line, w, N, wa, wb)) {
+    double2 A, D, B, Cc;
+    acn1_flow_terms(line, w, wa, wb, Vm, Vr, Vi, A, D, B, Cc);
+    const double pf = D.x + A.x, qf = D.y + A.y, pt = Cc.x + B.x, qt = Cc.y + B.y;
+    const double sf = sqrt(pf * pf + qf * qf), s_t = sqrt(pt * pt + qt * qt);
+    const double r = rt ? rt[w] : 1.0;
+    if (sf >= s_t) { if (sf > 0.0) cot.wf = make_double2(gw * (pf / sf) / r, gw * (qf / sf) / r); }
+    else cot.wt = make_double2(gw * (pt / s_t) / r, gw * (qt / s_t) / r);
+    cot.w = w;
+  }
+  const double g_lo = gr.v_min ? gr.v_min[row] : 0.0, g_hi = gr.v_max ? gr.v_max[row] : 0.0;
+  const int i_lo = lo_in[row], i_hi = hi_in[row];
+
+  // J^T lambda = dl/dx: the theta and |V| cotangents at the unknowns plus the flows' derivatives, a bus per lane (the slack's
+  // theta is the constant 0)
+  for (int i = lane; i < N; i += PF_THREADS) {
+    double dth = gr.theta ? gr.theta[row * N + i] : 0.0;
+    double dvm = gr.v ? gr.v[row * N + i] : 0.0;
+    if (i == i_lo) dvm += g_lo;
+    if (i == i_hi) dvm += g_hi;
+    acn1_flow_cot_bus(i, N, y_diag, st_ptr, st, line, cot, Vm, Vr, Vi, dth, dvm);
+    dV[i] = dvm;
+    if (th_idx[i] >= 0) rhs[th_idx[i]] = dth;
+    if (vm_idx[i] >= 0) rhs[vm_idx[i]] = dvm;
+  }
+  __syncthreads();
+  pf_run_program(t_nsteps, t_step_ptr, t_ops, F, lane);
+  bool bad = false;
+  for (int i = lane; i < N; i += PF_THREADS) {
+    const double lp = th_idx[i] >= 0 ? rhs[th_idx[i]] : 0.0, lq = vm_idx[i] >= 0 ? rhs[vm_idx[i]] : 0.0;
+    lamP[i] = lp; lamQ[i] = lq;
+    bad |= !pf_finite(lp) || !pf_finite(lq);
+  }
+  if (__ballot(bad)) return false;
+  __syncthreads();
+
+  // dl/dp = direct - lambda^T dF/dp, gns_pf_adjoint's algebra (pf_adjoint_grid) on the row's Y-bus, added to the chunk's sums
+  for (int i = lane; i < N; i += PF_THREADS) {
+    const double m2 = Vm[i] * Vm[i], lp = lamP[i], lq = lamQ[i];
+    double* pb = part_bus + 4 * i;
+    pb[0] += lp; pb[1] += lq; pb[2] += m2 * lp; pb[3] += m2 * lq;
+  }
+  for (int q = lane; q < Gn; q += PF_THREADS) {      // a lane per generator slot, in the blob's by-bus order
+    int b = 0, hi = N;                               // the bus of slot q: gen_ptr[b] <= q < gen_ptr[b + 1]
+    while (hi - b > 1) {
+      const int mid = (b + hi) >> 1;
+      if (gen_ptr[mid] <= q) b = mid;
+      else hi = mid;
+    }
+    if (q != gen_ptr[b] || role[b] == 0) continue;   // the first generator of a PV / slack bus sets |V_b|
+    const double uc = Vr[b] / Vm[b], us = Vi[b] / Vm[b];   // e^{j theta_b}
+    double acc = 0.0;
+    for (int p = y_ptr[b]; p < y_ptr[b + 1]; ++p) {
+      const int c = y_col[p];
+      const int r = acn1_find_entry(y_ptr, y_col, c, b);   // Y_cb (the pattern is structurally symmetric)
+      if (r < 0) continue;
+      const double2 y = Y.at(r);
+      const double wr = y.x * uc - y.y * us, wi = y.x * us + y.y * uc;   // Y_cb e^{j theta_b}
+      double dr = Vr[c] * wr + Vi[c] * wi, di = Vi[c] * wr - Vr[c] * wi;  // dS_c / d|V_b| = V_c conj(Y_cb e^{j theta_b}) ...
+      if (c == b) { dr += uc * Ir[b] + us * Ii[b]; di += us * Ir[b] - uc * Ii[b]; }   // ... + e^{j theta_b} conj(I_b) at c = b
+      acc += lamP[c] * dr + lamQ[c] * di;
+    }
+    part_gen[q] += dV[b] - acc;
+  }
+  for (int e = lane; e < E; e += PF_THREADS) {      // a line per lane, over its four stamps; the row adds nothing to a line that is out
+    int a, b2;
+    if (Y.out(e) || !acn1_line_ends(line, e, N, a, b2)) continue;
+    double2 Wf, Wt;
+    cot.at(e, Wf, Wt);
+    // Lambda_f - W_f and Lambda_t - W_t: the flow term is +Re(conj(W) S) on the line's own stamps, the mismatch term -Re(conj(Lambda) S)
+    const double lpf = lamP[a] - Wf.x, lqf = lamQ[a] - Wf.y, lpt = lamP[b2] - Wt.x, lqt = lamQ[b2] - Wt.y;
+    const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
+    const double den = r * r + x * x;
+    const double ysr = r / den, ysi = -x / den, t2 = tau * tau;
+    const double cs = cos(sh), sn = sin(sh);
+    const double mf = Vm[a] * Vm[a], mt = Vm[b2] * Vm[b2];
+    const double gffr = 0.0 - mf * lpf, gffi = mf * lqf;
+    const double gttr = 0.0 - mt * lpt, gtti = mt * lqt;
+    const double pr = Vr[a] * Vr[b2] + Vi[a] * Vi[b2], pi = Vi[a] * Vr[b2] - Vr[a] * Vi[b2];   // V_f conj(V_t)
+    const double gftr = 0.0 - (pr * lpf + pi * lqf), gfti = 0.0 - (pi * lpf - pr * lqf);
+    const double gtfr = 0.0 - (pr * lpt - pi * lqt), gtfi = 0.0 - (0.0 - pi * lpt - pr * lqt);
+    const double gmr = gffr / t2 + gttr - ((cs * gftr + sn * gfti) + (cs * gtfr - sn * gtfi)) / tau;
+    const double gmi = gffi / t2 + gtti - ((cs * gfti - sn * gftr) + (cs * gtfi + sn * gtfr)) / tau;
+    const double y2r = ysr * ysr - ysi * ysi, y2i = 2.0 * ysr * ysi;
+    const double qr = y2r * gmr + y2i * gmi, qi = y2r * gmi - y2i * gmr;   // conj(y_s^2) Gamma
+    const double a0r = ysr / t2, a0i = (ysi + 0.5 * b) / t2;
+    const double a2r = -(ysr * cs - ysi * sn) / tau, a2i = -(ysr * sn + ysi * cs) / tau;
+    const double a3r = -(ysr * cs + ysi * sn) / tau, a3i = -(ysi * cs - ysr * sn) / tau;
+    const double d_tau = 0.0 - (2.0 * (a0r * gffr + a0i * gffi) + (a2r * gftr + a2i * gfti) + (a3r * gtfr + a3i * gtfi)) / tau;
+    const double d_sh = (a2r * gfti - a2i * gftr) - (a3r * gtfi - a3i * gtfr);
+    double* pl = part_line + 5 * e;
+    pl[0] += 0.0 - qr;                               // r
+    pl[1] += 0.0 - qi;                               // x
+    pl[2] += 0.5 * gffi / t2 + 0.5 * gtti;           // b
+    pl[3] += d_tau;                                  // tau
+    pl[4] += d_sh;                                   // shift
+  }
+  return true;
+}
+
+// A wave per grid: the chunks' partials summed in order, the contract applied, every element of the three gradient rows written
+__global__ __launch_bounds__(PF_THREADS) void gns_acn1_adjoint_reduce_kernel(const int32_t* __restrict__ topo,
+                                                                             const float* __restrict__ lines, const int nchunks,
+                                                                             const double* __restrict__ partials,
+                                                                             float* __restrict__ gb_out, float* __restrict__ gl_out,
+                                                                             float* __restrict__ gg_out) {
+  const int lane = threadIdx.x, g = blockIdx.x;
+  const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN];
+  const int32_t* gen_ptr = topo + topo[PH_GEN_PTR];
+  const int32_t* gen_idx = topo + topo[PH_GEN_IDX];
+  const int np = (int)acn1_adjoint_partial(topo);
+  const double* part = partials + (size_t)g * nchunks * np;
+  const float* line = lines + (size_t)g * E * 7;
+
+  bool bad = false, solved = false;
+  for (int c = lane; c < nchunks; c += PF_THREADS) {
+    const double status = part[(size_t)c * np + np - 1];
+    bad |= status != ACN1_PART_OK && status != ACN1_PART_UNSOLVED_ZERO;
+    solved |= status != ACN1_PART_UNSOLVED_ZERO;
+  }
+  const float fill = __ballot(bad) ? __builtin_nanf("") : 0.0f;
+  if (__ballot(bad) || !__ballot(solved)) {
+    if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = fill;
+    if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = fill;
+    if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = fill;
+    return;
+  }
+
+  // (0.0 - x rather than -x: an exact zero stays +0)
+  if (gb_out)
+    for (int i = lane; i < N; i += PF_THREADS) {
+      double s[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int c = 0; c < nchunks; ++c)
+        for (int u = 0; u < 4; ++u) s[u] += part[(size_t)c * np + 4 * i + u];
+      float* row = gb_out + ((size_t)g * N + i) * 6;
+      row[0] = 0.0f; row[1] = 0.0f;
+      row[2] = (float)(0.0 - s[0]);          // Pd
+      row[3] = (float)(0.0 - s[1]);          // Qd
+      row[4] = (float)(0.0 - s[2]);          // Gs
+      row[5] = (float)s[3];                  // Bs
+    }
+  if (gg_out)
+    for (int q = lane; q < Gn; q += PF_THREADS) {
+      int b = 0, hi = N;
+      while (hi - b > 1) {
+        const int mid = (b + hi) >> 1;
+        if (gen_ptr[mid] <= q) b = mid;
+        else hi = mid;
+      }
+      double dp = 0.0, dvg = 0.0;
+      for (int c = 0; c < nchunks; ++c) {
+        dp += part[(size_t)c * np + 4 * b];
+        dvg += part[(size_t)c * np + 4 * N + 5 * E + q];
+      }
+      float* row = gg_out + ((size_t)g * Gn + gen_idx[q]) * 7;
+      row[0] = 0.0f; row[1] = 0.0f; row[2] = 0.0f; row[3] = 0.0f;
+      row[4] = (float)dvg;                   // vg
+      row[5] = 0.0f;
+      row[6] = (float)dp;                    // Pg: S_spec += Pg
+    }
+  if (gl_out)
+    for (int e = lane; e < E; e += PF_THREADS) {
+      float* row = gl_out + ((size_t)g * E + e) * 7;
+      int f, t;
+      if (!acn1_line_ends(line, e, N, f, t)) {
+        for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
+        continue;
+      }
+      double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      for (int c = 0; c < nchunks; ++c)
+        for (int u = 0; u < 5; ++u) s[u] += part[(size_t)c * np + 4 * N + 5 * e + u];
+      row[0] = 0.0f; row[1] = 0.0f;
+      for (int u = 0; u < 5; ++u) row[2 + u] = (float)s[u];
+    }
+}
+
+// ---- host: what gns_acn1_adjoint and gns_acn2_adjoint (and their workspace queries) do alike
+
+// The partials of a call: one per (grid, chunk), rounded up to 256 bytes
+inline size_t acn1_adjoint_partial_bytes(const int32_t* h, int64_t Bt, int64_t nchunks) {
+  return ((size_t)Bt * nchunks * acn1_adjoint_partial(h) * sizeof(double) + 255) & ~(size_t)255;
+}
+
+// The workspace of either adjoint: the base Y-bus of every grid, then a partial per (grid, chunk of C rows of the list)
+inline int acn_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_row, int C, size_t* bytes) {
+  if (!cfg || !topo_host || !bytes || Bt <= 0 || n_row <= 0) return GNS_EINVAL;
+  const int32_t* h = static_cast<const int32_t*>(topo_host);
+  if (!pf_header_ok<PfBlobKind>(cfg, h)) return GNS_EINVAL;
+  int64_t nchunks = 0;
+  if (!pf_chunks(n_row, C, Bt, &nchunks)) return GNS_EINVAL;
+  if (pf_lds_bytes(h) > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
+  *bytes = pf_ws_bytes_nnzy(h[PH_NNZY], Bt) + acn1_adjoint_partial_bytes(h, Bt, nchunks);
+  return GNS_OK;
+}
+
+// An adjoint call around its own row kernel, in the order the codes win: the arguments, the blob's header, the list (list_ok(h): the
+// entry point's own check of its n_row outages or pairs against the blob at h), a workgroup per (grid, chunk of C rows) in one
+// launch, the LDS image; with no gradient output asked for GNS_OK without a launch; then the workspace.  Three launches: the base
+// Y-bus of every grid into the workspace, launch_rows(lds, nchunks, ybus, partials) (the entry point's row kernel, a workgroup per
+// (grid, chunk)), the sum of each grid's partials.
+template <class ListOk, class LaunchRows>
+int acn_adjoint_call(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev, const float* buses, const float* lines,
+                     const float* generators, int64_t Bt, const int32_t* list_host, const int32_t* list_dev, int32_t n_row,
+                     const uint8_t* islanding, int32_t rating_per_grid, const double* v, const double* theta, const uint8_t* converged,
+                     const int32_t* worst_line, const int32_t* v_min_bus, const int32_t* v_max_bus, const uint8_t* base_converged,
+                     float* grad_buses, float* grad_lines, float* grad_generators, void* workspace, size_t workspace_bytes,
+                     void* stream, int C, ListOk list_ok, LaunchRows launch_rows) {
+  if (!pf_config_ok(cfg) || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF ||
+      !list_host || !list_dev || n_row <= 0 || !islanding || (rating_per_grid != 0 && rating_per_grid != 1) || !v || !theta ||
+      !converged || !worst_line || !v_min_bus || !v_max_bus || !base_converged)
+    return GNS_EINVAL;
+  const int32_t* h = static_cast<const int32_t*>(topo_host);
+  if (!pf_header_ok<PfBlobKind>(cfg, h) || !list_ok(h)) return GNS_EINVAL;
+  int64_t nchunks = 0;
+  if (!pf_chunks(n_row, C, Bt, &nchunks)) return GNS_EINVAL;
+  const int64_t lds = pf_lds_bytes(h);
+  if (lds > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
+  if (!grad_buses && !grad_lines && !grad_generators) return GNS_OK;
+  if (!workspace) return GNS_EINVAL;
+  const size_t ybytes = pf_ws_bytes_nnzy(h[PH_NNZY], Bt);
+  if (workspace_bytes < ybytes + acn1_adjoint_partial_bytes(h, Bt, nchunks)) return GNS_ESIZE;
+  const int32_t* topo = static_cast<const int32_t*>(topo_dev);
+  double2* ybus = static_cast<double2*>(workspace);
+  double* partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + ybytes);
+  const int rc0 = pf_launch<gns_acn1_ybus_kernel>(Bt, 0, stream, topo, buses, lines, ybus);
+  if (rc0 != GNS_OK) return rc0;
+  const int rc1 = launch_rows(lds, nchunks, (const double2*)ybus, partials);
+  if (rc1 != GNS_OK) return rc1;
+  return pf_launch<gns_acn1_adjoint_reduce_kernel>(Bt, 0, stream, topo, lines, (int)nchunks, (const double*)partials, grad_buses,
+                                                   grad_lines, grad_generators);
+}
+
+}  // namespace

@@ -38,7 +38,8 @@ at the forward's state, on the same analysis.
 
 ``ac_n2_contingency_screen(...)`` is that screen for a list of double-line outages, such as the worst pairs
 ``dc_n2_contingency_screen`` ranked: Newton-Raphson on every ``(grid, pair)``, again on the base topology's analysis alone
-(``csrc/gns_acn2.hip``).
+(``csrc/gns_acn2.hip``).  ``ac_n2_contingency_screen_differentiable(...)`` is the same screen with a backward: one ``gns_acn2_adjoint`` call,
+per pair one factorisation and one transposed solve at the forward's state.
 """
 from __future__ import annotations
 
@@ -1093,9 +1094,10 @@ def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
 
 
 class _ACN1Function(torch.autograd.Function):
-    """``ac_contingency_screen(differentiable=True)`` when an input requires grad, as ``_DCN1Function``: the forward is the screen's
-    launch (``screen`` returns the fifteen outputs in ``gns_acn1_screen``'s order, ``v`` and ``theta`` always there), the backward
-    one ``gns_acn1_adjoint`` call on the forward's topology, outage list and state.  Newton is not run again."""
+    """``ac_contingency_screen(differentiable=True)`` and ``ac_n2_contingency_screen_differentiable`` when an input requires grad, as
+    ``_DCN1Function``: the forward is the screen's launch (``screen`` returns the fifteen outputs in ``gns_acn1_screen``'s order,
+    ``v`` and ``theta`` always there), the backward one ``gns_acn1_adjoint`` / ``gns_acn2_adjoint`` call (``adjoint``, ``_ac_screen``'s)
+    on the forward's topology, list and state.  Newton is not run again."""
 
     @staticmethod
     def forward(ctx, screen, adjoint, buses, lines, gens):
@@ -1171,15 +1173,24 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     Contract: ``include/gns_powerflow.h``, "AC contingency screening"."""
     s = _screen_setup('ac_contingency_screen', _NR, buses, lines, generators, B, L, G, slack_bus, outages, rating,
                       dict(flows=flows, states=states), differentiable, tol, max_iter)
+    base, outages_t, res, islanding = _ac_screen(s, _ACN1, states, flows)
+    return AcContingencyResult(PowerFlowResult(*base), outages_t, *res, islanding)
+
+
+def _ac_screen(s, solver, states, flows):
+    """Both AC screens after ``_screen_setup``: the base case as ``newton_raphson`` solves it, ``solver``'s screen launch
+    (``_ac_screen_launch``) on the list ``s.rows`` and, when the call is differentiated, the two through ``_NRFunction`` and
+    ``_ACN1Function`` with ``solver``'s adjoint entry point as the screen's backward.  Returns ``_screen_results``' tuple."""
     with torch.set_grad_enabled(s.grad):
         lib, cfg, topo, Bt, dev, grad = s.lib, s.cfg, s.topo, s.Bt, s.dev, s.grad
-        K = s.rows.size
+        n_rows = s.rows.shape[0]
         shared = _shared_args(s, _upload32(s.rows, dev))
         lds = topo.info['lds_bytes']
         target = _one_topology(topo)
+        adjoint_name = solver.prefix + '_adjoint'
 
         def adjoint_workspace_bytes():
-            return _screen_workspace_bytes(s, 'gns_acn1_adjoint_workspace_bytes', (K,), lds, _ACN1.formula)
+            return _screen_workspace_bytes(s, adjoint_name + '_workspace_bytes', (n_rows,), lds, solver.formula)
 
         # the base case as newton_raphson solves it (its refusals come first, then the backward's own, before anything is launched)
         if grad:
@@ -1192,26 +1203,25 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
         base_state = (base[0].detach(), base[1].detach(), base_conv)      # the warm start is not differentiated
 
         def screen(bu, li, ge):
-            return _ac_screen_launch(s, _ACN1, shared, K, base_state, states or grad, flows, bu, li, ge)
+            return _ac_screen_launch(s, solver, shared, n_rows, base_state, states or grad, flows, bu, li, ge)
 
         def adjoint(bu, li, ge, state, incoming, need):
-            """One ``gns_acn1_adjoint`` call at the forward's ``state`` (v, theta, converged, worst_line, v_min_bus, v_max_bus)."""
+            """One adjoint call at the forward's ``state`` (v, theta, converged, worst_line, v_min_bus, v_max_bus)."""
             gin = [torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need)]
             incoming = [None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming]
             ws = _gns._workspace(adjoint_workspace_bytes(), dev)
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev).cuda_stream
-                _check(lib.gns_acn1_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
-                                            li.data_ptr(), ge.data_ptr(), Bt, *shared(), *(t.data_ptr() for t in state),
-                                            base_conv.data_ptr(), *map(_ptr, incoming), *map(_ptr, gin), ws.data_ptr(), ws.numel(),
-                                            stream), 'gns_acn1_adjoint', lds, _ACN1.formula)
+                _check(getattr(lib, adjoint_name)(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                                  li.data_ptr(), ge.data_ptr(), Bt, *shared(), *(t.data_ptr() for t in state),
+                                                  base_conv.data_ptr(), *map(_ptr, incoming), *map(_ptr, gin), ws.data_ptr(),
+                                                  ws.numel(), stream), adjoint_name, lds, solver.formula)
             return gin
 
         res = list(_ACN1Function.apply(screen, adjoint, s.buses, s.lines, s.generators)) if grad else screen(*s.plain)
         if not states:
             res[0] = res[1] = None
-        base, outages_t, res, islanding = _screen_results(s, base, res, 12)
-        return AcContingencyResult(PowerFlowResult(*base), outages_t, *res, islanding)
+        return _screen_results(s, base, res, 12)
 
 
 def ac_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, pairs=None, rating=None,
@@ -1251,18 +1261,55 @@ def ac_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
     in any batch, in any pair list or order that holds it, in either order of its two lines, and from run to run.  With a 2-D single
     grid the batch dimension is dropped.
 
-    Not differentiable: the call runs as under ``torch.no_grad()``, and ``requires_grad`` on an input is ignored without an error.
-    Out of scope: gradients, batches that mix topologies, line plus generator outages and generator reactive limits.
+    This call runs as under ``torch.no_grad()``, and ``requires_grad`` on an input is ignored without an error; the same screen with
+    gradients is ``ac_n2_contingency_screen_differentiable``.
+    Out of scope: batches that mix topologies, line plus generator outages and generator reactive limits.
     Contract: ``include/gns_powerflow.h``, "AC N-2 contingency screening"."""
+    return _ac_n2_screen(buses, lines, generators, B, L, G, slack_bus, pairs, rating, tol, max_iter, flows, states, False)
+
+
+def _ac_n2_screen(buses, lines, generators, B, L, G, slack_bus, pairs, rating, tol, max_iter, flows, states, differentiable):
+    """``ac_n2_contingency_screen`` (``differentiable`` False) and ``ac_n2_contingency_screen_differentiable`` (True)."""
     s = _screen_setup('ac_n2_contingency_screen', _NR, buses, lines, generators, B, L, G, slack_bus, pairs, rating,
-                      dict(flows=flows, states=states), False, tol, max_iter)
-    with torch.no_grad():
-        # the base case as newton_raphson solves it (its refusals come first)
-        base = _solve(s.lib, _NR, s.cfg, _one_topology(s.topo), *s.plain, None, None)
-        res = _ac_screen_launch(s, _ACN2, _shared_args(s, _upload32(s.rows, s.dev)), s.rows.shape[0],
-                                (base[0], base[1], base[2].to(torch.uint8)), states, flows, *s.plain)
-        base, pairs_t, res, islanding = _screen_results(s, base, res, 12)
-        return AcN2ContingencyResult(PowerFlowResult(*base), pairs_t, *res, islanding)
+                      dict(flows=flows, states=states), differentiable, tol, max_iter)
+    base, pairs_t, res, islanding = _ac_screen(s, _ACN2, states, flows)
+    return AcN2ContingencyResult(PowerFlowResult(*base), pairs_t, *res, islanding)
+
+
+def ac_n2_contingency_screen_differentiable(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, pairs=None,
+                                            rating=None, tol=1e-8, max_iter=10, flows=False, states=False):
+    """``ac_n2_contingency_screen`` with gradients: the same arguments, the same ``AcN2ContingencyResult`` with every forward output
+    bit-identical to that call's, and a backward on the device, as ``ac_contingency_screen(differentiable=True)`` has one.  It is
+    the last step of the workflow the plain call names (``dc_n2_contingency_screen`` over every pair, the few hundred worst, the AC
+    check of those) for a security-constrained loss or a sensitivity study of the worst double outages.
+
+    With grad mode on and ``requires_grad`` on an input, ``v``, ``theta``, the four flows, ``worst_loading``, ``v_min`` and ``v_max``
+    are differentiable through one ``gns_acn2_adjoint`` call on the forward's topology, pair list and state (per row the implicit
+    function theorem on the grid without both lines: one factorisation of the row's Jacobian on the base analysis and one
+    transposed solve; Newton is not run again), and ``base.v`` / ``base.theta`` through ``newton_raphson``'s adjoint.  Otherwise
+    (grad mode off, no input requires grad) it is the plain call and returns plain tensors.
+
+    The derivative is exact at the returned state with respect to ``newton_raphson``'s columns (``Pd, Qd, Gs, Bs``; the lines'
+    ``r, x, b, tau, shift``; ``Pg`` and the ``vg`` of the first generator on a PV / slack bus); every other column gets 0, and row
+    ``(j,k)`` gives exactly 0 to the own columns of lines ``j`` and ``k``, whose flows are the constant 0.  ``rating`` is a constant
+    and the warm start is not differentiated (a converged row does not depend on it).  ``worst_loading`` sends its gradient to
+    ``worst_line``, at the end that attains the maximum (the from end on equality), ``v_min`` / ``v_max`` to the buses reported; the
+    index outputs, ``converged``, ``iterations``, ``mismatch``, ``islanding`` and ``pairs`` are not differentiable.
+
+    With ``states=False`` (the default) the summaries and the flows stay differentiable: ``v`` and ``theta`` are then kept for the
+    backward and not returned.  That costs ``16 Bt P N`` bytes until the backward has run: 32 MB per grid at every pair of case118
+    (P = 17 205, N = 118), 15 MB for 64 case118 grids and a list of 128 pairs.
+
+    A row whose incoming gradients are all exactly zero or absent is skipped, never multiplied by zero (a loss that indexes
+    ``converged`` rows); a non-zero gradient into a row that is not converged (an islanding pair, a stopped iteration), a zero or
+    non-finite pivot or a non-finite lambda makes the grid's three gradient rows NaN; a grid without a base solution gets NaN rows,
+    zero rows when all its incoming gradients are zero.  Other grids are unaffected.  A grid's gradient is bit-identical alone, in
+    any batch, from run to run and with the two lines of any pair swapped, for the same pair list (another order of the list may
+    change its last bits).
+
+    Out of scope: batches that mix topologies, line plus generator outages, generator reactive limits and second derivatives.
+    Contract: ``include/gns_powerflow.h``, "Gradients of the AC N-2 screen"."""
+    return _ac_n2_screen(buses, lines, generators, B, L, G, slack_bus, pairs, rating, tol, max_iter, flows, states, True)
 
 
 def _not_solved(Bt, N, dev):

@@ -488,8 +488,8 @@ int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  * Bt times the chunks of either kernel, above 2^31 - 1; GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES; GNS_ESIZE
  * for a short workspace.  GNS_EINVAL wins over GNS_EUNSUPPORTED, which wins over GNS_ESIZE (a NULL workspace is looked at with its
  * size).  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
- * Gradients: gns_dcn2_adjoint, below.  The AC solve of chosen pairs: gns_acn2_screen.  Not here: batches that mix topologies, line
- * plus generator outages. */
+ * Gradients: gns_dcn2_adjoint, below.  The AC solve of chosen pairs: gns_acn2_screen.  Generator outages, alone or with a line:
+ * "DC generator contingency screening", below.  Not here: batches that mix topologies. */
 int gns_dcn2_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
 int gns_dcn2_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_cand, size_t* bytes);
 int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
@@ -546,7 +546,7 @@ int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, const void*
  * Bt times the chunks of any kernel, or Bt * n_cand, above 2^31 - 1; then GNS_EUNSUPPORTED for an LDS image above
  * GNS_PF_LDS_MAX_BYTES (from the workspace query too); then, when an output is asked for, GNS_EINVAL for a NULL workspace and
  * GNS_ESIZE for a short one.  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
- * Not here: batches that mix topologies, line plus generator outages, second derivatives. */
+ * Not here: batches that mix topologies, second derivatives.  Generator outages: "DC generator contingency screening", below. */
 int gns_dcn2_adjoint_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
 int gns_dcn2_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_cand, int32_t n_pair,
                                      size_t* bytes);
@@ -559,6 +559,82 @@ int gns_dcn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
                      const double* grad_line_flow, const double* grad_worst_loading,
                      float* grad_buses, float* grad_lines, float* grad_generators,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* DC generator contingency screening: the post-outage DC flows of a list of generator outages, each alone or with one line out as
+ * well (the combined N-1 set: a unit out plus a line out), of every grid of a batch, from the base factorisation alone.  A generator
+ * outage changes the injections, not the matrix: it is one more solve on the base factor per distinct generator of the list.  The
+ * line on top of it is the rank-1 update of "DC contingency screening" above, from one single-line solve per distinct line.
+ *
+ * Semantics (the base case of "DC power flow": theta, F_l, b_l, Bbus; notation of "DC contingency screening": A = Bbus[r, r],
+ * A z_k = m_k on the base factor; fp64 throughout).  A row is (g, k): g a 0-based generator row, k a 0-based line or -1 for "no
+ * line out".
+ *   Generator g out: its Pg_g (column 6) leaves its bus m_g.  With pickup weights w_h >= 0 (per grid or shared) and W_g the sum of
+ *   w_h over h != g in generator-index order, every other generator h gains Pg_g * (w_h / W_g) at its bus when W_g > 0; when
+ *   W_g == 0 (every remaining weight exactly zero) or pickup is NULL nothing is redistributed and the slack picks the loss up, which
+ *   is what dcpf does with a unit whose Pg is set to 0.  dP is the resulting change of the bus injections: -Pg_g at m_g first, then
+ *   the shares in generator-index order.  No Pmax or Pmin limit is enforced on the units that pick up.
+ *     A u_g = dP_r on the base factor, u_g = 0 at the slack
+ *     D_g[l] = u_g[f_l] - u_g[t_l]
+ *     Fg_l = F_l + b_l * D_g[l]
+ *   Row (g, -1): F'_l = Fg_l.
+ *   Row (g, k), with H_k[l] = z_k[f_l] - z_k[t_l] and z_k exactly as the N-1 and N-2 screens make it:
+ *     den = 1 - b_k * H_k[k]
+ *     alpha = Fg_k / den
+ *     F'_l = Fg_l + (b_l * H_k[l]) * alpha   for l != k;   F'_k = 0
+ *   with exactly this association of the operations (the build has -ffp-contract=off, so the bits are determined).  A line from a
+ *   bus to itself has m = 0 and changes nothing.
+ *   worst_loading = max_l |F'_l| / rating_l (rating NULL: 1) and worst_line the 0-based line that attains it, the lowest of equals,
+ *   by the total order of the N-1 screen's reduction (NaN is worst of all).
+ *   Islanding: a generator outage never islands; row (g, k) islands exactly when k is a bridge.  The kernel does not decide that
+ *   numerically: the caller passes islanding[n_row].  Those rows get NaN in line_flow and worst_loading and -1 in worst_line, in
+ *   every grid.
+ *   Failure: a grid whose base solve fails (converged = 0, as gns_dc_solve decides it) gets NaN / -1 in every row; a row whose u_g,
+ *   z_k, den or alpha is not finite, or whose den is zero, gets NaN / -1 alone.
+ *   Every (grid, row) is bit-identical alone, in any batch, in any list or order that holds it (duplicates are independent rows) and
+ *   from run to run: no atomics, the reductions in a fixed order.
+ *   From the definition: where Pg_g is exactly 0, or g sits on the slack bus and pickup is NULL, dP_r is zero, so row (g, -1) is the
+ *   base line_flow and row (g, k) is row k of gns_dcn1_screen, bit for bit.
+ *
+ * Inputs: line_list [n_line] int32, the distinct lines of the rows, ascending (n_line may be 0: then the two pointers may be NULL),
+ * and gen_list [n_gen] int32, the distinct generators of the rows, ascending, each on the host (checked before the launch) and on
+ * the device; row_cols [n_row,2] int32, each row as a position into gen_list and a position into line_list or -1, on the host and
+ * on the device; islanding [n_row] uint8 on the device; rating NULL, [E] (rating_per_grid 0) or [Bt,E] (1) fp64 on the device;
+ * pickup NULL, [Gn] (pickup_per_grid 0) or [Bt,Gn] (1) fp64 on the device, by generator row (not by position into gen_list).
+ * Outputs: line_flow [Bt,n_row,E] fp64, or NULL for the summaries alone (8 Bt n_row E bytes not written); worst_loading [Bt,n_row]
+ * fp64; worst_line [Bt,n_row] int32; converged [Bt] uint8, the base solve's.
+ *
+ * Kernels (gns_dcg1.hip), the two-kernel shape of gns_dcn2.hip.  Factor: one wave per (grid, chunk of W candidates), the candidates
+ * being line_list followed by gen_list (n_cand = n_line + n_gen), with the N-1 screen's prologue, LDS image and lane solve
+ * (gns_dcn1_device.h): a line lane solves z_k as that screen does, bit for bit; a generator lane zeroes its column, writes dP_r (the
+ * bus of a generator from the blob's by-bus generator lists) and runs the same solve program.  A pass with a line per lane then
+ * stores z[f_l] - z[t_l] of every candidate (H_k, D_g) contiguously into the workspace with a finite flag per candidate, and chunk 0
+ * also stores F_l, b_l and the grid's status.  Its LDS image and W are gns_dcn1_lds_bytes' (gns_dcg1_lds_bytes reports them).  Row:
+ * one wave per (grid, chunk of Q consecutive rows), F, b and the rating in LDS (24 E bytes); per row den and alpha are computed
+ * identically on every lane, a line per lane forms F'_l from the two contiguous workspace rows, and the wave reduction of the N-1
+ * screen finishes the row.  Q comes from n_row alone (32 from 8192 rows on, else 8).  Workspace (gns_dcg1_workspace_bytes), the N-2
+ * screen's layout: Bt * (n_cand * E + 2 E + n_cand + 1) doubles (the candidates' rows, F, b, the flags, the status), rounded up to
+ * 256 bytes.
+ *
+ * Errors: GNS_EINVAL for a NULL cfg, blob, input, gen_list, row_cols, islanding mask, output other than line_flow or workspace, a
+ * NULL line_list with n_line > 0, a blob that is not an FD blob or whose N, E, Gn are not cfg's, n_line < 0 or above E, n_gen <= 0
+ * or above Gn, n_row <= 0, a line outside 0 .. E-1 or a generator outside 0 .. Gn-1, a list not ascending or not distinct, a
+ * generator column outside 0 .. n_gen-1, a line column outside -1 .. n_line-1, rating_per_grid or pickup_per_grid outside {0, 1}, or
+ * Bt, or Bt times the chunks of either kernel, above 2^31 - 1; GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES;
+ * GNS_ESIZE for a short workspace.  GNS_EINVAL wins over GNS_EUNSUPPORTED, which wins over GNS_ESIZE (a NULL workspace is looked at
+ * with its size).  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.  The values of
+ * pickup are the caller's to check (non-negative, finite): the kernel reads them as they are.
+ * Not here: AC generator outages (an outage can turn a PV bus into a PQ bus: another analysis), the gradients of this screen, limits
+ * on the units that pick up, batches that mix topologies, a generator plus two lines. */
+int gns_dcg1_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
+int gns_dcg1_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_line, int32_t n_gen, size_t* bytes);
+int gns_dcg1_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                    const float* buses, const float* lines, const float* generators, int64_t Bt,
+                    const int32_t* line_host, const int32_t* line_dev, int32_t n_line,
+                    const int32_t* gen_host, const int32_t* gen_dev, int32_t n_gen,
+                    const int32_t* row_cols_host, const int32_t* row_cols_dev, int32_t n_row, const uint8_t* islanding,
+                    const double* rating, int32_t rating_per_grid, const double* pickup, int32_t pickup_per_grid,
+                    double* line_flow, double* worst_loading, int32_t* worst_line, uint8_t* converged,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* AC contingency screening: Newton-Raphson on every grid of a batch with each single line of a list out of service (an N-1 set),
  * with the post-outage state, the branch flows at both ends of every line and their summaries, from the base analysis alone.

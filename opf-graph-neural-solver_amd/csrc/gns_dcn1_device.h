@@ -1,7 +1,8 @@
-// The device helpers of the DC contingency screens that gns_dcn1.hip (single outages and their adjoint) and gns_dcn2.hip (double
-// outages) share: the LDS image of a screen workgroup, the base case of a grid as gns_dc_kernel solves it, a lane's own solve of
-// z_k on the base factor, the post-outage flow of a line and the total order of the worst-loading reductions.  Both screens run
-// this code, so z_k and the base flows of the double-outage screen are the single-outage screen's bit for bit.  At the end, what
+// The device helpers of the DC contingency screens that gns_dcn1.hip (single outages and their adjoint), gns_dcn2.hip (double
+// outages) and gns_dcg1.hip (generator and generator-plus-line outages) share: the LDS image of a screen workgroup, the base case of
+// a grid as gns_dc_kernel solves it, a lane's own solve of z_k on the base factor, the post-outage flow of a line and the total order
+// of the worst-loading reductions.  Every screen runs this code, so z_k and the base flows of the other screens are the single-outage
+// screen's bit for bit.  Then the workspace of the screens that run a factor kernel and a streaming row kernel.  At the end, what
 // the two adjoints share: the scan for non-zero incoming gradients, the status of a chunk's partial and the kernel that reduces the
 // partials, applies the contract and writes the fp32 gradient rows.
 #pragma once
@@ -158,6 +159,37 @@ __device__ __forceinline__ double dcn1_flow(const Dcn1Image& m, const int l, con
   const double zf = en.x >= 0 ? m.Z[en.x * ld + j] : 0.0, zt = en.y >= 0 ? m.Z[en.y * ld + j] : 0.0;
   return m.lF[l] + m.lb[l] * (zf - zt) * alpha;
 }
+
+// ---- what the screens that run a factor kernel and then a streaming row kernel share (gns_dcn2.hip: double outages; gns_dcg1.hip:
+// generator and generator-plus-line outages)
+
+// The workspace of one call: H [Bt][n_cand][E], then F [Bt][E], b [Bt][E], the candidates' finite flags [Bt][n_cand] and the grids'
+// status [Bt] (1: the base case is solved), all doubles
+struct Dcn2Workspace {
+  double* H;
+  double* F;
+  double* b;
+  double* fin;
+  double* status;
+};
+
+__host__ __device__ inline Dcn2Workspace dcn2_workspace(double* ws, const int64_t Bt, const int64_t n_cand, const int64_t E) {
+  Dcn2Workspace w;
+  w.H = ws;
+  w.F = w.H + Bt * n_cand * E;
+  w.b = w.F + Bt * E;
+  w.fin = w.b + Bt * E;
+  w.status = w.fin + Bt * n_cand;
+  return w;
+}
+
+size_t dcn2_ws_bytes(const int32_t* h, int64_t Bt, int64_t n_cand) {
+  const int64_t E = h[FH_E];
+  return ((size_t)Bt * (size_t)(n_cand * E + 2 * E + n_cand + 1) * sizeof(double) + 255) & ~(size_t)255;
+}
+
+// Rows (pairs) a workgroup of the row kernel takes one after the other: from the length of the list alone
+int dcn2_pairs_per_wave(int64_t n_pair) { return n_pair >= 8192 ? 32 : 8; }
 
 // ---- what the adjoints of both screens share (gns_dcn1_adjoint, gns_dcn2_adjoint)
 

@@ -23,26 +23,6 @@
 
 namespace {
 
-// The workspace of one call: H [Bt][n_cand][E], then F [Bt][E], b [Bt][E], the candidates' finite flags [Bt][n_cand] and the grids'
-// status [Bt] (1: the base case is solved), all doubles
-struct Dcn2Workspace {
-  double* H;
-  double* F;
-  double* b;
-  double* fin;
-  double* status;
-};
-
-__host__ __device__ inline Dcn2Workspace dcn2_workspace(double* ws, const int64_t Bt, const int64_t n_cand, const int64_t E) {
-  Dcn2Workspace w;
-  w.H = ws;
-  w.F = w.H + Bt * n_cand * E;
-  w.b = w.F + Bt * E;
-  w.fin = w.b + Bt * E;
-  w.status = w.fin + Bt * n_cand;
-  return w;
-}
-
 __global__ __launch_bounds__(PF_THREADS) void gns_dcn2_factor_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
                                                                      const float* __restrict__ lines, const float* __restrict__ gens,
                                                                      const int32_t* __restrict__ cand, const int n_cand, const int Bt,
@@ -164,9 +144,6 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcn2_pair_kernel(const int32_t
   }
 }
 
-// Pairs a workgroup of the pair kernel takes one after the other: from the length of the pair list alone
-int dcn2_pairs_per_wave(int64_t n_pair) { return n_pair >= 8192 ? 32 : 8; }
-
 // One blob, one candidate list and one pair list: GNS_EINVAL unless it is an FD blob of cfg's shape, the candidates are lines of it,
 // ascending and distinct, and every pair holds two different positions into them; lanes and lds are the chunk width and the LDS
 // image of the factor kernel's launch (the N-1 screen's)
@@ -184,11 +161,6 @@ int dcn2_check(const gns_pf_config* cfg, const void* topo_host, const int32_t* c
   *lanes = dcn1_lanes(h, GNS_PF_LDS_MAX_BYTES);
   *lds = dcn1_lds_bytes(h, *lanes);
   return GNS_OK;
-}
-
-size_t dcn2_ws_bytes(const int32_t* h, int64_t Bt, int64_t n_cand) {
-  const int64_t E = h[FH_E];
-  return ((size_t)Bt * (size_t)(n_cand * E + 2 * E + n_cand + 1) * sizeof(double) + 255) & ~(size_t)255;
 }
 
 // ---- the adjoint (gns_dcn2_adjoint; include/gns_powerflow.h, "DC N-2 contingency screening", gradients)

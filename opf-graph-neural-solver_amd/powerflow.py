@@ -30,6 +30,10 @@ With ``differentiable=True`` its backward is one ``gns_dcn1_adjoint`` call: a se
 the DC matrix, so the single-outage solves (one per distinct line of the list) and a 2x2 system per pair give the exact flows
 (``csrc/gns_dcn2.hip``); the pairs that disconnect the grid are found on the host.
 
+``dc_generator_contingency_screen(...)`` screens a batch against a list of generator outages, each alone or with a line out as well
+(the combined N-1 set): a generator outage changes the injections alone, so it is one more solve on the base factor per distinct
+generator, and the line on top of it is the single-outage update again (``csrc/gns_dcg1.hip``).
+
 ``ac_contingency_screen(...)`` is the AC answer to the same question: Newton-Raphson on every ``(grid, outage)`` pair, warm-started
 from the base solution, on the base topology's analysis alone (an outage only removes Jacobian entries), with the post-outage
 voltages, the branch flows at both ends of every line, the worst loading and the voltage extremes (``csrc/gns_acn1.hip``).
@@ -65,6 +69,9 @@ DcContingencyResult = namedtuple('DcContingencyResult', ['base', 'outages', 'lin
 
 DcN2ContingencyResult = namedtuple('DcN2ContingencyResult', ['base', 'pairs', 'line_flow', 'worst_loading', 'worst_line', 'islanding',
                                                              'converged'])
+
+DcGeneratorContingencyResult = namedtuple('DcGeneratorContingencyResult', ['base', 'contingencies', 'line_flow', 'worst_loading',
+                                                                           'worst_line', 'islanding', 'converged'])
 
 AcContingencyResult = namedtuple('AcContingencyResult', ['base', 'outages', 'v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to',
                                                          'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max', 'v_max_bus',
@@ -160,6 +167,9 @@ _DCN1 = _Solver('gns_dcn1', FdTopology, _DCN1_LDS_FORMULA)   # the DC contingenc
 _DCN2_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per workgroup of the factor kernel: the DC N-1 screen's image, "
                      "the right-hand sides of W candidate lines side by side, here with W = 1, the narrowest")
 _DCN2 = _Solver('gns_dcn2', FdTopology, _DCN2_LDS_FORMULA)   # the DC N-2 screen: the N-1 screen's analysis and image
+_DCG1_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per workgroup of the factor kernel: the DC N-1 screen's image, "
+                     "the right-hand sides of W candidates (lines, then generators) side by side, here with W = 1, the narrowest")
+_DCG1 = _Solver('gns_dcg1', FdTopology, _DCG1_LDS_FORMULA)   # the DC generator screen: the N-1 screen's analysis and image again
 _ACN1 = _Solver('gns_acn1', PowerFlowTopology, _LDS_FORMULA)   # the AC contingency screen: Newton-Raphson's analysis and LDS image
 _ACN2 = _Solver('gns_acn2', PowerFlowTopology, _LDS_FORMULA)   # the AC N-2 screen: the same analysis and image again
 _DCN1_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W) bytes per workgroup: the screen's image, a second "
@@ -742,14 +752,14 @@ def _dcn1_adjoint_lds_bytes(host):
 
 
 def _screen_setup(name, solver, buses, lines, generators, B, L, G, slack_bus, rows, rating, flags, differentiable, tol=0.0,
-                  max_iter=0):
-    """What the four contingency screens do before their own launches, in the order their refusals are raised: the bool ``flags``
+                  max_iter=0, pickup=None):
+    """What the contingency screens do before their own launches, in the order their refusals are raised: the bool ``flags``
     (a dict by name), ``tol`` / ``max_iter`` (the DC screens' never fail) and ``differentiable`` (False from a screen without
-    gradients); whether the call is differentiated (``grad``); the shapes, the list ``rows`` (outages, or pairs for a screen named
-    ``*_n2_*``) and the rating, checked where no device is visible too; ``_inputs``; ``solver``'s cached analysis of the one topology;
-    the islanding mask of the list, on the host (``isl_np``) and uploaded (``isl_dev``).  Returns a namespace of these and of the
-    shapes, the configuration ``cfg`` and the detached inputs ``plain``.  The caller goes on under
-    ``torch.set_grad_enabled(s.grad)``."""
+    gradients); whether the call is differentiated (``grad``); the shapes, the list ``rows`` (outages, pairs for a screen named
+    ``*_n2_*``, or (generator, line) rows for one named ``*_generator_*``, which also takes ``pickup``) and the rating, checked where
+    no device is visible too; ``_inputs``; ``solver``'s cached analysis of the one topology; the islanding mask of the list, on the
+    host (``isl_np``) and uploaded (``isl_dev``).  Returns a namespace of these and of the shapes, the configuration ``cfg`` and the
+    detached inputs ``plain``.  The caller goes on under ``torch.set_grad_enabled(s.grad)``."""
     for flag, value in flags.items():
         if not isinstance(value, bool):
             raise ValueError(f'{flag} must be a bool, got {value!r}')
@@ -759,12 +769,16 @@ def _screen_setup(name, solver, buses, lines, generators, B, L, G, slack_bus, ro
     s = SimpleNamespace()
     s.grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
                                                                 for t in (buses, lines, generators))
-    pairs = '_n2_' in name
+    pairs, generator = '_n2_' in name, '_generator_' in name
     with torch.no_grad():
         # the shapes first, so that a bad list or rating is refused where no device is visible too
-        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
+        single, shaped, shaped_lines, shaped_gens = _as_batch(buses, lines, generators, B, L, G)
         E = shaped_lines.shape[1]
-        s.rows = _pair_list(rows, E, name.replace('_n2', '')) if pairs else _outage_list(rows, E)
+        if generator:
+            s.rows = _generator_contingency_list(rows, shaped_gens.shape[1], E)
+            pickup = _pickup(pickup, shaped_gens, single)
+        else:
+            s.rows = _pair_list(rows, E, name.replace('_n2', '')) if pairs else _outage_list(rows, E)
         rating = _rating(rating, shaped.shape[0], E, single)
     with torch.set_grad_enabled(s.grad):
         if not s.grad:
@@ -774,11 +788,15 @@ def _screen_setup(name, solver, buses, lines, generators, B, L, G, slack_bus, ro
         s.lib = load_library()
         s.Bt, s.N, s.E, s.dev = s.buses.shape[0], s.buses.shape[1], s.lines.shape[1], s.buses.device
         s.rating = None if rating is None else rating.to(s.dev).contiguous()
+        s.pickup = None if pickup is None else pickup.to(s.dev).contiguous()
         s.cfg = PfConfig(s.N, s.E, s.generators.shape[1], int(max_iter), float(tol))
         s.plain = (s.buses.detach(), s.lines.detach(), s.generators.detach())
         key, args = _topology_key(*s.plain, slack_bus, name)
         s.topo = _analysed(solver, key, args, s.dev)
-        s.isl_np = _topology_pair_islanding(s.topo, args, s.rows) if pairs else _topology_bridges(s.topo, args)[s.rows]
+        if generator:
+            s.isl_np = _generator_islanding(_topology_bridges(s.topo, args), s.rows)
+        else:
+            s.isl_np = _topology_pair_islanding(s.topo, args, s.rows) if pairs else _topology_bridges(s.topo, args)[s.rows]
         s.isl_dev = torch.from_numpy(s.isl_np.astype(np.uint8)).to(s.dev)
     return s
 
@@ -820,10 +838,11 @@ def _screen_results(s, base, res, conv_at):
 
 
 def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_bytes, adjoint_formula, flows):
-    """Both DC screens after ``_screen_setup``: ``solver``'s screen launch (with its adjoint through ``_DCN1Function`` when the call is
+    """The DC screens after ``_screen_setup``: ``solver``'s screen launch (with its adjoint through ``_DCN1Function`` when the call is
     differentiated) and the base case.  ``shared``: ``_shared_args``'s closure; ``n_rows``: the rows per grid; ``counts`` /
     ``adjoint_counts``: what the two workspace queries take after Bt; ``adjoint_lds_bytes`` / ``adjoint_formula``: the adjoint's LDS
-    query and the formula its refusal names.  Returns ``(base, [line_flow, worst_loading, worst_line, converged])``."""
+    query and the formula its refusal names (None for a screen without gradients: the call is then never differentiated).  Returns
+    ``(base, [line_flow, worst_loading, worst_line, converged])``."""
     lib, cfg, topo, Bt, dev = s.lib, s.cfg, s.topo, s.Bt, s.dev
     lds = lambda: _dcn1_lds_bytes(topo.host)[0]                              # noqa: E731
     adjoint_lds = lambda: adjoint_lds_bytes(topo.host)[0]                    # noqa: E731
@@ -1077,7 +1096,8 @@ def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
     are NaN (zero rows for an unsolved grid whose incoming gradients are all zero).  The forward outputs are bit-identical with and
     without gradients.  A grid's gradient is bit-identical alone, in any batch and from run to run for the same pair list, and a
     list that holds ``(k,j)`` where another holds ``(j,k)`` gives the same bits; the order of the list may change its last bits.
-    Mixed topologies, line plus generator outages and second derivatives are out of scope; the AC solve of chosen pairs is
+    Mixed topologies and second derivatives are out of scope; generator outages, alone or with a line, are
+    ``dc_generator_contingency_screen``; the AC solve of chosen pairs is
     ``ac_n2_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "DC N-2 contingency screening"."""
     s = _screen_setup('dc_n2_contingency_screen', _FD, buses, lines, generators, B, L, G, slack_bus, pairs, rating, dict(flows=flows),
@@ -1091,6 +1111,114 @@ def dc_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
         base, res = _dc_screen(s, _DCN2, shared, P, (n_cand,), (n_cand, P), _dcn2_adjoint_lds_bytes, _DCN2_ADJOINT_LDS_FORMULA, flows)
         base, pairs_t, res, islanding = _screen_results(s, base, res, 3)
         return DcN2ContingencyResult(DcPowerFlowResult(*base), pairs_t, res[0], res[1], res[2], islanding, res[3])
+
+
+def _generator_contingency_list(rows, Gn, E):
+    """The checked list of generator contingencies as an int64 numpy array ``[P,2]`` of ``(generator, line or -1)``; None: for each
+    generator in order, ``(g,-1), (g,0), ..., (g,E-1)``."""
+    if rows is None:
+        g = np.repeat(np.arange(Gn, dtype=np.int64), E + 1)
+        k = np.tile(np.arange(-1, E, dtype=np.int64), Gn)
+        return np.stack([g, k], axis=1)
+    o = rows.detach().cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)
+    if o.size == 0:
+        raise ValueError('contingencies is empty: give at least one (generator, line or -1) row (None: every generator alone and with '
+                         'every line)')
+    if o.ndim != 2 or o.shape[1] != 2:
+        raise ValueError(f'contingencies must be a [P,2] sequence of (generator, line or -1), got shape {tuple(o.shape)}')
+    if o.dtype == np.bool_ or not np.issubdtype(o.dtype, np.integer):
+        raise ValueError(f'contingencies must hold integers (0-based generator rows and line indices), got dtype {o.dtype}')
+    o = o.astype(np.int64)
+    if o[:, 0].min() < 0 or o[:, 0].max() > Gn - 1:
+        raise ValueError(f'contingencies must name generators in 0..{Gn - 1} (0-based generator rows), got '
+                         f'{int(o[:, 0].min())}..{int(o[:, 0].max())}')
+    if o[:, 1].min() < -1 or o[:, 1].max() > E - 1:
+        raise ValueError(f'contingencies must name lines in -1..{E - 1} (0-based line indices, -1: no line out), got '
+                         f'{int(o[:, 1].min())}..{int(o[:, 1].max())}')
+    return o
+
+
+def _generator_islanding(bridges, rows):
+    """bool ``[P]``: the rows ``(generator, line or -1)`` that disconnect the grid.  A generator outage never does, so it is the rows
+    whose line is one of ``bridges`` (bool ``[E]``, ``_bridges``)."""
+    k = rows[:, 1]
+    return bridges[np.maximum(k, 0)] & (k >= 0)
+
+
+def _pickup(pickup, generators, single):
+    """The checked pickup weights of ``generators`` ``[Bt,Gn,7]``: None (the slack picks up), or float64 ``[Gn]`` / ``[Bt,Gn]``
+    (``'pmax'``: the generators' column 1)."""
+    if pickup is None:
+        return None
+    Bt, Gn = generators.shape[0], generators.shape[1]
+    if isinstance(pickup, str):
+        if pickup != 'pmax':
+            raise ValueError(f"pickup must be None, 'pmax' or weights [{Gn}] or [{Bt},{Gn}], got {pickup!r}")
+        w = generators[:, :, 1].to(torch.float64)
+    else:
+        w = torch.as_tensor(pickup).to(torch.float64)
+        if single and w.dim() == 2 and w.shape[0] == 1:
+            w = w[0]
+    if tuple(w.shape) not in ((Gn,), (Bt, Gn)):
+        raise ValueError(f'pickup must be [{Gn}] or [{Bt},{Gn}], got {tuple(w.shape)}')
+    if not bool((torch.isfinite(w) & (w >= 0)).all()):
+        raise ValueError('pickup must be non-negative and finite')
+    return w
+
+
+def dc_generator_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, contingencies=None,
+                                    pickup=None, rating=None, flows=False):
+    """DC generator contingency screening of every grid of a batch, on the device: the exact post-outage DC flows of each row of
+    ``contingencies``, a generator out alone or with a line out as well (the combined N-1 set of a planner).  A generator outage
+    changes the injections alone: one more solve on the base factor per distinct generator of the list gives its flows, and the
+    line on top of it is the rank-1 update ``dc_contingency_screen`` makes, from one more solve per distinct line.  Nothing is
+    factored per row, as ``dc_power_flow`` on the expanded batch (with ``mixed_topologies=True`` for the rows with a line) would.
+
+    Inputs, column maps, the slack, the device handling and ``rating`` are those of ``dc_contingency_screen``; the whole batch
+    shares one topology.  ``contingencies``: a ``[P,2]`` integer tensor, array or sequence of ``(generator, line)``, 0-based
+    generator rows and line indices, line -1 for "no line out"; default, for each generator in order, ``(g,-1), (g,0), ...,
+    (g,E-1)`` (``Gn (E + 1)`` rows).  Duplicates are independent rows.
+
+    The outaged generator's ``Pg`` leaves its bus.  ``pickup`` says who replaces it: None, the slack (what ``dcpf`` does with a unit
+    whose ``Pg`` is set to 0); ``'pmax'``, the other generators in proportion to their column 1; or weights ``[Gn]`` / ``[Bt,Gn]``,
+    non-negative and finite, used in float64: generator ``h != g`` gains ``Pg_g w_h / W_g`` with ``W_g`` the sum of the others'
+    weights, and when that sum is exactly zero the slack picks up.  No Pmax or Pmin limit is enforced on the units that pick up.
+
+    Returns ``DcGeneratorContingencyResult(base, contingencies, line_flow, worst_loading, worst_line, islanding, converged)``:
+      base           the ``DcPowerFlowResult`` of ``dc_power_flow`` on the same inputs, bit for bit
+      contingencies  ``[P,2]`` int64, as given
+      line_flow      None by default; with ``flows=True`` ``[Bt,P,E]`` float64, the flows with the generator (and the line) out, 0 at
+                     the outaged line
+      worst_loading  ``[Bt,P]`` float64, ``max_l |line_flow| / rating``;  worst_line ``[Bt,P]`` int32, the line that attains it (the
+                     lowest of equals)
+      islanding      ``[P]`` bool: the row's line is a bridge of the topology (found on the host and kept with the topology, never
+                     from a numeric threshold); a generator outage alone never islands.  Those rows are NaN / -1 in every grid.
+      converged      ``[Bt]`` bool, the base solve's.  A grid whose base solve fails has NaN / -1 in every row; a row whose update
+                     is not finite has NaN / -1 alone.
+    Every ``(grid, row)`` is bit-identical alone, in any batch, in any list or order that holds it, and from run to run.  Where
+    ``Pg_g`` is exactly 0, or the generator sits on the slack bus and ``pickup`` is None, row ``(g,-1)`` is ``base.line_flow`` and row
+    ``(g,k)`` is row ``k`` of ``dc_contingency_screen``, bit for bit.  With a 2-D single grid the batch dimension is dropped.
+
+    The outputs are not differentiable (the call runs as under ``torch.no_grad()``).  Mixed topologies, limits on the pickup, a
+    generator with two lines and the AC counterpart (an outage can turn a PV bus into a PQ bus) are out of scope.
+    Contract: ``include/gns_powerflow.h``, "DC generator contingency screening"."""
+    s = _screen_setup('dc_generator_contingency_screen', _FD, buses, lines, generators, B, L, G, slack_bus, contingencies, rating,
+                      dict(flows=flows), False, pickup=pickup)
+    with torch.set_grad_enabled(s.grad):
+        # the distinct lines and generators of the list, ascending, and each row as two positions into them (-1: no line)
+        P = s.rows.shape[0]
+        gen_np, gen_col = np.unique(s.rows[:, 0], return_inverse=True)
+        k = s.rows[:, 1]
+        line_np = np.unique(k[k >= 0])
+        cols_np = np.stack([gen_col.reshape(P), np.where(k >= 0, np.searchsorted(line_np, k), -1)], axis=1)
+        lists = _shared_args(s, _upload32(line_np, s.dev), _upload32(gen_np, s.dev), _upload32(cols_np, s.dev))
+
+        def shared():
+            return (*lists(), _ptr(s.pickup), int(s.pickup is not None and s.pickup.dim() == 2))
+
+        base, res = _dc_screen(s, _DCG1, shared, P, (line_np.size, gen_np.size), None, None, None, flows)
+        base, rows_t, res, islanding = _screen_results(s, base, res, 3)
+        return DcGeneratorContingencyResult(DcPowerFlowResult(*base), rows_t, res[0], res[1], res[2], islanding, res[3])
 
 
 class _ACN1Function(torch.autograd.Function):

@@ -12,7 +12,8 @@ outage).  Measured worst scaled error (and islanding lines / lines) of the famil
 lattice8x8 2.1e-14 (0/112), lattice16x16 9.7e-14 (0/480), random24_stacked_gens 6.5e-15 (5/38), random40_parallel_selfloop 3.0e-15
 (7/63), random97_parallel_selfloop 1.9e-14 (21/148), ring30_slack_no_gen 3.9e-15 (0/31), and the all-bridge star65_pv, path65 and
 pair (64/64, 64/64, 1/1: nothing to compare but the islanding rows).  No family failed the probe; the remaining ones (other paths
-and stars, complete33, hub150) repeat these shapes."""
+and stars, complete33, hub150) repeat these shapes.  These grids have x > 0 and taps near 1; the 'wide' regime (x of both signs, taps
+0.5 .. 1.5, shifts within +-30 degrees) lives in ``test_dc_wide_gpu``."""
 import numpy as np
 import pytest
 import torch

@@ -16,7 +16,8 @@ default rows of the families included here:
   ring30_slack_no_gen 1.2e-14, 6.4e-3 (0/96);  lattice8x8 2.3e-14, 6.7e-2 (0/1469);
   path64 and path65 0 (63/64, 64/65: the one generator sits on the slack), path66_pv1 4.0e-14 (130/132) and hub150_70lines_70gens
   6.2e-14 (10430/10500): every line is a bridge, only the generator-alone rows are compared.
-No family failed the probe."""
+No family failed the probe.  These grids have x > 0 and taps near 1; the 'wide' regime (x of both signs, taps 0.5 .. 1.5, shifts
+within +-30 degrees) lives in ``test_dc_wide_gpu``."""
 import numpy as np
 import pytest
 import torch

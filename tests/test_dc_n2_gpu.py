@@ -15,7 +15,8 @@ error, smallest |det| and islanding / selected pairs of the families included he
   random24_stacked_gens 1.4e-14, 9.5e-3 (185/703);  random40_parallel_selfloop 1.0e-14, 3.8e-3 (422/1953);
   random97_parallel_selfloop 2.1e-14, 3.2e-3 (119/336);  ring30_slack_no_gen 2.3e-14, 9.8e-5 (211/465);
   star65_pv and path65 (2016/2016: nothing to compare but the islanding rows).
-No family failed the probe."""
+No family failed the probe.  These grids have x > 0 and taps near 1; the 'wide' regime (x of both signs, so determinants of both
+signs, taps 0.5 .. 1.5, shifts within +-30 degrees) lives in ``test_dc_wide_gpu``."""
 import numpy as np
 import pytest
 import torch

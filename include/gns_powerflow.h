@@ -623,7 +623,8 @@ int gns_dcn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  * GNS_ESIZE for a short workspace.  GNS_EINVAL wins over GNS_EUNSUPPORTED, which wins over GNS_ESIZE (a NULL workspace is looked at
  * with its size).  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.  The values of
  * pickup are the caller's to check (non-negative, finite): the kernel reads them as they are.
- * Not here: AC generator outages (an outage can turn a PV bus into a PQ bus: another analysis), the gradients of this screen, limits
+ * Gradients: gns_dcg1_adjoint, below.
+ * Not here: AC generator outages (an outage can turn a PV bus into a PQ bus: another analysis), limits
  * on the units that pick up, batches that mix topologies, a generator plus two lines. */
 int gns_dcg1_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
 int gns_dcg1_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_line, int32_t n_gen, size_t* bytes);
@@ -635,6 +636,70 @@ int gns_dcg1_screen(const gns_pf_config* cfg, const void* topo_host, const void*
                     const double* rating, int32_t rating_per_grid, const double* pickup, int32_t pickup_per_grid,
                     double* line_flow, double* worst_loading, int32_t* worst_line, uint8_t* converged,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Gradients of the DC generator screen.  gns_dcg1_adjoint takes the inputs of a gns_dcg1_screen call (the same three lists,
+ * islanding mask, rating and pickup), its outputs worst_line [Bt,n_row] and converged [Bt], and the incoming gradients of a loss
+ * of its two fp64 outputs: grad_line_flow [Bt,n_row,E] and grad_worst_loading [Bt,n_row] (each may be NULL: zero).  It writes
+ * dl/d(input) into grad_buses [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32 and dl/d(pickup) into grad_pickup
+ * [Bt,Gn] fp64 (per grid also when pickup is shared: the caller sums), each of which may be NULL (not computed; with all four NULL
+ * nothing is launched).  Every element of each non-NULL output is written (overwritten, not accumulated).  The row state is
+ * recomputed from the inputs, not kept by the forward.
+ *
+ * Method, per grid, in the notation of "DC generator contingency screening": row (g, k) is the N-1 screen's row k at the
+ * injections P + dP_g, dP_g = Pg_g c_g with c_g = -e_{m_g} + sum_{h != g} (w_h / W_g) e_{m_h} on the non-slack buses (the sum only
+ * with a pickup and W_g > 0).
+ *   G_l = grad_line_flow[l] plus, at l = worst_line, grad_worst_loading sign(F'_w) / rating_w; G_k = 0.
+ *   Row (g, -1): gFg_l = G_l.  Row (g, k): ga = sum_l G_l b_l H_k[l], v = ga / den, gFg_l = G_l for l != k and gFg_k = v;
+ *   T_k[l] += G_l alpha for l != k and T_k[k] += v alpha (the derivative of den).  Every row: gF_l += gFg_l and S_g[l] += gFg_l.
+ *   Per grid: y_0 = A^-1 sum_l gF_l b_l m_l, y_k = A^-1 sum_l b_l T_k[l] m_l per distinct line and y_g = A^-1 sum_l b_l S_g[l] m_l
+ *   per distinct generator: n_line + n_gen + 1 solves on the base factor, and the n_line + n_gen solves and the base case that
+ *   recompute the forward's state; nothing is factored or solved per row, and with grad_line_flow NULL a row is O(1) work.
+ *   w_l = gF_l - m_l^T y_0;  dl/db_l = w_l (theta_f - theta_t - shift_l) + sum_k H_k[l] (T_k[l] - m_l^T y_k)
+ *   + sum_g D_g[l] (S_g[l] - m_l^T y_g);  dl/dshift_l = -b_l w_l;  dl/dP = y_0, sent to Pd, Gs and Pg as gns_dcn1_adjoint sends it;
+ *   dl/dPg_g += c_g^T y_g for each generator of the list;  dl/dw_h = sum over the listed g != h with W_g > 0 of
+ *   (Pg_g / W_g) (y_g[m_h] - sum_{h' != g} (w_h' / W_g) y_g[m_h']), y_g = 0 at the slack bus.  The branch W_g == 0 (the slack
+ *   picks up) is not differentiated: it gives exactly 0 to the weights.
+ *
+ * Contract (gns_dcn2_adjoint's): buses cols 2, 4 (Pd, Gs); lines cols 3, 5, 6 (x, tau, shift); generators col 6 (Pg); every other
+ *   column exactly 0.  rating is a constant; a tie in the worst loading goes to the worst_line the forward reported.  A row the
+ *   forward left NaN / -1 is skipped when its incoming gradients are exactly zero or NULL, never multiplied by zero; with a
+ *   non-zero incoming gradient, or a non-finite solve, the grid's gradient rows are NaN, grad_pickup's row included.  A grid with
+ *   converged == 0 gets NaN rows when an incoming gradient of it is non-zero, zero rows otherwise.  Other grids are unaffected.
+ *   Row (g, k) contributes 0 to the own columns of line k: exactly when every contributing row of the grid holds k, else the row's
+ *   own part cancels to rounding in the shared solves.  fp64 throughout, rounded once to fp32; grad_pickup stays fp64.  No
+ *   atomics, every sum in a fixed order: a grid's gradient is bit-identical alone, in any batch and from run to run for the same
+ *   list; another order of the list may change the last bits.
+ *
+ * Kernels (gns_dcg1.hip), five launches, the shape of gns_dcn2_adjoint: the forward's factor kernel again, into the adjoint's own
+ * workspace; a row kernel, one wave per (grid, chunk of Q rows, the forward's Q), 32 E bytes of LDS, which writes a record of 4
+ * doubles per (grid, row) (alpha, v, the worst-line term, whether the row contributes and its worst line) and the chunk's partial
+ * of gF; a gather kernel, one wave per (grid, candidate), 8 E bytes of LDS, which scans the row list 64 rows at a time and sums T_k
+ * or S_g over the rows that hold its candidate in list order, lane l mod 64 owning line l; the N-2 adjoint's solve kernel
+ * (gns_dcn1_device.h), one wave per (grid, chunk of W columns: y_0, the lines, the generators) on the N-1 adjoint's LDS image and
+ * width, which also stores y_g by bus; and a reduce kernel, gns_dcn1_adjoint's sums and contract with the Pg and w terms of the
+ * generators.  LDS (gns_dcg1_adjoint_lds_bytes): max(8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W), 32 E) bytes.
+ * Workspace (gns_dcg1_adjoint_workspace_bytes): gns_dcg1_workspace_bytes' figure, plus, with n_cand = n_line + n_gen,
+ * Bt * (n_cand * E + 4 n_row + ceil(n_row / Q) * (E + 1) + E + n_cand + ceil((n_cand + 1) / W) * (N + 2 E + 1) + n_gen * N + 3 n_gen)
+ * doubles and Bt bytes, rounded up to 256 bytes.
+ *
+ * Errors, in order (gns_dcn2_adjoint's): GNS_EINVAL for what gns_dcg1_screen refuses with it, a NULL worst_line or converged, or
+ * Bt times the chunks of any kernel, or Bt * n_cand, above 2^31 - 1; then GNS_EUNSUPPORTED for an LDS image above
+ * GNS_PF_LDS_MAX_BYTES (from the workspace query too); then, when an output is asked for, GNS_EINVAL for a NULL workspace and
+ * GNS_ESIZE for a short one.  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
+ * Not here: batches that mix topologies, limits on the pickup, a generator with two lines, second derivatives. */
+int gns_dcg1_adjoint_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
+int gns_dcg1_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_line, int32_t n_gen,
+                                     int32_t n_row, size_t* bytes);
+int gns_dcg1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const int32_t* line_host, const int32_t* line_dev, int32_t n_line,
+                     const int32_t* gen_host, const int32_t* gen_dev, int32_t n_gen,
+                     const int32_t* row_cols_host, const int32_t* row_cols_dev, int32_t n_row, const uint8_t* islanding,
+                     const double* rating, int32_t rating_per_grid, const double* pickup, int32_t pickup_per_grid,
+                     const int32_t* worst_line, const uint8_t* converged,
+                     const double* grad_line_flow, const double* grad_worst_loading,
+                     float* grad_buses, float* grad_lines, float* grad_generators, double* grad_pickup,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* AC contingency screening: Newton-Raphson on every grid of a batch with each single line of a list out of service (an N-1 set),
  * with the post-outage state, the branch flows at both ends of every line and their summaries, from the base analysis alone.

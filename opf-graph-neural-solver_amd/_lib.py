@@ -135,6 +135,10 @@ def load_library():
     lib.gns_dcg1_workspace_bytes.argtypes = [pfcp, vp, i64, i32, i32, ctypes.POINTER(sz)]
     lib.gns_dcg1_screen.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp,
                                     vp, vp, sz, vp]
+    lib.gns_dcg1_adjoint_lds_bytes.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    lib.gns_dcg1_adjoint_workspace_bytes.argtypes = [pfcp, vp, i64, i32, i32, i32, ctypes.POINTER(sz)]
+    lib.gns_dcg1_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp,
+                                     vp, vp, vp, vp, vp, vp, sz, vp]
     lib.gns_acn1_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
     lib.gns_acn1_screen.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32] + [vp] * 18 + [vp, sz, vp]
     lib.gns_acn1_adjoint_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
@@ -144,7 +148,7 @@ def load_library():
     lib.gns_acn2_adjoint_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
     lib.gns_acn2_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32] + [vp] * 19 + [vp, sz, vp]
     for f in (PF_EXPORTS + FD_EXPORTS + DC_EXPORTS + DCN1_EXPORTS + DCN2_EXPORTS + DCN2_ADJOINT_EXPORTS + ACN1_EXPORTS + ACN1_ADJOINT_EXPORTS +
-              ACN2_EXPORTS + ACN2_ADJOINT_EXPORTS + DCG1_EXPORTS):
+              ACN2_EXPORTS + ACN2_ADJOINT_EXPORTS + DCG1_EXPORTS + DCG1_ADJOINT_EXPORTS):
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
               'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
@@ -190,6 +194,8 @@ ACN2_ADJOINT_EXPORTS = ('gns_acn2_adjoint_workspace_bytes', 'gns_acn2_adjoint')
 # the DC generator contingency screen's C-ABI (include/gns_powerflow.h, "DC generator contingency screening"): on the fast-decoupled
 # blob too
 DCG1_EXPORTS = ('gns_dcg1_lds_bytes', 'gns_dcg1_workspace_bytes', 'gns_dcg1_screen')
+# the gradients of the DC generator screen (include/gns_powerflow.h, "Gradients of the DC generator screen")
+DCG1_ADJOINT_EXPORTS = ('gns_dcg1_adjoint_lds_bytes', 'gns_dcg1_adjoint_workspace_bytes', 'gns_dcg1_adjoint')
 # the limits of include/gns_powerflow.h
 PF_LDS_MAX_BYTES = 163840
 PF_MAX_SLOTS = 65535

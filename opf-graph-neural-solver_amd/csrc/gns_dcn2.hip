@@ -172,7 +172,7 @@ int dcn2_check(const gns_pf_config* cfg, const void* topo_host, const int32_t* c
 //            v = M^-T ga; a record per (grid, pair) and the chunk's partial of gF, each line's sum owned by lane l mod 64
 //   gather   one wave per (grid, candidate): it scans the pair list 64 pairs at a time, takes the pairs that hold its candidate in
 //            list order and sums T'_c[l] = sum_p G_pl a_pc, plus v_r a_pc at the two outaged lines (the 2x2 terms), a line per lane
-//   solve    one wave per (grid, chunk of W columns) on the N-1 adjoint's image: column 0 is q_0 = sum_l gF_l b_l m_l, column c + 1
+//   solve    (gns_dcn1_device.h, shared with gns_dcg1_adjoint) one wave per (grid, chunk of W columns) on the N-1 adjoint's image: column 0 is q_0 = sum_l gF_l b_l m_l, column c + 1
 //            is sum_l b_l T'_c[l] m_l; lane j solves its column on the base factor, then a line per lane forms the chunk's partial
 //   reduce   gns_dcn1_adjoint_reduce_kernel: the chunks in order, the contract, every element written
 
@@ -396,139 +396,6 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcn2_adjoint_gather_kernel(con
   if (lane == 0) others_out[(size_t)g * n_cand + c] = (double)others;
 }
 
-// Lane j's own right-hand side sum_l x_l b_l m_l of the row x [E] into column uc, a few entries fetched ahead; whether any x_l is
-// not exactly zero
-__device__ __forceinline__ bool dcn2_lane_rhs(const Dcn1Image& m, const int E, const int d1, const double* x, double* uc, const int ld) {
-  for (int s = 0; s < d1; ++s) uc[s * ld] = 0.0;
-  bool has = false;
-  for (int l0 = 0; l0 < E; l0 += DCN1_PREFETCH) {
-    double xv[DCN1_PREFETCH];
-#pragma unroll
-    for (int u = 0; u < DCN1_PREFETCH; ++u) xv[u] = x[min(l0 + u, E - 1)];
-#pragma unroll
-    for (int u = 0; u < DCN1_PREFETCH; ++u) {
-      const int l = l0 + u;
-      if (l >= E || xv[u] == 0.0) continue;
-      has = true;
-      const int2 en = m.ends[l];
-      if (en.x == en.y) continue;                             // m_l = 0
-      const double y = xv[u] * m.lb[l];
-      if (en.x >= 0) uc[en.x * ld] += y;
-      if (en.y >= 0) uc[en.y * ld] -= y;
-    }
-  }
-  return has;
-}
-
-__global__ __launch_bounds__(PF_THREADS) void gns_dcn2_adjoint_solve_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
-                                                                            const float* __restrict__ lines, const float* __restrict__ gens,
-                                                                            const int32_t* __restrict__ cand, const int n_cand,
-                                                                            const uint8_t* __restrict__ conv_in,
-                                                                            const int Bt, const int W, const int nchunks,
-                                                                            const int nchunks_p, const double* __restrict__ ws,
-                                                                            const double* __restrict__ T_in,
-                                                                            const double* __restrict__ gf_part,
-                                                                            const double* __restrict__ others, double* __restrict__ gf,
-                                                                            double* __restrict__ partials) {
-  extern __shared__ double lds[];
-  const int lane = threadIdx.x;
-  const int g = blockIdx.x / nchunks, k0 = (blockIdx.x % nchunks) * W;
-  const int nk = min(W, n_cand + 1 - k0);                    // column 0 is y_0, column c + 1 candidate c
-  const int N = topo[FH_N], E = topo[FH_E], Gn = topo[FH_GN], d1 = topo[FH_DIM1], nnz1 = topo[FH_NNZLU1];
-  const int32_t* p_idx = topo + topo[FH_P_IDX];
-  const Dcn1Image m = dcn1_image(topo, lds);
-  const int ld = W + 1;
-  double* U = m.Z + d1 * ld;                                 // [d1][ld] the columns' right-hand sides, then y
-  int* o_has = reinterpret_cast<int*>(U + d1 * ld);          // [W] whether the column holds anything
-  const int np = (int)dcn1_adjoint_partial(topo);
-  double* part = partials + (size_t)blockIdx.x * np;         // [N] dl/dP, [E] dl/db, [E] sum of w, the status
-  const float* line = lines + (size_t)g * E * 7;
-  const Dcn2Workspace w = dcn2_workspace(const_cast<double*>(ws), Bt, n_cand, E);
-
-  // the pair chunks' statuses: one that is NaN makes the grid's gradient NaN
-  bool nan = false;
-  for (int q = lane; q < nchunks_p; q += PF_THREADS) nan |= gf_part[((size_t)g * nchunks_p + q) * (E + 1) + E] == DCN1_PART_NAN;
-  nan = __ballot(nan) != 0;
-  if (!conv_in[g] || w.status[g] == 0.0 ||
-      !dcn1_base_case(topo, buses + (size_t)g * N * 6, line, gens + (size_t)g * Gn * 7, m, lane)) {
-    dcn1_partial_none(part, np, nan ? DCN1_PART_NAN : DCN1_PART_UNSOLVED_ZERO);
-    return;
-  }
-  if (nan) { dcn1_partial_none(part, np, DCN1_PART_NAN); return; }
-
-  // chunk 0: gF_l, the pair chunks' partials summed in order, for lane 0's right-hand side and the pass below
-  double* gfg = gf + (size_t)g * E;
-  if (k0 == 0) {
-    for (int l = lane; l < E; l += PF_THREADS) {
-      double s = 0.0;
-      for (int q = 0; q < nchunks_p; ++q) s += gf_part[((size_t)g * nchunks_p + q) * (E + 1) + l];
-      gfg[l] = s;
-    }
-    __syncthreads();
-  }
-
-  // lane j: the right-hand side of column k0 + j and its solve on the base factor
-  const double* Tg = T_in + (size_t)g * n_cand * E;
-  bool has = false, bad = false;
-  if (lane < nk) {
-    const int col = k0 + lane;
-    double* uc = U + lane;
-    has = dcn2_lane_rhs(m, E, d1, col == 0 ? gfg : Tg + (size_t)(col - 1) * E, uc, ld);
-    if (has) {
-      dcn1_lane_solve(topo[FH_NOPS_S1], reinterpret_cast<const int2*>(topo + topo[FH_OPS_S1]), m.F, nnz1, uc, ld);
-      bool fin = true;
-      for (int s = 0; s < d1; ++s) fin &= pf_finite(uc[s * ld]);
-      bad = !fin;
-    }
-  }
-  if (lane < W) o_has[lane] = has;
-  __syncthreads();
-  if (__ballot(bad)) { dcn1_partial_none(part, np, DCN1_PART_NAN); return; }
-
-  // a line per lane over the chunk's columns in order.  Column 0: w = gF - (y0_f - y0_t), dl/db += w (theta_f - theta_t - shift), the
-  // sum of w gives dl/dshift = -b sum w.  Column c + 1: dl/db += H_c[l] (T'_c[l] - (y_f - y_t)).
-  // A pair gives nothing to its own two lines: through the shared solves that zero is reached to rounding only, so a candidate line
-  // that every contributing pair of the grid holds (an empty sum over the others) gets the exact zero.
-  const double* Hg = w.H + (size_t)g * n_cand * E;
-  for (int l = lane; l < E; l += PF_THREADS) {
-    int c = 0, hi = n_cand;                                  // the candidate of line l, if it is one: cand ascends
-    while (hi - c > 1) {
-      const int mid = (c + hi) >> 1;
-      if (cand[mid] <= l) c = mid;
-      else hi = mid;
-    }
-    if (cand[c] == l && others[(size_t)g * n_cand + c] == 0.0) {
-      part[N + l] = 0.0;
-      part[N + E + l] = 0.0;
-      continue;
-    }
-    const int2 en = m.ends[l];
-    const double thf = en.x >= 0 ? m.rhs[en.x] : 0.0, tht = en.y >= 0 ? m.rhs[en.y] : 0.0;
-    const double sh = (double)line[l * 7 + 6];
-    double d_b = 0.0, sw = 0.0;
-    for (int j = 0; j < nk; ++j) {
-      if (!o_has[j]) continue;
-      const double yf = en.x >= 0 ? U[en.x * ld + j] : 0.0, yt = en.y >= 0 ? U[en.y * ld + j] : 0.0;
-      if (k0 + j == 0) {
-        const double x = gfg[l] - (yf - yt);
-        d_b += x * ((thf - tht) - sh);
-        sw += x;
-      } else {
-        const size_t at = (size_t)(k0 + j - 1) * E + l;
-        d_b += Hg[at] * (Tg[at] - (yf - yt));
-      }
-    }
-    part[N + l] = d_b;
-    part[N + E + l] = sw;
-  }
-  // a bus per lane: dl/dP_i = y0[i], 0 at the slack
-  for (int i = lane; i < N; i += PF_THREADS) {
-    const int p = p_idx[i];
-    part[i] = k0 == 0 && p >= 0 && o_has[0] ? U[p * ld] : 0.0;
-  }
-  if (lane == 0) part[np - 1] = DCN1_PART_OK;
-}
-
 // The launch shape of the adjoint: the forward's pair chunks, the N-1 adjoint's width over n_cand + 1 columns, and the largest LDS
 // image of its kernels
 struct Dcn2AdjointShape {
@@ -659,7 +526,8 @@ extern "C" int gns_dcn2_adjoint(const gns_pf_config* cfg, const void* topo_host,
   rl = pf_launch<gns_dcn2_adjoint_gather_kernel>(Bt * n_cand, 8 * (int64_t)E, stream, cand_dev, (int)n_cand, pair_cols_dev, (int)n_pair,
                                                  converged, grad_line_flow, E, (int)Bt, (const double*)ws, (const double*)a.rec, a.T, a.others);
   if (rl != GNS_OK) return rl;
-  rl = pf_launch<gns_dcn2_adjoint_solve_kernel>(Bt * s.chunks_a, s.lds_solve, stream, topo, buses, lines, generators, cand_dev, (int)n_cand, converged,
+  rl = pf_launch<gns_dcn2_adjoint_solve_kernel>(Bt * s.chunks_a, s.lds_solve, stream, topo, buses, lines, generators, cand_dev, (int)n_cand, (int)n_cand,
+                                                (double*)nullptr, converged,
                                                 (int)Bt, s.lanes, (int)s.chunks_a, (int)s.chunks_p, (const double*)ws, (const double*)a.T,
                                                 (const double*)a.gf_part, (const double*)a.others, a.gf, a.part);
   if (rl != GNS_OK) return rl;

@@ -33,6 +33,8 @@ the DC matrix, so the single-outage solves (one per distinct line of the list) a
 ``dc_generator_contingency_screen(...)`` screens a batch against a list of generator outages, each alone or with a line out as well
 (the combined N-1 set): a generator outage changes the injections alone, so it is one more solve on the base factor per distinct
 generator, and the line on top of it is the single-outage update again (``csrc/gns_dcg1.hip``).
+``dc_generator_contingency_screen_differentiable(...)`` is the same call with a backward on the device (``gns_dcg1_adjoint``), the
+pickup weights included.
 
 ``ac_contingency_screen(...)`` is the AC answer to the same question: Newton-Raphson on every ``(grid, outage)`` pair, warm-started
 from the base solution, on the base topology's analysis alone (an outage only removes Jacobian entries), with the post-outage
@@ -180,6 +182,12 @@ _DCN1_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) 
 _DCN2_ADJOINT_LDS_FORMULA = ("max(8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W), 32 E) bytes per workgroup: the DC N-1 adjoint's image "
                              "(the screen's image and a second array of W right-hand sides) for the solves on the base factor, or "
                              "four doubles per line for the pair kernel, here with W = 1, the narrowest")
+
+
+_DCG1_ADJOINT_LDS_FORMULA = ("max(8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W), 32 E) bytes per workgroup: the DC N-1 adjoint's image "
+                             "(the screen's image and a second array of W right-hand sides) for the solves on the base factor (one "
+                             "column per line, per generator and one more), or four doubles per line for the row kernel, here with "
+                             "W = 1, the narrowest")
 
 
 def _analysis(solver):
@@ -768,7 +776,7 @@ def _screen_setup(name, solver, buses, lines, generators, B, L, G, slack_bus, ro
         raise ValueError(f'differentiable must be a bool, got {differentiable!r}')
     s = SimpleNamespace()
     s.grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
-                                                                for t in (buses, lines, generators))
+                                                                for t in (buses, lines, generators, pickup))
     pairs, generator = '_n2_' in name, '_generator_' in name
     with torch.no_grad():
         # the shapes first, so that a bad list or rating is refused where no device is visible too
@@ -837,11 +845,13 @@ def _screen_results(s, base, res, conv_at):
     return base, rows_t, res, islanding
 
 
-def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_bytes, adjoint_formula, flows):
+def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_bytes, adjoint_formula, flows, weights=None):
     """The DC screens after ``_screen_setup``: ``solver``'s screen launch (with its adjoint through ``_DCN1Function`` when the call is
     differentiated) and the base case.  ``shared``: ``_shared_args``'s closure; ``n_rows``: the rows per grid; ``counts`` /
     ``adjoint_counts``: what the two workspace queries take after Bt; ``adjoint_lds_bytes`` / ``adjoint_formula``: the adjoint's LDS
-    query and the formula its refusal names (None for a screen without gradients: the call is then never differentiated).  Returns
+    query and the formula its refusal names (None for a screen without gradients: the call is then never differentiated);
+    ``weights``: the generator screen's pickup weights ``[Gn]`` / ``[Bt,Gn]`` float64 on the autograd graph when they take a gradient
+    (the adjoint then has a fourth output ``[Bt,Gn]`` float64 after the three inputs', through ``_DCG1Function``).  Returns
     ``(base, [line_flow, worst_loading, worst_line, converged])``."""
     lib, cfg, topo, Bt, dev = s.lib, s.cfg, s.topo, s.Bt, s.dev
     lds = lambda: _dcn1_lds_bytes(topo.host)[0]                              # noqa: E731
@@ -865,22 +875,27 @@ def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_by
         return flow, worst, worst_line, conv
 
     def adjoint(bu, li, ge, worst_line, conv, incoming, need):
-        gb, gl, gg = (torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need))
+        gin = [torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need)]
+        if len(need) == 4:                                   # the generator screen: dl/d(pickup), float64, a row per grid
+            gin.append(torch.empty(Bt, ge.shape[1], dtype=torch.float64, device=dev) if need[3] else None)
         gflow, gworst = (None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming)
         ws = _gns._workspace(adjoint_workspace_bytes(), dev)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
             _check(getattr(lib, adjoint_name)(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
                                               li.data_ptr(), ge.data_ptr(), Bt, *shared(), worst_line.data_ptr(), conv.data_ptr(),
-                                              _ptr(gflow), _ptr(gworst), _ptr(gb), _ptr(gl), _ptr(gg), ws.data_ptr(), ws.numel(),
+                                              _ptr(gflow), _ptr(gworst), *map(_ptr, gin), ws.data_ptr(), ws.numel(),
                                               stream), adjoint_name, adjoint_lds, adjoint_formula)
-        return [gb, gl, gg]
+        return gin
 
     base_target = _one_topology(topo)._replace(lds=_dc_lds_bytes(topo.host))
     if s.grad:
         # the backward's own refusal (its LDS image is the largest of the call) comes before anything is launched
         adjoint_workspace_bytes()
-        res = _DCN1Function.apply(screen, adjoint, s.buses, s.lines, s.generators)
+        if solver is _DCG1:
+            res = _DCG1Function.apply(screen, adjoint, s.buses, s.lines, s.generators, weights)
+        else:
+            res = _DCN1Function.apply(screen, adjoint, s.buses, s.lines, s.generators)
         base = list(_DCFunction.apply(lambda *a: _dc_solve(lib, cfg, base_target, *a),
                                       lambda *a: _dc_adjoint(lib, cfg, base_target, *a), s.buses, s.lines, s.generators))
     else:
@@ -935,6 +950,31 @@ class _DCN1Function(torch.autograd.Function):
         buses, lines, gens, worst_line, conv = ctx.saved_tensors
         grads = ctx.adjoint(buses, lines, gens, worst_line, conv, (gfl, gwl), ctx.needs_input_grad[2:5])
         return (None, None, *grads)
+
+
+class _DCG1Function(torch.autograd.Function):
+    """``dc_generator_contingency_screen_differentiable`` when an input or the pickup weights require grad, as ``_DCN1Function``: the
+    backward is one ``gns_dcg1_adjoint`` call.  ``weights`` (None, ``[Gn]`` or ``[Bt,Gn]`` float64) is on the graph for its gradient
+    alone: the kernels read the values the forward uploaded.  A ``[Gn]`` tensor gets the sum over the grids."""
+
+    @staticmethod
+    def forward(ctx, screen, adjoint, buses, lines, gens, weights):
+        flow, worst, worst_line, conv = screen(buses, lines, gens)
+        ctx.mark_non_differentiable(worst_line, conv)
+        ctx.set_materialize_grads(False)
+        ctx.adjoint = adjoint
+        ctx.shared_weights = weights is not None and weights.dim() == 1
+        ctx.save_for_backward(buses, lines, gens, worst_line, conv)
+        return flow, worst, worst_line, conv
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gfl, gwl, _gwi, _gconv):
+        buses, lines, gens, worst_line, conv = ctx.saved_tensors
+        gb, gl, gg, gp = ctx.adjoint(buses, lines, gens, worst_line, conv, (gfl, gwl), ctx.needs_input_grad[2:6])
+        if gp is not None and ctx.shared_weights:
+            gp = gp.sum(dim=0)
+        return (None, None, gb, gl, gg, gp)
 
 
 def dc_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, outages=None, rating=None,
@@ -1199,11 +1239,23 @@ def dc_generator_contingency_screen(buses, lines, generators, B=None, L=None, G=
     ``Pg_g`` is exactly 0, or the generator sits on the slack bus and ``pickup`` is None, row ``(g,-1)`` is ``base.line_flow`` and row
     ``(g,k)`` is row ``k`` of ``dc_contingency_screen``, bit for bit.  With a 2-D single grid the batch dimension is dropped.
 
-    The outputs are not differentiable (the call runs as under ``torch.no_grad()``).  Mixed topologies, limits on the pickup, a
+    The outputs are not differentiable (the call runs as under ``torch.no_grad()``, whatever requires grad): the same call with a
+    backward on the device is ``dc_generator_contingency_screen_differentiable``.  Mixed topologies, limits on the pickup, a
     generator with two lines and the AC counterpart (an outage can turn a PV bus into a PQ bus) are out of scope.
     Contract: ``include/gns_powerflow.h``, "DC generator contingency screening"."""
+    return _dc_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, flows, False)
+
+
+def _dcg1_adjoint_lds_bytes(host):
+    """``(LDS image, W)`` of the generator screen's adjoint (``gns_dcg1_adjoint_lds_bytes``) on the FD blob ``host``, as
+    ``_dcn2_adjoint_lds_bytes``."""
+    return _screen_lds_bytes('gns_dcg1_adjoint_lds_bytes', host)
+
+
+def _dc_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, flows, differentiable):
+    """``dc_generator_contingency_screen`` and its differentiable twin: one set-up, one launch."""
     s = _screen_setup('dc_generator_contingency_screen', _FD, buses, lines, generators, B, L, G, slack_bus, contingencies, rating,
-                      dict(flows=flows), False, pickup=pickup)
+                      dict(flows=flows), differentiable, pickup=pickup)
     with torch.set_grad_enabled(s.grad):
         # the distinct lines and generators of the list, ascending, and each row as two positions into them (-1: no line)
         P = s.rows.shape[0]
@@ -1216,9 +1268,51 @@ def dc_generator_contingency_screen(buses, lines, generators, B=None, L=None, G=
         def shared():
             return (*lists(), _ptr(s.pickup), int(s.pickup is not None and s.pickup.dim() == 2))
 
-        base, res = _dc_screen(s, _DCG1, shared, P, (line_np.size, gen_np.size), None, None, None, flows)
+        # the weights as the graph sees them: column 1 of the canonical generators for 'pmax', the caller's tensor when it requires
+        # grad; anything else takes no gradient (grad_pickup is then NULL)
+        weights = None
+        if s.grad and isinstance(pickup, str):
+            weights = s.generators[:, :, 1].to(torch.float64)
+        elif s.grad and isinstance(pickup, torch.Tensor) and pickup.requires_grad:
+            weights = pickup.to(device=s.dev, dtype=torch.float64).reshape(s.pickup.shape)
+        base, res = _dc_screen(s, _DCG1, shared, P, (line_np.size, gen_np.size), (line_np.size, gen_np.size, P),
+                               _dcg1_adjoint_lds_bytes, _DCG1_ADJOINT_LDS_FORMULA, flows, weights)
         base, rows_t, res, islanding = _screen_results(s, base, res, 3)
         return DcGeneratorContingencyResult(DcPowerFlowResult(*base), rows_t, res[0], res[1], res[2], islanding, res[3])
+
+
+def dc_generator_contingency_screen_differentiable(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None,
+                                                   contingencies=None, pickup=None, rating=None, flows=False):
+    """``dc_generator_contingency_screen`` with gradients: the same arguments, the same ``DcGeneratorContingencyResult`` with every
+    forward output and ``base.*`` bit-identical to that call's, and a backward on the device, for a security-constrained loss
+    over the combined N-1 set (a unit trips, the others pick its output up) or a sensitivity study of the dispatch and the
+    participation factors.
+
+    With grad mode on and ``requires_grad`` on an input (or on a tensor ``pickup``), ``worst_loading`` (and ``line_flow`` with
+    ``flows=True``) is differentiable through one ``gns_dcg1_adjoint`` call on the forward's topology and lists: per row the
+    single-outage update again, per distinct line and per distinct generator of the list one more solve on the base factor and
+    one for the whole list; nothing is factored or solved per row, ``line_flow`` is not kept for the backward, and with
+    ``flows=False`` no ``[Bt,P,E]`` tensor is formed in either direction.  ``base.theta``, ``base.line_flow`` and ``base.slack_p``
+    are differentiable through ``dc_power_flow``'s adjoint.  Otherwise it is the plain call and returns plain tensors.
+
+    The derivative is exact with respect to ``Pd``, ``Gs``, the lines' ``x``, ``tau``, ``shift`` and the generators' ``Pg`` (the
+    outaged unit's own ``Pg`` included); every other column gets 0.  The pickup weights: with ``pickup='pmax'`` their gradient is
+    added into the generators' column 1, which joins the contract for this pickup only; a tensor ``pickup`` that requires grad
+    receives it in its own dtype, a ``[Gn]`` tensor the sum over the grids; otherwise it is not computed.  The branch in which a
+    unit's remaining weights sum to exactly zero (the slack picks up) is not differentiated: it gives the weights 0.  Row
+    ``(g,k)`` gives 0 to line ``k``'s own columns (exact when every contributing row of the grid holds ``k``, else the row's own
+    part cancels to rounding in the shared solves).  ``rating`` is a constant; a tie in the worst loading sends the gradient to
+    ``worst_line``; ``worst_line``, ``islanding``, ``converged`` and ``contingencies`` are not differentiable.
+
+    A row that is NaN / -1 (an islanding row, a non-finite update) contributes nothing when its incoming gradients are exactly
+    zero or absent (a loss that indexes ``~islanding``); otherwise, and for a grid that is not solved, the grid's gradient rows
+    (the weights' included) are NaN, zero rows for an unsolved grid whose incoming gradients are all zero.  Other grids are
+    unaffected.  A grid's gradient is bit-identical alone, in any batch and from run to run for the same list; another order of
+    the list may change its last bits.
+
+    Out of scope: mixed topologies, limits on the pickup, a generator with two lines, AC generator outages, second derivatives.
+    Contract: ``include/gns_powerflow.h``, "Gradients of the DC generator screen"."""
+    return _dc_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, flows, True)
 
 
 class _ACN1Function(torch.autograd.Function):

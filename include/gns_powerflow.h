@@ -473,7 +473,7 @@ int gns_dcn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  * Outputs: line_flow [Bt,n_pair,E] fp64, or NULL for the summaries alone (8 Bt n_pair E bytes not written); worst_loading
  * [Bt,n_pair] fp64; worst_line [Bt,n_pair] int32; converged [Bt] uint8, the base solve's.
  *
- * Kernels (gns_dcn2.hip).  Factor: one wave per (grid, chunk of W candidate lines) with the N-1 screen's prologue, LDS image and
+ * Kernels (gns_dcn2_device.h, the pair as gns_dcn2.hip's row model).  Factor: one wave per (grid, chunk of W candidate lines) with the N-1 screen's prologue, LDS image and
  * lane solve (gns_dcn1_device.h), so z_c is that screen's bit for bit; a pass with a line per lane then stores H_c[0 .. E)
  * contiguously into the workspace with a finite flag per candidate, and chunk 0 also stores F_l, b_l and the grid's status.  Its LDS
  * image and W are gns_dcn1_lds_bytes' (gns_dcn2_lds_bytes reports them).  Pair: one wave per (grid, chunk of Q consecutive pairs), F,
@@ -530,7 +530,7 @@ int gns_dcn2_screen(const gns_pf_config* cfg, const void* topo_host, const void*
  *   batch and from run to run for the same pair list, and (k, j) gives the bits of (j, k); another order of the list may change the
  *   last bits.
  *
- * Kernels (gns_dcn2.hip), five launches: the forward's factor kernel again, into the adjoint's own workspace (the pool is reused
+ * Kernels (gns_dcn2_device.h), five launches: the forward's factor kernel again, into the adjoint's own workspace (the pool is reused
  * between forward and backward, so nothing of the forward's is read); a pair kernel, one wave per (grid, chunk of Q pairs, the
  * forward's Q), 32 E bytes of LDS, which writes a record of 6 doubles per (grid, pair) (a, v, the worst-line term, whether the row
  * contributes and its worst line) and the chunk's partial of gF; a gather kernel, one wave per (grid, candidate), 8 E bytes of LDS,
@@ -603,7 +603,7 @@ int gns_dcn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  * Outputs: line_flow [Bt,n_row,E] fp64, or NULL for the summaries alone (8 Bt n_row E bytes not written); worst_loading [Bt,n_row]
  * fp64; worst_line [Bt,n_row] int32; converged [Bt] uint8, the base solve's.
  *
- * Kernels (gns_dcg1.hip), the two-kernel shape of gns_dcn2.hip.  Factor: one wave per (grid, chunk of W candidates), the candidates
+ * Kernels (gns_dcn2_device.h, the two kernels of the N-2 screen with gns_dcg1.hip's row model).  Factor: one wave per (grid, chunk of W candidates), the candidates
  * being line_list followed by gen_list (n_cand = n_line + n_gen), with the N-1 screen's prologue, LDS image and lane solve
  * (gns_dcn1_device.h): a line lane solves z_k as that screen does, bit for bit; a generator lane zeroes its column, writes dP_r (the
  * bus of a generator from the blob's by-bus generator lists) and runs the same solve program.  A pass with a line per lane then
@@ -670,12 +670,12 @@ int gns_dcg1_screen(const gns_pf_config* cfg, const void* topo_host, const void*
  *   atomics, every sum in a fixed order: a grid's gradient is bit-identical alone, in any batch and from run to run for the same
  *   list; another order of the list may change the last bits.
  *
- * Kernels (gns_dcg1.hip), five launches, the shape of gns_dcn2_adjoint: the forward's factor kernel again, into the adjoint's own
+ * Kernels (gns_dcn2_device.h and gns_dcg1.hip), five launches, those of gns_dcn2_adjoint but for the last: the forward's factor kernel again, into the adjoint's own
  * workspace; a row kernel, one wave per (grid, chunk of Q rows, the forward's Q), 32 E bytes of LDS, which writes a record of 4
  * doubles per (grid, row) (alpha, v, the worst-line term, whether the row contributes and its worst line) and the chunk's partial
  * of gF; a gather kernel, one wave per (grid, candidate), 8 E bytes of LDS, which scans the row list 64 rows at a time and sums T_k
  * or S_g over the rows that hold its candidate in list order, lane l mod 64 owning line l; the N-2 adjoint's solve kernel
- * (gns_dcn1_device.h), one wave per (grid, chunk of W columns: y_0, the lines, the generators) on the N-1 adjoint's LDS image and
+ * (gns_dcn2_device.h), one wave per (grid, chunk of W columns: y_0, the lines, the generators) on the N-1 adjoint's LDS image and
  * width, which also stores y_g by bus; and a reduce kernel, gns_dcn1_adjoint's sums and contract with the Pg and w terms of the
  * generators.  LDS (gns_dcg1_adjoint_lds_bytes): max(8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W), 32 E) bytes.
  * Workspace (gns_dcg1_adjoint_workspace_bytes): gns_dcg1_workspace_bytes' figure, plus, with n_cand = n_line + n_gen,

@@ -141,8 +141,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcn1_adjoint_kernel(const int3
       const double gw = gwl ? gwl[row] : 0.0;
       const int w = wi_in[row];
       if (gw != 0.0 && w >= 0 && w < E && w != e_k) {  // d|F'_w| / rating_w: the sign of the flow the forward found worst
-        const double fw = dcn1_flow(m, w, ld, lane, alpha);
-        gterm = gw * (fw > 0.0 ? 1.0 : fw < 0.0 ? -1.0 : 0.0) / (rt ? rt[w] : 1.0);
+        gterm = dcn1_worst_term(gw, dcn1_flow(m, w, ld, lane, alpha), rt ? rt[w] : 1.0);
         wl = w;
       }
       bool has = false;

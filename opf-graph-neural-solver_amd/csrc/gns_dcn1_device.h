@@ -1,11 +1,11 @@
 // The device helpers of the DC contingency screens that gns_dcn1.hip (single outages and their adjoint), gns_dcn2.hip (double
 // outages) and gns_dcg1.hip (generator and generator-plus-line outages) share: the LDS image of a screen workgroup, the base case of
 // a grid as gns_dc_kernel solves it, a lane's own solve of z_k on the base factor, the post-outage flow of a line and the total order
-// of the worst-loading reductions.  Every screen runs this code, so z_k and the base flows of the other screens are the single-outage
-// screen's bit for bit.  Then the workspace of the screens that run a factor kernel and a streaming row kernel.  At the end, what
-// the adjoints share: the scan for non-zero incoming gradients, the status of a chunk's partial, the kernel that reduces the
-// partials, applies the contract and writes the fp32 gradient rows (and its parts, for the generator screen's own reduce kernel),
-// and the kernel that solves the columns of gns_dcn2_adjoint and gns_dcg1_adjoint on the base factor.
+// of the worst-loading reductions.  Every screen runs this code, so z_k and the base flows of the
+// other screens are the single-outage screen's bit for bit.  At the end, what the adjoints share: the worst line's term, the scan for
+// non-zero incoming gradients, the status of a chunk's partial, and the kernel that reduces the partials, applies the contract and
+// writes the fp32 gradient rows (and its parts, for the generator screen's own reduce kernel).  What only the screens with a factor
+// kernel and a streaming row kernel share is in gns_dcn2_device.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -161,38 +161,13 @@ __device__ __forceinline__ double dcn1_flow(const Dcn1Image& m, const int l, con
   return m.lF[l] + m.lb[l] * (zf - zt) * alpha;
 }
 
-// ---- what the screens that run a factor kernel and then a streaming row kernel share (gns_dcn2.hip: double outages; gns_dcg1.hip:
-// generator and generator-plus-line outages)
-
-// The workspace of one call: H [Bt][n_cand][E], then F [Bt][E], b [Bt][E], the candidates' finite flags [Bt][n_cand] and the grids'
-// status [Bt] (1: the base case is solved), all doubles
-struct Dcn2Workspace {
-  double* H;
-  double* F;
-  double* b;
-  double* fin;
-  double* status;
-};
-
-__host__ __device__ inline Dcn2Workspace dcn2_workspace(double* ws, const int64_t Bt, const int64_t n_cand, const int64_t E) {
-  Dcn2Workspace w;
-  w.H = ws;
-  w.F = w.H + Bt * n_cand * E;
-  w.b = w.F + Bt * E;
-  w.fin = w.b + Bt * E;
-  w.status = w.fin + Bt * n_cand;
-  return w;
-}
-
-size_t dcn2_ws_bytes(const int32_t* h, int64_t Bt, int64_t n_cand) {
-  const int64_t E = h[FH_E];
-  return ((size_t)Bt * (size_t)(n_cand * E + 2 * E + n_cand + 1) * sizeof(double) + 255) & ~(size_t)255;
-}
-
-// Rows (pairs) a workgroup of the row kernel takes one after the other: from the length of the list alone
-int dcn2_pairs_per_wave(int64_t n_pair) { return n_pair >= 8192 ? 32 : 8; }
-
 // ---- what the adjoints of the screens share (gns_dcn1_adjoint, gns_dcn2_adjoint, gns_dcg1_adjoint)
+
+// What grad_worst_loading gw adds to a row's gradient at the line the forward found worst, fw its post-outage flow and rt its
+// rating: d|F'_w| / rating_w is the sign of the flow over the rating
+__device__ __forceinline__ double dcn1_worst_term(const double gw, const double fw, const double rt) {
+  return gw * (fw > 0.0 ? 1.0 : fw < 0.0 ? -1.0 : 0.0) / rt;
+}
 
 // Whether one of the rows row0 + j of the incoming gradients, j a set bit of rows, holds a value that is not exactly zero (NaN
 // counts).  The whole wave scans each row with a line per lane; the answer is the same in every lane.
@@ -313,154 +288,6 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcn1_adjoint_reduce_kernel(con
       for (int c = 0; c < 6; ++c) row[c] = 0.0f;
       row[6] = (float)dcn1_reduce_dp(part, nchunks, np, dcn1_slot_bus(gen_ptr, N, q));   // Pg
     }
-}
-
-// ---- what the adjoints of the screens with a factor kernel share (gns_dcn2_adjoint, gns_dcg1_adjoint): the solves on the base factor
-
-// Lane j's own right-hand side sum_l x_l b_l m_l of the row x [E] into column uc, a few entries fetched ahead; whether any x_l is
-// not exactly zero
-__device__ __forceinline__ bool dcn2_lane_rhs(const Dcn1Image& m, const int E, const int d1, const double* x, double* uc, const int ld) {
-  for (int s = 0; s < d1; ++s) uc[s * ld] = 0.0;
-  bool has = false;
-  for (int l0 = 0; l0 < E; l0 += DCN1_PREFETCH) {
-    double xv[DCN1_PREFETCH];
-#pragma unroll
-    for (int u = 0; u < DCN1_PREFETCH; ++u) xv[u] = x[min(l0 + u, E - 1)];
-#pragma unroll
-    for (int u = 0; u < DCN1_PREFETCH; ++u) {
-      const int l = l0 + u;
-      if (l >= E || xv[u] == 0.0) continue;
-      has = true;
-      const int2 en = m.ends[l];
-      if (en.x == en.y) continue;                             // m_l = 0
-      const double y = xv[u] * m.lb[l];
-      if (en.x >= 0) uc[en.x * ld] += y;
-      if (en.y >= 0) uc[en.y * ld] -= y;
-    }
-  }
-  return has;
-}
-
-// One wave per (grid, chunk of W columns): column 0 is y_0 from gF, column c + 1 is y_c from row c of T_in, each solved by its own
-// lane on the base factor; then a line per lane forms the chunk's partial.  The first n_own of the n_cand candidates are the lines
-// cand lists (ascending); the rest (the generator screen's generators) have rows of H and T_in like them but no own line, and their
-// y goes by bus into ycols [Bt][n_cand - n_own][N] for the reduce kernel.
-__global__ __launch_bounds__(PF_THREADS) void gns_dcn2_adjoint_solve_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
-                                                                            const float* __restrict__ lines, const float* __restrict__ gens,
-                                                                            const int32_t* __restrict__ cand, const int n_own, const int n_cand,
-                                                                            double* __restrict__ ycols,
-                                                                            const uint8_t* __restrict__ conv_in,
-                                                                            const int Bt, const int W, const int nchunks,
-                                                                            const int nchunks_p, const double* __restrict__ ws,
-                                                                            const double* __restrict__ T_in,
-                                                                            const double* __restrict__ gf_part,
-                                                                            const double* __restrict__ others, double* __restrict__ gf,
-                                                                            double* __restrict__ partials) {
-  extern __shared__ double lds[];
-  const int lane = threadIdx.x;
-  const int g = blockIdx.x / nchunks, k0 = (blockIdx.x % nchunks) * W;
-  const int nk = min(W, n_cand + 1 - k0);                    // column 0 is y_0, column c + 1 candidate c
-  const int N = topo[FH_N], E = topo[FH_E], Gn = topo[FH_GN], d1 = topo[FH_DIM1], nnz1 = topo[FH_NNZLU1];
-  const int32_t* p_idx = topo + topo[FH_P_IDX];
-  const Dcn1Image m = dcn1_image(topo, lds);
-  const int ld = W + 1;
-  double* U = m.Z + d1 * ld;                                 // [d1][ld] the columns' right-hand sides, then y
-  int* o_has = reinterpret_cast<int*>(U + d1 * ld);          // [W] whether the column holds anything
-  const int np = (int)dcn1_adjoint_partial(topo);
-  double* part = partials + (size_t)blockIdx.x * np;         // [N] dl/dP, [E] dl/db, [E] sum of w, the status
-  const float* line = lines + (size_t)g * E * 7;
-  const Dcn2Workspace w = dcn2_workspace(const_cast<double*>(ws), Bt, n_cand, E);
-
-  // the pair chunks' statuses: one that is NaN makes the grid's gradient NaN
-  bool nan = false;
-  for (int q = lane; q < nchunks_p; q += PF_THREADS) nan |= gf_part[((size_t)g * nchunks_p + q) * (E + 1) + E] == DCN1_PART_NAN;
-  nan = __ballot(nan) != 0;
-  if (!conv_in[g] || w.status[g] == 0.0 ||
-      !dcn1_base_case(topo, buses + (size_t)g * N * 6, line, gens + (size_t)g * Gn * 7, m, lane)) {
-    dcn1_partial_none(part, np, nan ? DCN1_PART_NAN : DCN1_PART_UNSOLVED_ZERO);
-    return;
-  }
-  if (nan) { dcn1_partial_none(part, np, DCN1_PART_NAN); return; }
-
-  // chunk 0: gF_l, the pair chunks' partials summed in order, for lane 0's right-hand side and the pass below
-  double* gfg = gf + (size_t)g * E;
-  if (k0 == 0) {
-    for (int l = lane; l < E; l += PF_THREADS) {
-      double s = 0.0;
-      for (int q = 0; q < nchunks_p; ++q) s += gf_part[((size_t)g * nchunks_p + q) * (E + 1) + l];
-      gfg[l] = s;
-    }
-    __syncthreads();
-  }
-
-  // lane j: the right-hand side of column k0 + j and its solve on the base factor
-  const double* Tg = T_in + (size_t)g * n_cand * E;
-  bool has = false, bad = false;
-  if (lane < nk) {
-    const int col = k0 + lane;
-    double* uc = U + lane;
-    has = dcn2_lane_rhs(m, E, d1, col == 0 ? gfg : Tg + (size_t)(col - 1) * E, uc, ld);
-    if (has) {
-      dcn1_lane_solve(topo[FH_NOPS_S1], reinterpret_cast<const int2*>(topo + topo[FH_OPS_S1]), m.F, nnz1, uc, ld);
-      bool fin = true;
-      for (int s = 0; s < d1; ++s) fin &= pf_finite(uc[s * ld]);
-      bad = !fin;
-    }
-  }
-  if (lane < W) o_has[lane] = has;
-  __syncthreads();
-  if (__ballot(bad)) { dcn1_partial_none(part, np, DCN1_PART_NAN); return; }
-
-  // a line per lane over the chunk's columns in order.  Column 0: w = gF - (y0_f - y0_t), dl/db += w (theta_f - theta_t - shift), the
-  // sum of w gives dl/dshift = -b sum w.  Column c + 1: dl/db += H_c[l] (T'_c[l] - (y_f - y_t)).
-  // A pair gives nothing to its own two lines: through the shared solves that zero is reached to rounding only, so a candidate line
-  // that every contributing pair of the grid holds (an empty sum over the others) gets the exact zero.
-  const double* Hg = w.H + (size_t)g * n_cand * E;
-  for (int l = lane; l < E; l += PF_THREADS) {
-    int c = 0, hi = n_own;                                   // the candidate of line l, if it is one: cand ascends
-    while (hi - c > 1) {
-      const int mid = (c + hi) >> 1;
-      if (cand[mid] <= l) c = mid;
-      else hi = mid;
-    }
-    if (n_own > 0 && cand[c] == l && others[(size_t)g * n_cand + c] == 0.0) {
-      part[N + l] = 0.0;
-      part[N + E + l] = 0.0;
-      continue;
-    }
-    const int2 en = m.ends[l];
-    const double thf = en.x >= 0 ? m.rhs[en.x] : 0.0, tht = en.y >= 0 ? m.rhs[en.y] : 0.0;
-    const double sh = (double)line[l * 7 + 6];
-    double d_b = 0.0, sw = 0.0;
-    for (int j = 0; j < nk; ++j) {
-      if (!o_has[j]) continue;
-      const double yf = en.x >= 0 ? U[en.x * ld + j] : 0.0, yt = en.y >= 0 ? U[en.y * ld + j] : 0.0;
-      if (k0 + j == 0) {
-        const double x = gfg[l] - (yf - yt);
-        d_b += x * ((thf - tht) - sh);
-        sw += x;
-      } else {
-        const size_t at = (size_t)(k0 + j - 1) * E + l;
-        d_b += Hg[at] * (Tg[at] - (yf - yt));
-      }
-    }
-    part[N + l] = d_b;
-    part[N + E + l] = sw;
-  }
-  // a bus per lane: dl/dP_i = y0[i], 0 at the slack
-  for (int i = lane; i < N; i += PF_THREADS) {
-    const int p = p_idx[i];
-    part[i] = k0 == 0 && p >= 0 && o_has[0] ? U[p * ld] : 0.0;
-  }
-  // the columns without an own line: y by bus, 0 at the slack and for a column that holds nothing
-  for (int j = max(n_own + 1 - k0, 0); j < nk; ++j) {
-    double* y = ycols + ((size_t)g * (n_cand - n_own) + (k0 + j - 1 - n_own)) * N;
-    for (int i = lane; i < N; i += PF_THREADS) {
-      const int p = p_idx[i];
-      y[i] = p >= 0 && o_has[j] ? U[p * ld + j] : 0.0;
-    }
-  }
-  if (lane == 0) part[np - 1] = DCN1_PART_OK;
 }
 
 }  // namespace

@@ -142,6 +142,14 @@ inline bool pf_lines_ok(const int32_t* h, const int32_t* list, int64_t n) {
   return true;
 }
 
+// Whether the n entries of list are indices below bound, ascending and distinct (the candidate lists of the N-2 and the generator
+// screen)
+inline bool dcg1_list_ok(const int32_t* list, int32_t n, int32_t bound) {
+  for (int32_t c = 0; c < n; ++c)
+    if (list[c] < 0 || list[c] >= bound || (c > 0 && list[c] <= list[c - 1])) return false;
+  return true;
+}
+
 // The chunks of `width` a list of n items is cut into; false when Bt grids of that many chunks are more workgroups than one launch
 // takes (a workgroup per (grid, chunk))
 inline bool pf_chunks(int64_t n, int64_t width, int64_t Bt, int64_t* nchunks) {

@@ -845,14 +845,15 @@ def _screen_results(s, base, res, conv_at):
     return base, rows_t, res, islanding
 
 
-def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_bytes, adjoint_formula, flows, weights=None):
+def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_bytes, adjoint_formula, flows, pickup_grad=False,
+               weights=None):
     """The DC screens after ``_screen_setup``: ``solver``'s screen launch (with its adjoint through ``_DCN1Function`` when the call is
     differentiated) and the base case.  ``shared``: ``_shared_args``'s closure; ``n_rows``: the rows per grid; ``counts`` /
     ``adjoint_counts``: what the two workspace queries take after Bt; ``adjoint_lds_bytes`` / ``adjoint_formula``: the adjoint's LDS
     query and the formula its refusal names (None for a screen without gradients: the call is then never differentiated);
-    ``weights``: the generator screen's pickup weights ``[Gn]`` / ``[Bt,Gn]`` float64 on the autograd graph when they take a gradient
-    (the adjoint then has a fourth output ``[Bt,Gn]`` float64 after the three inputs', through ``_DCG1Function``).  Returns
-    ``(base, [line_flow, worst_loading, worst_line, converged])``."""
+    ``pickup_grad``: the adjoint has a fourth output after the three inputs', the generator screen's ``grad_pickup`` ``[Bt,Gn]``
+    float64; ``weights``: the pickup weights ``[Gn]`` / ``[Bt,Gn]`` float64 on the autograd graph when they take that gradient
+    (``grad_pickup`` is NULL otherwise).  Returns ``(base, [line_flow, worst_loading, worst_line, converged])``."""
     lib, cfg, topo, Bt, dev = s.lib, s.cfg, s.topo, s.Bt, s.dev
     lds = lambda: _dcn1_lds_bytes(topo.host)[0]                              # noqa: E731
     adjoint_lds = lambda: adjoint_lds_bytes(topo.host)[0]                    # noqa: E731
@@ -876,7 +877,7 @@ def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_by
 
     def adjoint(bu, li, ge, worst_line, conv, incoming, need):
         gin = [torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need)]
-        if len(need) == 4:                                   # the generator screen: dl/d(pickup), float64, a row per grid
+        if pickup_grad:                                      # the generator screen: dl/d(pickup), float64, a row per grid
             gin.append(torch.empty(Bt, ge.shape[1], dtype=torch.float64, device=dev) if need[3] else None)
         gflow, gworst = (None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming)
         ws = _gns._workspace(adjoint_workspace_bytes(), dev)
@@ -892,10 +893,7 @@ def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_by
     if s.grad:
         # the backward's own refusal (its LDS image is the largest of the call) comes before anything is launched
         adjoint_workspace_bytes()
-        if solver is _DCG1:
-            res = _DCG1Function.apply(screen, adjoint, s.buses, s.lines, s.generators, weights)
-        else:
-            res = _DCN1Function.apply(screen, adjoint, s.buses, s.lines, s.generators)
+        res = _DCN1Function.apply(screen, adjoint, s.buses, s.lines, s.generators, weights)
         base = list(_DCFunction.apply(lambda *a: _dc_solve(lib, cfg, base_target, *a),
                                       lambda *a: _dc_adjoint(lib, cfg, base_target, *a), s.buses, s.lines, s.generators))
     else:
@@ -931,31 +929,12 @@ def _ac_screen_launch(s, solver, shared, n_rows, base_state, keep_state, flows, 
 
 
 class _DCN1Function(torch.autograd.Function):
-    """``dc_contingency_screen(differentiable=True)`` when an input requires grad, as ``_DCFunction``: the forward is the screen's
-    launch, the backward one ``gns_dcn1_adjoint`` call on the forward's topology and outage list.  ``line_flow`` is not saved: the
-    adjoint recomputes each row's state from the inputs, the forward's ``worst_line`` and ``converged``."""
-
-    @staticmethod
-    def forward(ctx, screen, adjoint, buses, lines, gens):
-        flow, worst, worst_line, conv = screen(buses, lines, gens)
-        ctx.mark_non_differentiable(worst_line, conv)
-        ctx.set_materialize_grads(False)
-        ctx.adjoint = adjoint
-        ctx.save_for_backward(buses, lines, gens, worst_line, conv)
-        return flow, worst, worst_line, conv
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gfl, gwl, _gwi, _gconv):
-        buses, lines, gens, worst_line, conv = ctx.saved_tensors
-        grads = ctx.adjoint(buses, lines, gens, worst_line, conv, (gfl, gwl), ctx.needs_input_grad[2:5])
-        return (None, None, *grads)
-
-
-class _DCG1Function(torch.autograd.Function):
-    """``dc_generator_contingency_screen_differentiable`` when an input or the pickup weights require grad, as ``_DCN1Function``: the
-    backward is one ``gns_dcg1_adjoint`` call.  ``weights`` (None, ``[Gn]`` or ``[Bt,Gn]`` float64) is on the graph for its gradient
-    alone: the kernels read the values the forward uploaded.  A ``[Gn]`` tensor gets the sum over the grids."""
+    """A DC screen's differentiable call when an input requires grad, as ``_DCFunction``: the forward is the screen's launch, the
+    backward one call of its adjoint (``gns_dcn1_adjoint``, ``gns_dcn2_adjoint``, ``gns_dcg1_adjoint``) on the forward's topology and
+    lists.  ``line_flow`` is not saved: the adjoint recomputes each row's state from the inputs, the forward's ``worst_line`` and
+    ``converged``.  ``weights`` (None, or the generator screen's pickup weights ``[Gn]`` / ``[Bt,Gn]`` float64) is on the graph for
+    its gradient alone, the adjoint's fourth output: the kernels read the values the forward uploaded.  A ``[Gn]`` tensor gets the
+    sum over the grids."""
 
     @staticmethod
     def forward(ctx, screen, adjoint, buses, lines, gens, weights):
@@ -971,7 +950,8 @@ class _DCG1Function(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gfl, gwl, _gwi, _gconv):
         buses, lines, gens, worst_line, conv = ctx.saved_tensors
-        gb, gl, gg, gp = ctx.adjoint(buses, lines, gens, worst_line, conv, (gfl, gwl), ctx.needs_input_grad[2:6])
+        gb, gl, gg, *gp = ctx.adjoint(buses, lines, gens, worst_line, conv, (gfl, gwl), ctx.needs_input_grad[2:6])
+        gp = gp[0] if gp else None
         if gp is not None and ctx.shared_weights:
             gp = gp.sum(dim=0)
         return (None, None, gb, gl, gg, gp)
@@ -1276,7 +1256,7 @@ def _dc_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingen
         elif s.grad and isinstance(pickup, torch.Tensor) and pickup.requires_grad:
             weights = pickup.to(device=s.dev, dtype=torch.float64).reshape(s.pickup.shape)
         base, res = _dc_screen(s, _DCG1, shared, P, (line_np.size, gen_np.size), (line_np.size, gen_np.size, P),
-                               _dcg1_adjoint_lds_bytes, _DCG1_ADJOINT_LDS_FORMULA, flows, weights)
+                               _dcg1_adjoint_lds_bytes, _DCG1_ADJOINT_LDS_FORMULA, flows, True, weights)
         base, rows_t, res, islanding = _screen_results(s, base, res, 3)
         return DcGeneratorContingencyResult(DcPowerFlowResult(*base), rows_t, res[0], res[1], res[2], islanding, res[3])
 

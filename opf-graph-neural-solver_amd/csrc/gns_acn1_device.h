@@ -1,10 +1,11 @@
 // What the AC contingency screens share, gns_acn1.hip (single outages and their adjoint) and gns_acn2.hip (double outages).  Device:
-// a line's Y-bus stamps, the Y-bus view of a row (the base values but for the entries its line or lines touch, with the predicate
-// "line l is out"), an entry of the Y-bus without the view's lines, the Jacobian row on such a view, the total order of the
-// reductions, the outputs of a call with the writer of a row that is not solved, the row routine both screen kernels run after
-// their prologue (acn_solve_row: Newton-Raphson, the extremes, the flows, the worst loading) and the kernel that writes the base
-// Y-bus of every grid.  Host: the workspace query and the checks and pre-kernel launch of a screen call.  Both screens run this code,
-// so a row of the double-outage screen is computed by the single-outage screen's routine, not by a copy of it.
+// a line's Y-bus stamps, the Y-bus view of a row (AcnYbus<M>: the base values but for the entries its M lines touch, with the
+// predicate "line l is out"), an entry of the Y-bus without the view's lines, the prologue of a row (acn_view: the decision that the
+// row is solved and its view, which the forward and the adjoint kernels both call), the Jacobian row on such a view, the total order
+// of the reductions, the outputs of a call with the writer of a row that is not solved, the row routine (acn_solve_row:
+// Newton-Raphson, the extremes, the flows, the worst loading), the row kernel (gns_acn_kernel<M>: acn_view, then acn_solve_row) and
+// the kernel that writes the base Y-bus of every grid.  Host: the workspace query and a screen call (acn_screen_call<Rows>) on the
+// screen's trait.  Both screens are this code at M = 1 and M = 2.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -47,37 +48,26 @@ __device__ __forceinline__ bool acn1_line_ends(const float* line, const int e, c
   return ff == (float)(f + 1) && ft == (float)(t + 1) && f >= 0 && f < N && t >= 0 && t < N;
 }
 
-// The Y-bus of a pair: the grid's base values, but for the entries at p[0..3] (the outaged line's ff, tt, ft, tf; all one entry for
-// a line from a bus to itself), which read y[0..3].  The same in every lane.
-struct Acn1Ybus {
+// The Y-bus of a row with M lines out: the grid's base values, but for the entries at p[0..4M-1] (ff, tt, ft, tf of the lowest
+// line, then of the next; all one entry for a line from a bus to itself), which read y[0..4M-1].  Entries two lines share (the
+// diagonal of a common bus, all four of parallel lines) appear more than once and hold the same value each time: the entry without
+// every line of the row.  The same in every lane.  out and at unroll to M and 4M compare-selects.
+template <int M>
+struct AcnYbus {
   const double2* base;
-  int k;                  // the outaged line
-  int p[4];
-  double2 y[4];
-  __device__ __forceinline__ bool out(const int l) const { return l == k; }
-  __device__ __forceinline__ double2 at(const int q) const {
-    double2 v = base[q];
-    if (q == p[0]) v = y[0];
-    if (q == p[1]) v = y[1];
-    if (q == p[2]) v = y[2];
-    if (q == p[3]) v = y[3];
-    return v;
+  int k[M];               // the outaged lines, ascending
+  int p[4 * M];
+  double2 y[4 * M];
+  __device__ __forceinline__ bool out(const int l) const {
+    bool o = l == k[0];
+#pragma unroll
+    for (int u = 1; u < M; ++u) o = o || l == k[u];
+    return o;
   }
-};
-
-// The Y-bus of a double outage: the base values, but for the entries at p[0..7] (ff, tt, ft, tf of the lower line, then of the
-// higher), which read y[0..7].  Entries the two lines share (the diagonal of a common bus, all four of parallel lines) appear more
-// than once and hold the same value each time: the entry without both lines.  The same in every lane.
-struct Acn2Ybus {
-  const double2* base;
-  int j, k;               // the outaged lines, j < k
-  int p[8];
-  double2 y[8];
-  __device__ __forceinline__ bool out(const int l) const { return l == j || l == k; }
   __device__ __forceinline__ double2 at(const int q) const {
     double2 v = base[q];
 #pragma unroll
-    for (int u = 0; u < 8; ++u)
+    for (int u = 0; u < 4 * M; ++u)
       if (q == p[u]) v = y[u];
     return v;
   }
@@ -85,7 +75,7 @@ struct Acn2Ybus {
 
 // Entry p of row i of the Y-bus without the line(s) of the view Y (Y.out): pf_ybus_row's sum over the entry's stamps in their order,
 // the outaged lines' skipped
-template <class YB>   // Acn1Ybus or Acn2Ybus
+template <class YB>   // an AcnYbus<M>
 __device__ __forceinline__ double2 acn_entry_without(const int i, const int p, const YB& Y, const int32_t* y_diag,
                                                      const int32_t* st_ptr, const int32_t* st, const float* bus, const float* line) {
   double yr = 0.0, yi = 0.0;
@@ -99,8 +89,56 @@ __device__ __forceinline__ double2 acn_entry_without(const int i, const int p, c
   return make_double2(yr, yi);
 }
 
+// The prologue of a row, once for both screens and their adjoints: the view Y of grid `base` without the M lines that row `pos` of
+// the list names, or false for a row that is not solved.  ok is what only the caller knows (no islanding row, a base solution; in
+// the adjoint a converged row); the builder refuses a line that is not one of the grid's (its index, or its id columns against the
+// blob's pattern) and, of a pair, twice the same line.  It orders a pair itself, so (j, k) and (k, j) are the same row bit for bit.
+// line[] is read behind the index check, y_diag[] behind the ends' check, y[] filled only in a row that is solved: the lower
+// line's ff, tt, ft, tf, then the higher line's.  The same decision in every lane.
+template <int M>
+__device__ __forceinline__ bool acn_view(bool ok, const int32_t* __restrict__ topo, const float* bus, const float* line,
+                                         const int32_t* __restrict__ list, const int pos, const double2* base, AcnYbus<M>& Y) {
+  static_assert(M == 1 || M == 2, "a row names one line or a pair");
+  const int N = topo[PH_N], E = topo[PH_E];
+  const int32_t* y_ptr = topo + topo[PH_Y_PTR];
+  const int32_t* y_col = topo + topo[PH_Y_COL];
+  const int32_t* y_diag = topo + topo[PH_Y_DIAG];
+  const int32_t* st_ptr = topo + topo[PH_ST_PTR];
+  const int32_t* st = topo + topo[PH_ST];
+  Y.base = base;
+  if constexpr (M == 1) Y.k[0] = list[pos];
+  else {
+    Y.k[0] = min(list[2 * pos], list[2 * pos + 1]);
+    Y.k[1] = max(list[2 * pos], list[2 * pos + 1]);
+    ok = ok && Y.k[0] != Y.k[1];
+  }
+  ok = ok && Y.k[0] >= 0 && Y.k[M - 1] < E;
+  int f[M] = {}, t[M] = {};
+#pragma unroll
+  for (int u = 0; u < M; ++u) ok = ok && acn1_line_ends(line, Y.k[u], N, f[u], t[u]);
+  if (ok) {
+#pragma unroll
+    for (int u = 0; u < M; ++u) {
+      Y.p[4 * u] = y_diag[f[u]];
+      Y.p[4 * u + 1] = y_diag[t[u]];
+      Y.p[4 * u + 2] = acn1_find_entry(y_ptr, y_col, f[u], t[u]);
+      Y.p[4 * u + 3] = acn1_find_entry(y_ptr, y_col, t[u], f[u]);
+      ok = ok && Y.p[4 * u + 2] >= 0 && Y.p[4 * u + 3] >= 0;
+    }
+  }
+  if (!ok) return false;
+#pragma unroll
+  for (int u = 0; u < M; ++u) {
+    Y.y[4 * u] = acn_entry_without(f[u], Y.p[4 * u], Y, y_diag, st_ptr, st, bus, line);
+    Y.y[4 * u + 1] = acn_entry_without(t[u], Y.p[4 * u + 1], Y, y_diag, st_ptr, st, bus, line);
+    Y.y[4 * u + 2] = acn_entry_without(f[u], Y.p[4 * u + 2], Y, y_diag, st_ptr, st, bus, line);
+    Y.y[4 * u + 3] = acn_entry_without(t[u], Y.p[4 * u + 3], Y, y_diag, st_ptr, st, bus, line);
+  }
+  return true;
+}
+
 // Row i (not the slack) of the Jacobian into its factor slots: gns_powerflow.hip's pf_jacobian_row on the pair's Y-bus
-template <class YB>   // Acn1Ybus or Acn2Ybus
+template <class YB>   // an AcnYbus<M>
 __device__ __forceinline__ void acn1_jacobian_row(const int i, const int slack, const int32_t* y_ptr, const int32_t* y_col,
                                                   const int32_t* jslot, const YB& Y, const double* Vm, const double* Vr,
                                                   const double* Vi, const double* Ir, const double* Ii, double* F) {
@@ -189,7 +227,7 @@ __device__ __forceinline__ void acn1_row_not_solved(const Acn1Out& o, const size
 // then the state, the voltage extremes, the branch flows and the worst loading of the iterate into row `row` of o.  gns_pf_kernel's
 // loop is restated here, once for both screens, rather than shared with it: pf_solve_grid stays as it is (its comments record what
 // sharing cost).
-template <class YB>   // Acn1Ybus or Acn2Ybus
+template <class YB>   // an AcnYbus<M>
 __device__ __forceinline__ void acn_solve_row(const int32_t* __restrict__ topo, const float* bus, const float* line, const float* gen,
                                               const int g, const size_t row, const YB& Y, const double* __restrict__ rating,
                                               const int rating_per_grid, const double* __restrict__ v0,
@@ -351,6 +389,33 @@ __device__ __forceinline__ void acn_solve_row(const int32_t* __restrict__ topo, 
   }
 }
 
+// The row kernel of both screens, M lines out per row: workgroup blockIdx.x = grid * K + position in the list (M ints per row)
+template <int M>
+__global__ __launch_bounds__(PF_THREADS) void gns_acn_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
+                                                             const float* __restrict__ lines, const float* __restrict__ gens,
+                                                             const int32_t* __restrict__ list, const int K,
+                                                             const uint8_t* __restrict__ islanding,
+                                                             const double* __restrict__ rating, const int rating_per_grid,
+                                                             const double* __restrict__ v0, const double* __restrict__ th0,
+                                                             const uint8_t* __restrict__ conv0,
+                                                             const double2* __restrict__ ybus_ws, const int max_iter,
+                                                             const double tol, const Acn1Out o) {
+  const size_t row = blockIdx.x;
+  const int g = (int)(blockIdx.x / (unsigned)K), pos = (int)(blockIdx.x % (unsigned)K);
+  const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN], nnzY = topo[PH_NNZY];
+  const float* bus = buses + (size_t)g * N * 6;
+  const float* line = lines + (size_t)g * E * 7;
+  const float* gen = gens + (size_t)g * Gn * 7;
+
+  // the row's Y-bus, or a row that is not solved: an islanding row, a grid without a base solution, what acn_view refuses
+  AcnYbus<M> Y;
+  if (!acn_view(!islanding[pos] && conv0[g] != 0, topo, bus, line, list, pos, ybus_ws + (size_t)g * nnzY, Y)) {
+    acn1_row_not_solved(o, row, N, E);
+    return;
+  }
+  acn_solve_row(topo, bus, line, gen, g, row, Y, rating, rating_per_grid, v0, th0, max_iter, tol, o);
+}
+
 // The base Y-bus of every grid into the workspace: a wave per grid, a row per lane (what gns_pf_kernel writes for itself)
 __global__ __launch_bounds__(PF_THREADS) void gns_acn1_ybus_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
                                                                    const float* __restrict__ lines, double2* __restrict__ ybus_ws) {
@@ -377,33 +442,37 @@ inline int acn_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, 
   return GNS_OK;
 }
 
-// A screen call up to its own launch, in the order the codes win: the arguments, the blob's header, the list (list_ok(h): the entry
-// point's own check of its n_row outages or pairs against the blob at h), a workgroup per (grid, row) in one launch, the workspace
-// and the LDS image (pf_check_topology); then the launch of the base Y-bus of every grid into the workspace.  Returns GNS_OK with
-// the LDS image of the row kernel and the outputs as that kernel takes them.
-template <class ListOk>
-int acn_screen_begin(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev, const float* buses, const float* lines,
-                     const float* generators, int64_t Bt, const int32_t* list_host, const int32_t* list_dev, int32_t n_row,
-                     const uint8_t* islanding, int32_t rating_per_grid, const double* base_v, const double* base_theta,
-                     const uint8_t* base_converged, double* v, double* theta, double* p_from, double* q_from, double* p_to,
-                     double* q_to, double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
-                     int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch, void* workspace,
-                     size_t workspace_bytes, void* stream, ListOk list_ok, int64_t* lds, Acn1Out* out) {
+// A screen call, in the order the codes win: the arguments, the blob's header, the list (Rows::list_ok: the screen's own check of
+// its n_row outages or pairs against the blob at h), a workgroup per (grid, row) in one launch, the workspace and the LDS image
+// (pf_check_topology); then two launches: the base Y-bus of every grid into the workspace, and the row kernel at Rows::M lines out.
+// Rows is the screen's trait (Acn1Rows in gns_acn1.hip, Acn2Pairs in gns_acn2.hip): M, list_ok and the adjoint's chunk rule.
+template <class Rows>
+int acn_screen_call(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev, const float* buses, const float* lines,
+                    const float* generators, int64_t Bt, const int32_t* list_host, const int32_t* list_dev, int32_t n_row,
+                    const uint8_t* islanding, const double* rating, int32_t rating_per_grid, const double* base_v,
+                    const double* base_theta, const uint8_t* base_converged, double* v, double* theta, double* p_from,
+                    double* q_from, double* p_to, double* q_to, double* worst_loading, int32_t* worst_line, double* v_min,
+                    int32_t* v_min_bus, double* v_max, int32_t* v_max_bus, uint8_t* converged, int32_t* iterations,
+                    double* mismatch, void* workspace, size_t workspace_bytes, void* stream) {
   if (!pf_config_ok(cfg) || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF ||
       !list_host || !list_dev || n_row <= 0 || !islanding || (rating_per_grid != 0 && rating_per_grid != 1) || !base_v ||
       !base_theta || !base_converged || !worst_loading || !worst_line || !v_min || !v_min_bus || !v_max || !v_max_bus || !converged ||
       !iterations || !mismatch || !workspace)
     return GNS_EINVAL;
   const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!pf_header_ok<PfBlobKind>(cfg, h) || !list_ok(h)) return GNS_EINVAL;
-  int64_t rows = 0;
+  if (!pf_header_ok<PfBlobKind>(cfg, h) || !Rows::list_ok(h, list_host, n_row)) return GNS_EINVAL;
+  int64_t rows = 0, lds = 0;
   if (!pf_chunks(n_row, 1, Bt, &rows)) return GNS_EINVAL;
-  const int rc = pf_check_topology<PfBlobKind>(cfg, h, Bt, workspace_bytes, lds);
+  const int rc = pf_check_topology<PfBlobKind>(cfg, h, Bt, workspace_bytes, &lds);
   if (rc != GNS_OK) return rc;
-  *out = {v, theta, p_from, q_from, p_to, q_to, worst_loading, worst_line, v_min, v_min_bus, v_max, v_max_bus,
-          converged, iterations, mismatch};
-  return pf_launch<gns_acn1_ybus_kernel>(Bt, 0, stream, static_cast<const int32_t*>(topo_dev), buses, lines,
-                                         static_cast<double2*>(workspace));
+  const Acn1Out out = {v, theta, p_from, q_from, p_to, q_to, worst_loading, worst_line, v_min, v_min_bus, v_max, v_max_bus,
+                       converged, iterations, mismatch};
+  const int32_t* topo = static_cast<const int32_t*>(topo_dev);
+  const int rc0 = pf_launch<gns_acn1_ybus_kernel>(Bt, 0, stream, topo, buses, lines, static_cast<double2*>(workspace));
+  if (rc0 != GNS_OK) return rc0;
+  return pf_launch<gns_acn_kernel<Rows::M>>(Bt * n_row, lds, stream, topo, buses, lines, generators, list_dev, (int)n_row, islanding,
+                                            rating, (int)rating_per_grid, base_v, base_theta, base_converged,
+                                            static_cast<const double2*>(workspace), cfg->max_iter, cfg->tol, out);
 }
 
 }  // namespace

@@ -1,10 +1,9 @@
 // What the adjoints of the two AC contingency screens share, gns_acn1_adjoint (gns_acn1.hip) and gns_acn2_adjoint (gns_acn2.hip).
 // Device: the incoming gradients of a call, a row's effective flow cotangents and their gather to the buses, the layout and the
-// status of a (grid, chunk) partial, the routine both adjoint kernels run per solved row after their prologue (acn_adjoint_row: the
-// implicit function theorem on the grid without the row's line or lines, templated on the Y-bus view as acn_solve_row is) and the
-// kernel that sums a grid's partials.  Host: the workspace query and the checks and launches of an adjoint call around its own
-// row kernel.  Both adjoints run this code: a row of the double-outage adjoint is computed by the single-outage adjoint's routine,
-// not by a copy of it.
+// status of a (grid, chunk) partial, the routine of a solved row (acn_adjoint_row: the implicit function theorem on the grid without
+// the row's line or lines, templated on the Y-bus view as acn_solve_row is), the row kernel (gns_acn_adjoint_kernel<M>: acn_view,
+// the forward's prologue, then acn_adjoint_row, over a chunk's rows) and the kernel that sums a grid's partials.  Host: the workspace
+// query and an adjoint call (acn_adjoint_call<Rows>), on the screen's trait.  Both adjoints are this code at M = 1 and M = 2.
 #pragma once
 #include "gns_acn1_device.h"
 
@@ -47,7 +46,7 @@ __device__ __forceinline__ bool acn1_row_nonzero(const Acn1Grad& gr, const size_
 
 // The effective flow cotangents of one row: W_f = grad_p_from + j grad_q_from and W_t likewise, with what grad_worst_loading adds
 // at line w's from end (wf) or to end (wt); zero at the outaged line(s) of the row's Y-bus view.  The same in every lane.
-template <class YB>   // Acn1Ybus or Acn2Ybus
+template <class YB>   // an AcnYbus<M>
 struct Acn1Cot {
   const double* gpf;   // the row's [E] incoming gradients, NULL: zero
   const double* gqf;
@@ -129,7 +128,7 @@ __device__ __forceinline__ void acn1_partial_status(double* part, const int np, 
 // solve, and the bus, generator and line sums added into the chunk's partial `part`, every lane into the addresses it alone owns.
 // False when the row gives the grid a NaN gradient (a zero or non-finite pivot, a non-finite lambda); the same in every lane.
 // Flows and flow cotangents are skipped at every line Y.out names, and the row adds exactly 0 to those lines' own columns.
-template <class YB>   // Acn1Ybus or Acn2Ybus
+template <class YB>   // an AcnYbus<M>
 __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo, const float* line, const size_t row, const YB& Y,
                                                 const double* rt, const Acn1Grad& gr, const double* __restrict__ v_in,
                                                 const double* __restrict__ th_in, const int32_t* __restrict__ wl_in,
@@ -305,6 +304,54 @@ __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo
   return true;
 }
 
+// The row kernel of both adjoints, M lines out per row: workgroup blockIdx.x = grid * nchunks + chunk walks rows k0 .. k0 + C of the
+// grid's list in order, each lane adding into the addresses of the chunk's partial it alone owns (a bus, a line or a generator
+// slot per lane)
+template <int M>
+__global__ __launch_bounds__(PF_THREADS) void gns_acn_adjoint_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
+                                                                     const float* __restrict__ lines, const float* __restrict__ gens,
+                                                                     const int32_t* __restrict__ list, const int K,
+                                                                     const uint8_t* __restrict__ islanding,
+                                                                     const double* __restrict__ rating, const int rating_per_grid,
+                                                                     const double* __restrict__ v_in, const double* __restrict__ th_in,
+                                                                     const uint8_t* __restrict__ conv_in,
+                                                                     const int32_t* __restrict__ wl_in, const int32_t* __restrict__ lo_in,
+                                                                     const int32_t* __restrict__ hi_in,
+                                                                     const uint8_t* __restrict__ conv0, const Acn1Grad gr,
+                                                                     const double2* __restrict__ ybus_ws, const int C, const int nchunks,
+                                                                     double* __restrict__ partials) {
+  const int lane = threadIdx.x;
+  const int g = (int)(blockIdx.x / (unsigned)nchunks), k0 = (int)(blockIdx.x % (unsigned)nchunks) * C;
+  const int nk = min(C, K - k0);
+  const int N = topo[PH_N], E = topo[PH_E], nnzY = topo[PH_NNZY];
+  const float* bus = buses + (size_t)g * N * 6;
+  const float* line = lines + (size_t)g * E * 7;
+  const double* rt = rating ? rating + (rating_per_grid ? (size_t)g * E : 0) : nullptr;
+  const int np = (int)acn1_adjoint_partial(topo);
+  double* part = partials + (size_t)blockIdx.x * np;
+
+  for (int q = lane; q < np - 1; q += PF_THREADS) part[q] = 0.0;   // bus i's, line l's and slot q's doubles all sit at lane + 64 m
+  bool solved_row = false;
+
+  for (int j = 0; j < nk; ++j) {
+    const size_t row = (size_t)g * K + k0 + j;
+    // a row whose incoming gradients are all exactly zero or NULL is skipped, never multiplied by zero
+    if (!acn1_row_nonzero(gr, row, N, E)) continue;
+    // a row without a solution (no base solution, an islanding row, a stopped or unconverged iteration, what acn_view refuses): the
+    // grid's gradient is NaN.  The view is the forward's: the same builder on the same row.
+    AcnYbus<M> Y;
+    if (!acn_view(conv0[g] != 0 && conv_in[row] != 0 && !islanding[k0 + j], topo, bus, line, list, k0 + j,
+                  ybus_ws + (size_t)g * nnzY, Y) ||
+        !acn_adjoint_row(topo, line, row, Y, rt, gr, v_in, th_in, wl_in, lo_in, hi_in, part)) {
+      acn1_partial_status(part, np, ACN1_PART_NAN);
+      return;
+    }
+    solved_row = true;
+  }
+  // a grid without a base solution whose chunk asked for nothing: zero rows when every chunk says so
+  acn1_partial_status(part, np, !solved_row && conv0[g] == 0 ? ACN1_PART_UNSOLVED_ZERO : ACN1_PART_OK);
+}
+
 // A wave per grid: the chunks' partials summed in order, the contract applied, every element of the three gradient rows written
 __global__ __launch_bounds__(PF_THREADS) void gns_acn1_adjoint_reduce_kernel(const int32_t* __restrict__ topo,
                                                                              const float* __restrict__ lines, const int nchunks,
@@ -388,36 +435,38 @@ inline size_t acn1_adjoint_partial_bytes(const int32_t* h, int64_t Bt, int64_t n
   return ((size_t)Bt * nchunks * acn1_adjoint_partial(h) * sizeof(double) + 255) & ~(size_t)255;
 }
 
-// The workspace of either adjoint: the base Y-bus of every grid, then a partial per (grid, chunk of C rows of the list)
-inline int acn_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_row, int C, size_t* bytes) {
+// The workspace of either adjoint: the base Y-bus of every grid, then a partial per (grid, chunk of Rows::chunk(n_row) rows of the
+// list)
+template <class Rows>
+int acn_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_row, size_t* bytes) {
   if (!cfg || !topo_host || !bytes || Bt <= 0 || n_row <= 0) return GNS_EINVAL;
   const int32_t* h = static_cast<const int32_t*>(topo_host);
   if (!pf_header_ok<PfBlobKind>(cfg, h)) return GNS_EINVAL;
   int64_t nchunks = 0;
-  if (!pf_chunks(n_row, C, Bt, &nchunks)) return GNS_EINVAL;
+  if (!pf_chunks(n_row, Rows::chunk(n_row), Bt, &nchunks)) return GNS_EINVAL;
   if (pf_lds_bytes(h) > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
   *bytes = pf_ws_bytes_nnzy(h[PH_NNZY], Bt) + acn1_adjoint_partial_bytes(h, Bt, nchunks);
   return GNS_OK;
 }
 
-// An adjoint call around its own row kernel, in the order the codes win: the arguments, the blob's header, the list (list_ok(h): the
-// entry point's own check of its n_row outages or pairs against the blob at h), a workgroup per (grid, chunk of C rows) in one
-// launch, the LDS image; with no gradient output asked for GNS_OK without a launch; then the workspace.  Three launches: the base
-// Y-bus of every grid into the workspace, launch_rows(lds, nchunks, ybus, partials) (the entry point's row kernel, a workgroup per
-// (grid, chunk)), the sum of each grid's partials.
-template <class ListOk, class LaunchRows>
+// An adjoint call, in the order the codes win: the arguments, the blob's header, the list (Rows::list_ok, as in acn_screen_call), a
+// workgroup per (grid, chunk of C = Rows::chunk(n_row) rows) in one launch, the LDS image; with no gradient output asked for GNS_OK
+// without a launch; then the workspace.  Three launches: the base Y-bus of every grid into the workspace, the row kernel at Rows::M
+// lines out (a workgroup per (grid, chunk)), the sum of each grid's partials.
+template <class Rows>
 int acn_adjoint_call(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev, const float* buses, const float* lines,
                      const float* generators, int64_t Bt, const int32_t* list_host, const int32_t* list_dev, int32_t n_row,
-                     const uint8_t* islanding, int32_t rating_per_grid, const double* v, const double* theta, const uint8_t* converged,
-                     const int32_t* worst_line, const int32_t* v_min_bus, const int32_t* v_max_bus, const uint8_t* base_converged,
-                     float* grad_buses, float* grad_lines, float* grad_generators, void* workspace, size_t workspace_bytes,
-                     void* stream, int C, ListOk list_ok, LaunchRows launch_rows) {
+                     const uint8_t* islanding, const double* rating, int32_t rating_per_grid, const double* v, const double* theta,
+                     const uint8_t* converged, const int32_t* worst_line, const int32_t* v_min_bus, const int32_t* v_max_bus,
+                     const uint8_t* base_converged, const Acn1Grad& gr, float* grad_buses, float* grad_lines,
+                     float* grad_generators, void* workspace, size_t workspace_bytes, void* stream) {
+  const int C = Rows::chunk(n_row);
   if (!pf_config_ok(cfg) || !topo_host || !topo_dev || !buses || !lines || !generators || Bt <= 0 || Bt > 0x7FFFFFFF ||
       !list_host || !list_dev || n_row <= 0 || !islanding || (rating_per_grid != 0 && rating_per_grid != 1) || !v || !theta ||
       !converged || !worst_line || !v_min_bus || !v_max_bus || !base_converged)
     return GNS_EINVAL;
   const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!pf_header_ok<PfBlobKind>(cfg, h) || !list_ok(h)) return GNS_EINVAL;
+  if (!pf_header_ok<PfBlobKind>(cfg, h) || !Rows::list_ok(h, list_host, n_row)) return GNS_EINVAL;
   int64_t nchunks = 0;
   if (!pf_chunks(n_row, C, Bt, &nchunks)) return GNS_EINVAL;
   const int64_t lds = pf_lds_bytes(h);
@@ -431,7 +480,10 @@ int acn_adjoint_call(const gns_pf_config* cfg, const void* topo_host, const void
   double* partials = reinterpret_cast<double*>(static_cast<char*>(workspace) + ybytes);
   const int rc0 = pf_launch<gns_acn1_ybus_kernel>(Bt, 0, stream, topo, buses, lines, ybus);
   if (rc0 != GNS_OK) return rc0;
-  const int rc1 = launch_rows(lds, nchunks, (const double2*)ybus, partials);
+  const int rc1 = pf_launch<gns_acn_adjoint_kernel<Rows::M>>(Bt * nchunks, lds, stream, topo, buses, lines, generators, list_dev,
+                                                             (int)n_row, islanding, rating, (int)rating_per_grid, v, theta, converged,
+                                                             worst_line, v_min_bus, v_max_bus, base_converged, gr,
+                                                             (const double2*)ybus, C, (int)nchunks, partials);
   if (rc1 != GNS_OK) return rc1;
   return pf_launch<gns_acn1_adjoint_reduce_kernel>(Bt, 0, stream, topo, lines, (int)nchunks, (const double*)partials, grad_buses,
                                                    grad_lines, grad_generators);

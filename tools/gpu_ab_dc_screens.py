@@ -1,27 +1,38 @@
-"""Bit-for-bit A/B of the three DC contingency screens between two builds of the project on one GPU.
+"""Bit-for-bit A/B of the contingency screens between two builds of the project on one GPU: the three DC screens (``dc``) or the
+two AC screens (``ac``).
 
-dump     imports the package (and with it the library) from ROOT, runs a fixed set of seeded calls of ``dc_contingency_screen``,
-         ``dc_n2_contingency_screen`` and ``dc_generator_contingency_screen_differentiable``, each differentiable, with ``flows`` on
-         and off, and saves every returned tensor and every gradient to OUT.
+dump     imports the package (and with it the library) from ROOT, runs the fixed set of seeded calls of SET, each differentiable,
+         and saves every returned tensor and every gradient to OUT.
 compare  runs dump once per root, each in a fresh child process, and compares the two files tensor by tensor: the same shape and
          dtype, NaN at the same positions and the same bits everywhere else (so -0 and +0 differ).  One line per tensor; the exit
          status is 1 when a tensor differs.
 
-The calls: ``synth.solvable_grids(14, 3, seed=0)`` with no rating, ``[E]`` and ``[Bt,E]``; pickup None, ``'pmax'``, a ``[Gn]`` and a
-``[Bt,Gn]`` tensor that requires grad; the default lists (they hold islanding rows; the generator screen's holds rows without a
-line), lists of 1, 8, 9 and 65 rows (a chunk of Q = 8, its tail, the gather's scan of 64 rows plus one), a generator list without a
-line; one grid with a line that cannot be solved; a loss over ``worst_loading`` alone, over ``line_flow`` alone and over both; and
-case300 x 2 grids with the candidates over three chunks of the 16 lanes.
+The ``dc`` calls (``dc_contingency_screen``, ``dc_n2_contingency_screen``, ``dc_generator_contingency_screen_differentiable``, with
+``flows`` on and off): ``synth.solvable_grids(14, 3, seed=0)`` with no rating, ``[E]`` and ``[Bt,E]``; pickup None, ``'pmax'``, a
+``[Gn]`` and a ``[Bt,Gn]`` tensor that requires grad; the default lists (they hold islanding rows; the generator screen's holds rows
+without a line), lists of 1, 8, 9 and 65 rows (a chunk of Q = 8, its tail, the gather's scan of 64 rows plus one), a generator list
+without a line; one grid with a line that cannot be solved; a loss over ``worst_loading`` alone, over ``line_flow`` alone and over
+both; and case300 x 2 grids with the candidates over three chunks of the 16 lanes.
 
-usage: python tools/gpu_ab_dc_screens.py dump ROOT OUT
-       python tools/gpu_ab_dc_screens.py compare ROOT_A ROOT_B > profiles/.../ab_bitwise.txt"""
+The ``ac`` calls (``ac_contingency_screen(differentiable=True)``, ``ac_n2_contingency_screen_differentiable``): the same base batch
+with no rating, ``[E]`` and ``[Bt,E]``; ``flows`` / ``states`` both on, both off and one of each; a loss over the states alone, the
+flows alone, the summaries alone (``worst_loading``, ``v_min``, ``v_max``) and all, on the converged rows.  N-1 lists by the adjoint's
+rows per wave C = min(8, max(1, ceil(K / 32))): the default list (20 rows, C = 1, islanding rows included), 33 outages (C = 2, a tail
+chunk of 1), 257 outages with repeats (C = 8, the cap: 33 chunks, the last of 1).  N-2 lists by C = max(1, ceil(P / 64)): every pair
+(190 rows: C = 3, 64 chunks, the last of 1), 64 pairs (C = 1), 65 pairs (C = 2 with a tail), and a list that names pairs in both
+orders, pairs that share a bus and, where the topology has them, parallel lines.  One grid whose base solve fails (a NaN in a line),
+with zero and with non-zero incoming gradients into it.  case118 x 2 grids with 40 outages and 40 pairs (parallel lines among
+them), where the lane loops make a second trip (N = 118 > 64).
+
+usage: python tools/gpu_ab_dc_screens.py dump dc|ac ROOT OUT
+       python tools/gpu_ab_dc_screens.py compare dc|ac ROOT_A ROOT_B > profiles/.../ab_bitwise.txt"""
 import os
 import subprocess
 import sys
 import tempfile
 
 
-def dump(root, out_path):
+def dump(which, root, out_path):
     sys.path.insert(0, os.path.abspath(root))
     import numpy as np
     import torch
@@ -35,91 +46,177 @@ def dump(root, out_path):
         g = torch.Generator().manual_seed(seed)
         return (torch.rand(shape, generator=g, dtype=torch.float64) - 0.5).to(dev)
 
-    def run(name, call, grids, slack, flows_modes=(True, False), pickup_grad=None, **kw):
-        """One configuration: per ``flows`` and per loss a fresh forward and backward."""
-        for flows in flows_modes:
-            for loss_kind in (('worst', 'flow', 'both') if flows else ('worst',)):
-                bu, li, ge = (t.clone().requires_grad_(True) for t in grids)
-                pk = pickup_grad.clone().requires_grad_(True) if pickup_grad is not None else None
-                res = call(bu, li, ge, slack_bus=slack, flows=flows, **({'pickup': pk} if pk is not None else {}), **kw)
-                keep = ~res.islanding
-                loss = 0.0
-                if loss_kind != 'flow':
-                    wl = res.worst_loading[:, keep]
-                    loss = loss + (wl * weights(wl.shape, 11)).sum()
-                if loss_kind != 'worst':
-                    fl = res.line_flow[:, keep]
-                    loss = loss + (fl * weights(fl.shape, 12)).sum()
-                loss.backward()
-                tag = f'{name} flows={int(flows)} loss={loss_kind}'
-                if loss_kind == 'worst':
-                    out[f'{tag} worst_loading'] = res.worst_loading.detach().cpu()
-                    out[f'{tag} worst_line'] = res.worst_line.detach().cpu()
-                    out[f'{tag} converged'] = res.converged.detach().cpu()
-                    out[f'{tag} islanding'] = res.islanding.detach().cpu()
-                    if flows:
-                        out[f'{tag} line_flow'] = res.line_flow.detach().cpu()
-                for label, t in (('grad_buses', bu), ('grad_lines', li), ('grad_generators', ge), ('grad_pickup', pk)):
-                    if t is not None:
+    def dc_calls():
+        def run(name, call, grids, slack, flows_modes=(True, False), pickup_grad=None, **kw):
+            """One configuration: per ``flows`` and per loss a fresh forward and backward."""
+            for flows in flows_modes:
+                for loss_kind in (('worst', 'flow', 'both') if flows else ('worst',)):
+                    bu, li, ge = (t.clone().requires_grad_(True) for t in grids)
+                    pk = pickup_grad.clone().requires_grad_(True) if pickup_grad is not None else None
+                    res = call(bu, li, ge, slack_bus=slack, flows=flows, **({'pickup': pk} if pk is not None else {}), **kw)
+                    keep = ~res.islanding
+                    loss = 0.0
+                    if loss_kind != 'flow':
+                        wl = res.worst_loading[:, keep]
+                        loss = loss + (wl * weights(wl.shape, 11)).sum()
+                    if loss_kind != 'worst':
+                        fl = res.line_flow[:, keep]
+                        loss = loss + (fl * weights(fl.shape, 12)).sum()
+                    loss.backward()
+                    tag = f'{name} flows={int(flows)} loss={loss_kind}'
+                    if loss_kind == 'worst':
+                        out[f'{tag} worst_loading'] = res.worst_loading.detach().cpu()
+                        out[f'{tag} worst_line'] = res.worst_line.detach().cpu()
+                        out[f'{tag} converged'] = res.converged.detach().cpu()
+                        out[f'{tag} islanding'] = res.islanding.detach().cpu()
+                        if flows:
+                            out[f'{tag} line_flow'] = res.line_flow.detach().cpu()
+                    for label, t in (('grad_buses', bu), ('grad_lines', li), ('grad_generators', ge), ('grad_pickup', pk)):
+                        if t is not None:
+                            out[f'{tag} {label}'] = t.grad.detach().cpu()
+
+        def n1(bu, li, ge, **kw):
+            return powerflow.dc_contingency_screen(bu, li, ge, differentiable=True, **kw)
+
+        def n2(bu, li, ge, **kw):
+            return powerflow.dc_n2_contingency_screen(bu, li, ge, differentiable=True, **kw)
+
+        g1 = powerflow.dc_generator_contingency_screen_differentiable
+
+        buses, lines, gens, slack, _, _ = synth.solvable_grids(14, 3, seed=0, device=dev)
+        grids = (buses, lines, gens)
+        Bt, E, Gn = lines.shape[0], lines.shape[1], gens.shape[1]
+        rng = np.random.default_rng(5)
+        ratings = {'none': None, 'E': 0.5 + weights((E,), 21).abs(), 'BtE': 0.5 + weights((Bt, E), 22).abs()}
+        all_pairs = powerflow._pair_list(None, E).tolist()
+        all_rows = powerflow._generator_contingency_list(None, Gn, E).tolist()
+        for rname, rating in ratings.items():
+            run(f'case14 n1 default rating={rname}', n1, grids, slack, rating=rating)
+            run(f'case14 n2 default rating={rname}', n2, grids, slack, rating=rating)
+            run(f'case14 g1 default pmax rating={rname}', g1, grids, slack, rating=rating, pickup='pmax')
+        run('case14 g1 default pickup=None', g1, grids, slack)
+        run('case14 g1 default pickup=[Gn]', g1, grids, slack, pickup_grad=0.5 + weights((Gn,), 23).abs())
+        run('case14 g1 default pickup=[Bt,Gn]', g1, grids, slack, pickup_grad=0.5 + weights((Bt, Gn), 24).abs(), rating=ratings['BtE'])
+        run('case14 g1 no line', g1, grids, slack, contingencies=[[g, -1] for g in range(Gn)], pickup='pmax')
+        for n in (1, 8, 9, 65):
+            run(f'case14 n1 rows={n}', n1, grids, slack, outages=rng.integers(0, E, n).tolist())
+            run(f'case14 n2 rows={n}', n2, grids, slack, pairs=[all_pairs[i] for i in rng.integers(0, len(all_pairs), n)])
+            run(f'case14 g1 rows={n}', g1, grids, slack, contingencies=[all_rows[i] for i in rng.integers(0, len(all_rows), n)],
+                pickup_grad=0.5 + weights((Bt, Gn), 25).abs())
+        bad = lines.clone()
+        bad[2, 7, 3] = float('nan')                                  # grid 2 has a line that cannot be solved
+        run('case14 n1 failed grid', n1, (buses, bad, gens), slack)
+        run('case14 n2 failed grid', n2, (buses, bad, gens), slack)
+        run('case14 g1 failed grid', g1, (buses, bad, gens), slack, pickup='pmax')
+
+        # case300: 16 lanes per chunk, the candidates over three chunks
+        buses, lines, gens, slack, _, _ = synth.solvable_grids(300, 2, seed=0, device=dev)
+        grids = (buses, lines, gens)
+        E, Gn = lines.shape[1], gens.shape[1]
+        cand = rng.choice(E, 41, replace=False)
+        pairs = [[int(cand[i]), int(cand[(i + 5) % 41])] for i in range(41)] + [[int(cand[i]), int(cand[(i + 1) % 41])] for i in range(19)]
+        run('case300 n2 41 candidates', n2, grids, slack, pairs=pairs, rating=0.5 + weights((E,), 26).abs())
+        rows = [[int(g), int(k)] for g, k in zip(rng.integers(0, Gn, 60), rng.choice(E, 60, replace=False))] + [[int(g), -1] for g in range(9)]
+        run('case300 g1 60 lines', g1, grids, slack, contingencies=rows, pickup='pmax')
+        run('case300 n1 40 outages', n1, grids, slack, outages=rng.choice(E, 40, replace=False).tolist())
+
+    def ac_calls():
+        GROUPS = {'state': ('v', 'theta'), 'flow': ('p_from', 'q_from', 'p_to', 'q_to'), 'summary': ('worst_loading', 'v_min', 'v_max')}
+        FORWARD = ('v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to', 'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max',
+                   'v_max_bus', 'converged', 'iterations', 'mismatch', 'islanding')
+        ALL_MODES = ((True, True), (False, False), (True, False), (False, True))
+
+        def run(name, call, grids, slack, modes=ALL_MODES, also_grid=None, **kw):
+            """One configuration: per (``flows``, ``states``) and per loss a fresh forward and backward.  The loss weighs the
+            converged rows; with ``also_grid`` every row of that grid too (non-zero gradients into rows without a solution)."""
+            for flows, states in modes:
+                kinds = ['summary'] + (['state'] if states else []) + (['flow'] if flows else []) + (['all'] if flows and states else [])
+                for n_kind, kind in enumerate(kinds):
+                    bu, li, ge = (t.clone().requires_grad_(True) for t in grids)
+                    res = call(bu, li, ge, slack_bus=slack, flows=flows, states=states, **kw)
+                    rows = res.converged.clone()
+                    if also_grid is not None:
+                        rows[also_grid] = True
+                    loss = 0.0
+                    for group, fields in GROUPS.items():
+                        if kind in (group, 'all'):
+                            for seed, field in enumerate(fields):
+                                x = getattr(res, field)[rows]
+                                loss = loss + (x * weights(x.shape, 31 + seed)).sum()
+                    loss.backward()
+                    tag = f'{name} flows={int(flows)} states={int(states)} loss={kind}'
+                    if n_kind == 0:
+                        for field in FORWARD:
+                            if getattr(res, field) is not None:
+                                out[f'{tag} {field}'] = getattr(res, field).detach().cpu()
+                        for field in ('v', 'theta', 'converged', 'iterations'):
+                            out[f'{tag} base.{field}'] = getattr(res.base, field).detach().cpu()
+                    for label, t in (('grad_buses', bu), ('grad_lines', li), ('grad_generators', ge)):
                         out[f'{tag} {label}'] = t.grad.detach().cpu()
 
-    def n1(bu, li, ge, **kw):
-        return powerflow.dc_contingency_screen(bu, li, ge, differentiable=True, **kw)
+        def n1(bu, li, ge, **kw):
+            return powerflow.ac_contingency_screen(bu, li, ge, differentiable=True, **kw)
 
-    def n2(bu, li, ge, **kw):
-        return powerflow.dc_n2_contingency_screen(bu, li, ge, differentiable=True, **kw)
+        n2 = powerflow.ac_n2_contingency_screen_differentiable
 
-    g1 = powerflow.dc_generator_contingency_screen_differentiable
+        def special_pairs(case, E):
+            """Pairs in both orders, pairs that share a bus, every pair of parallel lines of the topology"""
+            f, t, _ = synth.case_topology(case)
+            ends = [frozenset((int(a), int(b))) for a, b in zip(f, t)]
+            share = [[j, k] for j in range(E) for k in range(j + 1, E) if len(ends[j] & ends[k]) == 1][:6]
+            parallel = [[j, k] for j in range(E) for k in range(j + 1, E) if ends[j] == ends[k]]
+            some = share[:3] + parallel + [[0, E - 1], [1, E // 2]]
+            return some + [[k, j] for j, k in some] + share[3:], len(parallel)
 
-    buses, lines, gens, slack, _, _ = synth.solvable_grids(14, 3, seed=0, device=dev)
-    grids = (buses, lines, gens)
-    Bt, E, Gn = lines.shape[0], lines.shape[1], gens.shape[1]
-    rng = np.random.default_rng(5)
-    ratings = {'none': None, 'E': 0.5 + weights((E,), 21).abs(), 'BtE': 0.5 + weights((Bt, E), 22).abs()}
-    all_pairs = powerflow._pair_list(None, E).tolist()
-    all_rows = powerflow._generator_contingency_list(None, Gn, E).tolist()
-    for rname, rating in ratings.items():
-        run(f'case14 n1 default rating={rname}', n1, grids, slack, rating=rating)
-        run(f'case14 n2 default rating={rname}', n2, grids, slack, rating=rating)
-        run(f'case14 g1 default pmax rating={rname}', g1, grids, slack, rating=rating, pickup='pmax')
-    run('case14 g1 default pickup=None', g1, grids, slack)
-    run('case14 g1 default pickup=[Gn]', g1, grids, slack, pickup_grad=0.5 + weights((Gn,), 23).abs())
-    run('case14 g1 default pickup=[Bt,Gn]', g1, grids, slack, pickup_grad=0.5 + weights((Bt, Gn), 24).abs(), rating=ratings['BtE'])
-    run('case14 g1 no line', g1, grids, slack, contingencies=[[g, -1] for g in range(Gn)], pickup='pmax')
-    for n in (1, 8, 9, 65):
-        run(f'case14 n1 rows={n}', n1, grids, slack, outages=rng.integers(0, E, n).tolist())
-        run(f'case14 n2 rows={n}', n2, grids, slack, pairs=[all_pairs[i] for i in rng.integers(0, len(all_pairs), n)])
-        run(f'case14 g1 rows={n}', g1, grids, slack, contingencies=[all_rows[i] for i in rng.integers(0, len(all_rows), n)],
-            pickup_grad=0.5 + weights((Bt, Gn), 25).abs())
-    bad = lines.clone()
-    bad[2, 7, 3] = float('nan')                                  # grid 2 has a line that cannot be solved
-    run('case14 n1 failed grid', n1, (buses, bad, gens), slack)
-    run('case14 n2 failed grid', n2, (buses, bad, gens), slack)
-    run('case14 g1 failed grid', g1, (buses, bad, gens), slack, pickup='pmax')
+        buses, lines, gens, slack, _, _ = synth.solvable_grids(14, 3, seed=0, device=dev)
+        grids = (buses, lines, gens)
+        Bt, E = lines.shape[0], lines.shape[1]
+        rng = np.random.default_rng(7)
+        ratings = {'none': None, 'E': 0.5 + weights((E,), 21).abs(), 'BtE': 0.5 + weights((Bt, E), 22).abs()}
+        all_pairs = powerflow._pair_list(None, E).tolist()
+        both = ((True, True), (False, False))
+        for rname, rating in ratings.items():
+            run(f'case14 n1 default rating={rname}', n1, grids, slack, rating=rating)
+            run(f'case14 n2 every pair rating={rname}', n2, grids, slack, rating=rating)
+        for n in (33, 257):
+            run(f'case14 n1 rows={n}', n1, grids, slack, modes=both, outages=rng.integers(0, E, n).tolist())
+        for n in (64, 65):
+            run(f'case14 n2 rows={n}', n2, grids, slack, modes=both, pairs=[all_pairs[i] for i in rng.choice(len(all_pairs), n, replace=False)])
+        special, n_parallel = special_pairs(14, E)
+        run(f'case14 n2 both orders, shared buses, {n_parallel} parallel', n2, grids, slack, modes=both, pairs=special,
+            rating=ratings['BtE'])
+        bad = lines.clone()
+        bad[2, 7, 3] = float('nan')                                  # grid 2 has no base solution
+        for name, also in (('zero gradients into it', None), ('gradients into it', 2)):
+            run(f'case14 n1 failed grid, {name}', n1, (buses, bad, gens), slack, modes=both, also_grid=also)
+            run(f'case14 n2 failed grid, {name}', n2, (buses, bad, gens), slack, modes=both, also_grid=also,
+                pairs=[all_pairs[i] for i in rng.choice(len(all_pairs), 70, replace=False)])
 
-    # case300: 16 lanes per chunk, the candidates over three chunks
-    buses, lines, gens, slack, _, _ = synth.solvable_grids(300, 2, seed=0, device=dev)
-    grids = (buses, lines, gens)
-    E, Gn = lines.shape[1], gens.shape[1]
-    cand = rng.choice(E, 41, replace=False)
-    pairs = [[int(cand[i]), int(cand[(i + 5) % 41])] for i in range(41)] + [[int(cand[i]), int(cand[(i + 1) % 41])] for i in range(19)]
-    run('case300 n2 41 candidates', n2, grids, slack, pairs=pairs, rating=0.5 + weights((E,), 26).abs())
-    rows = [[int(g), int(k)] for g, k in zip(rng.integers(0, Gn, 60), rng.choice(E, 60, replace=False))] + [[int(g), -1] for g in range(9)]
-    run('case300 g1 60 lines', g1, grids, slack, contingencies=rows, pickup='pmax')
-    run('case300 n1 40 outages', n1, grids, slack, outages=rng.choice(E, 40, replace=False).tolist())
+        # case118: two trips of the lane loops over the buses, three over the lines
+        buses, lines, gens, slack, _, _ = synth.solvable_grids(118, 2, seed=0, device=dev)
+        grids = (buses, lines, gens)
+        E = lines.shape[1]
+        special, n_parallel = special_pairs(118, E)
+        every = powerflow._pair_list(None, E)
+        pairs = special + every[rng.choice(every.shape[0], 40 - len(special), replace=False)].tolist()
+        rating = 0.5 + weights((E,), 26).abs()
+        run('case118 n1 40 outages', n1, grids, slack, modes=both, outages=rng.choice(E, 40, replace=False).tolist(), rating=rating)
+        run(f'case118 n2 40 pairs, {n_parallel} parallel', n2, grids, slack, modes=both, pairs=pairs, rating=rating)
+
+    {'dc': dc_calls, 'ac': ac_calls}[which]()
     torch.cuda.synchronize()
     torch.save(out, out_path)
-    print(f'{root}: {len(out)} tensors from {powerflow.__file__}', flush=True)
+    print(f'{root}: {len(out)} tensors of the {which} screens from {powerflow.__file__}', flush=True)
 
 
-def compare(root_a, root_b):
+def compare(which, root_a, root_b):
     import torch
 
     tmp = tempfile.mkdtemp()
     files = []
     for tag, root in (('a', root_a), ('b', root_b)):
         files.append(os.path.join(tmp, f'{tag}.pt'))
-        done = subprocess.run([sys.executable, os.path.abspath(__file__), 'dump', root, files[-1]], timeout=600)
+        done = subprocess.run([sys.executable, os.path.abspath(__file__), 'dump', which, root, files[-1]], timeout=600)
         if done.returncode != 0:
             print(f'dump of {root} ended with status {done.returncode}: nothing compared')
             return 2
@@ -150,9 +247,9 @@ def compare(root_a, root_b):
 
 
 if __name__ == '__main__':
-    if len(sys.argv) == 4 and sys.argv[1] == 'dump':
-        dump(sys.argv[2], sys.argv[3])
-    elif len(sys.argv) == 4 and sys.argv[1] == 'compare':
-        sys.exit(compare(sys.argv[2], sys.argv[3]))
+    if len(sys.argv) == 5 and sys.argv[1] == 'dump' and sys.argv[2] in ('dc', 'ac'):
+        dump(*sys.argv[2:])
+    elif len(sys.argv) == 5 and sys.argv[1] == 'compare' and sys.argv[2] in ('dc', 'ac'):
+        sys.exit(compare(*sys.argv[2:]))
     else:
         sys.exit(__doc__)

@@ -92,6 +92,20 @@ int gns_pf_topology_info(const void* topo_host, gns_pf_info* info);
 int gns_pf_topology_slots(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                           const int32_t* gen_bus, int32_t slack, int64_t* slots);
 
+/* The same analysis with generator row out_gen (0-based) out of service: the blob a row of gns_acg1_screen ("AC generator
+ * contingency screening", below) is solved on.  The row gives its bus no role (a sole unit's bus that is not the slack becomes a PQ
+ * bus and gains a |V| unknown: dim is the plain analysis' plus one exactly then) and is left off the by-bus generator lists, which
+ * hold the other Gn - 1 rows under their original numbers; the header's n_gen stays Gn, so the header checks of every entry point
+ * and the indexing of generators [Bt,Gn,7] are untouched.  The Y-bus pattern and its stamps come from the lines alone: the same
+ * words whatever out_gen is.  out_gen = -1 gives gns_pf_prepare_topology's blob byte for byte; GNS_EINVAL for an out_gen outside
+ * -1 .. n_gen-1; otherwise the arguments and errors of the three entry points above. */
+int gns_pf_topology_bytes_out_gen(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                                  const int32_t* gen_bus, int32_t slack, int32_t out_gen, size_t* bytes);
+int gns_pf_prepare_topology_out_gen(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                                    const int32_t* gen_bus, int32_t slack, int32_t out_gen, void* topo_host_out, size_t topo_bytes);
+int gns_pf_topology_slots_out_gen(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                                  const int32_t* gen_bus, int32_t slack, int32_t out_gen, int64_t* slots);
+
 /* Device workspace of a solve of Bt grids (the Y-bus values, 16 bytes per structural nonzero and grid). */
 int gns_pf_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
 
@@ -623,9 +637,8 @@ int gns_dcn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  * GNS_ESIZE for a short workspace.  GNS_EINVAL wins over GNS_EUNSUPPORTED, which wins over GNS_ESIZE (a NULL workspace is looked at
  * with its size).  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.  The values of
  * pickup are the caller's to check (non-negative, finite): the kernel reads them as they are.
- * Gradients: gns_dcg1_adjoint, below.
- * Not here: AC generator outages (an outage can turn a PV bus into a PQ bus: another analysis), limits
- * on the units that pick up, batches that mix topologies, a generator plus two lines. */
+ * Gradients: gns_dcg1_adjoint, below.  The AC screen of the same rows: gns_acg1_screen, "AC generator contingency screening" below.
+ * Not here: limits on the units that pick up, batches that mix topologies, a generator plus two lines. */
 int gns_dcg1_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes /* W; may be NULL */);
 int gns_dcg1_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_line, int32_t n_gen, size_t* bytes);
 int gns_dcg1_screen(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
@@ -728,8 +741,9 @@ int gns_dcg1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  *   whose line's id columns do not name an entry of the blob's Y-bus pattern.  Other rows are unaffected.
  *   Every (grid, outage) row is bit-identical alone, in any batch, for any outage list or order that holds the outage (duplicates
  *   are independent rows), and from run to run: no atomics, the reductions by a total order.
- *   Gradients: gns_acn1_adjoint, below.  Double outages: gns_acn2_screen, "AC N-2 contingency screening" below.  Not here: batches
- *   that mix topologies (one blob per call), generator reactive limits.
+ *   Gradients: gns_acn1_adjoint, below.  Double outages: gns_acn2_screen, "AC N-2 contingency screening" below.  Generator outages,
+ *   alone or with a line: gns_acg1_screen, "AC generator contingency screening" below.  Not here: batches that mix topologies (one
+ *   blob per call), generator reactive limits.
  *
  * Inputs: outages as 0-based line indices, on the host (checked before the launch) and on the device (read by the kernel), both
  * [n_outage] int32; islanding [n_outage] uint8 on the device; rating NULL, [E] (rating_per_grid 0) or [Bt,E] (1) fp64 on the device;
@@ -849,8 +863,8 @@ int gns_acn1_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  *   blob's Y-bus pattern (nothing is read out of bounds for it).  Other rows are unaffected.
  *   Every (grid, pair) row is bit-identical alone, in any batch, for any pair list or order that holds the pair, in either order of
  *   its two lines, and from run to run: no atomics, the reductions by a total order.
- *   Gradients: gns_acn2_adjoint, below.  Not here: batches that mix topologies (one blob per call), line plus generator outages,
- *   generator reactive limits.
+ *   Gradients: gns_acn2_adjoint, below.  A generator with one line: gns_acg1_screen, "AC generator contingency screening" below.
+ *   Not here: batches that mix topologies (one blob per call), a generator plus two lines, generator reactive limits.
  *
  * Inputs: gns_acn1_screen's, but for the list: pairs as 0-based line indices [n_pair,2] int32, on the host (checked before the
  * launch) and on the device (read by the kernel); islanding [n_pair] uint8 on the device.
@@ -923,7 +937,8 @@ int gns_acn2_screen(const gns_pf_config* cfg, const void* topo_host, const void*
  * above 2^31 - 1; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES (from the workspace query too); then, when an
  * output is asked for, GNS_EINVAL for a NULL workspace and GNS_ESIZE for a short one.  Every refusal comes before any launch;
  * nothing is allocated and the host is not synchronised.
- * Not here: batches that mix topologies, line plus generator outages, generator reactive limits, second derivatives. */
+ * Not here: batches that mix topologies, a generator plus two lines (a generator with one line: "AC generator contingency
+ * screening" below, forward only), generator reactive limits, second derivatives. */
 int gns_acn2_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_pair, size_t* bytes);
 int gns_acn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
                      const float* buses, const float* lines, const float* generators, int64_t Bt,
@@ -936,6 +951,84 @@ int gns_acn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
                      const double* grad_v_min, const double* grad_v_max,
                      float* grad_buses, float* grad_lines, float* grad_generators,
                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* AC generator contingency screening: Newton-Raphson on every grid of a batch with each generator of a list out of service, alone or
+ * with one line out as well (the combined N-1 set: a unit out plus a line out; the rows of "DC generator contingency screening"),
+ * with the outputs of "AC contingency screening" above per (grid, row).  One host analysis per distinct generator of the list, none
+ * per row or per grid.
+ *
+ * Semantics.  A row is (g, k): g a 0-based generator row, k a 0-based line or -1 for "no line out".  Row (grid, (g, k)) is
+ *   Newton-Raphson on the grid with generator row g deleted and, when k >= 0, line k out of service: what gns_pf_solve computes on
+ *   those inputs, warm-started from the base solution.  Everything not named here is gns_acn1_screen's, word for word: the
+ *   convergence test, the update, max_iter and the failure rules; the branch flows, all four exactly 0 at line k; worst_loading /
+ *   worst_line, v_min / v_max and their buses; a NaN wins its summary, the lowest index among equals; no atomics; fp64.
+ *   Bus roles: the slack stays the slack.  The bus of g stays PV when another generator is listed on it; otherwise it becomes a PQ
+ *   bus: |V| is an unknown there and the Q equation is solved with Qsp = -Qd.
+ *   Set points: |V| at a PV or slack bus is vg of the first REMAINING generator listed on it, so the outage of the first-listed unit
+ *   of a shared bus moves the set point to the next unit's vg; a slack with none left takes 1, as in gns_pf_solve.
+ *   Injections: Psp_i = (sum of Pg_h over the remaining generators h of bus i, in row order) + (sum of their pickup shares, in row
+ *   order) - Pd_i, with exactly this association.  pickup has the meaning and the arithmetic of "DC generator contingency
+ *   screening": NULL, the slack picks the lost Pg_g up and nothing is added; weights w_h >= 0 (per grid or shared), W_g the sum of
+ *   w_h over h != g in generator-row order: the share of h != g is Pg_g * (w_h / W_g) when W_g > 0, and when W_g == 0 the slack
+ *   picks up.  No Pmax or Pmin limit is enforced.  In AC the slack also takes the change of the losses, whatever the pickup.
+ *   Start: |V| at the row's PQ buses from base_v (a freed bus starts at its old set point), theta = base_theta - base_theta[slack],
+ *   |V| at PV and slack buses from the row's set points.
+ *   Islanding: a generator outage never islands; row (g, k) islands exactly when k is a bridge.  The kernel does not decide that
+ *   numerically: the caller passes islanding[n_row].  Those rows, every row of a grid with base_converged = 0, and a row whose line's
+ *   id columns do not name an entry of the Y-bus pattern get NaN in every fp64 output, -1 in worst_line, v_min_bus, v_max_bus and
+ *   iterations, and converged = 0.  Other rows are unaffected.
+ *   Every (grid, row) is bit-identical alone, in any batch, in any list or order that holds it (duplicates are independent rows),
+ *   with any of the optional outputs NULL, and from run to run.
+ *   From the definition: where Pg_g is exactly 0 and g is not the first generator listed on its bus (nor the only one), the row's
+ *   system is the base case's, so row (g, -1) starts converged at the base state with 0 iterations.
+ *
+ * The set.  The call takes one Newton-Raphson blob per distinct generator of the list, gns_pf_prepare_topology_out_gen's with
+ * out_gen = gen_list[m], in the set layout of gns_pf_solve_set: set_host / set_dev, set_words int32 words, member m at the word
+ * offset member_off[m], a multiple of 16 (64 bytes), its whole blob inside the set.  Every member has cfg's N, E, Gn and the same
+ * nnz(Y) (the pattern comes from the lines alone), and the members share ONE base Y-bus per grid in the workspace.
+ * Inputs: gns_acn1_screen's buses, lines, generators, rating, base_v, base_theta, base_converged and cfg; the set, with member_off
+ * [n_member] int32 on the host (checked before the launch) and on the device (read by the kernel); gen_list [n_member] int32,
+ * ascending and distinct, on the host and on the device; row_cols [n_row,2] int32, each row as a position into gen_list and a
+ * 0-based line or -1, on the host and on the device; islanding [n_row] uint8 on the device; pickup NULL, [Gn] (pickup_per_grid 0)
+ * or [Bt,Gn] (1) fp64 on the device, by generator row (not by position into gen_list); its values are the caller's to check
+ * (non-negative, finite).
+ * Outputs (row r = grid * n_row + position in the list): gns_acn1_screen's fifteen, shaped [Bt,n_row,...]; v, theta and the four
+ * flows may be NULL (not written).
+ *
+ * Kernels (gns_acg1.hip): gns_acn1_screen's pre-kernel writes the base Y-bus of every grid to the workspace once, from the first
+ * member's pattern; then one wave per (grid, row) with gns_pf_solve's LDS image, the launch asking for the largest member's.  The
+ * row takes its blob at set + member_off[position] after the member checks of gns_pf_solve_set's kernel (an offset that is
+ * negative, misaligned or outside the set, or a blob of another shape, nnz(Y) or a larger image: the row is not solved and nothing
+ * outside the set is indexed), builds gns_acn1_screen's Y-bus view for k >= 0 or a view with nothing out for k = -1, and runs the
+ * row routine of the AC line screens on that blob's roles, unknowns, by-bus generator lists and program, with the pickup added to
+ * the specified P.  Workspace (gns_acg1_workspace_bytes): gns_acn1_workspace_bytes' figure, the base Y-bus, 16 bytes per structural
+ * nonzero and GRID, whatever n_row and n_member are.
+ *
+ * Errors, in order: GNS_EINVAL for a NULL cfg, set, member_off, input, gen_list, row_cols, islanding mask, base_v, base_theta,
+ * base_converged, workspace or output other than v, theta and the four flows, a negative max_iter or tol, n_member <= 0 or above
+ * Gn, n_row <= 0, set_words above 2^31 - 1, a member offset that is negative, misaligned or whose blob does not lie inside the set,
+ * a member that is not a Newton-Raphson blob of cfg's N, E, Gn, members whose nnz(Y) differ, a gen_list entry outside 0 .. Gn-1 or a
+ * gen_list not ascending or not distinct, a member m whose by-bus lists are not the Gn - 1 rows without gen_list[m], a generator
+ * column outside 0 .. n_member-1, a line column outside -1 .. E-1, rating_per_grid or pickup_per_grid outside {0, 1}, or Bt or
+ * Bt * n_row above 2^31 - 1; then GNS_ESIZE for a short workspace; then GNS_EUNSUPPORTED, for the whole call, when any member's LDS
+ * image is above GNS_PF_LDS_MAX_BYTES.  gns_acg1_workspace_bytes: GNS_EINVAL for a NULL bytes, Bt <= 0, n_row <= 0 and what the
+ * call refuses of the set; it does not refuse a large image.  Every refusal comes before any launch; nothing is allocated and the
+ * host is not synchronised.
+ * Not here: an adjoint (this screen has no gradients yet), reactive limits on the remaining units, Pmax / Pmin limits on
+ * the pickup, batches that mix topologies, a generator plus two lines. */
+int gns_acg1_workspace_bytes(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
+                             int32_t n_member, int64_t Bt, int32_t n_row, size_t* bytes);
+int gns_acg1_screen(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                    const int32_t* member_off_host, const int32_t* member_off_dev, int32_t n_member,
+                    const float* buses, const float* lines, const float* generators, int64_t Bt,
+                    const int32_t* gen_host, const int32_t* gen_dev,
+                    const int32_t* row_cols_host, const int32_t* row_cols_dev, int32_t n_row, const uint8_t* islanding,
+                    const double* rating, int32_t rating_per_grid, const double* pickup, int32_t pickup_per_grid,
+                    const double* base_v, const double* base_theta, const uint8_t* base_converged,
+                    double* v, double* theta, double* p_from, double* q_from, double* p_to, double* q_to,
+                    double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
+                    int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -147,8 +147,14 @@ def load_library():
     lib.gns_acn2_screen.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32] + [vp] * 18 + [vp, sz, vp]
     lib.gns_acn2_adjoint_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
     lib.gns_acn2_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32] + [vp] * 19 + [vp, sz, vp]
+    lib.gns_pf_topology_bytes_out_gen.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, ctypes.POINTER(sz)]
+    lib.gns_pf_prepare_topology_out_gen.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, vp, sz]
+    lib.gns_pf_topology_slots_out_gen.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, ctypes.POINTER(i64)]
+    lib.gns_acg1_workspace_bytes.argtypes = [pfcp, vp, sz, vp, i32, i64, i32, ctypes.POINTER(sz)]
+    lib.gns_acg1_screen.argtypes = [pfcp, vp, vp, sz, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32] + \
+        [vp] * 18 + [vp, sz, vp]
     for f in (PF_EXPORTS + FD_EXPORTS + DC_EXPORTS + DCN1_EXPORTS + DCN2_EXPORTS + DCN2_ADJOINT_EXPORTS + ACN1_EXPORTS + ACN1_ADJOINT_EXPORTS +
-              ACN2_EXPORTS + ACN2_ADJOINT_EXPORTS + DCG1_EXPORTS + DCG1_ADJOINT_EXPORTS):
+              ACN2_EXPORTS + ACN2_ADJOINT_EXPORTS + DCG1_EXPORTS + DCG1_ADJOINT_EXPORTS + ACG1_EXPORTS):
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
               'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
@@ -169,7 +175,8 @@ EXPORTS = ('gns_version', 'gns_param_count', 'gns_config_supported', 'gns_topolo
 
 # the power-flow solver's C-ABI (include/gns_powerflow.h)
 PF_EXPORTS = ('gns_pf_topology_bytes', 'gns_pf_prepare_topology', 'gns_pf_topology_info', 'gns_pf_workspace_bytes', 'gns_pf_solve',
-              'gns_pf_workspace_bytes_set', 'gns_pf_solve_set', 'gns_pf_adjoint', 'gns_pf_adjoint_set', 'gns_pf_topology_slots')
+              'gns_pf_workspace_bytes_set', 'gns_pf_solve_set', 'gns_pf_adjoint', 'gns_pf_adjoint_set', 'gns_pf_topology_slots',
+              'gns_pf_topology_bytes_out_gen', 'gns_pf_prepare_topology_out_gen', 'gns_pf_topology_slots_out_gen')
 # the fast-decoupled solver's C-ABI (include/gns_powerflow.h, "Fast-decoupled")
 FD_EXPORTS = ('gns_fd_topology_bytes', 'gns_fd_prepare_topology', 'gns_fd_topology_info', 'gns_fd_topology_slots',
               'gns_fd_workspace_bytes', 'gns_fd_solve', 'gns_fd_workspace_bytes_set', 'gns_fd_solve_set')
@@ -196,6 +203,9 @@ ACN2_ADJOINT_EXPORTS = ('gns_acn2_adjoint_workspace_bytes', 'gns_acn2_adjoint')
 DCG1_EXPORTS = ('gns_dcg1_lds_bytes', 'gns_dcg1_workspace_bytes', 'gns_dcg1_screen')
 # the gradients of the DC generator screen (include/gns_powerflow.h, "Gradients of the DC generator screen")
 DCG1_ADJOINT_EXPORTS = ('gns_dcg1_adjoint_lds_bytes', 'gns_dcg1_adjoint_workspace_bytes', 'gns_dcg1_adjoint')
+# the AC generator contingency screen's C-ABI (include/gns_powerflow.h, "AC generator contingency screening"): on a set of
+# Newton-Raphson blobs, each the analysis without one generator row (gns_pf_prepare_topology_out_gen)
+ACG1_EXPORTS = ('gns_acg1_workspace_bytes', 'gns_acg1_screen')
 # the limits of include/gns_powerflow.h
 PF_LDS_MAX_BYTES = 163840
 PF_MAX_SLOTS = 65535

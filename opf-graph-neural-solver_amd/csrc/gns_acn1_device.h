@@ -5,9 +5,12 @@
 // of the reductions, the outputs of a call with the writer of a row that is not solved, the row routine (acn_solve_row:
 // Newton-Raphson, the extremes, the flows, the worst loading), the row kernel (gns_acn_kernel<M>: acn_view, then acn_solve_row) and
 // the kernel that writes the base Y-bus of every grid.  Host: the workspace query and a screen call (acn_screen_call<Rows>) on the
-// screen's trait.  Both screens are this code at M = 1 and M = 2.
+// screen's trait.  Both screens are this code at M = 1 and M = 2.  gns_acg1.hip (generator outages, alone or with a line) has a
+// kernel and an entry point of its own on a set of blobs and runs acn_view at M = 1 and acn_solve_row from here.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/gns_powerflow.h"
 #include "gns_pf_common.h"
@@ -226,12 +229,17 @@ __device__ __forceinline__ void acn1_row_not_solved(const Acn1Out& o, const size
 // the grid without the row's line or lines): Newton-Raphson on gns_pf_kernel's LDS image from the base solution v0, th0 of grid g,
 // then the state, the voltage extremes, the branch flows and the worst loading of the iterate into row `row` of o.  gns_pf_kernel's
 // loop is restated here, once for both screens, rather than shared with it: pf_solve_grid stays as it is (its comments record what
-// sharing cost).
-template <class YB>   // an AcnYbus<M>
+// sharing cost).  The bus roles, the unknowns, the by-bus generator lists and the program are those of the blob at topo, whichever
+// it is: the base topology's in the line screens, the analysis without the row's generator in gns_acg1.hip, whose pickup is the one
+// hook here (Extra: what a bus's specified P gains on top of its generators' Pg; AcnNoExtra compiles to nothing).
+struct AcnNoExtra {};
+
+template <class YB, class Extra = AcnNoExtra>   // an AcnYbus<M>; a functor (bus, gen_ptr, gen_idx) -> double, or AcnNoExtra
 __device__ __forceinline__ void acn_solve_row(const int32_t* __restrict__ topo, const float* bus, const float* line, const float* gen,
                                               const int g, const size_t row, const YB& Y, const double* __restrict__ rating,
                                               const int rating_per_grid, const double* __restrict__ v0,
-                                              const double* __restrict__ th0, const int max_iter, const double tol, const Acn1Out& o) {
+                                              const double* __restrict__ th0, const int max_iter, const double tol, const Acn1Out& o,
+                                              const Extra& extra = Extra()) {
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
   const int N = topo[PH_N], E = topo[PH_E], slack = topo[PH_SLACK], dim = topo[PH_DIM];
@@ -263,6 +271,7 @@ __device__ __forceinline__ void acn_solve_row(const int32_t* __restrict__ topo, 
   for (int i = lane; i < N; i += PF_THREADS) {
     double pg = 0.0;
     for (int q = gen_ptr[i]; q < gen_ptr[i + 1]; ++q) pg += (double)gen[gen_idx[q] * 7 + 6];
+    if constexpr (!std::is_same_v<Extra, AcnNoExtra>) pg += extra(i, gen_ptr, gen_idx);
     Psp[i] = pg - (double)bus[i * 6 + 2];
     Qsp[i] = -(double)bus[i * 6 + 3];
     const int ro = role[i];

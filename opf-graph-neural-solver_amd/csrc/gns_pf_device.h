@@ -2,7 +2,7 @@
 // fast-decoupled).  Device: one wave per grid, the Y-bus of a grid from its line stamps, I = Y V, the pivot test, the interpreter of
 // the blobs' op programs and the grid and member checks of a set kernel.  Host: the checks of a call's
 // arguments, of one blob and of a set of blobs, and the launch; for the contingency screens (gns_dcn1.hip, gns_dcn2.hip, gns_acn1.hip,
-// gns_acn2.hip) the check of a list of lines, the chunk count of a launch and the body of their LDS queries.
+// gns_acn2.hip, gns_acg1.hip) the check of a list of lines, the chunk count of a launch and the body of their LDS queries.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -181,8 +181,8 @@ int pf_check_topology(const gns_pf_config* shape, const int32_t* h, int64_t Bt, 
 }
 
 // Host check of the members of a set: each at an aligned word offset with its whole blob inside set_words, a blob of this kind and
-// shape.  Returns GNS_OK with the largest nnz(Y) and LDS image, GNS_EINVAL, or GNS_EUNSUPPORTED when a member's LDS image is too
-// large (GNS_EINVAL wins over it whichever member comes first).
+// shape.  Returns GNS_OK, GNS_EINVAL, or GNS_EUNSUPPORTED when a member's LDS image is too large (GNS_EINVAL wins over it whichever
+// member comes first); unless it is GNS_EINVAL the largest nnz(Y) and LDS image are written.
 template <class Kind>
 int pf_scan_set(const gns_pf_config* shape, const void* set_host, size_t set_words, const int32_t* member_off, int32_t n_member,
                 int32_t* nnzy_max, int64_t* lds_max) {
@@ -202,10 +202,9 @@ int pf_scan_set(const gns_pf_config* shape, const void* set_host, size_t set_wor
     lds = b > lds ? b : lds;
     too_big |= b > GNS_PF_LDS_MAX_BYTES;
   }
-  if (too_big) return GNS_EUNSUPPORTED;
   *nnzy_max = ny;
   *lds_max = lds;
-  return GNS_OK;
+  return too_big ? GNS_EUNSUPPORTED : GNS_OK;
 }
 
 // Launches Kernel with a workgroup per grid and lds_bytes of dynamic LDS.  Before the first launch the kernel's dynamic-LDS limit

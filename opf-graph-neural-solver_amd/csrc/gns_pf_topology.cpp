@@ -12,6 +12,14 @@
 
 namespace {
 
+// One topology as the entry points take it.  out_gen: a generator row out of service (gns_pf_prepare_topology_out_gen), -1 for none.
+struct TopologyArgs {
+  int32_t n_bus, n_line, n_gen;
+  const int32_t *f_bus, *t_bus, *gen_bus;
+  int32_t slack;
+  int32_t out_gen = -1;
+};
+
 struct PfBlob {
   std::vector<int32_t> w;
   PfBlob() : w(PF_HDR_WORDS, 0) {}
@@ -85,8 +93,10 @@ struct PfGrid {
   int npv = 0, npq = 0, nnzY = 0;
 };
 
-int pf_grid(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, PfGrid& G) {
-  if (N <= 0 || E < 0 || Gn < 0 || (E > 0 && (!f || !t)) || (Gn > 0 && !gb)) return GNS_EINVAL;
+// out_gen >= 0: that generator row is out of service.  It gives its bus no role and is left off the by-bus lists, which keep the
+// original row numbers of the others (Gn - 1 entries; the header's Gn and the indexing of generators [Bt,Gn,7] stay as they are).
+int pf_grid(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, int out_gen, PfGrid& G) {
+  if (N <= 0 || E < 0 || Gn < 0 || (E > 0 && (!f || !t)) || (Gn > 0 && !gb) || out_gen < -1 || out_gen >= Gn) return GNS_EINVAL;
   if (slack < 0 || slack >= N) return GNS_ETOPOLOGY;
   for (int e = 0; e < E; ++e) if (f[e] < 0 || f[e] >= N || t[e] < 0 || t[e] >= N) return GNS_ETOPOLOGY;
   for (int g = 0; g < Gn; ++g) if (gb[g] < 0 || gb[g] >= N) return GNS_ETOPOLOGY;
@@ -108,12 +118,12 @@ int pf_grid(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int3
   std::vector<int32_t>& role = G.role;
   std::vector<int32_t>& gen_ptr = G.gen_ptr;
   role.assign(N, 0); gen_ptr.assign(N + 1, 0); G.gen_idx.assign(std::max(Gn, 1), 0);
-  for (int g = 0; g < Gn; ++g) { role[gb[g]] = 1; ++gen_ptr[gb[g] + 1]; }
+  for (int g = 0; g < Gn; ++g) if (g != out_gen) { role[gb[g]] = 1; ++gen_ptr[gb[g] + 1]; }
   role[slack] = 2;
   for (int i = 0; i < N; ++i) gen_ptr[i + 1] += gen_ptr[i];
   {
     std::vector<int32_t> c(gen_ptr.begin(), gen_ptr.end() - 1);
-    for (int g = 0; g < Gn; ++g) G.gen_idx[c[gb[g]]++] = g;
+    for (int g = 0; g < Gn; ++g) if (g != out_gen) G.gen_idx[c[gb[g]]++] = g;
   }
   for (int i = 0; i < N; ++i) { G.npv += role[i] == 1; G.npq += role[i] == 0; }
 
@@ -178,10 +188,10 @@ struct SymLU {
 };
 
 // With slots_out, the factor's slot count nnz(L+U) + dim is written there as soon as it is known, also when it is refused.
-int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& out,
-            int64_t* slots_out = nullptr) {
+int analyse(const TopologyArgs& a, std::vector<int32_t>& out, int64_t* slots_out = nullptr) {
+  const int N = a.n_bus, E = a.n_line, Gn = a.n_gen, slack = a.slack;
   PfGrid G;
-  const int rc = pf_grid(N, E, Gn, f, t, gb, slack, G);
+  const int rc = pf_grid(N, E, Gn, a.f_bus, a.t_bus, a.gen_bus, slack, a.out_gen, G);
   if (rc != GNS_OK) return rc;
   const std::vector<int32_t>& role = G.role;
   const std::vector<int32_t>& y_ptr = G.y_ptr;
@@ -281,10 +291,10 @@ int analyse(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int3
 // The fast-decoupled analysis: B' on the PV+PQ buses and B'' on the PQ buses share the Y-bus pattern; each gets a minimum-degree
 // ordering of its bus subgraph, a symbolic LU, and a factorisation and a solve program (layout: gns_pf_common.h, FH_*).  With
 // slots_out, the larger of the two factors' slot counts is written there as soon as both are known.
-int analyse_fd(int N, int E, int Gn, const int32_t* f, const int32_t* t, const int32_t* gb, int slack, std::vector<int32_t>& out,
-               int64_t* slots_out = nullptr) {
+int analyse_fd(const TopologyArgs& a, std::vector<int32_t>& out, int64_t* slots_out = nullptr) {
+  const int N = a.n_bus, E = a.n_line, Gn = a.n_gen, slack = a.slack;
   PfGrid G;
-  const int rc = pf_grid(N, E, Gn, f, t, gb, slack, G);
+  const int rc = pf_grid(N, E, Gn, a.f_bus, a.t_bus, a.gen_bus, slack, a.out_gen, G);
   if (rc != GNS_OK) return rc;
   const int nnzY = G.nnzY;
   std::vector<int32_t> idx[2] = {std::vector<int32_t>(N, -1), std::vector<int32_t>(N, -1)};
@@ -347,16 +357,10 @@ int analyse_fd(int N, int E, int Gn, const int32_t* f, const int32_t* t, const i
 
 // The three entry points of an analysis (analyse or analyse_fd), written once.  An exception of the analysis (out of memory on an
 // absurd shape) is GNS_EINVAL.
-using Analysis = int (*)(int, int, int, const int32_t*, const int32_t*, const int32_t*, int, std::vector<int32_t>&, int64_t*);
-
-struct TopologyArgs {
-  int32_t n_bus, n_line, n_gen;
-  const int32_t *f_bus, *t_bus, *gen_bus;
-  int32_t slack;
-};
+using Analysis = int (*)(const TopologyArgs&, std::vector<int32_t>&, int64_t*);
 
 int analyse_safe(Analysis fn, const TopologyArgs& a, std::vector<int32_t>& w, int64_t* slots_out = nullptr) {
-  try { return fn(a.n_bus, a.n_line, a.n_gen, a.f_bus, a.t_bus, a.gen_bus, a.slack, w, slots_out); } catch (...) { return GNS_EINVAL; }
+  try { return fn(a, w, slots_out); } catch (...) { return GNS_EINVAL; }
 }
 
 int topology_bytes(Analysis fn, const TopologyArgs& a, size_t* bytes) {
@@ -401,6 +405,25 @@ extern "C" int gns_pf_topology_slots(int32_t n_bus, int32_t n_line, int32_t n_ge
 extern "C" int gns_pf_prepare_topology(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
                                        const int32_t* gen_bus, int32_t slack, void* topo_host_out, size_t topo_bytes) {
   return prepare_topology(analyse, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack}, topo_host_out, topo_bytes);
+}
+
+// The analysis with generator row out_gen out of service (-1: none, gns_pf_prepare_topology's blob byte for byte): what the AC
+// generator contingency screen runs a row on.  The Y-bus pattern and its stamps come from the lines alone: the same words whatever
+// out_gen is.
+extern "C" int gns_pf_topology_bytes_out_gen(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                                             const int32_t* gen_bus, int32_t slack, int32_t out_gen, size_t* bytes) {
+  return topology_bytes(analyse, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, out_gen}, bytes);
+}
+
+extern "C" int gns_pf_topology_slots_out_gen(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                                             const int32_t* gen_bus, int32_t slack, int32_t out_gen, int64_t* slots) {
+  return topology_slots(analyse, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, out_gen}, slots);
+}
+
+extern "C" int gns_pf_prepare_topology_out_gen(int32_t n_bus, int32_t n_line, int32_t n_gen, const int32_t* f_bus, const int32_t* t_bus,
+                                               const int32_t* gen_bus, int32_t slack, int32_t out_gen, void* topo_host_out,
+                                               size_t topo_bytes) {
+  return prepare_topology(analyse, {n_bus, n_line, n_gen, f_bus, t_bus, gen_bus, slack, out_gen}, topo_host_out, topo_bytes);
 }
 
 extern "C" int gns_pf_topology_info(const void* topo_host, gns_pf_info* info) {

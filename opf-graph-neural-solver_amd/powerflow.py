@@ -46,6 +46,11 @@ at the forward's state, on the same analysis.
 ``dc_n2_contingency_screen`` ranked: Newton-Raphson on every ``(grid, pair)``, again on the base topology's analysis alone
 (``csrc/gns_acn2.hip``).  ``ac_n2_contingency_screen_differentiable(...)`` is the same screen with a backward: one ``gns_acn2_adjoint`` call,
 per pair one factorisation and one transposed solve at the forward's state.
+
+``ac_generator_contingency_screen(...)`` is the AC screen of the rows ``dc_generator_contingency_screen`` takes, a generator out alone
+or with a line out as well: the bus of a lost unit may turn from PV to PQ, so the topology is analysed once per distinct generator of
+the list (``gns_pf_prepare_topology_out_gen``) and every row runs Newton-Raphson on its generator's analysis, the line on top of it
+as in ``ac_contingency_screen`` (``csrc/gns_acg1.hip``).  Forward only.
 """
 from __future__ import annotations
 
@@ -82,6 +87,11 @@ AcContingencyResult = namedtuple('AcContingencyResult', ['base', 'outages', 'v',
 AcN2ContingencyResult = namedtuple('AcN2ContingencyResult', ['base', 'pairs', 'v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to',
                                                              'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max', 'v_max_bus',
                                                              'converged', 'iterations', 'mismatch', 'islanding'])
+
+AcGeneratorContingencyResult = namedtuple('AcGeneratorContingencyResult', ['base', 'contingencies', 'v', 'theta', 'p_from', 'q_from',
+                                                                           'p_to', 'q_to', 'worst_loading', 'worst_line', 'v_min',
+                                                                           'v_min_bus', 'v_max', 'v_max_bus', 'converged', 'iterations',
+                                                                           'mismatch', 'islanding'])
 
 MixedPlan = namedtuple('MixedPlan', ['topology', 'order', 'grid_off', 'member_off', 'topo_set', 'slack_bus', 'islanded'])
 
@@ -174,6 +184,7 @@ _DCG1_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) bytes per
 _DCG1 = _Solver('gns_dcg1', FdTopology, _DCG1_LDS_FORMULA)   # the DC generator screen: the N-1 screen's analysis and image again
 _ACN1 = _Solver('gns_acn1', PowerFlowTopology, _LDS_FORMULA)   # the AC contingency screen: Newton-Raphson's analysis and LDS image
 _ACN2 = _Solver('gns_acn2', PowerFlowTopology, _LDS_FORMULA)   # the AC N-2 screen: the same analysis and image again
+_ACG1 = _Solver('gns_acg1', PowerFlowTopology, _LDS_FORMULA)   # the AC generator screen: that analysis without the lost unit's row, one per unit
 _DCN1_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p (W + 1) + 3 W) bytes per workgroup: the screen's image, a second "
                              "array of W right-hand sides for the adjoint solves and three doubles per outage, here with W = 1, the "
                              "narrowest")
@@ -245,12 +256,16 @@ def _islanded(n_bus, f_bus, t_bus, slack):
     return np.flatnonzero(~seen)
 
 
-def analyse_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
+def analyse_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None, out_gen=None):
     """Analyse one topology from 1-based ``f_bus[E]``, ``t_bus[E]``, ``gen_bus[Gn]`` and the 1-based ``slack_bus`` (host arrays).
     Returns a ``PowerFlowTopology`` (its ``info`` dict holds the Jacobian dimension, nnz(L+U), ...); with ``device`` the blob is
     also copied there (on first use).  Raises ValueError for ids out of range or a slack that is not a bus, and its subclass
-    ``IslandedTopology`` for buses islanded from the slack."""
-    return _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, 'gns_pf', PowerFlowTopology)
+    ``IslandedTopology`` for buses islanded from the slack.
+
+    ``out_gen``: a 0-based generator row that is out of service (``gns_pf_prepare_topology_out_gen``, what a row of
+    ``ac_generator_contingency_screen`` is solved on): the row gives its bus no role and is left off the by-bus generator lists, which
+    keep the others' row numbers; ``n_gen`` stays ``Gn``.  None or -1: the plain analysis, byte for byte."""
+    return _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, 'gns_pf', PowerFlowTopology, out_gen)
 
 
 def analyse_fd_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
@@ -258,7 +273,7 @@ def analyse_fd_topology(n_bus, f_bus, t_bus, gen_bus, slack_bus, device=None):
     return _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, 'gns_fd', FdTopology)
 
 
-def _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, prefix, cls):
+def _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, prefix, cls, out_gen=None):
     f = np.asarray(f_bus, dtype=np.float64).reshape(-1)
     t = np.asarray(t_bus, dtype=np.float64).reshape(-1)
     g = np.asarray(gen_bus, dtype=np.float64).reshape(-1)
@@ -277,19 +292,25 @@ def _analyse(n_bus, f_bus, t_bus, gen_bus, slack_bus, device, prefix, cls):
     lib = load_library()
     nbytes = ctypes.c_size_t()
     args = (int(n_bus), int(f32.size), int(g32.size), f32.ctypes.data, t32.ctypes.data, g_arg.ctypes.data, slack)
-    rc = getattr(lib, prefix + '_topology_bytes')(*args, ctypes.byref(nbytes))
+    suffix = ''
+    if out_gen is not None:                  # the entry points that take the generator row that is out
+        if out_gen != int(out_gen) or not -1 <= out_gen < g32.size:
+            raise ValueError(f'out_gen = {out_gen!r} is not a generator row (0..{g32.size - 1}, or -1 for none)')
+        args, suffix = (*args, int(out_gen)), '_out_gen'
+    rc = getattr(lib, prefix + '_topology_bytes' + suffix)(*args, ctypes.byref(nbytes))
     if rc == GNS_ETOPOLOGY:
         isl = _islanded(int(n_bus), f32, t32, slack) + 1
         raise IslandedTopology(f'buses {isl.tolist()} have no path of lines to slack_bus {slack + 1}: their angles are undetermined '
                          '(the power-flow Jacobian is structurally singular)')
     if rc == GNS_EUNSUPPORTED:
         slots = ctypes.c_int64()
-        _check(getattr(lib, prefix + '_topology_slots')(*args, ctypes.byref(slots)), prefix + '_topology_slots')
+        _check(getattr(lib, prefix + '_topology_slots' + suffix)(*args, ctypes.byref(slots)), prefix + '_topology_slots' + suffix)
         raise _gns.GNSError(f'{prefix}_topology_bytes failed: GNS_EUNSUPPORTED (the factor of this topology needs {slots.value} slots, '
                             f'nnz(L+U) + dim, more than the {PF_MAX_SLOTS}-slot limit of the program\'s 16-bit operands)')
     _check(rc, prefix + '_topology_bytes')
     host = np.zeros(nbytes.value // 4, dtype=np.int32)
-    _check(getattr(lib, prefix + '_prepare_topology')(*args, host.ctypes.data, host.nbytes), prefix + '_prepare_topology')
+    _check(getattr(lib, prefix + '_prepare_topology' + suffix)(*args, host.ctypes.data, host.nbytes),
+           prefix + '_prepare_topology' + suffix)
     return cls(host, device)
 
 
@@ -799,7 +820,7 @@ def _screen_setup(name, solver, buses, lines, generators, B, L, G, slack_bus, ro
         s.pickup = None if pickup is None else pickup.to(s.dev).contiguous()
         s.cfg = PfConfig(s.N, s.E, s.generators.shape[1], int(max_iter), float(tol))
         s.plain = (s.buses.detach(), s.lines.detach(), s.generators.detach())
-        key, args = _topology_key(*s.plain, slack_bus, name)
+        key, args = s.topo_key, s.topo_args = _topology_key(*s.plain, slack_bus, name)
         s.topo = _analysed(solver, key, args, s.dev)
         if generator:
             s.isl_np = _generator_islanding(_topology_bridges(s.topo, args), s.rows)
@@ -903,12 +924,10 @@ def _dc_screen(s, solver, shared, n_rows, counts, adjoint_counts, adjoint_lds_by
     return [torch.ones(Bt, s.N, dtype=torch.float64, device=dev), *base], list(res)
 
 
-def _ac_screen_launch(s, solver, shared, n_rows, base_state, keep_state, flows, bu, li, ge):
-    """One ``gns_acn1_screen`` / ``gns_acn2_screen`` launch (``solver``): the fifteen outputs in its order (``converged`` as uint8),
-    every row warm-started from ``base_state`` (the base ``v``, ``theta`` and ``converged`` as uint8).  ``v`` and ``theta`` are None
-    unless ``keep_state``, the four flows unless ``flows``."""
-    lib, cfg, topo, Bt, dev = s.lib, s.cfg, s.topo, s.Bt, s.dev
-    lds, name = topo.info['lds_bytes'], solver.prefix + '_screen'
+def _ac_screen_outputs(s, n_rows, keep_state, flows):
+    """The fifteen outputs of an AC screen launch in ``gns_acn1_screen``'s order, uninitialised (the kernel writes every element):
+    ``v`` and ``theta`` are None unless ``keep_state``, the four flows unless ``flows``."""
+    Bt, dev = s.Bt, s.dev
 
     def rows(n, dtype):
         return [torch.empty(Bt, n_rows, dtype=dtype, device=dev) for _ in range(n)]
@@ -918,7 +937,16 @@ def _ac_screen_launch(s, solver, shared, n_rows, base_state, keep_state, flows, 
     worst, v_min, v_max, mismatch = rows(4, torch.float64)
     worst_line, v_min_bus, v_max_bus, iterations = rows(4, torch.int32)
     conv, = rows(1, torch.uint8)
-    out = [*state, *flow, worst, worst_line, v_min, v_min_bus, v_max, v_max_bus, conv, iterations, mismatch]
+    return [*state, *flow, worst, worst_line, v_min, v_min_bus, v_max, v_max_bus, conv, iterations, mismatch]
+
+
+def _ac_screen_launch(s, solver, shared, n_rows, base_state, keep_state, flows, bu, li, ge):
+    """One ``gns_acn1_screen`` / ``gns_acn2_screen`` launch (``solver``): the fifteen outputs in its order (``converged`` as uint8),
+    every row warm-started from ``base_state`` (the base ``v``, ``theta`` and ``converged`` as uint8).  ``v`` and ``theta`` are None
+    unless ``keep_state``, the four flows unless ``flows``."""
+    lib, cfg, topo, Bt, dev = s.lib, s.cfg, s.topo, s.Bt, s.dev
+    lds, name = topo.info['lds_bytes'], solver.prefix + '_screen'
+    out = _ac_screen_outputs(s, n_rows, keep_state, flows)
     ws = _gns._workspace(_screen_workspace_bytes(s, solver.prefix + '_workspace_bytes', (n_rows,), lds, solver.formula), dev)
     with torch.cuda.device(dev):
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -1220,8 +1248,8 @@ def dc_generator_contingency_screen(buses, lines, generators, B=None, L=None, G=
     ``(g,k)`` is row ``k`` of ``dc_contingency_screen``, bit for bit.  With a 2-D single grid the batch dimension is dropped.
 
     The outputs are not differentiable (the call runs as under ``torch.no_grad()``, whatever requires grad): the same call with a
-    backward on the device is ``dc_generator_contingency_screen_differentiable``.  Mixed topologies, limits on the pickup, a
-    generator with two lines and the AC counterpart (an outage can turn a PV bus into a PQ bus) are out of scope.
+    backward on the device is ``dc_generator_contingency_screen_differentiable``.  The AC check of the same rows is
+    ``ac_generator_contingency_screen``.  Mixed topologies, limits on the pickup and a generator with two lines are out of scope.
     Contract: ``include/gns_powerflow.h``, "DC generator contingency screening"."""
     return _dc_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, flows, False)
 
@@ -1290,7 +1318,8 @@ def dc_generator_contingency_screen_differentiable(buses, lines, generators, B=N
     unaffected.  A grid's gradient is bit-identical alone, in any batch and from run to run for the same list; another order of
     the list may change its last bits.
 
-    Out of scope: mixed topologies, limits on the pickup, a generator with two lines, AC generator outages, second derivatives.
+    Out of scope: mixed topologies, limits on the pickup, a generator with two lines, second derivatives.  AC generator outages:
+    ``ac_generator_contingency_screen`` (forward only).
     Contract: ``include/gns_powerflow.h``, "Gradients of the DC generator screen"."""
     return _dc_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, flows, True)
 
@@ -1371,7 +1400,8 @@ def ac_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, s
     gradients; a grid's gradient is bit-identical alone, in any batch and from run to run for the same outage list (another order
     of the list may change its last bits).
 
-    Out of scope: batches that mix topologies and generator reactive limits.  Double outages: ``ac_n2_contingency_screen``.
+    Out of scope: batches that mix topologies and generator reactive limits.  Double outages: ``ac_n2_contingency_screen``;
+    generator outages, alone or with a line: ``ac_generator_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "AC contingency screening"."""
     s = _screen_setup('ac_contingency_screen', _NR, buses, lines, generators, B, L, G, slack_bus, outages, rating,
                       dict(flows=flows, states=states), differentiable, tol, max_iter)
@@ -1465,7 +1495,8 @@ def ac_n2_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *
 
     This call runs as under ``torch.no_grad()``, and ``requires_grad`` on an input is ignored without an error; the same screen with
     gradients is ``ac_n2_contingency_screen_differentiable``.
-    Out of scope: batches that mix topologies, line plus generator outages and generator reactive limits.
+    Out of scope: batches that mix topologies, a generator with two lines and generator reactive limits.  A generator with one
+    line: ``ac_generator_contingency_screen``.
     Contract: ``include/gns_powerflow.h``, "AC N-2 contingency screening"."""
     return _ac_n2_screen(buses, lines, generators, B, L, G, slack_bus, pairs, rating, tol, max_iter, flows, states, False)
 
@@ -1509,9 +1540,112 @@ def ac_n2_contingency_screen_differentiable(buses, lines, generators, B=None, L=
     any batch, from run to run and with the two lines of any pair swapped, for the same pair list (another order of the list may
     change its last bits).
 
-    Out of scope: batches that mix topologies, line plus generator outages, generator reactive limits and second derivatives.
+    Out of scope: batches that mix topologies, a generator with two lines, generator reactive limits and second derivatives (a
+    generator with one line: ``ac_generator_contingency_screen``, forward only).
     Contract: ``include/gns_powerflow.h``, "Gradients of the AC N-2 screen"."""
     return _ac_n2_screen(buses, lines, generators, B, L, G, slack_bus, pairs, rating, tol, max_iter, flows, states, True)
+
+
+def _analysed_without(key, args, device, g):
+    """The cached Newton-Raphson analysis of the topology ``_topology_key`` gave ``key`` and ``args`` for, without generator row
+    ``g``: the analysis cache's entry of that topology and ``out_gen``."""
+    cache = _analysis(_NR)[0]
+    topo = cache.get(key + (g,))
+    if topo is None:
+        topo = cache[key + (g,)] = analyse_topology(*args, device=device, out_gen=g)
+    return topo
+
+
+def ac_generator_contingency_screen(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None, contingencies=None,
+                                    pickup=None, rating=None, tol=1e-8, max_iter=10, flows=False, states=False):
+    """AC generator contingency screening of every grid of a batch, on the device: Newton-Raphson on each ``(grid, row)`` of
+    ``contingencies``, a generator out alone or with a line out as well (the combined N-1 set of a planner), with the outputs of
+    ``ac_contingency_screen`` per row.  It is the AC check of the rows ``dc_generator_contingency_screen`` ranks: a unit trip takes
+    the voltage support of its bus away, which the DC screen (``|V| = 1`` everywhere) cannot see.
+
+    A generator outage leaves the Y-bus alone and may change the unknowns: the bus of a sole unit turns from PV to PQ, and on a bus
+    with several units the set point may move.  Both depend on the topology and the unit alone, so the topology is analysed once per
+    distinct generator of the list (``analyse_topology(..., out_gen=g)``, cached with the other analyses) and never per row or per
+    grid; the line on top of the unit is ``ac_contingency_screen``'s Y-bus view on that analysis.  ``newton_raphson(
+    mixed_topologies=True)`` on the expanded batch would analyse one topology per distinct row and hold a copy of the inputs per row.
+
+    Inputs, column maps, the slack, the device handling, ``rating``, ``tol`` and ``max_iter`` are those of
+    ``ac_contingency_screen``; the whole batch shares one topology.  ``contingencies`` and ``pickup`` are those of
+    ``dc_generator_contingency_screen``: a ``[P,2]`` integer tensor, array or sequence of ``(generator, line)``, 0-based generator
+    rows and line indices, line -1 for "no line out"; default, for each generator in order, ``(g,-1), (g,0), ..., (g,E-1)``
+    (``Gn (E + 1)`` rows, so the two screens line up row for row).  Duplicates are independent rows.
+
+    Row ``(grid, (g, k))`` is Newton-Raphson on the grid with generator row ``g`` deleted and, when ``k >= 0``, line ``k`` out of
+    service, which is what ``newton_raphson`` computes on those inputs:
+      roles       the slack stays the slack; the bus of ``g`` stays PV when another generator is listed on it, otherwise it becomes a
+                  PQ bus (``|V|`` an unknown, the Q equation solved with ``Qsp = -Qd``)
+      set points  ``|V|`` at a PV or slack bus is ``vg`` of the first remaining generator listed on it (the outage of the first-listed
+                  unit of a shared bus moves the set point to the next unit's); a slack with none left takes 1
+      injections  ``Psp_i`` = the sum of ``Pg`` over the remaining generators of bus ``i``, plus their pickup, minus ``Pd_i``.
+                  ``pickup``: None, the slack picks the lost ``Pg_g`` up; ``'pmax'`` or weights ``[Gn]`` / ``[Bt,Gn]`` (non-negative,
+                  finite, float64), generator ``h != g`` injects ``Pg_g w_h / W_g`` more, ``W_g`` the sum of the others' weights in
+                  generator-row order; when ``W_g`` is exactly 0 the slack picks up.  No Pmax or Pmin limit is enforced, and in AC the
+                  slack also takes the change of the losses, whatever the pickup.
+      start       ``|V|`` at the row's PQ buses from ``base.v`` (a freed bus starts at its old set point), ``theta = base.theta -
+                  base.theta[slack]``, ``|V|`` at PV and slack buses from the row's set points
+    The convergence test, the update, ``max_iter``, the failure rules, the branch flows (all four exactly 0 at line ``k``), the
+    summaries and their order (the lowest index among equals, NaN first) are ``ac_contingency_screen``'s.
+
+    Returns ``AcGeneratorContingencyResult``, ``AcContingencyResult``'s fields with ``contingencies`` in place of ``outages``:
+      base           the ``PowerFlowResult`` of ``newton_raphson`` on the same inputs with the same ``tol`` and ``max_iter``, bit for bit
+      contingencies  ``[P,2]`` int64, as given
+      v, theta       None by default; with ``states=True`` ``[Bt,P,N]`` float64, the post-outage state
+      p_from, q_from, p_to, q_to   None by default; with ``flows=True`` ``[Bt,P,E]`` float64
+      worst_loading, worst_line, v_min, v_min_bus, v_max, v_max_bus, converged, iterations, mismatch   ``[Bt,P]``, as
+                     ``ac_contingency_screen`` returns them
+      islanding      ``[P]`` bool: the row's line is a bridge of the topology (found on the host and kept with the topology); a generator
+                     outage alone never islands
+    An islanding row has NaN / -1 / ``converged`` False / ``iterations`` -1 in every grid; so has every row of a grid whose base
+    solve did not converge.  A row that does not converge keeps its last finite iterate with ``converged`` False.  Every row is
+    bit-identical alone, in any batch, in any list or order that holds it, with any of ``flows`` / ``states``, and from run to run.
+    With a 2-D single grid the batch dimension is dropped.
+
+    The outputs are not differentiable: the call runs as under ``torch.no_grad()``, and ``requires_grad`` on an input is ignored
+    without an error.  The backward of this screen is not written yet.
+    Out of scope: reactive limits on the remaining units, Pmax / Pmin limits on the pickup, batches that mix topologies, a generator
+    with two lines.  Contract: ``include/gns_powerflow.h``, "AC generator contingency screening"."""
+    s = _screen_setup('ac_generator_contingency_screen', _NR, buses, lines, generators, B, L, G, slack_bus, contingencies, rating,
+                      dict(flows=flows, states=states), False, tol, max_iter, pickup=pickup)
+    with torch.no_grad():
+        lib, cfg, Bt, dev = s.lib, s.cfg, s.Bt, s.dev
+        # the base case as newton_raphson solves it: its refusals come first, before any other analysis is made
+        base = _solve(lib, _NR, cfg, _one_topology(s.topo), *s.plain, None, None)
+        base_state = (base[0], base[1], base[2].to(torch.uint8))
+        # the distinct generators of the list, ascending, each with its analysis in the topology's set of them; a row as a
+        # position into the generators and its line (-1: none)
+        P = s.rows.shape[0]
+        gen_np, gen_col = np.unique(s.rows[:, 0], return_inverse=True)
+        set_cache = _analysis(_NR)[1]
+        set_key = s.topo_key + ('out_gen',)
+        members = set_cache.get(set_key)
+        if members is None:
+            members = set_cache[set_key] = _PfTopologySet(dev)
+        off_np = np.array([members.add(s.topo_key + (g,), _analysed_without(s.topo_key, s.topo_args, dev, g)) for g in gen_np.tolist()])
+        members.sync()
+        (off_host, off_dev), (gen_host, gen_dev) = _upload32(off_np, dev), _upload32(gen_np, dev)
+        cols_host, cols_dev = _upload32(np.stack([gen_col.reshape(P), s.rows[:, 1]], axis=1), dev)
+        set_host, set_blob = members.host, members.blob          # this call's: a later call may grow the set
+        lds = lambda: _set_lds_bytes(set_host, off_host)                         # noqa: E731
+        ws_bytes = _size_query(lib.gns_acg1_workspace_bytes, 'gns_acg1_workspace_bytes',
+                               (ctypes.byref(cfg), set_host.ctypes.data, set_host.size, off_host.ctypes.data, off_host.size, Bt, P), lds,
+                               _ACG1.formula)
+        ws = _gns._workspace(ws_bytes, dev)
+        res = _ac_screen_outputs(s, P, states, flows)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_acg1_screen(ctypes.byref(cfg), set_host.ctypes.data, set_blob.data_ptr(), set_host.size, off_host.ctypes.data,
+                                       off_dev.data_ptr(), off_host.size, *(t.data_ptr() for t in s.plain), Bt, gen_host.ctypes.data,
+                                       gen_dev.data_ptr(), cols_host.ctypes.data, cols_dev.data_ptr(), P, s.isl_dev.data_ptr(),
+                                       _ptr(s.rating), int(s.rating is not None and s.rating.dim() == 2), _ptr(s.pickup),
+                                       int(s.pickup is not None and s.pickup.dim() == 2), *(t.data_ptr() for t in base_state),
+                                       *map(_ptr, res), ws.data_ptr(), ws.numel(), stream), 'gns_acg1_screen', lds, _ACG1.formula)
+        base, rows_t, res, islanding = _screen_results(s, base, res, 12)
+        return AcGeneratorContingencyResult(PowerFlowResult(*base), rows_t, *res, islanding)
 
 
 def _not_solved(Bt, N, dev):

@@ -5,7 +5,8 @@
 // the buses.  Per reverse step k:
 //   Pb-0    adjoint of delta_p_{k+1} is completed (loss term) and the scalar adjoint of lambda is reduced
 //   Pb-edge per line: adjoints of the line physics w.r.t. v, theta of its 2 (+4 bus-id-as-line-index) buses,
-//           stored per line (no atomics); every bus later gathers its own lists in a fixed order
+//           stored per line (no atomics); every bus later gathers its own lists in a fixed order.  The line's trig and
+//           state adjoint are shared with the other backward kernels: gns_phys_device.h
 //   Ub      per bus: gather, then the update step is recomputed and back-propagated; the weight gradient
 //           (a contraction over the 64 grids of the wave) goes through an LDS transpose into register-resident
 //           accumulators - fp32 MFMA tiles by default, 4x4 packed-FMA tiles with GNS_DW_MFMA=0 - that are
@@ -16,6 +17,7 @@
 #include "gns_kernels.h"
 
 #include "gns_dw.h"
+#include "gns_phys_device.h"
 
 #ifndef GNS_BWD_PLANES
 #define GNS_BWD_PLANES 1          // 0 (diagnostic build): the line phase gathers its neighbour values from HBM / L2 rows
@@ -224,79 +226,28 @@ __global__ void __launch_bounds__(GNS_BWD_THREADS) gns_backward_kernel(GnsBwdArg
         L.Fb = row_ptr(A.adj, adj_row(t), lane)->z;                          // dp[t] += p_from   (main.py:94)
         L.Tb = row_ptr(A.adj, adj_row(s), lane)->z;                          // dp[s] += p_to     (main.py:95)
       };
-      struct EdgeOut { float dvs, dvt, dths, dbar, dbar2; };
-      auto edge_store = [&](int p, const EdgeOut& R) {
-        // dtht == -dths bit for bit (Bb - Ab + Cb against Ab - Bb - Cb): plane 3 is not written, the gather negates plane 2
+      auto edge_store = [&](int p, const LineAdj& R) {
+        // dtht == -dths bit for bit (gns_phys_device.h): plane 3 is not written, the gather negates plane 2
         *slot_ptr(0, p) = R.dvs; *slot_ptr(1, p) = R.dvt; *slot_ptr(2, p) = R.dths;
         *slot_ptr(4, p) = R.dbar; *slot_ptr(5, p) = R.dbar2;
       };
-      auto edge_adjoint = [&](int p, const EdgeIn& L, EdgeOut& R) {
-        const f4 e1v = L.e1v, o0 = L.o0;
-        const float Fb = L.Fb, Tb = L.Tb;
-        const float vs = L.ss.x, ths = L.ss.y, vt = L.st.x, tht = L.st.y;
-        const float ys = e1v.y, taus = e1v.z, shs = e1v.w;
-        const float dl = L.tha - L.thb, dl2 = L.thd - L.thc;
-        float sA, cA, sB, cB, sD, cD, sC, cC, sD2, cD2;
-#ifdef GNS_ABLATE_PHYS_TRIG       // diagnostic: no trigonometric evaluation (results wrong by design)
-        sA = ths - tht - dl - shs; cA = 1.f - sA; sB = tht - ths - dl + shs; cB = 1.f - sB; sD = dl; cD = 1.f - dl;
-        sC = tht - ths - dl2 - o0.z; cC = 1.f - sC; sD2 = dl2; cD2 = 1.f - dl2;
-#else
-        sincosf(ths - tht - dl - shs, &sA, &cA);
-        sincosf(tht - ths - dl + shs, &sB, &cB);
-        sincosf(dl, &sD, &cD);
-        sincosf(tht - ths - dl2 - o0.z, &sC, &cC);
-        sincosf(dl2, &sD2, &cD2);
-#endif
-        // "from" expressions: p_from (main.py:91) and |msg| of the joule loss (main.py:41)
-        const float yot = ys / taus, yot2 = ys / (taus * taus);
-        const float base = vs * vt * yot;
-        const float kJ = vs * yot2 + vt * vt * ys;
-        const float inner = base * (sA + sB) + kJ * sD;
-        const float Jb = pgbar * (inner > 0.f ? 1.f : (inner < 0.f ? -1.f : 0.f));
-        float dvs = Fb * (vt * yot * sA + 2.f * vs * yot2 * sD) + Jb * (vt * yot * (sA + sB) + yot2 * sD);
-        float dvt = Fb * (vs * yot * sA) + Jb * (vs * yot * (sA + sB) + 2.f * vt * ys * sD);
-        const float Ab = (Fb + Jb) * base * cA, Bb = Jb * base * cB;
-        const float dbar = Fb * (vs * vs * yot2) * cD + Jb * kJ * cD - Ab - Bb;
-        float dths = Ab - Bb, dtht = Bb - Ab;
-        // "to" expression: p_to (main.py:92)
-        const float yot_t = o0.x / o0.y;
-        const float base2 = vt * vs * yot_t;
-        dvt += Tb * (vs * yot_t * sC + 2.f * vt * o0.x * sD2);
-        dvs += Tb * (vt * yot_t * sC);
-        const float Cb = Tb * base2 * cC;
-        const float dbar2 = Tb * vt * vt * o0.x * cD2 - Cb;
-        dtht += Cb; dths -= Cb;
-        (void)dtht;
-#ifdef GNS_ABLATE_PHYS_STORE      // diagnostic: the results are computed but not stored
-        asm volatile("" :: "v"(dvs), "v"(dvt), "v"(dths), "v"(dbar), "v"(dbar2));
-        R = EdgeOut{0.f, 0.f, 0.f, 0.f, 0.f};
-#else
-        R = EdgeOut{dvs, dvt, dths, dbar, dbar2};
-#endif
+      auto edge_adjoint = [&](const EdgeIn& L) {
+        const LineTrig T = line_trig<false>(L.ss.y, L.st.y, L.tha, L.thb, L.thc, L.thd, L.e1v.w, L.o0.z);
+        return line_state_adjoint(T, L.ss.x, L.st.x, L.e1v.y, L.e1v.z, L.o0.x, L.o0.y, L.Fb, L.Tb, pgbar);
       };
-#ifdef GNS_ABLATE_PHYS
-      for (int p = e0; p < e0; p += 2) {
-#else
       for (int p = e0; p < e1; p += 2) {
-#endif
         EdgeIn L0, L1;
-        EdgeOut R0, R1;
         edge_load(p, L0);
         edge_load(min(p + 1, e1 - 1), L1);
-        edge_adjoint(p, L0, R0);
-        edge_store(p, R0);
-        if (p + 1 < e1) { edge_adjoint(p + 1, L1, R1); edge_store(p + 1, R1); }
+        edge_store(p, edge_adjoint(L0));
+        if (p + 1 < e1) edge_store(p + 1, edge_adjoint(L1));
       }
       STAMP(2)
       team_barrier(team);
       STAMP(3)
 
       // ---------------- Ub, pass G: every bus completes d/d(v,theta)_{k+1} from the per-line adjoints --------------
-#ifdef GNS_ABLATE_GATHER
-      for (int n = n0; n < n0; ++n) {
-#else
       for (int n = n0; n < n1; ++n) {
-#endif
         const long long ar = adj_row(n);
         const f4 a0 = *row_ptr(A.adj, ar, lane);
         float vbar = a0.x, thbar = a0.y;

@@ -5,7 +5,9 @@
 //                          Pb-0 closes step k+1 (identity paths main.py:182,186 + the input-adjoint parts of its sweeps), adds
 //                          the loss term (main.py:198-199), reduces the adjoint of lambda (main.py:47-57); the line phase
 //                          reverses global_active_compensation / local_power_imbalance (main.py:34-104) per line; the gather
-//                          sums every bus's incidence lists in fixed order.  The phases that were latency-bound at the two
+//                          sums every bus's incidence lists in fixed order (line adjoint: gns_phys_device.h, shared with the
+//                          persistent kernel; the input-gradient kernel below takes its state and parameter adjoints from the
+//                          same place).  The phases that were latency-bound at the two
 //                          waves per SIMD of the 256-register sweep now run at four.
 //   gns_bwds_sweep_kernel  ONE-WAVE workgroups, one per (family, bus chunk, block of groups), no barrier at all: the update
 //                          step (main.py:155-188) is recomputed and back-propagated for the buses of the chunk exactly as in
@@ -17,6 +19,7 @@
 #include "gns_device.h"
 #include "gns_kernels.h"
 #include "gns_dw.h"
+#include "gns_phys_device.h"
 
 typedef int gns_i8v __attribute__((ext_vector_type(8)));   // one line record of TH_EREC
 #ifndef GNS_BWDS_ONE_LAYOUT
@@ -182,40 +185,13 @@ __global__ void __launch_bounds__(GNS_BWDS_PHYS_THREADS) gns_bwds_phys_kernel(Gn
       }
     };
     auto edge_adjoint = [&](int p, const EdgeIn& L) {
-      const f4 e1v = L.e1v, o0 = L.o0;
-      const float vs = L.vs, ths = L.ths, vt = L.vt, tht = L.tht, Fb = L.Fb, Tb = L.Tb;
-      const float ys = e1v.y, taus = e1v.z, shs = e1v.w;
-      const float dl = L.tha - L.thb, dl2 = L.thd - L.thc;
-      float sA, cA, sB, cB, sD, cD, sC, cC, sD2, cD2;
-      sincosf(ths - tht - dl - shs, &sA, &cA);
-      sincosf(tht - ths - dl + shs, &sB, &cB);
-      sincosf(dl, &sD, &cD);
-      sincosf(tht - ths - dl2 - o0.z, &sC, &cC);
-      sincosf(dl2, &sD2, &cD2);
-      // "from" expressions: p_from (main.py:91) and |msg| of the joule loss (main.py:41)
-      const float yot = ys / taus, yot2 = ys / (taus * taus);
-      const float base = vs * vt * yot;
-      const float kJ = vs * yot2 + vt * vt * ys;
-      const float inner = base * (sA + sB) + kJ * sD;
-      const float Jb = pgbar * (inner > 0.f ? 1.f : (inner < 0.f ? -1.f : 0.f));
-      float dvs = Fb * (vt * yot * sA + 2.f * vs * yot2 * sD) + Jb * (vt * yot * (sA + sB) + yot2 * sD);
-      float dvt = Fb * (vs * yot * sA) + Jb * (vs * yot * (sA + sB) + 2.f * vt * ys * sD);
-      const float Ab = (Fb + Jb) * base * cA, Bb = Jb * base * cB;
-      const float dbar = Fb * (vs * vs * yot2) * cD + Jb * kJ * cD - Ab - Bb;
-      float dths = Ab - Bb;
-      // "to" expression: p_to (main.py:92)
-      const float yot_t = o0.x / o0.y;
-      const float base2 = vt * vs * yot_t;
-      dvt += Tb * (vs * yot_t * sC + 2.f * vt * o0.x * sD2);
-      dvs += Tb * (vt * yot_t * sC);
-      const float Cb = Tb * base2 * cC;
-      const float dbar2 = Tb * vt * vt * o0.x * cD2 - Cb;
-      dths -= Cb;
-      // dtht == -dths bit for bit (Bb - Ab + Cb against Ab - Bb - Cb): plane 3 is not written, the gather negates plane 2
-      if (!L.gs) *slot_ptr(0, p) = dvs;
-      if (!L.gt) *slot_ptr(1, p) = dvt;
-      *slot_ptr(2, p) = dths;
-      *slot_ptr(4, p) = dbar; *slot_ptr(5, p) = dbar2;
+      const LineTrig T = line_trig<false>(L.ths, L.tht, L.tha, L.thb, L.thc, L.thd, L.e1v.w, L.o0.z);
+      const LineAdj R = line_state_adjoint(T, L.vs, L.vt, L.e1v.y, L.e1v.z, L.o0.x, L.o0.y, L.Fb, L.Tb, pgbar);
+      // dtht == -dths bit for bit (gns_phys_device.h): plane 3 is not written, the gather negates plane 2
+      if (!L.gs) *slot_ptr(0, p) = R.dvs;
+      if (!L.gt) *slot_ptr(1, p) = R.dvt;
+      *slot_ptr(2, p) = R.dths;
+      *slot_ptr(4, p) = R.dbar; *slot_ptr(5, p) = R.dbar2;
     };
     for (int p = e0; p < e1; p += 2) {
       EdgeIn L0, L1;
@@ -844,43 +820,21 @@ __global__ void __launch_bounds__(GNS_BWDS_PHYS_THREADS) gns_bwds_igrad_phys_ker
     const float tha = row_ptr(A.state, state_row(ia), lane)->y, thb = row_ptr(A.state, state_row(ib), lane)->y;
     const float thc = row_ptr(A.state, state_row(ic), lane)->y, thd = row_ptr(A.state, state_row(id), lane)->y;
     const float Fb = row_ptr(A.adj, adj_row(t), lane)->z, Tb = row_ptr(A.adj, adj_row(s), lane)->z;
-    const float ys = e1v.y, taus = e1v.z, shs = e1v.w;
-    const float dl = tha - thb, dl2 = thd - thc;
-    float sA, cA, sB, cB, sD, cD, sC, cC, sD2, cD2;
-    sincosf(ths - tht - dl - shs, &sA, &cA);
-    sincosf(tht - ths - dl + shs, &sB, &cB);
-    sincosf(dl, &sD, &cD);
-    sincosf(tht - ths - dl2 - o0.z, &sC, &cC);
-    sincosf(dl2, &sD2, &cD2);
-    const float yot = ys / taus, yot2 = ys / (taus * taus);
-    const float base = vs * vt * yot;
-    const float kJ = vs * yot2 + vt * vt * ys;
-    const float inner = base * (sA + sB) + kJ * sD;
-    const float Jb = pgbar * (inner > 0.f ? 1.f : (inner < 0.f ? -1.f : 0.f));
-    // d/d(y_s, tau_s, sh_s) of p_from (main.py:91) and of |joule| (main.py:41)
-    const float ybs = Fb * (vs * vt / taus * sA + vs * vs / (taus * taus) * sD) + Jb * (vs * vt / taus * (sA + sB) + (vs / (taus * taus) + vt * vt) * sD);
-    const float tbs = -(Fb * (base * sA + 2.f * vs * vs * yot2 * sD) + Jb * (base * (sA + sB) + 2.f * vs * yot2 * sD)) / taus;
-    const float sbs = Jb * base * cB - (Fb + Jb) * base * cA;
-    // d/d(y_t, tau_t, sh_t) of p_to (main.py:92)
-    const float yot_t = o0.x / o0.y;
-    const float base2 = vt * vs * yot_t;
-    const float ybt = Tb * (vt * vs / o0.y * sC + vt * vt * sD2);
-    const float tbt = -Tb * base2 * sC / o0.y;
-    const float sbt = -Tb * base2 * cC;
+    const LineTrig T = line_trig<false>(ths, tht, tha, thb, thc, thd, e1v.w, o0.z);
+    const LinePro Q = line_prologue(T, vs, vt, e1v.y, e1v.z, o0.x, o0.y, pgbar);
+    // d/d(y_s, tau_s, sh_s) of p_from (main.py:91) and of |joule| (main.py:41), d/d(y_t, tau_t, sh_t) of p_to (main.py:92)
+    const LineParAdj dP = line_param_adjoint(T, Q, vs, vt, e1v.z, o0.y, Fb, Tb);
     f4* rs = row_ptr(IG, row_ein + 3LL * p + 1, lane);
     f4* rt = row_ptr(IG, row_eout + q, lane);
     const f4 os = *rs, ot = *rt;
-    *rs = f4{os.x, os.y + ybs, os.z + tbs, os.w + sbs};
-    *rt = f4{ot.x + ybt, ot.y + tbt, ot.z + sbt, ot.w};
+    *rs = f4{os.x, os.y + dP.ybs, os.z + dP.tbs, os.w + dP.sbs};
+    *rt = f4{ot.x + dP.ybt, ot.y + dP.tbt, ot.z + dP.sbt, ot.w};
     // d/dv of the generator-bus ends, which gns_bwds_phys_kernel does not store (its slots 0 / 1 of the other ends stay as they are)
     const bool gs = is_gen[s] != 0, gt = is_gen[t] != 0;
     if (gs || gt) {
-      float dvs = Fb * (vt * yot * sA + 2.f * vs * yot2 * sD) + Jb * (vt * yot * (sA + sB) + yot2 * sD);
-      float dvt = Fb * (vs * yot * sA) + Jb * (vs * yot * (sA + sB) + 2.f * vt * ys * sD);
-      dvt += Tb * (vs * yot_t * sC + 2.f * vt * o0.x * sD2);
-      dvs += Tb * (vt * yot_t * sC);
-      if (gs) *slot_ptr(0, p) = dvs;
-      if (gt) *slot_ptr(1, p) = dvt;
+      const LineAdj R = line_state_adjoint(T, Q, vs, vt, e1v.y, o0.x, Fb, Tb);
+      if (gs) *slot_ptr(0, p) = R.dvs;
+      if (gt) *slot_ptr(1, p) = R.dvt;
     }
   }
   __syncthreads();

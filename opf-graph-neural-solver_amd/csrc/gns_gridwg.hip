@@ -11,54 +11,10 @@
 //   BUS-2  bus lanes: gather the per-line terms of their own lines, lambda (main.py:45-57), delta_p / delta_q, loss;
 //          falls straight through into BUS-1 of step k+1.
 // No atomics; every sum has a fixed order, so results are bitwise reproducible.
+// (ld4 / ld2, wave_sum, yof, read_row / write_row, sincos_small / sin_small: gns_phys_device.h, shared with gns_gridwg_bwd.hip)
 #include "gns_device.h"
 #include "gns_gridwg.h"
-
-namespace {
-
-struct __attribute__((packed, aligned(4))) GwU4 { float x, y, z, w; };
-struct __attribute__((packed, aligned(4))) GwU2 { float x, y; };
-__device__ __forceinline__ f4 gw_ld4(const float* p) { const GwU4 u = *reinterpret_cast<const GwU4*>(p); return f4{u.x, u.y, u.z, u.w}; }
-__device__ __forceinline__ f2 gw_ld2(const float* p) { const GwU2 u = *reinterpret_cast<const GwU2*>(p); return f2{u.x, u.y}; }
-
-__device__ __forceinline__ float gw_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// main.py:38: 1 / sqrt(r^2 + x^2), each op rounded like torch does
-__device__ __forceinline__ float gw_yof(float r, float x) {
-  return __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(__fmul_rn(r, r), __fmul_rn(x, x))));
-}
-
-// sin / cos on |x| <= pi/4 without range reduction (Cephes single-precision kernels, < 1 ulp); the caller votes
-// wave-wide that every angle is in range and otherwise takes the library path.
-__device__ __forceinline__ void gw_sincos_small(float x, float& s, float& c) {
-  const float z = x * x;
-  const float ps = __builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
-  s = __builtin_fmaf(ps * z, x, x);
-  const float pc = __builtin_fmaf(__builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f);
-  c = __builtin_fmaf(pc * z, z, __builtin_fmaf(-0.5f, z, 1.0f));
-}
-__device__ __forceinline__ float gw_sin_small(float x) {
-  const float z = x * x;
-  const float ps = __builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
-  return __builtin_fmaf(ps * z, x, x);
-}
-
-template <int NF>
-__device__ __forceinline__ void lds_read_row(const float* row, f2 (&dst)[NF / 2]) {
-#pragma unroll
-  for (int i = 0; i < NF / 2; ++i) dst[i] = reinterpret_cast<const f2*>(row)[i];
-}
-template <int NF>
-__device__ __forceinline__ void lds_write_row(float* row, const f2 (&src)[NF / 2]) {
-#pragma unroll
-  for (int i = 0; i < NF / 2; ++i) reinterpret_cast<f2*>(row)[i] = src[i];
-}
-
-}  // namespace
+#include "gns_phys_device.h"
 
 template <int D, int H, bool MULTI, int MAXT, int MINW>
 __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs A) {
@@ -122,12 +78,12 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
     if (bus_wave) {
       float vg = 0.f, pg = 0.f, qg = 0.f;
       if (is_bus) {
-        const f4 bq = gw_ld4(A.buses + (b * N + n) * 6 + 2);      // Pd, Qd, Gs, Bs
+        const f4 bq = ld4(A.buses + (b * N + n) * 6 + 2);      // Pd, Qd, Gs, Bs
         Pd = bq.x; Qd = bq.y; Gs = bq.z; Bs = bq.w;
         for (int q = g0; q < g1; ++q) {                           // generators on this bus, in generator order (main.py:146-151)
           const float* r = A.gens + (b * Gn + gen_idx[q]) * 7;    // (bus_i,Pmax,Pmin,Pg_set,vg,qg,Pg) utils.py:9
-          const f4 ra = gw_ld4(r + 1);
-          const f2 rb = gw_ld2(r + 5);
+          const f4 ra = ld4(r + 1);
+          const f2 rb = ld2(r + 5);
           pmax += ra.x; pmin += ra.y; pset += ra.z; vg += ra.w; qg += rb.x; pg += rb.y;
         }
       }
@@ -135,7 +91,7 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
       sdp = __fsub_rn(__fsub_rn(pg, Pd), __fmul_rn(Gs, __fmul_rn(sv, sv)));     // main.py:150
       sdq = __fadd_rn(__fsub_rn(qg, Qd), __fmul_rn(Bs, __fmul_rn(sv, sv)));     // main.py:152
       // per-grid sums of main.py:45,47-51
-      const float r0 = gw_wave_sum(Pd), r1 = gw_wave_sum(pset), r2 = gw_wave_sum(pmin), r3 = gw_wave_sum(pmax);
+      const float r0 = wave_sum(Pd), r1 = wave_sum(pset), r2 = wave_sum(pmin), r3 = wave_sum(pmax);
       if (lane == 0) { red[4 * WPG + 0 * WPG + wig] = r0; red[4 * WPG + 1 * WPG + wig] = r1; red[4 * WPG + 2 * WPG + wig] = r2; red[4 * WPG + 3 * WPG + wig] = r3; }
     }
     // line parameters: own line e, and - the reference's bus-id-as-line-index quirk - line NUMBER s and line NUMBER t
@@ -143,15 +99,15 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
     float ys = 0.f, taus = 1.f, shs = 0.f, bs = 0.f, yt = 0.f, taut = 1.f, sht = 0.f, bt = 0.f;
     if (edge_wave) {
       const float* lb = A.lines + b * (long long)E * 7;
-      const f4 ea = gw_ld4(lb + e_id * 7 + 2);                     // r, x, b, tau
+      const f4 ea = ld4(lb + e_id * 7 + 2);                     // r, x, b, tau
       const float she = lb[e_id * 7 + 6];
-      const f4 sa = gw_ld4(lb + es * 7 + 2);
+      const f4 sa = ld4(lb + es * 7 + 2);
       shs = lb[es * 7 + 6];
-      const f4 ta = gw_ld4(lb + et * 7 + 2);
+      const f4 ta = ld4(lb + et * 7 + 2);
       sht = lb[et * 7 + 6];
       xt[0] = f2{ea.x, ea.y}; xt[1] = f2{ea.z, ea.w}; xt[2] = f2{she, 0.f};
-      ys = gw_yof(sa.x, sa.y); taus = sa.w; bs = sa.z;
-      yt = gw_yof(ta.x, ta.y); taut = ta.w; bt = ta.z;
+      ys = yof(sa.x, sa.y); taus = sa.w; bs = sa.z;
+      yt = yof(ta.x, ta.y); taut = ta.w; bt = ta.z;
       // phi' of step 0: m = 0, so the bus share of the first layer is zero (main.py:141,155)
       f2 uz[H / 2];
 #pragma unroll
@@ -160,7 +116,7 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
         constexpr int f = decltype(f_)::value;
         f2 a1[H / 2], a2[H / 2];
         phi_tail<C::PHI_IN, H, D>(PT + A.t_off[f], uz, xt, a1, a2);
-        if (is_edge) lds_write_row<H>(h_l + li * UW + f * H, a2);
+        if (is_edge) write_row<H>(h_l + li * UW + f * H, a2);
       });
     }
     __syncthreads();
@@ -236,7 +192,7 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
 #pragma unroll
         for (int i = 0; i < D / 2; ++i) m[i] = m_new[i];
         if (is_bus) plane[n] = f2{sv, sth};
-        const float vs_part = gw_wave_sum(is_bus ? (sv * sv) * Gs : 0.f);         // sum v^2 Gs (main.py:45)
+        const float vs_part = wave_sum(is_bus ? (sv * sv) * Gs : 0.f);         // sum v^2 Gs (main.py:45)
         if (lane == 0) red[(par * 2 + 0) * WPG + wig] = vs_part;
         if (k + 1 < K) {                                              // bus share of phi' for the next step
           static_for<0, NPHI>([&](auto f_) {
@@ -244,7 +200,7 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
             if (MULTI && f == 2 && k + 2 >= K) return;              // phi_m of the last step only feeds the dead L_m
             f2 uh[H / 2];
             phi_head<D, H>(PT + A.t_off[f] + (koff + 1) * A.t_sz[f], m, uh);
-            if (is_bus) lds_write_row<H>(u_l + n * UW + f * H, uh);
+            if (is_bus) write_row<H>(u_l + n * UW + f * H, uh);
           });
         }
       }
@@ -260,8 +216,8 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
         float sA, cA, sB, sD, cD, sC, cC, sD2;
         const float amax = fmaxf(fmaxf(fmaxf(fabsf(angA), fabsf(angB)), fmaxf(fabsf(angC), fabsf(dl))), fabsf(dl2));
         if (__builtin_amdgcn_ballot_w64(!(amax <= 0.785f)) == 0) {
-          gw_sincos_small(angA, sA, cA); sB = gw_sin_small(angB); gw_sincos_small(dl, sD, cD);
-          gw_sincos_small(angC, sC, cC); sD2 = gw_sin_small(dl2);
+          sincos_small(angA, sA, cA); sB = sin_small(angB); sincos_small(dl, sD, cD);
+          sincos_small(angC, sC, cC); sD2 = sin_small(dl2);
         } else {
           sincosf(angA, &sA, &cA); sB = sinf(angB); sincosf(dl, &sD, &cD);
           sincosf(angC, &sC, &cC); sD2 = sinf(dl2);
@@ -275,16 +231,16 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
         const float p_to = base2 * sC + (vt * vt) * yt * sD2;                   // main.py:92
         const float q_to = -base2 * cC + (vt * vt) * (yt * sD2 - bt / 2.f);     // main.py:70-72 == :99
         if (is_edge) phys[li] = f4{p_from, q_from, p_to, q_to};
-        const float j_part = gw_wave_sum(is_edge ? msg : 0.f);                   // main.py:42-43
+        const float j_part = wave_sum(is_edge ? msg : 0.f);                   // main.py:42-43
         if (lane == 0) red[(par * 2 + 1) * WPG + wig] = j_part;
         if (k + 1 < K) {
           static_for<0, NPHI>([&](auto f_) {
             constexpr int f = decltype(f_)::value;
             if (MULTI && f == 2 && k + 2 >= K) return;              // (see BUS-1)
             f2 uh[H / 2], a1[H / 2], a2[H / 2];
-            lds_read_row<H>(u_l + et * UW + f * H, uh);
+            read_row<H>(u_l + et * UW + f * H, uh);
             phi_tail<C::PHI_IN, H, D>(PT + A.t_off[f] + (koff + 1) * A.t_sz[f], uh, xt, a1, a2);
-            if (is_edge) lds_write_row<H>(h_l + li * UW + f * H, a2);
+            if (is_edge) write_row<H>(h_l + li * UW + f * H, a2);
           });
         }
       }
@@ -343,7 +299,7 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_forward_kernel(GnsGwFwdArgs
         A.v_out[b * N + n] = (sv < 0.f) ? 0.f : sv;                              // main.py:201
         A.theta_out[b * N + n] = sth;
       }
-      const float t = gw_wave_sum(tot_lane), l = gw_wave_sum(last_lane);
+      const float t = wave_sum(tot_lane), l = wave_sum(last_lane);
       if (lane == 0) { red[8 * WPG + wig] = t; red[9 * WPG + wig] = l; }
     }
     __syncthreads();

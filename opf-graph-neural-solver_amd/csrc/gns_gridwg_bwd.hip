@@ -7,7 +7,8 @@
 // state read once per step plus the inputs; everything that crosses lanes goes through LDS.
 // Per reverse step k:
 //   P0   bus : close d total / d dp_{k+1} (loss term, main.py:198-199), reduce the adjoint of lambda, publish (v, theta, dpbar)
-//   P1   edge: adjoints of the line physics (main.py:34-104) w.r.t. v, theta of the 2 (+4 bus-id-as-line-index) buses
+//   P1   edge: adjoints of the line physics (main.py:34-104) w.r.t. v, theta of the 2 (+4 bus-id-as-line-index) buses: the one
+//              derivation of gns_phys_device.h, behind its wave-voted small-angle trig
 //   P2   bus : gather them in fixed order; then, per phi family (L_m's first - its upstream is mbar_{k+1} itself):
 //     B    bus : recompute L' from the saved state and back-propagate it layer by layer; each layer's weight gradient is
 //                contracted as soon as its operands exist (sub-record windows, gns_dw.h), the input adjoints come out of
@@ -20,6 +21,7 @@
 // delta_q carries no gradient (identically zero as a function of v, theta: main.py:64-76 vs :83,98-103).
 #include "gns_device.h"
 #include "gns_gridwg.h"
+#include "gns_phys_device.h"
 #ifndef GNS_GWB_KEEP_SLOPES
 #define GNS_GWB_KEEP_SLOPES 1     // as GNS_BWDS_KEEP_SLOPES (gns_backward_split.hip): the slopes of the hidden units are kept from the recomputation
 #endif
@@ -32,39 +34,6 @@
 #endif
 #include "gns_dw.h"
 
-namespace {
-struct __attribute__((packed, aligned(4))) GbU4 { float x, y, z, w; };
-__device__ __forceinline__ f4 gb_ld4(const float* p) { const GbU4 u = *reinterpret_cast<const GbU4*>(p); return f4{u.x, u.y, u.z, u.w}; }
-__device__ __forceinline__ float gb_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float gb_yof(float r, float x) {
-  return __fdiv_rn(1.0f, __fsqrt_rn(__fadd_rn(__fmul_rn(r, r), __fmul_rn(x, x))));
-}
-// sin / cos on |x| <= pi/4 without range reduction (Cephes single-precision kernels, < 1 ulp)
-__device__ __forceinline__ void gb_sincos_small(float x, float& s, float& c) {
-  const float z = x * x;
-  const float ps = __builtin_fmaf(__builtin_fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
-  s = __builtin_fmaf(ps * z, x, x);
-  const float pc = __builtin_fmaf(__builtin_fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f);
-  c = __builtin_fmaf(pc * z, z, __builtin_fmaf(-0.5f, z, 1.0f));
-}
-template <int NF>
-__device__ __forceinline__ void gb_read_row(const float* row, f2 (&dst)[NF / 2]) {
-#pragma unroll
-  for (int i = 0; i < NF / 2; ++i) dst[i] = reinterpret_cast<const f2*>(row)[i];
-}
-template <int NF>
-__device__ __forceinline__ void gb_write_row(float* row, const f2 (&src)[NF / 2]) {
-#pragma unroll
-  for (int i = 0; i < NF / 2; ++i) reinterpret_cast<f2*>(row)[i] = src[i];
-}
-
-constexpr int gb_max(int a, int b) { return a > b ? a : b; }
-}  // namespace
-
 template <int D, int H, bool MULTI>
 struct GwBwdDims {
   using C = GnsDims<D, H, MULTI>;
@@ -72,7 +41,7 @@ struct GwBwdDims {
   static_assert(LIN % 2 == 1, "the bias column of the first-layer record is the free half of the last input pair");
   static constexpr int GL_M = LIN * H + H + H * H + H + D * H + D;        // folded gradient block of L_m (the largest)
   static constexpr int GP = C::PHI_IN * H + H + H * H + H;               // folded gradient block of phi'
-  static constexpr int STG_L = (gb_max(GL_M, GP) + 63) / 64 * 64;        // per-wave stage: an L' (or the line part of a phi') block
+  static constexpr int STG_L = (gns_cmax(GL_M, GP) + 63) / 64 * 64;        // per-wave stage: an L' (or the line part of a phi') block
   static constexpr int STG_P = (H * D + 63) / 64 * 64;                   //                 the latent columns of phi' dW1
   static constexpr int STGF = STG_L + STG_P;
   static constexpr int RECF = GwSub::RECF;
@@ -168,15 +137,15 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_backward_kernel(GnsGwBwdArg
     if (bus_wave) {
       float Pd = 0.f;
       if (is_bus) {
-        const f4 bq = gb_ld4(A.buses + (b * N + n) * 6 + 2);
+        const f4 bq = ld4(A.buses + (b * N + n) * 6 + 2);
         Pd = bq.x; Gs = bq.z;
         for (int q = g0; q < g1_; ++q) {
           const float* r = A.gens + (b * Gn + gen_idx[q]) * 7;
-          const f4 ra = gb_ld4(r + 1);
+          const f4 ra = ld4(r + 1);
           pmax += ra.x; pmin += ra.y; pset += ra.z;
         }
       }
-      const float r0 = gb_wave_sum(Pd), r1 = gb_wave_sum(pset), r2 = gb_wave_sum(pmin), r3 = gb_wave_sum(pmax);
+      const float r0 = wave_sum(Pd), r1 = wave_sum(pset), r2 = wave_sum(pmin), r3 = wave_sum(pmax);
       if (lane == 0) { red[2 * WPG + wig] = r0; red[3 * WPG + wig] = r1; red[4 * WPG + wig] = r2; red[5 * WPG + wig] = r3; }
     }
     f2 xt[2][3];
@@ -185,10 +154,10 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_backward_kernel(GnsGwBwdArg
     for (int ep = 0; ep < 2; ++ep) {
       xt[ep][0] = f2{0.f, 0.f}; xt[ep][1] = f2{0.f, 0.f}; xt[ep][2] = f2{0.f, 0.f};
       if (e_wave[ep]) {
-        const f4 ea = gb_ld4(lb + e_id[ep] * 7 + 2);                    // r, x, b, tau of the lane's own line
+        const f4 ea = ld4(lb + e_id[ep] * 7 + 2);                    // r, x, b, tau of the lane's own line
         const float she = lb[e_id[ep] * 7 + 6];
         xt[ep][0] = f2{ea.x, ea.y}; xt[ep][1] = f2{ea.z, ea.w}; xt[ep][2] = f2{she, 0.f};
-        if (is_e[ep]) ylds[e_id[ep]] = gb_yof(ea.x, ea.y);
+        if (is_e[ep]) ylds[e_id[ep]] = yof(ea.x, ea.y);
       }
     }
     const float gt = (live && A.g_total) ? A.g_total[b] : 0.f;
@@ -245,7 +214,7 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_backward_kernel(GnsGwBwdArg
         dpb = dpbar_in + cdp * s1.z;
         const float lb = dpb * (low2 ? 2.f * (pset - pmin) : 2.f * (pmax - pset));    // d Pg_new / d lambda (main.py:53-57)
         if (is_bus) { plane3[3 * n] = s1.x; plane3[3 * n + 1] = s1.y; plane3[3 * n + 2] = dpb; }
-        const float lsum = gb_wave_sum(is_bus ? lb : 0.f);
+        const float lsum = wave_sum(is_bus ? lb : 0.f);
         if (lane == 0) red[par * WPG + wig] = lsum;
       }
       __syncthreads();
@@ -265,39 +234,11 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_backward_kernel(GnsGwBwdArg
         const float vs = plane3[3 * S_], ths = plane3[3 * S_ + 1], Tb = plane3[3 * S_ + 2];     // dp[s] += p_to   (main.py:95)
         const float vt = plane3[3 * T_], tht = plane3[3 * T_ + 1], Fb = plane3[3 * T_ + 2];     // dp[t] += p_from (main.py:94)
         const float tha = plane3[3 * ia_ + 1], thb = plane3[3 * ib_ + 1], thc = plane3[3 * ic_ + 1], thd = plane3[3 * id_ + 1];
-        const float dl = tha - thb, dl2 = thd - thc;
-        float sA, cA, sB, cB, sD, cD, sC, cC, sD2, cD2;
-        const float angA = ths - tht - dl - shs_, angB = tht - ths - dl + shs_, angC = tht - ths - dl2 - sht_;
-        const float amax = fmaxf(fmaxf(fmaxf(fabsf(angA), fabsf(angB)), fmaxf(fabsf(angC), fabsf(dl))), fabsf(dl2));
-        if (__builtin_amdgcn_ballot_w64(!(amax <= 0.785f)) == 0) {     // every angle of the wave within pi/4: no range reduction
-          gb_sincos_small(angA, sA, cA); gb_sincos_small(angB, sB, cB); gb_sincos_small(dl, sD, cD);
-          gb_sincos_small(angC, sC, cC); gb_sincos_small(dl2, sD2, cD2);
-        } else {
-          sincosf(angA, &sA, &cA); sincosf(angB, &sB, &cB); sincosf(dl, &sD, &cD);
-          sincosf(angC, &sC, &cC); sincosf(dl2, &sD2, &cD2);
-        }
-        // "from" expressions: p_from (main.py:91) and |msg| of the joule loss (main.py:41)
-        const float yot = ys_ / taus_, yot2 = ys_ / (taus_ * taus_);
-        const float base = vs * vt * yot;
-        const float kJ = vs * yot2 + vt * vt * ys_;
-        const float inner = base * (sA + sB) + kJ * sD;
-        const float Jb = pgbar * (inner > 0.f ? 1.f : (inner < 0.f ? -1.f : 0.f));
-        float dvs = Fb * (vt * yot * sA + 2.f * vs * yot2 * sD) + Jb * (vt * yot * (sA + sB) + yot2 * sD);
-        float dvt = Fb * (vs * yot * sA) + Jb * (vs * yot * (sA + sB) + 2.f * vt * ys_ * sD);
-        const float Ab = (Fb + Jb) * base * cA, Bb = Jb * base * cB;
-        const float dbar = Fb * (vs * vs * yot2) * cD + Jb * kJ * cD - Ab - Bb;
-        float dths = Ab - Bb, dtht = Bb - Ab;
-        // "to" expression: p_to (main.py:92)
-        const float yot_t = yt_ / taut_;
-        const float base2 = vt * vs * yot_t;
-        dvt += Tb * (vs * yot_t * sC + 2.f * vt * yt_ * sD2);
-        dvs += Tb * (vt * yot_t * sC);
-        const float Cb = Tb * base2 * cC;
-        const float dbar2 = Tb * vt * vt * yt_ * cD2 - Cb;
-        dtht += Cb; dths -= Cb;
+        const LineTrig T = line_trig<true>(ths, tht, tha, thb, thc, thd, shs_, sht_);
+        const LineAdj R = line_state_adjoint(T, vs, vt, ys_, taus_, yt_, taut_, Fb, Tb, pgbar);
         if (is_e[ep]) {
           f2* sp = reinterpret_cast<f2*>(slots + 6 * (li + ep * WL));
-          sp[0] = f2{dvs, dvt}; sp[1] = f2{dths, dtht}; sp[2] = f2{dbar, dbar2};
+          sp[0] = f2{R.dvs, R.dvt}; sp[1] = f2{R.dths, R.dtht}; sp[2] = f2{R.dbar, R.dbar2};
         }
       }
       __syncthreads();
@@ -439,11 +380,11 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_backward_kernel(GnsGwBwdArg
               }
             }
           });
-          if constexpr (!MULTI) { if (is_bus) gb_write_row<H>(gS_l + n * H, gSacc); }
+          if constexpr (!MULTI) { if (is_bus) write_row<H>(gS_l + n * H, gSacc); }
           f2 uh[H / 2];
           f2 (&mk)[D / 2] = reinterpret_cast<f2 (&)[D / 2]>(xs[2]);
           phi_head<D, H>(PT + A.t_off[pf] + koff * A.t_sz[pf], mk, uh);
-          if (is_bus) gb_write_row<H>(u_l + n * H, uh);
+          if (is_bus) write_row<H>(u_l + n * H, uh);
         }
         __syncthreads();
         if (rb_blk) {
@@ -459,8 +400,8 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_backward_kernel(GnsGwBwdArg
           for (int ep = 0; ep < 2; ++ep) {
             if (!e_wave[ep]) continue;
             f2 uh[H / 2], gh[H / 2], a1[H / 2], a2[H / 2], g2[H / 2], g1[H / 2];
-            gb_read_row<H>(u_l + et[ep] * H, uh);
-            gb_read_row<H>(gS_l + et[ep] * H, gh);
+            read_row<H>(u_l + et[ep] * H, uh);
+            read_row<H>(gS_l + et[ep] * H, gh);
             if (!is_e[ep]) {
 #pragma unroll
               for (int j = 0; j < H / 2; ++j) gh[j] = f2{0.f, 0.f};
@@ -472,7 +413,7 @@ __global__ void __launch_bounds__(MAXT, MINW) gns_gw_backward_kernel(GnsGwBwdArg
             bwd_rows<H, H>(PN + A.n_off[pf] + koff * A.n_sz[pf], g2, g1);
 #pragma unroll
             for (int u = 0; u < H / 2; ++u) g1[u] = g1[u] * GWB_SLOPE_OF(sl, 0, a1, u);
-            if (is_e[ep]) gb_write_row<H>(g1_l + (li + ep * WL) * H, g1);
+            if (is_e[ep]) write_row<H>(g1_l + (li + ep * WL) * H, g1);
             // phi' line columns of dW1, db1 and dW2, db2
             static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putA(rec, lane, j, g1[j]); });
             gws_putB(rec, lane, 0, xt[ep][0]); gws_putB(rec, lane, 1, xt[ep][1]); gws_putB(rec, lane, 2, f2{xt[ep][2].x, 1.f});

@@ -89,6 +89,20 @@ def odd_topologies():
     return out
 
 
+def ring_with_chords_320():
+    """A connected topology of 320 buses no case file has: the ring 1 -> 2 -> ... -> 320 -> 1 plus 100 seeded chords, five generators.
+    (N, f_bus, t_bus, gen_bus), 1-based, as odd_topologies gives them; E = 420 >= N keeps the bus-id-as-line-index gathers of the
+    reference (GNS/main.py:41) in range.  More than 312 buses: the split backward's phys kernel runs without LDS planes."""
+    n = 320
+    rng = np.random.default_rng(320)
+    f, t_ = list(range(1, n + 1)), list(range(2, n + 1)) + [1]
+    while len(f) < n + 100:
+        a, b = (int(z) for z in rng.integers(1, n + 1, size=2))
+        if a != b:
+            f.append(a); t_.append(b)
+    return n, f, t_, [1, 57, 160, 233, 320]
+
+
 def grids_on_topology(n, f_bus, t_bus, gen_bus, batch, seed):
     """(buses[B,N,6], lines[B,E,7], generators[B,Gn,7]) float32 CPU tensors in the layout of GNS/utils.py:17-41 on a given topology,
     continuous columns drawn in the ranges of opf_graph_neural_solver_amd.synth (per-unit values of a 100 MVA base)."""

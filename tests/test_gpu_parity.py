@@ -1085,6 +1085,49 @@ def test_split_backward_modes_agree_with_the_persistent_kernel(case, bt, d, K, m
         amd.set_option('bwd_variant', old[0]); amd.set_option('bwds_mode', old[1])
 
 
+def test_split_backward_without_line_phase_planes_against_oracle(lane_mapping):
+    """The split backward's phys kernel keeps (v, theta, dpbar) of every bus in LDS planes while they fit 160 KB: all three up to 208
+    buses, (v, theta) up to 312 (gns_bwds_phys_lds).  Beyond that its line phase gathers rows from L2 / HBM - a branch no case file
+    reaches (case300 has 300 buses).  320 buses (helpers.grids_on_topology on a ring with chords), 3 grids, K = 2, d = h = 10, three
+    phi nets: d(mean total_loss)/d(params) of the three sweep modes against the float64 oracle, with the bar of
+    test_parameter_gradient_matches_reference_autograd (5e-5 of max|grad|); each mode bitwise reproducible."""
+    import ctypes
+    import opf_graph_neural_solver_amd as amd
+    from helpers import grids_on_topology, last_path, oracle64, ring_with_chords_320
+    n, f, t_, gb = ring_with_chords_320()
+    # the level the library itself picks for this bus count (the host function the launch calls; no C name: its C++ symbol)
+    level = ctypes.c_int(-1)
+    phys_lds = getattr(amd.load_library(), '_Z17gns_bwds_phys_ldsiPi')
+    phys_lds.restype, phys_lds.argtypes = ctypes.c_size_t, [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    phys_lds(n, ctypes.byref(level))
+    assert level.value == 0, f'{n} buses run at plane level {level.value}: this test no longer reaches the branch without planes'
+    phys_lds(300, ctypes.byref(level))
+    assert level.value == 1                                                       # (what case300 reaches)
+    bt, d, h, K = 3, 10, 10, 2
+    bu, li, ge = (x.cuda() for x in grids_on_topology(n, f, t_, gb, bt, 320))
+    torch.manual_seed(5)
+    m = amd.GNS(d, h, K, 0.9, True).cuda()
+    w = dict(a=torch.full((bt,), 1.0 / bt), b=torch.zeros(bt), c=torch.zeros(bt, n), d=torch.zeros(bt, n))      # mean total_loss
+    _, o64 = oracle64(m.flat_parameters(), bu, li, ge, dict(latent_dim=d, hidden_dim=h, K=K, gamma=0.9, multiple_phi=True), range(bt), w)
+
+    def grads():
+        m.zero_grad()
+        v, th, tot, last = m(bu, li, ge)
+        tot.mean().backward()
+        return torch.cat([p.grad.reshape(-1) for p in m.parameters()]).clone()
+
+    old = amd.get_option('bwd_variant'), amd.get_option('bwds_mode')
+    try:
+        for mode in (0, 1, 2):
+            amd.set_option('bwd_variant', 4); amd.set_option('bwds_mode', mode)
+            g1, g2 = grads(), grads()
+            assert last_path('bwd_kernel', 'bwds_mode') == {'bwd_kernel': 4, 'bwds_mode': mode}
+            assert torch.equal(g1, g2), f'mode {mode} is not run-to-run reproducible'
+            assert_close(g1.cpu(), o64['grad_params'], 5e-5, abs_floor=1e-7, what=f'grad_params, mode {mode}')
+    finally:
+        amd.set_option('bwd_variant', old[0]); amd.set_option('bwds_mode', old[1])
+
+
 @pytest.mark.parametrize('d,h,multi', [(13, 12, True), (6, 7, False), (20, 14, True)])
 def test_widths_between_the_compiled_kernels_on_ragged_batches_against_oracle(d, h, multi):
     """A model narrower than a compiled (latent_dim, hidden_dim) pair runs on it zero-padded (gns_common.h, GnsFamilies): (13, 12) on the

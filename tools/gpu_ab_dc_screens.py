@@ -1,5 +1,5 @@
-"""Bit-for-bit A/B of the contingency screens between two builds of the project on one GPU: the three DC screens (``dc``) or the
-two AC screens (``ac``).
+"""Bit-for-bit A/B between two builds of the project on one GPU: the three DC screens (``dc``), the two AC screens (``ac``) or the
+GNS training step (``gns``: forward, parameter gradient, input gradients).
 
 dump     imports the package (and with it the library) from ROOT, runs the fixed set of seeded calls of SET, each differentiable,
          and saves every returned tensor and every gradient to OUT.
@@ -24,8 +24,25 @@ orders, pairs that share a bus and, where the topology has them, parallel lines.
 with zero and with non-zero incoming gradients into it.  case118 x 2 grids with 40 outages and 40 pairs (parallel lines among
 them), where the lane loops make a second trip (N = 118 > 64).
 
-usage: python tools/gpu_ab_dc_screens.py dump dc|ac ROOT OUT
-       python tools/gpu_ab_dc_screens.py compare dc|ac ROOT_A ROOT_B > profiles/.../ab_bitwise.txt"""
+The ``gns`` calls (``GNS.forward`` in training mode and ``.backward()`` under a loss with every upstream gradient non-zero; each
+saves v, theta, total, last and the flat parameter gradient, and the three input gradients where they are asked for) are the smallest
+that reach each branch of the backward kernels' line-physics adjoint (gns_phys_device.h) and per-bus gather, always from the
+inputs and goldens of the tree the TOOL lies in, so both builds see the same numbers:
+  goldens   the lane-per-grid kernels with the split and the persistent backward on ``odd_hub_indegree_40`` (the gather's tail rounds),
+            ``odd_hub_all_gens`` and ``odd_random_40_one_gen`` (generator ends), ``odd_chain_one_way`` (empty lists), ``c14_b3 lowload``
+            (dead lanes)
+  persist   ``bwd_variant`` 1, 2, 3 on case118 x 130, K = 4; ``team`` 1, 2, 4 on case14 x 3
+  split     ``bwds_mode`` 0, 1, 2 on case118 x 130 (plane level 2), case300 x 70 (level 1) and the 320-bus ring with chords of
+            tests/helpers.py x 3 (level 0); ``dw_mfma`` = 0 once
+  igrad     ``gns_backward_inputs`` on case30 x 70 and on ``odd_random_33_many_gens`` (generator ends)
+  gridwg    ``train_mapping`` 2 at ``gw_pack`` 1 and 4 on case30 x 77, and the same batch with a 1 rad phase shift on every line of its
+            first 20 grids: those grids' waves fail the pi / 4 vote and take the library's sincosf.  The tool prints, from the
+            returned theta (the state the FIRST reverse step, k = K-1, reads; the other steps are not checked), how many live grids pass or
+            fail that vote (case30 is one wave per grid; the dead lanes of a wave vote too and are not counted).
+  grouped   one mixed-topology call (``topology_check = 'group'``): case14 x 150 over two outages
+
+usage: python tools/gpu_ab_dc_screens.py dump dc|ac|gns ROOT OUT
+       python tools/gpu_ab_dc_screens.py compare dc|ac|gns ROOT_A ROOT_B > profiles/.../ab_bitwise.txt"""
 import os
 import subprocess
 import sys
@@ -203,10 +220,101 @@ def dump(which, root, out_path):
         run('case118 n1 40 outages', n1, grids, slack, modes=both, outages=rng.choice(E, 40, replace=False).tolist(), rating=rating)
         run(f'case118 n2 40 pairs, {n_parallel} parallel', n2, grids, slack, modes=both, pairs=pairs, rating=rating)
 
-    {'dc': dc_calls, 'ac': ac_calls}[which]()
+    def gns_calls():
+        import opf_graph_neural_solver_amd as amd
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+        import helpers                                           # the goldens and topologies of the tool's own tree, for both builds
+
+        DEFAULTS = {k: amd.get_option(k) for k in ('fwd_mapping', 'train_mapping', 'bwd_variant', 'bwds_mode', 'dw_mfma', 'team', 'gw_pack')}
+
+        def run(name, m, grids, igrad=False, **opts):
+            """One training step under ``opts`` (the other options at their defaults)"""
+            for k, v in {**DEFAULTS, **opts}.items():
+                amd.set_option(k, v)
+            bu, li, ge = (x.detach().clone().to(dev).requires_grad_(igrad) for x in grids)
+            m.zero_grad()
+            v, th, tot, last = m(bu, li, ge)
+            loss = (tot * weights(tot.shape, 41).float()).sum() + (last * weights(last.shape, 42).float()).sum() \
+                + (v * weights(v.shape, 43).float()).sum() + (th * weights(th.shape, 44).float()).sum()
+            loss.backward()
+            m.check_status()
+            for label, x in (('v', v), ('theta', th), ('total', tot), ('last', last)):
+                out[f'{name} {label}'] = x.detach().cpu()
+            out[f'{name} grad_params'] = torch.cat([p.grad.reshape(-1) for p in m.parameters()]).cpu()
+            if igrad:
+                for label, x in (('grad_buses', bu), ('grad_lines', li), ('grad_generators', ge)):
+                    out[f'{name} {label}'] = x.grad.detach().cpu()
+            return th.detach(), li.detach()
+
+        def model(d, h, K, multi, seed=7):
+            torch.manual_seed(seed)
+            return amd.GNS(d, h, K, 0.9, multi).to(dev)
+
+        def golden(name):
+            g = helpers.load_golden(name)
+            c = helpers.cfg_of(g)
+            m = model(c['latent_dim'], c['hidden_dim'], c['K'], c['multiple_phi'])
+            return m, tuple(torch.as_tensor(g[k]) for k in ('buses', 'lines', 'generators'))
+
+        for name in ('odd_hub_indegree_40_b2_K3_d10_multi', 'odd_hub_all_gens_b2_K4_d10_single', 'odd_random_40_one_gen_b2_K4_d20_multi',
+                     'odd_chain_one_way_b2_K2_d20_single', 'c14_b3_K4_d20_multi_lowload'):
+            m, grids = golden(name)
+            run(f'{name} split', m, grids, fwd_mapping=1, train_mapping=1, bwd_variant=4)
+            run(f'{name} persistent', m, grids, fwd_mapping=1, train_mapping=1, bwd_variant=2 if 'multi' in name else 1)
+
+        grids = amd.synth.synth_grids(118, 130, seed=13)
+        m = model(20, 10, 4, True)
+        for var in (1, 2, 3):
+            run(f'case118 x 130 bwd_variant={var}', m, grids, fwd_mapping=1, train_mapping=1, bwd_variant=var)
+        for mode in (0, 1, 2):
+            run(f'case118 x 130 bwds_mode={mode}', m, grids, fwd_mapping=1, train_mapping=1, bwd_variant=4, bwds_mode=mode)
+        run('case118 x 130 bwd_variant=4 dw_mfma=0', m, grids, fwd_mapping=1, train_mapping=1, bwd_variant=4, dw_mfma=0)
+        g14 = amd.synth.synth_grids(14, 3, seed=13)
+        m14 = model(20, 10, 4, True)
+        for team in (1, 2, 4):
+            run(f'case14 x 3 team={team}', m14, g14, fwd_mapping=1, train_mapping=1, bwd_variant=2, team=team)
+        grids = amd.synth.synth_grids(300, 70, seed=13)
+        for mode in (0, 1, 2):
+            run(f'case300 x 70 bwds_mode={mode}', m, grids, fwd_mapping=1, train_mapping=1, bwd_variant=4, bwds_mode=mode)
+        n, f, t_, gb = helpers.ring_with_chords_320()
+        grids = helpers.grids_on_topology(n, f, t_, gb, 3, 320)
+        m320 = model(10, 10, 2, True)
+        for mode in (0, 1, 2):
+            run(f'ring320 x 3 bwds_mode={mode}', m320, grids, fwd_mapping=1, train_mapping=1, bwd_variant=4, bwds_mode=mode)
+
+        run('case30 x 70 input gradients', model(20, 10, 3, True), amd.synth.synth_grids(30, 70, seed=13), igrad=True)
+        m, grids = golden('odd_random_33_many_gens_b2_K4_d20_single')
+        run('odd_random_33_many_gens input gradients', m, grids, igrad=True)
+
+        def trig_paths(th, li):
+            """Grids whose line angles at the returned state (what reverse step K-1 reads) pass / fail the grid-per-workgroup backward's pi / 4 vote"""
+            src, dst, sh = li[0, :, 0].long() - 1, li[0, :, 1].long() - 1, li[:, :, 6]
+            ds = th[:, src[src]] - th[:, dst[src]]                   # the reference gathers per-line arrays with bus ids (main.py:41)
+            dt = th[:, dst[dst]] - th[:, src[dst]]
+            dth = th[:, src] - th[:, dst]
+            amax = torch.stack([(dth - ds - sh[:, src]).abs(), (-dth - ds + sh[:, src]).abs(), (-dth - dt - sh[:, dst]).abs(), ds.abs(), dt.abs()]).amax(dim=(0, 2))
+            return int((amax <= 0.785).sum()), int((amax > 0.785).sum())
+
+        g30 = amd.synth.synth_grids(30, 77, seed=13)
+        shifted = tuple(x.clone() for x in g30)
+        shifted[1][:20, :, 6] += 1.0
+        m30 = model(10, 10, 3, False)
+        for pack in (1, 4):
+            for tag, grids in (('', g30), (' 1 rad shift in 20 grids', shifted)):
+                th, li = run(f'case30 x 77 train_mapping=2 gw_pack={pack}{tag}', m30, grids, train_mapping=2, gw_pack=pack)
+                small, lib = trig_paths(th, li)
+                print(f'case30 x 77 gw_pack={pack}{tag}: reverse step k = K-1 (estimate from the returned theta): {small} grids on the small-angle path, {lib} on the library path', flush=True)
+
+        mg = model(20, 10, 3, True)
+        mg.topology_check = 'group'
+        run('case14 x 150 two topologies grouped', mg, amd.synth.contingency_grids(14, 150, [4, 13], seed=11, shuffle=True)[:3])
+        for k, v in DEFAULTS.items():
+            amd.set_option(k, v)
+
+    {'dc': dc_calls, 'ac': ac_calls, 'gns': gns_calls}[which]()
     torch.cuda.synchronize()
     torch.save(out, out_path)
-    print(f'{root}: {len(out)} tensors of the {which} screens from {powerflow.__file__}', flush=True)
+    print(f'{root}: {len(out)} tensors of the {which} set from {powerflow.__file__}', flush=True)
 
 
 def compare(which, root_a, root_b):
@@ -247,9 +355,9 @@ def compare(which, root_a, root_b):
 
 
 if __name__ == '__main__':
-    if len(sys.argv) == 5 and sys.argv[1] == 'dump' and sys.argv[2] in ('dc', 'ac'):
+    if len(sys.argv) == 5 and sys.argv[1] == 'dump' and sys.argv[2] in ('dc', 'ac', 'gns'):
         dump(*sys.argv[2:])
-    elif len(sys.argv) == 5 and sys.argv[1] == 'compare' and sys.argv[2] in ('dc', 'ac'):
+    elif len(sys.argv) == 5 and sys.argv[1] == 'compare' and sys.argv[2] in ('dc', 'ac', 'gns'):
         sys.exit(compare(*sys.argv[2:]))
     else:
         sys.exit(__doc__)

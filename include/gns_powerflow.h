@@ -938,7 +938,7 @@ int gns_acn2_screen(const gns_pf_config* cfg, const void* topo_host, const void*
  * output is asked for, GNS_EINVAL for a NULL workspace and GNS_ESIZE for a short one.  Every refusal comes before any launch;
  * nothing is allocated and the host is not synchronised.
  * Not here: batches that mix topologies, a generator plus two lines (a generator with one line: "AC generator contingency
- * screening" below, forward only), generator reactive limits, second derivatives. */
+ * screening" below, with gns_acg1_adjoint), generator reactive limits, second derivatives. */
 int gns_acn2_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_pair, size_t* bytes);
 int gns_acn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
                      const float* buses, const float* lines, const float* generators, int64_t Bt,
@@ -1014,8 +1014,8 @@ int gns_acn2_adjoint(const gns_pf_config* cfg, const void* topo_host, const void
  * image is above GNS_PF_LDS_MAX_BYTES.  gns_acg1_workspace_bytes: GNS_EINVAL for a NULL bytes, Bt <= 0, n_row <= 0 and what the
  * call refuses of the set; it does not refuse a large image.  Every refusal comes before any launch; nothing is allocated and the
  * host is not synchronised.
- * Not here: an adjoint (this screen has no gradients yet), reactive limits on the remaining units, Pmax / Pmin limits on
- * the pickup, batches that mix topologies, a generator plus two lines. */
+ * Gradients: gns_acg1_adjoint, below.  Not here: reactive limits on the remaining units, Pmax / Pmin limits on the pickup, batches
+ * that mix topologies, a generator plus two lines. */
 int gns_acg1_workspace_bytes(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
                              int32_t n_member, int64_t Bt, int32_t n_row, size_t* bytes);
 int gns_acg1_screen(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
@@ -1029,6 +1029,72 @@ int gns_acg1_screen(const gns_pf_config* cfg, const void* set_host, const void* 
                     double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max,
                     int32_t* v_max_bus, uint8_t* converged, int32_t* iterations, double* mismatch,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* Gradients of the AC generator screen.  gns_acg1_adjoint is gns_acn1_adjoint ("Gradients of the AC screen" above) per row of a
+ * gns_acg1_screen call.  It takes the arguments of that call up to pickup_per_grid (the same set, lists, islanding mask, rating and
+ * pickup), its outputs v, theta [Bt,n_row,N], converged, worst_line, v_min_bus, v_max_bus [Bt,n_row] and the base_converged [Bt] it
+ * was given, and the incoming gradients of a loss of its nine fp64 outputs: grad_v, grad_theta [Bt,n_row,N], grad_p_from,
+ * grad_q_from, grad_p_to, grad_q_to [Bt,n_row,E], grad_worst_loading, grad_v_min, grad_v_max [Bt,n_row] (each may be NULL: zero).
+ * It writes dl/d(input) into grad_buses [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32 and dl/d(pickup weights) into
+ * grad_pickup [Bt,Gn] fp64, a row per grid whether the weights are per grid or shared; each may be NULL (not computed; with all four
+ * NULL nothing is launched).  Every element of each non-NULL output is written (overwritten, not accumulated).  The state is the
+ * forward's: Newton-Raphson is not run again, and the warm start (a freed bus's old set point included) is not differentiated.
+ *
+ * Method, per solved row (grid, (g, k)): the implicit function theorem on the grid with generator row g deleted and line k out, at
+ * the forward's state, on the row's own blob (the member without g) and gns_acn1_screen's Y-bus view: one factorisation of the
+ * row's Jacobian, one transposed solve, gns_acn1_adjoint's bus and line algebra unchanged (row (g, k) adds exactly 0 to line k's
+ * own columns).  What the generator brings:
+ *   unknowns and roles are the member's.  A freed sole-unit bus is PQ: its lambda_Q feeds Qd and Bs, and it gives no vg gradient.
+ *   vg goes to the first REMAINING unit listed on a PV or slack bus of the member, at that unit's original generator row; the lost
+ *   unit's vg gets exactly 0; a slack with no unit left has |V| = 1, a constant.
+ *   Pg.  mu_h = lambda_P of the bus of h, 0 at the slack, in the sign gns_acn1_adjoint gives Pg.  A remaining unit h != g gets
+ *   dl/dPg_h = mu_h.  With W = W_g > 0 as the forward sums it, the lost unit gets dl/dPg_g = M = sum_{h != g} mu_h (w_h / W), summed
+ *   in generator-row order; when the slack picks up (pickup NULL, or W exactly 0) it gets exactly 0.
+ *   Weights.  For h != g, dl/dw_h = Pg_g (mu_h - M) / W, and dl/dw_g = 0.  The W == 0 branch is not differentiated: it gives the
+ *   weights 0.  A caller whose weights are a column of the generators ('pmax': column 1) adds grad_pickup into that column.
+ *
+ * Contract, failure rules and arithmetic: gns_acn1_adjoint's, with "row" for "outage": gns_pf_adjoint's columns (Pd, Qd, Gs, Bs; r,
+ *   x, b, tau, shift; Pg, vg), every other column 0; a line whose id columns are not buses of the grid gets a NaN row; rating is a
+ *   constant.  A row whose incoming gradients are all exactly zero or NULL is skipped, never multiplied by zero.  A row with
+ *   converged == 0 (an islanding row, a stopped or unconverged iteration, NaN / -1) and a non-zero incoming gradient, a zero or
+ *   non-finite pivot, or a non-finite lambda: all gradient rows of that grid, grad_pickup's included, are NaN.  A grid with
+ *   base_converged == 0 gets NaN rows when an incoming gradient of it is non-zero, zero rows otherwise.  Other grids are unaffected.
+ *   fp64 throughout, the three input gradients rounded once to fp32.  No atomics, every sum in a fixed order: a grid's gradient is
+ *   bit-identical alone, in any batch and from run to run for the same list.  The order and the chunking of the list set the order
+ *   of the sums over rows, so another order of the same rows may change the last bits.
+ *
+ * Kernels (gns_acg1.hip), three launches: the base Y-bus of every grid from the first member's pattern; one wave per (grid, chunk of
+ * C consecutive rows of the list) with gns_pf_solve's LDS image, the launch asking for the largest member's; one wave per grid that
+ * sums the chunks' partials in order, applies the contract and writes vg, Pg and the weights by original generator row.  Each row
+ * takes its blob after gns_acg1_screen's member checks, builds the same view and sums W_g the same way, then runs the routine of the
+ * line adjoints (acn_adjoint_row, gns_acn_adjoint_device.h) with the generator part of the partial laid out by generator row.
+ * C = max(1, ceil(n_row / 64)): from the list's length alone, never from Bt; a grid has at most 64 partials however long the list.
+ * Workspace (gns_acg1_adjoint_workspace_bytes): the base Y-bus (gns_acg1_workspace_bytes' figure) plus Bt * ceil(n_row / C) partials
+ * of 4 N + 5 E + 4 Gn + 1 doubles, each part rounded up to 256 bytes.
+ *
+ * Errors, in order: GNS_EINVAL for what gns_acg1_screen refuses of cfg, the set, the inputs, the lists, the islanding mask,
+ * rating_per_grid, pickup_per_grid and Bt, for a NULL v, theta, converged, worst_line, v_min_bus, v_max_bus or base_converged, for
+ * a member whose by-bus lists name something that is not a generator row, or for Bt * ceil(n_row / C) above 2^31 - 1; then
+ * GNS_EUNSUPPORTED, for the whole call, when any member's LDS image is above GNS_PF_LDS_MAX_BYTES (from the workspace query too,
+ * unlike gns_acg1_workspace_bytes); then, when an output is asked for, GNS_EINVAL for a NULL workspace and GNS_ESIZE for a short one.
+ * Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
+ * Not here: batches that mix topologies, reactive limits on the remaining units, Pmax / Pmin limits on the pickup, a generator
+ * plus two lines, second derivatives. */
+int gns_acg1_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* set_host, size_t set_words, const int32_t* member_off,
+                                     int32_t n_member, int64_t Bt, int32_t n_row, size_t* bytes);
+int gns_acg1_adjoint(const gns_pf_config* cfg, const void* set_host, const void* set_dev, size_t set_words,
+                     const int32_t* member_off_host, const int32_t* member_off_dev, int32_t n_member,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const int32_t* gen_host, const int32_t* gen_dev,
+                     const int32_t* row_cols_host, const int32_t* row_cols_dev, int32_t n_row, const uint8_t* islanding,
+                     const double* rating, int32_t rating_per_grid, const double* pickup, int32_t pickup_per_grid,
+                     const double* v, const double* theta, const uint8_t* converged, const int32_t* worst_line,
+                     const int32_t* v_min_bus, const int32_t* v_max_bus, const uint8_t* base_converged,
+                     const double* grad_v, const double* grad_theta, const double* grad_p_from, const double* grad_q_from,
+                     const double* grad_p_to, const double* grad_q_to, const double* grad_worst_loading,
+                     const double* grad_v_min, const double* grad_v_max,
+                     float* grad_buses, float* grad_lines, float* grad_generators, double* grad_pickup,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -153,8 +153,11 @@ def load_library():
     lib.gns_acg1_workspace_bytes.argtypes = [pfcp, vp, sz, vp, i32, i64, i32, ctypes.POINTER(sz)]
     lib.gns_acg1_screen.argtypes = [pfcp, vp, vp, sz, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32] + \
         [vp] * 18 + [vp, sz, vp]
+    lib.gns_acg1_adjoint_workspace_bytes.argtypes = [pfcp, vp, sz, vp, i32, i64, i32, ctypes.POINTER(sz)]
+    lib.gns_acg1_adjoint.argtypes = [pfcp, vp, vp, sz, vp, vp, i32, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32] + \
+        [vp] * 20 + [vp, sz, vp]
     for f in (PF_EXPORTS + FD_EXPORTS + DC_EXPORTS + DCN1_EXPORTS + DCN2_EXPORTS + DCN2_ADJOINT_EXPORTS + ACN1_EXPORTS + ACN1_ADJOINT_EXPORTS +
-              ACN2_EXPORTS + ACN2_ADJOINT_EXPORTS + DCG1_EXPORTS + DCG1_ADJOINT_EXPORTS + ACG1_EXPORTS):
+              ACN2_EXPORTS + ACN2_ADJOINT_EXPORTS + DCG1_EXPORTS + DCG1_ADJOINT_EXPORTS + ACG1_EXPORTS + ACG1_ADJOINT_EXPORTS):
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
               'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
@@ -206,6 +209,8 @@ DCG1_ADJOINT_EXPORTS = ('gns_dcg1_adjoint_lds_bytes', 'gns_dcg1_adjoint_workspac
 # the AC generator contingency screen's C-ABI (include/gns_powerflow.h, "AC generator contingency screening"): on a set of
 # Newton-Raphson blobs, each the analysis without one generator row (gns_pf_prepare_topology_out_gen)
 ACG1_EXPORTS = ('gns_acg1_workspace_bytes', 'gns_acg1_screen')
+# the gradients of the AC generator screen (include/gns_powerflow.h, "Gradients of the AC generator screen")
+ACG1_ADJOINT_EXPORTS = ('gns_acg1_adjoint_workspace_bytes', 'gns_acg1_adjoint')
 # the limits of include/gns_powerflow.h
 PF_LDS_MAX_BYTES = 163840
 PF_MAX_SLOTS = 65535

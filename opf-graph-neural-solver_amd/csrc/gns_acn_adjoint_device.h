@@ -4,6 +4,9 @@
 // the row's line or lines, templated on the Y-bus view as acn_solve_row is), the row kernel (gns_acn_adjoint_kernel<M>: acn_view,
 // the forward's prologue, then acn_adjoint_row, over a chunk's rows) and the kernel that sums a grid's partials.  Host: the workspace
 // query and an adjoint call (acn_adjoint_call<Rows>), on the screen's trait.  Both adjoints are this code at M = 1 and M = 2.
+// gns_acg1_adjoint (gns_acg1.hip: generator outages) has a row kernel, a reduce kernel and an entry point of its own on a set of
+// blobs; its rows run acn_adjoint_row from here with the generator part of a partial laid out by generator row (the Gen hook), and
+// its reduce kernel sums the buses and the lines with the pieces of the reduce kernel here.
 #pragma once
 #include "gns_acn1_device.h"
 
@@ -111,11 +114,24 @@ __device__ __forceinline__ void acn1_flow_cot_bus(const int i, const int N, cons
   }
 }
 
+// The generator part of a partial as the line screens lay it out: a double per generator slot (the blob's by-bus order), dl/dvg.
+// Every row of those screens runs on the one base blob, so the slots mean the same in every row, and Pg is read off the bus sums.
+struct AcnSlotPartial {
+  static constexpr int GEN = 1;            // doubles per generator
+};
+
 // Doubles of one (grid, chunk) partial: per bus the sums of lambda_P, lambda_Q, |V|^2 lambda_P, |V|^2 lambda_Q; per line its five
-// columns; per generator slot (the blob's by-bus order) dl/dvg; the chunk's status
+// columns; the generator part, Layout::GEN doubles per generator; the chunk's status
+template <class Layout = AcnSlotPartial>
 __device__ __host__ inline int64_t acn1_adjoint_partial(const int32_t* h) {
-  return 4 * (int64_t)h[PH_N] + 5 * (int64_t)h[PH_E] + (int64_t)h[PH_GN] + 1;
+  return 4 * (int64_t)h[PH_N] + 5 * (int64_t)h[PH_E] + Layout::GEN * (int64_t)h[PH_GN] + 1;
 }
+
+// acn_adjoint_row's one hook, the generator part of a row.  The line screens' (this one, which compiles to nothing): dl/dvg of the
+// first generator of a PV / slack bus into that generator's slot.  gns_acg1.hip's Acg1Gen, for rows whose blobs differ: the slots
+// that are the blob's (gen_ptr[N] of them), dl/dvg into the unit's original generator row, and a call per remaining unit
+// (unit: its row and its bus's lambda_P) and one after them (lost), for what Pg and the pickup weights get.
+struct AcnSlotGen {};
 
 // The wave's exit with the chunk's status alone (its sums are not read then)
 __device__ __forceinline__ void acn1_partial_status(double* part, const int np, const double status) {
@@ -128,11 +144,13 @@ __device__ __forceinline__ void acn1_partial_status(double* part, const int np, 
 // solve, and the bus, generator and line sums added into the chunk's partial `part`, every lane into the addresses it alone owns.
 // False when the row gives the grid a NaN gradient (a zero or non-finite pivot, a non-finite lambda); the same in every lane.
 // Flows and flow cotangents are skipped at every line Y.out names, and the row adds exactly 0 to those lines' own columns.
-template <class YB>   // an AcnYbus<M>
+template <class YB, class Gen = AcnSlotGen>   // an AcnYbus<M>; AcnSlotGen, or a hook with unit() and lost() (Acg1Gen)
 __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo, const float* line, const size_t row, const YB& Y,
                                                 const double* rt, const Acn1Grad& gr, const double* __restrict__ v_in,
                                                 const double* __restrict__ th_in, const int32_t* __restrict__ wl_in,
-                                                const int32_t* __restrict__ lo_in, const int32_t* __restrict__ hi_in, double* part) {
+                                                const int32_t* __restrict__ lo_in, const int32_t* __restrict__ hi_in, double* part,
+                                                const Gen& gen = Gen()) {
+  constexpr bool by_row = !std::is_same_v<Gen, AcnSlotGen>;   // the generator part by original generator row, not by slot
   extern __shared__ double lds[];
   const int lane = threadIdx.x;
   const int N = topo[PH_N], E = topo[PH_E], Gn = topo[PH_GN], slack = topo[PH_SLACK], dim = topo[PH_DIM];
@@ -141,6 +159,7 @@ __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo
   const int32_t* th_idx = topo + topo[PH_TH_IDX];
   const int32_t* vm_idx = topo + topo[PH_VM_IDX];
   const int32_t* gen_ptr = topo + topo[PH_GEN_PTR];
+  const int32_t* gen_idx = topo + topo[PH_GEN_IDX];
   const int32_t* y_ptr = topo + topo[PH_Y_PTR];
   const int32_t* y_col = topo + topo[PH_Y_COL];
   const int32_t* y_diag = topo + topo[PH_Y_DIAG];
@@ -154,7 +173,7 @@ __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo
   const int2* t_ops = reinterpret_cast<const int2*>(topo + topo[PH_T_OPS]);
   double* part_bus = part;                 // [N][4]
   double* part_line = part + 4 * N;        // [E][5]
-  double* part_gen = part_line + 5 * E;    // [Gn]
+  double* part_gen = part_line + 5 * E;    // [Gn], or the hook's layout
 
   double* F = lds;                         // Newton-Raphson's image: [nnzLU] factor, then [dim] right-hand side / lambda
   double* rhs = lds + nnzLU;
@@ -246,13 +265,15 @@ __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo
     double* pb = part_bus + 4 * i;
     pb[0] += lp; pb[1] += lq; pb[2] += m2 * lp; pb[3] += m2 * lq;
   }
-  for (int q = lane; q < Gn; q += PF_THREADS) {      // a lane per generator slot, in the blob's by-bus order
+  const int n_slot = by_row ? gen_ptr[N] : Gn;       // a blob without a generator row lists one slot fewer
+  for (int q = lane; q < n_slot; q += PF_THREADS) {  // a lane per generator slot, in the blob's by-bus order
     int b = 0, hi = N;                               // the bus of slot q: gen_ptr[b] <= q < gen_ptr[b + 1]
     while (hi - b > 1) {
       const int mid = (b + hi) >> 1;
       if (gen_ptr[mid] <= q) b = mid;
       else hi = mid;
     }
+    if constexpr (by_row) gen.unit(part_gen, gen_idx[q], lamP[b]);
     if (q != gen_ptr[b] || role[b] == 0) continue;   // the first generator of a PV / slack bus sets |V_b|
     const double uc = Vr[b] / Vm[b], us = Vi[b] / Vm[b];   // e^{j theta_b}
     double acc = 0.0;
@@ -266,8 +287,9 @@ __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo
       if (c == b) { dr += uc * Ir[b] + us * Ii[b]; di += us * Ir[b] - uc * Ii[b]; }   // ... + e^{j theta_b} conj(I_b) at c = b
       acc += lamP[c] * dr + lamQ[c] * di;
     }
-    part_gen[q] += dV[b] - acc;
+    part_gen[by_row ? gen_idx[q] : q] += dV[b] - acc;
   }
+  if constexpr (by_row) gen.lost(part_gen);
   for (int e = lane; e < E; e += PF_THREADS) {      // a line per lane, over its four stamps; the row adds nothing to a line that is out
     int a, b2;
     if (Y.out(e) || !acn1_line_ends(line, e, N, a, b2)) continue;
@@ -352,6 +374,63 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acn_adjoint_kernel(const int32
   acn1_partial_status(part, np, !solved_row && conv0[g] == 0 ? ACN1_PART_UNSOLVED_ZERO : ACN1_PART_OK);
 }
 
+// The pieces of a reduce kernel (a wave per grid g; part: the grid's first partial, np doubles each), shared with gns_acg1.hip.
+
+// Whether a chunk of the grid says NaN (bad) and whether any holds sums (solved); the same in every lane
+__device__ __forceinline__ void acn1_reduce_status(const double* part, const int nchunks, const int np, bool& bad, bool& solved) {
+  bool b = false, s = false;
+  for (int c = threadIdx.x; c < nchunks; c += PF_THREADS) {
+    const double status = part[(size_t)c * np + np - 1];
+    b |= status != ACN1_PART_OK && status != ACN1_PART_UNSOLVED_ZERO;
+    s |= status != ACN1_PART_UNSOLVED_ZERO;
+  }
+  bad = __ballot(b) != 0;
+  solved = __ballot(s) != 0;
+}
+
+// Every element of the grid's three gradient rows is `fill`
+__device__ __forceinline__ void acn1_reduce_fill(const int g, const int N, const int E, const int Gn, const float fill, float* gb_out,
+                                                 float* gl_out, float* gg_out) {
+  const int lane = threadIdx.x;
+  if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = fill;
+  if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = fill;
+  if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = fill;
+}
+
+// The grid's bus rows: the chunks in order, the contract (0.0 - x rather than -x: an exact zero stays +0)
+__device__ __forceinline__ void acn1_reduce_buses(const int g, const int N, const int nchunks, const int np, const double* part,
+                                                  float* gb_out) {
+  for (int i = threadIdx.x; i < N; i += PF_THREADS) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < nchunks; ++c)
+      for (int u = 0; u < 4; ++u) s[u] += part[(size_t)c * np + 4 * i + u];
+    float* row = gb_out + ((size_t)g * N + i) * 6;
+    row[0] = 0.0f; row[1] = 0.0f;
+    row[2] = (float)(0.0 - s[0]);          // Pd
+    row[3] = (float)(0.0 - s[1]);          // Qd
+    row[4] = (float)(0.0 - s[2]);          // Gs
+    row[5] = (float)s[3];                  // Bs
+  }
+}
+
+// The grid's line rows: the chunks in order; a line whose id columns are not buses of the grid gets a NaN row
+__device__ __forceinline__ void acn1_reduce_lines(const int g, const int N, const int E, const float* line, const int nchunks,
+                                                  const int np, const double* part, float* gl_out) {
+  for (int e = threadIdx.x; e < E; e += PF_THREADS) {
+    float* row = gl_out + ((size_t)g * E + e) * 7;
+    int f, t;
+    if (!acn1_line_ends(line, e, N, f, t)) {
+      for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
+      continue;
+    }
+    double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < nchunks; ++c)
+      for (int u = 0; u < 5; ++u) s[u] += part[(size_t)c * np + 4 * N + 5 * e + u];
+    row[0] = 0.0f; row[1] = 0.0f;
+    for (int u = 0; u < 5; ++u) row[2 + u] = (float)s[u];
+  }
+}
+
 // A wave per grid: the chunks' partials summed in order, the contract applied, every element of the three gradient rows written
 __global__ __launch_bounds__(PF_THREADS) void gns_acn1_adjoint_reduce_kernel(const int32_t* __restrict__ topo,
                                                                              const float* __restrict__ lines, const int nchunks,
@@ -366,33 +445,14 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acn1_adjoint_reduce_kernel(con
   const double* part = partials + (size_t)g * nchunks * np;
   const float* line = lines + (size_t)g * E * 7;
 
-  bool bad = false, solved = false;
-  for (int c = lane; c < nchunks; c += PF_THREADS) {
-    const double status = part[(size_t)c * np + np - 1];
-    bad |= status != ACN1_PART_OK && status != ACN1_PART_UNSOLVED_ZERO;
-    solved |= status != ACN1_PART_UNSOLVED_ZERO;
-  }
-  const float fill = __ballot(bad) ? __builtin_nanf("") : 0.0f;
-  if (__ballot(bad) || !__ballot(solved)) {
-    if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = fill;
-    if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = fill;
-    if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = fill;
+  bool bad, solved;
+  acn1_reduce_status(part, nchunks, np, bad, solved);
+  if (bad || !solved) {
+    acn1_reduce_fill(g, N, E, Gn, bad ? __builtin_nanf("") : 0.0f, gb_out, gl_out, gg_out);
     return;
   }
 
-  // (0.0 - x rather than -x: an exact zero stays +0)
-  if (gb_out)
-    for (int i = lane; i < N; i += PF_THREADS) {
-      double s[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int c = 0; c < nchunks; ++c)
-        for (int u = 0; u < 4; ++u) s[u] += part[(size_t)c * np + 4 * i + u];
-      float* row = gb_out + ((size_t)g * N + i) * 6;
-      row[0] = 0.0f; row[1] = 0.0f;
-      row[2] = (float)(0.0 - s[0]);          // Pd
-      row[3] = (float)(0.0 - s[1]);          // Qd
-      row[4] = (float)(0.0 - s[2]);          // Gs
-      row[5] = (float)s[3];                  // Bs
-    }
+  if (gb_out) acn1_reduce_buses(g, N, nchunks, np, part, gb_out);
   if (gg_out)
     for (int q = lane; q < Gn; q += PF_THREADS) {
       int b = 0, hi = N;
@@ -412,27 +472,15 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acn1_adjoint_reduce_kernel(con
       row[5] = 0.0f;
       row[6] = (float)dp;                    // Pg: S_spec += Pg
     }
-  if (gl_out)
-    for (int e = lane; e < E; e += PF_THREADS) {
-      float* row = gl_out + ((size_t)g * E + e) * 7;
-      int f, t;
-      if (!acn1_line_ends(line, e, N, f, t)) {
-        for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
-        continue;
-      }
-      double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-      for (int c = 0; c < nchunks; ++c)
-        for (int u = 0; u < 5; ++u) s[u] += part[(size_t)c * np + 4 * N + 5 * e + u];
-      row[0] = 0.0f; row[1] = 0.0f;
-      for (int u = 0; u < 5; ++u) row[2 + u] = (float)s[u];
-    }
+  if (gl_out) acn1_reduce_lines(g, N, E, line, nchunks, np, part, gl_out);
 }
 
 // ---- host: what gns_acn1_adjoint and gns_acn2_adjoint (and their workspace queries) do alike
 
 // The partials of a call: one per (grid, chunk), rounded up to 256 bytes
+template <class Layout = AcnSlotPartial>
 inline size_t acn1_adjoint_partial_bytes(const int32_t* h, int64_t Bt, int64_t nchunks) {
-  return ((size_t)Bt * nchunks * acn1_adjoint_partial(h) * sizeof(double) + 255) & ~(size_t)255;
+  return ((size_t)Bt * nchunks * acn1_adjoint_partial<Layout>(h) * sizeof(double) + 255) & ~(size_t)255;
 }
 
 // The workspace of either adjoint: the base Y-bus of every grid, then a partial per (grid, chunk of Rows::chunk(n_row) rows of the

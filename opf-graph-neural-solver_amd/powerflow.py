@@ -50,7 +50,9 @@ per pair one factorisation and one transposed solve at the forward's state.
 ``ac_generator_contingency_screen(...)`` is the AC screen of the rows ``dc_generator_contingency_screen`` takes, a generator out alone
 or with a line out as well: the bus of a lost unit may turn from PV to PQ, so the topology is analysed once per distinct generator of
 the list (``gns_pf_prepare_topology_out_gen``) and every row runs Newton-Raphson on its generator's analysis, the line on top of it
-as in ``ac_contingency_screen`` (``csrc/gns_acg1.hip``).  Forward only.
+as in ``ac_contingency_screen`` (``csrc/gns_acg1.hip``).  ``ac_generator_contingency_screen_differentiable(...)`` is the same screen
+with a backward: one ``gns_acg1_adjoint`` call, per row one factorisation and one transposed solve at the forward's state on the
+row's own analysis, with the gradients of the dispatch, the set points and the pickup weights by generator row.
 """
 from __future__ import annotations
 
@@ -1319,7 +1321,7 @@ def dc_generator_contingency_screen_differentiable(buses, lines, generators, B=N
     the list may change its last bits.
 
     Out of scope: mixed topologies, limits on the pickup, a generator with two lines, second derivatives.  AC generator outages:
-    ``ac_generator_contingency_screen`` (forward only).
+    ``ac_generator_contingency_screen`` (with gradients: ``ac_generator_contingency_screen_differentiable``).
     Contract: ``include/gns_powerflow.h``, "Gradients of the DC generator screen"."""
     return _dc_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, flows, True)
 
@@ -1541,7 +1543,7 @@ def ac_n2_contingency_screen_differentiable(buses, lines, generators, B=None, L=
     change its last bits).
 
     Out of scope: batches that mix topologies, a generator with two lines, generator reactive limits and second derivatives (a
-    generator with one line: ``ac_generator_contingency_screen``, forward only).
+    generator with one line: ``ac_generator_contingency_screen_differentiable``).
     Contract: ``include/gns_powerflow.h``, "Gradients of the AC N-2 screen"."""
     return _ac_n2_screen(buses, lines, generators, B, L, G, slack_bus, pairs, rating, tol, max_iter, flows, states, True)
 
@@ -1606,16 +1608,54 @@ def ac_generator_contingency_screen(buses, lines, generators, B=None, L=None, G=
     With a 2-D single grid the batch dimension is dropped.
 
     The outputs are not differentiable: the call runs as under ``torch.no_grad()``, and ``requires_grad`` on an input is ignored
-    without an error.  The backward of this screen is not written yet.
+    without an error; the same call with a backward on the device is ``ac_generator_contingency_screen_differentiable``.
     Out of scope: reactive limits on the remaining units, Pmax / Pmin limits on the pickup, batches that mix topologies, a generator
     with two lines.  Contract: ``include/gns_powerflow.h``, "AC generator contingency screening"."""
+    return _ac_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, tol, max_iter, flows,
+                                states, False)
+
+
+class _ACG1Function(torch.autograd.Function):
+    """``ac_generator_contingency_screen_differentiable`` when an input requires grad: ``_ACN1Function`` with the pickup weights as
+    ``_DCN1Function`` takes them.  The forward is the screen's launch (the fifteen outputs in ``gns_acg1_screen``'s order, ``v`` and
+    ``theta`` always there), the backward one ``gns_acg1_adjoint`` call on the forward's set of analyses, lists and state.
+    ``weights`` (None, or the pickup weights ``[Gn]`` / ``[Bt,Gn]`` float64) is on the graph for its gradient alone, the adjoint's
+    fourth output: the kernels read the values the forward uploaded.  A ``[Gn]`` tensor gets the sum over the grids."""
+
+    @staticmethod
+    def forward(ctx, screen, adjoint, buses, lines, gens, weights):
+        out = screen(buses, lines, gens)
+        v, theta, _, _, _, _, _, worst_line, _, v_min_bus, _, v_max_bus, conv, iters, mis = out
+        ctx.mark_non_differentiable(worst_line, v_min_bus, v_max_bus, conv, iters, mis)
+        ctx.set_materialize_grads(False)
+        ctx.adjoint = adjoint
+        ctx.shared_weights = weights is not None and weights.dim() == 1
+        ctx.save_for_backward(buses, lines, gens, v, theta, conv, worst_line, v_min_bus, v_max_bus)
+        return tuple(out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gv, gth, gpf, gqf, gpt, gqt, gwl, _gwi, gvmin, _gi0, gvmax, _gi1, _gconv, _giters, _gmis):
+        buses, lines, gens, *state = ctx.saved_tensors
+        gb, gl, gg, gp = ctx.adjoint(buses, lines, gens, state, (gv, gth, gpf, gqf, gpt, gqt, gwl, gvmin, gvmax),
+                                     ctx.needs_input_grad[2:6])
+        if gp is not None and ctx.shared_weights:
+            gp = gp.sum(dim=0)
+        return (None, None, gb, gl, gg, gp)
+
+
+def _ac_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, tol, max_iter, flows, states,
+                         differentiable):
+    """``ac_generator_contingency_screen`` (``differentiable`` False) and ``ac_generator_contingency_screen_differentiable`` (True):
+    one set-up, one set of analyses, one launch."""
     s = _screen_setup('ac_generator_contingency_screen', _NR, buses, lines, generators, B, L, G, slack_bus, contingencies, rating,
-                      dict(flows=flows, states=states), False, tol, max_iter, pickup=pickup)
-    with torch.no_grad():
-        lib, cfg, Bt, dev = s.lib, s.cfg, s.Bt, s.dev
-        # the base case as newton_raphson solves it: its refusals come first, before any other analysis is made
-        base = _solve(lib, _NR, cfg, _one_topology(s.topo), *s.plain, None, None)
-        base_state = (base[0], base[1], base[2].to(torch.uint8))
+                      dict(flows=flows, states=states), differentiable, tol, max_iter, pickup=pickup)
+    with torch.set_grad_enabled(s.grad):
+        lib, cfg, Bt, dev, grad = s.lib, s.cfg, s.Bt, s.dev, s.grad
+        target = _one_topology(s.topo)
+        # the base case as newton_raphson solves it: its refusals come first, before any other analysis is made (a differentiated
+        # call solves it below, after the backward's own refusal)
+        base = None if grad else _solve(lib, _NR, cfg, target, *s.plain, None, None)
         # the distinct generators of the list, ascending, each with its analysis in the topology's set of them; a row as a
         # position into the generators and its line (-1: none)
         P = s.rows.shape[0]
@@ -1631,21 +1671,110 @@ def ac_generator_contingency_screen(buses, lines, generators, B=None, L=None, G=
         cols_host, cols_dev = _upload32(np.stack([gen_col.reshape(P), s.rows[:, 1]], axis=1), dev)
         set_host, set_blob = members.host, members.blob          # this call's: a later call may grow the set
         lds = lambda: _set_lds_bytes(set_host, off_host)                         # noqa: E731
-        ws_bytes = _size_query(lib.gns_acg1_workspace_bytes, 'gns_acg1_workspace_bytes',
-                               (ctypes.byref(cfg), set_host.ctypes.data, set_host.size, off_host.ctypes.data, off_host.size, Bt, P), lds,
-                               _ACG1.formula)
-        ws = _gns._workspace(ws_bytes, dev)
-        res = _ac_screen_outputs(s, P, states, flows)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_acg1_screen(ctypes.byref(cfg), set_host.ctypes.data, set_blob.data_ptr(), set_host.size, off_host.ctypes.data,
-                                       off_dev.data_ptr(), off_host.size, *(t.data_ptr() for t in s.plain), Bt, gen_host.ctypes.data,
-                                       gen_dev.data_ptr(), cols_host.ctypes.data, cols_dev.data_ptr(), P, s.isl_dev.data_ptr(),
-                                       _ptr(s.rating), int(s.rating is not None and s.rating.dim() == 2), _ptr(s.pickup),
-                                       int(s.pickup is not None and s.pickup.dim() == 2), *(t.data_ptr() for t in base_state),
-                                       *map(_ptr, res), ws.data_ptr(), ws.numel(), stream), 'gns_acg1_screen', lds, _ACG1.formula)
+
+        def workspace_bytes(query):
+            return _size_query(getattr(lib, query), query, (ctypes.byref(cfg), set_host.ctypes.data, set_host.size,
+                                                            off_host.ctypes.data, off_host.size, Bt, P), lds, _ACG1.formula)
+
+        def call(name, bu, li, ge, rest, ws):
+            """One C call of the screen: the set, the inputs, the lists, the rating and the pickup, then ``rest``."""
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(getattr(lib, name)(ctypes.byref(cfg), set_host.ctypes.data, set_blob.data_ptr(), set_host.size,
+                                          off_host.ctypes.data, off_dev.data_ptr(), off_host.size, bu.data_ptr(), li.data_ptr(),
+                                          ge.data_ptr(), Bt, gen_host.ctypes.data, gen_dev.data_ptr(), cols_host.ctypes.data,
+                                          cols_dev.data_ptr(), P, s.isl_dev.data_ptr(), _ptr(s.rating),
+                                          int(s.rating is not None and s.rating.dim() == 2), _ptr(s.pickup),
+                                          int(s.pickup is not None and s.pickup.dim() == 2), *rest, ws.data_ptr(), ws.numel(), stream),
+                       name, lds, _ACG1.formula)
+
+        if grad:
+            # the backward's own refusal (an oversize image, by name) comes before anything is launched
+            workspace_bytes('gns_acg1_adjoint_workspace_bytes')
+            base = list(_NRFunction.apply(lambda *a: _solve(lib, _NR, cfg, target, *a, None, None),
+                                          lambda *a: _adjoint(lib, cfg, target, *a), s.buses, s.lines, s.generators))
+        base_conv = base[2].to(torch.uint8)
+        base_state = (base[0].detach(), base[1].detach(), base_conv)      # the warm start is not differentiated
+
+        def screen(bu, li, ge):
+            ws = _gns._workspace(workspace_bytes('gns_acg1_workspace_bytes'), dev)
+            out = _ac_screen_outputs(s, P, states or grad, flows)
+            call('gns_acg1_screen', bu, li, ge, (*(t.data_ptr() for t in base_state), *map(_ptr, out)), ws)
+            return out
+
+        def adjoint(bu, li, ge, state, incoming, need):
+            """One adjoint call at the forward's ``state`` (v, theta, converged, worst_line, v_min_bus, v_max_bus)."""
+            gin = [torch.empty_like(t) if n else None for t, n in zip((bu, li, ge), need)]
+            gin.append(torch.empty(Bt, ge.shape[1], dtype=torch.float64, device=dev) if need[3] else None)
+            incoming = [None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming]
+            ws = _gns._workspace(workspace_bytes('gns_acg1_adjoint_workspace_bytes'), dev)
+            call('gns_acg1_adjoint', bu, li, ge, (*(t.data_ptr() for t in state), base_conv.data_ptr(), *map(_ptr, incoming),
+                                                  *map(_ptr, gin)), ws)
+            return gin
+
+        if grad:
+            # the weights as the graph sees them: column 1 of the canonical generators for 'pmax', the caller's tensor when it
+            # requires grad; anything else takes no gradient (grad_pickup is then NULL)
+            weights = None
+            if isinstance(pickup, str):
+                weights = s.generators[:, :, 1].to(torch.float64)
+            elif isinstance(pickup, torch.Tensor) and pickup.requires_grad:
+                weights = pickup.to(device=dev, dtype=torch.float64).reshape(s.pickup.shape)
+            res = list(_ACG1Function.apply(screen, adjoint, s.buses, s.lines, s.generators, weights))
+            if not states:
+                res[0] = res[1] = None
+        else:
+            res = screen(*s.plain)
         base, rows_t, res, islanding = _screen_results(s, base, res, 12)
         return AcGeneratorContingencyResult(PowerFlowResult(*base), rows_t, *res, islanding)
+
+
+def ac_generator_contingency_screen_differentiable(buses, lines, generators, B=None, L=None, G=None, *, slack_bus=None,
+                                                   contingencies=None, pickup=None, rating=None, tol=1e-8, max_iter=10, flows=False,
+                                                   states=False):
+    """``ac_generator_contingency_screen`` with gradients: the same arguments, the same ``AcGeneratorContingencyResult`` with every
+    forward output and ``base.*`` bit-identical to that call's, and a backward on the device, as
+    ``ac_n2_contingency_screen_differentiable`` and ``dc_generator_contingency_screen_differentiable`` have one.  It is the last step
+    of the planner's workflow for unit trips (``dc_generator_contingency_screen`` over the combined N-1 set, the worst rows checked
+    in AC here) for a security-constrained loss or a sensitivity study of the dispatch, the set points and the participation factors.
+
+    With grad mode on and ``requires_grad`` on an input (or on a tensor ``pickup``), ``v``, ``theta``, the four flows,
+    ``worst_loading``, ``v_min`` and ``v_max`` are differentiable through one ``gns_acg1_adjoint`` call on the forward's set of
+    analyses, lists and state (per row the implicit function theorem on the grid without the generator row and the line, on that
+    generator's own analysis: one factorisation of the row's Jacobian and one transposed solve; Newton is not run again), and
+    ``base.v`` / ``base.theta`` through ``newton_raphson``'s adjoint.  Otherwise it is the plain call and returns plain tensors.
+
+    The derivative is exact at the returned state with respect to ``newton_raphson``'s columns (``Pd, Qd, Gs, Bs``; the lines'
+    ``r, x, b, tau, shift``; ``Pg`` and ``vg``); every other column gets 0, and row ``(g,k)`` gives exactly 0 to line ``k``'s own
+    columns.  What the lost unit changes:
+      roles    the unknowns are the row's: a freed sole-unit bus is PQ, so its ``Qd`` and ``Bs`` take a gradient and no ``vg`` does;
+               its start value, the old set point, is not differentiated
+      vg       goes to the first remaining unit listed on a PV or slack bus (the next unit of a shared bus when the first is out);
+               the lost unit's ``vg`` gets exactly 0, and a slack with no unit left has the constant ``|V| = 1``
+      Pg       a remaining unit gets ``mu_h``, the multiplier of its bus's P equation (0 at the slack); the lost unit gets
+               ``sum_{h != g} mu_h w_h / W_g``, what its output does through the units that pick it up, and exactly 0 when the slack
+               picks up (``pickup=None``, or ``W_g`` exactly 0)
+      weights  ``dl/dw_h = Pg_g (mu_h - M) / W_g`` for ``h != g`` with ``M`` that weighted mean, 0 for ``h = g``.  With
+               ``pickup='pmax'`` it is added into the generators' column 1, which joins the contract for this pickup only; a tensor
+               ``pickup`` that requires grad receives it in its own dtype, a ``[Gn]`` tensor the sum over the grids; otherwise it is
+               not computed.  The ``W_g == 0`` branch is not differentiated: it gives the weights 0.
+    ``rating`` is a constant and the warm start is not differentiated.  ``worst_loading`` sends its gradient to ``worst_line``, at
+    the end that attains the maximum (the from end on equality), ``v_min`` / ``v_max`` to the buses reported; the index outputs,
+    ``converged``, ``iterations``, ``mismatch``, ``islanding`` and ``contingencies`` are not differentiable.
+
+    With ``states=False`` (the default) the summaries and the flows stay differentiable: ``v`` and ``theta`` are then kept for the
+    backward (``16 Bt P N`` bytes until it has run) and not returned.
+
+    A row whose incoming gradients are all exactly zero or absent is skipped, never multiplied by zero (a loss that indexes
+    ``converged`` rows); a non-zero gradient into a row that is not converged (an islanding row, a stopped iteration), a zero or
+    non-finite pivot or a non-finite lambda makes the grid's gradient rows NaN, the weights' row included; a grid without a base
+    solution gets NaN rows, zero rows when all its incoming gradients are zero.  Other grids are unaffected.  A grid's gradient is
+    bit-identical alone, in any batch and from run to run for the same list (another order of the list may change its last bits).
+
+    Out of scope: batches that mix topologies, reactive limits on the remaining units, Pmax / Pmin limits on the pickup, a generator
+    with two lines, second derivatives.  Contract: ``include/gns_powerflow.h``, "Gradients of the AC generator screen"."""
+    return _ac_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, tol, max_iter, flows,
+                                states, True)
 
 
 def _not_solved(Bt, N, dev):

@@ -1,0 +1,466 @@
+"""Gradients of the AC generator contingency screen on the MI355X (``powerflow.ac_generator_contingency_screen_differentiable``,
+include/gns_powerflow.h "Gradients of the AC generator screen"): against the float64 reference
+(``ac_generator_contingency_grad_reference``: the generator's row deleted, the pickup applied inside the torch graph, the line's row
+deleted, the reference's own Newton from the base, autograd's dense Jacobian and the implicit function theorem), against the
+product's other route (the sum over copies of ``newton_raphson(mixed_topologies=True)`` on the expanded, redispatched batch), where
+``vg``, ``Pg`` and the weights' gradients land, bitwise reproducibility, per-row and per-grid failure and the LDS refusal.
+
+The bar is the project's gradient bar per column per grid (test_ac_contingency_grad_gpu): the outputs are float32, so
+max|out - ref| <= 1e-5 max|ref| + 1e-7; every column outside the contract is exactly 0; ``grad_pickup`` is float64 and takes the
+same bar.  A loss reads only the rows where both the product converged and the reference converged with two iterations to spare, by
+indexing, so every other row's incoming gradient is exactly zero; each test asserts the share of rows it compares.  The counts
+stated with the tests were computed on the CPU from the reference alone: on case14 x 3 grids (the default list, 105 rows per grid)
+the reference qualifies 12 of the 15 generator-alone rows with ``pickup`` None and ``'pmax'``, 169 (None) and 173 (``'pmax'``) of
+the 285 non-islanding generator-plus-line rows, and 50 of the 54 generator-alone rows of case118; at least 60 % of the
+generator-alone rows and 50 % of the generator-plus-line rows must be in the loss, the caps the forward test uses."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+from opf_graph_neural_solver_amd import gns as gns_mod
+from opf_graph_neural_solver_amd import powerflow
+import ac_generator_contingency_grad_reference as ggref
+import ac_generator_contingency_reference as agref
+import pf_topologies as pt
+from test_ac_contingency_grad_gpu import CONTRACT, NAMES, OUT, SUMMARIES, _equal, _loss, _rating, _weights
+from test_ac_generator_contingency_gpu import MAX_IT, _case, _reference, _reference_rows, _two_on_a_bus
+from test_ac_generator_contingency_gpu import _weights as _pickup
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+E14, N14, G14 = 20, 14, 5
+DEFAULT14 = tuple((g, k) for g in range(G14) for k in range(-1, E14))
+# 15 rows of case14 the reference converges with two iterations to spare in all three grids, with pickup None and 'pmax' (counted
+# on the CPU from the reference alone): four generators alone, eleven with a line; the first twelve are the expanded route's list
+SUB14 = ((0, -1), (1, -1), (2, -1), (4, -1), (0, 3), (0, 14), (1, 2), (1, 9), (2, 4), (2, 8), (4, 2), (4, 5), (1, 19), (2, 14), (0, 7))
+
+
+def _spare(r):
+    return r is not None and bool(r.converged) and r.iterations <= MAX_IT - 2
+
+
+def _spare_mask(ref, batch, rows):
+    return torch.tensor([[_spare(ref[i, g, k]) for g, k in rows] for i in range(batch)], device=DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_rows(key, kind, rows):
+    """{(grid, generator, line): Row or None} of a cached case for a pickup kind (None, 'pmax', 'random') and a tuple of rows:
+    solved once, never changed."""
+    s = key[0](*key[1:])
+    return _reference_rows(s, _pickup(kind, s[0].shape[0], s[2].shape[1]), list(rows))
+
+
+def _diff(s, ins=None, **kw):
+    ins = s[:3] if ins is None else ins
+    return powerflow.ac_generator_contingency_screen_differentiable(*ins, slack_bus=s[3], **kw)
+
+
+def _grads(s, w, mask=None, req=(True, True, True), pickup=None, **kw):
+    """(result, the rows of the loss, gradients of the inputs that require grad, then of a tensor ``pickup`` that requires grad) of
+    the call with states and flows unless ``kw`` says otherwise.  ``mask``: None (the converged rows), a bool tensor that is and-ed
+    with them, or a callable of the result."""
+    ins = [t.detach().clone().requires_grad_(r) for t, r in zip(s[:3], req)]
+    res = _diff(s, ins, pickup=pickup, **{**dict(flows=True, states=True), **kw})
+    rows = mask(res) if callable(mask) else res.converged if mask is None else res.converged & mask
+    wrt = [t for t in ins if t.requires_grad] + ([pickup] if isinstance(pickup, torch.Tensor) and pickup.requires_grad else [])
+    return res, rows, torch.autograd.grad(_loss(res, w, rows), wrt)
+
+
+def _check(grads, s, res, w, rows, ref, pickup, rating, grids, name):
+    """Every contract column of every grid of ``grids`` to the bar; returns the worst error / bar.  ``grads``: the three inputs'
+    and, for a tensor ``pickup`` [Bt,Gn], its own; ``ref``: {(grid, generator, line): Row}.  With ``pickup='pmax'`` the weights'
+    gradient is part of the generators' column 1, which joins the contract."""
+    listed = res.contingencies.tolist()
+    worst = (0.0, None)
+    pmax = isinstance(pickup, str)
+    contract = dict(CONTRACT, generators=CONTRACT['generators'] + ([1] if pmax else []))
+    for i in grids:
+        r = None if rating is None else (rating if rating.dim() == 1 else rating[i]).cpu().numpy()
+        gen_i = s[2][i].cpu().double().numpy()
+        pw = agref.weights(pickup.detach().cpu().numpy() if isinstance(pickup, torch.Tensor) else pickup, gen_i, i)
+        want, cond = ggref.gradients(s[0][i].cpu(), s[1][i].cpu(), s[2][i].cpu(), s[3], listed, [ref[i, g, k] for g, k in listed],
+                                     rows[i].tolist(), {n: None if w[n] is None else w[n][i].cpu() for n in OUT}, pw, r)
+        if pmax:
+            want[2][:, 1] += want[3]
+        cols = [(what, grads[k][i].double().cpu().numpy(), want[k], contract[what]) for k, what in enumerate(NAMES)]
+        if len(grads) > 3:
+            assert grads[3].dtype == torch.float64 and grads[3].shape == (s[0].shape[0], s[2].shape[1])
+            cols.append(('pickup', grads[3][i].cpu().numpy()[:, None], want[3][:, None], [0]))
+        for k, what in enumerate(NAMES):
+            assert grads[k].dtype == torch.float32 and grads[k].shape == s[k].shape
+        for what, got, ref_g, cs in cols:
+            for c in range(got.shape[1]):
+                if c not in cs:
+                    assert np.all(got[:, c] == 0), (name, i, what, c)
+                    continue
+                err, scale = np.max(np.abs(got[:, c] - ref_g[:, c])), np.max(np.abs(ref_g[:, c]))
+                ratio = err / (1e-5 * scale + 1e-7)
+                worst = max(worst, (ratio, (i, what, c)))
+                print(f'{name}[{i}] d/d{what}[{c}]: err {err:.3e} scale {scale:.3e} ratio {ratio:.3f} (cond <= {cond:.1f})')
+        print(f'{name}[{i}]: {int(rows[i].sum())} rows in the loss')
+    print(f'{name}: worst error / bar {worst[0]:.3f} at {worst[1]}')
+    assert worst[0] <= 1.0, (name, worst)
+    return worst[0]
+
+
+@pytest.mark.parametrize('kind', ['pmax', None])
+def test_case14_every_row_against_the_reference(kind):
+    """315 rows: 15 generator-alone, 15 islanding, 285 others.  All nine outputs are weighted, the rating is per grid, gradients go
+    into all three inputs (with ``'pmax'`` column 1 of the generators included).  105 rows: C = 2, 53 chunks per grid, the last of a
+    single row, and chunk 10 (rows 20 and 21) crosses from generator 0 to generator 1.  Generator 0 sits on the slack: its ``Pg``
+    takes exactly 0 when the slack picks up, and the reference's value with ``'pmax'``."""
+    s = _case(14, 3)
+    ref = _reference(14, 3, kind, True)
+    spare = _spare_mask(ref, 3, DEFAULT14)
+    alone = torch.tensor([k < 0 for _, k in DEFAULT14], device=DEV)
+    assert int(spare[:, alone].sum()) == 12 and int(spare[:, ~alone].sum()) == (173 if kind else 169)
+    rating = _rating(E14, 61, 3)
+    w = _weights(3, len(DEFAULT14), N14, E14, 62)
+    res, rows, grads = _grads(s, w, spare, pickup=kind, rating=rating)
+    assert res.contingencies.tolist() == [list(r) for r in DEFAULT14] and int(res.islanding.sum()) == G14
+    n_alone, n_line = int(rows[:, alone].sum()), int(rows[:, ~alone].sum())
+    print(f'case14 pickup {kind}: {n_alone} of 15 generator-alone rows and {n_line} of 285 generator-plus-line rows in the loss')
+    assert n_alone >= 0.6 * 15 and n_line >= 0.5 * 285
+    assert res.v.requires_grad and res.q_to.requires_grad and res.worst_loading.requires_grad and res.v_min.requires_grad
+    assert not res.converged.requires_grad and not res.worst_line.requires_grad and not res.mismatch.requires_grad
+    _check(grads, s, res, w, rows, ref, kind, rating, range(3), f'case14 pickup {kind}')
+    assert int(s[2][0, 0, 0]) == s[3]                                              # generator 0 sits on the slack
+    if kind is None:
+        assert bool((grads[2][:, 0, 6] == 0).all()) and bool((grads[2][:, 1:, 6] != 0).all())
+    else:
+        assert bool((grads[2][:, 0, 6] != 0).all()) and bool((grads[2][:, :, 1] != 0).any())
+
+
+def test_weights_that_require_grad_take_their_gradient():
+    """Random [Bt,Gn] weights with one column exactly zero (the forward test's): ``pickup.grad`` against the reference, float64; a
+    [Gn] tensor gets the sum over the grids, a float32 tensor its own dtype."""
+    s = _case(14, 3)
+    pw = _pickup('random', 3, G14)
+    assert bool((pw[:, G14 // 2] == 0).all())
+    ref = _ref_rows((_case, 14, 3), 'random', SUB14)
+    spare = _spare_mask(ref, 3, SUB14)
+    w = _weights(3, len(SUB14), N14, E14, 63)
+    pick = pw.to(DEV).requires_grad_(True)
+    res, rows, grads = _grads(s, w, spare, pickup=pick, contingencies=list(SUB14))
+    print(f'case14 random weights: {int(rows.sum())} of {3 * len(SUB14)} rows in the loss')
+    assert int(rows.sum()) >= 0.6 * 3 * len(SUB14)
+    assert bool((grads[3] != 0).any()) and bool((grads[2][:, :, 1] == 0).all())
+    _check(grads, s, res, w, rows, ref, pick, None, range(3), 'case14 random weights')
+    # the inputs alone: the same bits, and no weights' gradient is computed
+    _, _, plain = _grads(s, w, spare, pickup=pw.to(DEV), contingencies=list(SUB14))
+    assert len(plain) == 3 and _equal(plain, grads[:3])
+    # a [Gn] tensor: the sum over the grids of the rows it would get per grid
+    one = pw[1].to(DEV).requires_grad_(True)
+    _, r1, g1 = _grads(s, w, lambda r: r.converged, pickup=one, contingencies=list(SUB14))
+    per = pw[1].expand(3, G14).contiguous().to(DEV).requires_grad_(True)
+    _, r3, g3 = _grads(s, w, lambda r: r.converged, pickup=per, contingencies=list(SUB14))
+    assert torch.equal(r1, r3) and g1[3].shape == (G14,) and torch.equal(g1[3], g3[3].sum(dim=0)) and _equal(g1[:3], g3[:3])
+    # float32 weights: their gradient in their own dtype
+    f32 = pw.float().to(DEV).requires_grad_(True)
+    _, _, g32 = _grads(s, w, lambda r: r.converged, pickup=f32, contingencies=list(SUB14))
+    assert g32[3].dtype == torch.float32 and g32[3].shape == (3, G14) and bool(torch.isfinite(g32[3]).all())
+
+
+def test_all_zero_weights_are_the_slack_picking_up():
+    """W_g exactly 0: the branch is not differentiated.  The weights get exactly 0, the lost unit's ``Pg`` gets exactly 0 (every
+    row of the list loses generator 2, so nothing else reaches its ``Pg``), and the inputs get the ``pickup=None`` gradients bit
+    for bit."""
+    s = _case(14, 3)
+    rows = [(2, -1), (2, 4), (2, 8), (2, 14)]
+    w = _weights(3, len(rows), N14, E14, 64)
+    zero = torch.zeros(3, G14, dtype=torch.float64, device=DEV, requires_grad=True)
+    res, used, grads = _grads(s, w, pickup=zero, contingencies=rows)
+    _, used0, none = _grads(s, w, contingencies=rows)
+    assert torch.equal(used, used0) and int(used.sum()) >= 9
+    assert bool((grads[3] == 0).all()) and bool((grads[2][:, 2, 6] == 0).all()) and bool((grads[2][:, 2, 4] == 0).all())
+    assert _equal(grads[:3], none) and bool((none[2][:, [1, 3, 4], 6] != 0).all())
+
+
+def test_two_units_on_one_bus_where_vg_lands():
+    """The forward test's grid: generator 0 is the slack's only unit, 1 and 2 share a bus (different set points), 4 is alone on its
+    bus.  The reference converges the four rows in 3, 3, 3 and 6 iterations: all four are compared.  Then row by row: with row 1
+    out the bus's ``vg`` gradient lands on row 2, with row 2 out on row 1; the freed bus of row 4 is PQ (its unit gets ``vg`` 0, its
+    ``Qd`` a gradient); the slack's lost unit gets 0 (|V| = 1 is a constant, and the slack picks up)."""
+    s = _two_on_a_bus()
+    rows = ((0, -1), (1, -1), (2, -1), (4, -1))
+    ref = _reference_rows(s, None, list(rows))
+    assert [ref[0, g, -1].iterations for g, _ in rows] == [3, 3, 3, 6] and all(_spare(ref[0, g, -1]) for g, _ in rows)
+    w = _weights(1, 4, N14, E14, 65)
+    res, used, grads = _grads(s, w, contingencies=list(rows))
+    assert bool(used.all())
+    _check(grads, s, res, w, used, ref, None, None, range(1), 'two on a bus')
+    gb = (s[2][0, :, 0].long() - 1).tolist()
+    one = lambda j: {n: x[:, [j]] for n, x in w.items()}                            # noqa: E731
+    _, _, g = _grads(s, one(1), contingencies=[rows[1]])
+    assert float(g[2][0, 1, 4]) == 0 and float(g[2][0, 2, 4]) != 0 and float(g[2][0, 1, 6]) == 0 and float(g[2][0, 2, 6]) != 0
+    _, _, g = _grads(s, one(2), contingencies=[rows[2]])
+    assert float(g[2][0, 2, 4]) == 0 and float(g[2][0, 1, 4]) != 0 and float(g[2][0, 2, 6]) == 0 and float(g[2][0, 1, 6]) != 0
+    _, _, g = _grads(s, one(3), contingencies=[rows[3]])
+    assert float(g[2][0, 4, 4]) == 0 and float(g[2][0, 4, 6]) == 0 and float(g[0][0, gb[4], 3]) != 0 and float(g[0][0, gb[4], 5]) != 0
+    _, _, g0 = _grads(s, one(1), contingencies=[rows[1]])
+    assert float(g0[0][0, gb[1], 3]) == 0                                          # a bus that stays PV: no Q equation, Qd gets 0
+    _, _, g = _grads(s, one(0), contingencies=[rows[0]])
+    assert bool((g[2][0, 0] == 0).all()) and float(g[2][0, 1, 4]) != 0
+
+
+def test_agrees_with_the_sum_over_copies_of_the_expanded_redispatched_route():
+    """The route the adjoint replaces: one grid per (grid, row) with the generator's row deleted, the others redispatched by
+    ``'pmax'`` inside the graph, the line's row deleted, ``newton_raphson(mixed_topologies=True)`` with requires_grad warm-started
+    from the base, autograd summing over the copies.  The loss reads v and theta (what that route returns) on the rows both routes
+    converged on, over the first twelve rows of ``SUB14``; both routes are compared to the bar.  (That route's inputs are float32, so
+    its redispatched ``Pg`` is rounded once more: 6e-8 relative, far inside the bar.)"""
+    s = _case(14, 3)
+    rows = SUB14[:12]
+    P = len(rows)
+    w = _weights(3, P, N14, E14, 66, only=('v', 'theta'))
+    res, used, grads = _grads(s, w, pickup='pmax', contingencies=list(rows), flows=False)
+    ins = [x.detach().clone().requires_grad_(True) for x in s[:3]]
+    wts = ins[2][:, :, 1].double()
+    mv, mth, mconv = [None] * P, [None] * P, [None] * P
+    for with_line in (False, True):
+        sel = [j for j, (_, k) in enumerate(rows) if (k >= 0) == with_line]
+        xg, xl = [], []
+        for j in sel:
+            g, k = rows[j]
+            others = [h for h in range(G14) if h != g]
+            share = ins[2][:, g, 6].double().unsqueeze(1) * (wts[:, others] / wts[:, others].sum(dim=1, keepdim=True))
+            rest = ins[2][:, others]
+            xg.append(torch.cat([rest[:, :, :6], (rest[:, :, 6].double() + share).float().unsqueeze(2)], dim=2))
+            xl.append(ins[1][:, [e for e in range(E14) if e != k]] if with_line else ins[1])
+        n = len(sel)
+        xg, xl = torch.stack(xg, dim=1).reshape(3 * n, G14 - 1, 7), torch.stack(xl, dim=1).reshape(3 * n, -1, 7)
+        xb = ins[0].repeat_interleave(n, dim=0)
+        v0, th0 = res.base.v.detach().repeat_interleave(n, dim=0), res.base.theta.detach().repeat_interleave(n, dim=0)
+        mixed = powerflow.newton_raphson(xb, xl, xg, slack_bus=s[3], mixed_topologies=True, v0=v0, theta0=th0)
+        for q, j in enumerate(sel):
+            mv[j], mth[j], mconv[j] = mixed.v.reshape(3, n, N14)[:, q], mixed.theta.reshape(3, n, N14)[:, q], mixed.converged.reshape(3, n)[:, q]
+    mv, mth, mconv = torch.stack(mv, dim=1), torch.stack(mth, dim=1), torch.stack(mconv, dim=1)
+    assert torch.equal(mconv, res.converged) and int(used.sum()) == 3 * P            # SUB14: rows every grid converges
+    want = torch.autograd.grad((w['v'][used] * mv[used]).sum() + (w['theta'][used] * mth[used]).sum(), ins)
+    worst = 0.0
+    for k, what in enumerate(NAMES):
+        for i in range(3):
+            for c in CONTRACT[what] + ([1] if what == 'generators' else []):
+                a, b = grads[k][i, :, c].double(), want[k][i, :, c].double()
+                err, scale = float((a - b).abs().max()), float(b.abs().max())
+                worst = max(worst, err / (1e-5 * scale + 1e-7))
+                print(f'expanded route [{i}] d/d{what}[{c}]: err {err:.3e} scale {scale:.3e}')
+                # both sides are float32 results of float64 arithmetic: each is within the bar of the exact value
+                assert err <= 1e-5 * scale + 1e-7, (what, i, c, err, scale)
+    print(f'expanded route: {int(used.sum())} rows, worst error / bar {worst:.3f}')
+    # ... and the screen's own route to the reference
+    ref = _ref_rows((_case, 14, 3), 'pmax', SUB14)
+    _check(grads, s, res, w, used, ref, 'pmax', None, range(3), 'expanded route list')
+
+
+def test_each_incoming_gradient_alone_and_the_slim_calls():
+    s = _case(14, 3)
+    P = len(SUB14)
+    ref = _ref_rows((_case, 14, 3), 'pmax', SUB14)
+    mask = _spare_mask(ref, 3, SUB14)
+    rating = _rating(E14, 67)
+    kw = dict(pickup='pmax', contingencies=list(SUB14), rating=rating)
+    for name in OUT:
+        w = _weights(3, P, N14, E14, 68, only=(name,))
+        res, rows, grads = _grads(s, w, mask, **kw)
+        _check(grads, s, res, w, rows, ref, 'pmax', rating, [1], f'case14 {name} alone')
+    # flows=False, states=False (the defaults): the summaries' gradients with the same bits, the tensors not returned
+    w = _weights(3, P, N14, E14, 69, only=SUMMARIES)
+    _, _, full = _grads(s, w, mask, **kw)
+    for slim_kw in (dict(flows=False), dict(states=False), dict(flows=False, states=False)):
+        res, _, slim = _grads(s, w, mask, **kw, **slim_kw)
+        assert _equal(slim, full), slim_kw
+        assert (res.v is None) == ('states' in slim_kw) and (res.p_from is None) == ('flows' in slim_kw)
+    ins = [t.detach().clone().requires_grad_(True) for t in s[:3]]
+    res = _diff(s, ins, **kw)                                                       # the call's own defaults
+    assert res.v is None and res.theta is None and res.p_from is None and res.q_to is None and res.worst_loading.requires_grad
+    assert _equal(torch.autograd.grad(_loss(res, w, res.converged & mask), ins), full)
+    # a subset of the inputs requires grad: the bits of all three
+    w = _weights(3, P, N14, E14, 70)
+    _, _, full = _grads(s, w, mask, **kw)
+    for req in ((True, False, False), (False, True, False), (False, False, True), (True, False, True)):
+        _, _, part = _grads(s, w, mask, req=req, **kw)
+        assert _equal(part, [g for g, r in zip(full, req) if r]), req
+
+
+def _bits(a):
+    return a.view(torch.uint8) if a.dtype == torch.bool else a.view(torch.int64 if a.element_size() == 8 else torch.int32)
+
+
+def test_base_gradients_are_newton_raphsons_and_the_forward_is_unchanged():
+    s = _case(14, 3)
+    g = torch.Generator().manual_seed(71)
+    wv, wt = (torch.randn(3, N14, generator=g, dtype=torch.float64).to(DEV) for _ in range(2))
+    ins = [t.detach().clone().requires_grad_(True) for t in s[:3]]
+    res = _diff(s, ins, contingencies=[(0, 4), (3, -1)], pickup='pmax')
+    got = torch.autograd.grad((wv * res.base.v).sum() + (wt * res.base.theta).sum(), ins)
+    ins2 = [t.detach().clone().requires_grad_(True) for t in s[:3]]
+    nr = powerflow.newton_raphson(*ins2, slack_bus=s[3])
+    want = torch.autograd.grad((wv * nr.v).sum() + (wt * nr.theta).sum(), ins2)
+    assert _equal(got, want)
+    # the forward: the bits of the plain call in every field, with every choice of flows, states and pickup
+    fields = powerflow.AcGeneratorContingencyResult._fields
+    for kw in (dict(flows=True, states=True, pickup='pmax'), dict(), dict(flows=True), dict(states=True, pickup=_pickup('random', 3, G14).to(DEV))):
+        plain = powerflow.ac_generator_contingency_screen(*s[:3], slack_bus=s[3], **kw)
+        ins = [t.detach().clone().requires_grad_(True) for t in s[:3]]
+        diff = _diff(s, ins, **kw)
+        assert type(diff) is powerflow.AcGeneratorContingencyResult
+        for k in fields[1:]:
+            a, b = getattr(plain, k), getattr(diff, k)
+            assert (a is None) == (b is None), (kw, k)
+            if a is not None:
+                assert a.dtype == b.dtype and torch.equal(_bits(a), _bits(b.detach())), (kw, k)
+        for a, b in zip(plain.base, diff.base):
+            assert torch.equal(a, b.detach())
+    # no grad asked for, or grad mode off: plain tensors
+    with torch.no_grad():
+        off = _diff(s, ins, contingencies=[(0, 1)], states=True)
+    assert not off.worst_loading.requires_grad and not off.v.requires_grad and not off.base.v.requires_grad
+    off = _diff(s, contingencies=[(0, 1)], states=True)
+    assert not off.worst_loading.requires_grad and not off.v.requires_grad and not off.base.v.requires_grad
+    # the plain call keeps ignoring requires_grad
+    plain = powerflow.ac_generator_contingency_screen(*ins, slack_bus=s[3], contingencies=[(0, 1)])
+    assert not plain.worst_loading.requires_grad and not plain.base.v.requires_grad
+
+
+def test_reproducible_bit_for_bit_and_other_input_forms(monkeypatch):
+    s = _case(14, 3)
+    buses, lines, gens, slack = s
+    rows = list(DEFAULT14) + [(3, 7), (3, 7), (1, -1)] + list(DEFAULT14[2:21])        # 127 rows: C = 2, 64 chunks, the last of one row
+    assert len(rows) == 127 and rows[20][0] != rows[21][0]                            # chunk 10 crosses from generator 0 to generator 1
+    w, rating = _weights(3, len(rows), N14, E14, 72), _rating(E14, 73)
+    kw = dict(pickup='pmax', contingencies=rows, rating=rating)
+    res, used, a = _grads(s, w, **kw)
+    _, _, b = _grads(s, w, **kw)                                                      # from run to run
+    assert _equal(a, b) and all(bool(torch.isfinite(x).all()) for x in a) and int(used.sum()) > 100
+    for sel in ([1], [2, 0]):                                                         # alone and in another batch
+        sub = tuple(x[sel] for x in s[:3]) + (slack,)
+        _, _, p = _grads(sub, {n: x[sel] for n, x in w.items()}, **kw)
+        assert _equal(p, [x[sel] for x in a]), sel
+    # per-grid weights that require grad: alone and in a batch, the weights' gradient too
+    pw = _pickup('random', 3, G14).to(DEV)
+    _, _, c = _grads(s, w, pickup=pw.clone().requires_grad_(True), contingencies=rows, rating=rating)
+    _, _, c1 = _grads(tuple(x[[1]] for x in s[:3]) + (slack,), {n: x[[1]] for n, x in w.items()}, pickup=pw[[1]].clone().requires_grad_(True),
+                      contingencies=rows, rating=rating)
+    assert _equal(c1[:3], [x[[1]] for x in c[:3]]) and torch.equal(c1[3], c[3][[1]]) and bool(torch.isfinite(c[3]).all())
+    # a 2-D single grid
+    ins = [x[1].detach().clone().requires_grad_(True) for x in s[:3]]
+    one = _diff(s, ins, flows=True, states=True, **kw)
+    assert one.v.shape == (len(rows), N14) and one.worst_loading.shape == (len(rows),)
+    g = torch.autograd.grad(_loss(one, {n: x[1] for n, x in w.items()}, one.converged), ins)
+    assert all(x.shape == y.shape for x, y in zip(g, ins)) and _equal(g, [x[1] for x in a])
+    # CPU tensors in: CPU outputs, CPU gradients, the same bits
+    ins = [x.cpu().clone().requires_grad_(True) for x in s[:3]]
+    cpu = _diff(s, ins, flows=True, states=True, pickup='pmax', contingencies=rows, rating=rating.cpu())
+    assert cpu.v.device.type == 'cpu' and cpu.worst_loading.requires_grad
+    g = torch.autograd.grad(_loss(cpu, w, cpu.converged), ins)
+    assert all(x.device.type == 'cpu' for x in g) and _equal(g, [x.cpu() for x in a])
+    # nothing is read that nothing wrote: the same bits from poisoned workspaces
+    monkeypatch.setattr(gns_mod, 'POISON_WORKSPACES', True)
+    _, _, d = _grads(s, w, **kw)
+    assert _equal(d, a)
+
+
+def test_failure_per_row_and_per_grid_and_a_rows_own_line():
+    s = _case(14, 3)
+    rows = list(DEFAULT14)
+    P = len(rows)
+    w = _weights(3, P, N14, E14, 74)
+    pw = _pickup('random', 3, G14).to(DEV)
+    grads = lambda sx, mask=None: _grads(sx, w, mask, pickup=pw.clone().requires_grad_(True), contingencies=rows)   # noqa: E731
+    res, used, good = grads(s)
+    assert all(bool(torch.isfinite(x).all()) for x in good) and len(good) == 4
+    conv, isl = res.converged, res.islanding
+    # a row (g, k) alone: exactly 0 in line k's own columns
+    for j in [j for j in torch.nonzero(conv.all(dim=0)).flatten().tolist() if rows[j][1] >= 0][:3]:
+        _, _, g1 = _grads(s, {n: x[:, [j]] for n, x in w.items()}, pickup='pmax', contingencies=[rows[j]])
+        assert bool((g1[1][:, rows[j][1], :] == 0).all()) and bool((g1[1] != 0).any()) and bool(torch.isfinite(g1[1]).all())
+    # a non-zero cotangent into a non-converged row: NaN rows for that grid, the weights' included, the others bit for bit
+    stopped = ~conv & ~isl.unsqueeze(0)
+    assert int(isl.sum()) == G14 and bool(stopped.any())
+    gi, ji = (int(x) for x in torch.nonzero(stopped)[0])
+    also = lambda g, p: (torch.arange(3, device=DEV).unsqueeze(1) == g) & (torch.arange(P, device=DEV) == p)   # noqa: E731
+    _, _, bad = grads(s, lambda r: r.converged | also(gi, ji))
+    others = [i for i in range(3) if i != gi]
+    for x, y in zip(bad, good):
+        assert bool(x[gi].isnan().all()) and torch.equal(x[others], y[others])
+    # ... and into an islanding row (NaN outputs)
+    jb = int(torch.nonzero(isl)[0])
+    _, _, bad = grads(s, lambda r: r.converged | also(2, jb))
+    for x, y in zip(bad, good):
+        assert bool(x[2].isnan().all()) and torch.equal(x[[0, 1]], y[[0, 1]])
+    # a grid without a base solution: NaN rows with a non-zero incoming gradient, zero rows without; the others bit for bit
+    buses = s[0].clone()
+    buses[1, :, 2:4] *= 40.0                                                         # loads no network of this size can serve
+    sb = (buses, s[1], s[2], s[3])
+    res_b, _, g = grads(sb, lambda r: torch.ones_like(r.converged))
+    assert res_b.base.converged.tolist() == [True, False, True] and not bool(res_b.converged[1].any())
+    for x in g:
+        assert bool(x[1].isnan().all())
+    _, _, g0 = grads(sb)                                                             # the converged rows: none of grid 1
+    for x, y in zip(g0, good):
+        assert bool((x[1] == 0).all()) and torch.equal(x[[0, 2]], y[[0, 2]])
+
+
+def test_a_unit_without_output_that_is_second_on_its_bus_agrees_with_the_line_screen():
+    """``_two_on_a_bus(zero_pg=True)``: generator 2 injects nothing and is not the first listed on its bus, so rows (2, k) are the
+    AC N-1 screen's rows k on the same lines.  The two adjoints run on different analyses and lay their partials out differently;
+    their gradients agree to the bar (both are float32 results of float64 arithmetic)."""
+    s = _two_on_a_bus(zero_pg=True)
+    rows = [(2, k) for k in range(E14)]
+    w = _weights(1, E14, N14, E14, 75)
+    res, used, got = _grads(s, w, pickup='pmax', contingencies=rows)
+    ins = [t.detach().clone().requires_grad_(True) for t in s[:3]]
+    n1 = powerflow.ac_contingency_screen(*ins, slack_bus=s[3], differentiable=True)
+    assert torch.equal(n1.converged, res.converged) and int(used.sum()) >= 0.5 * E14
+    want = torch.autograd.grad(_loss(n1, w, n1.converged), ins)
+    worst = 0.0
+    for k, what in enumerate(NAMES):
+        for c in range(got[k].shape[2]):
+            a, b = got[k][0, :, c].double(), want[k][0, :, c].double()
+            if c not in CONTRACT[what]:
+                assert bool((a == 0).all()), (what, c)                                # Pg_2 = 0: nothing reaches the weights either
+                continue
+            if what == 'generators' and c == 6:
+                a, b = a[[0, 1, 3, 4]], b[[0, 1, 3, 4]]                               # the lost unit's own Pg: what the others pick up
+            err, scale = float((a - b).abs().max()), float(b.abs().max())
+            worst = max(worst, err / (1e-5 * scale + 1e-7))
+            assert err <= 1e-5 * scale + 1e-7, (what, c, err, scale)
+    print(f'second unit without output: {int(used.sum())} rows, worst error / bar {worst:.3f}')
+
+
+def test_case118_every_generator_alone_against_the_reference():
+    """The 54 generator-alone rows of one grid with ``'pmax'``: the reference qualifies 50 (counted on the CPU from the reference
+    alone), at least 60 % must be in the loss.  The slack's unit takes the reference's ``Pg`` gradient with ``'pmax'`` and exactly
+    0 when the slack picks up."""
+    s = _case(118, 1)
+    Gn, E, N = s[2].shape[1], s[1].shape[1], 118
+    assert Gn == 54
+    rows = tuple((g, -1) for g in range(Gn))
+    ref = _reference(118, 1, 'pmax', False)
+    spare = _spare_mask(ref, 1, rows)
+    assert int(spare.sum()) == 50
+    w = _weights(1, Gn, N, E, 76)
+    rating = _rating(E, 77)
+    res, used, grads = _grads(s, w, spare, pickup='pmax', contingencies=list(rows), rating=rating)
+    print(f'case118: {int(used.sum())} of 54 generator-alone rows in the loss')
+    assert int(used.sum()) >= 0.6 * 54
+    _check(grads, s, res, w, used, ref, 'pmax', rating, range(1), 'case118')
+    on_slack = torch.nonzero(s[2][0, :, 0].long() == s[3]).flatten().tolist()
+    assert len(on_slack) == 1 and bool((grads[2][0, on_slack, 6] != 0).all())
+    _, _, none = _grads(s, w, spare, contingencies=list(rows), rating=rating)
+    assert bool((none[2][0, on_slack, 6] == 0).all())
+
+
+def test_an_oversize_image_is_refused_by_name_before_any_launch(monkeypatch):
+    tp = pt.path(4096)
+    buses, lines, gens, _, _ = pt.grids(tp, 'reference', 1, 0, device=DEV)
+    launched = []
+    monkeypatch.setattr(powerflow, '_solve', lambda *a, **k: launched.append('solve'))
+    with pytest.raises(gns_mod.GNSError, match=pt.LDS_MESSAGE) as e:
+        powerflow.ac_generator_contingency_screen_differentiable(buses, lines.requires_grad_(True), gens, slack_bus=tp.slack,
+                                                                 contingencies=[(0, -1)])
+    assert 'gns_acg1_adjoint_workspace_bytes' in str(e.value) and 'nnz(L+U) + dim + 8 N' in str(e.value) and not launched

@@ -115,6 +115,12 @@ def wheel(n=71):
     return Topo(f'wheel{n}', n, *_ids(f, t, [2, n // 3, 2 * n // 3]), 2)
 
 
+def wheel_many_generators(n=71, gn=66):
+    """``wheel(n)`` with a generator on each of the rim buses 2..gn + 1 (66 units: more generator rows than a wave's 64 lanes, every
+    one the sole unit of its bus, the first on the slack).  Not in ``families()``."""
+    return wheel(n)._replace(name=f'wheel{n}_{gn}gens', g=np.arange(2, gn + 2, dtype=np.int64))
+
+
 def _info(tp, analyse=powerflow.analyse_topology):
     """The info dict of ``analyse`` (``powerflow.analyse_topology`` or ``powerflow.analyse_fd_topology``) on tp."""
     return analyse(tp.n, tp.f, tp.t, tp.g, tp.slack).info

@@ -12,7 +12,9 @@ indexing, so every other row's incoming gradient is exactly zero; each test asse
 stated with the tests were computed on the CPU from the reference alone: on case14 x 3 grids (the default list, 105 rows per grid)
 the reference qualifies 12 of the 15 generator-alone rows with ``pickup`` None and ``'pmax'``, 169 (None) and 173 (``'pmax'``) of
 the 285 non-islanding generator-plus-line rows, and 50 of the 54 generator-alone rows of case118; at least 60 % of the
-generator-alone rows and 50 % of the generator-plus-line rows must be in the loss, the caps the forward test uses."""
+generator-alone rows and 50 % of the generator-plus-line rows must be in the loss, the caps the forward test uses.  The generated
+grids at the end (``GENERATED``: 66 and 70 generator rows, more than a wave's lanes, and four units on one bus) state their counts
+with the tests and ask for at least half of the non-islanding rows."""
 import functools
 
 import numpy as np
@@ -23,6 +25,7 @@ from opf_graph_neural_solver_amd import gns as gns_mod
 from opf_graph_neural_solver_amd import powerflow
 import ac_generator_contingency_grad_reference as ggref
 import ac_generator_contingency_reference as agref
+from ac_generator_rows import topology
 import pf_topologies as pt
 from test_ac_contingency_grad_gpu import CONTRACT, NAMES, OUT, SUMMARIES, _equal, _loss, _rating, _weights
 from test_ac_generator_contingency_gpu import MAX_IT, _case, _reference, _reference_rows, _two_on_a_bus
@@ -453,6 +456,115 @@ def test_case118_every_generator_alone_against_the_reference():
     assert len(on_slack) == 1 and bool((grads[2][0, on_slack, 6] != 0).all())
     _, _, none = _grads(s, w, spare, contingencies=list(rows), rating=rating)
     assert bool((none[2][0, on_slack, 6] == 0).all())
+
+
+# ---- generated grids at the shapes the adjoint's generator loops are written for: (seed of pt.grids, rows of the reference that
+# qualify with 'pmax' and with the random weights), counted on the CPU from the reference alone, of two grids
+GENERATED = {'wheel71_66gens': (0, {'pmax': 152, 'random': 152}), 'hub150_70lines_70gens': (11, {'pmax': 75, 'random': 74}),
+             'random24_stacked_gens': (1, {'pmax': 46, 'random': 45})}
+
+
+def acg1_chunk(n_row):
+    """C of ``gns_acg1_adjoint``: max(1, ceil(n_row / 64))."""
+    return max(1, -(-n_row // 64))
+
+
+def grad_rows(name):
+    """The rows of a generated family's gradient test.
+    wheel71_66gens (Gn 66, E 140): every unit alone, then twelve with a line (64, E - 1 and g % E), units 63, 64 and 65 among them:
+    78 rows, so C = 2 and every chunk of the first 33 crosses from one member to the next, one of them from the slack's unit (the
+    base dimension) to a freed bus.  hub150_70lines_70gens (Gn 70, every line a bridge): the 70 units alone, C = 2.
+    random24_stacked_gens (four units on bus 4, two on the slack): every unit alone and with lines 0 and E - 1, 24 rows, C = 1."""
+    tp = topology(name)
+    E, Gn = tp.f.size, tp.g.size
+    rows = [(g, -1) for g in range(Gn)]
+    if name == 'wheel71_66gens':
+        rows += [(g, 64) for g in (0, 63, 64, 65)] + [(g, E - 1) for g in (0, 63, 64, 65)] + [(g, g % E) for g in (1, 33, 62, 65)]
+    elif name == 'random24_stacked_gens':
+        rows += [(g, k) for g in range(Gn) for k in (0, E - 1)]
+    return tuple(rows)
+
+
+@functools.lru_cache(maxsize=None)
+def _generated(name):
+    """(buses, lines, gens, slack) of ``pt.grids(tp, 'reference', 2, seed)`` on the device: made once, never changed."""
+    tp = topology(name)
+    buses, lines, gens, _, _ = pt.grids(tp, 'reference', 2, GENERATED[name][0], device=DEV)
+    return buses, lines, gens, tp.slack
+
+
+def _generated_case(name, kind, seed):
+    """The gradients of a generated family against the reference: all nine outputs weighted, a rating per grid, gradients into the
+    buses, the lines, the generators and, for the random weights, the weights' own tensor; the rows the reference converges with two
+    iterations to spare in the loss, at least half of the non-islanding rows.  Returns what ``_grads`` returns and the case."""
+    s = _generated(name)
+    tp = topology(name)
+    N, E, Gn = tp.n, tp.f.size, tp.g.size
+    rows = grad_rows(name)
+    pick = kind if kind == 'pmax' else _pickup('random', 2, Gn).to(DEV).requires_grad_(True)
+    ref = _ref_rows((_generated, name), kind, rows)
+    spare = _spare_mask(ref, 2, rows)
+    bridges = powerflow._bridges(N, tp.f - 1, tp.t - 1)
+    n_solvable = 2 * sum(1 for _, k in rows if k < 0 or not bridges[k])
+    assert int(spare.sum()) == GENERATED[name][1][kind], (name, kind, int(spare.sum()))
+    rating = _rating(E, seed, 2)
+    w = _weights(2, len(rows), N, E, seed + 1)
+    res, used, grads = _grads(s, w, spare, pickup=pick, contingencies=list(rows), rating=rating)
+    print(f'{name} pickup {kind}: {int(used.sum())} of {n_solvable} non-islanding rows in the loss, the reference qualifies '
+          f'{int(spare.sum())}')
+    assert int(used.sum()) >= 0.5 * n_solvable
+    assert len(grads) == (3 if kind == 'pmax' else 4)
+    ratio = _check(grads, s, res, w, used, ref, pick, rating, range(2), f'{name} pickup {kind}')
+    return s, res, used, grads, ratio
+
+
+@pytest.mark.parametrize('kind', ['pmax', 'random'])
+def test_sixty_six_units_two_trips_of_the_generator_loops(kind):
+    """Gn 66: ``Acg1Gen::lost`` strides its store loop a second time for units 64 and 65, the partial's generator part is indexed
+    past a wave's lanes, and the reduce kernel writes ``vg``, ``Pg`` and the weights of rows 64 and 65.  78 rows: C = 2, 39 chunks,
+    the chunks of the generator-alone rows cross from one member to the next.  Every unit but the slack's is the sole unit of its
+    bus.  On the CPU, from the reference alone, 152 ('pmax') and 152 (random weights) of the 156 rows qualify."""
+    s, res, used, grads, _ = _generated_case('wheel71_66gens', kind, 81)
+    assert acg1_chunk(len(grad_rows('wheel71_66gens'))) == 2
+    assert bool(used[:, [63, 64, 65]].any(dim=0).all())                             # the rows of the units past the wave are in the loss
+    assert bool((grads[2][:, 64:, 6] != 0).all())                                   # ... and their Pg takes what the others pick up
+    if kind == 'random':
+        assert bool((grads[3][:, 64:] != 0).all()) and grads[3].shape == (2, 66)
+
+
+@pytest.mark.parametrize('kind', ['pmax', 'random'])
+def test_seventy_units_alone_on_a_hub_of_bridges(kind):
+    """Gn 70, N 150, 70 lines at one bus, every line a bridge: the 70 generator-alone rows, C = 2.  Seed 11 of ``pt.grids``: the
+    reference solves both base cases within 10 iterations.  On the CPU, from the reference alone, 75 ('pmax') and 74 (random
+    weights) of the 140 rows qualify."""
+    s, res, used, grads, _ = _generated_case('hub150_70lines_70gens', kind, 83)
+    assert acg1_chunk(len(grad_rows('hub150_70lines_70gens'))) == 2 and not bool(res.islanding.any())
+    assert bool((grads[2][:, 64:, 6] != 0).all())
+
+
+@pytest.mark.parametrize('kind', ['pmax', 'random'])
+def test_four_units_on_a_bus_and_two_on_the_slack_where_vg_lands(kind):
+    """``random24_stacked_gens``: rows 0, 3, 5 and 7 share bus 4, rows 1 and 4 the slack, rows 2 and 6 are sole units (their members
+    have one unknown more: a list of members of two dimensions).  Every unit alone and with lines 0 and E - 1; on the CPU, from the
+    reference alone, 46 ('pmax') and 45 (random weights) of the 48 rows qualify.  Then one lost unit at a time: the first REMAINING
+    unit of bus 4 and of the slack takes a non-zero ``dl/dvg``, every other unit of the two buses exactly 0."""
+    s, res, used, grads, _ = _generated_case('random24_stacked_gens', kind, 85)
+    tp = topology('random24_stacked_gens')
+    N, E = tp.n, tp.f.size
+    shared = {4: [0, 3, 5, 7], tp.slack: [1, 4]}
+    assert all(np.flatnonzero(tp.g == bus).tolist() == units for bus, units in shared.items()) and tp.slack == 1
+    w = _weights(2, 1, N, E, 87)
+    pick = kind if kind == 'pmax' else _pickup('random', 2, tp.g.size).to(DEV)
+    for g in shared[4] + shared[tp.slack]:
+        r, u, gr = _grads(s, w, pickup=pick, contingencies=[(g, -1)])
+        grid = int(torch.nonzero(u[:, 0])[0])                                       # a grid whose row converged
+        for units in shared.values():
+            first = next(h for h in units if h != g)
+            assert float(gr[2][grid, first, 4]) != 0, (g, first)
+            for h in units:
+                if h != first:
+                    assert float(gr[2][grid, h, 4]) == 0, (g, h)
+        assert bool((gr[2][grid, [2, 6], 4] != 0).all())                            # the sole units keep their buses PV
 
 
 def test_an_oversize_image_is_refused_by_name_before_any_launch(monkeypatch):

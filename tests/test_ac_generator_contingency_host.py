@@ -356,3 +356,48 @@ def test_the_blob_without_the_generator_serves_its_rows(name):
                     assert np.max(np.abs(vm - want.v)) <= 1e-9 and np.max(np.abs(va - want.theta)) <= 1e-9, (name, g, i, k)
     print(f'{name}: {n_cmp} of {n_rows} non-islanding rows compared')
     assert n_cmp >= 0.5 * n_rows, (name, n_cmp, n_rows)
+
+
+@pytest.mark.parametrize('regime', pt.REGIMES)
+@pytest.mark.parametrize('name', ['toy', 'random24_stacked_gens', 'random40_parallel_selfloop', 'ring63'])
+def test_zero_and_one_step_of_the_replay_on_every_listed_row(name, regime):
+    """The replay on the blob without generator g from a start with base_theta[slack] = 0.3, on EVERY non-islanding row of
+    ``ac_generator_rows.rows_list`` (no convergence needed), the pickup shared by random weights: after zero steps the state is the
+    reference start on the grid without the unit exactly and the mismatch is the reference's to ``_mismatch_and_bar``; one step
+    solves the reference Jacobian of the grid without the unit and the line to ``pt.STEP_TOL``, scipy's own step asserted first as
+    the guard.  Pins "the blob without the generator serves its rows" at 100 %: toy 32, random24_stacked_gens 444,
+    random40_parallel_selfloop 460 and ring63 390 rows of two grids."""
+    from ac_generator_rows import pickup_weights, row_reference, rows_islanding, rows_list, topology
+    from test_ac_contingency_host import one_step_ratios, shifted_base
+    from test_ac_contingency_rows_gpu import _mismatch_and_bar
+    from types import SimpleNamespace
+    tp = topology(name)
+    buses, lines, gens, v, theta = pt.grids(tp, regime, 2, seed=11)
+    b, l, ge = (x.double().numpy() for x in (buses, lines, gens))
+    base_v, base_theta = shifted_base(tp, v, theta)
+    s = SimpleNamespace(tp=tp, b=b, l=l, g=ge, base_v=base_v, base_theta=base_theta)
+    rows = rows_list(tp)
+    isl = rows_islanding(tp, rows)
+    pick = pickup_weights('random', 2, tp.g.size)
+    n_cmp, worst = 0, 0.0
+    for i in range(2):
+        assert base_theta[i, tp.slack - 1] == 0.3
+        for (g, k), island in zip(rows, isl):
+            if island:
+                continue
+            w = _without(tp, g).host
+            view, out = row_reference(s, i, g, k, pick[i])
+            rest, (vm0, va0) = view.g[i], view.starts[i]
+            z = emulate_row(w, b[i], l[i], rest, out, base_v[i], base_theta[i], tol=0.0, max_iter=0)
+            assert np.array_equal(z[0], vm0) and np.array_equal(z[1], va0) and z[3] == 0, (name, i, g, k)
+            want, bar = _mismatch_and_bar(b[i], l[i], rest, tp.slack, out, vm0, va0)
+            assert abs(z[4] - want) <= bar, (name, i, g, k, z[4], want, bar)
+            v1, th1, conv, it, _ = emulate_row(w, b[i], l[i], rest, out, base_v[i], base_theta[i], tol=0.0, max_iter=1)
+            assert it == 1 and not conv, (name, i, g, k)
+            r_scipy, r_replay = one_step_ratios(b[i], l[i], rest, tp.slack, out, vm0, va0, v1, th1)
+            assert r_scipy <= pt.STEP_TOL, (name, regime, i, g, k, r_scipy)
+            assert r_replay <= pt.STEP_TOL, (name, regime, i, g, k, r_replay)
+            worst = max(worst, r_replay)
+            n_cmp += 1
+    print(f'{name} ({regime}): {n_cmp} of {2 * int((~isl).sum())} non-islanding rows compared, worst one-step ratio {worst:.1e}')
+    assert n_cmp == 2 * int((~isl).sum()) > 0

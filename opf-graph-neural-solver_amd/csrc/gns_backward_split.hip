@@ -46,6 +46,30 @@ typedef int gns_i8v __attribute__((ext_vector_type(8)));   // one line record of
 #ifndef GNS_BWDS_FRESH_INPUTS
 #define GNS_BWDS_FRESH_INPUTS 1   // 0 (diagnostic): the nets of a bus share their broadcast input pairs (see gns_bwds_sweep_kernel)
 #endif
+// A sweep wave is one dependent chain and every row it loads used to be requested at the point of use, where the wave then waited a
+// full round trip with only its partner wave to cover it.  The switches below move requests (and one launch) off that chain; none
+// changes an operand, a summation order or a stored value.  0 = the earlier code, instruction for instruction, for A/B builds
+// (tools/build_variant.sh).  The two requests are compiled into the four instantiations they were measured in (BwdsMeasured).
+#ifndef GNS_BWDS_LINE_AHEAD
+#define GNS_BWDS_LINE_AHEAD 1     // BwdsPhi::bus requests the two rows of line p+1 (index clamped to the bus's last line) before it
+#endif                            // recomputes line p, and the sweep requests those of the bus's first line before the L net (8 VGPRs);
+                                  // 2 (diagnostic): in the L_m kernels only
+#ifndef GNS_BWDS_BUS_AHEAD
+#define GNS_BWDS_BUS_AHEAD 1      // the L_m kernels and the step-0 {theta, v} kernel request the next bus's top-of-bus rows (index clamped
+#endif                            // to the chunk's last bus) between the bus's L net and its line loop; the subset per instantiation: BwdsAhead
+#ifndef GNS_BWDS_AH_M
+#define GNS_BWDS_AH_M 5           // ... the subsets (bits: BwdsAhead) of the L_m kernel, of its step-0 instantiation and of the step-0
+#endif                            // {theta, v} kernel; diagnostic overrides
+#ifndef GNS_BWDS_AH_M0
+#define GNS_BWDS_AH_M0 5
+#endif
+#ifndef GNS_BWDS_AH_T0
+#define GNS_BWDS_AH_T0 4
+#endif
+#ifndef GNS_BWDS_LASTK_FOLD
+#define GNS_BWDS_LASTK_FOLD 0     // 1: modes 0 and 1, step K-1: the theta kernel zeroes the L_m / phi_m blocks of its slab (same workgroup ->
+#endif                            // same slab) and the L_m kernel, which has nothing else to do there, is not launched.  Measured: no
+                                  // gain that separates from the run-to-run spread ("Tried and rejected"): off
 #define GNS_BWDS_PHYS_THREADS (GNS_BWDS_PHYS_WAVES * 64)
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -465,6 +489,12 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
   }
 };
 
+// the two input rows of in-line p that the phi nets read: (r, x, b, tau) and (shift, ...)
+struct BwdsLineRows { f4 a, b; };
+__device__ __forceinline__ BwdsLineRows bwds_line_rows(const float* IN, long long row_ein, int p, int lane) {
+  return BwdsLineRows{*row_ptr(IN, row_ein + 3LL * p, lane), *row_ptr(IN, row_ein + 3LL * p + 1, lane)};
+}
+
 template <int D, int H, bool MULTI, int PF>
 struct BwdsPhi : BwdsShape<D, H, MULTI> {
   using B = BwdsShape<D, H, MULTI>;
@@ -491,10 +521,11 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
     TP1 = z4; TP2 = z4;
   }
 
-  // back through the hidden vectors of the lines p0..p1 ending at the bus: gS = the adjoint of their sum
-  template <bool STEP0, bool IG = false>
+  // back through the hidden vectors of the lines p0..p1 ending at the bus: gS = the adjoint of their sum.  first = the rows of line
+  // p0, requested by the caller before the L net (LA: GNS_BWDS_LINE_AHEAD; else unused)
+  template <bool STEP0, bool IG = false, bool LA = false>
   __device__ __forceinline__ void bus(const GnsBwdsArgs& A, float* rec, int lane, const f2 (&xs)[XL], const f2 (&gS)[H / 2],
-                                      f2 (&macc)[D / 2], int p0, int p1, long long row_ein) {
+                                      f2 (&macc)[D / 2], int p0, int p1, long long row_ein, const BwdsLineRows& first) {
     if (p0 >= p1) return;
     const float* IN = A.in;
     const f2 (&m)[D / 2] = reinterpret_cast<const f2 (&)[D / 2]>(xs[2]);
@@ -512,8 +543,18 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
     }
 #pragma unroll
     for (int j = 0; j < H / 2; ++j) G1[j] = f2{0.f, 0.f};
+    f4 ca, cb;                       // LA: the rows of the line about to be reversed
+    if constexpr (LA) { ca = first.a; cb = first.b; }
     for (int p = p0; p < p1; ++p) {
-      const f4 ea = *row_ptr(IN, row_ein + 3LL * p, lane), eb = *row_ptr(IN, row_ein + 3LL * p + 1, lane);
+      // LA: the next line's rows fly while this line is recomputed and reversed (the last line re-requests its own, cached rows:
+      // a branch around the dead request would split the loop)
+      f4 na, nb, ea, eb;
+      if constexpr (LA) {
+        na = *row_ptr(IN, row_ein + 3LL * min(p + 1, p1 - 1), lane); nb = *row_ptr(IN, row_ein + 3LL * min(p + 1, p1 - 1) + 1, lane);
+        ea = ca; eb = cb;
+      } else {
+        ea = *row_ptr(IN, row_ein + 3LL * p, lane); eb = *row_ptr(IN, row_ein + 3LL * p + 1, lane);
+      }
       const f2 xt[3] = {f2{ea.x, ea.y}, f2{ea.z, ea.w}, f2{eb.x, 0.f}};
       f2 a1[H / 2], a2[H / 2], g2[H / 2], g1[H / 2];
       f2 sl[2][H / 2];
@@ -554,6 +595,7 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
       static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putA<SW>(rec, lane, j, g2[j]); gws_putB<SW>(rec, lane, j, a1[j]); });
       gws_putB<SW>(rec, lane, H / 2, f2{1.f, 0.f});
       gws_w2r(); gws_pass<SW>(rec, lane, TP2); gws_r2w();
+      if constexpr (LA) { ca = na; cb = nb; }
     }
     // x = [m(dst) | ...] (main.py:155): d/dm += W1[:, :d]^T G1 and the latent columns of dW1 += G1 (x) m, once per bus
     if constexpr (STEP0) return;       // ... both zero at step 0: d/dm_0 is never read and m_0 = 0
@@ -605,6 +647,29 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
 // STEP0: the instantiation that reverses step 0 (its dead work compiled out); GROUPED: a grouped call (A.group_topo), instantiated apart
 // IG: input gradients (gns_backward_inputs): the phi nets add the adjoints of their line inputs to A.igrad, and step 0 stores the
 // adjoints of (v, theta, dp, dq)_0 in its X row for gns_bwds_igrad_unpack_kernel
+// The rows a sweep reads at the top of a bus: the adjoint row, the state row, the latent rows and (L_m) parts 0 and 2 of the latent
+// adjoint of step k+1.  GNS_BWDS_BUS_AHEAD: which of them an instantiation requests one bus ahead - bit 0 the two adjoint parts (the
+// L_m kernel's own extra, 2 * D / 4 rows), bit 1 the latent rows, bit 2 the adjoint and state rows.  Only kernels whose first net
+// runs on every bus have a place for the request: the L_m kernel (5: with the latent rows too it needs 256 VGPRs and scratch) and
+// the step-0 {theta, v} kernel (4: step 0 reads one bus's zero latent rows for every bus, nothing to request).  The main {theta, v}
+// kernel has no registers to spare.
+// BwdsMeasured: the instantiations both requests are compiled into - the four plain kernels of mode 1 at latent 20, hidden 10, the
+// shape they were timed at.  Every other instantiation (other dimensions, mode 0's {theta} and {v} kernels, bus-major, grouped,
+// input gradients) keeps the earlier code: the requests cost registers and spilled scalars there (some leave their occupancy class,
+// the bus-major and hidden-14 kernels spill vectors) and nothing has measured what they return.
+template <int D, int H, bool MULTI, int FAMS, bool GROUPED, bool IG>
+struct BwdsMeasured { static constexpr bool value = MULTI && D == 20 && H == 10 && (FAMS == 3 || FAMS == 4) && !GROUPED && !IG; };
+template <int D>
+struct BwdsTop { f4 a0, s0; f2 m[D / 2], q0[D / 2], q2[D / 2]; };
+template <int D, int H, bool MULTI, int FAMS, bool STEP0, bool GROUPED, bool IG>
+struct BwdsAhead {
+#if GNS_BWDS_BUS_AHEAD
+  static constexpr int value = !BwdsMeasured<D, H, MULTI, FAMS, GROUPED, IG>::value ? 0 : (FAMS == 4 ? (STEP0 ? GNS_BWDS_AH_M0 : GNS_BWDS_AH_M) : (STEP0 ? GNS_BWDS_AH_T0 : 0));
+#else
+  static constexpr int value = 0;
+#endif
+};
+
 template <int D, int H, bool MULTI, int FAMS, bool STEP0, bool GROUPED, bool IG>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWDS_WPE))) gns_bwds_sweep_kernel(GnsBwdsArgs A) {
   using C = GnsDims<D, H, MULTI>;
@@ -630,7 +695,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
   const long long g0 = gb * A.R, g1 = (g0 + A.R < A.G) ? g0 + A.R : A.G;
   float* slab = A.slab + (gb * A.C + c) * A.slab_floats;
   const bool lastk = k == K - 1;           // nothing reads m_K: L_m.{K-1} / phi_m.{K-1} get no gradient (reference: .grad is None)
-  if (HAS_M && lastk) {                    // ... but their blocks of the slab must read as zero
+  // GNS_BWDS_LASTK_FOLD: in modes 0 and 1 the theta kernel of the same (group block, chunk) - the same slab - writes those zeros,
+  // and gns_launch_bwds_sweep leaves the L_m kernel of step K-1 out (grouped and input-gradient calls launch it as before)
+  // line rows one line ahead: everywhere but in the instantiations that spill already (every added live row is scratch there): the
+  // bus-major kernels and the hidden-14 {theta, v} kernel
+  constexpr bool LA = BwdsMeasured<D, H, MULTI, FAMS, GROUPED, IG>::value && (GNS_BWDS_LINE_AHEAD == 1 || (GNS_BWDS_LINE_AHEAD == 2 && FAMS == 4));
+  constexpr bool ZERO_M = HAS_M || (GNS_BWDS_LASTK_FOLD && MULTI && HAS_T && !GROUPED && !IG);
+  if (ZERO_M && lastk) {                   // ... but their blocks of the slab must read as zero
     float* z0 = slab + A.g_off[C::NPHI + 2] + (long long)(K - 1) * A.g_sz[C::NPHI + 2];
     for (int i = lane; i < (int)A.g_sz[C::NPHI + 2]; i += 64) z0[i] = 0.f;
     if constexpr (MULTI) {
@@ -662,13 +733,29 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
     }
     const long long row_ein = g * R + 3LL * N;
     auto state_row = [&](int slot, int n) { return (((long long)slot * A.G + g) * N + n) * RB; };
+    // GNS_BWDS_BUS_AHEAD: the rows of bus nn that this instantiation requests one bus ahead (BwdsAhead).  Only the L_m kernel
+    // (modes 0 and 1, never at step K-1) requests adjoint parts, only kernels of steps > 0 latent rows.
+    constexpr int AH = BwdsAhead<D, H, MULTI, FAMS, STEP0, GROUPED, IG>::value;
+    auto request = [&](int nn, BwdsTop<D>& t) {
+      const long long arn = (g * N + nn) * RBA, mrn = arn + 4 + (long long)parn * 3 * MQ;
+      if constexpr (AH & 4) { t.a0 = *row_ptr(A.adj, arn, lane); t.s0 = *row_ptr(A.state, state_row(k, nn), lane); }
+      if constexpr (AH & 2) load_pairs<D>(A.state, state_row(k, nn) + 1, lane, t.m);
+      if constexpr (AH & 1) { load_pairs<D>(A.adj, mrn, lane, t.q0); load_pairs<D>(A.adj, mrn + (m2_live ? 2 : 0) * MQ, lane, t.q2); }
+    };
+    BwdsTop<D> nx;
+    if constexpr (AH != 0) { if (n0 < n1) request(n0, nx); }
     for (int n = n0; n < n1; ++n) {
       const long long ar = (g * N + n) * RBA, rr = state_row(k, n);
-      const f4 a0 = *row_ptr(A.adj, ar, lane);
-      const f4 s0 = *row_ptr(A.state, rr, lane);
+      const f4 a0 = [&]() { if constexpr (AH & 4) return nx.a0; else return *row_ptr(A.adj, ar, lane); }();
+      const f4 s0 = [&]() { if constexpr (AH & 4) return nx.s0; else return *row_ptr(A.state, rr, lane); }();
       f2 xs[XL];                                          // [v theta | dp dq | m | sum_e h_e | deg, 1]
       f2 (&m)[D / 2] = reinterpret_cast<f2 (&)[D / 2]>(xs[2]);
-      load_pairs<D>(A.state, (step0 ? state_row(0, n0) : rr) + 1, lane, m);   // m_0 = 0 for every bus: step 0 reads one (cached) bus's zero rows
+      if constexpr (AH & 2) {
+#pragma unroll
+        for (int i = 0; i < D / 2; ++i) m[i] = nx.m[i];
+      } else {
+        load_pairs<D>(A.state, (step0 ? state_row(0, n0) : rr) + 1, lane, m);   // m_0 = 0 for every bus: step 0 reads one (cached) bus's zero rows
+      }
       f2 macc[D / 2];                                     // d/dm: L_m's upstream (main.py:188) and / or this kernel's own terms
       if (HAS_M && !lastk) {
         // what the sweeps of step k+1 left, summed in the order of the old in-place accumulation (L_m, L_theta, L_v)
@@ -677,8 +764,13 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
           load_pairs<D>(A.adj, mr + 2 * MQ, lane, macc);
         } else {
           f2 p0v[D / 2];
-          load_pairs<D>(A.adj, mr, lane, p0v);
-          load_pairs<D>(A.adj, mr + (m2_live ? 2 : 0) * MQ, lane, macc);
+          if constexpr (AH & 1) {
+#pragma unroll
+            for (int i = 0; i < D / 2; ++i) { p0v[i] = nx.q0[i]; macc[i] = nx.q2[i]; }
+          } else {
+            load_pairs<D>(A.adj, mr, lane, p0v);
+            load_pairs<D>(A.adj, mr + (m2_live ? 2 : 0) * MQ, lane, macc);
+          }
           if (A.mode == 0) {
             f2 p1v[D / 2];
             load_pairs<D>(A.adj, mr + MQ, lane, p1v);
@@ -693,6 +785,9 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
 #pragma unroll
         for (int i = 0; i < D / 2; ++i) macc[i] = f2{0.f, 0.f};
       }
+      // between the bus's first L net and its line loop: the next bus's rows (the last bus of the chunk re-requests its own, cached
+      // rows - a branch around the dead request would split the round of loads)
+      auto ahead = [&]() { if constexpr (AH != 0) request(min(n + 1, n1 - 1), nx); };
       f4 xsum = f4{0.f, 0.f, 0.f, 0.f};                  // d/dv, d/dtheta, d/ddp of the L inputs of this kernel's families
       const int p0 = in_ptr[n], p1 = in_ptr[n + 1];
       xs[0] = f2{s0.x, s0.y}; xs[1] = f2{s0.z, s0.w};
@@ -707,20 +802,26 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
         pin_all(xs);
 #endif
       };
+      // LA: the rows of the bus's first in-line, requested in front of the L net whose phi net reads them (every family of a kernel
+      // asks again: the rows are cached, and eight registers held across another family's nets are not free).  A bus without
+      // in-lines still requests two rows per family that it never uses: the index is clamped to [0, E - 1], and on a grid without
+      // any line to the first row after the bus rows - inside the group's input rows either way.
+      BwdsLineRows lr;
+      auto first = [&]() { if constexpr (LA) lr = bwds_line_rows(A.in, row_ein, max(min(p0, E - 1), 0), lane); };
       if constexpr (MULTI) {
-        if constexpr (HAS_M) { if (!lastk) { fresh(); lm.template bus<false, STEP0, IG>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS); fresh(); pm.template bus<STEP0, IG>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); } }
-        if constexpr (HAS_T) { fresh(); lt.template bus<false, STEP0, IG>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS); fresh(); pt.template bus<STEP0, IG>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); }
+        if constexpr (HAS_M) { if (!lastk) { first(); fresh(); lm.template bus<false, STEP0, IG>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS); ahead(); fresh(); pm.template bus<STEP0, IG, LA>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); } }
+        if constexpr (HAS_T) { first(); fresh(); lt.template bus<false, STEP0, IG>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS); if constexpr (!HAS_M) ahead(); fresh(); pt.template bus<STEP0, IG, LA>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); }
         // v moves only on buses without a generator (main.py:184-186): on a generator bus the upstream of L_v is exactly zero, and with
         // it every adjoint and every weight-gradient term of L_v and of phi_v over the lines ending there - the bus is skipped (the
         // topology is the same for all 64 grids of the wave, so the branch is uniform).  46 % of case118's buses carry a generator.
-        if constexpr (HAS_V) { if (!is_gen[n]) { fresh(); lv.template bus<false, STEP0, IG>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS); fresh(); pv.template bus<STEP0, IG>(A, rec, lane, xs, gS, macc, p0, p1, row_ein); } }
+        if constexpr (HAS_V) { if (!is_gen[n]) { first(); fresh(); lv.template bus<false, STEP0, IG>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS); fresh(); pv.template bus<STEP0, IG, LA>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); } }
       } else {
 #pragma unroll
         for (int j = 0; j < H / 2; ++j) gS[j] = f2{0.f, 0.f};
         if (!lastk) { fresh(); lm.template bus<true, STEP0, IG>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS); }
-        fresh(); lt.template bus<true, STEP0, IG>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS);
+        first(); fresh(); lt.template bus<true, STEP0, IG>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS);
         if (!is_gen[n]) { fresh(); lv.template bus<true, STEP0, IG>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS); }     // (a generator bus: L_v's upstream is zero, see above)
-        fresh(); pm.template bus<STEP0, IG>(A, rec, lane, xs, gS, macc, p0, p1, row_ein);
+        fresh(); pm.template bus<STEP0, IG, LA>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr);
       }
       if constexpr (!step0) {
         *row_ptr(A.adj, ar + 1 + SLOT, lane) = xsum;
@@ -971,6 +1072,8 @@ int gns_launch_bwds_phys(const GnsBwdsArgs& A, size_t lds, hipStream_t st) {
 int gns_launch_bwds_sweep(int d, int h, int multi, const GnsBwdsArgs& A, hipStream_t st) {
   const long long GB = (A.G + A.R - 1) / A.R;
   const unsigned blocks = (unsigned)(GB * A.C);
+  // step K-1 of modes 0 and 1: the L_m kernel would only zero two blocks of its slab - the theta kernel does (ZERO_M in the kernel)
+  const bool fold_m = GNS_BWDS_LASTK_FOLD && A.k == A.K - 1 && !A.group_topo && !A.igrad;
 #define GNS_SWEEP1(DD, HH, MM, FAMS, GR, IG) do { if (A.k == 0) hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, true, GR, IG>), dim3(blocks), dim3(64), 0, st, A); \
                                                  else hipLaunchKernelGGL((gns_bwds_sweep_kernel<DD, HH, MM, FAMS, false, GR, IG>), dim3(blocks), dim3(64), 0, st, A); } while (0)
   // (input gradients are not offered on grouped calls: gns_api.hip never sets both)
@@ -981,8 +1084,8 @@ int gns_launch_bwds_sweep(int d, int h, int multi, const GnsBwdsArgs& A, hipStre
   if (d == DD && h == HH) {                                                                                                 \
     if (!multi) { if (A.mode != 2) return GNS_EINVAL; GNS_SWEEP(DD, HH, false, 7); }                                        \
     else if (A.mode == 2) GNS_SWEEP(DD, HH, true, 7);                                                                       \
-    else if (A.mode == 1) { GNS_SWEEP(DD, HH, true, 4); GNS_SWEEP(DD, HH, true, 3); }                                       \
-    else { GNS_SWEEP(DD, HH, true, 4); GNS_SWEEP(DD, HH, true, 1); GNS_SWEEP(DD, HH, true, 2); }                            \
+    else if (A.mode == 1) { if (!fold_m) GNS_SWEEP(DD, HH, true, 4); GNS_SWEEP(DD, HH, true, 3); }                          \
+    else { if (!fold_m) GNS_SWEEP(DD, HH, true, 4); GNS_SWEEP(DD, HH, true, 1); GNS_SWEEP(DD, HH, true, 2); }               \
     return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;                                                          \
   }
   GNS_FOR_EACH_DIMS(GNS_CASE)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds tools/var_<name>.so: the library with gns_backward.hip (or the file named by SRC=) compiled with extra -D flags,
 # for A/B timing on one box:  GNS_LIB=tools/var_<name>.so python tools/gpu_time.py 118 16384 4 1:0:2
-# usage: bash tools/build_variant.sh <name> [-DFLAG ...]      (the other objects must have been built by make)
+# usage: bash tools/build_variant.sh <name> [-DFLAG ...]      (every other object, the power-flow ones included, must have been built by make)
 set -e
 cd "$(dirname "$0")/../opf-graph-neural-solver_amd/csrc"
 SRC=${SRC:-gns_backward}
@@ -12,5 +12,7 @@ for o in gns_forward gns_backward gns_backward_split gns_gridwg gns_gridwg_bwd g
   if [ "$o" = "$SRC" ]; then OBJS="$OBJS /tmp/var_$name.o"; else OBJS="$OBJS $o.o"; fi
 done
 hipcc $F "$@" -Rpass-analysis=kernel-resource-usage -c $SRC.hip -o /tmp/var_$name.o 2> /tmp/var_$name.remarks || { cat /tmp/var_$name.remarks | grep -v remark | head -40; exit 1; }
-hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/var_$name.so $OBJS gns_topology.o
+# (the power-flow objects too: the python package resolves their entry points when it loads a library)
+PF="gns_powerflow.o gns_fdpf.o gns_dcpf.o gns_dcn1.o gns_dcn2.o gns_dcg1.o gns_acn1.o gns_acn2.o gns_acg1.o gns_pf_topology.o"
+hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/var_$name.so $OBJS gns_topology.o $PF
 grep -A12 "${KERNEL:-gns_backward_kernelILi20ELi10ELb1ELb1ELi2}" /tmp/var_$name.remarks | grep -E "VGPRs:|Spill|Scratch|LDS" | sed 's/ \[-Rpass.*//; s/.*remark: *//' | tr '\n' ';'; echo " <- $name"

@@ -1096,6 +1096,94 @@ int gns_acg1_adjoint(const gns_pf_config* cfg, const void* set_host, const void*
                      float* grad_buses, float* grad_lines, float* grad_generators, double* grad_pickup,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- The solved case -------------------------------------------------------------------------------------------------------------
+ * What PYPOWER's runpf returns next to the voltages (its pfsoln step), for every grid of a batch at a GIVEN state (v, theta): a
+ * solver's result, a warm start or a model's prediction.  Nothing is iterated or solved.  One Newton-Raphson blob per call
+ * (gns_pf_prepare_topology); buses, lines, generators and cfg (max_iter and tol are checked as gns_pf_solve checks them and not
+ * used) as in gns_pf_solve; v, theta [Bt,N] fp64 are used as given (theta is not shifted); rating NULL (1), [E]
+ * (rating_per_grid = 0) or [Bt,E] (1) fp64 as in gns_acn1_screen.
+ *
+ * Semantics.  V_i = v_i e^{j theta_i}; Y the makeYbus matrix gns_pf_solve builds (shunts included).
+ *   p_from, q_from, p_to, q_to [Bt,E]: gns_acn1_screen's branch flows on the line's own four stamps, S_f = V_f conj(Y_ff V_f +
+ *     Y_ft V_t), S_t = V_t conj(Y_tf V_f + Y_tt V_t), in its expression order; NaN at a line whose id columns are not buses of the
+ *     grid; a line from a bus to itself and parallel lines as there.
+ *   p_inj, q_inj [Bt,N]: Re and Im of V_i conj(sum_k Y_ik V_k), the row product and the power in gns_pf_solve's expression order.
+ *   mismatch [Bt]: gns_pf_solve's ||F||_inf at this state: the largest of |p_inj - Psp| at PV and PQ buses and |q_inj - Qsp| at PQ
+ *     buses (Psp = sum of the bus's Pg in listing order - Pd, Qsp = -Qd), NaN when a term is not finite.  At the v, theta that
+ *     gns_pf_solve returns it is that call's mismatch bit for bit.
+ *   gen_q [Bt,Gn]: a bus with n >= 1 listed units produces q_inj + Qd, each unit (q_inj + Qd) / n (pfsoln without limit ranges).
+ *   gen_p [Bt,Gn]: every unit's Pg (column 6) as given, but the first unit listed on the slack, which carries p_inj[slack] +
+ *     Pd[slack] - (the sum, in listing order, of Pg of the other units on the slack).
+ *   slack_p [Bt] = p_inj[slack] + Pd[slack] - (the sum, in listing order, of Pg on the slack): what the slack produces beyond its
+ *     listed dispatch (gns_dc_solve's slack_p), defined for a slack without a unit too.  Column 5 (qg) is not read, nor is vg.
+ *   worst_loading [Bt] = max_l max(|S_f|, |S_t|) / rating_l with worst_line [Bt]; v_min, v_max [Bt] with v_min_bus, v_max_bus:
+ *     gns_acn1_screen's definitions, total order and tie rules (a NaN wins at the lowest index that holds one, the lowest index
+ *     among equals).
+ *   Each of the [Bt,E], [Bt,N] and [Bt,Gn] outputs may be NULL: not written.  No atomics, every sum in a fixed order: a grid's
+ *   outputs are bit-identical alone, in any batch, with any optional output NULL and from run to run; a NaN in a grid's state makes
+ *   that grid's outputs NaN and leaves the others alone.
+ *
+ * Kernel (gns_pfs.hip): one wave per grid; the state and the injections in LDS, 40 N bytes per grid (below gns_pf_solve's image on
+ * every topology); the grid's Y-bus values go to the workspace, gns_pf_workspace_bytes' figure (gns_pfs_workspace_bytes).
+ *
+ * Errors, in order: GNS_EINVAL for a NULL cfg (or one gns_pf_solve refuses), blob, input, v, theta, [Bt] output or workspace, for
+ * rating_per_grid outside {0, 1}, for Bt <= 0 or above 2^31 - 1, for a blob that is not a Newton-Raphson blob or whose N, E, Gn are
+ * not cfg's; then GNS_ESIZE for a short workspace; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Every
+ * refusal comes before any launch; nothing is allocated and the host is not synchronised.
+ * Not here: batches that mix topologies, reactive limits, second derivatives. */
+int gns_pfs_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
+int gns_pfs_evaluate(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                     const float* buses, const float* lines, const float* generators, int64_t Bt,
+                     const double* v, const double* theta, const double* rating, int32_t rating_per_grid,
+                     double* p_from, double* q_from, double* p_to, double* q_to, double* p_inj, double* q_inj,
+                     double* gen_p, double* gen_q, double* mismatch, double* slack_p,
+                     double* worst_loading, int32_t* worst_line, double* v_min, int32_t* v_min_bus, double* v_max, int32_t* v_max_bus,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Gradients of the solved case ------------------------------------------------------------------------------------------------
+ * gns_pfs_adjoint: the gradients of a loss l of gns_pfs_evaluate's differentiable outputs (the four flows, p_inj, q_inj, gen_p,
+ * gen_q, slack_p, worst_loading, v_min, v_max) with respect to the state and the inputs, at the state the forward was given.  The
+ * incoming gradients grad_<output> have the outputs' shapes, fp64; each may be NULL (zero).  worst_line, v_min_bus, v_max_bus are
+ * the forward's.  mismatch and the indices are not differentiable, rating is a constant.
+ * Outputs, each may be NULL (with all five NULL nothing is launched), every element written: grad_v, grad_theta [Bt,N] fp64 at
+ * every bus, the slack included; grad_buses [Bt,N,6], grad_lines [Bt,E,7], grad_generators [Bt,Gn,7] fp32.
+ *
+ * Method: no linear solve.  The bus cotangent Lambda_i = grad_p_inj_i + j grad_q_inj_i, whose real part at the slack also takes
+ * grad_slack_p + grad_gen_p[first slack unit] and whose imaginary part at a bus with n_i >= 1 units also takes (sum_u grad_gen_q_u)
+ * / n_i, joins the flows' cotangents at the line ends: W_f,l = grad_p_from_l + j grad_q_from_l + Lambda_{f_l}, W_t,l likewise
+ * (S_i is the sum of the flows that leave bus i plus |V_i|^2 conj(Gs_i + j Bs_i)).  grad_worst_loading adds (p + jq) / |S| /
+ * rating_w to the end of worst_line that attains the maximum, as gns_acn1_adjoint does (the from end on equality, nothing at
+ * |S| = 0).
+ *   grad_theta, grad_v: gns_acn1_adjoint's gather of the flow cotangents with these W (a bus walks its diagonal's stamps, no
+ *     scatter), plus the shunt term 2 |V_i| (Gs Re Lambda_i - Bs Im Lambda_i), plus grad_v_min / grad_v_max at their buses.
+ *   lines, columns 2-6 (r, x, b, tau, shift): gns_pf_adjoint's stamp algebra with +W where the mismatch term has -Lambda; parallel
+ *     lines each get their own row; a line whose id columns are not buses of the grid gets a NaN row.  Columns 0, 1: 0.
+ *   buses: Pd = grad_slack_p + grad_gen_p[first slack unit] at the slack, 0 elsewhere; Qd = (sum_u grad_gen_q_u) / n_i; Gs = |V|^2
+ *     Re Lambda; Bs = -|V|^2 Im Lambda; columns 0, 1: 0.
+ *   generators, column 6 (Pg): a unit off the slack gets grad_gen_p_u; the first slack unit -grad_slack_p; every other slack unit
+ *     grad_gen_p_u - grad_slack_p - grad_gen_p[first slack unit] (its own gen_p is its Pg, and its Pg leaves both slack_p and the
+ *     first unit's gen_p).  Every other column 0 (the forward reads neither vg nor qg).
+ *   A grid whose incoming gradients are all exactly zero or NULL gets exactly zero rows whatever its state: it is skipped, never
+ *   multiplied by zero.  fp64 throughout, the three input gradients rounded once to fp32.  No atomics, every sum in a fixed order:
+ *   a grid's gradient is bit-identical alone, in any batch and from run to run.
+ *
+ * Kernel (gns_pfs.hip): one wave per grid, the forward's LDS image (40 N bytes).  It reads no Y-bus, so it needs no workspace:
+ * gns_pfs_adjoint_workspace_bytes answers 0 and workspace may be NULL.
+ * Errors, in order: GNS_EINVAL for what gns_pfs_evaluate refuses of cfg, the blob, the inputs, v, theta, rating_per_grid and Bt and
+ * for a NULL worst_line, v_min_bus or v_max_bus; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Before any
+ * launch, with no allocation and no host synchronisation.
+ * Not here: batches that mix topologies, second derivatives. */
+int gns_pfs_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
+int gns_pfs_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                    const float* buses, const float* lines, const float* generators, int64_t Bt,
+                    const double* v, const double* theta, const double* rating, int32_t rating_per_grid,
+                    const int32_t* worst_line, const int32_t* v_min_bus, const int32_t* v_max_bus,
+                    const double* grad_p_from, const double* grad_q_from, const double* grad_p_to, const double* grad_q_to,
+                    const double* grad_p_inj, const double* grad_q_inj, const double* grad_gen_p, const double* grad_gen_q,
+                    const double* grad_slack_p, const double* grad_worst_loading, const double* grad_v_min, const double* grad_v_max,
+                    double* grad_v, double* grad_theta, float* grad_buses, float* grad_lines, float* grad_generators,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

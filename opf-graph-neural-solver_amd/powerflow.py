@@ -53,6 +53,11 @@ the list (``gns_pf_prepare_topology_out_gen``) and every row runs Newton-Raphson
 as in ``ac_contingency_screen`` (``csrc/gns_acg1.hip``).  ``ac_generator_contingency_screen_differentiable(...)`` is the same screen
 with a backward: one ``gns_acg1_adjoint`` call, per row one factorisation and one transposed solve at the forward's state on the
 row's own analysis, with the gradients of the dispatch, the set points and the pickup weights by generator row.
+
+``solved_case(buses, lines, generators, v, theta)`` is the base row of that family and what PYPOWER's ``pfsoln`` adds to a solve: at
+a given state (a solver's, or a GNS prediction) the flows at both ends of every line, the bus injections, Newton-Raphson's own
+``||F||_inf``, the generators' ``P`` and ``Q``, the slack's balancing power and the screens' summaries, in one launch
+(``csrc/gns_pfs.hip``), with a backward (``gns_pfs_adjoint``) to the state and the inputs that needs no linear solve.
 """
 from __future__ import annotations
 
@@ -94,6 +99,9 @@ AcGeneratorContingencyResult = namedtuple('AcGeneratorContingencyResult', ['base
                                                                            'p_to', 'q_to', 'worst_loading', 'worst_line', 'v_min',
                                                                            'v_min_bus', 'v_max', 'v_max_bus', 'converged', 'iterations',
                                                                            'mismatch', 'islanding'])
+
+SolvedCase = namedtuple('SolvedCase', ['p_from', 'q_from', 'p_to', 'q_to', 'p_inj', 'q_inj', 'mismatch', 'gen_p', 'gen_q', 'slack_p',
+                                       'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max', 'v_max_bus'])
 
 MixedPlan = namedtuple('MixedPlan', ['topology', 'order', 'grid_off', 'member_off', 'topo_set', 'slack_bus', 'islanded'])
 
@@ -1775,6 +1783,148 @@ def ac_generator_contingency_screen_differentiable(buses, lines, generators, B=N
     with two lines, second derivatives.  Contract: ``include/gns_powerflow.h``, "Gradients of the AC generator screen"."""
     return _ac_generator_screen(buses, lines, generators, B, L, G, slack_bus, contingencies, pickup, rating, tol, max_iter, flows,
                                 states, True)
+
+
+_PFS_LDS_FORMULA = '40 N bytes per grid: five bus vectors'
+_PFS = _Solver('gns_pfs', PowerFlowTopology, _PFS_LDS_FORMULA)   # the solved case: Newton-Raphson's analysis, its own small LDS image
+
+# the [Bt,E] / [Bt,N] / [Bt,Gn] float64 outputs of gns_pfs_evaluate in its order, then its [Bt] outputs with their dtypes
+_PFS_ROWS = (('p_from', 'E'), ('q_from', 'E'), ('p_to', 'E'), ('q_to', 'E'), ('p_inj', 'N'), ('q_inj', 'N'), ('gen_p', 'Gn'),
+             ('gen_q', 'Gn'))
+_PFS_SCALARS = (('mismatch', torch.float64), ('slack_p', torch.float64), ('worst_loading', torch.float64), ('worst_line', torch.int32),
+                ('v_min', torch.float64), ('v_min_bus', torch.int32), ('v_max', torch.float64), ('v_max_bus', torch.int32))
+_PFS_C_ORDER = tuple(n for n, _ in _PFS_ROWS) + tuple(n for n, _ in _PFS_SCALARS)
+# the differentiable outputs in the order gns_pfs_adjoint takes their incoming gradients
+_PFS_DIFF = ('p_from', 'q_from', 'p_to', 'q_to', 'p_inj', 'q_inj', 'gen_p', 'gen_q', 'slack_p', 'worst_loading', 'v_min', 'v_max')
+
+
+def solved_case(buses, lines, generators, v, theta, B=None, L=None, G=None, *, slack_bus=None, rating=None):
+    """The solved case of an AC power flow at a given state, on the device: what PYPOWER's ``runpf`` returns next to the voltages
+    (its ``pfsoln`` step) and the base row of the AC contingency screens, for every grid of a batch that shares one topology.  The
+    state may be a solver's (``solved_case(b, l, g, *newton_raphson(b, l, g)[:2])``) or any other, such as a GNS prediction, which then
+    gets the solver's own ``||F||_inf`` and the branch-model loadings.  The call evaluates at the state given and iterates nothing.
+
+    ``buses``, ``lines``, ``generators``, the column maps ``B, L, G``, ``slack_bus`` and the device handling are ``newton_raphson``'s
+    (one topology per call, analysed and cached as there; a batch whose id columns differ raises).  ``v``, ``theta``: ``[Bt,N]`` of
+    any float dtype, used as float64 and as given (``theta`` is not shifted); with a 2-D single grid ``[N]`` is accepted.
+    ``rating``: None (1), ``[E]`` or ``[Bt,E]``, positive and finite, as the AC screens take it.
+
+    Returns ``SolvedCase``, float64 unless said, on the inputs' device:
+      p_from, q_from, p_to, q_to   ``[Bt,E]``: the screens' branch flows on the line's own makeYbus stamps, ``S_f = V_f conj(Y_ff V_f +
+                     Y_ft V_t)``, ``S_t = V_t conj(Y_tf V_f + Y_tt V_t)``; NaN at a line whose id columns are not buses of the grid
+      p_inj, q_inj   ``[Bt,N]``: what each bus injects into the network, ``V_i conj(sum_k Y_ik V_k)`` on the Y-bus with its shunts
+      mismatch       ``[Bt]``: Newton-Raphson's ``||F||_inf`` at this state (``|p_inj - Psp|`` at PV and PQ buses, ``|q_inj - Qsp|`` at PQ
+                     buses), NaN when a term is not finite; at ``newton_raphson``'s result it is that call's ``mismatch`` bit for bit
+      gen_p, gen_q   ``[Bt,Gn]``: a bus with n listed units produces ``q_inj + Qd``, shared equally among them (no limit ranges); ``gen_p``
+                     is every unit's ``Pg`` as given, but the first unit listed on the slack, which carries ``p_inj + Pd`` of the
+                     slack less the other slack units' ``Pg``.  The ``qg`` column is not read
+      slack_p        ``[Bt]``: ``p_inj + Pd`` of the slack less the ``Pg`` listed there: what the slack produces beyond its listed dispatch
+                     (``dc_power_flow``'s ``slack_p``); defined for a slack without a unit too
+      worst_loading  ``[Bt]``, ``max_l max(|S_f|, |S_t|) / rating_l``, with worst_line ``[Bt]`` int32
+      v_min, v_max   ``[Bt]`` with v_min_bus, v_max_bus ``[Bt]`` int32 (0-based)
+    The summaries have the AC screens' definitions and tie rules: the lowest index among equals, a NaN wins at the lowest index that
+    holds one.  A grid's outputs are bit-identical alone, in any batch and from run to run; a NaN in a grid's state gives that grid
+    NaN outputs and leaves the others alone.  With a 2-D single grid the batch dimension is dropped.
+
+    Gradients: with grad mode on and ``requires_grad`` on any of ``buses`` / ``lines`` / ``generators`` / ``v`` / ``theta``, the four
+    flows, ``p_inj``, ``q_inj``, ``gen_p``, ``gen_q``, ``slack_p``, ``worst_loading``, ``v_min`` and ``v_max`` are differentiable through one
+    ``gns_pfs_adjoint`` launch (no linear solve: every term reduces to cotangents at the line ends and the bus shunts): ``v`` and
+    ``theta`` at every bus, the slack included; ``Pd, Qd, Gs, Bs``; the lines' ``r, x, b, tau, shift``; the generators' ``Pg``.  Every
+    other column gets 0 (``vg`` is not read by the forward); a line whose id columns are not buses gets a NaN row.  ``mismatch`` and
+    the indices are not differentiable and ``rating`` is a constant.  ``worst_loading`` sends its gradient to ``worst_line`` at the end
+    that attains the maximum (the from end on equality), ``v_min`` / ``v_max`` to the buses reported.  Because ``v`` and ``theta`` are
+    ordinary inputs, a state that came from ``newton_raphson`` with ``requires_grad`` inputs backpropagates the total derivative
+    through ``gns_pf_adjoint`` by autograd's chain.  A grid whose incoming gradients are all exactly zero gets exactly zero rows
+    whatever its state (it is skipped, never multiplied by zero).  The forward's bits are the same with and without gradients; a
+    grid's gradient is bit-identical alone, in any batch and from run to run.
+
+    Out of scope: batches that mix topologies, second derivatives, reactive limits.
+    Contract: ``include/gns_powerflow.h``, "The solved case"."""
+    state_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (v, theta))
+    with torch.no_grad():                    # the shapes first, so that a bad state or rating is refused where no device is visible too
+        single, shaped, shaped_lines, _ = _as_batch(buses, lines, generators, B, L, G)
+        Bt, N, E = shaped.shape[0], shaped.shape[1], shaped_lines.shape[1]
+        rating = _rating(rating, Bt, E, single)
+    v, theta = (torch.as_tensor(x) for x in (v, theta))
+    state = []
+    for name, x in (('v', v), ('theta', theta)):
+        if not x.is_floating_point():
+            raise ValueError(f'{name} must be a float tensor, got {x.dtype}')
+        x = x.unsqueeze(0) if (single and x.dim() == 1) else x
+        if tuple(x.shape) != (Bt, N):
+            raise ValueError(f'v / theta must be [{Bt},{N}], got {tuple(x.shape)}')
+        state.append(x)
+    single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines, generators, B, L, G, None, None, 0.0, 0, False)
+    dev = buses.device
+    v, theta = (x.to(device=dev, dtype=torch.float64).contiguous() for x in state)
+    rating = None if rating is None else rating.to(dev).contiguous()
+    Gn = generators.shape[1]
+    lib = load_library()
+    cfg = PfConfig(N, E, Gn, 0, 0.0)
+    plain = (buses.detach(), lines.detach(), generators.detach())
+    topo = _topology(*plain, slack_bus)
+    lds = 40 * N
+    per_grid = int(rating is not None and rating.dim() == 2)
+    head = (ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr())
+
+    def evaluate(bu, li, ge, vv, th):
+        out = {n: torch.empty(Bt, dict(E=E, N=N, Gn=Gn)[d], dtype=torch.float64, device=dev) for n, d in _PFS_ROWS}
+        out.update({n: torch.empty(Bt, dtype=dt, device=dev) for n, dt in _PFS_SCALARS})
+        ws = _gns._workspace(_size_query(lib.gns_pfs_workspace_bytes, 'gns_pfs_workspace_bytes', (*head[:2], Bt), lds, _PFS.formula), dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_pfs_evaluate(*head, bu.data_ptr(), li.data_ptr(), ge.data_ptr(), Bt, vv.data_ptr(), th.data_ptr(),
+                                        _ptr(rating), per_grid, *(out[n].data_ptr() for n in _PFS_C_ORDER), ws.data_ptr(), ws.numel(),
+                                        stream), 'gns_pfs_evaluate', lds, _PFS.formula)
+        return tuple(out[n] for n in SolvedCase._fields)
+
+    def adjoint(bu, li, ge, vv, th, indices, incoming, need):
+        """One adjoint call at the forward's state and indices (worst_line, v_min_bus, v_max_bus); ``need``: which of buses, lines,
+        generators, v, theta want a gradient."""
+        gb, gl, gg, gv, gth = (torch.empty_like(t) if n else None for t, n in zip((bu, li, ge, vv, th), need))
+        incoming = [None if g is None else g.to(device=dev, dtype=torch.float64).contiguous() for g in incoming]
+        nbytes = _size_query(lib.gns_pfs_adjoint_workspace_bytes, 'gns_pfs_adjoint_workspace_bytes', (*head[:2], Bt), lds, _PFS.formula)
+        ws = _gns._workspace(nbytes, dev) if nbytes else None
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_pfs_adjoint(*head, bu.data_ptr(), li.data_ptr(), ge.data_ptr(), Bt, vv.data_ptr(), th.data_ptr(), _ptr(rating),
+                                       per_grid, *(t.data_ptr() for t in indices), *map(_ptr, incoming), *map(_ptr, (gv, gth, gb, gl, gg)),
+                                       _ptr(ws), nbytes, stream), 'gns_pfs_adjoint', lds, _PFS.formula)
+        return gb, gl, gg, gv, gth
+
+    grad = torch.is_grad_enabled() and (state_grad or any(t.requires_grad for t in (buses, lines, generators)))
+    if grad:
+        out = list(_PFSFunction.apply(evaluate, adjoint, buses, lines, generators, v, theta))
+    else:
+        out = list(evaluate(*plain, v.detach(), theta.detach()))
+    if in_dev != dev:
+        out = [t.to(in_dev) for t in out]
+    if single:
+        out = [t[0] for t in out]
+    return SolvedCase(*out)
+
+
+class _PFSFunction(torch.autograd.Function):
+    """``solved_case`` when an input or the state requires grad: the forward is the evaluation itself (``evaluate`` returns
+    ``SolvedCase``'s fields in order), the backward one ``gns_pfs_adjoint`` call (``adjoint``) at the forward's state and indices."""
+
+    @staticmethod
+    def forward(ctx, evaluate, adjoint, buses, lines, gens, v, theta):
+        out = evaluate(buses, lines, gens, v, theta)
+        res = SolvedCase(*out)
+        ctx.mark_non_differentiable(res.mismatch, res.worst_line, res.v_min_bus, res.v_max_bus)
+        ctx.set_materialize_grads(False)
+        ctx.adjoint = adjoint
+        ctx.save_for_backward(buses, lines, gens, v, theta, res.worst_line, res.v_min_bus, res.v_max_bus)
+        return tuple(out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gout):
+        buses, lines, gens, v, theta, *indices = ctx.saved_tensors
+        g = SolvedCase(*gout)
+        grads = ctx.adjoint(buses, lines, gens, v, theta, indices, [getattr(g, n) for n in _PFS_DIFF], ctx.needs_input_grad[2:7])
+        return (None, None, *grads)
 
 
 def _not_solved(Bt, N, dev):

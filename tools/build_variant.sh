@@ -1,5 +1,6 @@
 #!/bin/bash
-# Builds tools/var_<name>.so: the library with gns_backward.hip (or the file named by SRC=) compiled with extra -D flags,
+# Builds tools/var_<name>.so: the library with gns_backward.hip (or the file named by SRC=, a power-flow source included) compiled with
+# extra -D flags,
 # for A/B timing on one box:  GNS_LIB=tools/var_<name>.so python tools/gpu_time.py 118 16384 4 1:0:2
 # usage: bash tools/build_variant.sh <name> [-DFLAG ...]      (every other object, the power-flow ones included, must have been built by make)
 set -e
@@ -13,6 +14,9 @@ for o in gns_forward gns_backward gns_backward_split gns_gridwg gns_gridwg_bwd g
 done
 hipcc $F "$@" -Rpass-analysis=kernel-resource-usage -c $SRC.hip -o /tmp/var_$name.o 2> /tmp/var_$name.remarks || { cat /tmp/var_$name.remarks | grep -v remark | head -40; exit 1; }
 # (the power-flow objects too: the python package resolves their entry points when it loads a library)
-PF="gns_powerflow.o gns_fdpf.o gns_dcpf.o gns_dcn1.o gns_dcn2.o gns_dcg1.o gns_acn1.o gns_acn2.o gns_acg1.o gns_pf_topology.o"
+PF=""
+for o in gns_powerflow gns_fdpf gns_dcpf gns_dcn1 gns_dcn2 gns_dcg1 gns_acn1 gns_acn2 gns_acg1 gns_pfs gns_pf_topology; do
+  if [ "$o" = "$SRC" ]; then PF="$PF /tmp/var_$name.o"; else PF="$PF $o.o"; fi
+done
 hipcc --offload-arch=gfx950 -shared -fPIC -o ../../tools/var_$name.so $OBJS gns_topology.o $PF
 grep -A12 "${KERNEL:-gns_backward_kernelILi20ELi10ELb1ELb1ELi2}" /tmp/var_$name.remarks | grep -E "VGPRs:|Spill|Scratch|LDS" | sed 's/ \[-Rpass.*//; s/.*remark: *//' | tr '\n' ';'; echo " <- $name"

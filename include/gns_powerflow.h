@@ -1184,6 +1184,70 @@ int gns_pfs_adjoint(const gns_pf_config* cfg, const void* topo_host, const void*
                     double* grad_v, double* grad_theta, float* grad_buses, float* grad_lines, float* grad_generators,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- DC optimal power flow -------------------------------------------------------------------------------------------------------
+ * PYPOWER's DC OPF (dcopf / dcopf_solver) without piecewise-linear costs, for every grid of a batch: the dispatch of every listed
+ * unit that is cheapest within the units' bounds and the lines' ratings, its multipliers and the locational marginal prices.  One
+ * fast-decoupled blob per call (gns_fd_prepare_topology); buses, lines, generators as in gns_dc_solve.  cfg: n_bus, n_line, n_gen,
+ * max_iter (iterations allowed) and tol (the termination tolerance).
+ *
+ * Problem, per grid, fp64:  min sum_g c2_g p_g^2 + c1_g p_g  subject to  Bbus[r, r] theta_r = P_r(p),  theta_slack = 0,
+ *   |b_l (theta_f - theta_t) + Pfinj_l| <= rating_l,  Pmin_g <= p_g <= Pmax_g,
+ * with b, Pfinj, Pbusinj and P = sum p - Pd - Gs - Pbusinj exactly gns_dc_solve's; the slack's balance is the one equality left once
+ * theta is eliminated: sum_g p_g = sum_i (Pd_i + Gs_i).  The listed Pg (column 6) is not read; Pmax and Pmin are columns 1 and 2.
+ *   cost    [Gn,2] (cost_per_grid = 0) or [Bt,Gn,2] (1) fp64: (c2, c1) per unit, in per-unit p; c2 >= 0 (all zero: a linear program).
+ *   rating  NULL (no line has a limit), [E] (rating_per_grid = 0) or [Bt,E] (1) fp64: positive; +inf: that line has no limit.
+ *
+ * Method.  Shift factors: one solve z_g = A^-1 e_bus(g) per unit on the factor of A = Bbus[r, r] gives S_g[l] = b_l (z_g[f_l] -
+ * z_g[t_l]) (a zero column for a unit on the slack); f0 is the flow without generation; the inequalities are f0 + S p <= rating,
+ * -(f0 + S p) <= rating, p <= Pmax, -p <= -Pmin (h <= 0, rows of A_in).  A primal-dual interior point with PIPS's scheme on p, the
+ * slacks z > 0 and the multipliers mu > 0 and lambda:
+ *   start     p the midpoint of the bounds, z = max(1, -h), gamma = 1, mu = gamma / z, lambda = 0
+ *   test      before every update, all three below tol:  max(|g|, max h) / (1 + max(|p|_inf, |z|_inf)),
+ *             |L_x|_inf / (1 + max(|lambda|, |mu|_inf)),  z.mu / (1 + |p|_inf);   g = sum p - demand,
+ *             L_x = 2 c2 p + c1 + lambda + A_in^T mu
+ *   matrix    M = diag(2 c2) + A_in^T diag(mu / z) A_in, Gn x Gn, plus delta trace(M) / Gn on its diagonal, delta = 1e-14; dense
+ *             Cholesky in LDS; a pivot that is not positive or not finite ends the grid with its last iterate, converged 0
+ *   step      M w = -(L_x + A_in^T ((gamma + mu h) / z)), M u = 1, dlambda = (sum w + g) / sum u, dp = w - dlambda u,
+ *             dz = -h - z - A_in dp, dmu = -mu + (gamma - mu dz) / z; separate primal and dual lengths min(xi min(z / -dz), 1) and
+ *             min(xi min(mu / -dmu), 1) with xi = 0.99995; then gamma = sigma z.mu / n_ineq, sigma = 0.1.  A step that is not
+ *             finite is not taken: the grid ends with its last iterate, converged 0.
+ * Outputs, every element written:
+ *   pg [Bt,Gn]; theta [Bt,N] and line_flow [Bt,E]: gns_dc_solve's definitions at the injections of pg, formed and solved in fp64
+ *   (pg is never rounded to fp32); mu_line [Bt,E]: the multiplier of the upper limit minus that of the lower (0 at a line without a
+ *   limit); mu_pmax, mu_pmin [Bt,Gn] >= 0; lmp [Bt,N] = -lambda - PTDF^T mu_line, the derivative of the optimal cost with respect
+ *   to Pd at each bus, from one more solve on the symmetric factor with right-hand side sum_l b_l mu_line_l (e_f - e_t) (no [E,N]
+ *   matrix is formed); objective [Bt]: the cost at pg; converged [Bt] u8; iterations [Bt] i32: the updates made.
+ *   A grid that reaches max_iter keeps its last finite iterate with converged 0.  A grid is not solved (iterations -1, NaN in every
+ *   fp64 output, converged 0) when its base factor or a unit's solve fails, its data (Pd, Gs, the lines, Pmin, Pmax, cost, rating)
+ *   are not finite (a rating of +inf aside), a rating is not positive, a c2 is negative, some unit has Pmin >= Pmax, or its demand
+ *   lies outside [sum Pmin, sum Pmax]; the other grids are unaffected.  No atomics, every sum in a fixed order: a grid's result is
+ *   bit-identical alone, in any batch, in any order, with cost and rating shared or per grid, and from run to run.
+ *
+ * Kernels (gns_dcopf.hip), three launches, a wave per workgroup:
+ *   factor  per (grid, chunk of W units) on gns_dcn1_screen's LDS image at width W plus 32 Gn bytes (generator rows of zeros: the
+ *           base case is the one without generation): S as [E][Gn] per grid, f0, the units' finite flags and the grid's status
+ *   ipm     per grid; LDS 8 (Gn (Gn + 1) / 2 + 14 Gn + 10 E) bytes: the packed triangle of M and the iterate; S streams from
+ *           the workspace
+ *   finish  per grid on the factor kernel's image at width 1: theta, line_flow, lmp
+ * gns_dcopf_lds_bytes: the largest of these images, and W (NULL: not wanted), the largest power of two up to 64 whose factor image
+ * fits.  gns_dcopf_workspace_bytes: 8 Bt (E Gn + E + Gn + 3) bytes rounded up to 256.
+ *
+ * Errors, in order: GNS_EINVAL for a NULL device blob, input, cost, output or workspace, for cost_per_grid or rating_per_grid outside
+ * {0, 1}, for Bt <= 0 or above 2^31 - 1, for a NULL cfg or one gns_pf_solve refuses, a NULL host blob, a blob that is not a
+ * fast-decoupled blob or whose N, E, Gn are not cfg's, for Gn = 0, and for more workgroups than a launch takes; then GNS_ESIZE for
+ * a short workspace; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Every refusal comes before any launch;
+ * nothing is allocated and the host is not synchronised.
+ * Not here: batches that mix topologies, gradients of the optimum, AC OPF, units with Pmin = Pmax, piecewise-linear costs,
+ * contingency constraints. */
+int gns_dcopf_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes);
+int gns_dcopf_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
+int gns_dcopf_solve(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                    const float* buses, const float* lines, const float* generators, int64_t Bt,
+                    const double* cost, int32_t cost_per_grid, const double* rating, int32_t rating_per_grid,
+                    double* pg, double* theta, double* line_flow, double* lmp, double* mu_line, double* mu_pmax, double* mu_pmin,
+                    double* objective, uint8_t* converged, int32_t* iterations,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

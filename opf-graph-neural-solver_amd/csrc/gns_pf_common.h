@@ -122,6 +122,15 @@ PF_HOST_DEVICE inline int dcn1_adjoint_lanes(const int32_t* h, int64_t max_bytes
 // Doubles of one (grid, chunk) partial of the adjoint's workspace: dl/dP by bus, dl/db and the sum of w by line, then the chunk's status
 PF_HOST_DEVICE inline int64_t dcn1_adjoint_partial(const int32_t* h) { return (int64_t)h[FH_N] + 2 * (int64_t)h[FH_E] + 1; }
 
+// LDS image of one workgroup of the DC optimal power flow's interior-point kernel (gns_dcopf_lds_bytes), one grid per workgroup:
+// the packed lower triangle of the Gn x Gn normal matrix, fourteen doubles per generator (the dispatch, its bounds and costs, the
+// box rows' slacks and multipliers, the gradients, the two right-hand sides and the step) and ten per line (f0, the rating, the flow,
+// the limit rows' slacks and multipliers, their weights and the two vectors S^T is applied to)
+PF_HOST_DEVICE inline int64_t dcopf_lds_bytes(const int32_t* h) {
+  const int64_t Gn = h[FH_GN];
+  return 8 * (Gn * (Gn + 1) / 2 + 14 * Gn + 10 * (int64_t)h[FH_E]);
+}
+
 // What the code that handles either kind of blob (the set checks on the host and in the set kernels) needs to know of a kind.
 // The magic, the total, N, E and Gn sit at the same header words in both.
 static_assert(FH_MAGIC == PH_MAGIC && FH_TOTAL == PH_TOTAL && FH_N == PH_N && FH_E == PH_E && FH_GN == PH_GN, "shared header words");

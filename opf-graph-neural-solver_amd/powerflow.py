@@ -78,6 +78,9 @@ PowerFlowResult = namedtuple('PowerFlowResult', ['v', 'theta', 'converged', 'ite
 
 DcPowerFlowResult = namedtuple('DcPowerFlowResult', ['v', 'theta', 'line_flow', 'slack_p', 'converged'])
 
+DcOpfResult = namedtuple('DcOpfResult', ['pg', 'theta', 'line_flow', 'lmp', 'mu_line', 'mu_pmax', 'mu_pmin', 'objective', 'converged',
+                                         'iterations'])
+
 DcContingencyResult = namedtuple('DcContingencyResult', ['base', 'outages', 'line_flow', 'worst_loading', 'worst_line', 'islanding',
                                                          'converged'])
 
@@ -689,6 +692,113 @@ def _dc_adjoint(lib, cfg, target, buses, lines, gens, theta, conv, incoming, nee
         return _unsolved_grads(gin, incoming, Bt, dev)
     _launch(lib, _DC, 'adjoint', cfg, target, (buses, lines, gens), (theta, conv, *incoming, *gin))
     return gin
+
+
+_DCOPF_LDS_FORMULA = ("max(8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) + 32 Gn, 8 * (Gn (Gn + 1) / 2 + 14 Gn + 10 E)) bytes per "
+                      "workgroup: the DC N-1 screen's image with the solves of W units side by side (here W = 1, the narrowest) and "
+                      "a generator block of zeros, or the interior point's packed Gn x Gn normal matrix and its iterate")
+_DCOPF = _Solver('gns_dcopf', FdTopology, _DCOPF_LDS_FORMULA)   # the DC optimal power flow: the DC analysis and the screens' image
+
+
+def _dcopf_cost(cost, Bt, Gn, single):
+    """The checked cost: float64 ``[Gn,2]`` / ``[Bt,Gn,2]`` of ``(c2, c1)``, finite, ``c2 >= 0``."""
+    if cost is None:
+        raise ValueError('cost is required: float64 [Gn,2] or [Bt,Gn,2] of (c2, c1) per unit')
+    c = torch.as_tensor(cost)
+    if c.dtype != torch.float64:
+        raise ValueError(f'cost must be float64, got {c.dtype}')
+    if single and c.dim() == 3 and c.shape[0] == 1:
+        c = c[0]
+    if tuple(c.shape) not in ((Gn, 2), (Bt, Gn, 2)):
+        raise ValueError(f'cost must be [{Gn},2] or [{Bt},{Gn},2], got {tuple(c.shape)}')
+    if not bool(torch.isfinite(c).all()):
+        raise ValueError('cost must be finite')
+    if not bool((c[..., 0] >= 0).all()):
+        raise ValueError('cost: c2 (column 0) must be >= 0')
+    return c
+
+
+def _dcopf_rating(rating, Bt, E, single):
+    """The checked rating of the optimal power flow: None, or float64 ``[E]`` / ``[Bt,E]``, positive; ``+inf``: no limit there."""
+    if rating is None:
+        return None
+    r = torch.as_tensor(rating)
+    if r.dtype != torch.float64:
+        raise ValueError(f'rating must be float64, got {r.dtype}')
+    if single and r.dim() == 2 and r.shape[0] == 1:
+        r = r[0]
+    if tuple(r.shape) not in ((E,), (Bt, E)):
+        raise ValueError(f'rating must be [{E}] or [{Bt},{E}], got {tuple(r.shape)}')
+    if not bool((r > 0).all()):
+        raise ValueError('rating must be positive (+inf: the line has no limit)')
+    return r
+
+
+def dc_optimal_power_flow(buses, lines, generators, B=None, L=None, G=None, *, cost, rating=None, slack_bus=None, tol=1e-8,
+                          max_iter=150):
+    """DC optimal power flow (PYPOWER ``dcopf`` / ``dcopf_solver`` without piecewise-linear costs) of every grid of a batch, on the
+    device: the dispatch that is cheapest within the units' bounds and the lines' ratings, and what a megawatt costs at each bus.
+
+    Inputs, column maps, the slack and single-grid handling are ``dc_power_flow``'s; the batch has one topology.  The dispatch of
+    every listed unit is the variable: the listed ``Pg`` is ignored, the bounds are the ``Pmin`` and ``Pmax`` columns.  ``cost``:
+    float64 ``[Gn,2]`` or ``[Bt,Gn,2]`` of ``(c2, c1)`` per unit, the objective ``sum_g c2_g p_g^2 + c1_g p_g`` in per-unit ``p``;
+    ``c2 >= 0``, all entries finite (``c2 == 0`` everywhere is a linear program).  ``rating``: None, or float64 ``[E]`` / ``[Bt,E]``,
+    positive; ``+inf`` (or None) means the line has no limit.  ``tol``: the termination tolerance; ``max_iter``: iterations allowed.
+
+    Per grid, in float64: ``min f(p)`` subject to ``Bbus[r,r] theta_r = P_r(p)``, ``theta_slack = 0``, ``|b_l (theta_f - theta_t) +
+    Pfinj_l| <= rating_l`` and ``Pmin <= p <= Pmax``, with ``b``, ``Pfinj``, ``Pbusinj`` and ``P = sum p - Pd - Gs - Pbusinj`` exactly
+    ``dc_power_flow``'s.  A primal-dual interior point with PIPS's steps and termination, on the problem reduced to ``p`` by generator
+    shift factors (one more solve on the base factor per unit); method and constants: ``include/gns_powerflow.h``, "DC optimal power
+    flow".
+
+    Returns ``DcOpfResult(pg, theta, line_flow, lmp, mu_line, mu_pmax, mu_pmin, objective, converged, iterations)`` on the inputs'
+    device: ``pg`` float64 ``[Bt,Gn]``; ``theta`` ``[Bt,N]`` and ``line_flow`` ``[Bt,E]`` as ``dc_power_flow`` defines them at ``pg``
+    (kept in float64); ``lmp`` ``[Bt,N]``, the derivative of the optimal cost with respect to ``Pd`` at each bus (energy plus
+    congestion); ``mu_line`` ``[Bt,E]``, the multiplier of a line's upper limit minus that of its lower; ``mu_pmax``, ``mu_pmin``
+    ``[Bt,Gn]`` ``>= 0``; ``objective`` ``[Bt]``, the cost at ``pg``; ``converged`` bool ``[Bt]``; ``iterations`` int32 ``[Bt]``.
+    A grid that reaches ``max_iter`` (or meets a pivot that is not positive) keeps its last finite iterate with ``converged`` False.
+    A grid is not solved (``iterations`` -1, NaN outputs) when its base factor fails, its data are not finite, some unit has
+    ``Pmin >= Pmax`` or its demand lies outside ``[sum Pmin, sum Pmax]``; the other grids are unaffected, and every grid's result is
+    bit-identical alone, in any batch, in any order and from run to run.  There is no host synchronisation after the analysis of
+    the topology.  Not differentiable."""
+    _check_iteration(tol, max_iter)
+    with torch.no_grad():
+        # the shapes first, so that a bad cost or rating is refused where no device is visible too
+        single, shaped, shaped_lines, shaped_gens = _as_batch(buses, lines, generators, B, L, G)
+        Bt, E, Gn = shaped.shape[0], shaped_lines.shape[1], shaped_gens.shape[1]
+        if Gn == 0:
+            raise ValueError('dc_optimal_power_flow needs at least one generator')
+        cost = _dcopf_cost(cost, Bt, Gn, single)
+        rating = _dcopf_rating(rating, Bt, E, single)
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None,
+                                                                 None, tol, max_iter, False)
+        lib = load_library()
+        N, dev = buses.shape[1], buses.device
+        cfg = PfConfig(N, E, Gn, int(max_iter), float(tol))
+        topo = _analysed(_FD, *_topology_key(buses, lines, generators, slack_bus, 'dc_optimal_power_flow'), dev)
+        lds = lambda: _screen_lds_bytes('gns_dcopf_lds_bytes', topo.host)[0]     # noqa: E731
+        cost, rating = cost.to(dev).contiguous(), None if rating is None else rating.to(dev).contiguous()
+        f64 = dict(dtype=torch.float64, device=dev)
+        pg, mu_pmax, mu_pmin = (torch.empty(Bt, Gn, **f64) for _ in range(3))
+        theta, lmp = (torch.empty(Bt, N, **f64) for _ in range(2))
+        flow, mu_line = (torch.empty(Bt, E, **f64) for _ in range(2))
+        objective = torch.empty(Bt, **f64)
+        conv, iters = torch.empty(Bt, dtype=torch.uint8, device=dev), torch.empty(Bt, dtype=torch.int32, device=dev)
+        ws = _gns._workspace(_size_query(lib.gns_dcopf_workspace_bytes, 'gns_dcopf_workspace_bytes',
+                                         (ctypes.byref(cfg), topo.host.ctypes.data, Bt), lds, _DCOPF.formula), dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_dcopf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
+                                       generators.data_ptr(), Bt, cost.data_ptr(), int(cost.dim() == 3), _ptr(rating),
+                                       int(rating is not None and rating.dim() == 2),
+                                       *map(_ptr, (pg, theta, flow, lmp, mu_line, mu_pmax, mu_pmin, objective, conv, iters)),
+                                       ws.data_ptr(), ws.numel(), stream), 'gns_dcopf_solve', lds, _DCOPF.formula)
+        out = [pg, theta, flow, lmp, mu_line, mu_pmax, mu_pmin, objective, conv.bool(), iters]
+        if in_dev != dev:
+            out = [t.to(in_dev) for t in out]
+        if single:
+            out = [t[0] for t in out]
+        return DcOpfResult(*out)
 
 
 def _dcn1_lds_bytes(host):

@@ -100,7 +100,9 @@ int gns_forward(const gns_config* cfg, const void* topo_dev, const float* params
  * L_m.{K-1} (and phi_m.{K-1}) receive exactly zero, matching the reference where they get no gradient.
  * buses / lines / generators are the tensors the matching gns_forward was given (still owned by the caller, unchanged):
  * the grid-per-workgroup kernels re-read the batch-constant inputs from them; the lane-per-grid kernels ignore them.
- * The mapping ("train_mapping", "gw_pack" options) must not change between a forward and its backward. */
+ * Options must not change between a forward and its backward: the mapping ("train_mapping", "gw_pack") and everything that decides
+ * what the forward saves for which backward ("bwd_variant", "dw_mfma", "bwds_mode", "bwds_save": with "bwds_save" the workspace
+ * holds first-layer activations where it otherwise holds hidden sums, and only the backward the forward expected can read them). */
 int gns_backward(const gns_config* cfg, const void* topo_dev, const float* params,
                  const float* buses, const float* lines, const float* generators, int64_t Bt,
                  const void* packed_inputs,
@@ -212,6 +214,10 @@ int gns_profile_read(int backward, float* ms_sum, int* launches);
  *   "bwds_mode"   sweep kernels per reverse step of variant 4: 0 one per family | 1 (default) {L_m} {L_theta + L_v} | 2 all three
  *                 families of a bus in one kernel
  *   "bwds_chunks" bus chunks per 64-grid group of variant 4's sweeps: 0 auto | 8 | 12 | 16 | 24 | 32
+ *   "bwds_save"   1 (default): a plain training call (save_state 1, one topology, no input gradients) of a three-phi model on the
+ *                 (latent 20, hidden 10) kernels whose backward is variant 4 in "bwds_mode" 1 saves the first-layer activations of
+ *                 its L nets in the rows of the hidden sums, and the sweeps start from them instead of recomputing that layer:
+ *                 same results bit for bit, a faster step.  Every other call saves hidden sums, as does 0 (diagnostic).
  *   "dw_mfma"     0: weight-gradient contraction on packed FMAs instead of the fp32 matrix pipe
  *   "team"        lane-per-grid kernels, batches with fewer 64-grid groups than CUs: workgroups per group, 0 auto (as many
  *                 as keep every workgroup resident by the kernel's own occupancy at that launch configuration) | 1 none | 2 | 4.
@@ -230,6 +236,7 @@ int gns_profile_read(int backward, float* ms_sum, int* launches);
  *   "last.dw_mfma"     weight-gradient engine of a lane-per-grid backward: 1 matrix pipe | 0 packed FMAs
  *   "last.bwds_mode", "last.bwds_chunks", "last.bwds_R"   sweep mode, bus chunks per group and groups per sweep workgroup of a split backward
  *   "last.bwd_gw_pack" grids per workgroup of a grid-per-workgroup backward
+ *   "last.bwds_save"   1 the backward read saved first-layer activations ("bwds_save") | 0 hidden sums (every other backward)
  * Both mappings and both engines compute the same function of the reference (GNS/main.py:140-202, :288). */
 int gns_set_option(const char* name, int value);
 int gns_get_option(const char* name, int* value);

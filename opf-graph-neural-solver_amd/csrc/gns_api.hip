@@ -23,6 +23,7 @@ struct GnsTuning {
   int team;          // GNS_TEAM: workgroups per 64-grid group of the lane mapping when the batch leaves CUs idle: 0 auto, 1 none, 2, 4
   int bwds_mode;     // GNS_BWDS_MODE: sweep kernels per reverse step of the split backward: 0 one per family, 1 {L_m} {L_theta + L_v}, 2 all three families per bus in one kernel
   int bwds_chunks;   // GNS_BWDS_CHUNKS: bus chunks per 64-grid group of the split backward's sweeps (0 = auto: 8, 16 or 32)
+  int bwds_save;     // GNS_BWDS_SAVE: 1 (default) a training forward whose backward is the split backward in mode 1 at latent 20, hidden 10 saves L's first-layer activations in place of the hidden sums (saves_first_layer); 0 always the hidden sums
 };
 
 // One row per option: its name (gns_set_option / gns_get_option), where it lives, the values it takes (lo..hi, or `check`, which may
@@ -50,9 +51,10 @@ const GnsOption g_options[] = {
   {"team",          &GnsTuning::team,          0, GNS_MAX_TEAM, nullptr,   "GNS_TEAM",          env_int},
   {"bwds_mode",     &GnsTuning::bwds_mode,     0, 2,            nullptr,   "GNS_BWDS_MODE",     env_int},
   {"bwds_chunks",   &GnsTuning::bwds_chunks,   0, 0,            chunks_ok, "GNS_BWDS_CHUNKS",   env_int},
+  {"bwds_save",     &GnsTuning::bwds_save,     0, 1,            nullptr,   "GNS_BWDS_SAVE",     env_int},
 };
 GnsTuning make_tuning() {
-  GnsTuning t{0, 0, GNS_FWD_THREADS / 64, 2, 1, 0, 4, 0, 1, 0};
+  GnsTuning t{0, 0, GNS_FWD_THREADS / 64, 2, 1, 0, 4, 0, 1, 0, 1};
   for (const GnsOption& o : g_options)
     if (const char* e = std::getenv(o.env)) { int v = o.parse(e); if (o.accepts(v)) t.*o.member = v; }
   return t;
@@ -68,20 +70,22 @@ GnsTuning& tuning() {
 struct GnsLast {
   int fwd_kernel, fwd_waves, fwd_plane, team, gw_pack;                   // gns_forward / gns_forward_grouped
   int bwd_kernel, dw_mfma, bwds_mode, bwds_chunks, bwds_R, bwd_gw_pack;   // gns_backward / gns_backward_inputs / gns_backward_grouped
+  int bwds_save;                                                          // ... 1: it read saved first-layer activations, 0: hidden sums
 };
-GnsLast g_last{-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+GnsLast g_last{-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 struct GnsLastName { const char* name; int GnsLast::*member; };
 const GnsLastName g_last_names[] = {                                          // read as "last.<name>"
   {"fwd_kernel", &GnsLast::fwd_kernel}, {"fwd_waves", &GnsLast::fwd_waves}, {"fwd_plane", &GnsLast::fwd_plane}, {"team", &GnsLast::team},
   {"gw_pack", &GnsLast::gw_pack}, {"bwd_kernel", &GnsLast::bwd_kernel}, {"dw_mfma", &GnsLast::dw_mfma}, {"bwds_mode", &GnsLast::bwds_mode},
   {"bwds_chunks", &GnsLast::bwds_chunks}, {"bwds_R", &GnsLast::bwds_R}, {"bwd_gw_pack", &GnsLast::bwd_gw_pack},
+  {"bwds_save", &GnsLast::bwds_save},
 };
 void record_forward(int kernel, int waves, int plane, int team, int pack) {
   g_last.fwd_kernel = kernel; g_last.fwd_waves = waves; g_last.fwd_plane = plane; g_last.team = team; g_last.gw_pack = pack;
 }
-void record_backward(int kernel, int dw_mfma, int mode, int chunks, int R, int pack) {
+void record_backward(int kernel, int dw_mfma, int mode, int chunks, int R, int pack, int save = 0) {
   g_last.bwd_kernel = kernel; g_last.dw_mfma = dw_mfma; g_last.bwds_mode = mode; g_last.bwds_chunks = chunks; g_last.bwds_R = R;
-  g_last.bwd_gw_pack = pack;
+  g_last.bwd_gw_pack = pack; g_last.bwds_save = save;
 }
 
 // ---- per-device state: kernel attributes (dynamic LDS beyond 64 KB is an opt-in per kernel AND device) and the CU count, set up
@@ -202,6 +206,17 @@ bool use_split_backward(const gns_config* c) {
   if (!split_available(c)) return false;
   if (!gns_backward_persistent_supported(c->latent_dim, c->hidden_dim)) return true;      // the only lane-per-grid backward of this pair
   return T.bwd_variant == 4 && T.dw_mfma;
+}
+
+// "This call saves first-layer activations": the training forward stores a1 of every L net where it otherwise stores the hidden sum
+// the net read, and the split backward's sweeps start from it (gns_backward_split.hip, BwdsMeasured).  Evaluated identically by
+// lane_forward and split_backward - changing an option between a forward and its backward is a caller error (see route()).  True only
+// for the shape the saved-activation sweeps are compiled and measured in: a plain training call (save_state 1, one topology, no input
+// gradients) of a three-phi model on the (20, 10) kernels, reversed by the split backward in mode 1.
+bool saves_first_layer(const gns_config* k, int save_state, bool grouped) {
+  const GnsTuning& T = tuning();
+  return T.bwds_save == 1 && save_state == 1 && !grouped && k->multiple_phi == 1 && k->latent_dim == 20 && k->hidden_dim == 10 &&
+         T.bwds_mode == 1 && use_split_backward(k);
 }
 
 // Input gradients (gns_backward_inputs): the input-adjoint buffer behind the split backward's workspace, and the caller's outputs
@@ -389,6 +404,7 @@ int lane_forward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLayo
   fill_forward_families(A, fam);
   fill_loss_weights(A, cfg);
   A.Bt = Bt; A.G = L.groups; A.N = N; A.E = E; A.K = K; A.save = save_state ? 1 : 0;
+  A.save_a1 = saves_first_layer(cfg, save_state, group_topo != nullptr) ? 1 : 0;
   const int team0 = lane_team(L.groups * GNS_LANES);     // (= lane_team(Bt) for a one-topology batch)
   A.team = team0;
   A.team_ws = (unsigned char*)(ws + L.off_team);
@@ -445,7 +461,8 @@ int split_backward(const gns_config* cfg, const GnsFamilies& fam, const GnsFwdLa
     A.igrad = ig->buf;
     if (hipMemsetAsync(A.igrad, 0, ig->bytes, st) != hipSuccess) return GNS_ELAUNCH;
   }
-  record_backward(4, 1, A.mode, A.C, A.R, -1);
+  A.save_a1 = saves_first_layer(cfg, ig ? GNS_SAVE_IGRAD : 1, group_topo != nullptr) ? 1 : 0;
+  record_backward(4, 1, A.mode, A.C, A.R, -1, A.save_a1);
   prof_mark(1, true, st);
   for (int k = K - 1; k >= 0; --k) {
     A.k = k;

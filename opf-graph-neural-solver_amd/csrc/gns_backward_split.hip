@@ -344,13 +344,19 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
   // xs = [v theta | dp dq | m | (the hidden sum this net reads goes here) | deg, 1]; g3s = the upstream of the scalar output (L_theta:
   // thbar, L_v: vbar or 0 on a generator bus); L_m takes macc = d/dm_{k+1} as its upstream.  xsum (d/dv, d/dtheta, d/ddp of the L
   // inputs) and macc (d/dm) accumulate; gS = the adjoint of the hidden sum: assigned (ACC_GS false) or accumulated (the single phi).
-  template <bool ACC_GS, bool STEP0, bool IG = false>
+  // SV (saved activations, GnsBwdsArgs::save_a1): the slot holds a1 of this net instead of the hidden sum.  Layer 1 is not recomputed
+  // and the sum's two readers are gone from here: the caller's BwdsPhi::bus rebuilds the sum from the lines it walks anyway and
+  // finish() then runs the dW1 windows that hold its columns.  g1 and a2, which those windows need, wait in `park` (LDS, [10][64]
+  // pairs); g3 / the upstream of outputs 16.. wait in rows 10.. of the window's A block, which no pass of the line loop rewrites.
+  template <bool ACC_GS, bool STEP0, bool IG = false, bool SV = false>
   __device__ __forceinline__ void bus(const GnsBwdsArgs& A, float* rec, int lane, long long g, int n, float g3s, f2 (&xs)[XL],
-                                      f2 (&macc)[D / 2], f4& xsum, f2 (&gS)[H / 2]) {
+                                      f2 (&macc)[D / 2], f4& xsum, f2 (&gS)[H / 2], float* park = nullptr) {
+    static_assert(!SV || (MULTI && !GNS_BWDS_ONE_LAYOUT && WIDE && 2 * SOFF >= 16 && (FOLD4 || FOLDM)), "saved activations: the (20, 10) windows");
     f2 (&S)[H / 2] = reinterpret_cast<f2 (&)[H / 2]>(xs[SOFF]);
-    load_pairs<H>(A.msg, ((((long long)A.k * A.G + g) * A.N + n) * C::NPHI + fphi) * C::HQ, lane, S);
-    WFirst wf;
     f2 a1[H / 2], a2[H / 2], g2[H / 2], g1[H / 2];
+    if constexpr (SV) load_pairs<H>(A.msg, ((((long long)A.k * A.G + g) * A.N + n) * C::NPHI + fphi) * C::HQ, lane, a1);
+    else load_pairs<H>(A.msg, ((((long long)A.k * A.G + g) * A.N + n) * C::NPHI + fphi) * C::HQ, lane, S);
+    WFirst wf;
     f2 sl[2][H / 2];              // LeakyReLU's slopes at the hidden units, kept from the recomputation (GNS_BWDS_KEEP_SLOPES)
     using TL [[maybe_unused]] = TLay<LIN, H, OUTP>;   // the forward layout of the block: W1t b1 W2t b2 W4t b4
 #if GNS_BWDS_ONE_LAYOUT
@@ -358,7 +364,10 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
     mlp2_fwd<LIN, H>(ptl, xs, a1, a2, NoBG{}, NoLink{}, GNS_SLOPES(sl));
 #else
     using LKm = std::conditional_t<STEP0, NoLink, L2>; using LKs = std::conditional_t<STEP0, std::conditional_t<FOLD4, L0, NoLink>, std::conditional_t<FOLD4, L1, L2>>;
-    if constexpr (STEP0) {
+    if constexpr (SV) {
+      // layer 2 from the saved a1 (W2t, b2 of the same block); layer 1's slope comes from a1 itself below
+      mlp2_fwd_l2<LIN, H>(ptl, a1, a2, std::conditional_t<STEP0, NoLink, L0>{nullptr, nb, &wf}, GNS_SLOPES(sl));
+    } else if constexpr (STEP0) {
       // m_0 = 0 (main.py:141): the latent rows of W1t multiply zeros - exact zeros, so leaving them out changes no bit.  The first
       // layer is the four state inputs (phi_head's shape) + the hidden sum, deg, the bias and the second layer (phi_tail's shape).
       f2 u4[H / 2];
@@ -388,7 +397,9 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
 #endif
 #pragma unroll
     for (int u = 0; u < H / 2; ++u) g2[u] = g2[u] * GNS_SLOPE_OF(sl, 1, a2, u);
-    if constexpr (FOLD4 || FOLDM) {                   // parked at columns 16..26 until the last dW1 window contracts them
+    if constexpr (SV) static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; park_put(park, lane, H / 2 + j, a2[j]); });
+    if constexpr (SV && !FOLDM) {                     // (the line loop rewrites columns 16..: finish() puts a2 there)
+    } else if constexpr (FOLD4 || FOLDM) {            // parked at columns 16..26 until the last dW1 window contracts them
       static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putB<SW>(rec, lane, 8 + j, a2[j]); });
       gws_putB<SW>(rec, lane, 8 + H / 2, f2{1.f, 0.f});
       if constexpr (FOLDM) {
@@ -415,7 +426,11 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
     bwd_rows<H, H>(nb + NL::oW2, g2, g1, NoBG{}, std::conditional_t<FOLD4, L2, NoLink>{&wf, nullptr, nullptr});
 #endif
 #pragma unroll
-    for (int u = 0; u < H / 2; ++u) g1[u] = g1[u] * GNS_SLOPE_OF(sl, 0, a1, u);
+    for (int u = 0; u < H / 2; ++u) {
+      if constexpr (SV) g1[u] = g1[u] * dlrelu2(a1[u]);      // (dlrelu2 is written for the activation's output)
+      else g1[u] = g1[u] * GNS_SLOPE_OF(sl, 0, a1, u);
+    }
+    if constexpr (SV) static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; park_put(park, lane, j, g1[j]); });
     if constexpr (IG && STEP0) {
       // input gradients: the adjoints of (v, theta, dp, dq)_0, which close the initial state (main.py:144-152).  Columns 0..3 of W1,
       // input-major in the forward layout: xsum.w (d/d dq_0) is used by this instantiation only
@@ -436,7 +451,7 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
     static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putA<SW>(rec, lane, j, g1[j]); });
     if constexpr (FOLD4) gws_putA<SW>(rec, lane, H / 2, f2{g3s, 0.f});            // row 10: g3
     if constexpr (FOLDM) static_for<0, (OUT - 16) / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putA<SW>(rec, lane, H / 2 + j, macc[8 + j]); });   // rows 10..: upstream of outputs 16..d-1 (macc is still mbar_{k+1} here)
-    static_for<0, NB1>([&](auto t_) {
+    static_for<0, SV ? 1 : NB1>([&](auto t_) {                                     // SV: the windows with sum columns wait for finish()
       constexpr int t = decltype(t_)::value;
       constexpr int po = (WIDE && t == NB1 - 1) ? W2OFF / 2 : 0;                   // the last window sits right below column 16
       static_for<0, 8>([&](auto j_) { constexpr int j = decltype(j_)::value; if constexpr (8 * t + j < XL) gws_putB<SW>(rec, lane, po + j, xs[8 * t + j]); });
@@ -465,6 +480,24 @@ struct BwdsL : BwdsShape<D, H, MULTI> {
       bwd_inputs<(LIN + 3) / 4, H>(nb + NL::total, g1, to_consumers);
     }
 #endif
+  }
+
+  static __device__ __forceinline__ void park_put(float* park, int lane, int slot, f2 v) { reinterpret_cast<f2*>(park)[slot * GNS_LANES + lane] = v; }
+  static __device__ __forceinline__ f2 park_get(const float* park, int lane, int slot) { return reinterpret_cast<const f2*>(park)[slot * GNS_LANES + lane]; }
+
+  // SV: after the bus's line loop, which left the hidden sum in xs[SOFF..] (summed in line order from zero: the forward's bits): the
+  // dW1 windows 1.. of this bus, with the operands bus() would have given them - g1 back in rows 0..H-1 (rows 10.. still hold g3 /
+  // the upstream of outputs 16..), [a2 | 1] back at columns 16..26.  Each tile gets its one pass per bus, in bus order, as before.
+  __device__ __forceinline__ void finish(float* rec, const float* park, int lane, const f2 (&xs)[XL]) {
+    static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putA<SW>(rec, lane, j, park_get(park, lane, j)); });
+    static_for<0, H / 2>([&](auto j_) { constexpr int j = decltype(j_)::value; gws_putB<SW>(rec, lane, 8 + j, park_get(park, lane, H / 2 + j)); });
+    gws_putB<SW>(rec, lane, 8 + H / 2, f2{1.f, 0.f});
+    static_for<1, NB1>([&](auto t_) {
+      constexpr int t = decltype(t_)::value;
+      constexpr int po = (WIDE && t == NB1 - 1) ? W2OFF / 2 : 0;
+      static_for<0, 8>([&](auto j_) { constexpr int j = decltype(j_)::value; if constexpr (8 * t + j < XL) gws_putB<SW>(rec, lane, po + j, xs[8 * t + j]); });
+      gws_w2r(); gws_pass<SW, (WIDE && t == NB1 - 1) ? W2OFF : 0>(rec, lane, T1[t]); gws_r2w();
+    });
   }
 
   // the tiles -> the (family, step) block of the workgroup's slab (folded block: W1[H][IN] b1 W2 b2 W4 b4); plain stores
@@ -523,7 +556,8 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
 
   // back through the hidden vectors of the lines p0..p1 ending at the bus: gS = the adjoint of their sum.  first = the rows of line
   // p0, requested by the caller before the L net (LA: GNS_BWDS_LINE_AHEAD; else unused)
-  template <bool STEP0, bool IG = false, bool LA = false>
+  // SV (saved activations): also S += a2 of every line, in line order: the hidden sum the forward formed (S arrives as zeros)
+  template <bool STEP0, bool IG = false, bool LA = false, bool SV = false>
   __device__ __forceinline__ void bus(const GnsBwdsArgs& A, float* rec, int lane, const f2 (&xs)[XL], const f2 (&gS)[H / 2],
                                       f2 (&macc)[D / 2], int p0, int p1, long long row_ein, const BwdsLineRows& first) {
     if (p0 >= p1) return;
@@ -565,6 +599,11 @@ struct BwdsPhi : BwdsShape<D, H, MULTI> {
       bwd_rows_fwd_layout<H, H>(ptb + TLay2<PIN, H>::oW2, g2, g1);
 #else
       phi_tail<PIN, H, D>(ptb, uh, xt, a1, a2, NoBG{}, L0{nullptr, pnb, &wf}, GNS_SLOPES(sl));
+      if constexpr (SV) {                               // (xs is the caller's own array: the sum goes where BwdsL::finish reads it)
+        f2* const S = const_cast<f2*>(&xs[B::SOFF]);
+#pragma unroll
+        for (int u = 0; u < H / 2; ++u) S[u] += a2[u];
+      }
 #pragma unroll
       for (int u = 0; u < H / 2; ++u) g2[u] = gS[u] * GNS_SLOPE_OF(sl, 1, a2, u);
       bwd_rows<H, H>(pnb, g2, g1, NoBG{}, L2{&wf, nullptr, nullptr});
@@ -670,8 +709,15 @@ struct BwdsAhead {
 #endif
 };
 
-template <int D, int H, bool MULTI, int FAMS, bool STEP0, bool GROUPED, bool IG>
+// SV: the saved-activation sweeps (BwdsL::bus): BwdsMeasured's shape only, launched when GnsBwdsArgs::save_a1 is set.  Their park
+// (g1 and a2 of the L net across the line loop) is 5 KB of LDS beside the 13.3 KB window: eight workgroups still fit a CU's 160 KB.
+template <bool SV, int H> struct BwdsPark { static __device__ __forceinline__ float* get() { return nullptr; } };
+template <int H> struct BwdsPark<true, H> {
+  static __device__ __forceinline__ float* get() { __shared__ __attribute__((aligned(16))) float park[2 * H * GNS_LANES]; return park; }
+};
+template <int D, int H, bool MULTI, int FAMS, bool STEP0, bool GROUPED, bool IG, bool SV = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWDS_WPE))) gns_bwds_sweep_kernel(GnsBwdsArgs A) {
+  static_assert(!SV || BwdsMeasured<D, H, MULTI, FAMS, GROUPED, IG>::value, "saved activations: the measured shape only");
   using C = GnsDims<D, H, MULTI>;
   static_assert(MULTI || FAMS == 7, "the single phi is reversed after all three L nets");
   constexpr int RB = C::RB, MQ = C::MQ, RBA = 4 + 6 * MQ;
@@ -681,6 +727,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
   // the window alone (no pad behind the last row: every pass reads inside a row): 64 x 52 floats = 26 x 512 B, twelve per CU
   constexpr int RECF = 64 * (D > 16 ? GwSubWide::RS : GwSub::RS);
   __shared__ __attribute__((aligned(16))) float rec[RECF];
+  float* const park = BwdsPark<SV, H>::get();
   const int lane = threadIdx.x;
   // blockIdx = (bus chunk, group block), the group block fastest: blocks 8 apart (same group block modulo 8) share an XCD
   const long long GB = (A.G + A.R - 1) / A.R;
@@ -808,13 +855,21 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(GNS_BWD
       // any line to the first row after the bus rows - inside the group's input rows either way.
       BwdsLineRows lr;
       auto first = [&]() { if constexpr (LA) lr = bwds_line_rows(A.in, row_ein, max(min(p0, E - 1), 0), lane); };
+      // SV: the hidden sum starts every family at zero (the line loop rebuilds it; a bus without in-lines keeps the zeros)
+      constexpr int SOFF = 2 + D / 2;
+      auto zs = [&]() {
+        if constexpr (SV) {
+#pragma unroll
+          for (int j = 0; j < H / 2; ++j) xs[SOFF + j] = f2{0.f, 0.f};
+        }
+      };
       if constexpr (MULTI) {
-        if constexpr (HAS_M) { if (!lastk) { first(); fresh(); lm.template bus<false, STEP0, IG>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS); ahead(); fresh(); pm.template bus<STEP0, IG, LA>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); } }
-        if constexpr (HAS_T) { first(); fresh(); lt.template bus<false, STEP0, IG>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS); if constexpr (!HAS_M) ahead(); fresh(); pt.template bus<STEP0, IG, LA>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); }
+        if constexpr (HAS_M) { if (!lastk) { first(); zs(); fresh(); lm.template bus<false, STEP0, IG, SV>(A, rec, lane, g, n, 0.f, xs, macc, xsum, gS, park); ahead(); fresh(); pm.template bus<STEP0, IG, LA, SV>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); if constexpr (SV) lm.finish(rec, park, lane, xs); } }
+        if constexpr (HAS_T) { first(); zs(); fresh(); lt.template bus<false, STEP0, IG, SV>(A, rec, lane, g, n, a0.y, xs, macc, xsum, gS, park); if constexpr (!HAS_M) ahead(); fresh(); pt.template bus<STEP0, IG, LA, SV>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); if constexpr (SV) lt.finish(rec, park, lane, xs); }
         // v moves only on buses without a generator (main.py:184-186): on a generator bus the upstream of L_v is exactly zero, and with
         // it every adjoint and every weight-gradient term of L_v and of phi_v over the lines ending there - the bus is skipped (the
         // topology is the same for all 64 grids of the wave, so the branch is uniform).  46 % of case118's buses carry a generator.
-        if constexpr (HAS_V) { if (!is_gen[n]) { first(); fresh(); lv.template bus<false, STEP0, IG>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS); fresh(); pv.template bus<STEP0, IG, LA>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); } }
+        if constexpr (HAS_V) { if (!is_gen[n]) { first(); zs(); fresh(); lv.template bus<false, STEP0, IG, SV>(A, rec, lane, g, n, g3v, xs, macc, xsum, gS, park); fresh(); pv.template bus<STEP0, IG, LA, SV>(A, rec, lane, xs, gS, macc, p0, p1, row_ein, lr); if constexpr (SV) lv.finish(rec, park, lane, xs); } }
       } else {
 #pragma unroll
         for (int j = 0; j < H / 2; ++j) gS[j] = f2{0.f, 0.f};
@@ -1080,6 +1135,15 @@ int gns_launch_bwds_sweep(int d, int h, int multi, const GnsBwdsArgs& A, hipStre
 #define GNS_SWEEP(DD, HH, MM, FAMS) do { if (A.group_topo) GNS_SWEEP1(DD, HH, MM, FAMS, true, false); \
                                          else if (A.igrad) GNS_SWEEP1(DD, HH, MM, FAMS, false, true); \
                                          else GNS_SWEEP1(DD, HH, MM, FAMS, false, false); } while (0)
+  if (A.save_a1) {       // gns_api.hip sets it for this shape alone: anything else would read activations as sums
+    if (d != 20 || h != 10 || !multi || A.mode != 1 || A.group_topo || A.igrad) return GNS_EINVAL;
+#define GNS_SAVED(FAMS) do { if (A.k == 0) hipLaunchKernelGGL((gns_bwds_sweep_kernel<20, 10, true, FAMS, true, false, false, true>), dim3(blocks), dim3(64), 0, st, A); \
+                             else hipLaunchKernelGGL((gns_bwds_sweep_kernel<20, 10, true, FAMS, false, false, false, true>), dim3(blocks), dim3(64), 0, st, A); } while (0)
+    if (!fold_m) GNS_SAVED(4);
+    GNS_SAVED(3);
+#undef GNS_SAVED
+    return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
+  }
 #define GNS_CASE(DD, HH)                                                                                                    \
   if (d == DD && h == HH) {                                                                                                 \
     if (!multi) { if (A.mode != 2) return GNS_EINVAL; GNS_SWEEP(DD, HH, false, 7); }                                        \

@@ -285,12 +285,15 @@ struct TLay {
                        total = ob4 + OUTP;
 };
 
-template <int IN, int H, int OUTP>
-__device__ __forceinline__ void mlp_fwd(cfp blk, const f2 (&x)[(IN + 1) / 2], f2 (&a1)[H / 2], f2 (&a2)[H / 2], f2 (&y)[OUTP / 2]) {
+// at_a1(): called once, where a1 has become final (before the first FMA of layer 2): a caller that saves a1 stores it there
+struct NoHook { __device__ __forceinline__ void operator()() const {} };
+template <int IN, int H, int OUTP, class A1F = NoHook>
+__device__ __forceinline__ void mlp_fwd(cfp blk, const f2 (&x)[(IN + 1) / 2], f2 (&a1)[H / 2], f2 (&a2)[H / 2], f2 (&y)[OUTP / 2], A1F&& at_a1 = A1F{}) {
   using B = TLay<IN, H, OUTP>;
   static_assert(H % 2 == 0 && OUTP % 2 == 0, "pairs");
   stream_pairs<B::total>(blk, [&](auto w_, f2 s) {
     constexpr int w = decltype(w_)::value;
+    if constexpr (w == B::oW2) at_a1();
     if constexpr (w < B::ob1) {
       constexpr int i = w / H, j = (w % H) / 2;
       const f2 xi = splat(lane_of<i>(x));        // inputs arrive as aligned pairs: op_sel picks the half, no v_mov
@@ -391,6 +394,28 @@ __device__ __forceinline__ void mlp2_fwd(cfp blk, const f2 (&x)[(IN + 1) / 2], f
       a2[j] = act(a2[j] + s, 1, j);
     }
   }, bg, lk);
+  pin_all(a2);
+}
+
+// The second layer alone, from first-layer activations the forward saved (split backward, gns_backward_split.hip): W2t and b2 of the
+// same T-stream block, in mlp2_fwd's order, so a2 is bitwise what mlp2_fwd makes of the same a1.  SL: as in phi_tail, layer 1 only.
+template <int IN, int H, class LK = NoLink, class SL = decltype(nullptr)>
+__device__ __forceinline__ void mlp2_fwd_l2(cfp blk, const f2 (&a1)[H / 2], f2 (&a2)[H / 2], LK lk = LK{}, SL sl = nullptr) {
+  using B = TLay2<IN, H>;
+  constexpr bool KEEP = !std::is_same<SL, decltype(nullptr)>::value;
+  stream_pairs<B::total - B::oW2, cf16up>(blk + B::oW2, [&](auto w_, f2 s) {
+    constexpr int w = decltype(w_)::value + B::oW2;
+    if constexpr (w < B::ob2) {
+      constexpr int q = w - B::oW2, i = q / H, j = (q % H) / 2;
+      const f2 xi = splat(lane_of<i>(a1));
+      a2[j] = (i == 0) ? s * xi : __builtin_elementwise_fma(s, xi, a2[j]);
+    } else {
+      constexpr int j = (w - B::ob2) / 2;
+      const f2 z = a2[j] + s;
+      if constexpr (KEEP) { const f2 k = dlrelu2(z); sl[1][j] = k; a2[j] = z * k; }
+      else a2[j] = lrelu2(z);
+    }
+  }, NoBG{}, lk);
   pin_all(a2);
 }
 

@@ -199,10 +199,12 @@ __global__ void gns_pack_inputs_kernel(const int* __restrict__ topo, const float
 #define GNS_FWD_ROW_STORES 0      // 1 (diagnostic): keep the dead partial stores of theta / v into the state row
 #endif
 // ------------------------------------------------------------------------------------------------
-template <int D, int H, bool MULTI, bool GROUPED>   // GROUPED: a grouped call (A.group_topo, A.slot_grid), instantiated apart so that the
+// SAVE_A1: the instantiation launched when A.save_a1 is set (gns_api.hip, saves_first_layer: one shape) - every other one is the code it was
+template <int D, int H, bool MULTI, bool GROUPED, bool SAVE_A1 = false>   // GROUPED: a grouped call (A.group_topo, A.slot_grid), instantiated apart so that the
 __global__ void __launch_bounds__(GNS_FWD_MAX_THREADS) gns_forward_kernel(GnsFwdArgs A) {   // one-topology code is what it was
   using C = GnsDims<D, H, MULTI>;
   constexpr int MQ = C::MQ, RB = C::RB;
+  constexpr bool save_a1 = SAVE_A1;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nwaves = blockDim.x >> 6;
@@ -370,12 +372,17 @@ __global__ void __launch_bounds__(GNS_FWD_MAX_THREADS) gns_forward_kernel(GnsFwd
         constexpr int fphi = MULTI ? (l == 0 ? 1 : (l == 1 ? 0 : 2)) : 0;
         constexpr int js = MULTI ? j : 0;                   // the single phi: one sum serves all three L nets (main.py:169-171)
 #ifndef GNS_ABLATE_MSG_SAVE      // diagnostic: the hidden sums are not saved (the backward would have to recompute them): what their 1.1 GB of writes cost the forward
-        if (A.save && (MULTI || l == 0))
+        if (A.save && !save_a1 && (MULTI || l == 0))
 #else
         if (false)
 #endif
           store_pairs_nt<H>(A.msg, ((((long long)k * A.G + g) * N + n) * C::NPHI + fphi) * C::HQ, lane, S[js]);
-        if (l == 1 && skip_v) {                             // (a generator bus keeps its voltage: main.py:184-186)
+        // A.save_a1 (GnsFwdArgs): the slot takes L's first-layer activations instead, as soon as they are final; a generator bus stores
+        // nothing for the v family (the split backward skips it there)
+        auto keep_a1 = [&](const f2 (&a1)[H / 2]) {
+          if (save_a1) store_pairs_nt<H>(A.msg, ((((long long)k * A.G + g) * N + n) * C::NPHI + fphi) * C::HQ, lane, a1);
+        };
+        if (l == 1 && skip_v) {                          // (a generator bus keeps its voltage: main.py:184-186)
           vth_new.x = s0.x;
           if (!(use_plane && tsize == 1) || GNS_FWD_ROW_STORES) reinterpret_cast<float*>(row_ptr(A.state, wr, lane))[0] = s0.x;
           return;
@@ -390,7 +397,7 @@ __global__ void __launch_bounds__(GNS_FWD_MAX_THREADS) gns_forward_kernel(GnsFwd
         f2 a1[H / 2], a2[H / 2];
         if constexpr (l < 2) {
           f2 y[1];
-          mlp_fwd<C::LF_IN, H, 2>(PT + A.t_off[C::NPHI + l] + koff * A.t_sz[C::NPHI + l], x, a1, a2, y);
+          mlp_fwd<C::LF_IN, H, 2>(PT + A.t_off[C::NPHI + l] + koff * A.t_sz[C::NPHI + l], x, a1, a2, y, [&]() { keep_a1(a1); });
           // With the LDS plane inside one workgroup the physics phase takes (v, theta) from the plane and then writes the whole
           // state row: the two 4-byte-per-lane stores into that row (every 64-byte sector of 1 KiB touched for 256 bytes) are dead
           float* r0 = reinterpret_cast<float*>(row_ptr(A.state, wr, lane));
@@ -399,7 +406,7 @@ __global__ void __launch_bounds__(GNS_FWD_MAX_THREADS) gns_forward_kernel(GnsFwd
           else { vth_new.x = is_gen[n] ? s0.x : s0.x + y[0].x; if (row_needed) r0[0] = vth_new.x; }                  // v += L_v off generators (main.py:184-186)
         } else {
           f2 upd_m[D / 2], m_new[D / 2];
-          mlp_fwd<C::LF_IN, H, D>(PT + A.t_off[C::NPHI + 2] + koff * A.t_sz[C::NPHI + 2], x, a1, a2, upd_m);
+          mlp_fwd<C::LF_IN, H, D>(PT + A.t_off[C::NPHI + 2] + koff * A.t_sz[C::NPHI + 2], x, a1, a2, upd_m, [&]() { keep_a1(a1); });
 #pragma unroll
           for (int i = 0; i < D / 2; ++i) m_new[i] = m[i] + upd_m[i];        // main.py:188
           if (k < K - 1) store_pairs_nt<D>(A.state, wr + 1, lane, m_new);   // nothing reads m_K (the reference's L_m.{K-1} has no gradient)
@@ -585,6 +592,10 @@ template <int D, int H, bool MULTI>
 static int launch_forward_t(const GnsFwdArgs& A, int threads, hipStream_t st) {
   // (> 64 KB of dynamic LDS needs an opt-in per kernel and device: gns_fwd_init_device, once, from the library's initialisation)
   if (A.group_topo) hipLaunchKernelGGL((gns_forward_kernel<D, H, MULTI, true>), dim3((unsigned)(A.G * A.team)), dim3(threads), fwd_dyn_lds(A), st, A);
+  else if (A.save_a1) {
+    if constexpr (D == 20 && H == 10 && MULTI) hipLaunchKernelGGL((gns_forward_kernel<D, H, MULTI, false, true>), dim3((unsigned)(A.G * A.team)), dim3(threads), fwd_dyn_lds(A), st, A);
+    else return GNS_EINVAL;               // (gns_api.hip never asks: no backward of this shape reads first-layer activations)
+  }
   else hipLaunchKernelGGL((gns_forward_kernel<D, H, MULTI, false>), dim3((unsigned)(A.G * A.team)), dim3(threads), fwd_dyn_lds(A), st, A);
   return hipGetLastError() == hipSuccess ? GNS_OK : GNS_ELAUNCH;
 }
@@ -599,11 +610,13 @@ int gns_fwd_init_device() {
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_forward_kernel<DD, HH, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, GNS_FWD_DYN_LDS_MAX) != hipSuccess) rc = GNS_ELAUNCH;
   GNS_FOR_EACH_DIMS(GNS_CASE)
 #undef GNS_CASE
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gns_forward_kernel<20, 10, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, GNS_FWD_DYN_LDS_MAX) != hipSuccess) rc = GNS_ELAUNCH;
   if (rc != GNS_OK) (void)hipGetLastError();
   return rc;
 }
 
-// Workgroups of this launch configuration that one CU holds at once (teams need every member resident: gns_api.hip)
+// Workgroups of this launch configuration that one CU holds at once (teams need every member resident: gns_api.hip).  (The SAVE_A1
+// instantiation is asked as its twin: same launch bounds, same 128-register budget, same LDS - the same answer.)
 int gns_fwd_blocks_per_cu(int d, int h, int multi, const GnsFwdArgs& A, int threads) {
   int nb = 0;
 #define GNS_CASE(DD, HH)                                                                                                              \

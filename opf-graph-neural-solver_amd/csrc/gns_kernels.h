@@ -60,6 +60,9 @@ struct GnsFwdArgs {
   unsigned char* team_ws; // team > 1: [G] 64-byte counter lines (zero at launch) | [G][GNS_TEAM_RED_FLOATS] partial sums
   const int* group_topo;  // grouped call (gns_device.h, gns_group_topo): [G] word offset of group g's blob in the set `topo`; NULL: one topology
   const int* slot_grid;   // grouped call: [G][64] input grid of each lane, -1 = dead; v / theta / losses are written in input order
+  int save_a1;            // 1: msg holds the first-layer activations of each L net (same slots, same HQ rows) instead of the hidden-vector sums,
+                          //    and nothing for the v family of a generator bus: only the split backward's saved-activation sweeps read that
+                          //    (gns_api.hip, saves_first_layer: the forward and its backward evaluate the one predicate)
 };
 
 struct GnsBwdArgs {
@@ -111,6 +114,8 @@ struct GnsBwdsArgs {
   const int* group_topo;   // grouped call: as in GnsFwdArgs (NULL: one topology)
   const int* slot_grid;
   float* igrad;            // input gradients (gns_backward_inputs): adjoints of the packed input rows, [G][gns_in_rows][64] float4; NULL: none
+  int save_a1;             // 1: the forward saved first-layer activations (GnsFwdArgs::save_a1): the sweeps of BwdsMeasured's shape run their
+                           //    saved-activation instantiations; never set for any other shape
 };
 int gns_bwds_supported(int d, int h, int multi);
 size_t gns_bwds_phys_lds(int N, int* use_plane);

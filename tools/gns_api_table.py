@@ -20,8 +20,8 @@ lib = amd.load_library()
 GPU = torch.cuda.is_available()
 NCU = torch.cuda.get_device_properties(0).multi_processor_count if GPU else 256
 NONE = ctypes.c_size_t(-1).value
-OPTIONS = ('train_mapping', 'fwd_mapping', 'gw_pack', 'team', 'bwd_variant', 'dw_mfma', 'bwds_chunks', 'bwds_mode', 'fwd_waves', 'fwd_plane')
-LAST = ('fwd_kernel', 'fwd_waves', 'fwd_plane', 'team', 'gw_pack', 'bwd_kernel', 'dw_mfma', 'bwds_mode', 'bwds_chunks', 'bwds_R', 'bwd_gw_pack')
+OPTIONS = ('train_mapping', 'fwd_mapping', 'gw_pack', 'team', 'bwd_variant', 'dw_mfma', 'bwds_chunks', 'bwds_mode', 'bwds_save', 'fwd_waves', 'fwd_plane')
+LAST = ('fwd_kernel', 'fwd_waves', 'fwd_plane', 'team', 'gw_pack', 'bwd_kernel', 'dw_mfma', 'bwds_mode', 'bwds_chunks', 'bwds_R', 'bwd_gw_pack', 'bwds_save')
 DEFAULTS = {n: amd.get_option(n) for n in OPTIONS}
 # Grids on both sides of every automatic threshold of gw_train_pack (32 groups; 16 for case300), gw_eval_pack (NCU groups; NCU / 4 for
 # a case that does not pack) and lane_team (NCU / 4, NCU / 2 and 128 groups), for the CU count of the device

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acg1_adjoint_reduce_kernel(con
   bool bad, solved;
   acn1_reduce_status(part, nchunks, np, bad, solved);
   if (bad || !solved) {
-    acn1_reduce_fill(g, N, E, Gn, bad ? __builtin_nanf("") : 0.0f, gb_out, gl_out, gg_out);
+    pf_adjoint_fill(g, N, E, Gn, bad ? __builtin_nanf("") : 0.0f, gb_out, gl_out, gg_out);
     if (gp_out) for (int h = lane; h < Gn; h += PF_THREADS) gp_out[(size_t)g * Gn + h] = bad ? __builtin_nan("") : 0.0;
     return;
   }

@@ -17,7 +17,7 @@
 //
 // The adjoint (gns_acn1_adjoint): per solved row the implicit function theorem on the grid without the line at the forward's state
 // (v, theta are inputs: Newton is not run again).  One wave per (grid, chunk of C consecutive outages) on the same LDS image, lambda
-// in the Psp / Qsp vectors; J_k from acn1_jacobian_row on the pair's Y-bus, factored by the leading factor steps of the blob's
+// in the Psp / Qsp vectors; J_k from ac_jacobian_row (gns_ac_device.h) on the pair's Y-bus, factored by the leading factor steps of the blob's
 // program, then the transposed program, as pf_adjoint_grid does.  The flow cotangents reach dl/dx by a gather with a bus per lane
 // over the stamps of its diagonal entry (no scatter, no atomics).  The wave walks its rows in order and every lane adds into the
 // addresses it alone owns of the chunk's fp64 partial in the workspace (4 N + 5 E + Gn + 1 doubles); a second kernel, a wave per

@@ -1,12 +1,15 @@
 // What the AC contingency screens share, gns_acn1.hip (single outages and their adjoint) and gns_acn2.hip (double outages).  Device:
-// a line's Y-bus stamps, the Y-bus view of a row (AcnYbus<M>: the base values but for the entries its M lines touch, with the
-// predicate "line l is out"), an entry of the Y-bus without the view's lines, the prologue of a row (acn_view: the decision that the
-// row is solved and its view, which the forward and the adjoint kernels both call), the Jacobian row on such a view, the total order
-// of the reductions, the outputs of a call with the writer of a row that is not solved, the row routine (acn_solve_row:
-// Newton-Raphson, the extremes, the flows, the worst loading), the row kernel (gns_acn_kernel<M>: acn_view, then acn_solve_row) and
-// the kernel that writes the base Y-bus of every grid.  Host: the workspace query and a screen call (acn_screen_call<Rows>) on the
-// screen's trait.  Both screens are this code at M = 1 and M = 2.  gns_acg1.hip (generator outages, alone or with a line) has a
-// kernel and an entry point of its own on a set of blobs and runs acn_view at M = 1 and acn_solve_row from here.
+// the Y-bus view of a row (AcnYbus<M>: the base values but for the entries its M lines touch, with the predicate "line l is out"),
+// an entry of the Y-bus without the view's lines, the prologue of a row (acn_view: the decision that the row is solved and its
+// view, which the forward and the adjoint kernels both call), the outputs of a call with the writer of a row that is not solved,
+// the row routine (acn_solve_row: Newton-Raphson, the extremes, the flows, the worst loading), the row kernel (gns_acn_kernel<M>:
+// acn_view, then acn_solve_row) and the kernel that writes the base Y-bus of every grid.  Host: the workspace query and a screen
+// call (acn_screen_call<Rows>) on the screen's trait.  Both screens are this code at M = 1 and M = 2.  gns_acg1.hip (generator
+// outages, alone or with a line) has a kernel and an entry point of its own on a set of blobs and runs acn_view at M = 1 and
+// acn_solve_row from here.
+// What the solver and the solved case compute too is not written here: a line's stamp, its ends and the pattern search are
+// gns_pf_device.h's; the Jacobian row on a view, a line's flows and loading, the total order of the reductions and the voltage
+// extremes are gns_ac_device.h's.  Only Newton-Raphson's loop is restated (see acn_solve_row).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,41 +18,9 @@
 #include "../../include/gns_powerflow.h"
 #include "gns_pf_common.h"
 #include "gns_pf_device.h"
+#include "gns_ac_device.h"
 
 namespace {
-// Stamp `kind` (0 ff, 1 tt, 2 ft, 3 tf) of line e as (Re, Im): pf_ybus_row's arithmetic, expression for expression
-__device__ __forceinline__ double2 acn1_stamp(const float* line, const int e, const int kind) {
-  const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
-  const double den = r * r + x * x;
-  const double ysr = r / den, ysi = -x / den;
-  double ar, ai;
-  if (kind == 0) { ar = ysr / (tau * tau); ai = (ysi + 0.5 * b) / (tau * tau); }
-  else if (kind == 1) { ar = ysr; ai = ysi + 0.5 * b; }
-  else {
-    const double c = cos(sh), s = kind == 2 ? sin(sh) : -sin(sh);   // -y_s e^{+-j shift} / tau
-    ar = -(ysr * c - ysi * s) / tau;
-    ai = -(ysr * s + ysi * c) / tau;
-  }
-  return make_double2(ar, ai);
-}
-
-// The Y-bus entry (i, k) of the blob's CSR pattern (columns ascending), -1 if it is not there
-__device__ __forceinline__ int acn1_find_entry(const int32_t* y_ptr, const int32_t* y_col, const int i, const int k) {
-  int lo = y_ptr[i], hi = y_ptr[i + 1];
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (y_col[mid] < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < y_ptr[i + 1] && y_col[lo] == k ? lo : -1;
-}
-
-// The 0-based ends of line e from its id columns (those the blob was prepared from); false unless both are buses of the grid
-__device__ __forceinline__ bool acn1_line_ends(const float* line, const int e, const int N, int& f, int& t) {
-  const float ff = line[e * 7 + 0], ft = line[e * 7 + 1];
-  f = (int)ff - 1; t = (int)ft - 1;
-  return ff == (float)(f + 1) && ft == (float)(t + 1) && f >= 0 && f < N && t >= 0 && t < N;
-}
 
 // The Y-bus of a row with M lines out: the grid's base values, but for the entries at p[0..4M-1] (ff, tt, ft, tf of the lowest
 // line, then of the next; all one entry for a line from a bus to itself), which read y[0..4M-1].  Entries two lines share (the
@@ -86,7 +57,7 @@ __device__ __forceinline__ double2 acn_entry_without(const int i, const int p, c
   for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
     const int e = st[q] >> 2;
     if (Y.out(e)) continue;
-    const double2 a = acn1_stamp(line, e, st[q] & 3);
+    const double2 a = pf_stamp(line, e, st[q] & 3);
     yr += a.x; yi += a.y;
   }
   return make_double2(yr, yi);
@@ -118,14 +89,14 @@ __device__ __forceinline__ bool acn_view(bool ok, const int32_t* __restrict__ to
   ok = ok && Y.k[0] >= 0 && Y.k[M - 1] < E;
   int f[M] = {}, t[M] = {};
 #pragma unroll
-  for (int u = 0; u < M; ++u) ok = ok && acn1_line_ends(line, Y.k[u], N, f[u], t[u]);
+  for (int u = 0; u < M; ++u) ok = ok && pf_line_ends(line, Y.k[u], N, f[u], t[u]);
   if (ok) {
 #pragma unroll
     for (int u = 0; u < M; ++u) {
       Y.p[4 * u] = y_diag[f[u]];
       Y.p[4 * u + 1] = y_diag[t[u]];
-      Y.p[4 * u + 2] = acn1_find_entry(y_ptr, y_col, f[u], t[u]);
-      Y.p[4 * u + 3] = acn1_find_entry(y_ptr, y_col, t[u], f[u]);
+      Y.p[4 * u + 2] = pf_find_entry(y_ptr, y_col, f[u], t[u]);
+      Y.p[4 * u + 3] = pf_find_entry(y_ptr, y_col, t[u], f[u]);
       ok = ok && Y.p[4 * u + 2] >= 0 && Y.p[4 * u + 3] >= 0;
     }
   }
@@ -138,50 +109,6 @@ __device__ __forceinline__ bool acn_view(bool ok, const int32_t* __restrict__ to
     Y.y[4 * u + 3] = acn_entry_without(t[u], Y.p[4 * u + 3], Y, y_diag, st_ptr, st, bus, line);
   }
   return true;
-}
-
-// Row i (not the slack) of the Jacobian into its factor slots: gns_powerflow.hip's pf_jacobian_row on the pair's Y-bus
-template <class YB>   // an AcnYbus<M>
-__device__ __forceinline__ void acn1_jacobian_row(const int i, const int slack, const int32_t* y_ptr, const int32_t* y_col,
-                                                  const int32_t* jslot, const YB& Y, const double* Vm, const double* Vr,
-                                                  const double* Vi, const double* Ir, const double* Ii, double* F) {
-  const double vri = Vr[i], vii = Vi[i];
-  for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
-    const int k = y_col[p];
-    if (k == slack) continue;
-    const double2 y = Y.at(p);
-    const double a = y.x * Vr[k] - y.y * Vi[k], b = y.x * Vi[k] + y.y * Vr[k];   // Y_ik V_k
-    const double cr = vri * a + vii * b, ci = vii * a - vri * b;                 // V_i conj(Y_ik V_k)
-    double dar = ci, dai = -cr;                                                  // dS_i / dtheta_k
-    double dmr = cr, dmi = ci;                                                   // |V_k| dS_i / d|V_k|
-    if (k == i) {
-      const double P = vri * Ir[i] + vii * Ii[i], Q = vii * Ir[i] - vri * Ii[i];
-      dar -= Q; dai += P;
-      dmr += P; dmi += Q;
-    }
-    dmr /= Vm[k]; dmi /= Vm[k];
-    const int s0 = jslot[4 * p], s1 = jslot[4 * p + 1], s2 = jslot[4 * p + 2], s3 = jslot[4 * p + 3];
-    if (s0 >= 0) F[s0] = dar;
-    if (s1 >= 0) F[s1] = dmr;
-    if (s2 >= 0) F[s2] = dai;
-    if (s3 >= 0) F[s3] = dmi;
-  }
-}
-
-// Whether v at index i comes before the best so far (at index bi): larger, or equal at a lower index; NaN comes before everything
-__device__ __forceinline__ bool acn1_before(const double v, const int i, const double best, const int bi) {
-  if (v != v) return best == best || i < bi;
-  if (best != best) return false;
-  return v > best || (v == best && i < bi);
-}
-
-// The first of the wave's (best, bi) in acn1_before's order, in every lane: a total order, so the tree's shape does not matter
-__device__ __forceinline__ void acn1_wave_first(double& best, int& bi) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(best, o);
-    const int oi = __shfl_xor(bi, o);
-    if (acn1_before(ov, oi, best, bi)) { best = ov; bi = oi; }
-  }
 }
 
 // The outputs of a call: rows [Bt * K] of the (grid, outage) pairs.  v, theta and each of the four flows may be NULL: not written.
@@ -324,7 +251,7 @@ __device__ __forceinline__ void acn_solve_row(const int32_t* __restrict__ topo, 
     for (int s = lane; s < nnzLU; s += PF_THREADS) F[s] = 0.0;
     __syncthreads();
     for (int i = lane; i < N; i += PF_THREADS)
-      if (i != slack) acn1_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
+      if (i != slack) ac_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
     __syncthreads();
 
     // the base topology's program: LU factorisation and both triangular solves
@@ -347,53 +274,34 @@ __device__ __forceinline__ void acn_solve_row(const int32_t* __restrict__ topo, 
   // every exit leaves Vr, Vi at the iterate Vm, Va hold: the state the flows and the summaries are computed from
 
   // the state and the voltage extremes, a bus per lane (the lowest of equal buses)
-  const double inf = __builtin_inf();
-  double lo = -inf, hi = -inf;             // lo holds -|V|: the smallest |V| is the first in acn1_before's order of the negated values
-  int lo_i = INT32_MAX, hi_i = INT32_MAX;
-  for (int i = lane; i < N; i += PF_THREADS) {
-    const double vm = Vm[i];
+  const AcExtremes ex = ac_voltage_extremes(N, Vm, lane, [&](const int i, const double vm) {
     if (o.v) o.v[row * N + i] = vm;
     if (o.theta) o.theta[row * N + i] = Va[i];
-    if (acn1_before(-vm, i, lo, lo_i)) { lo = -vm; lo_i = i; }
-    if (acn1_before(vm, i, hi, hi_i)) { hi = vm; hi_i = i; }
-  }
-  acn1_wave_first(lo, lo_i);
-  acn1_wave_first(hi, hi_i);
+  });
 
-  // the branch flows, a line per lane: S_f = V_f conj(Y_ff V_f + Y_ft V_t), S_t = V_t conj(Y_tf V_f + Y_tt V_t) on the line's own
-  // stamps; zeros at the outaged line(s); NaN at a line whose id columns are not buses of the grid
+  // the branch flows, a line per lane, on the line's own stamps: zeros at the outaged line(s); NaN at a line whose id columns are
+  // not buses of the grid
   const double* rt = rating ? rating + (rating_per_grid ? (size_t)g * E : 0) : nullptr;
   double best = -1.0;
   int bi = INT32_MAX;
   for (int l = lane; l < E; l += PF_THREADS) {
-    double pf = 0.0, qf = 0.0, pt = 0.0, qt = 0.0;
+    AcFlows s = {0.0, 0.0, 0.0, 0.0};
     int a, b;
-    if (!acn1_line_ends(line, l, N, a, b)) pf = qf = pt = qt = __builtin_nan("");
-    else if (!Y.out(l)) {
-      const double2 yff = acn1_stamp(line, l, 0), ytt = acn1_stamp(line, l, 1), yft = acn1_stamp(line, l, 2), ytf = acn1_stamp(line, l, 3);
-      const double far = Vr[a], fai = Vi[a], tor = Vr[b], toi = Vi[b];
-      const double ifr = (yff.x * far - yff.y * fai) + (yft.x * tor - yft.y * toi);
-      const double ifi = (yff.x * fai + yff.y * far) + (yft.x * toi + yft.y * tor);
-      const double itr = (ytf.x * far - ytf.y * fai) + (ytt.x * tor - ytt.y * toi);
-      const double iti = (ytf.x * fai + ytf.y * far) + (ytt.x * toi + ytt.y * tor);
-      pf = far * ifr + fai * ifi; qf = fai * ifr - far * ifi;
-      pt = tor * itr + toi * iti; qt = toi * itr - tor * iti;
-    }
-    if (o.p_from) o.p_from[row * E + l] = pf;
-    if (o.q_from) o.q_from[row * E + l] = qf;
-    if (o.p_to) o.p_to[row * E + l] = pt;
-    if (o.q_to) o.q_to[row * E + l] = qt;
-    const double sf = sqrt(pf * pf + qf * qf), s_t = sqrt(pt * pt + qt * qt);
-    const double s = sf != sf ? sf : s_t != s_t ? s_t : fmax(sf, s_t);   // NaN from either end
-    const double load = rt ? s / rt[l] : s;
-    if (acn1_before(load, l, best, bi)) { best = load; bi = l; }
+    if (!pf_line_ends(line, l, N, a, b)) s.pf = s.qf = s.pt = s.qt = __builtin_nan("");
+    else if (!Y.out(l)) s = ac_line_flows(line, l, a, b, Vr, Vi);
+    if (o.p_from) o.p_from[row * E + l] = s.pf;
+    if (o.q_from) o.q_from[row * E + l] = s.qf;
+    if (o.p_to) o.p_to[row * E + l] = s.pt;
+    if (o.q_to) o.q_to[row * E + l] = s.qt;
+    const double load = ac_loading(s, rt, l);
+    if (ac_before(load, l, best, bi)) { best = load; bi = l; }
   }
-  acn1_wave_first(best, bi);
+  ac_wave_first(best, bi);
 
   if (lane == 0) {
     o.worst[row] = best; o.worst_line[row] = bi;
-    o.v_min[row] = -lo; o.v_min_bus[row] = lo_i;
-    o.v_max[row] = hi; o.v_max_bus[row] = hi_i;
+    o.v_min[row] = -ex.lo; o.v_min_bus[row] = ex.lo_i;
+    o.v_max[row] = ex.hi; o.v_max_bus[row] = ex.hi_i;
     o.conv[row] = conv ? 1 : 0; o.iters[row] = it; o.mis[row] = mis;
   }
 }

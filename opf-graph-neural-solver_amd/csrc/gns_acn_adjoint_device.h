@@ -1,12 +1,14 @@
 // What the adjoints of the two AC contingency screens share, gns_acn1_adjoint (gns_acn1.hip) and gns_acn2_adjoint (gns_acn2.hip).
-// Device: the incoming gradients of a call, a row's effective flow cotangents and their gather to the buses, the layout and the
-// status of a (grid, chunk) partial, the routine of a solved row (acn_adjoint_row: the implicit function theorem on the grid without
+// Device: the incoming gradients of a call, a row's effective flow cotangents, the layout and the status of a (grid, chunk) partial, the routine of a solved row (acn_adjoint_row: the implicit function theorem on the grid without
 // the row's line or lines, templated on the Y-bus view as acn_solve_row is), the row kernel (gns_acn_adjoint_kernel<M>: acn_view,
 // the forward's prologue, then acn_adjoint_row, over a chunk's rows) and the kernel that sums a grid's partials.  Host: the workspace
 // query and an adjoint call (acn_adjoint_call<Rows>), on the screen's trait.  Both adjoints are this code at M = 1 and M = 2.
 // gns_acg1_adjoint (gns_acg1.hip: generator outages) has a row kernel, a reduce kernel and an entry point of its own on a set of
 // blobs; its rows run acn_adjoint_row from here with the generator part of a partial laid out by generator row (the Gen hook), and
 // its reduce kernel sums the buses and the lines with the pieces of the reduce kernel here.
+// The algebra of a row is gns_ac_device.h's, shared with gns_pf_adjoint and the solved case: the Jacobian row, the worst-loading
+// cotangent, the gather of the flow cotangents to the buses, dl/dvg's column sum and the cotangents of a line row; the bus of a
+// generator slot and the fill of a grid's gradient rows are gns_pf_device.h's.
 #pragma once
 #include "gns_acn1_device.h"
 
@@ -48,7 +50,8 @@ __device__ __forceinline__ bool acn1_row_nonzero(const Acn1Grad& gr, const size_
 }
 
 // The effective flow cotangents of one row: W_f = grad_p_from + j grad_q_from and W_t likewise, with what grad_worst_loading adds
-// at line w's from end (wf) or to end (wt); zero at the outaged line(s) of the row's Y-bus view.  The same in every lane.
+// at line w's from end (wf) or to end (wt); zero at the outaged line(s) of the row's Y-bus view.  The same in every lane.  at()
+// has the signature ac_flow_cot_bus and ac_worst_cot ask for (gns_ac_device.h); these cotangents do not depend on the line's ends.
 template <class YB>   // an AcnYbus<M>
 struct Acn1Cot {
   const double* gpf;   // the row's [E] incoming gradients, NULL: zero
@@ -58,7 +61,7 @@ struct Acn1Cot {
   const YB& Y;
   int w;
   double2 wf, wt;
-  __device__ __forceinline__ void at(const int l, double2& Wf, double2& Wt) const {
+  __device__ __forceinline__ void at(const int l, const int, const int, double2& Wf, double2& Wt) const {
     Wf = make_double2(0.0, 0.0); Wt = Wf;
     if (Y.out(l)) return;
     if (gpf) Wf.x = gpf[l];
@@ -68,51 +71,6 @@ struct Acn1Cot {
     if (l == w) { Wf.x += wf.x; Wf.y += wf.y; Wt.x += wt.x; Wt.y += wt.y; }
   }
 };
-
-// The four terms of the flows of line l between buses a and b at V: A = V_a conj(Y_ft V_b), D = |V_a|^2 conj(Y_ff) (S_f = D + A),
-// B = V_b conj(Y_tf V_a), C = |V_b|^2 conj(Y_tt) (S_t = C + B), on the line's own stamps
-__device__ __forceinline__ void acn1_flow_terms(const float* line, const int l, const int a, const int b, const double* Vm,
-                                                const double* Vr, const double* Vi, double2& A, double2& D, double2& B, double2& C) {
-  const double2 yff = acn1_stamp(line, l, 0), ytt = acn1_stamp(line, l, 1), yft = acn1_stamp(line, l, 2), ytf = acn1_stamp(line, l, 3);
-  const double far = Vr[a], fai = Vi[a], tor = Vr[b], toi = Vi[b];
-  const double xr = yft.x * tor - yft.y * toi, xi = yft.x * toi + yft.y * tor;   // Y_ft V_t
-  A = make_double2(far * xr + fai * xi, fai * xr - far * xi);
-  const double zr = ytf.x * far - ytf.y * fai, zi = ytf.x * fai + ytf.y * far;   // Y_tf V_f
-  B = make_double2(tor * zr + toi * zi, toi * zr - tor * zi);
-  const double mf = Vm[a] * Vm[a], mt = Vm[b] * Vm[b];
-  D = make_double2(mf * yff.x, 0.0 - mf * yff.y);
-  C = make_double2(mt * ytt.x, 0.0 - mt * ytt.y);
-}
-
-// What the flow cotangents add to dl/dtheta_i and dl/d|V_i|: a gather.  Bus i walks the stamps of its diagonal entry, where kind 0
-// names every line it is the from end of and kind 1 every line it is the to end of (a line from a bus to itself: once per end).
-//   dS_f/dtheta_f = jA = -dS_f/dtheta_t,  dS_t/dtheta_t = jB = -dS_t/dtheta_f,
-//   |V_f| dS_f/d|V_f| = 2D + A,  |V_t| dS_f/d|V_t| = A,  |V_t| dS_t/d|V_t| = 2C + B,  |V_f| dS_t/d|V_f| = B;  dl = Re(conj(W) dS)
-template <class YB>
-__device__ __forceinline__ void acn1_flow_cot_bus(const int i, const int N, const int32_t* y_diag, const int32_t* st_ptr,
-                                                  const int32_t* st, const float* line, const Acn1Cot<YB>& cot, const double* Vm,
-                                                  const double* Vr, const double* Vi, double& dth, double& dvm) {
-  const int p = y_diag[i];
-  for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
-    const int e = st[q] >> 2, kind = st[q] & 3;
-    if (kind > 1) continue;
-    double2 Wf, Wt;
-    cot.at(e, Wf, Wt);
-    if (Wf.x == 0.0 && Wf.y == 0.0 && Wt.x == 0.0 && Wt.y == 0.0) continue;
-    int a, b;
-    if (!acn1_line_ends(line, e, N, a, b)) continue;       // NaN flows: the line's own gradient row is NaN
-    double2 A, D, B, C;
-    acn1_flow_terms(line, e, a, b, Vm, Vr, Vi, A, D, B, C);
-    const double tf = Wf.y * A.x - Wf.x * A.y, tt = Wt.y * B.x - Wt.x * B.y;   // Re(conj(W_f) jA), Re(conj(W_t) jB)
-    if (kind == 0) {
-      dth += tf - tt;
-      dvm += ((Wf.x * (2.0 * D.x + A.x) + Wf.y * (2.0 * D.y + A.y)) + (Wt.x * B.x + Wt.y * B.y)) / Vm[a];
-    } else {
-      dth += tt - tf;
-      dvm += ((Wt.x * (2.0 * C.x + B.x) + Wt.y * (2.0 * C.y + B.y)) + (Wf.x * A.x + Wf.y * A.y)) / Vm[b];
-    }
-  }
-}
 
 // The generator part of a partial as the line screens lay it out: a double per generator slot (the blob's by-bus order), dl/dvg.
 // Every row of those screens runs on the one base blob, so the slots mean the same in every row, and Pg is read off the bus sums.
@@ -210,29 +168,18 @@ __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo
   // the Jacobian at that state, factored by the leading steps of the solve program (its solve operations there see a zero
   // right-hand side)
   for (int i = lane; i < N; i += PF_THREADS)
-    if (i != slack) acn1_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
+    if (i != slack) ac_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
   __syncthreads();
   pf_run_program(t_step_ptr[t_nsteps + 1], step_ptr, ops, F, lane);
   if (__ballot(pf_bad_pivot(dim, pivot, F, lane))) return false;
 
-  // the row's effective cotangents.  grad_worst_loading goes to the end of worst_line that attains the maximum (the from end on
-  // equality) as S / |S| / rating, nothing at |S| = 0; grad_v_min and grad_v_max go to the buses the forward reported.
+  // the row's effective cotangents.  grad_worst_loading goes to worst_line by ac_worst_cot's rule, unless that line is out in this
+  // row; grad_v_min and grad_v_max go to the buses the forward reported.
   Acn1Cot<YB> cot = {gr.p_from ? gr.p_from + row * E : nullptr, gr.q_from ? gr.q_from + row * E : nullptr,
                      gr.p_to ? gr.p_to + row * E : nullptr, gr.q_to ? gr.q_to + row * E : nullptr, Y, -1,
                      make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
-  const double gw = gr.worst ? gr.worst[row] : 0.0;
   const int w = wl_in[row];
-  int wa = 0, wb = 0;
-  if (gw != 0.0 && w >= 0 && w < E && !Y.out(w) && acn1_line_ends(line, w, N, wa, wb)) {
-    double2 A, D, B, Cc;
-    acn1_flow_terms(line, w, wa, wb, Vm, Vr, Vi, A, D, B, Cc);
-    const double pf = D.x + A.x, qf = D.y + A.y, pt = Cc.x + B.x, qt = Cc.y + B.y;
-    const double sf = sqrt(pf * pf + qf * qf), s_t = sqrt(pt * pt + qt * qt);
-    const double r = rt ? rt[w] : 1.0;
-    if (sf >= s_t) { if (sf > 0.0) cot.wf = make_double2(gw * (pf / sf) / r, gw * (qf / sf) / r); }
-    else cot.wt = make_double2(gw * (pt / s_t) / r, gw * (qt / s_t) / r);
-    cot.w = w;
-  }
+  if (!Y.out(w)) ac_worst_cot(cot, gr.worst ? gr.worst[row] : 0.0, w, N, E, rt, line, Vm, Vr, Vi);
   const double g_lo = gr.v_min ? gr.v_min[row] : 0.0, g_hi = gr.v_max ? gr.v_max[row] : 0.0;
   const int i_lo = lo_in[row], i_hi = hi_in[row];
 
@@ -243,7 +190,7 @@ __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo
     double dvm = gr.v ? gr.v[row * N + i] : 0.0;
     if (i == i_lo) dvm += g_lo;
     if (i == i_hi) dvm += g_hi;
-    acn1_flow_cot_bus(i, N, y_diag, st_ptr, st, line, cot, Vm, Vr, Vi, dth, dvm);
+    ac_flow_cot_bus(i, N, y_diag, st_ptr, st, line, cot, Vm, Vr, Vi, dth, dvm);
     dV[i] = dvm;
     if (th_idx[i] >= 0) rhs[th_idx[i]] = dth;
     if (vm_idx[i] >= 0) rhs[vm_idx[i]] = dvm;
@@ -267,61 +214,22 @@ __device__ __forceinline__ bool acn_adjoint_row(const int32_t* __restrict__ topo
   }
   const int n_slot = by_row ? gen_ptr[N] : Gn;       // a blob without a generator row lists one slot fewer
   for (int q = lane; q < n_slot; q += PF_THREADS) {  // a lane per generator slot, in the blob's by-bus order
-    int b = 0, hi = N;                               // the bus of slot q: gen_ptr[b] <= q < gen_ptr[b + 1]
-    while (hi - b > 1) {
-      const int mid = (b + hi) >> 1;
-      if (gen_ptr[mid] <= q) b = mid;
-      else hi = mid;
-    }
+    const int b = pf_slot_bus(gen_ptr, N, q);
     if constexpr (by_row) gen.unit(part_gen, gen_idx[q], lamP[b]);
     if (q != gen_ptr[b] || role[b] == 0) continue;   // the first generator of a PV / slack bus sets |V_b|
-    const double uc = Vr[b] / Vm[b], us = Vi[b] / Vm[b];   // e^{j theta_b}
-    double acc = 0.0;
-    for (int p = y_ptr[b]; p < y_ptr[b + 1]; ++p) {
-      const int c = y_col[p];
-      const int r = acn1_find_entry(y_ptr, y_col, c, b);   // Y_cb (the pattern is structurally symmetric)
-      if (r < 0) continue;
-      const double2 y = Y.at(r);
-      const double wr = y.x * uc - y.y * us, wi = y.x * us + y.y * uc;   // Y_cb e^{j theta_b}
-      double dr = Vr[c] * wr + Vi[c] * wi, di = Vi[c] * wr - Vr[c] * wi;  // dS_c / d|V_b| = V_c conj(Y_cb e^{j theta_b}) ...
-      if (c == b) { dr += uc * Ir[b] + us * Ii[b]; di += us * Ir[b] - uc * Ii[b]; }   // ... + e^{j theta_b} conj(I_b) at c = b
-      acc += lamP[c] * dr + lamQ[c] * di;
-    }
+    const double acc = ac_vg_column(b, Vr[b] / Vm[b], Vi[b] / Vm[b], y_ptr, y_col, Y, Vr, Vi, Ir, Ii, lamP, lamQ);
     part_gen[by_row ? gen_idx[q] : q] += dV[b] - acc;
   }
   if constexpr (by_row) gen.lost(part_gen);
   for (int e = lane; e < E; e += PF_THREADS) {      // a line per lane, over its four stamps; the row adds nothing to a line that is out
     int a, b2;
-    if (Y.out(e) || !acn1_line_ends(line, e, N, a, b2)) continue;
+    if (Y.out(e) || !pf_line_ends(line, e, N, a, b2)) continue;
     double2 Wf, Wt;
-    cot.at(e, Wf, Wt);
+    cot.at(e, a, b2, Wf, Wt);
     // Lambda_f - W_f and Lambda_t - W_t: the flow term is +Re(conj(W) S) on the line's own stamps, the mismatch term -Re(conj(Lambda) S)
-    const double lpf = lamP[a] - Wf.x, lqf = lamQ[a] - Wf.y, lpt = lamP[b2] - Wt.x, lqt = lamQ[b2] - Wt.y;
-    const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
-    const double den = r * r + x * x;
-    const double ysr = r / den, ysi = -x / den, t2 = tau * tau;
-    const double cs = cos(sh), sn = sin(sh);
-    const double mf = Vm[a] * Vm[a], mt = Vm[b2] * Vm[b2];
-    const double gffr = 0.0 - mf * lpf, gffi = mf * lqf;
-    const double gttr = 0.0 - mt * lpt, gtti = mt * lqt;
-    const double pr = Vr[a] * Vr[b2] + Vi[a] * Vi[b2], pi = Vi[a] * Vr[b2] - Vr[a] * Vi[b2];   // V_f conj(V_t)
-    const double gftr = 0.0 - (pr * lpf + pi * lqf), gfti = 0.0 - (pi * lpf - pr * lqf);
-    const double gtfr = 0.0 - (pr * lpt - pi * lqt), gtfi = 0.0 - (0.0 - pi * lpt - pr * lqt);
-    const double gmr = gffr / t2 + gttr - ((cs * gftr + sn * gfti) + (cs * gtfr - sn * gtfi)) / tau;
-    const double gmi = gffi / t2 + gtti - ((cs * gfti - sn * gftr) + (cs * gtfi + sn * gtfr)) / tau;
-    const double y2r = ysr * ysr - ysi * ysi, y2i = 2.0 * ysr * ysi;
-    const double qr = y2r * gmr + y2i * gmi, qi = y2r * gmi - y2i * gmr;   // conj(y_s^2) Gamma
-    const double a0r = ysr / t2, a0i = (ysi + 0.5 * b) / t2;
-    const double a2r = -(ysr * cs - ysi * sn) / tau, a2i = -(ysr * sn + ysi * cs) / tau;
-    const double a3r = -(ysr * cs + ysi * sn) / tau, a3i = -(ysi * cs - ysr * sn) / tau;
-    const double d_tau = 0.0 - (2.0 * (a0r * gffr + a0i * gffi) + (a2r * gftr + a2i * gfti) + (a3r * gtfr + a3i * gtfi)) / tau;
-    const double d_sh = (a2r * gfti - a2i * gftr) - (a3r * gtfi - a3i * gtfr);
+    const AcLineCot d = ac_line_row_cot(line, e, a, b2, Vm, Vr, Vi, lamP[a] - Wf.x, lamQ[a] - Wf.y, lamP[b2] - Wt.x, lamQ[b2] - Wt.y);
     double* pl = part_line + 5 * e;
-    pl[0] += 0.0 - qr;                               // r
-    pl[1] += 0.0 - qi;                               // x
-    pl[2] += 0.5 * gffi / t2 + 0.5 * gtti;           // b
-    pl[3] += d_tau;                                  // tau
-    pl[4] += d_sh;                                   // shift
+    pl[0] += d.r; pl[1] += d.x; pl[2] += d.b; pl[3] += d.tau; pl[4] += d.sh;
   }
   return true;
 }
@@ -388,15 +296,6 @@ __device__ __forceinline__ void acn1_reduce_status(const double* part, const int
   solved = __ballot(s) != 0;
 }
 
-// Every element of the grid's three gradient rows is `fill`
-__device__ __forceinline__ void acn1_reduce_fill(const int g, const int N, const int E, const int Gn, const float fill, float* gb_out,
-                                                 float* gl_out, float* gg_out) {
-  const int lane = threadIdx.x;
-  if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = fill;
-  if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = fill;
-  if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = fill;
-}
-
 // The grid's bus rows: the chunks in order, the contract (0.0 - x rather than -x: an exact zero stays +0)
 __device__ __forceinline__ void acn1_reduce_buses(const int g, const int N, const int nchunks, const int np, const double* part,
                                                   float* gb_out) {
@@ -419,7 +318,7 @@ __device__ __forceinline__ void acn1_reduce_lines(const int g, const int N, cons
   for (int e = threadIdx.x; e < E; e += PF_THREADS) {
     float* row = gl_out + ((size_t)g * E + e) * 7;
     int f, t;
-    if (!acn1_line_ends(line, e, N, f, t)) {
+    if (!pf_line_ends(line, e, N, f, t)) {
       for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
       continue;
     }
@@ -448,19 +347,14 @@ __global__ __launch_bounds__(PF_THREADS) void gns_acn1_adjoint_reduce_kernel(con
   bool bad, solved;
   acn1_reduce_status(part, nchunks, np, bad, solved);
   if (bad || !solved) {
-    acn1_reduce_fill(g, N, E, Gn, bad ? __builtin_nanf("") : 0.0f, gb_out, gl_out, gg_out);
+    pf_adjoint_fill(g, N, E, Gn, bad ? __builtin_nanf("") : 0.0f, gb_out, gl_out, gg_out);
     return;
   }
 
   if (gb_out) acn1_reduce_buses(g, N, nchunks, np, part, gb_out);
   if (gg_out)
     for (int q = lane; q < Gn; q += PF_THREADS) {
-      int b = 0, hi = N;
-      while (hi - b > 1) {
-        const int mid = (b + hi) >> 1;
-        if (gen_ptr[mid] <= q) b = mid;
-        else hi = mid;
-      }
+      const int b = pf_slot_bus(gen_ptr, N, q);
       double dp = 0.0, dvg = 0.0;
       for (int c = 0; c < nchunks; ++c) {
         dp += part[(size_t)c * np + 4 * b];

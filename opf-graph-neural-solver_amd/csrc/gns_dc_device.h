@@ -1,5 +1,6 @@
 // The device helpers of the DC power flow that its kernels (gns_dcpf.hip) and the DC contingency screen (gns_dcn1.hip) share: a line's
-// b_l and ends, Bbus from the line rows into the B' factor slots, the injection of a bus, and the fill of a grid's gradient rows.
+// b_l, Bbus from the line rows into the B' factor slots and the injection of a bus.  A line's ends, a generator slot's bus and the
+// fill of a grid's gradient rows are gns_pf_device.h's, the same for every kind of kernel.
 #pragma once
 #include "gns_pf_device.h"
 
@@ -46,22 +47,6 @@ __device__ __forceinline__ double dc_injection(const int i, const int32_t* y_dia
     p -= kind == 0 ? pfinj : 0.0 - pfinj;
   }
   return p;
-}
-
-// The 0-based ends of line e from its id columns (those the blob was prepared from); false unless both are buses of the grid
-__device__ __forceinline__ bool dc_line_ends(const float* line, const int e, const int N, int& f, int& t) {
-  const float ff = line[e * 7 + 0], ft = line[e * 7 + 1];
-  f = (int)ff - 1; t = (int)ft - 1;
-  return ff == (float)(f + 1) && ft == (float)(t + 1) && f >= 0 && f < N && t >= 0 && t < N;
-}
-
-// Every element of grid g's three gradient rows set to x
-__device__ __forceinline__ void dc_adjoint_fill(const int g, const int N, const int E, const int Gn, const float x, float* gb_out,
-                                                float* gl_out, float* gg_out) {
-  const int lane = threadIdx.x;
-  if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = x;
-  if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = x;
-  if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = x;
 }
 
 }  // namespace

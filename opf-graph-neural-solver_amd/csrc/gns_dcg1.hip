@@ -130,7 +130,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcg1_adjoint_reduce_kernel(con
   const double status = dcn1_reduce_status(part, nchunks, np);
   if (status != DCN1_PART_OK) {
     const bool nan = status == DCN1_PART_NAN;
-    dc_adjoint_fill(g, N, E, Gn, nan ? __builtin_nanf("") : 0.0f, gb_out, gl_out, gg_out);
+    pf_adjoint_fill(g, N, E, Gn, nan ? __builtin_nanf("") : 0.0f, gb_out, gl_out, gg_out);
     if (gp_out) for (int h = lane; h < Gn; h += PF_THREADS) gp_out[(size_t)g * Gn + h] = nan ? __builtin_nan("") : 0.0;
     return;
   }
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcg1_adjoint_reduce_kernel(con
   __syncthreads();
 
   for (int q = lane; q < Gn; q += PF_THREADS) {        // a lane per generator, in the blob's by-bus order
-    const int bus = dcn1_slot_bus(gen_ptr, N, q), h = gen_idx[q];
+    const int bus = pf_slot_bus(gen_ptr, N, q), h = gen_idx[q];
     double dpg = dcn1_reduce_dp(part, nchunks, np, bus), dw = 0.0;
     for (int c = 0; c < n_gen; ++c) {                  // the listed generators in list order
       const double coef = gw[c * DCG1_GEN];

@@ -116,7 +116,7 @@ __device__ __forceinline__ bool dcn1_base_case(const int32_t* topo, const float*
   if (__ballot(bad)) return false;
   for (int e = lane; e < E; e += PF_THREADS) {
     int f, t;
-    const bool ok = dc_line_ends(line, e, N, f, t);
+    const bool ok = pf_line_ends(line, e, N, f, t);
     const double b = dc_line_b(line, e);
     m.lb[e] = b;
     m.lF[e] = ok ? b * (th[f] - th[t]) + (0.0 - b * (double)line[e * 7 + 6]) : __builtin_nan("");
@@ -227,7 +227,7 @@ __device__ __forceinline__ void dcn1_reduce_buses_lines(const int32_t* topo, con
     for (int e = lane; e < E; e += PF_THREADS) {
       float* row = gl_out + ((size_t)g * E + e) * 7;
       int f, t;
-      if (!dc_line_ends(line, e, N, f, t)) {
+      if (!pf_line_ends(line, e, N, f, t)) {
         for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
         continue;
       }
@@ -244,17 +244,6 @@ __device__ __forceinline__ void dcn1_reduce_buses_lines(const int32_t* topo, con
       row[5] = (float)(0.0 - d_b * b / tau);           // tau: db/dtau = -b / tau
       row[6] = (float)(0.0 - b * sw);                  // shift
     }
-}
-
-// The bus of generator slot q of the blob's by-bus order: gen_ptr[b] <= q < gen_ptr[b + 1]
-__device__ __forceinline__ int dcn1_slot_bus(const int32_t* gen_ptr, const int N, const int q) {
-  int b = 0, hi = N;
-  while (hi - b > 1) {
-    const int mid = (b + hi) >> 1;
-    if (gen_ptr[mid] <= q) b = mid;
-    else hi = mid;
-  }
-  return b;
 }
 
 // dl/dP at bus b: the chunks' partials summed in order
@@ -278,15 +267,15 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcn1_adjoint_reduce_kernel(con
   const double* part = partials + (size_t)g * nchunks * np;
 
   const double status = dcn1_reduce_status(part, nchunks, np);
-  if (status == DCN1_PART_NAN) { dc_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
-  if (status == DCN1_PART_UNSOLVED_ZERO) { dc_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
+  if (status == DCN1_PART_NAN) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
+  if (status == DCN1_PART_UNSOLVED_ZERO) { pf_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
 
   dcn1_reduce_buses_lines(topo, lines + (size_t)g * E * 7, nchunks, part, g, gb_out, gl_out);
   if (gg_out)
     for (int q = lane; q < Gn; q += PF_THREADS) {      // a lane per generator, in the blob's by-bus order
       float* row = gg_out + ((size_t)g * Gn + gen_idx[q]) * 7;
       for (int c = 0; c < 6; ++c) row[c] = 0.0f;
-      row[6] = (float)dcn1_reduce_dp(part, nchunks, np, dcn1_slot_bus(gen_ptr, N, q));   // Pg
+      row[6] = (float)dcn1_reduce_dp(part, nchunks, np, pf_slot_bus(gen_ptr, N, q));   // Pg
     }
 }
 

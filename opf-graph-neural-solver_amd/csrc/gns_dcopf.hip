@@ -570,7 +570,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcopf_finish_kernel(const int3
   __syncthreads();
   for (int e = lane; e < E; e += PF_THREADS) {
     int f, t;
-    const bool ok = dc_line_ends(line, e, N, f, t);
+    const bool ok = pf_line_ends(line, e, N, f, t);
     const double b = m.lb[e];
     flow_out[(size_t)g * E + e] = ok ? b * (m.th[f] - m.th[t]) + (0.0 - b * (double)line[e * 7 + 6]) : __builtin_nan("");
   }

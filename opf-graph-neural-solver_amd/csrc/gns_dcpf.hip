@@ -71,7 +71,7 @@ __device__ __forceinline__ void dc_solve_grid(const int32_t* topo, const int g, 
   for (int e = lane; e < E; e += PF_THREADS) {
     int f, t;
     double flow = __builtin_nan("");
-    if (dc_line_ends(line, e, N, f, t)) {
+    if (pf_line_ends(line, e, N, f, t)) {
       const double b = dc_line_b(line, e);
       flow = b * (th[f] - th[t]) + (0.0 - b * (double)line[e * 7 + 6]);
     }
@@ -156,7 +156,7 @@ __device__ __forceinline__ void dc_adjoint_grid(const int32_t* topo, const int g
   __syncthreads();
   pf_run_program(topo[FH_NSTEPS_F1], topo + topo[FH_STEP_F1], reinterpret_cast<const int2*>(topo + topo[FH_OPS_F1]), F, lane);
   if (__ballot(pf_bad_pivot(d1, topo + topo[FH_PIVOT1], F, lane))) {
-    dc_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out);
+    pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out);
     return;
   }
 
@@ -193,12 +193,7 @@ __device__ __forceinline__ void dc_adjoint_grid(const int32_t* topo, const int g
     }
   if (gg_out)
     for (int q = lane; q < Gn; q += PF_THREADS) {      // a lane per generator, in the blob's by-bus order
-      int b = 0, hi = N;                               // the bus of generator slot q: gen_ptr[b] <= q < gen_ptr[b + 1]
-      while (hi - b > 1) {
-        const int mid = (b + hi) >> 1;
-        if (gen_ptr[mid] <= q) b = mid;
-        else hi = mid;
-      }
+      const int b = pf_slot_bus(gen_ptr, N, q);
       float* row = gg_out + ((size_t)g * Gn + gen_idx[q]) * 7;
       for (int c = 0; c < 6; ++c) row[c] = 0.0f;
       row[6] = (float)(lam[b] - gs);                   // Pg
@@ -207,7 +202,7 @@ __device__ __forceinline__ void dc_adjoint_grid(const int32_t* topo, const int g
     for (int e = lane; e < E; e += PF_THREADS) {
       float* row = gl_out + ((size_t)g * E + e) * 7;
       int f, t;
-      if (!dc_line_ends(line, e, N, f, t)) {
+      if (!pf_line_ends(line, e, N, f, t)) {
         for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
         continue;
       }
@@ -231,8 +226,8 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dc_adjoint_kernel(const int32_
                                                                     float* __restrict__ gl_out, float* __restrict__ gg_out) {
   const int g = blockIdx.x;
   const int N = topo[FH_N], E = topo[FH_E], Gn = topo[FH_GN];
-  if (dc_zero_incoming(g, N, E, gth, gfl, gsp)) { dc_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
-  if (!conv_in[g]) { dc_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
+  if (dc_zero_incoming(g, N, E, gth, gfl, gsp)) { pf_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
+  if (!conv_in[g]) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
   dc_adjoint_grid(topo, g, lines, th_in, gth, gfl, gsp, gb_out, gl_out, gg_out);
 }
 
@@ -250,10 +245,10 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dc_adjoint_set_kernel(const in
   const int64_t g64 = pf_set_grid(order);
   if (g64 < 0 || g64 >= Bt) return;
   const int g = (int)g64;
-  if (dc_zero_incoming(g, N, E, gth, gfl, gsp)) { dc_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
+  if (dc_zero_incoming(g, N, E, gth, gfl, gsp)) { pf_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out); return; }
   const int32_t* topo;
   const bool ok = pf_set_member<DcBlobKind>(set, set_words, grid_off[g], N, E, Gn, lds_bytes, INT32_MAX, topo);
-  if (!ok || !conv_in[g]) { dc_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
+  if (!ok || !conv_in[g]) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
   dc_adjoint_grid(topo, g, lines, th_in, gth, gfl, gsp, gb_out, gl_out, gg_out);
 }
 

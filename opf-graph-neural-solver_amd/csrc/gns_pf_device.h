@@ -1,6 +1,7 @@
 // What the power-flow kernels and their entry points share (gns_powerflow.hip: Newton-Raphson and its adjoint; gns_fdpf.hip:
 // fast-decoupled).  Device: one wave per grid, the Y-bus of a grid from its line stamps, I = Y V, the pivot test, the interpreter of
-// the blobs' op programs and the grid and member checks of a set kernel.  Host: the checks of a call's
+// the blobs' op programs and the grid and member checks of a set kernel; and what every kind of kernel asks of a grid, AC or DC: the
+// ends of a line, the bus of a generator slot, an entry of the CSR pattern, the fill of the three gradient rows.  Host: the checks of a call's
 // arguments, of one blob and of a set of blobs, and the launch; for the contingency screens (gns_dcn1.hip, gns_dcn2.hip, gns_acn1.hip,
 // gns_acn2.hip, gns_acg1.hip) the check of a list of lines, the chunk count of a launch and the body of their LDS queries.
 #pragma once
@@ -20,6 +21,22 @@ __device__ inline double pf_wave_max(double x) {
   return x;
 }
 
+// Stamp `kind` (0 ff, 1 tt, 2 ft, 3 tf) of line e as (Re, Im)
+__device__ __forceinline__ double2 pf_stamp(const float* line, const int e, const int kind) {
+  const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
+  const double den = r * r + x * x;
+  const double ysr = r / den, ysi = -x / den;
+  double ar, ai;
+  if (kind == 0) { ar = ysr / (tau * tau); ai = (ysi + 0.5 * b) / (tau * tau); }
+  else if (kind == 1) { ar = ysr; ai = ysi + 0.5 * b; }
+  else {
+    const double c = cos(sh), s = kind == 2 ? sin(sh) : -sin(sh);   // -y_s e^{+-j shift} / tau
+    ar = -(ysr * c - ysi * s) / tau;
+    ai = -(ysr * s + ysi * c) / tau;
+  }
+  return make_double2(ar, ai);
+}
+
 // Y-bus values of row i (makeYbus) into Y[y_ptr[i] .. y_ptr[i+1]): the line stamps of every entry, Gs + jBs on the diagonal
 __device__ __forceinline__ void pf_ybus_row(const int i, const int32_t* y_ptr, const int32_t* y_diag, const int32_t* st_ptr,
                                             const int32_t* st, const float* bus, const float* line, double2* Y) {
@@ -27,22 +44,49 @@ __device__ __forceinline__ void pf_ybus_row(const int i, const int32_t* y_ptr, c
     double yr = 0.0, yi = 0.0;
     if (p == y_diag[i]) { yr = (double)bus[i * 6 + 4]; yi = (double)bus[i * 6 + 5]; }
     for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
-      const int e = st[q] >> 2, kind = st[q] & 3;
-      const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
-      const double den = r * r + x * x;
-      const double ysr = r / den, ysi = -x / den;
-      double ar, ai;
-      if (kind == 0) { ar = ysr / (tau * tau); ai = (ysi + 0.5 * b) / (tau * tau); }
-      else if (kind == 1) { ar = ysr; ai = ysi + 0.5 * b; }
-      else {
-        const double c = cos(sh), s = kind == 2 ? sin(sh) : -sin(sh);   // -y_s e^{+-j shift} / tau
-        ar = -(ysr * c - ysi * s) / tau;
-        ai = -(ysr * s + ysi * c) / tau;
-      }
-      yr += ar; yi += ai;
+      const double2 a = pf_stamp(line, st[q] >> 2, st[q] & 3);
+      yr += a.x; yi += a.y;
     }
     Y[p] = make_double2(yr, yi);
   }
+}
+
+// The 0-based ends of line e from its id columns (those the blob was prepared from); false unless both are buses of the grid
+__device__ __forceinline__ bool pf_line_ends(const float* line, const int e, const int N, int& f, int& t) {
+  const float ff = line[e * 7 + 0], ft = line[e * 7 + 1];
+  f = (int)ff - 1; t = (int)ft - 1;
+  return ff == (float)(f + 1) && ft == (float)(t + 1) && f >= 0 && f < N && t >= 0 && t < N;
+}
+
+// The bus of generator slot q of the blob's by-bus lists: gen_ptr[b] <= q < gen_ptr[b + 1]
+__device__ __forceinline__ int pf_slot_bus(const int32_t* gen_ptr, const int N, const int q) {
+  int b = 0, hi = N;
+  while (hi - b > 1) {
+    const int mid = (b + hi) >> 1;
+    if (gen_ptr[mid] <= q) b = mid;
+    else hi = mid;
+  }
+  return b;
+}
+
+// The Y-bus entry (i, k) of the blob's CSR pattern (columns ascending), -1 if it is not there
+__device__ __forceinline__ int pf_find_entry(const int32_t* y_ptr, const int32_t* y_col, const int i, const int k) {
+  int lo = y_ptr[i], hi = y_ptr[i + 1];
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (y_col[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < y_ptr[i + 1] && y_col[lo] == k ? lo : -1;
+}
+
+// Every element of grid g's three gradient rows set to x
+__device__ __forceinline__ void pf_adjoint_fill(const int g, const int N, const int E, const int Gn, const float x, float* gb_out,
+                                                float* gl_out, float* gg_out) {
+  const int lane = threadIdx.x;
+  if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = x;
+  if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = x;
+  if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = x;
 }
 
 // I_i = sum_k Y_ik V_k over row i of the Y-bus, as (Re, Im)

@@ -2,16 +2,17 @@
 // a batch, the branch flows at both ends of every line, the bus injections, Newton-Raphson's ||F||_inf, the generators' outputs, the
 // slack's balancing power and the screens' summaries (gns_pfs_evaluate), and the gradients of a loss of those with respect to the
 // state and the grid inputs (gns_pfs_adjoint).  One wave per grid, on the Newton-Raphson blob; nothing is iterated or solved.
-// The arithmetic that other kernels also do is written again here in their expression order (the build has -ffp-contract=off, so
-// the same order gives the same bits): the Y-bus row product and the mismatch of pf_solve_grid (gns_powerflow.hip), the flows, the
-// extremes and the worst loading of acn_solve_row (gns_acn1_device.h), the line-row stamp algebra of acn_adjoint_row
-// (gns_acn_adjoint_device.h).  No atomics; every sum in a fixed order.
+// What the AC screens and Newton-Raphson's adjoint also compute is gns_ac_device.h's, the one copy they all run: a line's flows and
+// loading, the voltage extremes, the worst-loading cotangent, the gather of the line-end cotangents and the cotangent algebra of a
+// line row; the Y-bus row and a line's stamp are gns_pf_device.h's.  Only the Y-bus row product and the mismatch stand here in
+// pf_solve_grid's expression order (gns_powerflow.hip keeps its own written out; the build has -ffp-contract=off, so the same order
+// gives the same bits).  No atomics; every sum in a fixed order.
 #include <hip/hip_runtime.h>
 
 #include "../../include/gns_powerflow.h"
 #include "gns_pf_common.h"
 #include "gns_pf_device.h"
-#include "gns_acn_adjoint_device.h"
+#include "gns_ac_device.h"
 
 namespace {
 
@@ -38,17 +39,6 @@ struct PfsOut {
   double* v_max;
   int32_t* v_max_bus;
 };
-
-// The bus of generator slot q of the blob's by-bus lists: gen_ptr[b] <= q < gen_ptr[b + 1]
-__device__ __forceinline__ int pfs_slot_bus(const int32_t* gen_ptr, const int N, const int q) {
-  int b = 0, hi = N;
-  while (hi - b > 1) {
-    const int mid = (b + hi) >> 1;
-    if (gen_ptr[mid] <= q) b = mid;
-    else hi = mid;
-  }
-  return b;
-}
 
 // Grids (waves) of one workgroup of gns_pfs_kernel.  1 is what ships; other values are builds for the packing measurement alone
 // (tools/build_variant.sh with SRC=gns_pfs -DPFS_WAVES=4, profiles/solved_case/gpu_time_packing.txt): every wave still works on
@@ -103,13 +93,10 @@ __global__ __launch_bounds__(PF_THREADS * PFS_WAVES) void gns_pfs_kernel(const i
   __syncthreads();
 
   // the injections S_i = V_i conj(sum_k Y_ik V_k), Newton-Raphson's mismatch and its infinity norm (pf_solve_grid's expressions),
-  // and the voltage extremes (acn_solve_row's), a bus per lane
-  const double inf = __builtin_inf();
+  // and the voltage extremes (the screens' ac_voltage_extremes, this loop's body as its per-bus work), a bus per lane
   double nrm = 0.0;
   bool bad = false;
-  double lo = -inf, hi = -inf;           // lo holds -|V|: the smallest |V| is the first in acn1_before's order of the negated values
-  int lo_i = INT32_MAX, hi_i = INT32_MAX;
-  for (int i = lane; i < N; i += PF_THREADS) {
+  const AcExtremes ex = ac_voltage_extremes(N, Vm, lane, [&](const int i, const double) {
     double ir = 0.0, ii = 0.0;
     for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
       const int k = y_col[p];
@@ -134,52 +121,35 @@ __global__ __launch_bounds__(PF_THREADS * PFS_WAVES) void gns_pfs_kernel(const i
       nrm = fmax(nrm, fabs(fq));
       bad |= !pf_finite(fq);
     }
-    const double vm = Vm[i];
-    if (acn1_before(-vm, i, lo, lo_i)) { lo = -vm; lo_i = i; }
-    if (acn1_before(vm, i, hi, hi_i)) { hi = vm; hi_i = i; }
-  }
+  });
   nrm = pf_wave_max(nrm);
   const double mis = __ballot(bad) ? __builtin_nan("") : nrm;
-  acn1_wave_first(lo, lo_i);
-  acn1_wave_first(hi, hi_i);
   __syncthreads();
 
-  // the branch flows on the line's own stamps and the worst loading, a line per lane (acn_solve_row's expressions); NaN at a line
-  // whose id columns are not buses of the grid
+  // the branch flows on the line's own stamps and the worst loading, a line per lane (the functions acn_solve_row calls); NaN at a
+  // line whose id columns are not buses of the grid
   const double* rt = rating ? rating + (rating_per_grid ? (size_t)g * E : 0) : nullptr;
   double best = -1.0;
   int bi = INT32_MAX;
   for (int l = lane; l < E; l += PF_THREADS) {
-    double pf = 0.0, qf = 0.0, pt = 0.0, qt = 0.0;
+    const double nan = __builtin_nan("");
     int a, b;
-    if (!acn1_line_ends(line, l, N, a, b)) pf = qf = pt = qt = __builtin_nan("");
-    else {
-      const double2 yff = acn1_stamp(line, l, 0), ytt = acn1_stamp(line, l, 1), yft = acn1_stamp(line, l, 2), ytf = acn1_stamp(line, l, 3);
-      const double far = Vr[a], fai = Vi[a], tor = Vr[b], toi = Vi[b];
-      const double ifr = (yff.x * far - yff.y * fai) + (yft.x * tor - yft.y * toi);
-      const double ifi = (yff.x * fai + yff.y * far) + (yft.x * toi + yft.y * tor);
-      const double itr = (ytf.x * far - ytf.y * fai) + (ytt.x * tor - ytt.y * toi);
-      const double iti = (ytf.x * fai + ytf.y * far) + (ytt.x * toi + ytt.y * tor);
-      pf = far * ifr + fai * ifi; qf = fai * ifr - far * ifi;
-      pt = tor * itr + toi * iti; qt = toi * itr - tor * iti;
-    }
-    if (o.p_from) o.p_from[(size_t)g * E + l] = pf;
-    if (o.q_from) o.q_from[(size_t)g * E + l] = qf;
-    if (o.p_to) o.p_to[(size_t)g * E + l] = pt;
-    if (o.q_to) o.q_to[(size_t)g * E + l] = qt;
-    const double sf = sqrt(pf * pf + qf * qf), s_t = sqrt(pt * pt + qt * qt);
-    const double s = sf != sf ? sf : s_t != s_t ? s_t : fmax(sf, s_t);   // NaN from either end
-    const double load = rt ? s / rt[l] : s;
-    if (acn1_before(load, l, best, bi)) { best = load; bi = l; }
+    const AcFlows s = pf_line_ends(line, l, N, a, b) ? ac_line_flows(line, l, a, b, Vr, Vi) : AcFlows{nan, nan, nan, nan};
+    if (o.p_from) o.p_from[(size_t)g * E + l] = s.pf;
+    if (o.q_from) o.q_from[(size_t)g * E + l] = s.qf;
+    if (o.p_to) o.p_to[(size_t)g * E + l] = s.pt;
+    if (o.q_to) o.q_to[(size_t)g * E + l] = s.qt;
+    const double load = ac_loading(s, rt, l);
+    if (ac_before(load, l, best, bi)) { best = load; bi = l; }
   }
-  acn1_wave_first(best, bi);
+  ac_wave_first(best, bi);
 
   // the generators, a lane per slot of the by-bus lists: a bus's q_inj + Qd shared equally among its units (pfsoln without limit
   // ranges); Pg as given, but the first unit listed on the slack carries what the slack injects beyond the other units there
   const double ps = Pi[slack] + (double)bus[slack * 6 + 2];
   if (o.gen_p || o.gen_q)
     for (int q = lane; q < Gn; q += PF_THREADS) {
-      const int b = pfs_slot_bus(gen_ptr, N, q);
+      const int b = pf_slot_bus(gen_ptr, N, q);
       const int j = gen_idx[q];
       if (o.gen_q) o.gen_q[(size_t)g * Gn + j] = (Qi[b] + (double)bus[b * 6 + 3]) / (double)(gen_ptr[b + 1] - gen_ptr[b]);
       if (o.gen_p) {
@@ -199,8 +169,8 @@ __global__ __launch_bounds__(PF_THREADS * PFS_WAVES) void gns_pfs_kernel(const i
     o.mis[g] = mis;
     o.slack_p[g] = ps - listed;
     o.worst[g] = best; o.worst_line[g] = bi;
-    o.v_min[g] = -lo; o.v_min_bus[g] = lo_i;
-    o.v_max[g] = hi; o.v_max_bus[g] = hi_i;
+    o.v_min[g] = -ex.lo; o.v_min_bus[g] = ex.lo_i;
+    o.v_max[g] = ex.hi; o.v_max_bus[g] = ex.hi_i;
   }
 }
 
@@ -266,34 +236,6 @@ struct PfsCot {
   }
 };
 
-// What the line-end cotangents add to dl/dtheta_i and dl/d|V_i|: acn1_flow_cot_bus's gather (gns_acn_adjoint_device.h) with these W.
-// Bus i walks the stamps of its diagonal entry, kind 0 for every line it is the from end of and kind 1 for every line it is the to
-// end of; no scatter.
-__device__ __forceinline__ void pfs_flow_cot_bus(const int i, const int N, const int32_t* y_diag, const int32_t* st_ptr,
-                                                 const int32_t* st, const float* line, const PfsCot& cot, const double* Vm,
-                                                 const double* Vr, const double* Vi, double& dth, double& dvm) {
-  const int p = y_diag[i];
-  for (int q = st_ptr[p]; q < st_ptr[p + 1]; ++q) {
-    const int e = st[q] >> 2, kind = st[q] & 3;
-    if (kind > 1) continue;
-    int a, b;
-    if (!acn1_line_ends(line, e, N, a, b)) continue;       // NaN flows: the line's own gradient row is NaN
-    double2 Wf, Wt;
-    cot.at(e, a, b, Wf, Wt);
-    if (Wf.x == 0.0 && Wf.y == 0.0 && Wt.x == 0.0 && Wt.y == 0.0) continue;
-    double2 A, D, B, C;
-    acn1_flow_terms(line, e, a, b, Vm, Vr, Vi, A, D, B, C);
-    const double tf = Wf.y * A.x - Wf.x * A.y, tt = Wt.y * B.x - Wt.x * B.y;   // Re(conj(W_f) jA), Re(conj(W_t) jB)
-    if (kind == 0) {
-      dth += tf - tt;
-      dvm += ((Wf.x * (2.0 * D.x + A.x) + Wf.y * (2.0 * D.y + A.y)) + (Wt.x * B.x + Wt.y * B.y)) / Vm[a];
-    } else {
-      dth += tt - tf;
-      dvm += ((Wt.x * (2.0 * C.x + B.x) + Wt.y * (2.0 * C.y + B.y)) + (Wf.x * A.x + Wf.y * A.y)) / Vm[b];
-    }
-  }
-}
-
 __global__ __launch_bounds__(PF_THREADS) void gns_pfs_adjoint_kernel(const int32_t* __restrict__ topo, const float* __restrict__ buses,
                                                                      const float* __restrict__ lines,
                                                                      const double* __restrict__ v_in, const double* __restrict__ th_in,
@@ -314,7 +256,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pfs_adjoint_kernel(const int32
 
   // a grid whose incoming gradients are all exactly zero or NULL: zero rows, whatever its state (skipped, never multiplied by zero)
   if (!pfs_grid_nonzero(gr, g, N, E, Gn)) {
-    acn1_reduce_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out);
+    pf_adjoint_fill(g, N, E, Gn, 0.0f, gb_out, gl_out, gg_out);
     for (int i = lane; i < N; i += PF_THREADS) {
       if (gv_out) gv_out[(size_t)g * N + i] = 0.0;
       if (gth_out) gth_out[(size_t)g * N + i] = 0.0;
@@ -366,25 +308,13 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pfs_adjoint_kernel(const int32
   }
   __syncthreads();
 
-  // the line-end cotangents.  grad_worst_loading goes to the end of worst_line that attains the maximum (the from end on equality)
-  // as S / |S| / rating, nothing at |S| = 0; grad_v_min and grad_v_max go to the buses the forward reported (acn_adjoint_row's rule).
+  // the line-end cotangents.  grad_worst_loading goes to worst_line by ac_worst_cot's rule; grad_v_min and grad_v_max go to the
+  // buses the forward reported.
   const double* rt = rating ? rating + (rating_per_grid ? (size_t)g * E : 0) : nullptr;
   PfsCot cot = {gr.p_from ? gr.p_from + (size_t)g * E : nullptr, gr.q_from ? gr.q_from + (size_t)g * E : nullptr,
                 gr.p_to ? gr.p_to + (size_t)g * E : nullptr, gr.q_to ? gr.q_to + (size_t)g * E : nullptr, LamR, LamI, -1,
                 make_double2(0.0, 0.0), make_double2(0.0, 0.0)};
-  const double gw = gr.worst ? gr.worst[g] : 0.0;
-  const int w = wl_in[g];
-  int wa = 0, wb = 0;
-  if (gw != 0.0 && w >= 0 && w < E && acn1_line_ends(line, w, N, wa, wb)) {
-    double2 A, D, B, Cc;
-    acn1_flow_terms(line, w, wa, wb, Vm, Vr, Vi, A, D, B, Cc);
-    const double pf = D.x + A.x, qf = D.y + A.y, pt = Cc.x + B.x, qt = Cc.y + B.y;
-    const double sf = sqrt(pf * pf + qf * qf), s_t = sqrt(pt * pt + qt * qt);
-    const double r = rt ? rt[w] : 1.0;
-    if (sf >= s_t) { if (sf > 0.0) cot.wf = make_double2(gw * (pf / sf) / r, gw * (qf / sf) / r); }
-    else cot.wt = make_double2(gw * (pt / s_t) / r, gw * (qt / s_t) / r);
-    cot.w = w;
-  }
+  ac_worst_cot(cot, gr.worst ? gr.worst[g] : 0.0, wl_in[g], N, E, rt, line, Vm, Vr, Vi);
   const double g_lo = gr.v_min ? gr.v_min[g] : 0.0, g_hi = gr.v_max ? gr.v_max[g] : 0.0;
   const int i_lo = lo_in[g], i_hi = hi_in[g];
 
@@ -395,7 +325,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pfs_adjoint_kernel(const int32
       double dvm = 2.0 * Vm[i] * ((double)bus[i * 6 + 4] * LamR[i] - (double)bus[i * 6 + 5] * LamI[i]);
       if (i == i_lo) dvm += g_lo;
       if (i == i_hi) dvm += g_hi;
-      pfs_flow_cot_bus(i, N, y_diag, st_ptr, st, line, cot, Vm, Vr, Vi, dth, dvm);
+      ac_flow_cot_bus(i, N, y_diag, st_ptr, st, line, cot, Vm, Vr, Vi, dth, dvm);
       if (gth_out) gth_out[(size_t)g * N + i] = dth;
       if (gv_out) gv_out[(size_t)g * N + i] = dvm;
     }
@@ -404,7 +334,7 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pfs_adjoint_kernel(const int32
   // Pg leaves slack_p, and every one but the first leaves the first unit's gen_p
   if (gg_out)
     for (int q = lane; q < Gn; q += PF_THREADS) {
-      const int b = pfs_slot_bus(gen_ptr, N, q);
+      const int b = pf_slot_bus(gen_ptr, N, q);
       const int j = gen_idx[q];
       double gp = ggp ? ggp[j] : 0.0;
       if (b == slack) gp = q == gen_ptr[slack] ? 0.0 - gsp : gp - gsp - gfirst;
@@ -413,44 +343,21 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pfs_adjoint_kernel(const int32
       row[6] = (float)gp;                              // Pg
     }
 
-  // the lines' r, x, b, tau, shift, a line per lane over its four stamps: acn_adjoint_row's algebra with +W where the mismatch
+  // the lines' r, x, b, tau, shift, a line per lane over its four stamps: ac_line_row_cot with -W where the mismatch
   // term has -Lambda; a line whose id columns are not buses of the grid gets a NaN row
   if (gl_out)
     for (int e = lane; e < E; e += PF_THREADS) {
       float* row = gl_out + ((size_t)g * E + e) * 7;
       int a, b2;
-      if (!acn1_line_ends(line, e, N, a, b2)) {
+      if (!pf_line_ends(line, e, N, a, b2)) {
         for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
         continue;
       }
       double2 Wf, Wt;
       cot.at(e, a, b2, Wf, Wt);
-      const double lpf = 0.0 - Wf.x, lqf = 0.0 - Wf.y, lpt = 0.0 - Wt.x, lqt = 0.0 - Wt.y;
-      const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
-      const double den = r * r + x * x;
-      const double ysr = r / den, ysi = -x / den, t2 = tau * tau;
-      const double cs = cos(sh), sn = sin(sh);
-      const double mf = Vm[a] * Vm[a], mt = Vm[b2] * Vm[b2];
-      const double gffr = 0.0 - mf * lpf, gffi = mf * lqf;
-      const double gttr = 0.0 - mt * lpt, gtti = mt * lqt;
-      const double pr = Vr[a] * Vr[b2] + Vi[a] * Vi[b2], pi = Vi[a] * Vr[b2] - Vr[a] * Vi[b2];   // V_f conj(V_t)
-      const double gftr = 0.0 - (pr * lpf + pi * lqf), gfti = 0.0 - (pi * lpf - pr * lqf);
-      const double gtfr = 0.0 - (pr * lpt - pi * lqt), gtfi = 0.0 - (0.0 - pi * lpt - pr * lqt);
-      const double gmr = gffr / t2 + gttr - ((cs * gftr + sn * gfti) + (cs * gtfr - sn * gtfi)) / tau;
-      const double gmi = gffi / t2 + gtti - ((cs * gfti - sn * gftr) + (cs * gtfi + sn * gtfr)) / tau;
-      const double y2r = ysr * ysr - ysi * ysi, y2i = 2.0 * ysr * ysi;
-      const double qr = y2r * gmr + y2i * gmi, qi = y2r * gmi - y2i * gmr;   // conj(y_s^2) Gamma
-      const double a0r = ysr / t2, a0i = (ysi + 0.5 * b) / t2;
-      const double a2r = -(ysr * cs - ysi * sn) / tau, a2i = -(ysr * sn + ysi * cs) / tau;
-      const double a3r = -(ysr * cs + ysi * sn) / tau, a3i = -(ysi * cs - ysr * sn) / tau;
-      const double d_tau = 0.0 - (2.0 * (a0r * gffr + a0i * gffi) + (a2r * gftr + a2i * gfti) + (a3r * gtfr + a3i * gtfi)) / tau;
-      const double d_sh = (a2r * gfti - a2i * gftr) - (a3r * gtfi - a3i * gtfr);
+      const AcLineCot d = ac_line_row_cot(line, e, a, b2, Vm, Vr, Vi, 0.0 - Wf.x, 0.0 - Wf.y, 0.0 - Wt.x, 0.0 - Wt.y);
       row[0] = 0.0f; row[1] = 0.0f;
-      row[2] = (float)(0.0 - qr);                                  // r
-      row[3] = (float)(0.0 - qi);                                  // x
-      row[4] = (float)(0.5 * gffi / t2 + 0.5 * gtti);              // b
-      row[5] = (float)d_tau;                                       // tau
-      row[6] = (float)d_sh;                                        // shift
+      row[2] = (float)d.r; row[3] = (float)d.x; row[4] = (float)d.b; row[5] = (float)d.tau; row[6] = (float)d.sh;
     }
 }
 

@@ -6,35 +6,9 @@
 #include "../../include/gns_powerflow.h"
 #include "gns_pf_common.h"
 #include "gns_pf_device.h"
+#include "gns_ac_device.h"
 
 namespace {
-
-// Row i (not the slack) of the Jacobian (MATPOWER dSbus_dV, polar) into its factor slots, at V = Vr + j Vi with I = Ir + j Ii = Y V
-__device__ __forceinline__ void pf_jacobian_row(const int i, const int slack, const int32_t* y_ptr, const int32_t* y_col,
-                                                const int32_t* jslot, const double2* Y, const double* Vm, const double* Vr,
-                                                const double* Vi, const double* Ir, const double* Ii, double* F) {
-  const double vri = Vr[i], vii = Vi[i];
-  for (int p = y_ptr[i]; p < y_ptr[i + 1]; ++p) {
-    const int k = y_col[p];
-    if (k == slack) continue;
-    const double2 y = Y[p];
-    const double a = y.x * Vr[k] - y.y * Vi[k], b = y.x * Vi[k] + y.y * Vr[k];   // Y_ik V_k
-    const double cr = vri * a + vii * b, ci = vii * a - vri * b;                 // V_i conj(Y_ik V_k)
-    double dar = ci, dai = -cr;                                                  // dS_i / dtheta_k
-    double dmr = cr, dmi = ci;                                                   // |V_k| dS_i / d|V_k|
-    if (k == i) {
-      const double P = vri * Ir[i] + vii * Ii[i], Q = vii * Ir[i] - vri * Ii[i];
-      dar -= Q; dai += P;
-      dmr += P; dmi += Q;
-    }
-    dmr /= Vm[k]; dmi /= Vm[k];
-    const int s0 = jslot[4 * p], s1 = jslot[4 * p + 1], s2 = jslot[4 * p + 2], s3 = jslot[4 * p + 3];
-    if (s0 >= 0) F[s0] = dar;
-    if (s1 >= 0) F[s1] = dmr;
-    if (s2 >= 0) F[s2] = dai;
-    if (s3 >= 0) F[s3] = dmi;
-  }
-}
 
 // The solve of grid g on the blob at topo: the body of both kernels below.  Its Y-bus values go to ybus_ws + g * (the blob's
 // nnz(Y)), or with SET to ybus_ws + g * ystride (the largest nnz(Y) of a set).
@@ -141,7 +115,7 @@ __device__ __forceinline__ void pf_solve_grid(const int32_t* topo, const int g, 
     for (int s = lane; s < nnzLU; s += PF_THREADS) F[s] = 0.0;
     __syncthreads();
     for (int i = lane; i < N; i += PF_THREADS)
-      if (i != slack) pf_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
+      if (i != slack) ac_jacobian_row(i, slack, y_ptr, y_col, jslot, AcPlainYbus{Y}, Vm, Vr, Vi, Ir, Ii, F);
     __syncthreads();
 
     // LU factorisation and both triangular solves: F[dst] -= F[a] F[b] or F[dst] /= F[a], independent within a step
@@ -216,15 +190,6 @@ __global__ __launch_bounds__(PF_THREADS) void gns_pf_set_kernel(const int32_t* _
 // ---- the adjoint (gns_pf_adjoint): gradients of a loss of (v, theta) at a converged solution, by the implicit function theorem:
 // J^T lambda = dl/dx at the solution, dl/dp = -lambda^T dF/dp (include/gns_powerflow.h, "Gradients").
 
-// Every element of grid g's three gradient rows set to x
-__device__ __forceinline__ void pf_adjoint_fill(const int g, const int N, const int E, const int Gn, const float x, float* gb_out,
-                                                float* gl_out, float* gg_out) {
-  const int lane = threadIdx.x;
-  if (gb_out) for (int q = lane; q < N * 6; q += PF_THREADS) gb_out[(size_t)g * N * 6 + q] = x;
-  if (gl_out) for (int q = lane; q < E * 7; q += PF_THREADS) gl_out[(size_t)g * E * 7 + q] = x;
-  if (gg_out) for (int q = lane; q < Gn * 7; q += PF_THREADS) gg_out[(size_t)g * Gn * 7 + q] = x;
-}
-
 // Whether grid g's incoming gradient rows are all exactly zero (a NULL row counts as zero)
 __device__ __forceinline__ bool pf_zero_incoming(const int g, const int N, const double* gv, const double* gth) {
   bool nz = false;
@@ -233,17 +198,6 @@ __device__ __forceinline__ bool pf_zero_incoming(const int g, const int N, const
     if (gth) nz |= gth[(size_t)g * N + i] != 0.0;
   }
   return __ballot(nz) == 0;
-}
-
-// The Y-bus entry (i, k) of the blob's CSR pattern (columns ascending), -1 if it is not there
-__device__ __forceinline__ int pf_find_entry(const int32_t* y_ptr, const int32_t* y_col, const int i, const int k) {
-  int lo = y_ptr[i], hi = y_ptr[i + 1];
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (y_col[mid] < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < y_ptr[i + 1] && y_col[lo] == k ? lo : -1;
 }
 
 // The adjoint of grid g (converged, with a non-zero incoming gradient) on the blob at topo: the body of both adjoint kernels.
@@ -305,7 +259,7 @@ __device__ __forceinline__ void pf_adjoint_grid(const int32_t* topo, const int g
 
   // J at the solution, factored by the leading steps of the solve program (its solve operations there see a zero right-hand side)
   for (int i = lane; i < N; i += PF_THREADS)
-    if (i != slack) pf_jacobian_row(i, slack, y_ptr, y_col, jslot, Y, Vm, Vr, Vi, Ir, Ii, F);
+    if (i != slack) ac_jacobian_row(i, slack, y_ptr, y_col, jslot, AcPlainYbus{Y}, Vm, Vr, Vi, Ir, Ii, F);
   __syncthreads();
   pf_run_program(t_step_ptr[t_nsteps + 1], step_ptr, ops, F, lane);   // the steps that hold the factorisation
   if (__ballot(pf_bad_pivot(dim, pivot, F, lane))) { pf_adjoint_fill(g, N, E, Gn, __builtin_nanf(""), gb_out, gl_out, gg_out); return; }
@@ -338,27 +292,11 @@ __device__ __forceinline__ void pf_adjoint_grid(const int32_t* topo, const int g
     }
   if (gg_out)
     for (int q = lane; q < Gn; q += PF_THREADS) {      // a lane per generator, in the blob's by-bus order
-      int b = 0, hi = N;                               // the bus of generator slot q: gen_ptr[b] <= q < gen_ptr[b + 1]
-      while (hi - b > 1) {
-        const int mid = (b + hi) >> 1;
-        if (gen_ptr[mid] <= q) b = mid;
-        else hi = mid;
-      }
+      const int b = pf_slot_bus(gen_ptr, N, q);
       const int j = gen_idx[q];
       double gvg = 0.0;
       if (q == gen_ptr[b] && role[b] != 0) {           // the first generator of a PV / slack bus sets |V_b|
-        const double uc = cos(Va[b]), us = sin(Va[b]);   // e^{j theta_b}
-        double acc = 0.0;
-        for (int p = y_ptr[b]; p < y_ptr[b + 1]; ++p) {
-          const int k = y_col[p];
-          const int r = pf_find_entry(y_ptr, y_col, k, b);   // Y_kb (the pattern is structurally symmetric)
-          if (r < 0) continue;
-          const double2 y = Y[r];
-          const double wr = y.x * uc - y.y * us, wi = y.x * us + y.y * uc;   // Y_kb e^{j theta_b}
-          double dr = Vr[k] * wr + Vi[k] * wi, di = Vi[k] * wr - Vr[k] * wi;  // dS_k / d|V_b| = V_k conj(Y_kb e^{j theta_b}) ...
-          if (k == b) { dr += uc * Ir[b] + us * Ii[b]; di += us * Ir[b] - uc * Ii[b]; }   // ... + e^{j theta_b} conj(I_b) at k = b
-          acc += lamP[k] * dr + lamQ[k] * di;
-        }
+        const double acc = ac_vg_column(b, cos(Va[b]), sin(Va[b]), y_ptr, y_col, AcPlainYbus{Y}, Vr, Vi, Ir, Ii, lamP, lamQ);
         gvg = (gv ? gv[(size_t)g * N + b] : 0.0) - acc;
       }
       float* row = gg_out + ((size_t)g * Gn + j) * 7;
@@ -370,40 +308,14 @@ __device__ __forceinline__ void pf_adjoint_grid(const int32_t* topo, const int g
   if (gl_out)
     for (int e = lane; e < E; e += PF_THREADS) {      // a lane per line, over its four stamps
       float* row = gl_out + ((size_t)g * E + e) * 7;
-      const float ff = line[e * 7 + 0], ft = line[e * 7 + 1];   // the id columns the blob was prepared from (1-based)
-      const int f = (int)ff - 1, t = (int)ft - 1;
-      if (!(ff == (float)(f + 1) && ft == (float)(t + 1) && f >= 0 && f < N && t >= 0 && t < N)) {
+      int f, t;                                        // from the id columns the blob was prepared from (1-based)
+      if (!pf_line_ends(line, e, N, f, t)) {
         for (int c = 0; c < 7; ++c) row[c] = __builtin_nanf("");
         continue;
       }
-      const double r = line[e * 7 + 2], x = line[e * 7 + 3], b = line[e * 7 + 4], tau = line[e * 7 + 5], sh = line[e * 7 + 6];
-      const double den = r * r + x * x;
-      const double ysr = r / den, ysi = -x / den, t2 = tau * tau;
-      const double cs = cos(sh), sn = sin(sh);
-      // G of the four entries: V_i conj(V_k) conj(Lambda_i), negated
-      const double mf = Vm[f] * Vm[f], mt = Vm[t] * Vm[t];
-      const double gffr = 0.0 - mf * lamP[f], gffi = mf * lamQ[f];
-      const double gttr = 0.0 - mt * lamP[t], gtti = mt * lamQ[t];
-      const double pr = Vr[f] * Vr[t] + Vi[f] * Vi[t], pi = Vi[f] * Vr[t] - Vr[f] * Vi[t];   // V_f conj(V_t)
-      const double gftr = 0.0 - (pr * lamP[f] + pi * lamQ[f]), gfti = 0.0 - (pi * lamP[f] - pr * lamQ[f]);
-      const double gtfr = 0.0 - (pr * lamP[t] - pi * lamQ[t]), gtfi = 0.0 - (0.0 - pi * lamP[t] - pr * lamQ[t]);
-      // through y_s: Gamma = G_ff / tau^2 + G_tt - e^{-j shift} G_ft / tau - e^{j shift} G_tf / tau; dy_s/dr = -y_s^2, dy_s/dx = -j y_s^2
-      const double gmr = gffr / t2 + gttr - ((cs * gftr + sn * gfti) + (cs * gtfr - sn * gtfi)) / tau;
-      const double gmi = gffi / t2 + gtti - ((cs * gfti - sn * gftr) + (cs * gtfi + sn * gtfr)) / tau;
-      const double y2r = ysr * ysr - ysi * ysi, y2i = 2.0 * ysr * ysi;
-      const double qr = y2r * gmr + y2i * gmi, qi = y2r * gmi - y2i * gmr;   // conj(y_s^2) Gamma
-      // the stamps A_ff = (y_s + jb/2) / tau^2, A_ft = -y_s e^{j shift} / tau, A_tf = -y_s e^{-j shift} / tau
-      const double a0r = ysr / t2, a0i = (ysi + 0.5 * b) / t2;
-      const double a2r = -(ysr * cs - ysi * sn) / tau, a2i = -(ysr * sn + ysi * cs) / tau;
-      const double a3r = -(ysr * cs + ysi * sn) / tau, a3i = -(ysi * cs - ysr * sn) / tau;
-      const double d_tau = 0.0 - (2.0 * (a0r * gffr + a0i * gffi) + (a2r * gftr + a2i * gfti) + (a3r * gtfr + a3i * gtfi)) / tau;
-      const double d_sh = (a2r * gfti - a2i * gftr) - (a3r * gtfi - a3i * gtfr);
+      const AcLineCot d = ac_line_row_cot(line, e, f, t, Vm, Vr, Vi, lamP[f], lamQ[f], lamP[t], lamQ[t]);
       row[0] = 0.0f; row[1] = 0.0f;
-      row[2] = (float)(0.0 - qr);                                  // r
-      row[3] = (float)(0.0 - qi);                                  // x
-      row[4] = (float)(0.5 * gffi / t2 + 0.5 * gtti);              // b: c = j/2 on Y_ff / tau^2 and Y_tt
-      row[5] = (float)d_tau;                                       // tau
-      row[6] = (float)d_sh;                                        // shift
+      row[2] = (float)d.r; row[3] = (float)d.x; row[4] = (float)d.b; row[5] = (float)d.tau; row[6] = (float)d.sh;
     }
 }
 

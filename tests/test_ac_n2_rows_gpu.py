@@ -237,7 +237,7 @@ def test_a_non_finite_mismatch_stops_the_rows_of_its_grid():
 
 def test_id_columns_that_name_no_bus_or_no_entry():
     """The solve reads the blob's stamps, never the id columns, so only the tampered line's own flows and the rows of the pairs that
-    hold it change.  ``acn1_line_ends`` and ``acn1_find_entry`` run once per line of the pair: the list holds the tampered line as
+    hold it change.  ``pf_line_ends`` and ``pf_find_entry`` run once per line of the pair: the list holds the tampered line as
     the lower line of a pair and as the higher."""
     s = _setup('random40_parallel_selfloop', 'reference')
     tp = s.tp

@@ -1,5 +1,6 @@
 """Bit-for-bit A/B between two builds of the project on one GPU: the three DC screens (``dc``), the two AC screens (``ac``) or the
-GNS training step (``gns``: forward, parameter gradient, input gradients).
+GNS training step (``gns``: forward, parameter gradient, input gradients), or the other consumers of the AC line and bus arithmetic
+(``pf``: Newton-Raphson, the solved case, the AC generator screen).
 
 dump     imports the package (and with it the library) from ROOT, runs the fixed set of seeded calls of SET, each differentiable,
          and saves every returned tensor and every gradient to OUT.
@@ -24,6 +25,13 @@ orders, pairs that share a bus and, where the topology has them, parallel lines.
 with zero and with non-zero incoming gradients into it.  case118 x 2 grids with 40 outages and 40 pairs (parallel lines among
 them), where the lane loops make a second trip (N = 118 > 64).
 
+The ``pf`` calls: ``newton_raphson`` forward and backward (a loss over v and theta) on the same case14 batch, cold and warm-started,
+on case118 x 2 and on one mixed-topology batch (case14 x 6 over two outages); ``solved_case`` forward and backward at that solution
+with no rating, ``[E]`` and ``[Bt,E]``, away from the solution, with two units on the slack and on case118, each under a loss over the
+flows alone, the injections and generators alone, the summaries alone and all, the state among the inputs that require grad; through
+the C entry points one batch with a line whose id columns are not buses (NaN flows, a NaN gradient row), which the Python call
+refuses; and ``ac_generator_contingency_screen_differentiable`` on its default list with the ``ac`` set's modes and losses.
+
 The ``gns`` calls (``GNS.forward`` in training mode and ``.backward()`` under a loss with every upstream gradient non-zero; each
 saves v, theta, total, last and the flat parameter gradient, and the three input gradients where they are asked for) are the smallest
 that reach each branch of the backward kernels' line-physics adjoint (gns_phys_device.h) and per-bus gather, always from the
@@ -41,8 +49,8 @@ inputs and goldens of the tree the TOOL lies in, so both builds see the same num
             fail that vote (case30 is one wave per grid; the dead lanes of a wave vote too and are not counted).
   grouped   one mixed-topology call (``topology_check = 'group'``): case14 x 150 over two outages
 
-usage: python tools/gpu_ab_dc_screens.py dump dc|ac|gns ROOT OUT
-       python tools/gpu_ab_dc_screens.py compare dc|ac|gns ROOT_A ROOT_B > profiles/.../ab_bitwise.txt"""
+usage: python tools/gpu_ab_dc_screens.py dump dc|ac|pf|gns ROOT OUT
+       python tools/gpu_ab_dc_screens.py compare dc|ac|pf|gns ROOT_A ROOT_B > profiles/.../ab_bitwise.txt"""
 import os
 import subprocess
 import sys
@@ -137,39 +145,136 @@ def dump(which, root, out_path):
         run('case300 g1 60 lines', g1, grids, slack, contingencies=rows, pickup='pmax')
         run('case300 n1 40 outages', n1, grids, slack, outages=rng.choice(E, 40, replace=False).tolist())
 
-    def ac_calls():
-        GROUPS = {'state': ('v', 'theta'), 'flow': ('p_from', 'q_from', 'p_to', 'q_to'), 'summary': ('worst_loading', 'v_min', 'v_max')}
-        FORWARD = ('v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to', 'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max',
-                   'v_max_bus', 'converged', 'iterations', 'mismatch', 'islanding')
-        ALL_MODES = ((True, True), (False, False), (True, False), (False, True))
+    GROUPS = {'state': ('v', 'theta'), 'flow': ('p_from', 'q_from', 'p_to', 'q_to'), 'summary': ('worst_loading', 'v_min', 'v_max')}
+    FORWARD = ('v', 'theta', 'p_from', 'q_from', 'p_to', 'q_to', 'worst_loading', 'worst_line', 'v_min', 'v_min_bus', 'v_max',
+               'v_max_bus', 'converged', 'iterations', 'mismatch', 'islanding')
+    ALL_MODES = ((True, True), (False, False), (True, False), (False, True))
 
-        def run(name, call, grids, slack, modes=ALL_MODES, also_grid=None, **kw):
-            """One configuration: per (``flows``, ``states``) and per loss a fresh forward and backward.  The loss weighs the
-            converged rows; with ``also_grid`` every row of that grid too (non-zero gradients into rows without a solution)."""
-            for flows, states in modes:
-                kinds = ['summary'] + (['state'] if states else []) + (['flow'] if flows else []) + (['all'] if flows and states else [])
-                for n_kind, kind in enumerate(kinds):
-                    bu, li, ge = (t.clone().requires_grad_(True) for t in grids)
-                    res = call(bu, li, ge, slack_bus=slack, flows=flows, states=states, **kw)
-                    rows = res.converged.clone()
-                    if also_grid is not None:
-                        rows[also_grid] = True
-                    loss = 0.0
-                    for group, fields in GROUPS.items():
-                        if kind in (group, 'all'):
-                            for seed, field in enumerate(fields):
-                                x = getattr(res, field)[rows]
-                                loss = loss + (x * weights(x.shape, 31 + seed)).sum()
-                    loss.backward()
-                    tag = f'{name} flows={int(flows)} states={int(states)} loss={kind}'
-                    if n_kind == 0:
-                        for field in FORWARD:
-                            if getattr(res, field) is not None:
-                                out[f'{tag} {field}'] = getattr(res, field).detach().cpu()
-                        for field in ('v', 'theta', 'converged', 'iterations'):
-                            out[f'{tag} base.{field}'] = getattr(res.base, field).detach().cpu()
-                    for label, t in (('grad_buses', bu), ('grad_lines', li), ('grad_generators', ge)):
-                        out[f'{tag} {label}'] = t.grad.detach().cpu()
+    def ac_run(name, call, grids, slack, modes=ALL_MODES, also_grid=None, **kw):
+        """One configuration: per (``flows``, ``states``) and per loss a fresh forward and backward.  The loss weighs the
+        converged rows; with ``also_grid`` every row of that grid too (non-zero gradients into rows without a solution)."""
+        for flows, states in modes:
+            kinds = ['summary'] + (['state'] if states else []) + (['flow'] if flows else []) + (['all'] if flows and states else [])
+            for n_kind, kind in enumerate(kinds):
+                bu, li, ge = (t.clone().requires_grad_(True) for t in grids)
+                res = call(bu, li, ge, slack_bus=slack, flows=flows, states=states, **kw)
+                rows = res.converged.clone()
+                if also_grid is not None:
+                    rows[also_grid] = True
+                loss = 0.0
+                for group, fields in GROUPS.items():
+                    if kind in (group, 'all'):
+                        for seed, field in enumerate(fields):
+                            x = getattr(res, field)[rows]
+                            loss = loss + (x * weights(x.shape, 31 + seed)).sum()
+                loss.backward()
+                tag = f'{name} flows={int(flows)} states={int(states)} loss={kind}'
+                if n_kind == 0:
+                    for field in FORWARD:
+                        if getattr(res, field) is not None:
+                            out[f'{tag} {field}'] = getattr(res, field).detach().cpu()
+                    for field in ('v', 'theta', 'converged', 'iterations'):
+                        out[f'{tag} base.{field}'] = getattr(res.base, field).detach().cpu()
+                for label, t in (('grad_buses', bu), ('grad_lines', li), ('grad_generators', ge)):
+                    out[f'{tag} {label}'] = t.grad.detach().cpu()
+
+    def pf_calls():
+        import ctypes
+
+        import opf_graph_neural_solver_amd as amd
+        from opf_graph_neural_solver_amd._lib import PfConfig
+
+        def nr(name, grids, slack, **kw):
+            """``newton_raphson`` forward and backward under a loss over v and theta of the converged grids"""
+            bu, li, ge = (t.clone().requires_grad_(True) for t in grids)
+            res = powerflow.newton_raphson(bu, li, ge, slack_bus=slack, **kw)
+            ok = res.converged
+            ((res.v[ok] * weights(res.v[ok].shape, 51)).sum() + (res.theta[ok] * weights(res.theta[ok].shape, 52)).sum()).backward()
+            for field in powerflow.PowerFlowResult._fields:
+                out[f'{name} {field}'] = getattr(res, field).detach().cpu()
+            for label, t in (('grad_buses', bu), ('grad_lines', li), ('grad_generators', ge)):
+                out[f'{name} {label}'] = t.grad.detach().cpu()
+            return res
+
+        SC_GROUPS = {'flow': ('p_from', 'q_from', 'p_to', 'q_to'), 'injection': ('p_inj', 'q_inj', 'gen_p', 'gen_q', 'slack_p'),
+                     'summary': ('worst_loading', 'v_min', 'v_max')}
+
+        def sc(name, grids, slack, v, theta, rating=None):
+            """``solved_case`` at (v, theta): per loss a fresh forward and backward, the state among the inputs that require grad"""
+            for n_kind, kind in enumerate(('flow', 'injection', 'summary', 'all')):
+                bu, li, ge, vv, th = (t.clone().requires_grad_(True) for t in (*grids, v, theta))
+                res = powerflow.solved_case(bu, li, ge, vv, th, slack_bus=slack, rating=rating)
+                loss = 0.0
+                for group, fields in SC_GROUPS.items():
+                    if kind in (group, 'all'):
+                        for seed, field in enumerate(fields):
+                            x = getattr(res, field)
+                            loss = loss + (x * weights(x.shape, 61 + seed)).sum()
+                loss.backward()
+                tag = f'{name} loss={kind}'
+                if n_kind == 0:
+                    for field in powerflow.SolvedCase._fields:
+                        out[f'{tag} {field}'] = getattr(res, field).detach().cpu()
+                for label, t in (('grad_buses', bu), ('grad_lines', li), ('grad_generators', ge), ('grad_v', vv), ('grad_theta', th)):
+                    out[f'{tag} {label}'] = t.grad.detach().cpu()
+
+        def sc_raw(name, grids, slack, v, theta, clean_lines):
+            """``gns_pfs_evaluate`` and ``gns_pfs_adjoint`` through the C entry points on the blob of ``clean_lines``' topology, for
+            lines the Python call refuses in its analysis (id columns that are not buses); every incoming gradient non-zero"""
+            lib = amd.load_library()
+            bu, li, ge = (t.contiguous() for t in grids)
+            Bt, N, E, Gn = bu.shape[0], bu.shape[1], li.shape[1], ge.shape[1]
+            ids = clean_lines[0].cpu().numpy()
+            topo = powerflow.analyse_topology(N, ids[:, 0], ids[:, 1], ge[0, :, 0].cpu().numpy(), slack, device=dev)
+            cfg = PfConfig(N, E, Gn, 0, 0.0)
+            need = ctypes.c_size_t(0)
+            assert lib.gns_pfs_workspace_bytes(ctypes.byref(cfg), topo.host.ctypes.data, Bt, ctypes.byref(need)) == 0
+            ws = torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
+            res = {k: torch.empty(Bt, dict(E=E, N=N, Gn=Gn)[d], dtype=torch.float64, device=dev) for k, d in powerflow._PFS_ROWS}
+            res.update({k: torch.empty(Bt, dtype=dt, device=dev) for k, dt in powerflow._PFS_SCALARS})
+            head = (ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(), li.data_ptr(), ge.data_ptr(), Bt,
+                    v.data_ptr(), theta.data_ptr(), None, 0)
+            stream = torch.cuda.current_stream().cuda_stream
+            assert lib.gns_pfs_evaluate(*head, *(res[k].data_ptr() for k in powerflow._PFS_C_ORDER), ws.data_ptr(), need.value, stream) == 0
+            incoming = [weights(res[k].shape, 71 + n).contiguous() for n, k in enumerate(powerflow._PFS_DIFF)]
+            grads = {'grad_v': torch.empty_like(v), 'grad_theta': torch.empty_like(theta), 'grad_buses': torch.empty_like(bu),
+                     'grad_lines': torch.empty_like(li), 'grad_generators': torch.empty_like(ge)}
+            assert lib.gns_pfs_adjoint(*head, res['worst_line'].data_ptr(), res['v_min_bus'].data_ptr(), res['v_max_bus'].data_ptr(),
+                                       *(t.data_ptr() for t in incoming), *(t.data_ptr() for t in grads.values()), None, 0, stream) == 0
+            torch.cuda.synchronize()
+            for k, t in {**res, **grads}.items():
+                out[f'{name} {k}'] = t.cpu()
+
+        buses, lines, gens, slack, v, theta = synth.solvable_grids(14, 3, seed=0, device=dev)
+        grids = (buses, lines, gens)
+        Bt, E = lines.shape[0], lines.shape[1]
+        base = nr('case14 newton_raphson', grids, slack)
+        nr('case14 newton_raphson warm start', grids, slack, v0=v, theta0=theta, max_iter=3)
+        for rname, rating in (('none', None), ('E', 0.5 + weights((E,), 21).abs()), ('BtE', 0.5 + weights((Bt, E), 22).abs())):
+            sc(f'case14 solved_case rating={rname}', grids, slack, base.v.detach(), base.theta.detach(), rating)
+        sc('case14 solved_case away from the solution', grids, slack, v.to(dev), (1.5 * theta).to(dev))
+        bad = lines.clone()
+        bad[:, 5, 0] = float(buses.shape[1] + 1)                     # line 5's from id is no bus: NaN flows, a NaN gradient row
+        sc_raw('case14 solved_case line 5 not between buses', (buses, bad, gens), slack, base.v.detach().contiguous(),
+               base.theta.detach().contiguous(), lines)
+        two = gens.clone()
+        other = int((two[0, :, 0] != slack).nonzero()[0])
+        two[:, other, 0] = float(slack)                              # a second unit on the slack
+        sc('case14 solved_case two units on the slack', (buses, lines, two), slack, v.to(dev), theta.to(dev))
+
+        b118 = synth.solvable_grids(118, 2, seed=0, device=dev)      # N = 118 > 64: the lane loops make a second trip
+        res = nr('case118 newton_raphson', b118[:3], b118[3])
+        sc('case118 solved_case', b118[:3], b118[3], res.v.detach(), res.theta.detach(), 0.5 + weights((b118[1].shape[1],), 26).abs())
+
+        mixed = synth.solvable_contingency_grids(14, 6, [4, 13], seed=11, device=dev, shuffle=True)
+        nr('case14 x 6 newton_raphson mixed topologies', mixed[:3], mixed[3], mixed_topologies=True)
+
+        g1 = powerflow.ac_generator_contingency_screen_differentiable
+        ac_run('case14 ac g1 default pickup=None', g1, grids, slack)
+        ac_run('case14 ac g1 default pmax rating=BtE', g1, grids, slack, pickup='pmax', rating=0.5 + weights((Bt, E), 22).abs())
+
+    def ac_calls():
+        run = ac_run
 
         def n1(bu, li, ge, **kw):
             return powerflow.ac_contingency_screen(bu, li, ge, differentiable=True, **kw)
@@ -311,7 +416,7 @@ def dump(which, root, out_path):
         for k, v in DEFAULTS.items():
             amd.set_option(k, v)
 
-    {'dc': dc_calls, 'ac': ac_calls, 'gns': gns_calls}[which]()
+    {'dc': dc_calls, 'ac': ac_calls, 'pf': pf_calls, 'gns': gns_calls}[which]()
     torch.cuda.synchronize()
     torch.save(out, out_path)
     print(f'{root}: {len(out)} tensors of the {which} set from {powerflow.__file__}', flush=True)
@@ -355,9 +460,9 @@ def compare(which, root_a, root_b):
 
 
 if __name__ == '__main__':
-    if len(sys.argv) == 5 and sys.argv[1] == 'dump' and sys.argv[2] in ('dc', 'ac', 'gns'):
+    if len(sys.argv) == 5 and sys.argv[1] == 'dump' and sys.argv[2] in ('dc', 'ac', 'pf', 'gns'):
         dump(*sys.argv[2:])
-    elif len(sys.argv) == 5 and sys.argv[1] == 'compare' and sys.argv[2] in ('dc', 'ac', 'gns'):
+    elif len(sys.argv) == 5 and sys.argv[1] == 'compare' and sys.argv[2] in ('dc', 'ac', 'pf', 'gns'):
         sys.exit(compare(*sys.argv[2:]))
     else:
         sys.exit(__doc__)

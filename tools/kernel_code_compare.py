@@ -63,7 +63,7 @@ def main(argv):
         total, same_total = total + len(a), same_total + len(same)
         print(f'{s}.hip: {len(same)} of {len(a)} kernels identical')
         for k in a:
-            name = names[k].split('(')[0].replace('void ', '')
+            name = names[k].replace('(anonymous namespace)::', '').split('(')[0].replace('void ', '')
             if k in same:
                 print(f'  identical  {name}  ({len(a[k])} instructions)')
                 continue

@@ -1237,7 +1237,7 @@ int gns_pfs_adjoint(const gns_pf_config* cfg, const void* topo_host, const void*
  * fast-decoupled blob or whose N, E, Gn are not cfg's, for Gn = 0, and for more workgroups than a launch takes; then GNS_ESIZE for
  * a short workspace; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Every refusal comes before any launch;
  * nothing is allocated and the host is not synchronised.
- * Not here: batches that mix topologies, gradients of the optimum, AC OPF, units with Pmin = Pmax, piecewise-linear costs,
+ * Not here: batches that mix topologies, gradients of the optimum (the adjoint below), AC OPF, units with Pmin = Pmax, piecewise-linear costs,
  * contingency constraints. */
 int gns_dcopf_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes);
 int gns_dcopf_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
@@ -1247,6 +1247,65 @@ int gns_dcopf_solve(const gns_pf_config* cfg, const void* topo_host, const void*
                     double* pg, double* theta, double* line_flow, double* lmp, double* mu_line, double* mu_pmax, double* mu_pmin,
                     double* objective, uint8_t* converged, int32_t* iterations,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- DC optimal power flow: adjoint ----------------------------------------------------------------------------------------------
+ * The gradient of a loss on the eight fp64 outputs of gns_dcopf_solve with respect to the data of the problem, for every grid of the
+ * batch, from the forward's inputs and returned tensors alone (the forward saves nothing else).  The optimum is differentiated by
+ * the implicit-function theorem on its KKT conditions with the active rows held as equalities and the multipliers of the others
+ * as constants; there is no second optimisation.
+ *   inputs   buses, lines, generators, cost, rating and their flags: the forward call's.  pg .. iterations: what it returned.
+ *   incoming grad_pg [Bt,Gn], grad_theta [Bt,N], grad_line_flow [Bt,E], grad_lmp [Bt,N], grad_mu_line [Bt,E], grad_mu_pmax,
+ *            grad_mu_pmin [Bt,Gn], grad_objective [Bt], fp64; NULL: zero.
+ *   outputs  (NULL: not wanted; every element written) grad_buses [Bt,N,6] fp32: Pd (2) and Gs (4), the other columns 0;
+ *            grad_generators [Bt,Gn,7] fp32: Pmax (1) and Pmin (2), the other columns 0, the listed Pg included; grad_cost
+ *            [Bt,Gn,2] fp64 (c2, c1), per grid whatever cost_per_grid says (a shared cost's gradient is the sum over the grids);
+ *            grad_rating [Bt,E] fp64, likewise, 0 at a rating of +inf.  The lines' x, tau and shift are not differentiated.
+ *
+ * Method, per grid.  S as the forward forms it (its factor kernel, unchanged, into this call's workspace).  Active set from the
+ * outputs: with the slacks z = rating -+ line_flow, Pmax - pg, pg - Pmin, a line's upper row is active when mu_line > max(z, 0), its
+ * lower one when -mu_line > max(z, 0), a unit's rows likewise with mu_pmax and mu_pmin; F is the set of units without an active
+ * row, k the number of active lines.  The cotangents are pulled back to (p, lambda, mu_line, nu): theta and line_flow through
+ * t = A^-1 (g_theta_r + B_f,r^T g_flow) on the base factor (A = Bbus[r, r] is symmetric), C_g^T t to p and -t to Pd and Gs; lmp
+ * through y = A^-1 g_lmp_r, -sum g_lmp to lambda and -b_l (y_f - y_t) to mu_line_l; objective gives g (2 c2 p + c1) to p, g p^2 to
+ * c2 and g p to c1; the cotangent of a multiplier whose row is not active is dropped (its derivative is 0).  Then
+ *     [ diag(2 c2_F)  1    S_aF^T ] [a_p     ]   [g_p     ]
+ *     [ 1^T           0    0      ] [a_lambda] = [g_lambda]
+ *     [ S_aF          0    0      ] [a_mu    ]   [g_mu    ]
+ * of order n = |F| + 1 + k <= 2 Gn, the units on a bound substituted (a_p there is the cotangent of the unit's own multiplier, a_nu
+ * follows from its stationarity row), is solved by dense LU with partial pivoting in LDS: exact for c2 = 0, no regularisation, no
+ * S Q^-1 S^T, and not the forward's normal matrix, which is conditioned 1e14 and worse on a linear program.  The gradients are
+ * -a^T dF/d(data): c1 -a_p, c2 -2 p a_p, every bus's Pd and Gs +a_lambda and, through f0, +A^-1 B_f,r^T a_mu (a third solve), an
+ * active line's rating +-a_mu by the sign of its row, Pmax or Pmin +a_nu.  Three network solves and one dense solve per grid.
+ * Rows.  A grid whose incoming gradients are all exactly zero (or NULL) gets zero rows.  Otherwise a grid with iterations -1,
+ * converged 0 or an output that is not finite gets NaN in every element of its rows, and so does a grid whose n exceeds the
+ * order the image holds or whose LU meets a pivot that is zero or not finite; the other grids are unaffected.  Near a degenerate
+ * optimum (a row whose slack and multiplier are both small) the gradient is that of the active set as classified: finite, and not
+ * reliable.  No atomics, every sum in a fixed order: a grid's rows are bit-identical alone, in any batch, in any order and from
+ * run to run.
+ *
+ * Kernels (gns_dcopf_adjoint.hip), a wave per workgroup: gns_dcopf.hip's factor kernel, then the adjoint kernel, one grid each.
+ * gns_dcopf_adjoint_lds_bytes: the adjoint kernel's image at the largest order n_max <= 2 Gn that fits GNS_PF_LDS_MAX_BYTES, and
+ * n_max (NULL: not wanted): 8 (nnz_lu_p + dim_p + N + 3 E + 2 dim_p) + 32 Gn bytes for the network solves, then
+ * 8 (3 Gn + E + ceil((2 Gn + E) / 2) + n_max ((n_max + 1) | 1)) bytes.  gns_dcopf_adjoint_workspace_bytes: gns_dcopf_workspace_bytes'
+ * (GNS_EUNSUPPORTED from the query too).
+ *
+ * Errors, in order: gns_dcopf_solve's GNS_EINVAL cases (the forward's outputs count as inputs here; the incoming gradients and
+ * the gradient outputs may be NULL); then GNS_ESIZE for a short workspace; then GNS_EUNSUPPORTED when the network-solve part of
+ * the image (n = 0) alone is above GNS_PF_LDS_MAX_BYTES.  With no gradient output asked for the call returns GNS_OK without a
+ * launch, after every other check.  Every refusal comes before any launch; nothing is allocated and the host is not synchronised.
+ * Not here: batches that mix topologies, gradients with respect to the lines, second derivatives. */
+int gns_dcopf_adjoint_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* order);
+int gns_dcopf_adjoint_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
+int gns_dcopf_adjoint(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                      const float* buses, const float* lines, const float* generators, int64_t Bt,
+                      const double* cost, int32_t cost_per_grid, const double* rating, int32_t rating_per_grid,
+                      const double* pg, const double* theta, const double* line_flow, const double* lmp,
+                      const double* mu_line, const double* mu_pmax, const double* mu_pmin, const double* objective,
+                      const uint8_t* converged, const int32_t* iterations,
+                      const double* grad_pg, const double* grad_theta, const double* grad_line_flow, const double* grad_lmp,
+                      const double* grad_mu_line, const double* grad_mu_pmax, const double* grad_mu_pmin, const double* grad_objective,
+                      float* grad_buses, float* grad_generators, double* grad_cost, double* grad_rating,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

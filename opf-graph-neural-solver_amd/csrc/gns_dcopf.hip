@@ -19,6 +19,7 @@
 #include "gns_pf_device.h"
 #include "gns_dc_device.h"
 #include "gns_dcn1_device.h"
+#include "gns_dcopf_device.h"
 
 namespace {
 
@@ -27,64 +28,15 @@ constexpr double DCOPF_SIGMA = 0.1;      // centring
 constexpr double DCOPF_DELTA = 1e-14;    // the normal matrix's diagonal gets DELTA trace(M) / Gn
 constexpr int DCOPF_TILE = 4;            // a lane forms DCOPF_TILE x DCOPF_TILE entries of the normal matrix at a time
 
-// The workspace of one call, all doubles: S [Bt][E][Gn], f0 [Bt][E], the units' finite flags [Bt][Gn], the base case's status [Bt]
-// (1: solved), then what the iteration leaves for the finish: lambda [Bt] and whether the grid has a dispatch [Bt]
-struct DcopfWorkspace {
-  double* S;
-  double* f0;
-  double* fin;
-  double* status;
-  double* lam;
-  double* solved;
-};
-
-__host__ __device__ inline DcopfWorkspace dcopf_workspace(double* ws, const int64_t Bt, const int64_t Gn, const int64_t E) {
-  DcopfWorkspace w;
-  w.S = ws;
-  w.f0 = w.S + Bt * E * Gn;
-  w.fin = w.f0 + Bt * E;
-  w.status = w.fin + Bt * Gn;
-  w.lam = w.status + Bt;
-  w.solved = w.lam + Bt;
-  return w;
-}
-
-size_t dcopf_ws_bytes(const int32_t* h, int64_t Bt) {
-  const int64_t E = h[FH_E], Gn = h[FH_GN];
-  return ((size_t)Bt * (size_t)(E * Gn + E + Gn + 3) * sizeof(double) + 255) & ~(size_t)255;
-}
-
-// The factor and the finish kernel keep a generator block of zeros behind the screens' image (four doubles per unit hold its seven
-// floats): the base case is the one without generation, whatever Pg the rows list
-int64_t dcopf_zero_gens_bytes(const int32_t* h) { return 32 * (int64_t)h[FH_GN]; }
-
-// Units a workgroup of the factor kernel takes side by side: dcn1_lanes on what the zeros leave
-int dcopf_lanes(const int32_t* h) { return dcn1_lanes(h, GNS_PF_LDS_MAX_BYTES - dcopf_zero_gens_bytes(h)); }
-
-int64_t dcopf_factor_lds(const int32_t* h, int lanes) { return dcn1_lds_bytes(h, lanes) + dcopf_zero_gens_bytes(h); }
-
 // The largest image of the three kernels (the finish runs on the factor kernel's image at width 1)
 int64_t dcopf_call_lds(const int32_t* h, int lanes) {
   const int64_t a = dcopf_factor_lds(h, lanes), b = dcopf_lds_bytes(h);
   return a > b ? a : b;
 }
 
-__device__ __forceinline__ double dcopf_wave_sum(double x) {
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
 __device__ __forceinline__ double dcopf_wave_min(double x) {
   for (int o = 32; o > 0; o >>= 1) x = fmin(x, __shfl_xor(x, o));
   return x;
-}
-
-// The zeros a base case without generation reads as its generator rows
-__device__ __forceinline__ const float* dcopf_zero_gens(double* at, const int Gn, const int lane) {
-  float* z = reinterpret_cast<float*>(at);
-  for (int q = lane; q < Gn * 7; q += PF_THREADS) z[q] = 0.0f;
-  __syncthreads();
-  return z;
 }
 
 // ---- the factor kernel
@@ -592,15 +544,15 @@ __global__ __launch_bounds__(PF_THREADS) void gns_dcopf_finish_kernel(const int3
   for (int i = lane; i < N; i += PF_THREADS) lmp_out[(size_t)g * N + i] = 0.0 - lam - (p_idx[i] >= 0 ? m.rhs[p_idx[i]] : 0.0);
 }
 
-// The host checks of a call on the blob at topo_host: GNS_EINVAL unless it is an FD blob of cfg's shape with a unit
-int dcopf_check(const gns_pf_config* cfg, const void* topo_host) {
-  if (!pf_config_ok(cfg) || !topo_host) return GNS_EINVAL;
-  const int32_t* h = static_cast<const int32_t*>(topo_host);
-  if (!pf_header_ok<DcBlobKind>(cfg, h) || h[FH_GN] <= 0) return GNS_EINVAL;
-  return GNS_OK;
-}
-
 }  // namespace
+
+int gns_dcopf_launch_factor(const int32_t* h, const void* topo_dev, const float* buses, const float* lines, const float* generators,
+                            int64_t Bt, double* ws, void* stream) {
+  const int lanes = dcopf_lanes(h);
+  const int64_t nchunks = (h[FH_GN] + lanes - 1) / lanes;
+  return pf_launch<gns_dcopf_factor_kernel>(Bt * nchunks, dcopf_factor_lds(h, lanes), stream, static_cast<const int32_t*>(topo_dev), buses,
+                                            lines, generators, (int)Bt, lanes, (int)nchunks, ws);
+}
 
 extern "C" int gns_dcopf_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes) {
   if (!topo_host || !bytes) return GNS_EINVAL;
@@ -640,8 +592,7 @@ extern "C" int gns_dcopf_solve(const gns_pf_config* cfg, const void* topo_host, 
   if (dcopf_call_lds(h, lanes) > GNS_PF_LDS_MAX_BYTES) return GNS_EUNSUPPORTED;
   const int32_t* topo = static_cast<const int32_t*>(topo_dev);
   double* ws = static_cast<double*>(workspace);
-  int rl = pf_launch<gns_dcopf_factor_kernel>(Bt * nchunks, dcopf_factor_lds(h, lanes), stream, topo, buses, lines, generators, (int)Bt,
-                                              lanes, (int)nchunks, ws);
+  int rl = gns_dcopf_launch_factor(h, topo_dev, buses, lines, generators, Bt, ws, stream);
   if (rl != GNS_OK) return rl;
   rl = pf_launch<gns_dcopf_ipm_kernel>(Bt, dcopf_lds_bytes(h), stream, topo, buses, generators, cost, (int)cost_per_grid, rating,
                                        (int)rating_per_grid, (int)Bt, cfg->tol, (int)cfg->max_iter, ws, pg, mu_line, mu_pmax, mu_pmin,

@@ -131,6 +131,24 @@ PF_HOST_DEVICE inline int64_t dcopf_lds_bytes(const int32_t* h) {
   return 8 * (Gn * (Gn + 1) / 2 + 14 * Gn + 10 * (int64_t)h[FH_E]);
 }
 
+// LDS image of one workgroup of the DC optimal power flow's adjoint (gns_dcopf_adjoint_lds_bytes), one grid per workgroup, at KKT
+// order n: the DC N-1 screen's image at width 1 with the 32 Gn bytes of generator zeros (the network solves), three doubles per unit
+// and one per line (the cotangents and the adjoint of the dispatch and of the line multipliers), two int32 per unit and one per line
+// (each unit's row state, the free units and the active lines in order), and the dense KKT matrix with its right-hand side as
+// [n][(n + 1) | 1] doubles (an odd row length: a column walks every bank)
+PF_HOST_DEVICE inline int64_t dcopf_adjoint_lds_bytes(const int32_t* h, int64_t n) {
+  const int64_t Gn = h[FH_GN], E = h[FH_E];
+  return dcn1_lds_bytes(h, 1) + 32 * Gn + 8 * (3 * Gn + E + (2 * Gn + E + 1) / 2 + n * ((n + 1) | 1));
+}
+
+// The largest KKT order the adjoint's image holds within max_bytes: up to 2 Gn, the worst case (Gn free units, Gn - 1 active lines
+// and the balance); 0 when even the network-solve part does not fit
+PF_HOST_DEVICE inline int dcopf_adjoint_order(const int32_t* h, int64_t max_bytes) {
+  int n = 2 * h[FH_GN];
+  while (n > 0 && dcopf_adjoint_lds_bytes(h, n) > max_bytes) --n;
+  return n;
+}
+
 // What the code that handles either kind of blob (the set checks on the host and in the set kernels) needs to know of a kind.
 // The magic, the total, N, E and Gn sit at the same header words in both.
 static_assert(FH_MAGIC == PH_MAGIC && FH_TOTAL == PH_TOTAL && FH_N == PH_N && FH_E == PH_E && FH_GN == PH_GN, "shared header words");

@@ -58,6 +58,12 @@ row's own analysis, with the gradients of the dispatch, the set points and the p
 a given state (a solver's, or a GNS prediction) the flows at both ends of every line, the bus injections, Newton-Raphson's own
 ``||F||_inf``, the generators' ``P`` and ``Q``, the slack's balancing power and the screens' summaries, in one launch
 (``csrc/gns_pfs.hip``), with a backward (``gns_pfs_adjoint``) to the state and the inputs that needs no linear solve.
+
+``dc_optimal_power_flow(...)`` chooses the dispatch the other calls evaluate (PYPOWER ``dcopf`` without piecewise-linear costs): a
+primal-dual interior point per grid on the problem reduced to the dispatch by generator shift factors (``csrc/gns_dcopf.hip``), with
+the locational marginal prices and the multipliers.  ``dc_optimal_power_flow_differentiable(...)`` is the same call with a backward
+(``gns_dcopf_adjoint``, ``csrc/gns_dcopf_adjoint.hip``): the implicit-function theorem on the KKT conditions of the active set, one
+dense LU in LDS and three solves on the base factor per grid.
 """
 from __future__ import annotations
 
@@ -760,45 +766,156 @@ def dc_optimal_power_flow(buses, lines, generators, B=None, L=None, G=None, *, c
     A grid is not solved (``iterations`` -1, NaN outputs) when its base factor fails, its data are not finite, some unit has
     ``Pmin >= Pmax`` or its demand lies outside ``[sum Pmin, sum Pmax]``; the other grids are unaffected, and every grid's result is
     bit-identical alone, in any batch, in any order and from run to run.  There is no host synchronisation after the analysis of
-    the topology.  Not differentiable."""
+    the topology.  This call ignores ``requires_grad``; ``dc_optimal_power_flow_differentiable`` is the same call with a backward."""
+    return _dc_opf(buses, lines, generators, B, L, G, cost, rating, slack_bus, tol, max_iter, False)
+
+
+_DCOPF_ADJOINT_LDS_FORMULA = ("8 * (nnz_lu_p + dim_p + N + 3 E + 2 dim_p) + 32 Gn + 8 * (3 Gn + E + ceil((2 Gn + E) / 2) + n ((n + 1) | 1)) "
+                              "bytes per workgroup: the DC N-1 screen's image at W = 1 and a generator block of zeros for the network "
+                              "solves, the cotangents, and the dense KKT system of order n = free units + 1 + active lines with "
+                              "its right-hand side, here with n = 0")
+
+
+def _dc_opf(buses, lines, generators, B, L, G, cost, rating, slack_bus, tol, max_iter, differentiable):
+    """``dc_optimal_power_flow`` and its differentiable twin: one set-up, the same launches."""
     _check_iteration(tol, max_iter)
+    if differentiable and isinstance(lines, torch.Tensor) and lines.requires_grad:
+        raise ValueError('dc_optimal_power_flow_differentiable does not differentiate with respect to lines (x, tau, shift): '
+                         'detach them (their derivative is not zero, so it is not returned as zero)')
+    grad = differentiable and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                                              for t in (buses, generators, cost, rating))
     with torch.no_grad():
         # the shapes first, so that a bad cost or rating is refused where no device is visible too
         single, shaped, shaped_lines, shaped_gens = _as_batch(buses, lines, generators, B, L, G)
         Bt, E, Gn = shaped.shape[0], shaped_lines.shape[1], shaped_gens.shape[1]
         if Gn == 0:
             raise ValueError('dc_optimal_power_flow needs at least one generator')
-        cost = _dcopf_cost(cost, Bt, Gn, single)
+        cost_g, rating_g = (t if grad and isinstance(t, torch.Tensor) and t.requires_grad else None for t in (cost, rating))
+        cost = _dcopf_cost(cost, Bt, Gn, single).detach()
         rating = _dcopf_rating(rating, Bt, E, single)
-        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None,
-                                                                 None, tol, max_iter, False)
+        rating = None if rating is None else rating.detach()
+    with torch.set_grad_enabled(grad):
+        if not grad:
+            buses, generators = buses.detach(), generators.detach()
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses, lines.detach(), generators, B, L, G, None, None, tol, max_iter,
+                                                                 False)
         lib = load_library()
         N, dev = buses.shape[1], buses.device
         cfg = PfConfig(N, E, Gn, int(max_iter), float(tol))
-        topo = _analysed(_FD, *_topology_key(buses, lines, generators, slack_bus, 'dc_optimal_power_flow'), dev)
+        plain = (buses.detach(), lines, generators.detach())
+        topo = _analysed(_FD, *_topology_key(*plain, slack_bus, 'dc_optimal_power_flow'), dev)
         lds = lambda: _screen_lds_bytes('gns_dcopf_lds_bytes', topo.host)[0]     # noqa: E731
+        adjoint_lds = lambda: _screen_lds_bytes('gns_dcopf_adjoint_lds_bytes', topo.host)[0]     # noqa: E731
         cost, rating = cost.to(dev).contiguous(), None if rating is None else rating.to(dev).contiguous()
+
+        def data():                      # (a closure, used as late as the backward: it keeps cost and rating alive)
+            return cost.data_ptr(), int(cost.dim() == 3), _ptr(rating), int(rating is not None and rating.dim() == 2)
+
         f64 = dict(dtype=torch.float64, device=dev)
-        pg, mu_pmax, mu_pmin = (torch.empty(Bt, Gn, **f64) for _ in range(3))
-        theta, lmp = (torch.empty(Bt, N, **f64) for _ in range(2))
-        flow, mu_line = (torch.empty(Bt, E, **f64) for _ in range(2))
-        objective = torch.empty(Bt, **f64)
-        conv, iters = torch.empty(Bt, dtype=torch.uint8, device=dev), torch.empty(Bt, dtype=torch.int32, device=dev)
-        ws = _gns._workspace(_size_query(lib.gns_dcopf_workspace_bytes, 'gns_dcopf_workspace_bytes',
-                                         (ctypes.byref(cfg), topo.host.ctypes.data, Bt), lds, _DCOPF.formula), dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            _check(lib.gns_dcopf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(), lines.data_ptr(),
-                                       generators.data_ptr(), Bt, cost.data_ptr(), int(cost.dim() == 3), _ptr(rating),
-                                       int(rating is not None and rating.dim() == 2),
-                                       *map(_ptr, (pg, theta, flow, lmp, mu_line, mu_pmax, mu_pmin, objective, conv, iters)),
-                                       ws.data_ptr(), ws.numel(), stream), 'gns_dcopf_solve', lds, _DCOPF.formula)
-        out = [pg, theta, flow, lmp, mu_line, mu_pmax, mu_pmin, objective, conv.bool(), iters]
+
+        def solve(bu, ge):
+            pg, mu_pmax, mu_pmin = (torch.empty(Bt, Gn, **f64) for _ in range(3))
+            theta, lmp = (torch.empty(Bt, N, **f64) for _ in range(2))
+            flow, mu_line = (torch.empty(Bt, E, **f64) for _ in range(2))
+            objective = torch.empty(Bt, **f64)
+            conv, iters = torch.empty(Bt, dtype=torch.uint8, device=dev), torch.empty(Bt, dtype=torch.int32, device=dev)
+            ws = _gns._workspace(_size_query(lib.gns_dcopf_workspace_bytes, 'gns_dcopf_workspace_bytes',
+                                             (ctypes.byref(cfg), topo.host.ctypes.data, Bt), lds, _DCOPF.formula), dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(lib.gns_dcopf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(), lines.data_ptr(),
+                                           ge.data_ptr(), Bt, *data(),
+                                           *map(_ptr, (pg, theta, flow, lmp, mu_line, mu_pmax, mu_pmin, objective, conv, iters)),
+                                           ws.data_ptr(), ws.numel(), stream), 'gns_dcopf_solve', lds, _DCOPF.formula)
+            return [pg, theta, flow, lmp, mu_line, mu_pmax, mu_pmin, objective, conv.bool(), iters], conv
+
+        def adjoint_workspace_bytes():
+            return _size_query(lib.gns_dcopf_adjoint_workspace_bytes, 'gns_dcopf_adjoint_workspace_bytes',
+                               (ctypes.byref(cfg), topo.host.ctypes.data, Bt), adjoint_lds, _DCOPF_ADJOINT_LDS_FORMULA)
+
+        def adjoint(bu, ge, out, conv, incoming, need):
+            gin = [torch.empty_like(bu) if need[0] else None, torch.empty_like(ge) if need[1] else None,
+                   torch.empty(Bt, Gn, 2, **f64) if need[2] else None, torch.empty(Bt, E, **f64) if need[3] else None]
+            incoming = [None if g is None else g.to(**f64).contiguous() for g in incoming]
+            ws = _gns._workspace(adjoint_workspace_bytes(), dev)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(lib.gns_dcopf_adjoint(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), bu.data_ptr(),
+                                             lines.data_ptr(), ge.data_ptr(), Bt, *data(), *map(_ptr, out[:8]), conv.data_ptr(),
+                                             out[9].data_ptr(), *map(_ptr, incoming), *map(_ptr, gin), ws.data_ptr(), ws.numel(), stream),
+                       'gns_dcopf_adjoint', adjoint_lds, _DCOPF_ADJOINT_LDS_FORMULA)
+            return gin
+
+        if grad:
+            # the backward's own refusal comes before anything is launched; a shared cost or rating is expanded to per-grid form
+            # here, so that autograd sums its gradient over the grids
+            adjoint_workspace_bytes()
+            if cost_g is not None:
+                cost_g = cost_g.to(dev).reshape(cost.shape).expand(Bt, Gn, 2)
+            if rating_g is not None:
+                rating_g = rating_g.to(dev).reshape(rating.shape).expand(Bt, E)
+            out = list(_DCOPFFunction.apply(solve, adjoint, buses, generators, cost_g, rating_g))
+        else:
+            out = solve(plain[0], plain[2])[0]
         if in_dev != dev:
             out = [t.to(in_dev) for t in out]
         if single:
             out = [t[0] for t in out]
         return DcOpfResult(*out)
+
+
+class _DCOPFFunction(torch.autograd.Function):
+    """``dc_optimal_power_flow_differentiable`` when an input requires grad: the forward is the plain call's launches, the backward one
+    ``gns_dcopf_adjoint`` call on the forward's topology, inputs and returned tensors.  ``cost`` ``[Bt,Gn,2]`` and ``rating``
+    ``[Bt,E]`` (None: no gradient wanted) are on the graph for their gradients alone: the kernels read the values the set-up
+    uploaded."""
+
+    @staticmethod
+    def forward(ctx, solve, adjoint, buses, gens, cost, rating):
+        out, conv = solve(buses, gens)
+        ctx.mark_non_differentiable(out[8], out[9])
+        ctx.set_materialize_grads(False)
+        ctx.adjoint = adjoint
+        ctx.save_for_backward(buses, gens, conv, *out)
+        return tuple(out)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gout):
+        buses, gens, conv, *out = ctx.saved_tensors
+        return (None, None, *ctx.adjoint(buses, gens, out, conv, gout[:8], ctx.needs_input_grad[2:6]))
+
+
+def dc_optimal_power_flow_differentiable(buses, lines, generators, B=None, L=None, G=None, *, cost, rating=None, slack_bus=None,
+                                         tol=1e-8, max_iter=150):
+    """``dc_optimal_power_flow`` with gradients: the same arguments, the same ``DcOpfResult`` with every output bit-identical to that
+    call's (its forward is that call's launches), and a backward on the device: for a model trained against dispatch cost, a loss
+    on locational prices, or the sensitivity of a dispatch to a load or a rating.
+
+    With grad mode on and ``requires_grad`` on ``buses``, ``generators``, ``cost`` or ``rating``, the outputs ``pg``, ``theta``,
+    ``line_flow``, ``lmp``, ``mu_line``, ``mu_pmax``, ``mu_pmin`` and ``objective`` are differentiable through one
+    ``gns_dcopf_adjoint`` call on the forward's analysed topology, inputs and returned tensors (nothing else is saved, nothing is
+    optimised again, the host is not synchronised): the optimum is differentiated by the implicit-function theorem on its KKT
+    conditions, with the active rows held as equalities.  Per grid: the shift factors again (the forward's factor kernel), three
+    solves on the base factor, and one dense LU with partial pivoting of order ``free units + 1 + active lines <= 2 Gn`` in LDS,
+    exact for linear programs (``c2 == 0``) too.  Otherwise it is the plain call and returns plain tensors.
+
+    The derivative is exact with respect to ``buses`` columns ``Pd`` (2) and ``Gs`` (4), ``generators`` columns ``Pmax`` (1) and
+    ``Pmin`` (2) (every other column gets 0, the ignored ``Pg`` included), ``cost`` (``c2``, ``c1``) and ``rating`` (0 at ``+inf``);
+    a shared ``cost [Gn,2]`` or ``rating [E]`` receives the sum over the grids.  ``lines`` are not differentiated: the call raises
+    ``ValueError`` when ``lines.requires_grad`` rather than return zeros for a derivative that is not zero.  ``converged`` and
+    ``iterations`` are not differentiable.
+
+    A row is active when its multiplier exceeds its slack (``mu_line > max(rating - line_flow, 0)`` and so on), read from the returned
+    tensors.  Near a degenerate optimum, where a row's slack and multiplier are both small, the optimum has no derivative: the
+    gradient returned is that of the active set as classified, finite and not reliable.  A grid with ``iterations == -1``,
+    ``converged`` False or a NaN output gets NaN gradient rows, and so does one whose KKT system exceeds the order the LDS image
+    holds or meets a zero pivot; a grid whose incoming gradients are all zero (a loss that indexes it out) gets zero rows.  Other
+    grids are unaffected, and a grid's gradient is bit-identical alone, in any batch, in any order and from run to run.
+
+    Out of scope: gradients with respect to ``lines``, second derivatives, mixed topologies.
+    Contract: ``include/gns_powerflow.h``, "DC optimal power flow: adjoint"."""
+    return _dc_opf(buses, lines, generators, B, L, G, cost, rating, slack_bus, tol, max_iter, True)
 
 
 def _dcn1_lds_bytes(host):

@@ -7,6 +7,8 @@ product is the contract of ``include/gns_powerflow.h`` ("DC optimal power flow")
 the DC solution there, z = max(1, -h), gamma = 1, mu = gamma / z, lambda = 0), PIPS's step rule (xi = 0.99995, separate primal and
 dual lengths, sigma = 0.1), ``delta trace / Gn`` on the diagonal of the Hessian's p block with delta = 1e-14, and the three termination
 quantities tested before every update.  The locational marginal prices are minus the bus balances' multipliers.
+Its iteration count is not the contract's: its termination figures take ``|x|_inf`` with theta in x where the contract has ``|p|_inf``,
+so it can stop an iteration or two earlier; ``dc_opf_reduced_reference`` follows the contract's figures and is what pins the count.
 
 Default tolerance.  The probe ``probe_default_tol()`` runs this reference at 1e-8, 1e-7 and 1e-6 on every grid of every set of
 ``dc_opf_cases`` and reports the tightest at which all converge within 150 iterations.  Outcome (CPU, all 13 sets, 28 grids):

@@ -1238,7 +1238,7 @@ int gns_pfs_adjoint(const gns_pf_config* cfg, const void* topo_host, const void*
  * a short workspace; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Every refusal comes before any launch;
  * nothing is allocated and the host is not synchronised.
  * Not here: batches that mix topologies, gradients of the optimum (the adjoint below), AC OPF, units with Pmin = Pmax, piecewise-linear costs,
- * contingency constraints. */
+ * contingency constraints (gns_dcscopf_solve below). */
 int gns_dcopf_lds_bytes(const void* topo_host, int64_t* bytes, int32_t* lanes);
 int gns_dcopf_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, size_t* bytes);
 int gns_dcopf_solve(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
@@ -1305,6 +1305,69 @@ int gns_dcopf_adjoint(const gns_pf_config* cfg, const void* topo_host, const voi
                       const double* grad_pg, const double* grad_theta, const double* grad_line_flow, const double* grad_lmp,
                       const double* grad_mu_line, const double* grad_mu_pmax, const double* grad_mu_pmin, const double* grad_objective,
                       float* grad_buses, float* grad_generators, double* grad_cost, double* grad_rating,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Security-constrained DC optimal power flow ----------------------------------------------------------------------------------
+ * gns_dcopf_solve's problem with contingency rows: the cheapest dispatch within the units' bounds, the lines' ratings and, for every
+ * listed row, the limit on a monitored line's flow after the outage of another line.  Blob, buses, lines, generators, cfg, cost,
+ * rating and their flags are gns_dcopf_solve's.  Additional inputs:
+ *   rows      int32 on the device, [R,2] (rows_per_grid = 0) or [Bt,R,2] (1), R = n_row >= 1: (l, k), line l monitored after the
+ *             outage of line k, 0-based; (-1, -1) is an empty slot.  Duplicates are independent rows.
+ *   rating_c  fp64 [E] (rating_c_per_grid = 0) or [Bt,E] (1), positive: the post-outage (emergency) rating of the monitored line;
+ *             NULL: rating with its flag is used (both NULL: no row constrains anything).  A row whose monitored line has a rating
+ *             of +inf constrains nothing and is treated as an empty slot.
+ *   bridge    u8 [E] on the device: the host's bridge flags of the topology (what the screens take per outage as `islanding`).
+ *
+ * Problem.  gns_dcopf_solve's, plus for every row r = (l, k) that is not empty:  |F_l + L_r F_k| <= rating_c_l,  with F = f0 + S p
+ * the base flows and L_r = b_l (z_k[f_l] - z_k[t_l]) / (1 - b_k d_k), z_k and d_k as gns_dcn1_screen defines them ("Semantics"): the
+ * post-outage flow of line l.  A line k from a bus to itself gives L_r = 0.  A row is a combination of two rows of S, so the normal
+ * matrix stays Gn x Gn however many rows are listed.
+ *
+ * Method.  gns_dcopf_solve's, constant for constant (start, xi, sigma, delta, the three termination figures, separate step lengths,
+ * the not-finite-step rule); both calls run one body.  The rows join A_in after the line rows and before the box rows:
+ * z = max(1, -h), mu = gamma / z at the start; n_ineq counts two per row that is not empty.  A row's value is fl[l] + L_r fl[k] from
+ * the current flows and A_r dp is (S dp)[l] + L_r (S dp)[k]; A_in^T v adds v_r at l and L_r v_r at k, the rows in list order, before
+ * the one S^T product; M gains sum_r d_r a_r a_r^T with a_r = S[l] + L_r S[k] after the lines' terms, the rows in list order.
+ *
+ * Outputs, every element written: gns_dcopf_solve's ten, and
+ *   mu_row [Bt,R]    the multiplier of the row's upper side minus that of its lower; 0 in an empty slot
+ *   row_flow [Bt,R]  line_flow_l + L_r line_flow_k at the returned dispatch; NaN in an empty slot
+ * lmp stays the derivative of the optimal cost with respect to Pd: the finish's right-hand side takes mu_line_l + sum_r mu_r at
+ * line l and L_r mu_r at line k.  With every slot empty the ten outputs are gns_dcopf_solve's bit for bit.
+ *   A grid is not solved (iterations -1, NaN in every fp64 output, mu_row and row_flow included in every slot, converged 0) under
+ *   gns_dcopf_solve's rules (rating_c read like rating, at the monitored lines of the rows), or when a row that is not (-1, -1) has
+ *   l or k outside 0 .. E - 1, has l = k, has bridge[k] != 0 (unless its rating_c is +inf: it is an empty slot), or has a z_k or a
+ *   denominator that is zero or not finite; the other grids are unaffected.  No atomics, every sum in a fixed order: a grid's
+ *   result is bit-identical alone, in any batch, in any order, with rows, cost and the ratings shared or per grid, and from run to
+ *   run.
+ *
+ * Kernels (gns_dcscopf.hip and gns_dcopf.hip), five launches, a wave per workgroup:
+ *   factor    gns_dcopf_solve's, unchanged
+ *   rows      per (grid, chunk of W slots) on the factor kernel's image: the base factor, a lane per slot for its own solve z_k (a
+ *             solve per slot, duplicates of k included), L_r and the slot's status into the workspace
+ *   ipm       per grid; gns_dcopf_solve's image plus 8 (10 R + ceil(E / 2)) bytes: per slot L_r, the rating, the two slacks and
+ *             multipliers, the weight, the row's entries of the two vectors A_in^T takes and (l, k); per line an int32, whether a
+ *             row names it
+ *   finish    gns_dcopf_solve's, unchanged, on the per-line multipliers above
+ *   row_flow  a thread per slot
+ * gns_dcscopf_lds_bytes: the larger of the factor image at W and the ipm image for n_row, and W (NULL: not wanted), as
+ * gns_dcopf_lds_bytes.  gns_dcscopf_workspace_bytes: gns_dcopf_workspace_bytes' plus 8 Bt (2 R + E) bytes rounded up to 256.
+ *
+ * Errors, in gns_dcopf_solve's order: GNS_EINVAL for its cases and for NULL rows, bridge, mu_row or row_flow, n_row <= 0, a flag
+ * outside {0, 1} and more workgroups than a launch takes (the units' chunks, the slots' chunks or the row_flow blocks); then
+ * GNS_ESIZE for a short workspace; then GNS_EUNSUPPORTED for an LDS image above GNS_PF_LDS_MAX_BYTES.  Every refusal comes before
+ * any launch; nothing is allocated and the host is not synchronised.
+ * Not here: batches that mix topologies, gradients of the secure dispatch, generator outages as constraints, corrective
+ * re-dispatch after an outage, double outages. */
+int gns_dcscopf_lds_bytes(const void* topo_host, int32_t n_row, int64_t* bytes, int32_t* lanes);
+int gns_dcscopf_workspace_bytes(const gns_pf_config* cfg, const void* topo_host, int64_t Bt, int32_t n_row, size_t* bytes);
+int gns_dcscopf_solve(const gns_pf_config* cfg, const void* topo_host, const void* topo_dev,
+                      const float* buses, const float* lines, const float* generators, int64_t Bt,
+                      const double* cost, int32_t cost_per_grid, const double* rating, int32_t rating_per_grid,
+                      const int32_t* rows, int32_t rows_per_grid, int32_t n_row,
+                      const double* rating_c, int32_t rating_c_per_grid, const uint8_t* bridge,
+                      double* pg, double* theta, double* line_flow, double* lmp, double* mu_line, double* mu_pmax, double* mu_pmin,
+                      double* objective, uint8_t* converged, int32_t* iterations, double* mu_row, double* row_flow,
                       void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus

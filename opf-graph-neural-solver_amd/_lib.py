@@ -166,9 +166,12 @@ def load_library():
     lib.gns_dcopf_adjoint_lds_bytes.argtypes = [vp, ctypes.POINTER(i64), ctypes.POINTER(i32)]
     lib.gns_dcopf_adjoint_workspace_bytes.argtypes = [pfcp, vp, i64, ctypes.POINTER(sz)]
     lib.gns_dcopf_adjoint.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32] + [vp] * 22 + [vp, sz, vp]
+    lib.gns_dcscopf_lds_bytes.argtypes = [vp, i32, ctypes.POINTER(i64), ctypes.POINTER(i32)]
+    lib.gns_dcscopf_workspace_bytes.argtypes = [pfcp, vp, i64, i32, ctypes.POINTER(sz)]
+    lib.gns_dcscopf_solve.argtypes = [pfcp, vp, vp, vp, vp, vp, i64, vp, i32, vp, i32, vp, i32, i32, vp, i32, vp] + [vp] * 12 + [vp, sz, vp]
     for f in (PF_EXPORTS + FD_EXPORTS + DC_EXPORTS + DCN1_EXPORTS + DCN2_EXPORTS + DCN2_ADJOINT_EXPORTS + ACN1_EXPORTS + ACN1_ADJOINT_EXPORTS +
               ACN2_EXPORTS + ACN2_ADJOINT_EXPORTS + DCG1_EXPORTS + DCG1_ADJOINT_EXPORTS + ACG1_EXPORTS + ACG1_ADJOINT_EXPORTS +
-              PFS_EXPORTS + DCOPF_EXPORTS + DCOPF_GRAD_EXPORTS):
+              PFS_EXPORTS + DCOPF_EXPORTS + DCOPF_GRAD_EXPORTS + DCSCOPF_EXPORTS):
         getattr(lib, f).restype = ctypes.c_int
     for f in ('gns_profile_enable', 'gns_profile_read', 'gns_param_count', 'gns_config_supported', 'gns_topology_bytes', 'gns_prepare_topology',
               'gns_workspace_bytes', 'gns_forward', 'gns_backward', 'gns_backward_inputs', 'gns_profile_enable', 'gns_profile_read',
@@ -228,6 +231,8 @@ PFS_EXPORTS = ('gns_pfs_workspace_bytes', 'gns_pfs_evaluate', 'gns_pfs_adjoint_w
 DCOPF_EXPORTS = ('gns_dcopf_lds_bytes', 'gns_dcopf_workspace_bytes', 'gns_dcopf_solve')
 # the gradients of the DC optimal power flow (include/gns_powerflow.h, "DC optimal power flow: adjoint")
 DCOPF_GRAD_EXPORTS = ('gns_dcopf_adjoint_lds_bytes', 'gns_dcopf_adjoint_workspace_bytes', 'gns_dcopf_adjoint')
+# the security-constrained DC optimal power flow (include/gns_powerflow.h, "Security-constrained DC optimal power flow")
+DCSCOPF_EXPORTS = ('gns_dcscopf_lds_bytes', 'gns_dcscopf_workspace_bytes', 'gns_dcscopf_solve')
 # the limits of include/gns_powerflow.h
 PF_LDS_MAX_BYTES = 163840
 PF_MAX_SLOTS = 65535

@@ -64,6 +64,11 @@ primal-dual interior point per grid on the problem reduced to the dispatch by ge
 the locational marginal prices and the multipliers.  ``dc_optimal_power_flow_differentiable(...)`` is the same call with a backward
 (``gns_dcopf_adjoint``, ``csrc/gns_dcopf_adjoint.hip``): the implicit-function theorem on the KKT conditions of the active set, one
 dense LU in LDS and three solves on the base factor per grid.
+
+``dc_security_constrained_opf(...)`` is that problem with contingency rows ``(l, k)``: line ``l``'s flow after the outage of line ``k``
+stays within its contingency rating (``csrc/gns_dcscopf.hip``: the screen's line-outage factor per row, then the same interior point
+with the rows behind the lines').  ``dc_secure_dispatch(...)`` is the constraint-generation driver around it and
+``dc_contingency_screen``: the cheapest dispatch that survives every single-line outage.
 """
 from __future__ import annotations
 
@@ -86,6 +91,8 @@ DcPowerFlowResult = namedtuple('DcPowerFlowResult', ['v', 'theta', 'line_flow', 
 
 DcOpfResult = namedtuple('DcOpfResult', ['pg', 'theta', 'line_flow', 'lmp', 'mu_line', 'mu_pmax', 'mu_pmin', 'objective', 'converged',
                                          'iterations'])
+DcScopfResult = namedtuple('DcScopfResult', DcOpfResult._fields + ('mu_row', 'row_flow'))
+DcSecureDispatch = namedtuple('DcSecureDispatch', ['result', 'rows', 'worst_loading', 'secure'])
 
 DcContingencyResult = namedtuple('DcContingencyResult', ['base', 'outages', 'line_flow', 'worst_loading', 'worst_line', 'islanding',
                                                          'converged'])
@@ -916,6 +923,221 @@ def dc_optimal_power_flow_differentiable(buses, lines, generators, B=None, L=Non
     Out of scope: gradients with respect to ``lines``, second derivatives, mixed topologies.
     Contract: ``include/gns_powerflow.h``, "DC optimal power flow: adjoint"."""
     return _dc_opf(buses, lines, generators, B, L, G, cost, rating, slack_bus, tol, max_iter, True)
+
+
+_DCSCOPF_LDS_FORMULA = ("max(8 * (nnz_lu_p + dim_p + N + 3 E + dim_p (W + 1)) + 32 Gn, 8 * (Gn (Gn + 1) / 2 + 14 Gn + 10 E + 10 R + "
+                        "ceil(E / 2))) bytes per workgroup: the DC optimal power flow's images with ten doubles per row slot and a flag "
+                        "per line behind the iterate")
+
+
+def _dcscopf_rows(rows, Bt, E, single):
+    """The row list as an int tensor ``[R,2]`` or ``[Bt,R,2]`` of ``(l, k)``: the dtype and the shape, which need no device and no
+    topology.  The rows themselves are ``_dcscopf_check_rows``'s."""
+    if rows is None:
+        raise ValueError('rows is required: int [R,2] or [Bt,R,2] of (monitored line, outaged line), (-1, -1) an empty slot')
+    r = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows))
+    if r.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'rows must hold integers (0-based (monitored line, outaged line) pairs), got dtype {r.dtype}')
+    if single and r.dim() == 3 and r.shape[0] == 1:
+        r = r[0]
+    if r.dim() not in (2, 3) or r.shape[-1] != 2 or r.shape[-2] < 1 or (r.dim() == 3 and r.shape[0] != Bt):
+        raise ValueError(f'rows must be [R,2] or [{Bt},R,2] with R >= 1, got {tuple(r.shape)}')
+    return r
+
+
+def _dcscopf_check_rows(r, E, bridges):
+    """A row list on the CPU (``_dcscopf_rows``' tensor) against the topology, in one pass: every row that is not ``(-1, -1)`` lies in
+    range, has ``l != k`` and does not outage a bridge (``bridges``: bool ``[E]``).  The first row that does not is named.  A tensor
+    on a device is not looked at: the kernel's rule applies, a bad row fails its grid."""
+    if r.device.type != 'cpu':
+        return
+    a = r.numpy().reshape(-1, 2)
+    l, k = a[:, 0], a[:, 1]
+    in_range = (l >= 0) & (l < E) & (k >= 0) & (k < E)
+    bridge = np.zeros(a.shape[0], dtype=bool)
+    bridge[in_range] = np.asarray(bridges, dtype=bool)[k[in_range]]
+    bad = np.flatnonzero(((l != -1) | (k != -1)) & (~in_range | (l == k) | bridge))
+    if bad.size == 0:
+        return
+    i = int(bad[0])
+    where = f'rows{[i] if r.dim() == 2 else [i // r.shape[1], i % r.shape[1]]} = ({int(l[i])}, {int(k[i])})'
+    if not in_range[i]:
+        raise ValueError(f'{where}: both must lie in 0..{E - 1} (0-based line indices; (-1, -1) is an empty slot)')
+    if l[i] == k[i]:
+        raise ValueError(f'{where}: the monitored line is the outaged line')
+    raise ValueError(f'{where}: the outage of line {int(k[i])} disconnects the grid (it is a bridge of the topology)')
+
+
+def dc_security_constrained_opf(buses, lines, generators, B=None, L=None, G=None, *, cost, rows, rating=None, contingency_rating=None,
+                                slack_bus=None, tol=1e-8, max_iter=150):
+    """``dc_optimal_power_flow`` with contingency rows: the cheapest dispatch within the units' bounds, the lines' ratings and, for
+    every listed row ``(l, k)``, the limit on line ``l``'s flow after the outage of line ``k``, on the device.
+
+    Inputs, ``cost``, ``rating``, ``tol`` and ``max_iter`` are ``dc_optimal_power_flow``'s.  ``rows``: an int tensor or array ``[R,2]``
+    (one list for the batch) or ``[Bt,R,2]`` (a list per grid) of 0-based ``(monitored line, outaged line)``; ``(-1, -1)`` is an empty
+    slot, ``R >= 1``.  A list on the CPU is checked here (range, ``l != k``, ``k`` not a bridge of the topology) and refused with a
+    ``ValueError`` that names the row; a tensor on the device is passed through without a synchronisation, and a bad row then fails
+    its grid alone.  ``contingency_rating``: the post-outage (emergency) rating of the monitored line, float64 ``[E]`` / ``[Bt,E]``,
+    positive, ``+inf``: rows on that line constrain nothing; None: ``rating`` is used.
+
+    Per row ``|F_l + L_r F_k| <= contingency_rating_l`` with ``F`` the base flows and ``L_r = b_l (z_k[f_l] - z_k[t_l]) /
+    (1 - b_k d_k)`` the line-outage factor of ``dc_contingency_screen``: a row is a combination of two rows of the shift-factor
+    matrix, so the interior point still works on a ``Gn x Gn`` matrix.  Method and constants are ``dc_optimal_power_flow``'s; the
+    rows follow the lines' rows (``include/gns_powerflow.h``, "Security-constrained DC optimal power flow").
+
+    Returns ``DcScopfResult``: ``DcOpfResult``'s ten fields, ``mu_row`` ``[Bt,R]`` (the multiplier of a row's upper side minus that of
+    its lower, 0 in an empty slot) and ``row_flow`` ``[Bt,R]`` (the post-outage flow at ``pg``, NaN in an empty slot).  ``lmp`` stays
+    the derivative of the optimal cost with respect to ``Pd``, the rows' congestion included.  With every slot empty the ten fields
+    are ``dc_optimal_power_flow``'s bit for bit.  A grid is not solved (``iterations`` -1, NaN outputs) under
+    ``dc_optimal_power_flow``'s rules or when a row of a device list is out of range, has ``l == k``, outages a bridge, or has a
+    zero or non-finite denominator; the other grids are unaffected, and a grid's result is bit-identical alone, in any batch, with
+    ``rows`` and the ratings shared or per grid, and from run to run.  Gradients, mixed topologies, generator outages as
+    constraints and corrective re-dispatch are out of scope."""
+    _check_iteration(tol, max_iter)
+    with torch.no_grad():
+        single, shaped, shaped_lines, shaped_gens = _as_batch(buses, lines, generators, B, L, G)
+        Bt, E, Gn = shaped.shape[0], shaped_lines.shape[1], shaped_gens.shape[1]
+        if Gn == 0:
+            raise ValueError('dc_security_constrained_opf needs at least one generator')
+        # the shapes first, so that a bad cost, rating or row list is refused where no device is visible too
+        cost = _dcopf_cost(cost, Bt, Gn, single).detach()
+        rating = _dcopf_rating(rating, Bt, E, single)
+        rating_c = _dcopf_rating(contingency_rating, Bt, E, single)
+        rows = _dcscopf_rows(rows, Bt, E, single)
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None, None,
+                                                                 tol, max_iter, False)
+        lib = load_library()
+        N, dev = buses.shape[1], buses.device
+        cfg = PfConfig(N, E, Gn, int(max_iter), float(tol))
+        key, args = _topology_key(buses, lines, generators, slack_bus, 'dc_security_constrained_opf')
+        topo = _analysed(_FD, key, args, dev)
+        bridges = _topology_bridges(topo, args)
+        _dcscopf_check_rows(rows, E, bridges)
+        rows = rows.to(device=dev, dtype=torch.int32).contiguous()
+        R = rows.shape[-2]
+        if getattr(topo, 'bridges_dev', None) is None:
+            topo.bridges_dev = torch.from_numpy(bridges.astype(np.uint8)).to(dev)
+        cost = cost.to(dev).contiguous()
+        rating, rating_c = (None if t is None else t.detach().to(dev).contiguous() for t in (rating, rating_c))
+
+        def lds():
+            b = ctypes.c_int64()
+            _check(lib.gns_dcscopf_lds_bytes(topo.host.ctypes.data, R, ctypes.byref(b), None), 'gns_dcscopf_lds_bytes')
+            return b.value
+
+        f64 = dict(dtype=torch.float64, device=dev)
+        pg, mu_pmax, mu_pmin = (torch.empty(Bt, Gn, **f64) for _ in range(3))
+        theta, lmp = (torch.empty(Bt, N, **f64) for _ in range(2))
+        flow, mu_line = (torch.empty(Bt, E, **f64) for _ in range(2))
+        mu_row, row_flow = (torch.empty(Bt, R, **f64) for _ in range(2))
+        objective = torch.empty(Bt, **f64)
+        conv, iters = torch.empty(Bt, dtype=torch.uint8, device=dev), torch.empty(Bt, dtype=torch.int32, device=dev)
+        ws = _gns._workspace(_size_query(lib.gns_dcscopf_workspace_bytes, 'gns_dcscopf_workspace_bytes',
+                                         (ctypes.byref(cfg), topo.host.ctypes.data, Bt, R), lds, _DCSCOPF_LDS_FORMULA), dev)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(lib.gns_dcscopf_solve(ctypes.byref(cfg), topo.host.ctypes.data, topo.blob.data_ptr(), buses.data_ptr(),
+                                         lines.data_ptr(), generators.data_ptr(), Bt, cost.data_ptr(), int(cost.dim() == 3),
+                                         _ptr(rating), int(rating is not None and rating.dim() == 2), rows.data_ptr(),
+                                         int(rows.dim() == 3), R, _ptr(rating_c), int(rating_c is not None and rating_c.dim() == 2),
+                                         topo.bridges_dev.data_ptr(),
+                                         *map(_ptr, (pg, theta, flow, lmp, mu_line, mu_pmax, mu_pmin, objective, conv, iters, mu_row,
+                                                     row_flow)), ws.data_ptr(), ws.numel(), stream),
+                   'gns_dcscopf_solve', lds, _DCSCOPF_LDS_FORMULA)
+        out = [pg, theta, flow, lmp, mu_line, mu_pmax, mu_pmin, objective, conv.bool(), iters, mu_row, row_flow]
+        if in_dev != dev:
+            out = [t.to(in_dev) for t in out]
+        if single:
+            out = [t[0] for t in out]
+        return DcScopfResult(*out)
+
+
+def dc_secure_dispatch(buses, lines, generators, B=None, L=None, G=None, *, cost, rating=None, contingency_rating=None, outages=None,
+                       rounds=4, rows_per_round=8, violation_tol=1e-5, slack_bus=None, tol=1e-8, max_iter=150):
+    """The cheapest dispatch that survives every single-line outage of ``outages``: constraint generation around
+    ``dc_security_constrained_opf`` and ``dc_contingency_screen`` with static shapes, on the device.
+
+    ``R = rounds * rows_per_round`` row slots per grid start empty.  Each of the ``rounds`` rounds solves with the rows listed so
+    far, writes the dispatch into the generators' ``Pg`` column, screens the outages, forms the loading ``|flow| /
+    contingency_rating`` of every (monitored line, outage) pair (the outaged line itself, islanding outages, lines without a rating
+    and the pairs already listed masked), takes the ``rows_per_round`` worst per grid and writes those above ``1 + violation_tol`` into
+    the round's slots; the others stay ``(-1, -1)``.  A last solve takes all the rows, and a last screen gives ``worst_loading`` ``[Bt]``
+    over all outages and ``secure = worst_loading <= 1 + violation_tol``.  ``outages``: as ``dc_contingency_screen``'s, None: every
+    line that is not a bridge (the bridges are never launched).  ``contingency_rating``: as ``dc_security_constrained_opf``'s (None: ``rating``; one of the two is needed).
+
+    The screen reads the dispatch rounded to float32 (the generator rows are float32), so its loadings carry that rounding:
+    ``violation_tol`` is the caller's overload tolerance and must sit above it (the default 1e-5 does for per-unit flows of order
+    1).  A grid that is secure from the start keeps every slot empty and returns ``dc_optimal_power_flow``'s bits.  A grid that is still
+    insecure after the last round has ``secure`` False: give it more rounds or rows.  The driver's own steps (the
+    write of ``Pg``, the loadings, the masks, ``topk``, the slots) read nothing back to the host; each solve and each screen makes
+    the one synchronisation of its topology lookup (the id columns against the cached analysis), as every call of this module does.
+    Gradients of the secure dispatch are out of scope.
+
+    Returns ``DcSecureDispatch(result, rows, worst_loading, secure)``: the last solve's ``DcScopfResult``, ``rows`` int32 ``[Bt,R,2]``,
+    ``worst_loading`` float64 ``[Bt]`` and ``secure`` bool ``[Bt]``."""
+    for name, v in (('rounds', rounds), ('rows_per_round', rows_per_round)):
+        if not (isinstance(v, (int, np.integer)) and v >= 1):
+            raise ValueError(f'{name} must be a positive integer, got {v!r}')
+    if not float(violation_tol) >= 0.0:
+        raise ValueError(f'violation_tol must be >= 0, got {violation_tol!r}')
+    with torch.no_grad():
+        single, in_dev, buses, lines, generators, _, _ = _inputs(buses.detach(), lines.detach(), generators.detach(), B, L, G, None, None,
+                                                                 tol, max_iter, False)
+        Bt, E, dev = buses.shape[0], lines.shape[1], buses.device
+        rc = _dcopf_rating(contingency_rating if contingency_rating is not None else rating, Bt, E, single)
+        if rc is None:
+            raise ValueError('dc_secure_dispatch needs contingency_rating or rating: without one no outage can overload a line')
+        rc = rc.detach().to(dev).reshape(-1, 1, E)                    # [1 or Bt, 1, E]
+        R = int(rounds) * int(rows_per_round)
+        rows = torch.full((Bt, R, 2), -1, dtype=torch.int32, device=dev)
+        gens = generators.clone()
+        if outages is None:
+            key, args = _topology_key(buses, lines, generators, slack_bus, 'dc_secure_dispatch')
+            outages = np.flatnonzero(~_topology_bridges(_analysed(_FD, key, args, dev), args))
+            if outages.size == 0:
+                raise ValueError('dc_secure_dispatch: every line is a bridge of the topology, no outage can be screened')
+        listed = lines_t = isl = None
+        thr = 1.0 + float(violation_tol)
+
+        def solve():
+            return dc_security_constrained_opf(buses, lines, generators, cost=cost, rows=rows, rating=rating,
+                                               contingency_rating=contingency_rating, slack_bus=slack_bus, tol=tol, max_iter=max_iter)
+
+        def loading(res):
+            """[Bt,K,E]: the loading of every pair at the dispatch of res, -1 where the pair cannot be a row"""
+            nonlocal lines_t, isl
+            gens[..., 6] = res.pg.float()
+            sc = dc_contingency_screen(buses, lines, gens, slack_bus=slack_bus, outages=outages, flows=True)
+            if lines_t is None:
+                lines_t, isl = sc.outages.to(dev), sc.islanding.to(dev)
+                if rows_per_round > lines_t.numel() * E:
+                    raise ValueError(f'rows_per_round {rows_per_round} exceeds the {lines_t.numel() * E} (line, outage) pairs')
+            load = sc.line_flow.abs() / rc
+            own = torch.arange(E, device=dev).reshape(1, 1, E) == lines_t.reshape(1, -1, 1)
+            return torch.where(own | isl.reshape(1, -1, 1) | torch.isinf(rc), load.new_full((), -1.0), load)
+
+        for i in range(int(rounds)):
+            load = loading(solve())
+            if listed is None:
+                listed = torch.zeros(Bt, lines_t.numel() * E, dtype=torch.bool, device=dev)
+            val, idx = torch.topk(torch.where(listed, load.new_full((), -1.0), load.reshape(Bt, -1)), int(rows_per_round), dim=1)
+            above = val > thr
+            pair = torch.stack([idx % E, lines_t[idx // E]], dim=-1).to(torch.int32)
+            rows[:, i * rows_per_round:(i + 1) * rows_per_round] = torch.where(above.unsqueeze(-1), pair, pair.new_full((), -1))
+            listed.scatter_(1, idx, above | listed.gather(1, idx))
+        res = solve()
+        load = loading(res).reshape(Bt, -1)
+        # (a NaN loading, of a grid without a dispatch, is the worst of all)
+        worst = torch.where(torch.isnan(load).any(dim=1), load.new_full((), float('nan')), load.amax(dim=1))
+        secure = worst <= thr
+        out_rows = rows
+        if in_dev != dev:
+            res = DcScopfResult(*(t.to(in_dev) for t in res))
+            out_rows, worst, secure = out_rows.to(in_dev), worst.to(in_dev), secure.to(in_dev)
+        if single:
+            res = DcScopfResult(*(t[0] for t in res))
+            out_rows, worst, secure = out_rows[0], worst[0], secure[0]
+        return DcSecureDispatch(res, out_rows, worst, secure)
 
 
 def _dcn1_lds_bytes(host):

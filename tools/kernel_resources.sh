@@ -3,7 +3,7 @@
 # usage: bash tools/kernel_resources.sh [source ...] > profiles/rNN/kernel_resources.txt     (sources without .hip; default: all)
 cd "$(dirname "$0")/../opf-graph-neural-solver_amd/csrc"
 F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-slp-vectorize -ffp-contract=off -Wno-unused-function"
-FILES="${*:-gns_forward gns_backward gns_backward_split gns_gridwg gns_gridwg_bwd gns_api gns_powerflow gns_fdpf gns_dcpf gns_dcn1 gns_dcn2 gns_dcg1 gns_acn1 gns_acn2 gns_acg1 gns_pfs gns_dcopf gns_dcopf_adjoint}"
+FILES="${*:-gns_forward gns_backward gns_backward_split gns_gridwg gns_gridwg_bwd gns_api gns_powerflow gns_fdpf gns_dcpf gns_dcn1 gns_dcn2 gns_dcg1 gns_acn1 gns_acn2 gns_acg1 gns_pfs gns_dcopf gns_dcopf_adjoint gns_dcscopf}"
 echo "# hipcc -Rpass-analysis=kernel-resource-usage, gfx950, shipped sources (per instantiation)"
 for f in $FILES; do
   [ -n "$KR_REUSE" ] || hipcc $F -Rpass-analysis=kernel-resource-usage -c $f.hip -o /tmp/kr_$f.o 2> /tmp/kr_$f.txt &

@@ -67,8 +67,9 @@ def _live(rows, rating_c):
 def solve(buses, lines, gens, cost, rating, slack_bus, rows, rating_c, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, best=False):
     """The contract's iteration on one grid with the rows ``[R,2]`` (empty slots (-1, -1) and rows on a line without a contingency
     rating skipped).  A dict: pg, mu_line, mu_row [R] (0 in a skipped slot), row_flow [R] (NaN there), mu_pmax, mu_pmin, lam, lmp,
-    objective, line_flow, iterations, converged, worst (the largest figure at the returned iterate).  ``best``: as
-    ``dc_opf_reference.solve``."""
+    objective, line_flow, iterations, converged, worst (the largest figure at the returned iterate), figures (the largest figure at
+    every termination test of the run, in order: ``iterations + 1`` of them, so that a near tie can be judged over the whole run).
+    ``best``: as ``dc_opf_reference.solve``."""
     with np.errstate(all='ignore'):
         buses, lines, gens = (np.asarray(x, dtype=np.float64) for x in (buses, lines, gens))
         rows = np.asarray(rows, dtype=int).reshape(-1, 2)
@@ -88,7 +89,7 @@ def solve(buses, lines, gens, cost, rating, slack_bus, rows, rating_c, tol=DEFAU
         z = np.where(-h > 1.0, -h, 1.0)
         gamma, lam = 1.0, 0.0
         mu = gamma / z
-        it, converged, kept = 0, False, None
+        it, converged, kept, figures = 0, False, None, []
         while True:
             g = p.sum() - m['demand']
             h = A @ p - ub
@@ -97,6 +98,7 @@ def solve(buses, lines, gens, cost, rating, slack_bus, rows, rating_c, tol=DEFAU
             fig = (max(abs(g), h.max()) / (1.0 + max(pinf, np.abs(z).max())), np.abs(Lx).max() / (1.0 + max(abs(lam), np.abs(mu).max())),
                    (z @ mu) / (1.0 + pinf))
             worst = max(fig)
+            figures.append(float(worst))
             if worst == worst and (kept is None or worst < kept[0]):
                 kept = (worst, p, z, lam, mu, it)
             if all(f < tol for f in fig):
@@ -134,7 +136,7 @@ def solve(buses, lines, gens, cost, rating, slack_bus, rows, rating_c, tol=DEFAU
         b = 2 * nl + 2 * nr
         return dict(pg=p.copy(), mu_line=mu_line, mu_row=mu_row, row_flow=row_flow, mu_pmax=mu[b:b + Gn].copy(), mu_pmin=mu[b + Gn:].copy(),
                     lam=float(lam), lmp=-lam - m['ptdf'].T @ mu_line - pr.T @ mr, objective=float(m['c2'] @ p ** 2 + m['c1'] @ p),
-                    line_flow=m['f0'] + m['S'] @ p, iterations=it, converged=converged, worst=worst)
+                    line_flow=m['f0'] + m['S'] @ p, iterations=it, converged=converged, worst=worst, figures=figures)
 
 
 def m_rating(rating, E):
@@ -155,10 +157,12 @@ def row_values(buses, lines, gens, slack_bus, rows, pg):
     return val, S
 
 
-def solve_full(buses, lines, gens, cost, rating, slack_bus, rows, rating_c, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER):
+def solve_full(buses, lines, gens, cost, rating, slack_bus, rows, rating_c, tol=DEFAULT_TOL, max_iter=DEFAULT_MAX_ITER, path=None):
     """The same problem with one angle vector per network: x = (theta_r of the base, theta_r of each distinct outage, p), the bus
     balances of every network as equalities.  A dict of pg, objective, lmp (minus the balance multipliers summed over the
-    networks), mu_row [R], converged, iterations."""
+    networks), mu_row [R], mu_line [E], mu_pmax, mu_pmin (the slices of mu that ``solve`` takes them from), converged, iterations.
+    ``path``: a list that takes the same dict at every termination test, so that one run gives the iterate after 0, 1, 2, ... updates
+    (what ``max_iter = k`` returns)."""
     with np.errstate(all='ignore'):
         buses, lines, gens = (np.asarray(x, dtype=np.float64) for x in (buses, lines, gens))
         rows = np.asarray(rows, dtype=int).reshape(-1, 2)
@@ -210,7 +214,21 @@ def solve_full(buses, lines, gens, cost, rating, slack_bus, rows, rating_c, tol=
         mu = gamma / z
         converged, it = False, 0
         pp = np.arange(nn * nth, n)
+
+        def result():
+            pg = x[nn * nth:].copy()
+            mu_row, mu_line = np.zeros(rows.shape[0]), np.zeros(E)
+            mu_row[live] = mu[2 * nl:2 * nl + nr] - mu[2 * nl + nr:2 * nl + 2 * nr]
+            mu_line[base['lim']] = mu[:nl] - mu[nl:2 * nl]
+            lmp = -lam[:N].copy()
+            lmp[r] -= lam[N:].reshape(nn - 1, nth).sum(axis=0)
+            b = 2 * nl + 2 * nr
+            return dict(pg=pg, objective=float(base['c2'] @ pg ** 2 + base['c1'] @ pg), lmp=lmp, mu_row=mu_row, mu_line=mu_line,
+                        mu_pmax=mu[b:b + Gn].copy(), mu_pmin=mu[b + Gn:].copy(), converged=converged, iterations=it)
+
         while True:
+            if path is not None:
+                path.append(result())
             g = G @ x - load
             h = A @ x - ub
             Lx = H * x + c + G.T @ lam + A.T @ mu
@@ -241,13 +259,7 @@ def solve_full(buses, lines, gens, cost, rating, slack_bus, rows, rating_c, tol=
             x, z, lam, mu = x + ap * dx, z + ap * dz, lam + ad * dlam, mu + ad * dmu
             gamma = SIGMA * (z @ mu) / z.size
             it += 1
-        pg = x[nn * nth:]
-        mu_row = np.zeros(rows.shape[0])
-        mu_row[live] = mu[2 * nl:2 * nl + nr] - mu[2 * nl + nr:2 * nl + 2 * nr]
-        lmp = -lam[:N].copy()
-        lmp[r] -= lam[N:].reshape(nn - 1, nth).sum(axis=0)
-        return dict(pg=pg, objective=float(base['c2'] @ pg ** 2 + base['c1'] @ pg), lmp=lmp, mu_row=mu_row,
-                    converged=converged, iterations=it)
+        return result()
 
 
 def all_rows(E, outages):

@@ -134,7 +134,11 @@ def kept_grids(name):
 
 
 def set_weights(name, only=None, seed=20):
-    """The seeded random weighting of every grid of a set (``only``: of that output alone), a list of dicts."""
+    """The seeded random weighting of every grid of a set (``only``: of that output alone), a list of dicts.  A set of
+    ``dc_opf_cases.SETS`` draws from its place among them; any other name from a place of its own past ``len(SETS)``, the CRC-32 of
+    the name, so that no set registered later moves it."""
+    import zlib
     import dc_opf_cases as cases
     names = sorted(cases.SETS)
-    return [random_weights(p, np.random.default_rng([seed, names.index(name), g]), only) for g, p in enumerate(cases.problems(name))]
+    place = names.index(name) if name in cases.SETS else len(names) + zlib.crc32(name.encode())
+    return [random_weights(p, np.random.default_rng([seed, place, g]), only) for g, p in enumerate(cases.problems(name))]
